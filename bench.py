@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/sec of the batched T-rex physics step (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu E]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu E] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work for N > 1: without a launcher the parent process - before it touches torch.cuda or the HIP library -
@@ -22,9 +22,17 @@ flailing on the ground. `state_mix` in the JSON line holds the contact-count his
 
 The JSON line carries `roofline` (algorithmic 912 B/env-step over the kernel's hipEvent-timed
 duration vs the 8 TB/s HBM peak; the kernel is latency/VALU bound so the fraction is tiny - see
-DESIGN.md), `roofline_issue` (VALU instructions per launch, from the committed SQ counters of the
-SAME kernel build, over the live launch duration vs the chip's VALU issue peak) and, at N=1,
-`cpu_baseline`: the f64 CPU oracle (a port; pybullet is absent) timed on the host cores.
+DESIGN.md) and `roofline_issue` (VALU instructions per launch, from the committed SQ counters of the
+SAME kernel build, over the live launch duration vs the chip's VALU issue peak), both from the timed window itself.
+
+A plain run sets up, pre-rolls, warms up, times the --steps steps and prints the line. What takes runs of its own is
+behind --full: at N=1 `cpu_baseline` (the f64 CPU oracle - a port; pybullet is absent - timed on the host cores before
+the GPU is initialised), for N>1 `gather` (the no-exchange and blocking forms, timed after the window).
+
+--dump-outputs DIR writes what the last timed step returned to its caller - obs [n, 3J], reward [n] and done [n] (as
+0 / 1) of this process's envs - as DIR/obs.npy, DIR/reward.npy, DIR/done.npy in float32 (at most 64 MB in all: a
+fixed, seeded sample of the env rows beyond that). The inputs are seeded, so two builds run with the same arguments
+can be compared output for output.
 """
 import argparse
 import json
@@ -247,6 +255,55 @@ def _self_launch(n, argv):
     sys.exit(rc)
 
 
+def action_pool(ids, n_draws, low, high, device, seed=0):
+    """[n_draws, n, J] f32: row t = sharding.synthetic_actions(ids, t, low, high, seed) - the same counter hash and the same
+    float operations in the same order, so bitwise the same values - computed for a chunk of steps at a time (one call per
+    step made the set-up of a long run grow by ~20 launches per timed step)."""
+    import torch
+    ids = torch.as_tensor(ids, dtype=torch.int64, device=device).reshape(1, -1, 1)
+    low = torch.as_tensor(low, dtype=torch.float32, device=device).reshape(1, 1, -1)
+    high = torch.as_tensor(high, dtype=torch.float32, device=device).reshape(1, 1, -1)
+    J = low.shape[2]
+    j = torch.arange(J, dtype=torch.int64, device=device).reshape(1, 1, -1)
+    pool = torch.empty(n_draws, ids.shape[1], J, device=device)
+    m = (1 << 31) - 1
+    chunk = max(1, (1 << 24) // max(1, ids.shape[1] * J))
+    for t0 in range(0, n_draws, chunk):
+        t = torch.arange(t0, min(n_draws, t0 + chunk), dtype=torch.int64, device=device).reshape(-1, 1, 1)
+        x = (ids * 1000003 + t) * 1000033 + j * 7919 + int(seed) * 104729 + 12345
+        x = x & m
+        for mul, sh in ((1103515245, 15), (214013, 13), (69069, 16)):
+            x = (x * mul + 12345) & m
+            x = x ^ (x >> sh)
+        u = (x & ((1 << 24) - 1)).to(torch.float32) / float(1 << 24)
+        pool[t0:t0 + t.shape[0]] = low + (high - low) * u
+    return pool
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, env, rows=None):
+    """obs / reward / done that the last timed step handed its caller -> out_dir/<name>.npy, float32. rows: the [n, 3J+2]
+    block of a step_many launch (the env's own views are not written by it). Over DUMP_BYTES_MAX in all, a fixed sample
+    of the env rows (seed 0, sorted) is written instead."""
+    import numpy as np
+    J = env.J
+    if rows is None:
+        obs, rew, done = env.obs, env.rew, env.done
+    else:
+        obs, rew, done = rows[:, :3 * J], rows[:, 3 * J], rows[:, 3 * J + 1] != 0
+    out = {"obs": obs.float().cpu().numpy(), "reward": rew.float().cpu().numpy(), "done": done.float().cpu().numpy()}
+    n = out["obs"].shape[0]
+    row_bytes = sum(a[0].nbytes if a.ndim > 1 else a.itemsize for a in out.values())
+    if n * row_bytes > DUMP_BYTES_MAX:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES_MAX // row_bytes, replace=False))
+        out = {k: a[keep] for k, a in out.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def _load_json(name):
     p = os.path.join(ROOT, "profiles", name)
     return json.load(open(p)) if os.path.exists(p) else None
@@ -287,7 +344,12 @@ def main():
     ap.add_argument("--steps-per-launch", type=int, default=1,
                     help="S > 1 (NOT the headline; one GPU): trex_batch_step_many, S env-steps of every env per launch - what an "
                          "open-loop action sequence allows: no wave waits for the slowest wave of a step. --steps must be a multiple of S")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline (N=1) and the no-exchange / blocking "
+                         "exchange forms (N>1); a plain run times the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write obs / reward / done of the last timed step as DIR/<name>.npy (float32, at most 64 MB)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU (tests/test_bench_launcher.py): the ranks rendezvous over gloo, gather one "
                          "row block of CPU tensors through trex_gym.sharding and rank 0 prints a JSON line marked dry_run; nothing is timed")
@@ -333,7 +395,7 @@ def main():
 
     _protect_stdout()
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()  # before the GPU is initialised (spawned workers never touch HIP)
 
     import torch
@@ -382,11 +444,9 @@ def main():
     mid, half = 0.5 * (lo + hi), 0.5 * (hi - lo) * args.action_scale
     # a[n, j] ~ U(low_j, high_j), keyed by (seed 0, GLOBAL env id, step), a fresh draw for every step
     # of the run, pre-generated on the device: [T, n, 25] f32 (553 MB at T = 1350, n = 4096)
-    n_blocking = 2 * (max(10, min(args.steps, 50)) + 5) if world > 1 else 0     # the two other exchange modes, timed after the window
+    n_blocking = 2 * (max(10, min(args.steps, 50)) + 5) if (world > 1 and args.full) else 0     # the two other exchange modes, timed after the window
     n_draws = args.action_cycle if args.action_cycle > 0 else args.preroll + args.warmup + args.steps + n_blocking
-    pool = torch.empty(n_draws, n_local, len(lo), device=dev)
-    for t in range(n_draws):
-        pool[t] = sharding.synthetic_actions(ids, t, mid - half, mid + half, seed=0, device=dev)
+    pool = action_pool(ids, n_draws, mid - half, mid + half, dev)
     if args.action_scale != 1.0:
         overrides = dict(overrides, action_scale=args.action_scale)
     stride = EVENT_STRIDE if args.steps >= EVENT_STRIDE else 1
@@ -497,6 +557,8 @@ def main():
     run(args.steps, t_base + args.warmup, timed=True)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, env, many_rows[-1] if S > 1 else None)
     env.batch.contact_stats(cnt_end, None)
     hist0, hist1 = ([int(x) for x in contact_hist(c).tolist()[:14]] for c in (cnt_start, cnt_end))
     if world > 1:
@@ -504,7 +566,7 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
     blocking_ms = no_exchange_ms = None
-    if world > 1:   # the two other forms, measured in the SAME process right after the timed region (not `value`): no
+    if world > 1 and args.full:   # the two other forms, measured in the SAME process right after the timed region (not `value`): no
         #             exchange at all (replica mode: what the step kernel alone scales like) and the blocking exchange.
         #             AFTER the window: their fences and read-backs would slow the launches that follow them
         nb = max(10, min(args.steps, 50))

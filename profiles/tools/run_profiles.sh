@@ -7,8 +7,8 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof
 rm -rf $OUT gpurun_out/pmc && mkdir -p $OUT
-python bench.py --steps 300 --warmup 30 > $OUT/bench_300.json 2> $OUT/bench_300.err
-python bench.py --steps 20 --warmup 5 > $OUT/bench_20.json 2> $OUT/bench_20.err      # the driver's call, CPU baseline included
+python bench.py --full --steps 300 --warmup 30 > $OUT/bench_300.json 2> $OUT/bench_300.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_20.json 2> $OUT/bench_20.err      # the headline call, CPU baseline included
 python bench.py --steps 300 --warmup 30 --no-cpu-baseline --action-cycle 16 > $OUT/bench_300_cycle16.json 2> $OUT/bench_300_cycle16.err   # rounds 1-2's input (NOT the headline)
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --action-cycle 16 > $OUT/bench_20_cycle16.json 2> $OUT/bench_20_cycle16.err
 python bench.py --steps 200 --warmup 30 --no-cpu-baseline --envs-per-gpu 256 > $OUT/bench_256.json 2> $OUT/bench_256.err   # one wave per four SIMDs: the serial floor of a launch
@@ -37,8 +37,8 @@ python scripts/soak.py 20000 2>&1 | grep -v amdgpu.ids > $OUT/soak.txt || echo "
 python scripts/refresh_profiles.py ${1:-r03} $OUT/final
 # the two headline lines once more, now that the traffic of THIS build is known (bench.py reads profiles/pmc_traffic.json)
 cp $OUT/final/pmc_traffic.json $OUT/final/sq_counters.json profiles/
-python bench.py --steps 300 --warmup 30 > $OUT/bench_300.json 2> $OUT/bench_300.err
-python bench.py --steps 20 --warmup 5 > $OUT/bench_20.json 2> $OUT/bench_20.err
+python bench.py --full --steps 300 --warmup 30 > $OUT/bench_300.json 2> $OUT/bench_300.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_20.json 2> $OUT/bench_20.err
 python scripts/refresh_profiles.py ${1:-r03} $OUT/final
 rm -rf $OUT/trace $OUT/sq $OUT/sq2 gpurun_out/pmc
 ls $OUT/final

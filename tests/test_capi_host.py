@@ -8,7 +8,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import ASSET_URDF, REFERENCE_ROOT, ROOT
+from conftest import ASSET_URDF, ROOT
 
 
 @pytest.fixture(scope="module")
@@ -46,11 +46,10 @@ def test_model_matches_oracle_model(capi, model):
     assert [n for n, _ in m.links()] == model["link_names"] and len(m.links()) == 133
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_ROOT), reason="reference only in the authoring container")
-def test_reference_urdf_with_dae_hulls_gives_same_model(capi):
+def test_reference_urdf_with_dae_hulls_gives_same_model(capi, reference_assets):
     a = capi.Model(ASSET_URDF)
-    b = capi.Model(os.path.join(REFERENCE_ROOT, "assets", "trex.urdf"),
-                   os.path.join(REFERENCE_ROOT, "assets", "collisions"))
+    b = capi.Model(os.path.join(reference_assets, "trex.urdf"),
+                   os.path.join(reference_assets, "collisions"))
     for name in ["parent", "joint_pos", "joint_rot", "mass", "com", "inertia", "sphere_radius"]:
         np.testing.assert_array_equal(a.array(name), b.array(name), err_msg=name)
     # hull vertices went through a decimal text round trip (%.9g): equal to f32 precision

@@ -11,7 +11,7 @@ import subprocess
 
 import pytest
 
-from conftest import ASSET_URDF, REFERENCE_ROOT, ROOT
+from conftest import ASSET_URDF, ROOT
 
 CSRC = os.path.join(ROOT, "trex-gym_amd", "csrc")
 CORPUS = os.path.join(ROOT, "tests", "golden", "malformed_urdf")
@@ -83,10 +83,9 @@ def test_valid_models_under_asan_ubsan(harness, tmp_path):
     assert rows[1][1] == "0" and rows[1][2].startswith("2 bodies")
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_ROOT), reason="reference only in the authoring container")
-def test_reference_urdf_and_dae_hulls_under_asan_ubsan(harness):
-    rc, rows, err = _run(harness, ["--dae", os.path.join(REFERENCE_ROOT, "assets", "collisions"),
-                                   os.path.join(REFERENCE_ROOT, "assets", "trex.urdf")])
+def test_reference_urdf_and_dae_hulls_under_asan_ubsan(harness, reference_assets):
+    rc, rows, err = _run(harness, ["--dae", os.path.join(reference_assets, "collisions"),
+                                   os.path.join(reference_assets, "trex.urdf")])
     assert rc == 0 and rows[0][2].startswith("26 bodies, 2181 hull points"), (rows, err[-2000:])
 
 

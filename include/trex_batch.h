@@ -91,7 +91,22 @@ int trex_model_fit_hull_primitives(const TrexModel *model, int group, double max
  * "max_coordinate_velocity" "max_contacts"  (setTimeStep / setPhysicsEngineParameter / setGravity,
  * trex_env.py:115-117; motor gains trex_robot.py:260,401,421). "max_contacts" is the contact-point budget
  * per env: default and upper limit 13 (25 motor rows + 3 x 13 contact rows = the 64 lanes of a wavefront;
- * larger values are clamped by the kernel). */
+ * larger values are clamped by the kernel).
+ * "warmstart" (default 0 = off; values outside [0, 1] are refused with TREX_E_INVALID): PGS warm start of the contact rows,
+ * Bullet's warmstartingFactor. Read when a batch is created, like every parameter. With warmstart > 0:
+ *   - a contact point is identified by its hull vertex (its index into the model's collision points, unique across bodies;
+ *     primitive collision keeps its sphere centres and capsule ends in the same array);
+ *   - every env keeps a record of the points its last solve used (at most 13): vertex and final normal / friction-x /
+ *     friction-y impulses, unscaled. A point found in the record starts the next solve at warmstart x those impulses on
+ *     its three rows (the friction pyramid uses world axes, so the rows mean the same from one solve to the next); every
+ *     other row - new points, motor rows, joint-limit rows - starts at 0, as with warmstart 0;
+ *   - every solve (every substep, the settle substep of a reset included) overwrites the record with its own points;
+ *   - the record is emptied for the envs that trex_batch_reset / trex_batch_reset_rows reset (before their settle substep;
+ *     the others keep theirs), for an env the step launch resets (episode limit, non-finite containment), and for every
+ *     env by trex_batch_set_state;
+ *   - it persists across launches (step, step_rows, step_many, time_steps) in a per-env device array of 256 B per env,
+ *     allocated at batch creation; trex_batch_debug_step is refused (TREX_E_INVALID): its diagnostics kernel has no record.
+ * With warmstart 0 nothing of this exists: the same kernels, rows and memory as without the parameter. */
 int trex_model_set_param(TrexModel *model, const char *name, double value);
 int trex_model_get_param(const TrexModel *model, const char *name, double *value);
 

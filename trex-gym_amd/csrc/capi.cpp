@@ -16,11 +16,11 @@
 
 extern "C" {
 hipError_t trex_launch_step(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, float *, uint8_t *,
-                            float *, float, float, float, float *, hipStream_t, float *, int, int, int, int);
+                            float *, float, float, float, float *, hipStream_t, float *, int, int, int, int, float *);
 hipError_t trex_launch_reset(const TrexDeviceModel *, TrexBatchArrays, int, const uint8_t *, float *, float, float,
-                             float, float *, hipStream_t, int, float *, float *, int, int, int);
+                             float, float *, hipStream_t, int, float *, float *, int, int, int, float *);
 hipError_t trex_launch_step_many(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, int, int, float *, uint8_t *,
-                                 float, float, float, hipStream_t, int, int, int);
+                                 float, float, float, hipStream_t, int, int, int, float *);
 hipError_t trex_launch_pack_state(const TrexDeviceModel *, TrexBatchArrays, int, float *, int, hipStream_t);
 hipError_t trex_launch_head(const TrexDeviceModel *, TrexBatchArrays, int, float *, hipStream_t);
 hipError_t trex_launch_link_transforms(const TrexDeviceModel *, TrexBatchArrays, int, float *, hipStream_t, int);
@@ -31,6 +31,7 @@ hipError_t trex_launch_fill_u8(uint8_t *, uint8_t, int, hipStream_t);
 hipError_t trex_launch_copy_mass_scale(const float *, float *, int, int, hipStream_t);
 int trex_step_lds_bytes(int);
 int trex_step_envs_per_workgroup(int);
+int trex_step_warm_lds_bytes(void);
 }
 
 struct TrexModel {
@@ -41,6 +42,7 @@ struct TrexBatch {
   int n = 0, device = 0, nb = 0, nj = 0;
   TrexDeviceModel *dmodel = nullptr;
   TrexBatchArrays arr{};
+  float *warm = nullptr;                       // PGS warm-start records [n][TREX_WARM_WORDS] (device_model.h); warmstart > 0 only
   float wd = 1.0f, we = 0.005f, wk = 0.002f;  // trex_env.py:42-44
   bool pen_in_rows = false;                    // trex_batch_set_penalties_in_rows
   int balance_mode = -1;                       // trex_batch_set_wave_balance: -1 auto, 0 off, 1 on
@@ -78,7 +80,7 @@ void fill_device_model(const trex::HostModel &h, TrexDeviceModel &d) {
   const trex::Params &p = h.prm;
   const double prm[TP_COUNT] = {p.dt, p.substeps, p.iterations, p.gravity, p.motor_kp, p.motor_kd, p.motor_max_force,
                                 p.floor_z, p.friction, p.erp, p.contact_erp, p.contact_margin, p.link_damping,
-                                p.max_coordinate_velocity, p.max_contacts};
+                                p.max_coordinate_velocity, p.max_contacts, p.warmstart};
   for (int i = 0; i < TP_COUNT; i++) d.prm[i] = (float)prm[i];
   d.n_substeps = (int)p.substeps; d.n_iterations = (int)p.iterations; d.max_contacts = (int)p.max_contacts;
   d.inv_dt = 1.0f / (float)p.dt;
@@ -333,6 +335,8 @@ int trex_model_set_param(TrexModel *m, const char *name, double value) {
   double *p = m->host.prm.find(name);
   if (!p) return fail(TREX_E_INVALID, std::string("unknown parameter '") + name + "'");
   if (!std::isfinite(value)) return fail(TREX_E_INVALID, "parameter value is not finite");
+  if (std::strcmp(name, "warmstart") == 0 && !(value >= 0.0 && value <= 1.0))
+    return fail(TREX_E_INVALID, "warmstart must lie in [0, 1] (0 = off)");
   *p = value;
   return TREX_OK;
 }
@@ -415,6 +419,8 @@ int trex_batch_create(const TrexModel *model, int num_envs, int device, TrexBatc
   A(n * TREX_TL * sizeof(float), (void **)&b->arr.mass_scale);
   A(n * sizeof(float), (void **)&b->arr.friction);
   A(TREX_BAL_WORDS(n) * sizeof(int32_t), (void **)&b->arr.balance);
+  // the warm-start records exist only for a model with warmstart > 0 (zeroed by alloc: every record empty)
+  if (model->host.prm.warmstart > 0) A(n * TREX_WARM_WORDS * sizeof(float), (void **)&b->warm);
   b->arr.max_episode_steps = 0;
   b->arr.domain = 0;
   size_t nv = model->host.hull_xyz.size();
@@ -514,7 +520,7 @@ int trex_batch_reset(TrexBatch *b, const uint8_t *mask_dev, float *obs_out_dev, 
   BUF_TRY(mask_dev, n, "trex_batch_reset: mask");
   BUF_TRY(obs_out_dev, n * 3 * b->nj * sizeof(float), "trex_batch_reset: obs_out");
   HIP_TRY(trex_launch_reset(b->dmodel, b->arr, b->n, mask_dev, obs_out_dev, b->wd, b->we, b->wk, nullptr,
-                            (hipStream_t)stream, 3 * b->nj, nullptr, nullptr, 1, b->nj, 0));
+                            (hipStream_t)stream, 3 * b->nj, nullptr, nullptr, 1, b->nj, 0, b->warm));
   return TREX_OK;
 }
 
@@ -528,7 +534,7 @@ int trex_batch_reset_rows(TrexBatch *b, const uint8_t *mask_dev, float *rows_dev
   BUF_TRY(rows_dev, ((n - 1) * row_stride + 3 * b->nj + (b->pen_in_rows ? 5 : 2)) * sizeof(float), "trex_batch_reset_rows: rows");
   HIP_TRY(trex_launch_reset(b->dmodel, b->arr, b->n, mask_dev, rows_dev, b->wd, b->we, b->wk, nullptr,
                             (hipStream_t)stream, row_stride, rows_dev + 3 * b->nj, rows_dev + 3 * b->nj + 1, row_stride, b->nj,
-                            b->pen_in_rows ? 1 : 0));
+                            b->pen_in_rows ? 1 : 0, b->warm));
   return TREX_OK;
 }
 
@@ -544,7 +550,7 @@ int trex_batch_step(TrexBatch *b, const float *actions_dev, float *obs_dev, floa
   BUF_TRY(done_dev, n, "trex_batch_step: done");
   BUF_TRY(penalties_dev, n * 3 * sizeof(float), "trex_batch_step: penalties");
   HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, reward_dev, done_dev, penalties_dev, b->wd,
-                           b->we, b->wk, nullptr, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0));
+                           b->we, b->wk, nullptr, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm));
   return TREX_OK;
 }
 
@@ -561,7 +567,7 @@ int trex_batch_step_rows(TrexBatch *b, const float *actions_dev, float *rows_dev
   BUF_TRY(done_dev, n, "trex_batch_step_rows: done");
   float *rew = rows_dev + 3 * b->nj;
   HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, rows_dev, rew, done_dev, penalties_dev, b->wd, b->we,
-                           b->wk, nullptr, (hipStream_t)stream, rew + 1, row_stride, row_stride, b->balance(), b->pen_in_rows ? 1 : 0));
+                           b->wk, nullptr, (hipStream_t)stream, rew + 1, row_stride, row_stride, b->balance(), b->pen_in_rows ? 1 : 0, b->warm));
   return TREX_OK;
 }
 
@@ -578,7 +584,7 @@ int trex_batch_step_many(TrexBatch *b, const float *actions_dev, float *rows_dev
   BUF_TRY(penalties_dev, S * n * 3 * sizeof(float), "trex_batch_step_many: penalties");
   BUF_TRY(done_dev, S * n, "trex_batch_step_many: done");
   HIP_TRY(trex_launch_step_many(b->dmodel, b->arr, b->n, actions_dev, rows_dev, row_stride, num_steps, penalties_dev, done_dev,
-                                b->wd, b->we, b->wk, (hipStream_t)stream, b->balance(), b->nj, b->pen_in_rows ? 1 : 0));
+                                b->wd, b->we, b->wk, (hipStream_t)stream, b->balance(), b->nj, b->pen_in_rows ? 1 : 0, b->warm));
   return TREX_OK;
 }
 
@@ -589,8 +595,10 @@ int trex_batch_debug_step(TrexBatch *b, const float *actions_dev, float *obs_dev
   BUF_TRY(actions_dev, (size_t)b->n * b->nj * sizeof(float), "trex_batch_debug_step: actions");
   BUF_TRY(obs_dev, (size_t)b->n * 3 * b->nj * sizeof(float), "trex_batch_debug_step: obs");
   BUF_TRY(debug_dev, 4096 * sizeof(float), "trex_batch_debug_step: debug");   // (diagnostic builds: 4096 + 16 N)
+  if (b->warm)   // (the diagnostics instantiation has no warm-start record: it would step cold without saying so)
+    return fail(TREX_E_INVALID, "trex_batch_debug_step: not available for a batch with warmstart > 0");
   HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, nullptr, nullptr, nullptr, b->wd, b->we, b->wk,
-                           debug_dev, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0));
+                           debug_dev, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm));
   return TREX_OK;
 }
 
@@ -626,6 +634,8 @@ int trex_batch_set_state(TrexBatch *b, const float *state_dev, void *stream) {
   DeviceGuard guard(b->device);
   BUF_TRY(state_dev, (size_t)b->n * (13 + 2 * b->nj) * sizeof(float), "trex_batch_set_state: state");
   HIP_TRY(trex_launch_pack_state(b->dmodel, b->arr, b->n, const_cast<float *>(state_dev), 0, (hipStream_t)stream));
+  if (b->warm)   // the recorded impulses belong to the states just replaced: every record is emptied
+    HIP_TRY(hipMemsetAsync(b->warm, 0, (size_t)b->n * TREX_WARM_WORDS * sizeof(float), (hipStream_t)stream));
   return TREX_OK;
 }
 int trex_batch_set_motors_enabled(TrexBatch *b, int enabled, void *stream) {
@@ -708,7 +718,7 @@ int trex_batch_launch_info(const TrexBatch *b, int *grid, int *block, int *lds_b
   const int epw = trex_step_envs_per_workgroup(b->n);
   if (grid) *grid = (b->n + epw - 1) / epw;
   if (block) *block = 64 * epw;       // one wavefront per env
-  if (lds_bytes) *lds_bytes = trex_step_lds_bytes(b->n);
+  if (lds_bytes) *lds_bytes = trex_step_lds_bytes(b->n) + (b->warm ? epw * trex_step_warm_lds_bytes() : 0);
   // state in + out (13 + 2J floats each), action in (J), obs out (3J), reward (4 B), done (padded 4 B): SURVEY 8d
   if (alg_bytes_per_env_step) *alg_bytes_per_env_step = 4 * (2 * (13 + 2 * b->nj) + b->nj + 3 * b->nj + 1 + 1);
   return TREX_OK;
@@ -730,7 +740,7 @@ int trex_batch_time_steps(TrexBatch *b, const float *actions_dev, float *obs_dev
   HIP_TRY(hipEventRecord(e0, s));
   for (int i = 0; i < steps; i++)
     HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, reward_dev, done_dev, nullptr, b->wd, b->we,
-                             b->wk, nullptr, s, nullptr, 3 * b->nj, 1, b->balance(), 0));
+                             b->wk, nullptr, s, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm));
   HIP_TRY(hipEventRecord(e1, s));
   HIP_TRY(hipEventSynchronize(e1));
   float ms = 0.f;

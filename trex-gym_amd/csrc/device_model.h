@@ -11,7 +11,7 @@
 enum TrexParam {
   TP_DT, TP_SUBSTEPS, TP_ITERATIONS, TP_GRAVITY, TP_MOTOR_KP, TP_MOTOR_KD, TP_MOTOR_MAX_FORCE,
   TP_FLOOR_Z, TP_FRICTION, TP_ERP, TP_CONTACT_ERP, TP_CONTACT_MARGIN, TP_LINK_DAMPING,
-  TP_MAX_COORD_VEL, TP_MAX_CONTACTS, TP_COUNT
+  TP_MAX_COORD_VEL, TP_MAX_CONTACTS, TP_WARMSTART, TP_COUNT
 };
 
 /* Model constants, one copy in HBM (about 5 KB + hull vertices), L2-resident for every wave.
@@ -86,3 +86,9 @@ struct TrexBatchArrays {
   const int *visual_body; /* [V] body of each <visual> mesh */
   const float *visual_tf; /* [V][12] body<-mesh transform (link frame in its body x the visual's <origin>) */
 };
+/* PGS warm start (model parameter `warmstart` > 0 at batch creation; else no array and nothing read or written): [N][64] floats
+ * per ENV - never per workgroup: the wave balance moves envs between workgroups - the record of the points the env's last solve
+ * used, lane-aligned with the constraint rows of the step kernel. Word 1 + s (s < TREX_MAXC): the hull vertex of point slot s
+ * PLUS ONE, as an int, 0 = empty slot; the words of the slot's three contact rows (normal, friction x, friction y: the lanes of
+ * the kernel's rows 3 s .. 3 s + 2) its final impulses, unscaled; every other word 0. An all-zero row is an empty record. */
+#define TREX_WARM_WORDS 64

@@ -183,7 +183,8 @@ double *Params::find(const std::string &n) {
       {"motor_max_force", &Params::motor_max_force}, {"floor_z", &Params::floor_z},
       {"friction", &Params::friction}, {"erp", &Params::erp}, {"contact_erp", &Params::contact_erp},
       {"contact_margin", &Params::contact_margin}, {"link_damping", &Params::link_damping},
-      {"max_coordinate_velocity", &Params::max_coordinate_velocity}, {"max_contacts", &Params::max_contacts}};
+      {"max_coordinate_velocity", &Params::max_coordinate_velocity}, {"max_contacts", &Params::max_contacts},
+      {"warmstart", &Params::warmstart}};
   auto it = tab.find(n);
   return it == tab.end() ? nullptr : &(this->*(it->second));
 }

@@ -33,6 +33,7 @@ struct Params {
   double link_damping = 0.04;       // [EXT]
   double max_coordinate_velocity = 100.0;  // [EXT]
   double max_contacts = 13;   // 25 motor rows + 3 x 13 contact rows = one row per lane of a wavefront
+  double warmstart = 0;       // PGS warm start: a contact point starts its solve at this factor x its last solve's impulses; 0 = off
   double *find(const std::string &name);
 };
 

@@ -333,6 +333,13 @@ constexpr int NROW = NJMAX + 3 * MAXC;   // constraint rows of one env: 25 motor
 static_assert(NROW == 64, "one constraint row per lane");
 #define KROW_LANE(k) ((k) < 3 * MAXC - 1 ? NJMAX + 1 + (k) : 0)
 constexpr int CLANE0 = NJMAX + 1;        // contact row k lives on lane CLANE0 + k (k < 38) and on lane 0 (k = 38)
+// WARM: the word of the LDS record (float4 per point slot: key, normal, friction x, friction y) that lane l carries in the env's
+// [64] row in HBM (device_model.h): lanes 1..13 the key of slot l - 1, a contact-row lane its row's impulse, the others none (-1)
+__device__ __forceinline__ int warm_word(int l) {
+  if (l >= 1 && l <= MAXC) return 4 * (l - 1);
+  if (l == 0 || l >= CLANE0) { const int k = l == 0 ? 3 * MAXC - 1 : l - CLANE0; return 4 * (k / 3) + 1 + k % 3; }
+  return -1;
+}
 // Body record, parked after the tree phases and read by the row walks (float4 reads, 80-byte stride:
 // 16 lanes reading 16 different records hit 16 different bank quartets):
 //   q0 = joint axis (world) xyz | 1/D      q1 = origin r (rel. base origin) xyz | updated joint rate
@@ -349,7 +356,7 @@ struct WaveLds {
     float4 desc[64][4];       // B build: column descriptor of the row on lane L: chain | zc[6] | z0[6]     4096 B
     float4 cg[160];           // contact generation (single-env launches): CgLds (below)                     2560 B
   } u;
-  float cpt[MAXC][8];         // contact points: body, x, y, z (rel. base origin), distance     416 B
+  float cpt[MAXC][8];         // contact points: body, x, y, z (rel. base origin), distance | WARM: hull vertex + 1 (int)     416 B
   float st[6][TL];            // per body lane, parked across the phases: q, qd, motor torque, target, updated rate, 1/M^-1_jj  768 B
   float xch[44];              // PAIR launches, between the two waves of a workgroup: [0..5] base twist w, v | [6] env | [7] substeps
                               // of this step | [8..28] Cholesky factor of the base's articulated inertia | [29..34] base acceleration
@@ -385,6 +392,8 @@ struct KernelArgs {
   int n_steps;
   long long step_rows;
   int pen_in_rows;        // row-block launches of a batch with trex_batch_set_penalties_in_rows: the three penalties follow done in the row
+  float *warm;            // WARM launches: the per-env warm-start records [N][TREX_WARM_WORDS] (device_model.h); last, so that
+                          // every other argument keeps its offset
 };
 
 }  // namespace
@@ -415,10 +424,17 @@ struct KernelArgs {
 // 11.53 M; roles with adjacent ranks paired +1.7 % at 2048 envs, heavy + light +7.7 %; at 4096 envs, where four waves share a
 // SIMD, 11.70 M against 11.50 M). The same arithmetic per lane: BITWISE the rows of the single-env launch (scripts/state_digest.py,
 // 300 steps of 4096 envs; the test-suite compares even batches - this form - with step_many, resets and odd batches - that form).
+// WARM (the model's `warmstart` > 0; args.warm holds the per-env records, device_model.h): PGS warm start. A contact point whose hull
+// vertex was a point of the env's last solve starts its solve at warmstart x that solve's final impulses, on its three rows; every
+// other row starts at 0. The record of the last solve lives in LDS (`Wrec`, outside the union area and `cpt`, which the next
+// substep's contact generation overwrites) for the whole launch: loaded from the env's row at the start, rewritten by every solve,
+// emptied by a reset (launch, episode limit, containment), stored at the end. Separate instantiations: the kernels without it are
+// the code they were.
 #define WSYNC() do { if (PAIR) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); else __syncthreads(); } while (0)
-template <bool RESET, bool DEBUG, bool MULTI, bool PAIR = false>
+template <bool RESET, bool DEBUG, bool MULTI, bool PAIR = false, bool WARM = false>
 __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int wg_in) {   // wg_in: blockIdx.x
   static_assert(!PAIR || (!RESET && !DEBUG && !MULTI), "the pair form exists for the product step launch only");
+  static_assert(!(WARM && DEBUG), "the diagnostics dump has no warm-start form");
   __shared__ WaveLds Wpair[PAIR ? 2 : 1];
   __shared__ __attribute__((aligned(16))) unsigned char Gpair[PAIR ? sizeof(CgLds) : 16];   // PAIR: contact-generation scratch of the workgroup (wave 1)
   const int wave = PAIR ? uni((int)threadIdx.x >> 6) : 0;
@@ -428,6 +444,9 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
   int wave_v = PAIR ? (int)threadIdx.x >> 6 : 0;
   if (PAIR) asm volatile("" : "+v"(wave_v));
   WaveLds &W = Wpair[wave_v];
+  // WARM: the record of this wave's env, slot s = (vertex + 1 as an int, normal, friction x, friction y impulse); key 0 = empty
+  __shared__ float4 Wrec[WARM ? (PAIR ? 2 : 1) : 1][MAXC];
+  float4 *const Wr = Wrec[WARM ? wave_v : 0];
   const int wg = PAIR ? 2 * wg_in + wave : wg_in;       // the index the env-to-wave deal and the priorities go by
   const int tid = (int)threadIdx.x & 63;
   const TrexDeviceModel *__restrict__ M = args.model;
@@ -557,6 +576,11 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
     if (tid < TL) {
       W.st[ST_Q][tid] = q; W.st[ST_QD][tid] = qd; W.st[ST_TAU][tid] = mtau; W.st[ST_TARGET][tid] = target;
       W.st[ST_NQD][tid] = 0.f;
+    }
+    if (WARM) {   // the env's record, one coalesced load (a RESET launch gets here only for an env it resets: empty record)
+      const int w = warm_word(tid);
+      const float v = RESET ? 0.f : args.warm[(size_t)env * TREX_WARM_WORDS + tid];
+      if (w >= 0) reinterpret_cast<float *>(Wr)[w] = v;
     }
   }
   WSYNC();
@@ -717,6 +741,7 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
       W.st[ST_Q][l] = l < nb ? Mo()->q_start[l] : 0.f;
       W.st[ST_QD][l] = 0.f; W.st[ST_TAU][l] = 0.f;
     }
+    if (WARM && l < MAXC) Wr[l].x = 0.f;   // a new episode (or a contained env) starts with an empty record
     WSYNC();
   };
   const int n_launch_steps = MULTI ? args.n_steps : 1;
@@ -985,6 +1010,7 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
         if (mine) {
           float *o = E.cpt[slot];
           o[0] = __int_as_float(lt); o[1] = a_x[0]; o[2] = a_x[1]; o[3] = a_x[2]; o[4] = a_d;
+          if (WARM) o[5] = __int_as_float(a_v + 1);   // the point's identity across solves: its hull vertex
         }
         nc = n_active;
       } else {
@@ -1002,7 +1028,7 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
             if (gi == i) { b = __ffs(am) - 1; act = true; }
         }
         float Rb[9], rb[3], px[4][3];
-        int sel[3] = {-1, -1, -1};
+        int sel[3] = {-1, -1, -1}, sel3 = -1;     // (sel3, the vertex of pass 3: WARM only)
 #pragma unroll
         for (int c = 0; c < 9; c++) Rb[c] = wshfl(R[c], b);
 #pragma unroll
@@ -1143,6 +1169,7 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
           }
           if (!stop) {
             if (pass < 3) sel[pass] = bi;
+            else sel3 = bi;
             nsel = pass + 1;
           }
         }
@@ -1160,6 +1187,7 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
             if (k < nsel && off + k < maxc) {
               float *o = E.cpt[off + k];
               o[0] = __int_as_float(b); o[1] = px[k][0]; o[2] = px[k][1]; o[3] = px[k][2]; o[4] = posz + px[k][2] - floor_z;
+              if (WARM) o[5] = __int_as_float((k == 0 ? sel[0] : (k == 1 ? sel[1] : (k == 2 ? sel[2] : sel3))) + 1);
             }
           }
         }
@@ -2045,6 +2073,33 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
       y = zs[64 * 6 + lt]; mhi = zs[64 * 7 + lt]; lr = zs[64 * 8 + lt]; ldir = zs[64 * 9 + lt];
     }
     float lam = 0.f, lam_c = 0.f, lim_lam = 0.f;
+    if (WARM) {
+      // Warm start. A contact-row lane whose point's hull vertex is in the record starts at warmstart x the recorded impulse of
+      // its row. Starting from impulses lam0 means y_s += sum_r B_sr lam0_r on EVERY lane (B_rr = -1 on the row's own lane), one
+      // v_readlane + one fma per warm row; slots without a match are skipped by a scalar mask, so an empty record is the cold
+      // solve bitwise. A limit row needs nothing more: its residual is lr + ldir y with lr formed from the COLD y before the B
+      // build, so the term reaches it through y. The dead-point masks are formed per sweep from lam: they see lam0.
+      const bool crow = lt == 0 || lt >= CLANE0;
+      const int k = crow ? (lt == 0 ? 3 * MAXC - 1 : lt - CLANE0) : 0, slot = k / 3, dir = k - 3 * slot;
+      const int key = (crow && slot >= s0) ? __float_as_int(W.cpt[slot - s0][5]) : 0;
+      const float *rw = reinterpret_cast<const float *>(Wr);
+      float l0 = 0.f;
+#pragma unroll
+      for (int r = 0; r < MAXC; r++)
+        if (key != 0 && __float_as_int(rw[4 * r]) == key) l0 = rw[4 * r + 1 + dir];
+      lam = Mo()->prm[TP_WARMSTART] * l0;
+      const unsigned long long wm = __ballot(lam != 0.f);
+      if (wm != 0ull) {
+#pragma unroll
+        for (int s = 0; s < MAXC; s++) {
+          const unsigned long long sm = (1ull << KROW_LANE(3 * s)) | (1ull << KROW_LANE(3 * s + 1)) | (1ull << KROW_LANE(3 * s + 2));
+          if (s >= s0 && (wm & sm) != 0ull) {
+#pragma unroll
+            for (int a = 0; a < 3; a++) y = __builtin_fmaf(Bc[3 * s + a], rl(lam, KROW_LANE(3 * s + a)), y);
+          }
+        }
+      }
+    }
     int dvec = 0;   // lane j: the impulse change of motor row j in the current sweep (the other lanes stay 0)
     {
 #define TREX_ROW(LANE, BCOL, LO, HI)                                                                   \
@@ -2393,6 +2448,13 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
 #undef TREX_POINTS1
       lam -= lam_c;
     }
+    if (WARM) {   // this solve's record: its points' hull vertices and final impulses, unscaled (slots not in use: empty)
+      const int l = lane_id(), w = warm_word(l);
+      const int slot = l >= 1 && l <= MAXC ? l - 1 : (l == 0 ? MAXC - 1 : (l - CLANE0) / 3);
+      float v = 0.f;
+      if (slot >= s0) v = (l >= 1 && l <= MAXC) ? W.cpt[slot - s0][5] : lam;
+      if (w >= 0) reinterpret_cast<float *>(Wr)[w] = v;
+    }
 #if TREX_PRIO_MODE == 1
     prio_nc = nc;
     set_tree_priority(sub);
@@ -2558,6 +2620,10 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
       args.arr.q[(size_t)env * TL + lt] = q;
       args.arr.qd[(size_t)env * TL + lt] = qd;
     }
+    if (WARM) {   // the record goes back to the env's row: one coalesced store
+      const int w = warm_word(lt);
+      args.warm[(size_t)env * TREX_WARM_WORDS + lt] = w >= 0 ? reinterpret_cast<const float *>(Wr)[w] : 0.f;
+    }
   }
   if (lt == 0) {
     if (!RESET && args.bal) {
@@ -2589,6 +2655,11 @@ __global__ __launch_bounds__(64, 4) void trex_step_kernel(KernelArgs args) { tre
 __global__ __launch_bounds__(128, 4) void trex_step_pair_kernel(KernelArgs args) { trex_step_body<false, false, false, true>(args, (int)blockIdx.x); }
 // S env-steps per launch (trex_batch_step_many)
 __global__ __launch_bounds__(64, 4) void trex_step_many_kernel(KernelArgs args) { trex_step_body<false, false, true>(args, (int)blockIdx.x); }
+// the same launches with the PGS warm start (WARM above): chosen on the host for a batch whose model has warmstart > 0
+template <bool RESET>
+__global__ __launch_bounds__(64, 4) void trex_step_warm_kernel(KernelArgs args) { trex_step_body<RESET, false, false, false, true>(args, (int)blockIdx.x); }
+__global__ __launch_bounds__(128, 4) void trex_step_pair_warm_kernel(KernelArgs args) { trex_step_body<false, false, false, true, true>(args, (int)blockIdx.x); }
+__global__ __launch_bounds__(64, 4) void trex_step_many_warm_kernel(KernelArgs args) { trex_step_body<false, false, true, false, true>(args, (int)blockIdx.x); }
 
 // ---------------------------------------------------------------- small utility kernels
 __global__ void trex_pack_state_kernel(const TrexDeviceModel *M, TrexBatchArrays arr, int n, float *out, int pack) {
@@ -2759,19 +2830,28 @@ extern "C" {
 hipError_t trex_launch_step(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions,
                             float *obs, float *reward, uint8_t *done, float *penalties, float wd, float we,
                             float wk, float *debug, hipStream_t stream, float *done_f, int obs_stride, int scal_stride,
-                            int balance, int pen_in_rows) {
+                            int balance, int pen_in_rows, float *warm) {
   // balance: the env-to-wave assignment by contact rank (trex_batch_set_wave_balance decides; capi.cpp). Diagnostics
   // launches keep env k in workgroup k (the stamped build is balanced like the product: it reports the env of every wave)
   int32_t *perm = ((debug && !TREX_STAMPS) || !balance) ? nullptr : arr.balance;
   KernelArgs a{model, arr, n, actions, obs, reward, done, done_f, obs_stride, scal_stride, penalties, nullptr, perm, wd, we, wk, debug,
-               1, 0, pen_in_rows};
+               1, 0, pen_in_rows, warm};
 
+  const bool pair = TREX_PAIR_LAUNCH && (n & 1) == 0 && n <= TREX_PAIR_MAX;
 #if TREX_STAMPS   // diagnostic build: the PRODUCT instantiation, stamped (the dump of <false, true> would change its code)
-  if (TREX_PAIR_LAUNCH && (n & 1) == 0 && n <= TREX_PAIR_MAX) hipLaunchKernelGGL(trex_step_pair_kernel, dim3(n / 2), dim3(128), 0, stream, a);
+  if (warm) {
+    if (pair) hipLaunchKernelGGL(trex_step_pair_warm_kernel, dim3(n / 2), dim3(128), 0, stream, a);
+    else hipLaunchKernelGGL(trex_step_warm_kernel<false>, dim3(n), dim3(64), 0, stream, a);
+  } else if (pair) hipLaunchKernelGGL(trex_step_pair_kernel, dim3(n / 2), dim3(128), 0, stream, a);
   else hipLaunchKernelGGL((trex_step_kernel<false, false>), dim3(n), dim3(64), 0, stream, a);
 #else
-  if (debug) hipLaunchKernelGGL((trex_step_kernel<false, true>), dim3(n), dim3(64), 0, stream, a);
-  else if (TREX_PAIR_LAUNCH && (n & 1) == 0 && n <= TREX_PAIR_MAX) hipLaunchKernelGGL(trex_step_pair_kernel, dim3(n / 2), dim3(128), 0, stream, a);
+  if (debug) {   // (capi.cpp refuses a diagnostics step of a warm batch: this instantiation has no record)
+    if (warm) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((trex_step_kernel<false, true>), dim3(n), dim3(64), 0, stream, a);
+  } else if (warm) {
+    if (pair) hipLaunchKernelGGL(trex_step_pair_warm_kernel, dim3(n / 2), dim3(128), 0, stream, a);
+    else hipLaunchKernelGGL(trex_step_warm_kernel<false>, dim3(n), dim3(64), 0, stream, a);
+  } else if (pair) hipLaunchKernelGGL(trex_step_pair_kernel, dim3(n / 2), dim3(128), 0, stream, a);
   else hipLaunchKernelGGL((trex_step_kernel<false, false>), dim3(n), dim3(64), 0, stream, a);
 #endif
   return hipGetLastError();
@@ -2781,20 +2861,22 @@ hipError_t trex_launch_step(const TrexDeviceModel *model, TrexBatchArrays arr, i
 // penalties [S, N, 3] and done bytes [S, N] nullable
 hipError_t trex_launch_step_many(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions, float *rows,
                                  int row_stride, int n_steps, float *penalties, uint8_t *done, float wd, float we, float wk,
-                                 hipStream_t stream, int balance, int nj, int pen_in_rows) {
+                                 hipStream_t stream, int balance, int nj, int pen_in_rows, float *warm) {
   float *rew = rows + 3 * nj;
   KernelArgs a{model, arr, n, actions, rows, rew, done, rew + 1, row_stride, row_stride, penalties, nullptr,
-               balance ? arr.balance : nullptr, wd, we, wk, nullptr, n_steps, (long long)n * row_stride, pen_in_rows};
-  hipLaunchKernelGGL(trex_step_many_kernel, dim3(n), dim3(64), 0, stream, a);
+               balance ? arr.balance : nullptr, wd, we, wk, nullptr, n_steps, (long long)n * row_stride, pen_in_rows, warm};
+  if (warm) hipLaunchKernelGGL(trex_step_many_warm_kernel, dim3(n), dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL(trex_step_many_kernel, dim3(n), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 
 hipError_t trex_launch_reset(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const uint8_t *mask,
                              float *obs, float wd, float we, float wk, float *debug, hipStream_t stream, int obs_stride,
-                             float *reward, float *done_f, int scal_stride, int nj, int pen_in_rows) {
+                             float *reward, float *done_f, int scal_stride, int nj, int pen_in_rows, float *warm) {
   KernelArgs a{model, arr, n, nullptr, obs, reward, nullptr, done_f, obs_stride, scal_stride, nullptr, mask, nullptr, wd, we, wk, debug,
-               1, 0, (reward && done_f && pen_in_rows) ? 1 : 0};
-  hipLaunchKernelGGL((trex_step_kernel<true, false>), dim3(n), dim3(64), 0, stream, a);
+               1, 0, (reward && done_f && pen_in_rows) ? 1 : 0, warm};
+  if (warm) hipLaunchKernelGGL(trex_step_warm_kernel<true>, dim3(n), dim3(64), 0, stream, a);
+  else hipLaunchKernelGGL((trex_step_kernel<true, false>), dim3(n), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -2844,5 +2926,6 @@ hipError_t trex_launch_copy_mass_scale(const float *src, float *dst, int n, int 
 // even batch that is resident at once, one otherwise
 int trex_step_envs_per_workgroup(int n) { return (TREX_PAIR_LAUNCH && (n & 1) == 0 && n <= TREX_PAIR_MAX) ? 2 : 1; }
 int trex_step_lds_bytes(int n) { return trex_step_envs_per_workgroup(n) == 2 ? (int)(2 * sizeof(WaveLds) + sizeof(CgLds)) : (int)sizeof(WaveLds); }
+int trex_step_warm_lds_bytes(void) { return (int)(MAXC * sizeof(float4)); }   // per env, on top of the above in the warm kernels
 
 }  // extern "C"

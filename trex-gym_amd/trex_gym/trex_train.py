@@ -19,9 +19,11 @@ from .vec_env import TrexVecEnv
 _URDF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "assets", "trex_collide.urdf")
 
 
-def build_environment(num_envs, device="cuda:0", max_episode_steps=1000):   # (weights of trex_train.py:66)
+def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0):   # (weights of trex_train.py:66)
+    # warmstart > 0: the contact solver starts from that fraction of each point's impulses of the last solve (model parameter)
+    params = {"warmstart": float(warmstart)} if warmstart else None
     return TrexVecEnv(num_envs, urdf_path=_URDF_PATH, device=device, distance_weight=2e2, energy_weight=1e-6,
-                      drift_weight=1.0, max_episode_steps=max_episode_steps)
+                      drift_weight=1.0, max_episode_steps=max_episode_steps, params=params)
 
 
 # Hyper-parameter presets. "reference" is the ppo2.learn call of the reference's script (trex_train.py:47-60):
@@ -115,13 +117,15 @@ def main(argv=None):
     ap.add_argument("--noptepochs", type=int, default=None, help="override the preset's epochs per update")
     ap.add_argument("--max_episode_steps", type=int, default=1000)
     ap.add_argument("--save", type=str, default=None)
+    ap.add_argument("--warmstart", type=float, default=0.0,
+                    help="PGS warm start: contact points start each solve at this factor x their last impulses, in [0, 1] (0 = off)")
     ap.add_argument("--graphs", action="store_true", help="replay the rollout and the minibatch update as HIP graphs")
     ap.add_argument("--play", action="store_true", help="after training: run the policy and record the frames' mesh poses (trex_train.py:25,126-136)")
     ap.add_argument("--num_play_timesteps", type=int, default=int(2e3))          # trex_train.py:28
     ap.add_argument("--export", type=str, default=None, help="with --play: .npz of mesh names + [T, 252, 7] world poses for an external renderer")
     ap.add_argument("--play_deterministic", action="store_true", help="with --play: the mean action and frozen normalisation statistics (the reference samples and keeps updating)")
     args = ap.parse_args(argv)
-    env = build_environment(args.num_envs, max_episode_steps=args.max_episode_steps)
+    env = build_environment(args.num_envs, max_episode_steps=args.max_episode_steps, warmstart=args.warmstart)
     agent, _ = train(env, args.num_timesteps, args.random_seed, args.nsteps, args.noptepochs, args.save, use_graphs=args.graphs,
                      preset=args.preset)
     if args.play:

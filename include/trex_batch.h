@@ -114,7 +114,11 @@ int trex_model_get_param(const TrexModel *model, const char *name, double *value
  * element count (or a negative error). Names: "parent" "depth" "joint_axis" "joint_pos" "joint_rot"
  * "q_lower" "q_upper" "joint_damping" "mass" "com" "inertia" "obs_order" "head_body" "head_point"
  * "hull_xyz" "hull_radius" "hull_group_start" "hull_start" "sphere_center" "sphere_radius" "q_start" "base_start_pos"
- * "base_start_quat" "revolute_joint_indices" "link_body" "link_tf" (12 per link: R row-major, t). */
+ * "base_start_quat" "revolute_joint_indices" "link_body" "link_tf" (12 per link: R row-major, t).
+ * "hull_plane" / "hull_plane_start": what trex_batch_render draws a hull with - the face planes (nx, ny, nz, d per plane,
+ * body frame, unit n, n.x <= d inside) of the convex hull of every hull group's radius-0 points, computed from the VERTICES
+ * (coplanar triangles merged; every plane touches at least 3 of them), with a CSR start per group. A group with fewer than
+ * 4 non-coplanar such points has no plane and draws nothing. */
 int trex_model_get_array(const TrexModel *model, const char *name, double *out, int capacity);
 
 /* ---- batch: N independent env copies resident on one GPU ---- */
@@ -225,6 +229,40 @@ int trex_model_num_visuals(const TrexModel *model);
 int trex_model_visual_info(const TrexModel *model, int visual, const char **mesh_file, int *link, double xyz[3],
                            double quat_xyzw[4]);
 int trex_batch_visual_transforms(TrexBatch *batch, float *out_dev, void *stream);
+
+/* ---- rendering (trex_env.py:156-181 getCameraImage; no GUI): a ray caster over the collision geometry the physics holds
+ *
+ * What is drawn: every body's convex hulls (the planes of "hull_plane" above) or, after trex_model_use_primitive_collision,
+ * its collision spheres, and the floor - the plane z = floor_z (model parameter: the floor box's top face), a 1 m
+ * checkerboard. Deterministic shading: one colour per body (a fixed palette), Lambert under one fixed directional light
+ * plus ambient, a constant sky; one ray per pixel centre - no anti-aliasing, shadows or textures. Pixel parity with
+ * pybullet's image is NOT a goal: pybullet draws the visual meshes (not shipped), this draws the collision hulls.
+ *
+ * Camera (pybullet's computeViewMatrixFromYawPitchRoll with upAxisIndex = 2, roll 0, and computeProjectionMatrixFOV):
+ *   eye = target + Rz(yaw) Rx(pitch) (0, -distance, 0), up = Rz(yaw) Rx(pitch) (0, 0, 1), +z up, looking at target;
+ *   the reference's camera (distance 10, yaw 90, pitch -30) sits at target + (8.66, 0, 5.0) looking along -x.
+ *   NOT CONFIRMED against pybullet (not available here): that is the convention of its source as recalled.
+ *   Projection: OpenGL perspective, VERTICAL fov, aspect = width / height; row 0 is the TOP of the image (getCameraImage).
+ *   Geometry closer than near_z is cut away; farther than far_z is not drawn. */
+typedef struct TrexCamera {
+  float distance, yaw_deg, pitch_deg, fov_deg, near_z, far_z;
+  int follow_base;        /* != 0: target = each env's base position (trex_env.py:157); else target[] */
+  float target[3];
+} TrexCamera;
+
+/* Render num_views views: view v shows env env_ids[v] (a HOST array; NULL = all N envs in order, num_views then 0 or N).
+ * Outputs per view, each device and nullable (not all three):
+ *   rgb_dev   [V, H, W, 3] u8;
+ *   depth_dev [V, H, W] f32: linear eye-space z in metres (pybullet's depth buffer is depth_to_zbuffer of it), far_z where
+ *             nothing is hit;
+ *   seg_dev   [V, H, W] i32: body index in [0, num_bodies), -1 floor, -2 nothing.
+ * Every pixel of every non-NULL buffer is written. An env id out of range, a width or height <= 0 or > 4096, more than
+ * 65535 views, a non-finite or degenerate camera, all outputs NULL or a buffer shorter than the call needs return
+ * TREX_E_INVALID before anything reaches the GPU; a model with more than 512 drawable primitives TREX_E_UNSUPPORTED.
+ * Ordered on `stream`. Reads the state and writes nothing else (no state, warm-start record or episode count). The first
+ * call computes the hull planes and keeps them in the batch; env ids are copied to a batch-owned device buffer. */
+int trex_batch_render(TrexBatch *batch, const TrexCamera *camera, int width, int height, const int32_t *env_ids,
+                      int num_views, uint8_t *rgb_dev, float *depth_dev, int32_t *seg_dev, void *stream);
 
 /* domain randomisation (BASELINE config 5; no reference counterpart): per-env mass scale of each
  * moving body [N, num_bodies] and per-env friction coefficient [N]; either may be NULL. */

@@ -13,6 +13,7 @@
 #include "device_model.h"
 #include "internal.hpp"
 #include "model.hpp"
+#include "render.h"
 
 extern "C" {
 hipError_t trex_launch_step(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, float *, uint8_t *,
@@ -32,6 +33,7 @@ hipError_t trex_launch_copy_mass_scale(const float *, float *, int, int, hipStre
 int trex_step_lds_bytes(int);
 int trex_step_envs_per_workgroup(int);
 int trex_step_warm_lds_bytes(void);
+hipError_t trex_launch_render(const TrexRenderArgs &, hipStream_t);
 }
 
 struct TrexModel {
@@ -48,6 +50,17 @@ struct TrexBatch {
   int balance_mode = -1;                       // trex_batch_set_wave_balance: -1 auto, 0 off, 1 on
   bool balance() const { return balance_mode < 0 ? n >= 2048 : balance_mode != 0; }
   std::vector<void *> allocs;
+  // renderer (trex_batch_render): the model's hull data, its primitive / plane table made on the first render call
+  std::vector<trex::Vec3> hull_xyz;
+  std::vector<double> hull_radius;
+  std::vector<int> hull_start, hull_group_start;
+  double floor_z = 0;
+  bool render_ready = false;
+  int render_nprim = 0;
+  TrexRenderPrim *render_prim = nullptr;
+  float4 *render_plane = nullptr;
+  int32_t *render_ids = nullptr;     // device copy of the env ids of the last call
+  size_t render_ids_cap = 0;
   // caller allocations already validated as memory of this device (base address, bytes known to be good):
   // the hot path pays one hash-free scan of a handful of entries, hipPointerGetAttributes only on a new one
   std::vector<TrexSeen> seen;
@@ -380,6 +393,11 @@ int trex_model_get_array(const TrexModel *m, const char *name, double *out, int 
   else if (n == "q_start") v = h.q_start;
   else if (n == "base_start_pos") v = {h.base_start_pos.x, h.base_start_pos.y, h.base_start_pos.z};
   else if (n == "base_start_quat") v.assign(h.base_start_quat, h.base_start_quat + 4);
+  else if (n == "hull_plane" || n == "hull_plane_start") {
+    std::vector<int> start;
+    trex::hull_group_planes(h, v, start);
+    if (n == "hull_plane_start") v.assign(start.begin(), start.end());
+  }
   else return fail(TREX_E_INVALID, "unknown array '" + n + "'");
   if (out) {
     if (capacity < (int)v.size()) return fail(TREX_E_INVALID, "capacity too small for '" + n + "'");
@@ -423,6 +441,9 @@ int trex_batch_create(const TrexModel *model, int num_envs, int device, TrexBatc
   if (model->host.prm.warmstart > 0) A(n * TREX_WARM_WORDS * sizeof(float), (void **)&b->warm);
   b->arr.max_episode_steps = 0;
   b->arr.domain = 0;
+  b->floor_z = model->host.prm.floor_z;
+  b->hull_xyz = model->host.hull_xyz; b->hull_radius = model->host.hull_radius;
+  b->hull_start = model->host.hull_start; b->hull_group_start = model->host.hull_group_start;
   size_t nv = model->host.hull_xyz.size();
   A((nv ? nv : 1) * sizeof(float4), (void **)&b->arr.hull);
   const size_t nl = model->host.link_names.size();
@@ -483,6 +504,7 @@ void trex_batch_destroy(TrexBatch *b) {
   DeviceGuard guard(b->device);
   (void)hipDeviceSynchronize();
   for (void *p : b->allocs) (void)hipFree(p);
+  if (b->render_ids) (void)hipFree(b->render_ids);
   delete b;
 }
 
@@ -748,6 +770,97 @@ int trex_batch_time_steps(TrexBatch *b, const float *actions_dev, float *obs_dev
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   *avg_ms_out = ms / steps;
+  return TREX_OK;
+}
+
+int trex_batch_render(TrexBatch *b, const TrexCamera *cam, int width, int height, const int32_t *env_ids, int num_views,
+                      uint8_t *rgb_dev, float *depth_dev, int32_t *seg_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!cam) return fail(TREX_E_INVALID, "trex_batch_render: camera is null");
+  if (width <= 0 || height <= 0 || width > TREX_RENDER_MAXDIM || height > TREX_RENDER_MAXDIM)
+    return fail(TREX_E_INVALID, "trex_batch_render: width and height must lie in [1, " + std::to_string(TREX_RENDER_MAXDIM) + "]");
+  if (!rgb_dev && !depth_dev && !seg_dev) return fail(TREX_E_INVALID, "trex_batch_render: all three outputs are null");
+  const float cv[] = {cam->distance, cam->yaw_deg, cam->pitch_deg, cam->fov_deg, cam->near_z, cam->far_z,
+                      cam->target[0], cam->target[1], cam->target[2]};
+  for (float x : cv)
+    if (!std::isfinite(x)) return fail(TREX_E_INVALID, "trex_batch_render: camera value is not finite");
+  if (!(cam->distance > 0) || !(cam->fov_deg > 0 && cam->fov_deg < 180) || !(cam->near_z > 0 && cam->far_z > cam->near_z))
+    return fail(TREX_E_INVALID, "trex_batch_render: camera needs distance > 0, 0 < fov < 180, 0 < near < far");
+  if (env_ids) {
+    if (num_views <= 0) return fail(TREX_E_INVALID, "trex_batch_render: num_views must be positive");
+    for (int v = 0; v < num_views; v++)
+      if (env_ids[v] < 0 || env_ids[v] >= b->n)
+        return fail(TREX_E_INVALID, "trex_batch_render: env id " + std::to_string(env_ids[v]) + " out of range [0, " +
+                                        std::to_string(b->n) + ")");
+  } else {
+    if (num_views != 0 && num_views != b->n) return fail(TREX_E_INVALID, "trex_batch_render: env_ids NULL needs num_views 0 or N");
+    num_views = b->n;
+  }
+  if (num_views > 65535) return fail(TREX_E_INVALID, "trex_batch_render: at most 65535 views per call");
+  DeviceGuard guard(b->device);
+  const size_t px = (size_t)num_views * height * width;
+  BUF_TRY(rgb_dev, px * 3, "trex_batch_render: rgb");
+  BUF_TRY(depth_dev, px * sizeof(float), "trex_batch_render: depth");
+  BUF_TRY(seg_dev, px * sizeof(int32_t), "trex_batch_render: seg");
+  hipStream_t s = (hipStream_t)stream;
+  if (!b->render_ready) {   // the primitive / plane table, once per batch (trex_model_load stays as fast as it was)
+    trex::HostModel hm;
+    hm.nb = b->nb;
+    hm.hull_xyz = b->hull_xyz; hm.hull_radius = b->hull_radius; hm.hull_start = b->hull_start; hm.hull_group_start = b->hull_group_start;
+    std::vector<TrexRenderPrim> prims;
+    std::vector<float> planes;
+    const int np = trex::render_table(hm, prims, planes);
+    if (np > TREX_RENDER_MAXPRIM)
+      return fail(TREX_E_UNSUPPORTED, "trex_batch_render: the model has " + std::to_string(np) + " drawable primitives, the renderer " +
+                                          std::to_string(TREX_RENDER_MAXPRIM));
+    if (planes.empty()) planes.assign(4, 0.f);
+    if (prims.empty()) prims.resize(1);
+    void *pp = nullptr, *pl = nullptr;
+    HIP_TRY(hipMalloc(&pp, prims.size() * sizeof(TrexRenderPrim)));
+    b->allocs.push_back(pp);
+    HIP_TRY(hipMalloc(&pl, planes.size() * sizeof(float)));
+    b->allocs.push_back(pl);
+    HIP_TRY(hipMemcpy(pp, prims.data(), prims.size() * sizeof(TrexRenderPrim), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(pl, planes.data(), planes.size() * sizeof(float), hipMemcpyHostToDevice));
+    b->render_prim = (TrexRenderPrim *)pp; b->render_plane = (float4 *)pl; b->render_nprim = np;
+    b->render_ready = true;
+  }
+  if (env_ids) {
+    if (b->render_ids_cap < (size_t)num_views) {   // (grows rarely: the old buffer may still be read by an earlier call)
+      HIP_TRY(hipDeviceSynchronize());
+      if (b->render_ids) (void)hipFree(b->render_ids);
+      b->render_ids = nullptr; b->render_ids_cap = 0;
+      HIP_TRY(hipMalloc((void **)&b->render_ids, (size_t)num_views * sizeof(int32_t)));
+      b->render_ids_cap = (size_t)num_views;
+    }
+    HIP_TRY(hipMemcpyAsync(b->render_ids, env_ids, (size_t)num_views * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  }
+  // camera (include/trex_batch.h): eye = target + Rz(yaw) Rx(pitch) (0, -distance, 0), up = Rz(yaw) Rx(pitch) (0, 0, 1)
+  const double d2r = 3.14159265358979323846 / 180.0, yw = cam->yaw_deg * d2r, pt = cam->pitch_deg * d2r;
+  const double off[3] = {cam->distance * std::cos(pt) * std::sin(yw), -cam->distance * std::cos(pt) * std::cos(yw),
+                         -cam->distance * std::sin(pt)};
+  const double up0[3] = {std::sin(pt) * std::sin(yw), -std::sin(pt) * std::cos(yw), std::cos(pt)};
+  double f[3] = {-off[0] / cam->distance, -off[1] / cam->distance, -off[2] / cam->distance};
+  double r[3] = {f[1] * up0[2] - f[2] * up0[1], f[2] * up0[0] - f[0] * up0[2], f[0] * up0[1] - f[1] * up0[0]};
+  const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  for (double &x : r) x /= rl;
+  const double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};
+  TrexRenderArgs a{};
+  a.model = b->dmodel; a.base = b->arr.base; a.q = b->arr.q;
+  a.env_ids = env_ids ? b->render_ids : nullptr;
+  a.prim = b->render_prim; a.plane = b->render_plane;
+  a.rgb = rgb_dev; a.depth = depth_dev; a.seg = seg_dev;
+  a.num_views = num_views; a.width = width; a.height = height;
+  a.nprim = b->render_nprim; a.follow_base = cam->follow_base != 0;
+  for (int c = 0; c < 3; c++) {
+    a.target[c] = cam->target[c]; a.offset[c] = (float)off[c];
+    a.fwd[c] = (float)f[c]; a.right[c] = (float)r[c]; a.up[c] = (float)u[c];
+  }
+  const double ty = std::tan(0.5 * cam->fov_deg * d2r);
+  a.tan_y = (float)ty; a.tan_x = (float)(ty * width / height);
+  a.near_z = cam->near_z; a.far_z = cam->far_z;
+  a.floor_z = (float)b->floor_z;
+  HIP_TRY(trex_launch_render(a, s));
   return TREX_OK;
 }
 

@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+struct TrexRenderPrim;
+
 namespace trex {
 
 constexpr int kLanes = 32;      // lanes per env team (half a wavefront)
@@ -82,6 +84,14 @@ std::vector<Primitive> fit_primitives(const std::vector<Vec3> &points, double ma
 // Replace every hull of the model by the end spheres of its fitted primitives.
 void use_primitive_collision(HostModel &m, double max_radius, int max_divisions, int min_points);
 Mat3 rpy_to_matrix(double r, double p, double y);
+
+// Renderer (render.cpp). Face planes (nx, ny, nz, d: n.x <= d inside, |n| = 1, body frame) of the convex hull of a point
+// set; none for fewer than 4 non-coplanar points.
+std::vector<std::array<double, 4>> convex_hull_planes(const std::vector<Vec3> &points);
+// The planes of every hull group (its radius-0 points): 4 doubles per plane, CSR `start` per group.
+void hull_group_planes(const HostModel &m, std::vector<double> &plane, std::vector<int> &start);
+// The ray kernel's primitive table (render.h): one hull per group with planes, one sphere per point of radius > 0.
+int render_table(const HostModel &m, std::vector<TrexRenderPrim> &prims, std::vector<float> &planes);
 void matrix_to_quat(const Mat3 &m, double q[4]);
 
 }  // namespace trex

@@ -40,6 +40,7 @@ SYMBOLS = [
     "trex_batch_set_episode_limit", "trex_batch_get_episode_steps",
     "trex_batch_set_wave_balance", "trex_batch_forget_buffers", "trex_batch_set_penalties_in_rows",
     "trex_model_num_visuals", "trex_model_visual_info", "trex_batch_visual_transforms", "trex_batch_step_many",
+    "trex_batch_render",
 ]
 
 # every symbol include/trex_policy.h declares (the trainer-side kernels)
@@ -100,6 +101,14 @@ lib.trex_batch_visual_transforms.argtypes = [_vp, _vp, _vp]
 lib.trex_batch_contact_stats.argtypes = [_vp, _vp, _vp, _vp]
 lib.trex_batch_launch_info.argtypes = [_vp] + [C.POINTER(C.c_int)] * 4
 lib.trex_batch_time_steps.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.POINTER(C.c_float)]
+
+
+class TrexCamera(C.Structure):     # include/trex_batch.h
+    _fields_ = [("distance", C.c_float), ("yaw_deg", C.c_float), ("pitch_deg", C.c_float), ("fov_deg", C.c_float),
+                ("near_z", C.c_float), ("far_z", C.c_float), ("follow_base", C.c_int), ("target", C.c_float * 3)]
+
+
+lib.trex_batch_render.argtypes = [_vp, C.POINTER(TrexCamera), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _vp, _vp, _vp, _vp]
 
 
 lib.trex_policy_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]
@@ -397,6 +406,26 @@ class Batch:
         n = self.num_envs
         check(lib.trex_batch_contact_stats(self.h, self._p(count, "int32", n, "count"),
                                            self._p(normal_impulse, "float32", n, "normal_impulse"), self._stream(stream)))
+
+    def render(self, camera, width, height, env_ids=None, rgb=None, depth=None, seg=None, stream=None):
+        """Ray-cast views of the envs (trex_batch_render): camera = trex_gym.render.Camera (or anything with its fields),
+        env_ids = host sequence of env indices (None = all n in order); rgb [V, H, W, 3] uint8, depth [V, H, W] float32,
+        seg [V, H, W] int32 device tensors, any of them None."""
+        cam = TrexCamera(float(camera.distance), float(camera.yaw), float(camera.pitch), float(camera.fov), float(camera.near),
+                         float(camera.far), 1 if camera.target is None else 0,
+                         (C.c_float * 3)(*([0.0] * 3 if camera.target is None else [float(x) for x in camera.target])))
+        if env_ids is None:
+            ids, V = None, self.num_envs
+        else:
+            arr = np.ascontiguousarray(np.asarray(env_ids, dtype=np.int64).reshape(-1))
+            if arr.size == 0 or np.any(arr < np.iinfo(np.int32).min) or np.any(arr > np.iinfo(np.int32).max):
+                raise TrexError(E_INVALID, "env_ids: expected a non-empty list of env indices")
+            arr = arr.astype(np.int32)
+            ids, V = arr.ctypes.data_as(C.POINTER(C.c_int32)), int(arr.size)
+        px = V * max(int(width), 0) * max(int(height), 0)
+        check(lib.trex_batch_render(self.h, C.byref(cam), int(width), int(height), ids, V if env_ids is not None else 0,
+                                    self._p(rgb, "uint8", 3 * px, "rgb"), self._p(depth, "float32", px, "depth"),
+                                    self._p(seg, "int32", px, "seg"), self._stream(stream)))
 
     def launch_info(self):
         g, b, l, a = C.c_int(), C.c_int(), C.c_int(), C.c_int()

@@ -26,8 +26,8 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
 
     def __init__(self, urdf_path=None, action_repeat=1, distance_weight=1.0, energy_weight=0.005,
                  drift_weight=0.002, render=False, device=None):
-        if render:
-            raise NotImplementedError("rendering is outside the accelerated path (DESIGN.md, out of scope)")
+        if render:   # (the reference's render=True opens pybullet's GUI; rgb_array frames need no flag: render())
+            raise NotImplementedError("render=True asks for a GUI, which this env has not; render('rgb_array') draws frames")
         self._time_step = 0.01 / NUM_SUBSTEPS
         self._urdf_path = urdf_path
         self._action_repeat = action_repeat * NUM_SUBSTEPS
@@ -79,7 +79,14 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
         return self._observation, self.compute_reward(), self.should_terminate(), {}
 
     def render(self, mode='rgb_array', close=False):
-        return np.array([])
+        """'rgb_array': uint8 [720, 960, 3] from the reference's camera (distance 10, yaw 90, pitch -30, fov 60, following the
+        base: trex_env.py:156-181), ray-cast from the collision hulls (trex_batch_render). 'human' returns np.array([]) as
+        the reference's method does without a GUI."""
+        if mode != 'rgb_array':
+            return np.array([])
+        from .render import Camera
+        rgb = self._vec.render_tensor([0], RENDER_WIDTH, RENDER_HEIGHT, Camera())
+        return rgb[0].cpu().numpy()
 
     def should_terminate(self):
         return False

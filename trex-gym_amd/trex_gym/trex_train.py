@@ -5,7 +5,8 @@ vec env with the on-device PPO of trex_gym.ppo instead of baselines.ppo2 + TF1.
 
 Reward weights are the training ones of the reference (distance 2e2, energy 1e-6, drift 1.0,
 trex_train.py:66). --play runs the trained policy and records what a renderer needs per frame (the world poses of the 252
-visual meshes); drawing the frames (pybullet's renderer, --debug_render) is out of scope.
+visual meshes); --frames DIR also writes one PNG per step, ray-cast from the collision hulls (trex_batch_render). Turning
+them into a movie (the reference's ffmpeg call) stays the user's.
 """
 import argparse
 import os
@@ -55,22 +56,36 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
     return agent, hist
 
 
-def play(agent, num_play_timesteps, export_path=None, env_index=0, log=print, deterministic=False, update_stats=True, seed=0):
+def _png_writer():
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise ImportError("play(frames_dir=...) writes PNGs with Pillow (PIL), which is not installed") from e
+    return Image
+
+
+def play(agent, num_play_timesteps, export_path=None, env_index=0, log=print, deterministic=False, update_stats=True, seed=0,
+         frames_dir=None, frame_size=(960, 720), camera=None):
     """The reference's play loop (trex_train.py:126-136: model.step -> env.step -> render a frame -> PNGs -> ffmpeg) up to
-    the renderer: every frame's world poses of the 252 visual meshes are recorded (trex_batch_visual_transforms) - what a
-    renderer needs to draw the frame; drawing itself is out of scope.
+    the movie: every frame's world poses of the 252 visual meshes are recorded (trex_batch_visual_transforms) - what an
+    external mesh renderer needs -, and with frames_dir a PNG of the collision hulls is written per step.
     Defaults = the reference's behaviour: `model.step(obs)[0]` is a SAMPLED action (deterministic=False: N(0, 1) noise for
     the policy kernel) and the VecNormalize env it plays in keeps updating its running statistics with every observation
     (update_stats=True: the statistics kernel runs after each step). deterministic=True plays the mean action,
     update_stats=False freezes the statistics after the reset - the repeatable variant for comparing checkpoints (what this
     function did until round 3, then under the name of the reference's loop).
     export_path: .npz with `mesh_files`, `mesh_links`, `poses` [T, 252, 7] (xyz + quaternion xyzw of env `env_index`),
-    `reward` [T], `fps` = 50 (metadata of trex_env.py:36)."""
+    `reward` [T], `fps` = 50 (metadata of trex_env.py:36).
+    frames_dir: one PNG per step of env `env_index` ('%05d-of-%05d.png', the reference's names), frame_size = (width,
+    height), camera = trex_gym.render.Camera (default: the reference's, following the base)."""
     import numpy as np
     env, k = agent.env, agent.kern
     noise = torch.zeros(env.num_envs, env.J, device=env.device)
     gen = torch.Generator(device=env.device).manual_seed(int(seed))
     frames, rewards = [], []
+    if frames_dir is not None:
+        Image = _png_writer()
+        os.makedirs(frames_dir, exist_ok=True)
     env.reset_tensor()
     k.observe(env.rows, with_reward=False)
     for _ in range(num_play_timesteps):
@@ -82,6 +97,9 @@ def play(agent, num_play_timesteps, export_path=None, env_index=0, log=print, de
             k.observe(env.rows)       # (VecNormalize.step_wait: the observation moments AND the return moments move on)
         frames.append(env.visual_transforms()[env_index].cpu().numpy())
         rewards.append(float(env.rew[env_index]))
+        if frames_dir is not None:
+            rgb = env.render_tensor([env_index], frame_size[0], frame_size[1], camera)[0].cpu().numpy()
+            Image.fromarray(rgb).save(os.path.join(frames_dir, "%05d-of-%05d.png" % (len(rewards) - 1, num_play_timesteps)))
     log("Episode reward: %.3f over %d frames" % (sum(rewards), len(rewards)))
     if export_path:
         table = env.model.visuals()
@@ -123,13 +141,15 @@ def main(argv=None):
     ap.add_argument("--play", action="store_true", help="after training: run the policy and record the frames' mesh poses (trex_train.py:25,126-136)")
     ap.add_argument("--num_play_timesteps", type=int, default=int(2e3))          # trex_train.py:28
     ap.add_argument("--export", type=str, default=None, help="with --play: .npz of mesh names + [T, 252, 7] world poses for an external renderer")
+    ap.add_argument("--frames", type=str, default=None, help="with --play: directory for one 960 x 720 PNG per step (trex_train.py:132-134)")
     ap.add_argument("--play_deterministic", action="store_true", help="with --play: the mean action and frozen normalisation statistics (the reference samples and keeps updating)")
     args = ap.parse_args(argv)
     env = build_environment(args.num_envs, max_episode_steps=args.max_episode_steps, warmstart=args.warmstart)
     agent, _ = train(env, args.num_timesteps, args.random_seed, args.nsteps, args.noptepochs, args.save, use_graphs=args.graphs,
                      preset=args.preset)
     if args.play:
-        play(agent, args.num_play_timesteps, args.export, deterministic=args.play_deterministic, update_stats=not args.play_deterministic)
+        play(agent, args.num_play_timesteps, args.export, deterministic=args.play_deterministic, update_stats=not args.play_deterministic,
+             frames_dir=args.frames)
 
 
 if __name__ == "__main__":

@@ -233,8 +233,39 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         self.batch.forget_buffers()
         self.batch.close()
 
+    # ---- rendering (trex_batch_render: a ray caster over the collision hulls, include/trex_batch.h)
+    def render_tensor(self, env_ids=None, width=84, height=84, camera=None, depth=False, segmentation=False):
+        """Pixel observations on the device: rgb [V, H, W, 3] uint8 of the envs env_ids (host sequence, None = all n), plus
+        depth [V, H, W] float32 (linear eye-space metres) and / or seg [V, H, W] int32 (body index, -1 floor, -2 nothing)
+        when asked - then a tuple (rgb, depth?, seg?). camera: trex_gym.render.Camera (default: the reference's, following
+        each env's base). One launch, stream-ordered, no host sync; the state is only read."""
+        from .render import Camera
+        camera = Camera() if camera is None else camera
+        V = self.num_envs if env_ids is None else len(env_ids)
+        rgb = torch.empty(V, height, width, 3, dtype=torch.uint8, device=self.device)
+        dep = torch.empty(V, height, width, dtype=torch.float32, device=self.device) if depth else None
+        seg = torch.empty(V, height, width, dtype=torch.int32, device=self.device) if segmentation else None
+        self.batch.render(camera, width, height, env_ids, rgb, dep, seg)
+        if not depth and not segmentation:
+            return rgb
+        return (rgb,) + ((dep,) if depth else ()) + ((seg,) if segmentation else ())
+
+    def get_images(self, width=None, height=None, camera=None, env_ids=None):
+        """baselines' VecEnv.get_images: a list of H x W x 3 uint8 numpy frames, one per env (default 720 x 960, the
+        reference's frame size: mind the memory for large batches - render_tensor keeps them on the device)."""
+        from .render import RENDER_HEIGHT, RENDER_WIDTH
+        rgb = self.render_tensor(env_ids, width or RENDER_WIDTH, height or RENDER_HEIGHT, camera)
+        return list(rgb.cpu().numpy())
+
     def render(self, mode="rgb_array"):
-        return np.array([])  # rendering is outside the accelerated path
+        """'rgb_array': ONE near-square tile (baselines' tile_images) of the first min(n, 16) envs at 720 x 960 each - not
+        of all n: 4 096 full frames would be 8 GB. 'human' raises NotImplementedError (no display)."""
+        from .render import tile_images
+        if mode == "human":
+            raise NotImplementedError("render('human'): there is no display; use 'rgb_array' or render_tensor()")
+        if mode != "rgb_array":
+            raise ValueError("render mode must be 'rgb_array' or 'human'")
+        return tile_images(np.stack(self.get_images(env_ids=list(range(min(self.num_envs, 16))))))
 
     def seed(self, seed=None):
         return [seed]  # the env is deterministic; np_random is never consumed (trex_env.py:124-126)

@@ -422,7 +422,8 @@ struct KernelArgs {
 // heavy + light: the wave that generates contacts does it for both envs one after the other, and two contact-heavy envs in one
 // workgroup leave nothing of the overlap (round 4, first form: the partner merely WAITED during the tree phases - 11.40 M against
 // 11.53 M; roles with adjacent ranks paired +1.7 % at 2048 envs, heavy + light +7.7 %; at 4096 envs, where four waves share a
-// SIMD, 11.70 M against 11.50 M). The same arithmetic per lane: BITWISE the rows of the single-env launch (scripts/state_digest.py,
+// SIMD, 11.70 M against 11.50 M). The same arithmetic per lane - the tree phases are ONE text for both forms, the single-env form
+// being the pair form's lower half alone -: BITWISE the rows of the single-env launch (scripts/state_digest.py,
 // 300 steps of 4096 envs; the test-suite compares even batches - this form - with step_many, resets and odd batches - that form).
 // WARM (the model's `warmstart` > 0; args.warm holds the per-env records, device_model.h): PGS warm start. A contact point whose hull
 // vertex was a point of the env's last solve starts its solve at warmstart x that solve's final impulses, on its three rows; every
@@ -821,12 +822,7 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
         rec[4] = make_float4(dpar0[0], dpar0[1], dpar0[2], __uint_as_float(ch4));
       }
     }
-    // (axis, parent offset, parent and depth are re-read from the record by the phases that sweep the tree)
-#define REAXIS() do { const float4 q0_ = W.body[BREC * bl], q4_ = W.body[BREC * bl + 4];                          \
-                      Sa[0] = is_joint ? q0_.x : 0.f; Sa[1] = is_joint ? q0_.y : 0.f; Sa[2] = is_joint ? q0_.z : 0.f; \
-                      dpar[0] = q4_.x; dpar[1] = q4_.y; dpar[2] = q4_.z; } while (0)
-#define RETREE() do { const int lk_ = __float_as_int(reinterpret_cast<const float *>(&W.body[BREC * bl + 3])[2]); \
-                      psrc = lk_ & 255; depth = is_body ? (lk_ >> 8) : -1; } while (0)
+    // (axis, parent offset, parent and depth are re-read from the record by the phases that sweep the tree: REAXIS, RETREE)
     if (PAIR) {   // hand this env's rotations, base twist and base height to the workgroup's LDS
       const int l_ = lane_id();
       if (l_ < TL) {
@@ -1200,344 +1196,29 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
     }   // e
     }   // contact generation (PAIR: wave 1)
     STAMP(1);
-    if (!PAIR) {
-    RELANE();
-    RETREE();
-    REAXIS();
-    }
 
     Chol6 I0c;
     float a0[6];
     float nw[3], nv[3];
-#ifndef TREX_GENERIC_TREE
-#define TREX_GENERIC_TREE 0      // diagnostic: the single-env launch through the two-env form of the tree phases (with one half)
-#endif
-    if (!PAIR && !TREX_GENERIC_TREE) {
+    if (!PAIR || wave == 0) {   // (PAIR: wave 0, for BOTH envs)
     // ================================================================ tree dynamics
-    // ---- rigid-body spatial inertia about the body origin, bias force (both straight to the body's LDS slot:
-    // the tip-to-base pass works on LDS-resident inertias), velocity-product acceleration cv (registers)
-    float cv[6];
-    {
-      Sym6 IA;
-      float pA[6];
-      const float qd = W.st[ST_QD][bl];
-      // spatial velocity of every body ABOUT ITS OWN ORIGIN for the base twist and the joint rates
-      float vel[6];
-#pragma unroll
-      for (int c = 0; c < 3; c++) { vel[c] = bw[c]; vel[3 + c] = bv[c]; }
-      for (int d = 1; d <= maxdepth; d++) {
-        float pv[6];
-#pragma unroll
-        for (int c = 0; c < 6; c++) pv[c] = wshfl(vel[c], psrc);
-        if (depth == d) {
-          float wxd[3];
-          cross3(pv, dpar, wxd);   // velocity of the parent-body point at this body's origin
-#pragma unroll
-          for (int c = 0; c < 3; c++) { vel[c] = pv[c] + Sa[c] * qd; vel[3 + c] = pv[3 + c] + wxd[c]; }
-        }
-      }
-      const TrexDeviceModel *Mi = Mo();
-      float comb[3], inb[6];
-      const float mscale = args.arr.domain ? args.arr.mass_scale[(size_t)env * TL + bl] : 1.0f;
-      const float mass = Mi->mass[bl] * mscale;
-#pragma unroll
-      for (int c = 0; c < 3; c++) comb[c] = Mi->com[c][bl];
-#pragma unroll
-      for (int c = 0; c < 6; c++) inb[c] = Mi->inertia[c][bl];
-      const float grav = Mi->prm[TP_GRAVITY], kdamp = Mi->prm[TP_LINK_DAMPING];
-      float comw[3], Icw[6];   // comw = COM offset from the body origin, world axes
-      {
-        matvec3(R, comb, comw);
-        // Ic_world = R Ib R^T (symmetric)
-        float t[9];
-        const float Ib[9] = {inb[0], inb[1], inb[2], inb[1], inb[3], inb[4], inb[2], inb[4], inb[5]};
-        matmul3(R, Ib, t);
-        const int ia[6] = {0, 0, 0, 1, 1, 2}, ib[6] = {0, 1, 2, 1, 2, 2};
-#pragma unroll
-        for (int k = 0; k < 6; k++)
-          Icw[k] = mscale * (t[3 * ia[k]] * R[3 * ib[k]] + t[3 * ia[k] + 1] * R[3 * ib[k] + 1] + t[3 * ia[k] + 2] * R[3 * ib[k] + 2]);
-      }
-      {
-        const float cc = dot3(comw, comw);
-        IA.A[0] = Icw[0] + mass * (cc - comw[0] * comw[0]);
-        IA.A[1] = Icw[1] - mass * comw[0] * comw[1];
-        IA.A[2] = Icw[2] - mass * comw[0] * comw[2];
-        IA.A[3] = Icw[3] + mass * (cc - comw[1] * comw[1]);
-        IA.A[4] = Icw[4] - mass * comw[1] * comw[2];
-        IA.A[5] = Icw[5] + mass * (cc - comw[2] * comw[2]);
-        // B = m * [c]x
-        IA.B[0] = 0.f;              IA.B[1] = -mass * comw[2];  IA.B[2] = mass * comw[1];
-        IA.B[3] = mass * comw[2];   IA.B[4] = 0.f;              IA.B[5] = -mass * comw[0];
-        IA.B[6] = -mass * comw[1];  IA.B[7] = mass * comw[0];   IA.B[8] = 0.f;
-        IA.C[0] = mass; IA.C[1] = 0.f; IA.C[2] = 0.f; IA.C[3] = mass; IA.C[4] = 0.f; IA.C[5] = mass;
-      }
-      if (!is_body) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) { IA.A[k] = (k == 0 || k == 3 || k == 5) ? 1.f : 0.f; IA.C[k] = IA.A[k]; }
-#pragma unroll
-        for (int k = 0; k < 9; k++) IA.B[k] = 0.f;
-      }
-      {
-        float h[6];
-        sym6_mul(IA, vel, h);
-        // v x* h
-        float a[3], b[3], c[3];
-        cross3(vel, h, a); cross3(vel + 3, h + 3, b); cross3(vel, h + 3, c);
-#pragma unroll
-        for (int k = 0; k < 3; k++) { pA[k] = a[k] + b[k]; pA[3 + k] = c[k]; }
-        float f[3] = {0.f, 0.f, -mass * grav}, n[3] = {0.f, 0.f, 0.f};
-        if (kdamp > 0.f) {
-          float vc[3], wxc[3], Iw[3];
-          cross3(vel, comw, wxc);
-#pragma unroll
-          for (int k = 0; k < 3; k++) vc[k] = vel[3 + k] + wxc[k];
-          const float sv = sqrtf(dot3(vc, vc)), sw = sqrtf(dot3(vel, vel));
-          sym3_mul(Icw, vel, Iw);
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-            f[k] -= mass * vc[k] * (kdamp + kdamp * sv);
-            n[k] -= Iw[k] * (kdamp + kdamp * sw);
-          }
-        }
-        float cxf[3];
-        cross3(comw, f, cxf);
-#pragma unroll
-        for (int k = 0; k < 3; k++) { pA[k] -= n[k] + cxf[k]; pA[3 + k] -= f[k]; }
-        // c = vel x (S qd), S = [Sa; 0]
-        float sq[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) sq[k] = Sa[k] * qd;
-        float x0[3], x2[3];
-        cross3(vel, sq, x0); cross3(vel + 3, sq, x2);
-#pragma unroll
-        for (int k = 0; k < 3; k++) { cv[k] = x0[k]; cv[3 + k] = x2[k]; }
-        if (!is_body) {
-#pragma unroll
-          for (int k = 0; k < 6; k++) { pA[k] = 0.f; cv[k] = 0.f; }
-        }
-      }
-      if (is_body) {
-        float *o = W.u.t.aba[bl];
-#pragma unroll
-        for (int k = 0; k < 6; k++) { o[k] = IA.A[k]; o[15 + k] = IA.C[k]; o[21 + k] = pA[k]; }
-#pragma unroll
-        for (int k = 0; k < 9; k++) o[6 + k] = IA.B[k];
-      }
-    }
-    WSYNC();
-    STAMP(2);
+    // One text for both forms, the single-env form being the pair form's lower half alone: H = the LDS of the lane's env,
+    // hoff = the first lane of its half (single-env: the wave's own LDS and 0); `PAIR ? ... : ...` where the forms differ.
+    WaveLds *H;
+    int hoff;
+    // (the tree phases' RELANE also re-derives H and hoff; in the pair form a lane of the upper half is a body of its env)
+#pragma push_macro("RELANE")
+#undef RELANE
+#define RELANE() do { lt = lane_id(); bl = lt & (TL - 1); hoff = PAIR ? (lt & TL) : 0; H = &Wpair[PAIR ? (lt >> 5) : 0];            \
+                      is_body = (PAIR ? bl : lt) < nb; is_joint = (PAIR ? bl : lt) >= 1 && (PAIR ? bl : lt) < nb; } while (0)
+#define REAXIS() do { const float4 q0_ = H->body[BREC * bl], q4_ = H->body[BREC * bl + 4];                          \
+                      Sa[0] = is_joint ? q0_.x : 0.f; Sa[1] = is_joint ? q0_.y : 0.f; Sa[2] = is_joint ? q0_.z : 0.f; \
+                      dpar[0] = q4_.x; dpar[1] = q4_.y; dpar[2] = q4_.z; } while (0)
+#define RETREE() do { const int lk_ = __float_as_int(reinterpret_cast<const float *>(&H->body[BREC * bl + 3])[2]); \
+                      psrc = lk_ & 255; depth = is_body ? (lk_ >> 8) : -1; } while (0)
     RELANE();
     RETREE();
     REAXIS();
-
-    // ---- ABA pass 2 (tip to base) on LDS-resident inertias: slot b of W.u.t.aba holds body b's rigid-body inertia
-    // (21) and bias force (6) about its own origin. Level by level, the lanes AT depth d take their slot, add
-    // what their children left in theirs (already shifted to this body's origin; fixed order), form U, 1/D, u
-    // (which go to the body record: pass 3 and the row walks read them there), remove the joint's freedom,
-    // shift to the parent's origin and put the result back for the parent. One LDS round trip and one barrier
-    // per level; nothing of this is carried in registers between levels. Level 0 is the base: it only sums.
-    {
-      const TrexDeviceModel *Mi = Mo();
-      const float tau_j = -Mi->damp[bl] * W.st[ST_QD][bl];  // explicit joint damping torque
-      for (int d = maxdepth; d >= 0; d--) {
-        if (depth == d) {
-          float *o = W.u.t.aba[bl];
-          const unsigned ch4 = __float_as_uint(reinterpret_cast<const float *>(&W.body[BREC * bl + 4])[3]);
-          float acc[27];
-          {
-            // own slot and first child's in flight together (most bodies have exactly one child)
-            const int c0 = (int)(ch4 & 255u);
-            const float *c = W.u.t.aba[c0 == 255 ? bl : c0];
-            const float w0 = c0 == 255 ? 0.f : 1.f;
-#pragma unroll
-            for (int k = 0; k < 27; k++) acc[k] = __builtin_fmaf(w0, c[k], o[k]);
-          }
-#pragma unroll 1
-          for (int kc = 1; kc < MAXCH; kc++) {   // further children, fixed order (packed without gaps)
-            const int ch = (int)((ch4 >> (8 * kc)) & 255u);
-            if (ch == 255) break;
-            const float *c = W.u.t.aba[ch];
-#pragma unroll
-            for (int k = 0; k < 27; k++) acc[k] += c[k];
-          }
-          if (d == 0) {
-#pragma unroll
-            for (int k = 0; k < 27; k++) o[k] = acc[k];
-          } else {
-            Sym6 IA;
-            float pA[6];
-#pragma unroll
-            for (int k = 0; k < 6; k++) { IA.A[k] = acc[k]; IA.C[k] = acc[15 + k]; pA[k] = acc[21 + k]; }
-#pragma unroll
-            for (int k = 0; k < 9; k++) IA.B[k] = acc[6 + k];
-            float U[6];   // U = IA S, S = [Sa; 0]
-            sym3_mul(IA.A, Sa, U);
-            U[3] = IA.B[0] * Sa[0] + IA.B[3] * Sa[1] + IA.B[6] * Sa[2];
-            U[4] = IA.B[1] * Sa[0] + IA.B[4] * Sa[1] + IA.B[7] * Sa[2];
-            U[5] = IA.B[2] * Sa[0] + IA.B[5] * Sa[1] + IA.B[8] * Sa[2];
-            const float D = dot3(Sa, U);
-            const float rD = __builtin_amdgcn_rcpf(D);
-#if TREX_ABLATE_EXACT_MATH
-            const float invD = 1.0f / D;
-#else
-            const float invD = rD * __builtin_fmaf(-D, rD, 2.0f);   // v_rcp_f32 + one Newton step (no IEEE division expansion)
-#endif
-            const float u = tau_j - dot3(Sa, pA);
-            float Ud[6];
-#pragma unroll
-            for (int k = 0; k < 6; k++) Ud[k] = U[k] * invD;
-            {
-              float4 *rec = &W.body[BREC * bl];
-              rec[0] = make_float4(Sa[0], Sa[1], Sa[2], invD);
-              rec[2] = make_float4(Ud[0], Ud[1], Ud[2], Ud[3]);
-              rec[3] = make_float4(Ud[4], Ud[5], __int_as_float(psrc + 256 * depth), u * invD);
-            }
-            {   // pa = pA + Ia c + U u / D with Ia c = IA c - U (U.c) / D
-              float Ic[6];
-              sym6_mul(IA, cv, Ic);
-              const float coef = (u - dot6(U, cv)) * invD;
-#pragma unroll
-              for (int k = 0; k < 6; k++) pA[k] += Ic[k] + U[k] * coef;
-            }
-            sym6_rank1_sub(IA, U, Ud);
-            // shift both to the parent's origin (this origin = parent origin + d, d = dpar):
-            //   n' = n + d x f,  B' = B + [d]x C,  A' = A + X^T + X', X = [d]x B^T, X' = [d]x B'^T
-            {
-              cross3_acc(dpar, pA + 3, pA[0], pA[1], pA[2]);
-              const int sidx[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
-#pragma unroll
-              for (int i = 0; i < 3; i++) {   // A_ij += X_ji = (d x row i of B)_j, j >= i
-                float t[3] = {0.f, 0.f, 0.f};
-                if (i == 0) cross3_acc(dpar, IA.B, IA.A[0], IA.A[1], IA.A[2]);
-                else if (i == 1) cross3_acc(dpar, IA.B + 3, t[0], IA.A[3], IA.A[4]);
-                else cross3_acc(dpar, IA.B + 6, t[0], t[1], IA.A[5]);
-              }
-#pragma unroll
-              for (int j = 0; j < 3; j++) {   // column j of [d]x C = d x (column j of C)
-                const float cj[3] = {IA.C[sidx[0][j]], IA.C[sidx[1][j]], IA.C[sidx[2][j]]};
-                cross3_acc(dpar, cj, IA.B[j], IA.B[3 + j], IA.B[6 + j]);
-              }
-#pragma unroll
-              for (int j = 0; j < 3; j++) {   // A_ij += X'_ij = (d x row j of B')_i, i <= j
-                float t[3] = {0.f, 0.f, 0.f};
-                if (j == 0) cross3_acc(dpar, IA.B, IA.A[0], t[1], t[2]);
-                else if (j == 1) cross3_acc(dpar, IA.B + 3, IA.A[1], IA.A[3], t[2]);
-                else cross3_acc(dpar, IA.B + 6, IA.A[2], IA.A[4], IA.A[5]);
-              }
-            }
-#pragma unroll
-            for (int k = 0; k < 6; k++) { o[k] = IA.A[k]; o[15 + k] = IA.C[k]; o[21 + k] = pA[k]; }
-#pragma unroll
-            for (int k = 0; k < 9; k++) o[6 + k] = IA.B[k];
-          }
-        }
-        WSYNC();
-      }
-      if (lt < TL && !is_joint) {   // base and unused lanes: inert records
-        float4 *rec = &W.body[BREC * lt];
-        rec[0] = make_float4(0.f, 0.f, 0.f, 0.f);
-        rec[2] = make_float4(0.f, 0.f, 0.f, 0.f);
-        rec[3] = make_float4(0.f, 0.f, __int_as_float(psrc + 256 * (depth < 0 ? 255 : depth)), 0.f);
-      }
-    }
-    STAMP(3);
-    RELANE();
-    RETREE();
-    REAXIS();
-
-    // ---- floating base: a0 = -(IA_0)^-1 pA_0; the Cholesky factor of IA_0 is wave-uniform (SGPRs)
-    {
-      const float *o = W.u.t.aba[0];   // every lane reads the same words: LDS broadcast
-      Sym6 I0;
-#pragma unroll
-      for (int k = 0; k < 6; k++) { I0.A[k] = o[k]; I0.C[k] = o[15 + k]; }
-#pragma unroll
-      for (int k = 0; k < 9; k++) I0.B[k] = o[6 + k];
-      float p0[6];
-#pragma unroll
-      for (int k = 0; k < 6; k++) p0[k] = -o[21 + k];
-      float full[36];
-      sym6_full(I0, full);
-      Chol6 c;
-      chol6_factor(full, c);
-#pragma unroll
-      for (int k = 0; k < 15; k++) I0c.l[k] = uni(c.l[k]);
-#pragma unroll
-      for (int k = 0; k < 6; k++) I0c.il[k] = uni(c.il[k]);
-      chol6_solve(I0c, p0, a0);
-#pragma unroll
-      for (int k = 0; k < 6; k++) a0[k] = uni(a0[k]);
-    }
-    // ---- ABA pass 3 (base to tip): accelerations; qdd = (u - U.a) / D = u/D - (U/D).a from the body record
-    float qdd = 0.f;
-    {
-      const float4 q2 = W.body[BREC * bl + 2], q3 = W.body[BREC * bl + 3];
-      const float Ud[6] = {q2.x, q2.y, q2.z, q2.w, q3.x, q3.y};
-      float acc[6];
-#pragma unroll
-      for (int k = 0; k < 6; k++) acc[k] = a0[k];
-      for (int d = 1; d <= maxdepth; d++) {
-        float pa[6];
-#pragma unroll
-        for (int k = 0; k < 6; k++) pa[k] = wshfl(acc[k], psrc);
-        if (depth == d) {
-          float axd[3];
-          cross3(pa, dpar, axd);   // parent acceleration seen at this body's origin
-#pragma unroll
-          for (int k = 0; k < 3; k++) pa[3 + k] += axd[k];
-#pragma unroll
-          for (int k = 0; k < 6; k++) pa[k] += cv[k];
-          qdd = q3.w - dot6(Ud, pa);
-#pragma unroll
-          for (int k = 0; k < 3; k++) acc[k] = pa[k] + Sa[k] * qdd;
-#pragma unroll
-          for (int k = 3; k < 6; k++) acc[k] = pa[k];
-        }
-      }
-    }
-    // ---- unconstrained velocity update
-    {
-      const float vmax = M->prm[TP_MAX_COORD_VEL];
-      float wxv[3];
-      cross3(bw, bv, wxv);
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        nw[k] = uni(fminf(fmaxf(bw[k] + a0[k] * dt, -vmax), vmax));
-        nv[k] = uni(fminf(fmaxf(bv[k] + (a0[3 + k] + wxv[k]) * dt, -vmax), vmax));
-      }
-      const float nqd = is_joint ? fminf(fmaxf(W.st[ST_QD][bl] + qdd * dt, -vmax), vmax) : 0.f;
-      // ---- the last thing the row walks need of a body: its updated joint rate
-      if (lt < TL) {
-        reinterpret_cast<float *>(&W.body[BREC * lt + 1])[3] = nqd;
-        W.st[ST_NQD][lt] = nqd;
-      }
-      if (DEBUG && args.debug && wg == 0) {
-        float *D = args.debug;
-        if (lt < TL) { D[lt] = qdd; D[64 + lt] = nqd; }
-#pragma unroll
-        for (int k = 0; k < 6; k++)
-          if (lt == k) D[32 + k] = a0[k];
-        if (lt == 0) {
-          for (int k = 0; k < 3; k++) { D[64 + nb + k] = nw[k]; D[64 + nb + 3 + k] = nv[k]; }
-        }
-      }
-    }
-    } else {
-      if (wave == 0) {
-        // ... which runs the lane-per-body phases for BOTH: H = the LDS of the lane's half, hoff = its first lane
-        WaveLds *H;
-        int hoff;
-#define RELANE2() do { lt = lane_id(); bl = lt & (TL - 1); hoff = PAIR ? (lt & TL) : 0; H = &Wpair[PAIR ? (lt >> 5) : 0];            \
-                       is_body = (PAIR ? bl : lt) < nb; is_joint = (PAIR ? bl : lt) >= 1 && (PAIR ? bl : lt) < nb; } while (0)
-#define REAXIS2() do { const float4 q0_ = H->body[BREC * bl], q4_ = H->body[BREC * bl + 4];                          \
-                       Sa[0] = is_joint ? q0_.x : 0.f; Sa[1] = is_joint ? q0_.y : 0.f; Sa[2] = is_joint ? q0_.z : 0.f; \
-                       dpar[0] = q4_.x; dpar[1] = q4_.y; dpar[2] = q4_.z; } while (0)
-#define RETREE2() do { const int lk_ = __float_as_int(reinterpret_cast<const float *>(&H->body[BREC * bl + 3])[2]); \
-                       psrc = lk_ & 255; depth = is_body ? (lk_ >> 8) : -1; } while (0)
-        RELANE2();
-        RETREE2();
-        REAXIS2();
-    // ================================================================ tree dynamics
     // ---- rigid-body spatial inertia about the body origin, bias force (both straight to the body's LDS slot:
     // the tip-to-base pass works on LDS-resident inertias), velocity-product acceleration cv (registers)
     float cv[6];
@@ -1548,7 +1229,7 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
       // spatial velocity of every body ABOUT ITS OWN ORIGIN for the base twist and the joint rates
       float vel[6];
 #pragma unroll
-      for (int c = 0; c < 3; c++) { vel[c] = H->xch[c]; vel[3 + c] = H->xch[3 + c]; }
+      for (int c = 0; c < 3; c++) { vel[c] = PAIR ? H->xch[c] : bw[c]; vel[3 + c] = PAIR ? H->xch[3 + c] : bv[c]; }
       for (int d = 1; d <= maxdepth; d++) {
         float pv[6];
 #pragma unroll
@@ -1560,12 +1241,12 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
           for (int c = 0; c < 3; c++) { vel[c] = pv[c] + Sa[c] * qd; vel[3 + c] = pv[3 + c] + wxd[c]; }
         }
       }
-      float Rh[9];
+      float Rh[9];   // the body's rotation (pair: from the table in LDS)
 #pragma unroll
-      for (int c = 0; c < 9; c++) Rh[c] = H->u.t.rtab[bl][c];
+      for (int c = 0; c < 9; c++) Rh[c] = PAIR ? H->u.t.rtab[bl][c] : R[c];
       const TrexDeviceModel *Mi = Mo();
       float comb[3], inb[6];
-      const float mscale = args.arr.domain ? args.arr.mass_scale[(size_t)__float_as_int(H->xch[6]) * TL + bl] : 1.0f;
+      const float mscale = args.arr.domain ? args.arr.mass_scale[(size_t)(PAIR ? __float_as_int(H->xch[6]) : env) * TL + bl] : 1.0f;
       const float mass = Mi->mass[bl] * mscale;
 #pragma unroll
       for (int c = 0; c < 3; c++) comb[c] = Mi->com[c][bl];
@@ -1652,9 +1333,10 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
       }
     }
     WSYNC();
-    RELANE2();
-    RETREE2();
-    REAXIS2();
+    if (!PAIR) STAMP(2);
+    RELANE();
+    RETREE();
+    REAXIS();
 
     // ---- ABA pass 2 (tip to base) on LDS-resident inertias: slot b of H->u.t.aba holds body b's rigid-body inertia
     // (21) and bias force (6) about its own origin. Level by level, the lanes AT depth d take their slot, add
@@ -1760,21 +1442,23 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
         WSYNC();
       }
       if ((PAIR || lt < TL) && !is_joint) {   // base and unused lanes: inert records
-        float4 *rec = &H->body[BREC * bl];
+        float4 *rec = &H->body[BREC * (PAIR ? bl : lt)];
         rec[0] = make_float4(0.f, 0.f, 0.f, 0.f);
         rec[2] = make_float4(0.f, 0.f, 0.f, 0.f);
         rec[3] = make_float4(0.f, 0.f, __int_as_float(psrc + 256 * (depth < 0 ? 255 : depth)), 0.f);
       }
     }
-    RELANE2();
-    RETREE2();
-    REAXIS2();
+    if (!PAIR) STAMP(3);
+    RELANE();
+    RETREE();
+    REAXIS();
 
-    // ---- floating base: a0 = -(IA_0)^-1 pA_0; every lane of a half factors its env's matrix (the same arithmetic on the
-    // same words); lane 0 of the half hands the factor and a0 to the env's own wave
-    float a0h[6];
+    // ---- floating base: a0 = -(IA_0)^-1 pA_0. Single-env: the Cholesky factor of IA_0 is wave-uniform (SGPRs). Pair: every
+    // lane of a half factors its env's matrix (the same arithmetic on the same words); lane 0 of the half hands the factor and
+    // a0 to the env's own wave
+    float a0h[6];   // (pair) the a0 of the lane's env
     {
-      const float *o = H->u.t.aba[0];
+      const float *o = H->u.t.aba[0];   // every lane reads the same words of its env: LDS broadcast
       Sym6 I0;
 #pragma unroll
       for (int k = 0; k < 6; k++) { I0.A[k] = o[k]; I0.C[k] = o[15 + k]; }
@@ -1787,13 +1471,23 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
       sym6_full(I0, full);
       Chol6 c;
       chol6_factor(full, c);
-      chol6_solve(c, p0, a0h);
-      if (bl == 0) {
-        float *x = H->xch + 8;
+      if constexpr (PAIR) {
+        chol6_solve(c, p0, a0h);
+        if (bl == 0) {
+          float *x = H->xch + 8;
 #pragma unroll
-        for (int k = 0; k < 15; k++) x[k] = c.l[k];
+          for (int k = 0; k < 15; k++) x[k] = c.l[k];
 #pragma unroll
-        for (int k = 0; k < 6; k++) { x[15 + k] = c.il[k]; x[21 + k] = a0h[k]; }
+          for (int k = 0; k < 6; k++) { x[15 + k] = c.il[k]; x[21 + k] = a0h[k]; }
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 15; k++) I0c.l[k] = uni(c.l[k]);
+#pragma unroll
+        for (int k = 0; k < 6; k++) I0c.il[k] = uni(c.il[k]);
+        chol6_solve(I0c, p0, a0);
+#pragma unroll
+        for (int k = 0; k < 6; k++) a0[k] = uni(a0[k]);
       }
     }
     // ---- ABA pass 3 (base to tip): accelerations; qdd = (u - U.a) / D = u/D - (U/D).a from the body record
@@ -1803,7 +1497,7 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
       const float Ud[6] = {q2.x, q2.y, q2.z, q2.w, q3.x, q3.y};
       float acc[6];
 #pragma unroll
-      for (int k = 0; k < 6; k++) acc[k] = a0h[k];
+      for (int k = 0; k < 6; k++) acc[k] = PAIR ? a0h[k] : a0[k];
       for (int d = 1; d <= maxdepth; d++) {
         float pa[6];
 #pragma unroll
@@ -1823,20 +1517,41 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
         }
       }
     }
-    // ---- unconstrained joint rates of both envs (each wave forms its own base twist below)
+    // ---- unconstrained velocity update (pair: the joint rates of both envs; each wave forms its own base twist below)
     {
       const float vmax = M->prm[TP_MAX_COORD_VEL];
+      if constexpr (!PAIR) {
+        float wxv[3];
+        cross3(bw, bv, wxv);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          nw[k] = uni(fminf(fmaxf(bw[k] + a0[k] * dt, -vmax), vmax));
+          nv[k] = uni(fminf(fmaxf(bv[k] + (a0[3 + k] + wxv[k]) * dt, -vmax), vmax));
+        }
+      }
       const float nqd = is_joint ? fminf(fmaxf(H->st[ST_QD][bl] + qdd * dt, -vmax), vmax) : 0.f;
+      // ---- the last thing the row walks need of a body: its updated joint rate
       if (PAIR || lt < TL) {
-        reinterpret_cast<float *>(&H->body[BREC * bl + 1])[3] = nqd;
-        H->st[ST_NQD][bl] = nqd;
+        reinterpret_cast<float *>(&H->body[BREC * (PAIR ? bl : lt) + 1])[3] = nqd;
+        H->st[ST_NQD][PAIR ? bl : lt] = nqd;
+      }
+      if (DEBUG && args.debug && wg == 0) {
+        float *D = args.debug;
+        if (lt < TL) { D[lt] = qdd; D[64 + lt] = nqd; }
+#pragma unroll
+        for (int k = 0; k < 6; k++)
+          if (lt == k) D[32 + k] = a0[k];
+        if (lt == 0) {
+          for (int k = 0; k < 3; k++) { D[64 + nb + k] = nw[k]; D[64 + nb + 3 + k] = nv[k]; }
+        }
       }
     }
-#undef RELANE2
-#undef REAXIS2
-#undef RETREE2
-      }
-      if (PAIR) { SUBSTAMP(17); __syncthreads(); SUBSTAMP(18); } else WSYNC();      // records (U/D, 1/D, u/D, updated rates), base factor and base acceleration are in LDS
+#undef REAXIS
+#undef RETREE
+#pragma pop_macro("RELANE")
+    }   // tree dynamics (PAIR: wave 0)
+    if (PAIR) {
+      SUBSTAMP(17); __syncthreads(); SUBSTAMP(18);      // records (U/D, 1/D, u/D, updated rates), base factor and base acceleration are in LDS
       if (act) {
         nc = uni(__float_as_int(W.xch[35]));
         const float *x = W.xch + 8;      // (every lane reads the same words: LDS broadcast)
@@ -2551,8 +2266,6 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
     STAMP(8);
     }   // act (rows, sweeps, integration)
 #undef RELANE
-#undef RETREE
-#undef REAXIS
 #undef REROW
   }
 
@@ -2825,6 +2538,9 @@ __global__ void trex_copy_mass_scale_kernel(const float *src, float *dst, int n,
 }
 
 // ---------------------------------------------------------------- host launchers (called by capi.cpp)
+// the step launch of a batch of n envs takes the pair form (two envs per workgroup) for an even batch that is resident at once
+static bool trex_pair_launch(int n) { return TREX_PAIR_LAUNCH && (n & 1) == 0 && n <= TREX_PAIR_MAX; }
+
 extern "C" {
 
 hipError_t trex_launch_step(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions,
@@ -2837,23 +2553,17 @@ hipError_t trex_launch_step(const TrexDeviceModel *model, TrexBatchArrays arr, i
   KernelArgs a{model, arr, n, actions, obs, reward, done, done_f, obs_stride, scal_stride, penalties, nullptr, perm, wd, we, wk, debug,
                1, 0, pen_in_rows, warm};
 
-  const bool pair = TREX_PAIR_LAUNCH && (n & 1) == 0 && n <= TREX_PAIR_MAX;
-#if TREX_STAMPS   // diagnostic build: the PRODUCT instantiation, stamped (the dump of <false, true> would change its code)
-  if (warm) {
-    if (pair) hipLaunchKernelGGL(trex_step_pair_warm_kernel, dim3(n / 2), dim3(128), 0, stream, a);
-    else hipLaunchKernelGGL(trex_step_warm_kernel<false>, dim3(n), dim3(64), 0, stream, a);
-  } else if (pair) hipLaunchKernelGGL(trex_step_pair_kernel, dim3(n / 2), dim3(128), 0, stream, a);
-  else hipLaunchKernelGGL((trex_step_kernel<false, false>), dim3(n), dim3(64), 0, stream, a);
-#else
-  if (debug) {   // (capi.cpp refuses a diagnostics step of a warm batch: this instantiation has no record)
+  const bool pair = trex_pair_launch(n);
+  // the stamped diagnostic build launches the PRODUCT instantiation, stamped, for a debug pointer too (the dump of
+  // <false, true> would change its code; `if constexpr`: that build does not instantiate <false, true> at all)
+  if (debug && !TREX_STAMPS) {   // (capi.cpp refuses a diagnostics step of a warm batch: this instantiation has no record)
     if (warm) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((trex_step_kernel<false, true>), dim3(n), dim3(64), 0, stream, a);
+    if constexpr (!TREX_STAMPS) hipLaunchKernelGGL((trex_step_kernel<false, true>), dim3(n), dim3(64), 0, stream, a);
   } else if (warm) {
     if (pair) hipLaunchKernelGGL(trex_step_pair_warm_kernel, dim3(n / 2), dim3(128), 0, stream, a);
     else hipLaunchKernelGGL(trex_step_warm_kernel<false>, dim3(n), dim3(64), 0, stream, a);
   } else if (pair) hipLaunchKernelGGL(trex_step_pair_kernel, dim3(n / 2), dim3(128), 0, stream, a);
   else hipLaunchKernelGGL((trex_step_kernel<false, false>), dim3(n), dim3(64), 0, stream, a);
-#endif
   return hipGetLastError();
 }
 
@@ -2922,9 +2632,8 @@ hipError_t trex_launch_copy_mass_scale(const float *src, float *dst, int n, int 
   return hipGetLastError();
 }
 
-// launch shape of the step launch for a batch of n envs (trex_batch_launch_info): two envs per workgroup - the pair form - for an
-// even batch that is resident at once, one otherwise
-int trex_step_envs_per_workgroup(int n) { return (TREX_PAIR_LAUNCH && (n & 1) == 0 && n <= TREX_PAIR_MAX) ? 2 : 1; }
+// launch shape of the step launch for a batch of n envs (trex_batch_launch_info)
+int trex_step_envs_per_workgroup(int n) { return trex_pair_launch(n) ? 2 : 1; }
 int trex_step_lds_bytes(int n) { return trex_step_envs_per_workgroup(n) == 2 ? (int)(2 * sizeof(WaveLds) + sizeof(CgLds)) : (int)sizeof(WaveLds); }
 int trex_step_warm_lds_bytes(void) { return (int)(MAXC * sizeof(float4)); }   // per env, on top of the above in the warm kernels
 

@@ -269,6 +269,25 @@ int trex_batch_render(TrexBatch *batch, const TrexCamera *camera, int width, int
 int trex_batch_set_domain(TrexBatch *batch, const float *mass_scale_dev, const float *friction_dev,
                           void *stream);
 
+/* External wrench per env and moving body, world frame: wrench_dev [N, num_bodies, 6] f32 = fx fy fz (N) at the
+ * body's centre of mass, tx ty tz (N m) about it. NULL clears it. (pybullet's applyExternalForce / applyExternalTorque;
+ * no reference counterpart: pushes, perturbations, load cases.)
+ *   - the values are COPIED on `stream` into a batch-owned buffer (allocated at the first non-NULL call: a batch that never
+ *     sets a wrench allocates nothing) and stay in force until the next call replaces them or NULL clears them; resets,
+ *     trex_batch_set_state and trex_batch_set_domain do not clear them;
+ *   - they act, held constant, on EVERY SUBSTEP of every env-step of trex_batch_step, _step_rows, _step_many (all S steps) and
+ *     _time_steps. pybullet's applyExternalForce lasts one stepSimulation - ONE substep here -: this call holds the wrench
+ *     for the whole env-step (substeps x dt seconds);
+ *   - they do NOT act on a reset's settle substep: trex_batch_reset / _reset_rows, and the settle substep of an
+ *     episode-limit reset inside a step launch - the first observation of an episode never depends on the wrench;
+ *   - values are not validated: a non-finite value in an env's wrench makes that env non-finite, and containment handles it
+ *     (done = 1, reward 0, start pose - at every step while the value stays); no other env is affected;
+ *   - trex_batch_debug_step returns TREX_E_INVALID while a wrench is set;
+ *   - a buffer shorter than N * num_bodies * 6 floats, host memory or another device's memory returns TREX_E_INVALID
+ *     before anything is launched.
+ * While a wrench is set the step launches run separate kernel instantiations; after NULL the default kernels again. */
+int trex_batch_set_external_wrench(TrexBatch *batch, const float *wrench_dev, void *stream);
+
 /* diagnostics of the last substep: contact count per env [N] i32 (nullable), summed normal
  * impulse per env [N] f32 (nullable). */
 int trex_batch_contact_stats(TrexBatch *batch, int32_t *count_dev, float *normal_impulse_dev, void *stream);

@@ -17,11 +17,12 @@
 
 extern "C" {
 hipError_t trex_launch_step(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, float *, uint8_t *,
-                            float *, float, float, float, float *, hipStream_t, float *, int, int, int, int, float *);
+                            float *, float, float, float, float *, hipStream_t, float *, int, int, int, int, float *,
+                            const float *);
 hipError_t trex_launch_reset(const TrexDeviceModel *, TrexBatchArrays, int, const uint8_t *, float *, float, float,
                              float, float *, hipStream_t, int, float *, float *, int, int, int, float *);
 hipError_t trex_launch_step_many(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, int, int, float *, uint8_t *,
-                                 float, float, float, hipStream_t, int, int, int, float *);
+                                 float, float, float, hipStream_t, int, int, int, float *, const float *);
 hipError_t trex_launch_pack_state(const TrexDeviceModel *, TrexBatchArrays, int, float *, int, hipStream_t);
 hipError_t trex_launch_head(const TrexDeviceModel *, TrexBatchArrays, int, float *, hipStream_t);
 hipError_t trex_launch_link_transforms(const TrexDeviceModel *, TrexBatchArrays, int, float *, hipStream_t, int);
@@ -30,6 +31,7 @@ hipError_t trex_launch_scalars_get(TrexBatchArrays, int, int32_t *, float *, int
 hipError_t trex_launch_scalars_set(TrexBatchArrays, int, const int32_t *, int, int, hipStream_t);
 hipError_t trex_launch_fill_u8(uint8_t *, uint8_t, int, hipStream_t);
 hipError_t trex_launch_copy_mass_scale(const float *, float *, int, int, hipStream_t);
+hipError_t trex_launch_copy_wrench(const float *, float *, int, int, hipStream_t);
 int trex_step_lds_bytes(int);
 int trex_step_envs_per_workgroup(int);
 int trex_step_warm_lds_bytes(void);
@@ -45,6 +47,9 @@ struct TrexBatch {
   TrexDeviceModel *dmodel = nullptr;
   TrexBatchArrays arr{};
   float *warm = nullptr;                       // PGS warm-start records [n][TREX_WARM_WORDS] (device_model.h); warmstart > 0 only
+  float *ext = nullptr;                        // external wrench [n][6][TREX_TL] (trex_batch_set_external_wrench); first non-NULL call on
+  bool ext_on = false;                         // set: the step launches take the EXT kernels
+  const float *wrench() const { return ext_on ? ext : nullptr; }
   float wd = 1.0f, we = 0.005f, wk = 0.002f;  // trex_env.py:42-44
   bool pen_in_rows = false;                    // trex_batch_set_penalties_in_rows
   int balance_mode = -1;                       // trex_batch_set_wave_balance: -1 auto, 0 off, 1 on
@@ -572,7 +577,7 @@ int trex_batch_step(TrexBatch *b, const float *actions_dev, float *obs_dev, floa
   BUF_TRY(done_dev, n, "trex_batch_step: done");
   BUF_TRY(penalties_dev, n * 3 * sizeof(float), "trex_batch_step: penalties");
   HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, reward_dev, done_dev, penalties_dev, b->wd,
-                           b->we, b->wk, nullptr, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm));
+                           b->we, b->wk, nullptr, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, b->wrench()));
   return TREX_OK;
 }
 
@@ -589,7 +594,8 @@ int trex_batch_step_rows(TrexBatch *b, const float *actions_dev, float *rows_dev
   BUF_TRY(done_dev, n, "trex_batch_step_rows: done");
   float *rew = rows_dev + 3 * b->nj;
   HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, rows_dev, rew, done_dev, penalties_dev, b->wd, b->we,
-                           b->wk, nullptr, (hipStream_t)stream, rew + 1, row_stride, row_stride, b->balance(), b->pen_in_rows ? 1 : 0, b->warm));
+                           b->wk, nullptr, (hipStream_t)stream, rew + 1, row_stride, row_stride, b->balance(), b->pen_in_rows ? 1 : 0, b->warm,
+                           b->wrench()));
   return TREX_OK;
 }
 
@@ -606,7 +612,8 @@ int trex_batch_step_many(TrexBatch *b, const float *actions_dev, float *rows_dev
   BUF_TRY(penalties_dev, S * n * 3 * sizeof(float), "trex_batch_step_many: penalties");
   BUF_TRY(done_dev, S * n, "trex_batch_step_many: done");
   HIP_TRY(trex_launch_step_many(b->dmodel, b->arr, b->n, actions_dev, rows_dev, row_stride, num_steps, penalties_dev, done_dev,
-                                b->wd, b->we, b->wk, (hipStream_t)stream, b->balance(), b->nj, b->pen_in_rows ? 1 : 0, b->warm));
+                                b->wd, b->we, b->wk, (hipStream_t)stream, b->balance(), b->nj, b->pen_in_rows ? 1 : 0, b->warm,
+                                b->wrench()));
   return TREX_OK;
 }
 
@@ -619,8 +626,10 @@ int trex_batch_debug_step(TrexBatch *b, const float *actions_dev, float *obs_dev
   BUF_TRY(debug_dev, 4096 * sizeof(float), "trex_batch_debug_step: debug");   // (diagnostic builds: 4096 + 16 N)
   if (b->warm)   // (the diagnostics instantiation has no warm-start record: it would step cold without saying so)
     return fail(TREX_E_INVALID, "trex_batch_debug_step: not available for a batch with warmstart > 0");
+  if (b->ext_on)   // (nor an external wrench)
+    return fail(TREX_E_INVALID, "trex_batch_debug_step: not available while an external wrench is set");
   HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, nullptr, nullptr, nullptr, b->wd, b->we, b->wk,
-                           debug_dev, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm));
+                           debug_dev, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, nullptr));
   return TREX_OK;
 }
 
@@ -725,6 +734,22 @@ int trex_batch_set_domain(TrexBatch *b, const float *mass_scale_dev, const float
   return TREX_OK;
 }
 
+int trex_batch_set_external_wrench(TrexBatch *b, const float *wrench_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!wrench_dev) { b->ext_on = false; return TREX_OK; }   // the default kernels again; the buffer stays for the next call
+  DeviceGuard guard(b->device);
+  BUF_TRY(wrench_dev, (size_t)b->n * b->nb * 6 * sizeof(float), "trex_batch_set_external_wrench: wrench");
+  if (!b->ext) {   // first use: a batch that never sets a wrench allocates nothing
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, (size_t)b->n * 6 * TREX_TL * sizeof(float)));
+    b->allocs.push_back(p);
+    b->ext = (float *)p;
+  }
+  HIP_TRY(trex_launch_copy_wrench(wrench_dev, b->ext, b->n, b->nb, (hipStream_t)stream));
+  b->ext_on = true;
+  return TREX_OK;
+}
+
 int trex_batch_contact_stats(TrexBatch *b, int32_t *count_dev, float *normal_impulse_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
   DeviceGuard guard(b->device);
@@ -762,7 +787,7 @@ int trex_batch_time_steps(TrexBatch *b, const float *actions_dev, float *obs_dev
   HIP_TRY(hipEventRecord(e0, s));
   for (int i = 0; i < steps; i++)
     HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, reward_dev, done_dev, nullptr, b->wd, b->we,
-                             b->wk, nullptr, s, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm));
+                             b->wk, nullptr, s, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, b->wrench()));
   HIP_TRY(hipEventRecord(e1, s));
   HIP_TRY(hipEventSynchronize(e1));
   float ms = 0.f;

@@ -394,6 +394,8 @@ struct KernelArgs {
   int pen_in_rows;        // row-block launches of a batch with trex_batch_set_penalties_in_rows: the three penalties follow done in the row
   float *warm;            // WARM launches: the per-env warm-start records [N][TREX_WARM_WORDS] (device_model.h); last, so that
                           // every other argument keeps its offset
+  const float *ext;       // EXT launches: the per-env external wrench [N][6][TREX_TL] (fx fy fz tx ty tz, world axes, at / about the
+                          // body's COM; trex_batch_set_external_wrench); after warm for the same reason
 };
 
 }  // namespace
@@ -431,11 +433,17 @@ struct KernelArgs {
 // substep's contact generation overwrites) for the whole launch: loaded from the env's row at the start, rewritten by every solve,
 // emptied by a reset (launch, episode limit, containment), stored at the end. Separate instantiations: the kernels without it are
 // the code they were.
+// EXT (the batch holds an external wrench, trex_batch_set_external_wrench; args.ext): every body lane adds its env's force and torque
+// to the bias force of its COM - f = (0, 0, -m g) + F, n = T, before the damping terms and the moment c x f - on every substep of
+// the env-step, never on the settle substep of an episode-limit reset (sub == n_sub). Loaded from global memory at the top of the
+// tree block (no LDS: the pair workgroup's is spent), one coalesced row per component. Non-RESET product launches only; with
+// F = T = 0 every added term is an exact x + 0, so an all-zero wrench gives the rows of the kernels without it.
 #define WSYNC() do { if (PAIR) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); else __syncthreads(); } while (0)
-template <bool RESET, bool DEBUG, bool MULTI, bool PAIR = false, bool WARM = false>
+template <bool RESET, bool DEBUG, bool MULTI, bool PAIR = false, bool WARM = false, bool EXT = false>
 __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int wg_in) {   // wg_in: blockIdx.x
   static_assert(!PAIR || (!RESET && !DEBUG && !MULTI), "the pair form exists for the product step launch only");
   static_assert(!(WARM && DEBUG), "the diagnostics dump has no warm-start form");
+  static_assert(!EXT || (!RESET && !DEBUG), "the external wrench exists for the product step launches only");
   __shared__ WaveLds Wpair[PAIR ? 2 : 1];
   __shared__ __attribute__((aligned(16))) unsigned char Gpair[PAIR ? sizeof(CgLds) : 16];   // PAIR: contact-generation scratch of the workgroup (wave 1)
   const int wave = PAIR ? uni((int)threadIdx.x >> 6) : 0;
@@ -730,6 +738,12 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
     for (int k = 0; k < 3; k++) badl |= !(fabsf(pos[k]) < 3.0e38f) || !(fabsf(bv[k]) < 3.0e38f) || !(fabsf(bw[k]) < 3.0e38f);
 #pragma unroll
     for (int k = 0; k < 4; k++) badl |= !(fabsf(quat[k]) < 3.0e38f);
+    if constexpr (EXT) {   // a non-finite wrench counts as a non-finite state (the solver's clamps could otherwise absorb it;
+                           // `if constexpr`: the default kernels' lambda captures nothing new)
+      const float *xw = args.ext + (size_t)env * (6 * TL) + bl;
+#pragma unroll
+      for (int c = 0; c < 6; c++) badl |= is_body && !(fabsf(xw[c * TL]) < 3.0e38f);
+    }
     env_bad = bad || (__ballot(badl) != 0ull);
   };
   auto to_start_pose = [&]() {
@@ -1219,6 +1233,14 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
     RELANE();
     RETREE();
     REAXIS();
+    // EXT: this body's external force and torque (world axes, at / about its COM), issued here so that the loads hide behind
+    // the velocity pass; zero on the settle substep of an episode-limit reset
+    float fext[3] = {0.f, 0.f, 0.f}, text[3] = {0.f, 0.f, 0.f};
+    if (EXT && sub < n_sub) {
+      const float *xw = args.ext + (size_t)(PAIR ? __float_as_int(H->xch[6]) : env) * (6 * TL) + bl;
+#pragma unroll
+      for (int c = 0; c < 3; c++) { fext[c] = xw[c * TL]; text[c] = xw[(3 + c) * TL]; }
+    }
     // ---- rigid-body spatial inertia about the body origin, bias force (both straight to the body's LDS slot:
     // the tip-to-base pass works on LDS-resident inertias), velocity-product acceleration cv (registers)
     float cv[6];
@@ -1294,6 +1316,10 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
 #pragma unroll
         for (int k = 0; k < 3; k++) { pA[k] = a[k] + b[k]; pA[3 + k] = c[k]; }
         float f[3] = {0.f, 0.f, -mass * grav}, n[3] = {0.f, 0.f, 0.f};
+        if (EXT) {
+#pragma unroll
+          for (int k = 0; k < 3; k++) { f[k] += fext[k]; n[k] += text[k]; }
+        }
         if (kdamp > 0.f) {
           float vc[3], wxc[3], Iw[3];
           cross3(vel, comw, wxc);
@@ -2373,6 +2399,14 @@ template <bool RESET>
 __global__ __launch_bounds__(64, 4) void trex_step_warm_kernel(KernelArgs args) { trex_step_body<RESET, false, false, false, true>(args, (int)blockIdx.x); }
 __global__ __launch_bounds__(128, 4) void trex_step_pair_warm_kernel(KernelArgs args) { trex_step_body<false, false, false, true, true>(args, (int)blockIdx.x); }
 __global__ __launch_bounds__(64, 4) void trex_step_many_warm_kernel(KernelArgs args) { trex_step_body<false, false, true, false, true>(args, (int)blockIdx.x); }
+// the same product launches with the external wrench (EXT above): chosen on the host for a batch that holds one (templates: the
+// stamped diagnostic build, which launches none of them, instantiates none)
+template <bool WARM>
+__global__ __launch_bounds__(64, 4) void trex_step_ext_kernel(KernelArgs args) { trex_step_body<false, false, false, false, WARM, true>(args, (int)blockIdx.x); }
+template <bool WARM>
+__global__ __launch_bounds__(128, 4) void trex_step_pair_ext_kernel(KernelArgs args) { trex_step_body<false, false, false, true, WARM, true>(args, (int)blockIdx.x); }
+template <bool WARM>
+__global__ __launch_bounds__(64, 4) void trex_step_many_ext_kernel(KernelArgs args) { trex_step_body<false, false, true, false, WARM, true>(args, (int)blockIdx.x); }
 
 // ---------------------------------------------------------------- small utility kernels
 __global__ void trex_pack_state_kernel(const TrexDeviceModel *M, TrexBatchArrays arr, int n, float *out, int pack) {
@@ -2536,6 +2570,13 @@ __global__ void trex_copy_mass_scale_kernel(const float *src, float *dst, int n,
   const int e = i / TL, l = i % TL;
   dst[i] = l < nb ? src[e * nb + l] : 1.0f;
 }
+__global__ void trex_copy_wrench_kernel(const float *src, float *dst, int n, int nb) {
+  // [N, nb, 6] -> [N, 6, 32] (component-major: the step's body lanes load one coalesced row per component)
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * 6 * TL) return;
+  const int e = i / (6 * TL), c = (i / TL) % 6, l = i % TL;
+  dst[i] = l < nb ? src[((size_t)e * nb + l) * 6 + c] : 0.0f;
+}
 
 // ---------------------------------------------------------------- host launchers (called by capi.cpp)
 // the step launch of a batch of n envs takes the pair form (two envs per workgroup) for an even batch that is resident at once
@@ -2546,14 +2587,27 @@ extern "C" {
 hipError_t trex_launch_step(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions,
                             float *obs, float *reward, uint8_t *done, float *penalties, float wd, float we,
                             float wk, float *debug, hipStream_t stream, float *done_f, int obs_stride, int scal_stride,
-                            int balance, int pen_in_rows, float *warm) {
+                            int balance, int pen_in_rows, float *warm, const float *ext) {
   // balance: the env-to-wave assignment by contact rank (trex_batch_set_wave_balance decides; capi.cpp). Diagnostics
   // launches keep env k in workgroup k (the stamped build is balanced like the product: it reports the env of every wave)
   int32_t *perm = ((debug && !TREX_STAMPS) || !balance) ? nullptr : arr.balance;
   KernelArgs a{model, arr, n, actions, obs, reward, done, done_f, obs_stride, scal_stride, penalties, nullptr, perm, wd, we, wk, debug,
-               1, 0, pen_in_rows, warm};
+               1, 0, pen_in_rows, warm, ext};
 
   const bool pair = trex_pair_launch(n);
+  if (ext) {   // (capi.cpp refuses a diagnostics step of a batch with a wrench; the stamped build has no EXT instantiations)
+    if (debug || TREX_STAMPS) return hipErrorInvalidValue;
+    if constexpr (!TREX_STAMPS) {
+      if (pair) {
+        if (warm) hipLaunchKernelGGL(trex_step_pair_ext_kernel<true>, dim3(n / 2), dim3(128), 0, stream, a);
+        else hipLaunchKernelGGL(trex_step_pair_ext_kernel<false>, dim3(n / 2), dim3(128), 0, stream, a);
+      } else {
+        if (warm) hipLaunchKernelGGL(trex_step_ext_kernel<true>, dim3(n), dim3(64), 0, stream, a);
+        else hipLaunchKernelGGL(trex_step_ext_kernel<false>, dim3(n), dim3(64), 0, stream, a);
+      }
+    }
+    return hipGetLastError();
+  }
   // the stamped diagnostic build launches the PRODUCT instantiation, stamped, for a debug pointer too (the dump of
   // <false, true> would change its code; `if constexpr`: that build does not instantiate <false, true> at all)
   if (debug && !TREX_STAMPS) {   // (capi.cpp refuses a diagnostics step of a warm batch: this instantiation has no record)
@@ -2571,11 +2625,17 @@ hipError_t trex_launch_step(const TrexDeviceModel *model, TrexBatchArrays arr, i
 // penalties [S, N, 3] and done bytes [S, N] nullable
 hipError_t trex_launch_step_many(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions, float *rows,
                                  int row_stride, int n_steps, float *penalties, uint8_t *done, float wd, float we, float wk,
-                                 hipStream_t stream, int balance, int nj, int pen_in_rows, float *warm) {
+                                 hipStream_t stream, int balance, int nj, int pen_in_rows, float *warm, const float *ext) {
   float *rew = rows + 3 * nj;
   KernelArgs a{model, arr, n, actions, rows, rew, done, rew + 1, row_stride, row_stride, penalties, nullptr,
-               balance ? arr.balance : nullptr, wd, we, wk, nullptr, n_steps, (long long)n * row_stride, pen_in_rows, warm};
-  if (warm) hipLaunchKernelGGL(trex_step_many_warm_kernel, dim3(n), dim3(64), 0, stream, a);
+               balance ? arr.balance : nullptr, wd, we, wk, nullptr, n_steps, (long long)n * row_stride, pen_in_rows, warm, ext};
+  if (ext) {
+    if (TREX_STAMPS) return hipErrorInvalidValue;
+    if constexpr (!TREX_STAMPS) {
+      if (warm) hipLaunchKernelGGL(trex_step_many_ext_kernel<true>, dim3(n), dim3(64), 0, stream, a);
+      else hipLaunchKernelGGL(trex_step_many_ext_kernel<false>, dim3(n), dim3(64), 0, stream, a);
+    }
+  } else if (warm) hipLaunchKernelGGL(trex_step_many_warm_kernel, dim3(n), dim3(64), 0, stream, a);
   else hipLaunchKernelGGL(trex_step_many_kernel, dim3(n), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
@@ -2584,7 +2644,7 @@ hipError_t trex_launch_reset(const TrexDeviceModel *model, TrexBatchArrays arr, 
                              float *obs, float wd, float we, float wk, float *debug, hipStream_t stream, int obs_stride,
                              float *reward, float *done_f, int scal_stride, int nj, int pen_in_rows, float *warm) {
   KernelArgs a{model, arr, n, nullptr, obs, reward, nullptr, done_f, obs_stride, scal_stride, nullptr, mask, nullptr, wd, we, wk, debug,
-               1, 0, (reward && done_f && pen_in_rows) ? 1 : 0, warm};
+               1, 0, (reward && done_f && pen_in_rows) ? 1 : 0, warm, nullptr};
   if (warm) hipLaunchKernelGGL(trex_step_warm_kernel<true>, dim3(n), dim3(64), 0, stream, a);
   else hipLaunchKernelGGL((trex_step_kernel<true, false>), dim3(n), dim3(64), 0, stream, a);
   return hipGetLastError();
@@ -2629,6 +2689,10 @@ hipError_t trex_launch_fill_u8(uint8_t *p, uint8_t v, int n, hipStream_t stream)
 }
 hipError_t trex_launch_copy_mass_scale(const float *src, float *dst, int n, int nb, hipStream_t stream) {
   hipLaunchKernelGGL(trex_copy_mass_scale_kernel, dim3((n * TL + 255) / 256), dim3(256), 0, stream, src, dst, n, nb);
+  return hipGetLastError();
+}
+hipError_t trex_launch_copy_wrench(const float *src, float *dst, int n, int nb, hipStream_t stream) {
+  hipLaunchKernelGGL(trex_copy_wrench_kernel, dim3((n * 6 * TL + 255) / 256), dim3(256), 0, stream, src, dst, n, nb);
   return hipGetLastError();
 }
 

@@ -40,7 +40,7 @@ SYMBOLS = [
     "trex_batch_set_episode_limit", "trex_batch_get_episode_steps",
     "trex_batch_set_wave_balance", "trex_batch_forget_buffers", "trex_batch_set_penalties_in_rows",
     "trex_model_num_visuals", "trex_model_visual_info", "trex_batch_visual_transforms", "trex_batch_step_many",
-    "trex_batch_render",
+    "trex_batch_render", "trex_batch_set_external_wrench",
 ]
 
 # every symbol include/trex_policy.h declares (the trainer-side kernels)
@@ -90,6 +90,7 @@ lib.trex_batch_set_state.argtypes = [_vp, _vp, _vp]
 lib.trex_batch_set_motors_enabled.argtypes = [_vp, C.c_int, _vp]
 lib.trex_batch_head_position.argtypes = [_vp, _vp, _vp]
 lib.trex_batch_set_domain.argtypes = [_vp, _vp, _vp, _vp]
+lib.trex_batch_set_external_wrench.argtypes = [_vp, _vp, _vp]
 lib.trex_model_use_primitive_collision.argtypes = [_vp, C.c_double, C.c_int, C.c_int]
 lib.trex_model_fit_hull_primitives.argtypes = [_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
 lib.trex_model_num_links.argtypes = [_vp]
@@ -401,6 +402,17 @@ class Batch:
         n = self.num_envs
         check(lib.trex_batch_set_domain(self.h, self._p(mass_scale, "float32", n * self.model.num_bodies, "mass_scale"),
                                         self._p(friction, "float32", n, "friction"), self._stream(stream)))
+
+    def set_external_wrench(self, wrench=None, stream=None):
+        """External wrench [n, num_bodies, 6] f32 on the batch's device: fx fy fz at each moving body's COM, tx ty tz about
+        it, world axes (include/trex_batch.h). Copied; held for every substep of every later env-step until replaced.
+        None clears it (the default kernels again)."""
+        if wrench is not None:
+            shape = (self.num_envs, self.model.num_bodies, 6)
+            if tuple(wrench.shape) != shape:
+                raise TrexError(E_INVALID, "wrench: expected shape %s, got %s" % (shape, tuple(wrench.shape)))
+        check(lib.trex_batch_set_external_wrench(self.h, self._p(wrench, "float32", self.num_envs * self.model.num_bodies * 6,
+                                                                 "wrench"), self._stream(stream)))
 
     def contact_stats(self, count=None, normal_impulse=None, stream=None):
         n = self.num_envs

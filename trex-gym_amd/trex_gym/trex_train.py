@@ -14,17 +14,27 @@ import sys
 
 import torch
 
+from .perturb import RandomPushes
 from .ppo import PPO
 from .vec_env import TrexVecEnv
 
 _URDF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "assets", "trex_collide.urdf")
 
 
-def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0):   # (weights of trex_train.py:66)
+def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0, push_force=0.0, push_interval=100,
+                      push_duration=5, push_probability=1.0, seed=0):   # (weights of trex_train.py:66)
     # warmstart > 0: the contact solver starts from that fraction of each point's impulses of the last solve (model parameter)
     params = {"warmstart": float(warmstart)} if warmstart else None
+    # push_force > 0: random horizontal pushes of the base, up to push_force N, every push_interval env-steps for
+    # push_duration env-steps (trex_gym.perturb.RandomPushes); 0 = none
+    pushes = None
+    if push_force > 0:
+        dev = torch.device(device)
+        gen = torch.Generator(device=dev).manual_seed(int(seed))
+        pushes = RandomPushes(num_envs, body=0, interval=push_interval, probability=push_probability, max_force=push_force,
+                              duration=push_duration, generator=gen, device=dev)
     return TrexVecEnv(num_envs, urdf_path=_URDF_PATH, device=device, distance_weight=2e2, energy_weight=1e-6,
-                      drift_weight=1.0, max_episode_steps=max_episode_steps, params=params)
+                      drift_weight=1.0, max_episode_steps=max_episode_steps, params=params, pushes=pushes)
 
 
 # Hyper-parameter presets. "reference" is the ppo2.learn call of the reference's script (trex_train.py:47-60):
@@ -123,7 +133,7 @@ def load_agent(load_path, num_envs=1, device="cuda:0", max_episode_steps=1000):
     return agent
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--train", action="store_true", default=True)
     ap.add_argument("--num_timesteps", type=int, default=int(5e6))   # trex_train.py:27
@@ -143,8 +153,21 @@ def main(argv=None):
     ap.add_argument("--export", type=str, default=None, help="with --play: .npz of mesh names + [T, 252, 7] world poses for an external renderer")
     ap.add_argument("--frames", type=str, default=None, help="with --play: directory for one 960 x 720 PNG per step (trex_train.py:132-134)")
     ap.add_argument("--play_deterministic", action="store_true", help="with --play: the mean action and frozen normalisation statistics (the reference samples and keeps updating)")
+    ap.add_argument("--push_force", type=float, default=0.0,
+                    help="random horizontal pushes of the base of up to this many N (0 = off; trex_gym.perturb.RandomPushes)")
+    ap.add_argument("--push_interval", type=int, default=100, help="with --push_force: env-steps between two pushes of an env")
+    ap.add_argument("--push_duration", type=int, default=5, help="with --push_force: env-steps a push lasts")
     args = ap.parse_args(argv)
-    env = build_environment(args.num_envs, max_episode_steps=args.max_episode_steps, warmstart=args.warmstart)
+    if args.push_force > 0 and args.graphs:   # (the pushes are drawn per step on the host's step count: not in a replayed graph)
+        ap.error("--push_force cannot be combined with --graphs")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    env = build_environment(args.num_envs, max_episode_steps=args.max_episode_steps, warmstart=args.warmstart,
+                            push_force=args.push_force, push_interval=args.push_interval, push_duration=args.push_duration,
+                            seed=args.random_seed)
     agent, _ = train(env, args.num_timesteps, args.random_seed, args.nsteps, args.noptepochs, args.save, use_graphs=args.graphs,
                      preset=args.preset)
     if args.play:

@@ -33,10 +33,12 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
                  distance_weight=1.0, energy_weight=0.005, drift_weight=0.002,
                  max_episode_steps=None, starting_configuration=None, params=None,
                  rank=0, world_size=1, process_group=None, collision="hulls", primitive_max_radius=0.2, row_buffers=1,
-                 penalties_in_rows=False):
+                 penalties_in_rows=False, pushes=None):
         """num_envs is the GLOBAL env count; this process owns sharding.shard_range(num_envs, rank, world_size).
         row_buffers=2: successive steps write two row blocks in turn (`rows`, `obs`, `rew`, `done_f` always name the
-        block of the LAST step), which lets the pipelined all-gather read a block in place."""
+        block of the LAST step), which lets the pipelined all-gather read a block in place.
+        pushes: a trex_gym.perturb.RandomPushes over this process's n envs; step_tensor / step_wait draw its pushes before
+        each step launch and apply them, on top of the wrench of set_external_wrench / apply_external_force."""
         self.global_num_envs = int(num_envs)
         self.rank, self.world_size, self.process_group = int(rank), int(world_size), process_group
         self.env_lo, self.env_hi = sharding.shard_range(self.global_num_envs, self.rank, self.world_size)
@@ -89,6 +91,11 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         self._pipe = None
         self._copy_pipe = None
         self._ep_ret = self._ep_len = None      # episode statistics of the numpy API (step_wait)
+        self._wrench = None                     # the caller's external wrench [n, num_bodies, 6] (None: none)
+        self._link_table = None
+        self.pushes = pushes
+        if pushes is not None and pushes.num_envs != n:
+            raise ValueError("pushes: RandomPushes over %d envs, the env has %d" % (pushes.num_envs, n))
 
     # ---- tensor-native API (stays on device, stream-ordered, no host sync)
     def reset_tensor(self, mask=None):
@@ -121,6 +128,9 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
             raise ValueError("actions must have shape (%d, %d), got %s" % (self.num_envs, self.J, tuple(actions.shape)))
         # (with max_episode_steps the launch also resets the envs whose episode ends with this step: done = 1,
         # reward of the finished step, observation of the new episode - VecEnv semantics, no second launch)
+        if self.pushes is not None:   # this step's pushes (those of envs that ended their episode last step are dropped)
+            w = self.pushes.wrench(self.model.num_bodies, self.done).to(self.device)
+            self.batch.set_external_wrench(w if self._wrench is None else w + self._wrench)
         if len(self._row_blocks) > 1:
             self._point_at(1 - self._row_k)
         self.batch.step_rows(actions, self.rows, self._penalties, done=self.done)   # (None: the penalties ride in the row block)
@@ -313,3 +323,35 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
             friction = friction.to(device=self.device, dtype=torch.float32).contiguous()
             assert tuple(friction.shape) == (self.num_envs,)
         self.batch.set_domain(mass_scale, friction)
+
+    # ---- external forces (trex_batch_set_external_wrench; trex_gym.perturb)
+    def set_external_wrench(self, wrench):
+        """wrench [n, num_bodies, 6]: force at each moving body's COM and torque about it, world axes (N, N m). Held for
+        every substep of every later step until replaced or cleared - not for the settle substep of a reset. None clears."""
+        if wrench is None:
+            return self.clear_external_wrench()
+        wrench = wrench.to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(wrench.shape) != (self.num_envs, self.model.num_bodies, 6):
+            raise ValueError("wrench must have shape (%d, %d, 6), got %s" % (self.num_envs, self.model.num_bodies, tuple(wrench.shape)))
+        self._wrench = wrench.clone()
+        self.batch.set_external_wrench(self._wrench)
+
+    def apply_external_force(self, link, force, position=None, frame="world", env_ids=None):
+        """pybullet's applyExternalForce for link `link` (index or name): force [3] or [n, 3] at `position` (None: the
+        body's COM), both in world coordinates (frame="world") or the link's frame (frame="link"), on the envs env_ids
+        (None: all). ADDS to the held wrench (clear_external_wrench() removes it) and holds it for the whole env-step,
+        every later step - pybullet's lasts one stepSimulation. The moment arm is taken at the current state."""
+        from .perturb import LinkTable, link_wrench
+        if self._link_table is None:
+            self._link_table = LinkTable.from_model(self.model)
+        w = link_wrench(self._link_table, self.link_transforms(), link, force, position, frame)
+        if env_ids is not None:
+            keep = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
+            keep[torch.as_tensor(env_ids, device=self.device, dtype=torch.long)] = True
+            w = torch.where(keep.view(-1, 1, 1), w, torch.zeros_like(w))
+        self.set_external_wrench(w if self._wrench is None else self._wrench + w)
+        return self._wrench
+
+    def clear_external_wrench(self):
+        self._wrench = None
+        self.batch.set_external_wrench(None)

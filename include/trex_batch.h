@@ -288,6 +288,32 @@ int trex_batch_set_domain(TrexBatch *batch, const float *mass_scale_dev, const f
  * While a wrench is set the step launches run separate kernel instantiations; after NULL the default kernels again. */
 int trex_batch_set_external_wrench(TrexBatch *batch, const float *wrench_dev, void *stream);
 
+/* Contact sensor: the floor-contact wrench per env and moving body (pybullet's getContactPoints(bodyA, linkIndexA) -
+ * normalForce, lateralFriction1/2 - summed per link; no reference counterpart: foot-contact flags, contact rewards,
+ * ground-reaction forces). enabled != 0: the step and reset launches record it (separate kernel instantiations); 0: they stop
+ * (the default kernels again). The first enable allocates the batch-owned buffer, zeroed: a batch that never enables the
+ * sensor allocates nothing, and the values are zero until the first launch that records. */
+int trex_batch_set_contact_sensor(TrexBatch *batch, int enabled);
+
+/* out_dev [N, num_bodies, 6] f32 device: fx fy fz (N), tx ty tz (N m) - world axes, force at the body's COM, torque about it
+ * (the layout of trex_batch_set_external_wrench). TREX_E_INVALID while the sensor has never been enabled or is off.
+ *   - the value: for each env and body, the MEAN floor-contact wrench over the solves since the env's last observation. For
+ *     every contact point of the body, its final impulses lambda = (lambda_x, lambda_y, lambda_n) of the solve are summed as
+ *     the world vector (lambda_x, lambda_y, lambda_n), and the moment (p - c) x lambda about the body's world COM c, p being
+ *     the point the contact rows act at; the sums are divided by (number of solves x dt). This is the wrench the solver
+ *     applied: with gravity and the external wrench it closes the momentum balance;
+ *   - a stepped env averages the `substeps` solves of its env-step; an env that was reset - trex_batch_reset / _reset_rows
+ *     (mask honoured: the other envs keep their values) or an episode-limit reset inside a step launch - reports its one
+ *     settle substep, the state its observation shows (trex_batch_contact_stats reports the same substep); an env that
+ *     containment put back reports zeros;
+ *   - trex_batch_step, _step_rows, _time_steps and _step_many record it; _step_many reports the LAST of its S steps;
+ *     with or without warmstart, an external wrench, a domain, primitive collision, in either launch form;
+ *   - read-only: state, observations, rewards, done, penalties, contact_stats, the warm-start record and the episode counts
+ *     are bitwise those of the same launches with the sensor off;
+ *   - trex_batch_debug_step returns TREX_E_INVALID while the sensor is on; a buffer shorter than N * num_bodies * 6 floats,
+ *     host memory or another device's memory returns TREX_E_INVALID before anything is launched. */
+int trex_batch_contact_wrench(TrexBatch *batch, float *out_dev, void *stream);
+
 /* diagnostics of the last substep: contact count per env [N] i32 (nullable), summed normal
  * impulse per env [N] f32 (nullable). */
 int trex_batch_contact_stats(TrexBatch *batch, int32_t *count_dev, float *normal_impulse_dev, void *stream);

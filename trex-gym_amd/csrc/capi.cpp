@@ -18,11 +18,11 @@
 extern "C" {
 hipError_t trex_launch_step(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, float *, uint8_t *,
                             float *, float, float, float, float *, hipStream_t, float *, int, int, int, int, float *,
-                            const float *);
+                            const float *, float *);
 hipError_t trex_launch_reset(const TrexDeviceModel *, TrexBatchArrays, int, const uint8_t *, float *, float, float,
-                             float, float *, hipStream_t, int, float *, float *, int, int, int, float *);
+                             float, float *, hipStream_t, int, float *, float *, int, int, int, float *, float *);
 hipError_t trex_launch_step_many(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, int, int, float *, uint8_t *,
-                                 float, float, float, hipStream_t, int, int, int, float *, const float *);
+                                 float, float, float, hipStream_t, int, int, int, float *, const float *, float *);
 hipError_t trex_launch_pack_state(const TrexDeviceModel *, TrexBatchArrays, int, float *, int, hipStream_t);
 hipError_t trex_launch_head(const TrexDeviceModel *, TrexBatchArrays, int, float *, hipStream_t);
 hipError_t trex_launch_link_transforms(const TrexDeviceModel *, TrexBatchArrays, int, float *, hipStream_t, int);
@@ -32,6 +32,8 @@ hipError_t trex_launch_scalars_set(TrexBatchArrays, int, const int32_t *, int, i
 hipError_t trex_launch_fill_u8(uint8_t *, uint8_t, int, hipStream_t);
 hipError_t trex_launch_copy_mass_scale(const float *, float *, int, int, hipStream_t);
 hipError_t trex_launch_copy_wrench(const float *, float *, int, int, hipStream_t);
+hipError_t trex_launch_contact_wrench(const float *, float *, int, int, hipStream_t);
+int trex_contact_sensor_floats(void);
 int trex_step_lds_bytes(int);
 int trex_step_envs_per_workgroup(int);
 int trex_step_warm_lds_bytes(void);
@@ -50,6 +52,9 @@ struct TrexBatch {
   float *ext = nullptr;                        // external wrench [n][6][TREX_TL] (trex_batch_set_external_wrench); first non-NULL call on
   bool ext_on = false;                         // set: the step launches take the EXT kernels
   const float *wrench() const { return ext_on ? ext : nullptr; }
+  float *sens = nullptr;                       // contact sensor [n][trex_contact_sensor_floats()] (trex_batch_set_contact_sensor); first enable
+  bool sens_on = false;                        // on: every step and reset launch takes the SENS kernels
+  float *sensor() const { return sens_on ? sens : nullptr; }
   float wd = 1.0f, we = 0.005f, wk = 0.002f;  // trex_env.py:42-44
   bool pen_in_rows = false;                    // trex_batch_set_penalties_in_rows
   int balance_mode = -1;                       // trex_batch_set_wave_balance: -1 auto, 0 off, 1 on
@@ -547,7 +552,7 @@ int trex_batch_reset(TrexBatch *b, const uint8_t *mask_dev, float *obs_out_dev, 
   BUF_TRY(mask_dev, n, "trex_batch_reset: mask");
   BUF_TRY(obs_out_dev, n * 3 * b->nj * sizeof(float), "trex_batch_reset: obs_out");
   HIP_TRY(trex_launch_reset(b->dmodel, b->arr, b->n, mask_dev, obs_out_dev, b->wd, b->we, b->wk, nullptr,
-                            (hipStream_t)stream, 3 * b->nj, nullptr, nullptr, 1, b->nj, 0, b->warm));
+                            (hipStream_t)stream, 3 * b->nj, nullptr, nullptr, 1, b->nj, 0, b->warm, b->sensor()));
   return TREX_OK;
 }
 
@@ -561,7 +566,7 @@ int trex_batch_reset_rows(TrexBatch *b, const uint8_t *mask_dev, float *rows_dev
   BUF_TRY(rows_dev, ((n - 1) * row_stride + 3 * b->nj + (b->pen_in_rows ? 5 : 2)) * sizeof(float), "trex_batch_reset_rows: rows");
   HIP_TRY(trex_launch_reset(b->dmodel, b->arr, b->n, mask_dev, rows_dev, b->wd, b->we, b->wk, nullptr,
                             (hipStream_t)stream, row_stride, rows_dev + 3 * b->nj, rows_dev + 3 * b->nj + 1, row_stride, b->nj,
-                            b->pen_in_rows ? 1 : 0, b->warm));
+                            b->pen_in_rows ? 1 : 0, b->warm, b->sensor()));
   return TREX_OK;
 }
 
@@ -577,7 +582,7 @@ int trex_batch_step(TrexBatch *b, const float *actions_dev, float *obs_dev, floa
   BUF_TRY(done_dev, n, "trex_batch_step: done");
   BUF_TRY(penalties_dev, n * 3 * sizeof(float), "trex_batch_step: penalties");
   HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, reward_dev, done_dev, penalties_dev, b->wd,
-                           b->we, b->wk, nullptr, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, b->wrench()));
+                           b->we, b->wk, nullptr, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, b->wrench(), b->sensor()));
   return TREX_OK;
 }
 
@@ -595,7 +600,7 @@ int trex_batch_step_rows(TrexBatch *b, const float *actions_dev, float *rows_dev
   float *rew = rows_dev + 3 * b->nj;
   HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, rows_dev, rew, done_dev, penalties_dev, b->wd, b->we,
                            b->wk, nullptr, (hipStream_t)stream, rew + 1, row_stride, row_stride, b->balance(), b->pen_in_rows ? 1 : 0, b->warm,
-                           b->wrench()));
+                           b->wrench(), b->sensor()));
   return TREX_OK;
 }
 
@@ -613,7 +618,7 @@ int trex_batch_step_many(TrexBatch *b, const float *actions_dev, float *rows_dev
   BUF_TRY(done_dev, S * n, "trex_batch_step_many: done");
   HIP_TRY(trex_launch_step_many(b->dmodel, b->arr, b->n, actions_dev, rows_dev, row_stride, num_steps, penalties_dev, done_dev,
                                 b->wd, b->we, b->wk, (hipStream_t)stream, b->balance(), b->nj, b->pen_in_rows ? 1 : 0, b->warm,
-                                b->wrench()));
+                                b->wrench(), b->sensor()));
   return TREX_OK;
 }
 
@@ -628,8 +633,10 @@ int trex_batch_debug_step(TrexBatch *b, const float *actions_dev, float *obs_dev
     return fail(TREX_E_INVALID, "trex_batch_debug_step: not available for a batch with warmstart > 0");
   if (b->ext_on)   // (nor an external wrench)
     return fail(TREX_E_INVALID, "trex_batch_debug_step: not available while an external wrench is set");
+  if (b->sens_on)   // (nor the contact sensor)
+    return fail(TREX_E_INVALID, "trex_batch_debug_step: not available while the contact sensor is on");
   HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, nullptr, nullptr, nullptr, b->wd, b->we, b->wk,
-                           debug_dev, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, nullptr));
+                           debug_dev, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, nullptr, nullptr));
   return TREX_OK;
 }
 
@@ -750,6 +757,33 @@ int trex_batch_set_external_wrench(TrexBatch *b, const float *wrench_dev, void *
   return TREX_OK;
 }
 
+int trex_batch_set_contact_sensor(TrexBatch *b, int enabled) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!enabled) { b->sens_on = false; return TREX_OK; }   // the default kernels again; the buffer stays for the next enable
+  if (!b->sens) {   // first enable: a batch that never enables the sensor allocates nothing; zeros until a launch records
+    DeviceGuard guard(b->device);
+    const size_t bytes = (size_t)b->n * trex_contact_sensor_floats() * sizeof(float);
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, bytes));
+    b->allocs.push_back(p);
+    HIP_TRY(hipMemset(p, 0, bytes));
+    HIP_TRY(hipDeviceSynchronize());   // (the zeros are in place before a launch on any stream)
+    b->sens = (float *)p;
+  }
+  b->sens_on = true;
+  return TREX_OK;
+}
+
+int trex_batch_contact_wrench(TrexBatch *b, float *out_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!b->sens_on) return fail(TREX_E_INVALID, "trex_batch_contact_wrench: the contact sensor is off (trex_batch_set_contact_sensor)");
+  if (!out_dev) return fail(TREX_E_INVALID, "trex_batch_contact_wrench: out is null");
+  DeviceGuard guard(b->device);
+  BUF_TRY(out_dev, (size_t)b->n * b->nb * 6 * sizeof(float), "trex_batch_contact_wrench: out");
+  HIP_TRY(trex_launch_contact_wrench(b->sens, out_dev, b->n, b->nb, (hipStream_t)stream));
+  return TREX_OK;
+}
+
 int trex_batch_contact_stats(TrexBatch *b, int32_t *count_dev, float *normal_impulse_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
   DeviceGuard guard(b->device);
@@ -787,7 +821,7 @@ int trex_batch_time_steps(TrexBatch *b, const float *actions_dev, float *obs_dev
   HIP_TRY(hipEventRecord(e0, s));
   for (int i = 0; i < steps; i++)
     HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, reward_dev, done_dev, nullptr, b->wd, b->we,
-                             b->wk, nullptr, s, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, b->wrench()));
+                             b->wk, nullptr, s, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, b->wrench(), b->sensor()));
   HIP_TRY(hipEventRecord(e1, s));
   HIP_TRY(hipEventSynchronize(e1));
   float ms = 0.f;

@@ -396,7 +396,11 @@ struct KernelArgs {
                           // every other argument keeps its offset
   const float *ext;       // EXT launches: the per-env external wrench [N][6][TREX_TL] (fx fy fz tx ty tz, world axes, at / about the
                           // body's COM; trex_batch_set_external_wrench); after warm for the same reason
+  float *sens;            // SENS launches: the per-env contact sensor [N][SENS_ROWS][TREX_TL] (below; trex_batch_set_contact_sensor); last
 };
+// SENS rows of an env: 0..5 the floor-contact wrench of every body (fx fy fz tx ty tz, world axes, at / about its COM), 6..8 the
+// body's COM of the current substep relative to the base origin (written by the tree phases, read by the env's results pass)
+constexpr int SENS_ROWS = 9;
 
 }  // namespace
 
@@ -438,12 +442,21 @@ struct KernelArgs {
 // the env-step, never on the settle substep of an episode-limit reset (sub == n_sub). Loaded from global memory at the top of the
 // tree block (no LDS: the pair workgroup's is spent), one coalesced row per component. Non-RESET product launches only; with
 // F = T = 0 every added term is an exact x + 0, so an all-zero wrench gives the rows of the kernels without it.
+// SENS (the batch's contact sensor is on, trex_batch_set_contact_sensor; args.sens): read-only. After every solve each body lane
+// gathers the final impulses (x, y, normal = z) of its env's points on that body - v_readlane from the row lanes, points from W.cpt,
+// at most MAXC - and adds the force and the moment (p - c) x lambda about its COM c to its env's row in global memory (the first
+// solve of an env-step stores without loading, the last one scales by 1 / (solves x dt)). c (relative to the base origin, the frame
+// of W.cpt) is written by the tree phases, which are the only phase that has the body's rotation, to rows 6..8 of the same buffer
+// and read back after the solve: no LDS (the pair workgroup's is spent) and no register lives across the phases. The settle substep
+// of a reset (launch or episode limit) starts afresh; containment stores zeros. Every launch family has a SENS form (reset too),
+// with and without WARM and EXT; nothing the physics reads is written.
 #define WSYNC() do { if (PAIR) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); else __syncthreads(); } while (0)
-template <bool RESET, bool DEBUG, bool MULTI, bool PAIR = false, bool WARM = false, bool EXT = false>
+template <bool RESET, bool DEBUG, bool MULTI, bool PAIR = false, bool WARM = false, bool EXT = false, bool SENS = false>
 __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int wg_in) {   // wg_in: blockIdx.x
   static_assert(!PAIR || (!RESET && !DEBUG && !MULTI), "the pair form exists for the product step launch only");
   static_assert(!(WARM && DEBUG), "the diagnostics dump has no warm-start form");
   static_assert(!EXT || (!RESET && !DEBUG), "the external wrench exists for the product step launches only");
+  static_assert(!SENS || !DEBUG, "the diagnostics dump has no contact-sensor form");
   __shared__ WaveLds Wpair[PAIR ? 2 : 1];
   __shared__ __attribute__((aligned(16))) unsigned char Gpair[PAIR ? sizeof(CgLds) : 16];   // PAIR: contact-generation scratch of the workgroup (wave 1)
   const int wave = PAIR ? uni((int)threadIdx.x >> 6) : 0;
@@ -1278,6 +1291,13 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
       float comw[3], Icw[6];   // comw = COM offset from the body origin, world axes
       {
         matvec3(Rh, comb, comw);
+        if constexpr (SENS) {   // the COM of this substep, relative to the base origin, for the env's results pass
+          if (is_body) {
+            const float4 q1_ = H->body[BREC * bl + 1];
+            float *sc = args.sens + (size_t)(PAIR ? __float_as_int(H->xch[6]) : env) * (SENS_ROWS * TL) + 6 * TL + bl;
+            sc[0] = q1_.x + comw[0]; sc[TL] = q1_.y + comw[1]; sc[2 * TL] = q1_.z + comw[2];
+          }
+        }
         // Ic_world = R Ib R^T (symmetric)
         float t[9];
         const float Ib[9] = {inb[0], inb[1], inb[2], inb[1], inb[3], inb[4], inb[2], inb[4], inb[5]};
@@ -2227,6 +2247,38 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
     const float nimp = uni(wsum((!mlane && cdir == 0) ? lam : 0.f));
     const float mdg = W.st[ST_MDG][bl];
     const float dv = mrow ? dvj * mdg : 0.f;
+    if constexpr (SENS) {   // this solve's floor-contact wrench of every body (SENS above)
+      const bool first = sub == 0 || sub == n_sub, last = sub + 1 >= n_sub;   // (sub == n_sub: the settle substep of a reset)
+      float *sw = args.sens + (size_t)env * (SENS_ROWS * TL) + bl;
+      float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, cb[3] = {0.f, 0.f, 0.f};
+      if (is_body) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) cb[k] = sw[(6 + k) * TL];
+        if (!first) {
+#pragma unroll
+          for (int k = 0; k < 6; k++) acc[k] = sw[k * TL];
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < MAXC; s++) {
+        if (s >= s0) {
+          const float fs[3] = {rl(lam, krow_lane(3 * s + 1)), rl(lam, krow_lane(3 * s + 2)), rl(lam, krow_lane(3 * s))};
+          const float *cp = W.cpt[s - s0];
+          if (__float_as_int(cp[0]) == lt) {
+            const float d[3] = {cp[1] - cb[0], cp[2] - cb[1], cp[3] - cb[2]};
+            float m[3];
+            cross3(d, fs, m);
+#pragma unroll
+            for (int k = 0; k < 3; k++) { acc[k] += fs[k]; acc[3 + k] += m[k]; }
+          }
+        }
+      }
+      if (is_body) {
+        const float scale = last ? inv_dt / (float)(sub == n_sub ? 1 : n_sub) : 1.f;
+#pragma unroll
+        for (int k = 0; k < 6; k++) sw[k * TL] = acc[k] * scale;
+      }
+    }
 
     if (DEBUG && args.debug && wg == 0) {
       float *D = args.debug;
@@ -2304,6 +2356,14 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
   // ---- end of the env-step: outputs
   if (RESET || !time_up) finish_step();
   if (env_bad && !time_up) to_start_pose();     // (a time-limit reset already left a sound state)
+  if constexpr (SENS) {   // a contained env reports no contact
+    const int lt = lane_id();
+    if (env_bad && !time_up && lt < nb) {
+      float *sw = args.sens + (size_t)env * (SENS_ROWS * TL) + lt;
+#pragma unroll
+      for (int k = 0; k < 6; k++) sw[k * TL] = 0.f;
+    }
+  }
   const int steps_out = (RESET || args.arr.max_episode_steps > 0) ? ((RESET || time_up || env_bad) ? 0 : age) : steps_in;
   {
     const int lt = lane_id();
@@ -2407,6 +2467,16 @@ template <bool WARM>
 __global__ __launch_bounds__(128, 4) void trex_step_pair_ext_kernel(KernelArgs args) { trex_step_body<false, false, false, true, WARM, true>(args, (int)blockIdx.x); }
 template <bool WARM>
 __global__ __launch_bounds__(64, 4) void trex_step_many_ext_kernel(KernelArgs args) { trex_step_body<false, false, true, false, WARM, true>(args, (int)blockIdx.x); }
+// every launch with the contact sensor (SENS above), with and without WARM and EXT: chosen on the host while the sensor is on
+// (templates: the stamped diagnostic build instantiates none)
+template <bool WARM, bool EXT>
+__global__ __launch_bounds__(64, 4) void trex_step_sens_kernel(KernelArgs args) { trex_step_body<false, false, false, false, WARM, EXT, true>(args, (int)blockIdx.x); }
+template <bool WARM, bool EXT>
+__global__ __launch_bounds__(128, 4) void trex_step_pair_sens_kernel(KernelArgs args) { trex_step_body<false, false, false, true, WARM, EXT, true>(args, (int)blockIdx.x); }
+template <bool WARM, bool EXT>
+__global__ __launch_bounds__(64, 4) void trex_step_many_sens_kernel(KernelArgs args) { trex_step_body<false, false, true, false, WARM, EXT, true>(args, (int)blockIdx.x); }
+template <bool WARM>
+__global__ __launch_bounds__(64, 4) void trex_reset_sens_kernel(KernelArgs args) { trex_step_body<true, false, false, false, WARM, false, true>(args, (int)blockIdx.x); }
 
 // ---------------------------------------------------------------- small utility kernels
 __global__ void trex_pack_state_kernel(const TrexDeviceModel *M, TrexBatchArrays arr, int n, float *out, int pack) {
@@ -2577,6 +2647,13 @@ __global__ void trex_copy_wrench_kernel(const float *src, float *dst, int n, int
   const int e = i / (6 * TL), c = (i / TL) % 6, l = i % TL;
   dst[i] = l < nb ? src[((size_t)e * nb + l) * 6 + c] : 0.0f;
 }
+__global__ void trex_contact_wrench_kernel(const float *src, float *dst, int n, int nb) {
+  // the sensor's rows 0..5 [N, SENS_ROWS, 32] -> [N, nb, 6]
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * nb * 6) return;
+  const int e = i / (nb * 6), l = (i / 6) % nb, c = i % 6;
+  dst[i] = src[(size_t)e * (SENS_ROWS * TL) + c * TL + l];
+}
 
 // ---------------------------------------------------------------- host launchers (called by capi.cpp)
 // the step launch of a batch of n envs takes the pair form (two envs per workgroup) for an even batch that is resident at once
@@ -2587,14 +2664,32 @@ extern "C" {
 hipError_t trex_launch_step(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions,
                             float *obs, float *reward, uint8_t *done, float *penalties, float wd, float we,
                             float wk, float *debug, hipStream_t stream, float *done_f, int obs_stride, int scal_stride,
-                            int balance, int pen_in_rows, float *warm, const float *ext) {
+                            int balance, int pen_in_rows, float *warm, const float *ext, float *sens) {
   // balance: the env-to-wave assignment by contact rank (trex_batch_set_wave_balance decides; capi.cpp). Diagnostics
   // launches keep env k in workgroup k (the stamped build is balanced like the product: it reports the env of every wave)
   int32_t *perm = ((debug && !TREX_STAMPS) || !balance) ? nullptr : arr.balance;
   KernelArgs a{model, arr, n, actions, obs, reward, done, done_f, obs_stride, scal_stride, penalties, nullptr, perm, wd, we, wk, debug,
-               1, 0, pen_in_rows, warm, ext};
+               1, 0, pen_in_rows, warm, ext, sens};
 
   const bool pair = trex_pair_launch(n);
+  if (sens) {   // (capi.cpp refuses a diagnostics step while the sensor is on; the stamped build has no SENS instantiations)
+    if (debug || TREX_STAMPS) return hipErrorInvalidValue;
+    if constexpr (!TREX_STAMPS) {
+      const dim3 g(pair ? n / 2 : n), b(pair ? 128 : 64);
+      if (pair) {
+        if (warm) { if (ext) hipLaunchKernelGGL((trex_step_pair_sens_kernel<true, true>), g, b, 0, stream, a);
+                    else hipLaunchKernelGGL((trex_step_pair_sens_kernel<true, false>), g, b, 0, stream, a); }
+        else { if (ext) hipLaunchKernelGGL((trex_step_pair_sens_kernel<false, true>), g, b, 0, stream, a);
+               else hipLaunchKernelGGL((trex_step_pair_sens_kernel<false, false>), g, b, 0, stream, a); }
+      } else {
+        if (warm) { if (ext) hipLaunchKernelGGL((trex_step_sens_kernel<true, true>), g, b, 0, stream, a);
+                    else hipLaunchKernelGGL((trex_step_sens_kernel<true, false>), g, b, 0, stream, a); }
+        else { if (ext) hipLaunchKernelGGL((trex_step_sens_kernel<false, true>), g, b, 0, stream, a);
+               else hipLaunchKernelGGL((trex_step_sens_kernel<false, false>), g, b, 0, stream, a); }
+      }
+    }
+    return hipGetLastError();
+  }
   if (ext) {   // (capi.cpp refuses a diagnostics step of a batch with a wrench; the stamped build has no EXT instantiations)
     if (debug || TREX_STAMPS) return hipErrorInvalidValue;
     if constexpr (!TREX_STAMPS) {
@@ -2625,11 +2720,20 @@ hipError_t trex_launch_step(const TrexDeviceModel *model, TrexBatchArrays arr, i
 // penalties [S, N, 3] and done bytes [S, N] nullable
 hipError_t trex_launch_step_many(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions, float *rows,
                                  int row_stride, int n_steps, float *penalties, uint8_t *done, float wd, float we, float wk,
-                                 hipStream_t stream, int balance, int nj, int pen_in_rows, float *warm, const float *ext) {
+                                 hipStream_t stream, int balance, int nj, int pen_in_rows, float *warm, const float *ext,
+                                 float *sens) {
   float *rew = rows + 3 * nj;
   KernelArgs a{model, arr, n, actions, rows, rew, done, rew + 1, row_stride, row_stride, penalties, nullptr,
-               balance ? arr.balance : nullptr, wd, we, wk, nullptr, n_steps, (long long)n * row_stride, pen_in_rows, warm, ext};
-  if (ext) {
+               balance ? arr.balance : nullptr, wd, we, wk, nullptr, n_steps, (long long)n * row_stride, pen_in_rows, warm, ext, sens};
+  if (sens) {
+    if (TREX_STAMPS) return hipErrorInvalidValue;
+    if constexpr (!TREX_STAMPS) {
+      if (warm) { if (ext) hipLaunchKernelGGL((trex_step_many_sens_kernel<true, true>), dim3(n), dim3(64), 0, stream, a);
+                  else hipLaunchKernelGGL((trex_step_many_sens_kernel<true, false>), dim3(n), dim3(64), 0, stream, a); }
+      else { if (ext) hipLaunchKernelGGL((trex_step_many_sens_kernel<false, true>), dim3(n), dim3(64), 0, stream, a);
+             else hipLaunchKernelGGL((trex_step_many_sens_kernel<false, false>), dim3(n), dim3(64), 0, stream, a); }
+    }
+  } else if (ext) {
     if (TREX_STAMPS) return hipErrorInvalidValue;
     if constexpr (!TREX_STAMPS) {
       if (warm) hipLaunchKernelGGL(trex_step_many_ext_kernel<true>, dim3(n), dim3(64), 0, stream, a);
@@ -2642,10 +2746,16 @@ hipError_t trex_launch_step_many(const TrexDeviceModel *model, TrexBatchArrays a
 
 hipError_t trex_launch_reset(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const uint8_t *mask,
                              float *obs, float wd, float we, float wk, float *debug, hipStream_t stream, int obs_stride,
-                             float *reward, float *done_f, int scal_stride, int nj, int pen_in_rows, float *warm) {
+                             float *reward, float *done_f, int scal_stride, int nj, int pen_in_rows, float *warm, float *sens) {
   KernelArgs a{model, arr, n, nullptr, obs, reward, nullptr, done_f, obs_stride, scal_stride, nullptr, mask, nullptr, wd, we, wk, debug,
-               1, 0, (reward && done_f && pen_in_rows) ? 1 : 0, warm, nullptr};
-  if (warm) hipLaunchKernelGGL(trex_step_warm_kernel<true>, dim3(n), dim3(64), 0, stream, a);
+               1, 0, (reward && done_f && pen_in_rows) ? 1 : 0, warm, nullptr, sens};
+  if (sens) {
+    if (TREX_STAMPS) return hipErrorInvalidValue;
+    if constexpr (!TREX_STAMPS) {
+      if (warm) hipLaunchKernelGGL(trex_reset_sens_kernel<true>, dim3(n), dim3(64), 0, stream, a);
+      else hipLaunchKernelGGL(trex_reset_sens_kernel<false>, dim3(n), dim3(64), 0, stream, a);
+    }
+  } else if (warm) hipLaunchKernelGGL(trex_step_warm_kernel<true>, dim3(n), dim3(64), 0, stream, a);
   else hipLaunchKernelGGL((trex_step_kernel<true, false>), dim3(n), dim3(64), 0, stream, a);
   return hipGetLastError();
 }
@@ -2691,6 +2801,10 @@ hipError_t trex_launch_copy_mass_scale(const float *src, float *dst, int n, int 
   hipLaunchKernelGGL(trex_copy_mass_scale_kernel, dim3((n * TL + 255) / 256), dim3(256), 0, stream, src, dst, n, nb);
   return hipGetLastError();
 }
+hipError_t trex_launch_contact_wrench(const float *src, float *dst, int n, int nb, hipStream_t stream) {
+  hipLaunchKernelGGL(trex_contact_wrench_kernel, dim3((n * nb * 6 + 255) / 256), dim3(256), 0, stream, src, dst, n, nb);
+  return hipGetLastError();
+}
 hipError_t trex_launch_copy_wrench(const float *src, float *dst, int n, int nb, hipStream_t stream) {
   hipLaunchKernelGGL(trex_copy_wrench_kernel, dim3((n * 6 * TL + 255) / 256), dim3(256), 0, stream, src, dst, n, nb);
   return hipGetLastError();
@@ -2699,6 +2813,7 @@ hipError_t trex_launch_copy_wrench(const float *src, float *dst, int n, int nb, 
 // launch shape of the step launch for a batch of n envs (trex_batch_launch_info)
 int trex_step_envs_per_workgroup(int n) { return trex_pair_launch(n) ? 2 : 1; }
 int trex_step_lds_bytes(int n) { return trex_step_envs_per_workgroup(n) == 2 ? (int)(2 * sizeof(WaveLds) + sizeof(CgLds)) : (int)sizeof(WaveLds); }
+int trex_contact_sensor_floats(void) { return SENS_ROWS * TL; }   // per env: the batch's contact-sensor buffer (capi.cpp)
 int trex_step_warm_lds_bytes(void) { return (int)(MAXC * sizeof(float4)); }   // per env, on top of the above in the warm kernels
 
 }  // extern "C"

@@ -40,7 +40,7 @@ SYMBOLS = [
     "trex_batch_set_episode_limit", "trex_batch_get_episode_steps",
     "trex_batch_set_wave_balance", "trex_batch_forget_buffers", "trex_batch_set_penalties_in_rows",
     "trex_model_num_visuals", "trex_model_visual_info", "trex_batch_visual_transforms", "trex_batch_step_many",
-    "trex_batch_render", "trex_batch_set_external_wrench",
+    "trex_batch_render", "trex_batch_set_external_wrench", "trex_batch_set_contact_sensor", "trex_batch_contact_wrench",
 ]
 
 # every symbol include/trex_policy.h declares (the trainer-side kernels)
@@ -91,6 +91,8 @@ lib.trex_batch_set_motors_enabled.argtypes = [_vp, C.c_int, _vp]
 lib.trex_batch_head_position.argtypes = [_vp, _vp, _vp]
 lib.trex_batch_set_domain.argtypes = [_vp, _vp, _vp, _vp]
 lib.trex_batch_set_external_wrench.argtypes = [_vp, _vp, _vp]
+lib.trex_batch_set_contact_sensor.argtypes = [_vp, C.c_int]
+lib.trex_batch_contact_wrench.argtypes = [_vp, _vp, _vp]
 lib.trex_model_use_primitive_collision.argtypes = [_vp, C.c_double, C.c_int, C.c_int]
 lib.trex_model_fit_hull_primitives.argtypes = [_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
 lib.trex_model_num_links.argtypes = [_vp]
@@ -413,6 +415,22 @@ class Batch:
                 raise TrexError(E_INVALID, "wrench: expected shape %s, got %s" % (shape, tuple(wrench.shape)))
         check(lib.trex_batch_set_external_wrench(self.h, self._p(wrench, "float32", self.num_envs * self.model.num_bodies * 6,
                                                                  "wrench"), self._stream(stream)))
+
+    def set_contact_sensor(self, enabled=True):
+        """On: the step and reset launches record each env's floor-contact wrench per body (include/trex_batch.h);
+        off: they stop (the default kernels again)."""
+        check(lib.trex_batch_set_contact_sensor(self.h, 1 if enabled else 0))
+
+    def contact_wrench(self, out=None, stream=None):
+        """The contact sensor's values into out [n, num_bodies, 6] f32 on the batch's device (made when None) and returned:
+        force at each body's COM and torque about it, world axes, the mean over the solves since the env's last
+        observation."""
+        import torch
+        if out is None:
+            out = torch.empty(self.num_envs, self.model.num_bodies, 6, dtype=torch.float32, device=self.device)
+        check(lib.trex_batch_contact_wrench(self.h, self._p(out, "float32", self.num_envs * self.model.num_bodies * 6, "out"),
+                                            self._stream(stream)))
+        return out
 
     def contact_stats(self, count=None, normal_impulse=None, stream=None):
         n = self.num_envs

@@ -6,6 +6,11 @@ torque (N m) about it, world axes, held for every substep of the env-steps that 
 
     link_wrench     forces on URDF LINKS (index or name; WORLD_FRAME or LINK_FRAME; any point) -> that body wrench
     RandomPushes    horizontal pushes on one body, drawn on the device without a host sync (push recovery, training noise)
+
+and, the other way round, what the contact sensor (trex_batch_contact_wrench) reports in the same [n, num_bodies, 6] layout:
+
+    link_contact_forces    the floor-contact force on the bodies of URDF links (the feet), summed per entry
+    contact_flags          which bodies carry floor load
 """
 import math
 
@@ -84,6 +89,24 @@ def link_wrench(table, link_poses, link, force, point=None, frame=WORLD_FRAME, w
             p = pl + (Rl @ p.unsqueeze(-1)).squeeze(-1)
         wrench[:, b, 3:] += torch.linalg.cross(p - c, F, dim=-1)
     return wrench
+
+
+def link_contact_forces(table, wrench, links):
+    """Floor-contact forces [n, K, 3] of K entries from a sensor wrench [n, num_bodies, 6]. links: a sequence of K entries,
+    each a link (index or name) or a sequence of links; an entry sums the force part over the DISTINCT bodies of its links
+    (links joined by fixed joints share a body, which counts once)."""
+    cols = []
+    for entry in links:
+        group = [entry] if isinstance(entry, (str, int, np.integer)) else list(entry)
+        bodies = sorted({int(table.link_body[table.index(l)]) for l in group})
+        cols.append(wrench[:, bodies, :3].sum(1))
+    return torch.stack(cols, 1)
+
+
+def contact_flags(wrench, threshold=0.0):
+    """[n, num_bodies] bool from a sensor wrench [n, num_bodies, 6]: the body's normal (z) contact force exceeds
+    `threshold` N. Bodies off the floor report exact zeros, so threshold 0 flags every body the floor pushes."""
+    return wrench[..., 2] > threshold
 
 
 class RandomPushes:

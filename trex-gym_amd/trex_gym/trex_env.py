@@ -25,7 +25,7 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
     }
 
     def __init__(self, urdf_path=None, action_repeat=1, distance_weight=1.0, energy_weight=0.005,
-                 drift_weight=0.002, render=False, device=None):
+                 drift_weight=0.002, render=False, device=None, contact_sensor=False):
         if render:   # (the reference's render=True opens pybullet's GUI; rgb_array frames need no flag: render())
             raise NotImplementedError("render=True asks for a GUI, which this env has not; render('rgb_array') draws frames")
         self._time_step = 0.01 / NUM_SUBSTEPS
@@ -49,6 +49,9 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
                                drift_weight=drift_weight,
                                starting_configuration=self._starting_configuration)
         self.model = trex_robot.TrexRobot(self._vec, 0)
+        self._sensor_on = bool(contact_sensor)   # (contact_wrench(); off: the default kernels)
+        if self._sensor_on:
+            self._vec.enable_contact_sensor(True)
         self.np_random = None
         self.seed()
         self.reset()
@@ -87,6 +90,15 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
         from .render import Camera
         rgb = self._vec.render_tensor([0], RENDER_WIDTH, RENDER_HEIGHT, Camera())
         return rgb[0].cpu().numpy()
+
+    def contact_wrench(self):
+        """[num_bodies, 6] numpy: the floor-contact wrench per body of the last step (force at the body's COM, torque
+        about it, world axes; TrexVecEnv.contact_wrench). Construct with contact_sensor=True to record from the first
+        reset; otherwise the first call switches the sensor on and reports zeros until the next step or reset."""
+        if not self._sensor_on:
+            self._vec.enable_contact_sensor(True)
+            self._sensor_on = True
+        return self._vec.contact_wrench()[0].cpu().numpy()
 
     def should_terminate(self):
         return False

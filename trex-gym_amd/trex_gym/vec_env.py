@@ -355,3 +355,27 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
     def clear_external_wrench(self):
         self._wrench = None
         self.batch.set_external_wrench(None)
+
+    # ---- contact sensor (trex_batch_set_contact_sensor / trex_batch_contact_wrench; no host sync)
+    def enable_contact_sensor(self, on=True):
+        """on: every later step and reset records each env's floor-contact wrench per body (contact_wrench()); off: the
+        default kernels again. The physics is bitwise the same either way."""
+        self.batch.set_contact_sensor(on)
+
+    def contact_wrench(self, out=None):
+        """[n, num_bodies, 6] on the device: floor-contact force at each body's COM and torque about it, world axes (N, N m),
+        the mean over the substeps of the last step (a reset env: its settle substep; a contained env: zeros)."""
+        return self.batch.contact_wrench(out)
+
+    def contact_forces(self, links):
+        """[n, K, 3] floor-contact force on URDF links: links = K entries, each a link name / index or a list of them (the
+        force summed over their distinct bodies), e.g. contact_forces(["foot_L", "foot_R"])."""
+        from .perturb import LinkTable, link_contact_forces
+        if self._link_table is None:
+            self._link_table = LinkTable.from_model(self.model)
+        return link_contact_forces(self._link_table, self.contact_wrench(), links)
+
+    def in_contact(self, threshold=0.0):
+        """[n, num_bodies] bool: the floor pushes the body with more than `threshold` N (normal force)."""
+        from .perturb import contact_flags
+        return contact_flags(self.contact_wrench(), threshold)

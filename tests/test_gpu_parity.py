@@ -16,6 +16,8 @@ f32 on ill-conditioned contact states, in a summation order that differs from th
 show the v_rsq / v_rcp / series shortcuts are not the cause; the oracle's OWN f32 build is 2.1e-4 .. 3.2e-3 off its f64 build
 on the landing states, scripts/kstep_separation.py). The rate / torque tolerance was 5e-3 until round 3; it is 3e-3 now: 2x the
 measured bound.
+Joint-limit rows (each joint on each stop, stops with contacts, all 25 on a stop, the launch forms with limit rows live) have a file
+of their own at these tolerances, tests/test_gpu_joint_limits.py; test_joint_limit_rows below keeps its ill-conditioned all-lower state.
 """
 import os
 

@@ -1961,64 +1961,97 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
           {
             int jt_;
             static_assert(NJMAX == 25, "the jump table below has 25 entries");
+            // The assembler checks that arithmetic (labels and directives only, no instruction): 7 = where s_getpc points,
+            // 8 = entry 1, 6 = the end of entry K. A preamble that is not 16 bytes or an entry that is not 8 (a VOP3 or
+            // literal encoding of a v_fmac, a long branch) fails the build instead of aiming s_setpc somewhere else.
+#define TREX_JT_END(K) "6:\n\t.if (6b - 8b) != 8 * " #K "\n\t.error \"limit-row jump table: entry " #K " does not end 8 * " #K " bytes after entry 1\"\n\t.endif\n\t"
             asm volatile("s_getpc_b64 vcc\n\t"
+                         "7:\n\t"
                          "s_lshl3_add_u32 %[t], %[j], 8\n\t"
                          "s_add_u32 vcc_lo, vcc_lo, %[t]\n\t"
                          "s_addc_u32 vcc_hi, vcc_hi, 0\n\t"
                          "s_setpc_b64 vcc\n\t"
+                         "8:\n\t"
+                         ".if (8b - 7b) != 16\n\t.error \"limit-row jump table: entry 1 is not 16 bytes after the address s_getpc_b64 returns\"\n\t.endif\n\t"
                          "v_fmac_f32_e32 %[y], %[sd], %[b1]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(1)
                          "v_fmac_f32_e32 %[y], %[sd], %[b2]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(2)
                          "v_fmac_f32_e32 %[y], %[sd], %[b3]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(3)
                          "v_fmac_f32_e32 %[y], %[sd], %[b4]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(4)
                          "v_fmac_f32_e32 %[y], %[sd], %[b5]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(5)
                          "v_fmac_f32_e32 %[y], %[sd], %[b6]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(6)
                          "v_fmac_f32_e32 %[y], %[sd], %[b7]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(7)
                          "v_fmac_f32_e32 %[y], %[sd], %[b8]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(8)
                          "v_fmac_f32_e32 %[y], %[sd], %[b9]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(9)
                          "v_fmac_f32_e32 %[y], %[sd], %[b10]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(10)
                          "v_fmac_f32_e32 %[y], %[sd], %[b11]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(11)
                          "v_fmac_f32_e32 %[y], %[sd], %[b12]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(12)
                          "v_fmac_f32_e32 %[y], %[sd], %[b13]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(13)
                          "v_fmac_f32_e32 %[y], %[sd], %[b14]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(14)
                          "v_fmac_f32_e32 %[y], %[sd], %[b15]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(15)
                          "v_fmac_f32_e32 %[y], %[sd], %[b16]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(16)
                          "v_fmac_f32_e32 %[y], %[sd], %[b17]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(17)
                          "v_fmac_f32_e32 %[y], %[sd], %[b18]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(18)
                          "v_fmac_f32_e32 %[y], %[sd], %[b19]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(19)
                          "v_fmac_f32_e32 %[y], %[sd], %[b20]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(20)
                          "v_fmac_f32_e32 %[y], %[sd], %[b21]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(21)
                          "v_fmac_f32_e32 %[y], %[sd], %[b22]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(22)
                          "v_fmac_f32_e32 %[y], %[sd], %[b23]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(23)
                          "v_fmac_f32_e32 %[y], %[sd], %[b24]\n\t"
                          "s_branch 9f\n\t"
+                         TREX_JT_END(24)
                          "v_fmac_f32_e32 %[y], %[sd], %[b25]\n\t"
                          "9:\n\t"
+                         ".if (9b - 8b) != 8 * 25 - 4\n\t.error \"limit-row jump table: entry 25 (no branch) does not end 8 * 25 - 4 bytes after entry 1\"\n\t.endif\n\t"
                          : [y] "+v"(y), [t] "=&s"(jt_)
                          : [sd] "s"(sd), [j] "s"(j), [b1] "v"(Bm[0]), [b2] "v"(Bm[1]), [b3] "v"(Bm[2]), [b4] "v"(Bm[3]), [b5] "v"(Bm[4]), [b6] "v"(Bm[5]), [b7] "v"(Bm[6]), [b8] "v"(Bm[7]), [b9] "v"(Bm[8]), [b10] "v"(Bm[9]), [b11] "v"(Bm[10]), [b12] "v"(Bm[11]), [b13] "v"(Bm[12]), [b14] "v"(Bm[13]), [b15] "v"(Bm[14]), [b16] "v"(Bm[15]), [b17] "v"(Bm[16]), [b18] "v"(Bm[17]), [b19] "v"(Bm[18]), [b20] "v"(Bm[19]), [b21] "v"(Bm[20]), [b22] "v"(Bm[21]), [b23] "v"(Bm[22]), [b24] "v"(Bm[23]), [b25] "v"(Bm[24])
                          : "vcc", "scc");
+#undef TREX_JT_END
           }
         }
         // motor rows (joints beyond nb are null rows: y = 0, bounds 0), hand-placed: 5 issue slots per row (the compiler's

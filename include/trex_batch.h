@@ -288,6 +288,47 @@ int trex_batch_set_domain(TrexBatch *batch, const float *mass_scale_dev, const f
  * While a wrench is set the step launches run separate kernel instantiations; after NULL the default kernels again. */
 int trex_batch_set_external_wrench(TrexBatch *batch, const float *wrench_dev, void *stream);
 
+/* Actuator model: per-joint control modes, per-env motor gains, stiffness actions (pybullet's setJointMotorControlArray
+ * with POSITION_CONTROL / VELOCITY_CONTROL / TORQUE_CONTROL, its positionGains / velocityGains / forces arguments; the reference's
+ * intended action space "a desired joint angle and stiffness", trex_env.py:30, trex_robot.py:399-401, 420). One motor row per joint
+ * stays; a row is (target position, target velocity, kp, kd, max_force). With all modes POSITION, no gains and stiffness actions
+ * off - the default - nothing of this exists: the kernels, rows and memory are the ones without it.
+ *   - POSITION joint: action = target angle, clipped to the joint limits; target velocity 0; kp, kd, max_force from the gains
+ *     where set, else the model parameters (motor_kp, motor_kd, motor_max_force);
+ *   - VELOCITY joint: action = target velocity (rad/s), clipped to +- max_coordinate_velocity; the row has kp = 0: velocity
+ *     error x kd, bounded by max_force. (pybullet's default velocityGain is 1; here the gain stays the joint's kd - set kd = 1
+ *     for pybullet's default; unpinned: pybullet is not available to compare against);
+ *   - TORQUE joint: action = torque (N m), clipped to +- the joint's max_force, added to the joint force on every substep of the
+ *     env-step; the motor row is a null row. The observation's torque column and the energy penalty use the clipped command;
+ *   - a reset's settle substep (trex_batch_reset / _reset_rows, the episode-limit reset inside a step launch) applies no motor
+ *     and no commanded torque; resets, trex_batch_set_state and trex_batch_set_domain clear neither modes nor gains;
+ *   - trex_batch_debug_step returns TREX_E_INVALID while any of the three is active.
+ *   - the first call that activates any of the three allocates the batch-owned gains buffer and waits for the device once
+ *     (hipDeviceSynchronize: not inside a stream capture); with stiffness actions the step launches also WRITE that buffer
+ *     (the env-step's kp, kd), so two step launches of one batch must not run on two streams at the same time;
+ *   - a batch with warm start (model parameter warmstart > 0) AND an active actuator model steps through the single-env launch
+ *     form at every size (the rows are bitwise those of the pair form); trex_batch_launch_info reports that form.
+ * While any of the three is active the step launches run separate kernel instantiations; after clearing all, the default ones. */
+#define TREX_CTRL_POSITION 0   /* default */
+#define TREX_CTRL_VELOCITY 1
+#define TREX_CTRL_TORQUE   2
+/* mode_host: J ints in observation order, a HOST array, shared by all envs (NULL = all POSITION). A value outside 0..2 returns
+ * TREX_E_INVALID and changes nothing. */
+int trex_batch_set_control_mode(TrexBatch *batch, const int32_t *mode_host);
+/* Per env and joint, observation order, each [N, J] f32 device, each nullable = "the model parameter"; all three NULL clears.
+ * Copied on `stream` into a batch-owned buffer (allocated at the first use of the actuator model: a batch that never uses it
+ * allocates nothing). Values are not validated: a negative value is clamped to 0; a non-finite value (an infinite max_force
+ * included) makes that env non-finite, and containment handles it (done = 1, reward 0, start pose - at every step while the
+ * value stays); no other env is affected. The same holds for a non-finite torque action of a TORQUE joint. A buffer shorter
+ * than N * J floats, host memory or another device's memory returns TREX_E_INVALID before anything is launched. */
+int trex_batch_set_motor_gains(TrexBatch *batch, const float *kp_dev, const float *kd_dev,
+                               const float *max_force_dev, void *stream);
+/* enabled != 0: every action row is [2J]: J targets, then J stiffnesses kp, clipped to [0, kp_max]; kd = sqrt(2 kp)
+ * (trex_robot.py:399-401: kp = 5e-3 gives the default kd = 0.1). They replace the gains' kp and kd for POSITION joints (max_force
+ * stays the gains'); VELOCITY and TORQUE joints ignore their stiffness column. trex_batch_step, _step_rows, _step_many
+ * ([S, N, 2J]) and _time_steps then expect action buffers of 2J columns. kp_max non-finite or < 0 returns TREX_E_INVALID. */
+int trex_batch_set_stiffness_actions(TrexBatch *batch, int enabled, float kp_max);
+
 /* Contact sensor: the floor-contact wrench per env and moving body (pybullet's getContactPoints(bodyA, linkIndexA) -
  * normalForce, lateralFriction1/2 - summed per link; no reference counterpart: foot-contact flags, contact rewards,
  * ground-reaction forces). enabled != 0: the step and reset launches record it (separate kernel instantiations); 0: they stop

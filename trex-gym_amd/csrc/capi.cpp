@@ -23,6 +23,14 @@ hipError_t trex_launch_reset(const TrexDeviceModel *, TrexBatchArrays, int, cons
                              float, float *, hipStream_t, int, float *, float *, int, int, int, float *, float *);
 hipError_t trex_launch_step_many(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, int, int, float *, uint8_t *,
                                  float, float, float, hipStream_t, int, int, int, float *, const float *, float *);
+hipError_t trex_launch_step_act(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, float *, uint8_t *,
+                                float *, float, float, float, hipStream_t, float *, int, int, int, int, float *,
+                                const float *, float *, const TrexActuators *);
+hipError_t trex_launch_step_many_act(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, int, int, float *, uint8_t *,
+                                     float, float, float, hipStream_t, int, int, int, float *, const float *, float *,
+                                     const TrexActuators *);
+hipError_t trex_launch_copy_gains(const TrexDeviceModel *, const float *, const float *, const float *, float *, int, hipStream_t);
+int trex_actuator_floats(void);
 hipError_t trex_launch_pack_state(const TrexDeviceModel *, TrexBatchArrays, int, float *, int, hipStream_t);
 hipError_t trex_launch_head(const TrexDeviceModel *, TrexBatchArrays, int, float *, hipStream_t);
 hipError_t trex_launch_link_transforms(const TrexDeviceModel *, TrexBatchArrays, int, float *, hipStream_t, int);
@@ -37,6 +45,7 @@ int trex_contact_sensor_floats(void);
 int trex_step_lds_bytes(int);
 int trex_step_envs_per_workgroup(int);
 int trex_step_warm_lds_bytes(void);
+int trex_step_single_lds_bytes(void);
 hipError_t trex_launch_render(const TrexRenderArgs &, hipStream_t);
 }
 
@@ -55,6 +64,16 @@ struct TrexBatch {
   float *sens = nullptr;                       // contact sensor [n][trex_contact_sensor_floats()] (trex_batch_set_contact_sensor); first enable
   bool sens_on = false;                        // on: every step and reset launch takes the SENS kernels
   float *sensor() const { return sens_on ? sens : nullptr; }
+  // actuator model (trex_batch_set_control_mode / _set_motor_gains / _set_stiffness_actions): while any of the three is active the
+  // step launches take the ACT kernels; the gains buffer [n][trex_actuator_floats()] exists from the first use of any of them and
+  // then always holds what the launches are to read - the caller's gains, or the model parameters
+  std::vector<int> obs_order;                  // observation slot -> body lane
+  TrexActuators act{nullptr, 0u, 0u, 0, 0.f};
+  bool single_form() const { return warm && act_on(); }   // a warm batch with actuators steps through the single-env form (trex_step.hip)
+  float *gains = nullptr;
+  bool gains_set = false, stiff = false;
+  bool act_on() const { return (act.vel_mask | act.tor_mask) != 0u || gains_set || stiff; }
+  int action_cols() const { return stiff ? 2 * nj : nj; }
   float wd = 1.0f, we = 0.005f, wk = 0.002f;  // trex_env.py:42-44
   bool pen_in_rows = false;                    // trex_batch_set_penalties_in_rows
   int balance_mode = -1;                       // trex_batch_set_wave_balance: -1 auto, 0 off, 1 on
@@ -212,6 +231,32 @@ void fill_device_model(const trex::HostModel &h, TrexDeviceModel &d) {
 }
 
 int check_batch(const TrexBatch *b) { return b ? TREX_OK : fail(TREX_E_INVALID, "null batch"); }
+
+// the gains buffer of a batch whose actuator model is about to be used: allocated on first use, holding the model parameters
+int ensure_gains(TrexBatch *b) {
+  if (b->gains) return TREX_OK;
+  DeviceGuard guard(b->device);
+  void *p = nullptr;
+  HIP_TRY(hipMalloc(&p, (size_t)b->n * trex_actuator_floats() * sizeof(float)));
+  b->allocs.push_back(p);
+  HIP_TRY(trex_launch_copy_gains(b->dmodel, nullptr, nullptr, nullptr, (float *)p, b->n, nullptr));
+  HIP_TRY(hipDeviceSynchronize());   // (in place before a launch on any stream)
+  b->gains = (float *)p;
+  b->act.gains = b->gains;
+  return TREX_OK;
+}
+
+// the step launch of the batch: the ACT kernels while its actuator model is active, else the launches as they were
+hipError_t launch_step(TrexBatch *b, const float *actions, float *obs, float *reward, uint8_t *done, float *penalties,
+                       hipStream_t stream, float *done_f, int obs_stride, int scal_stride, int pen_in_rows) {
+  if (b->act_on()) {
+    b->act.action_cols = b->action_cols();
+    return trex_launch_step_act(b->dmodel, b->arr, b->n, actions, obs, reward, done, penalties, b->wd, b->we, b->wk, stream, done_f,
+                                obs_stride, scal_stride, b->balance(), pen_in_rows, b->warm, b->wrench(), b->sensor(), &b->act);
+  }
+  return trex_launch_step(b->dmodel, b->arr, b->n, actions, obs, reward, done, penalties, b->wd, b->we, b->wk, nullptr, stream, done_f,
+                          obs_stride, scal_stride, b->balance(), pen_in_rows, b->warm, b->wrench(), b->sensor());
+}
 
 int check_device_buffer(TrexBatch *b, const void *p, size_t bytes, const char *what) {
   return trex_check_device_buffer(b->device, b->seen, p, bytes, what);
@@ -429,6 +474,7 @@ int trex_batch_create(const TrexModel *model, int num_envs, int device, TrexBatc
   if (!guard.ok) return fail(TREX_E_HIP, "hipSetDevice failed");
   auto b = std::make_unique<TrexBatch>();
   b->n = num_envs; b->device = device; b->nb = model->host.nb; b->nj = b->nb - 1;
+  b->obs_order = model->host.obs_order;
   auto alloc = [&](size_t bytes, void **p) -> hipError_t {
     hipError_t r = hipMalloc(p, bytes);
     if (r == hipSuccess) { b->allocs.push_back(*p); r = hipMemset(*p, 0, bytes); }
@@ -576,13 +622,12 @@ int trex_batch_step(TrexBatch *b, const float *actions_dev, float *obs_dev, floa
   if (!actions_dev) return fail(TREX_E_INVALID, "trex_batch_step: actions is null");
   DeviceGuard guard(b->device);
   const size_t n = (size_t)b->n;
-  BUF_TRY(actions_dev, n * b->nj * sizeof(float), "trex_batch_step: actions");
+  BUF_TRY(actions_dev, n * b->action_cols() * sizeof(float), "trex_batch_step: actions");
   BUF_TRY(obs_dev, n * 3 * b->nj * sizeof(float), "trex_batch_step: obs");
   BUF_TRY(reward_dev, n * sizeof(float), "trex_batch_step: reward");
   BUF_TRY(done_dev, n, "trex_batch_step: done");
   BUF_TRY(penalties_dev, n * 3 * sizeof(float), "trex_batch_step: penalties");
-  HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, reward_dev, done_dev, penalties_dev, b->wd,
-                           b->we, b->wk, nullptr, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, b->wrench(), b->sensor()));
+  HIP_TRY(launch_step(b, actions_dev, obs_dev, reward_dev, done_dev, penalties_dev, (hipStream_t)stream, nullptr, 3 * b->nj, 1, 0));
   return TREX_OK;
 }
 
@@ -593,14 +638,13 @@ int trex_batch_step_rows(TrexBatch *b, const float *actions_dev, float *rows_dev
   if (row_stride < 3 * b->nj + (b->pen_in_rows ? 5 : 2)) return fail(TREX_E_INVALID, "trex_batch_step_rows: row_stride < 3J + 2 (3J + 5 with penalties in rows)");
   DeviceGuard guard(b->device);
   const size_t n = (size_t)b->n;
-  BUF_TRY(actions_dev, n * b->nj * sizeof(float), "trex_batch_step_rows: actions");
+  BUF_TRY(actions_dev, n * b->action_cols() * sizeof(float), "trex_batch_step_rows: actions");
   BUF_TRY(rows_dev, ((n - 1) * row_stride + 3 * b->nj + (b->pen_in_rows ? 5 : 2)) * sizeof(float), "trex_batch_step_rows: rows");
   BUF_TRY(penalties_dev, n * 3 * sizeof(float), "trex_batch_step_rows: penalties");
   BUF_TRY(done_dev, n, "trex_batch_step_rows: done");
   float *rew = rows_dev + 3 * b->nj;
-  HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, rows_dev, rew, done_dev, penalties_dev, b->wd, b->we,
-                           b->wk, nullptr, (hipStream_t)stream, rew + 1, row_stride, row_stride, b->balance(), b->pen_in_rows ? 1 : 0, b->warm,
-                           b->wrench(), b->sensor()));
+  HIP_TRY(launch_step(b, actions_dev, rows_dev, rew, done_dev, penalties_dev, (hipStream_t)stream, rew + 1, row_stride, row_stride,
+                      b->pen_in_rows ? 1 : 0));
   return TREX_OK;
 }
 
@@ -612,10 +656,17 @@ int trex_batch_step_many(TrexBatch *b, const float *actions_dev, float *rows_dev
   if (row_stride < 3 * b->nj + (b->pen_in_rows ? 5 : 2)) return fail(TREX_E_INVALID, "trex_batch_step_many: row_stride < 3J + 2 (3J + 5 with penalties in rows)");
   DeviceGuard guard(b->device);
   const size_t n = (size_t)b->n, S = (size_t)num_steps;
-  BUF_TRY(actions_dev, S * n * b->nj * sizeof(float), "trex_batch_step_many: actions");
+  BUF_TRY(actions_dev, S * n * b->action_cols() * sizeof(float), "trex_batch_step_many: actions");
   BUF_TRY(rows_dev, ((S * n - 1) * row_stride + 3 * b->nj + (b->pen_in_rows ? 5 : 2)) * sizeof(float), "trex_batch_step_many: rows");
   BUF_TRY(penalties_dev, S * n * 3 * sizeof(float), "trex_batch_step_many: penalties");
   BUF_TRY(done_dev, S * n, "trex_batch_step_many: done");
+  if (b->act_on()) {
+    b->act.action_cols = b->action_cols();
+    HIP_TRY(trex_launch_step_many_act(b->dmodel, b->arr, b->n, actions_dev, rows_dev, row_stride, num_steps, penalties_dev, done_dev,
+                                      b->wd, b->we, b->wk, (hipStream_t)stream, b->balance(), b->nj, b->pen_in_rows ? 1 : 0, b->warm,
+                                      b->wrench(), b->sensor(), &b->act));
+    return TREX_OK;
+  }
   HIP_TRY(trex_launch_step_many(b->dmodel, b->arr, b->n, actions_dev, rows_dev, row_stride, num_steps, penalties_dev, done_dev,
                                 b->wd, b->we, b->wk, (hipStream_t)stream, b->balance(), b->nj, b->pen_in_rows ? 1 : 0, b->warm,
                                 b->wrench(), b->sensor()));
@@ -635,6 +686,8 @@ int trex_batch_debug_step(TrexBatch *b, const float *actions_dev, float *obs_dev
     return fail(TREX_E_INVALID, "trex_batch_debug_step: not available while an external wrench is set");
   if (b->sens_on)   // (nor the contact sensor)
     return fail(TREX_E_INVALID, "trex_batch_debug_step: not available while the contact sensor is on");
+  if (b->act_on())   // (nor the actuator model)
+    return fail(TREX_E_INVALID, "trex_batch_debug_step: not available while control modes, motor gains or stiffness actions are set");
   HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, nullptr, nullptr, nullptr, b->wd, b->we, b->wk,
                            debug_dev, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, nullptr, nullptr));
   return TREX_OK;
@@ -757,6 +810,48 @@ int trex_batch_set_external_wrench(TrexBatch *b, const float *wrench_dev, void *
   return TREX_OK;
 }
 
+int trex_batch_set_control_mode(TrexBatch *b, const int32_t *mode_host) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  uint32_t vel = 0u, tor = 0u;
+  for (int k = 0; mode_host && k < b->nj; k++) {
+    const int32_t m = mode_host[k];
+    if (m < TREX_CTRL_POSITION || m > TREX_CTRL_TORQUE)
+      return fail(TREX_E_INVALID, "trex_batch_set_control_mode: mode " + std::to_string(m) + " of joint " + std::to_string(k) +
+                                      " (0 position, 1 velocity, 2 torque)");
+    if (m == TREX_CTRL_VELOCITY) vel |= 1u << b->obs_order[k];
+    if (m == TREX_CTRL_TORQUE) tor |= 1u << b->obs_order[k];
+  }
+  if ((vel | tor) != 0u)
+    if (int c = ensure_gains(b)) return c;
+  b->act.vel_mask = vel; b->act.tor_mask = tor;
+  return TREX_OK;
+}
+
+int trex_batch_set_motor_gains(TrexBatch *b, const float *kp_dev, const float *kd_dev, const float *max_force_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  DeviceGuard guard(b->device);
+  const size_t bytes = (size_t)b->n * b->nj * sizeof(float);
+  BUF_TRY(kp_dev, bytes, "trex_batch_set_motor_gains: kp");
+  BUF_TRY(kd_dev, bytes, "trex_batch_set_motor_gains: kd");
+  BUF_TRY(max_force_dev, bytes, "trex_batch_set_motor_gains: max_force");
+  const bool any = kp_dev || kd_dev || max_force_dev;
+  if (!any && !b->gains) { b->gains_set = false; return TREX_OK; }   // nothing was ever set: nothing to clear, nothing allocated
+  if (int c = ensure_gains(b)) return c;
+  // (all three NULL: the buffer goes back to the model parameters - control modes and stiffness actions keep reading it)
+  HIP_TRY(trex_launch_copy_gains(b->dmodel, kp_dev, kd_dev, max_force_dev, b->gains, b->n, (hipStream_t)stream));
+  b->gains_set = any;
+  return TREX_OK;
+}
+
+int trex_batch_set_stiffness_actions(TrexBatch *b, int enabled, float kp_max) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!enabled) { b->stiff = false; return TREX_OK; }
+  if (!std::isfinite(kp_max) || kp_max < 0.f) return fail(TREX_E_INVALID, "trex_batch_set_stiffness_actions: kp_max must be finite and >= 0");
+  if (int c = ensure_gains(b)) return c;
+  b->stiff = true; b->act.kp_max = kp_max;
+  return TREX_OK;
+}
+
 int trex_batch_set_contact_sensor(TrexBatch *b, int enabled) {
   if (check_batch(b)) return TREX_E_INVALID;
   if (!enabled) { b->sens_on = false; return TREX_OK; }   // the default kernels again; the buffer stays for the next enable
@@ -796,10 +891,12 @@ int trex_batch_contact_stats(TrexBatch *b, int32_t *count_dev, float *normal_imp
 
 int trex_batch_launch_info(const TrexBatch *b, int *grid, int *block, int *lds_bytes, int *alg_bytes_per_env_step) {
   if (!b) return fail(TREX_E_INVALID, "null batch");
-  const int epw = trex_step_envs_per_workgroup(b->n);
+  // (a warm batch with an active actuator model steps through the single-env form: trex_step.hip)
+  const int epw = b->single_form() ? 1 : trex_step_envs_per_workgroup(b->n);
   if (grid) *grid = (b->n + epw - 1) / epw;
   if (block) *block = 64 * epw;       // one wavefront per env
-  if (lds_bytes) *lds_bytes = trex_step_lds_bytes(b->n) + (b->warm ? epw * trex_step_warm_lds_bytes() : 0);
+  if (lds_bytes) *lds_bytes = (b->single_form() ? trex_step_single_lds_bytes() : trex_step_lds_bytes(b->n)) +
+                              (b->warm ? epw * trex_step_warm_lds_bytes() : 0);
   // state in + out (13 + 2J floats each), action in (J), obs out (3J), reward (4 B), done (padded 4 B): SURVEY 8d
   if (alg_bytes_per_env_step) *alg_bytes_per_env_step = 4 * (2 * (13 + 2 * b->nj) + b->nj + 3 * b->nj + 1 + 1);
   return TREX_OK;
@@ -810,7 +907,7 @@ int trex_batch_time_steps(TrexBatch *b, const float *actions_dev, float *obs_dev
   if (check_batch(b)) return TREX_E_INVALID;
   if (!actions_dev || !avg_ms_out || steps <= 0) return fail(TREX_E_INVALID, "trex_batch_time_steps: bad argument");
   DeviceGuard guard(b->device);
-  BUF_TRY(actions_dev, (size_t)b->n * b->nj * sizeof(float), "trex_batch_time_steps: actions");
+  BUF_TRY(actions_dev, (size_t)b->n * b->action_cols() * sizeof(float), "trex_batch_time_steps: actions");
   BUF_TRY(obs_dev, (size_t)b->n * 3 * b->nj * sizeof(float), "trex_batch_time_steps: obs");
   BUF_TRY(reward_dev, (size_t)b->n * sizeof(float), "trex_batch_time_steps: reward");
   BUF_TRY(done_dev, (size_t)b->n, "trex_batch_time_steps: done");
@@ -820,8 +917,7 @@ int trex_batch_time_steps(TrexBatch *b, const float *actions_dev, float *obs_dev
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipEventRecord(e0, s));
   for (int i = 0; i < steps; i++)
-    HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, reward_dev, done_dev, nullptr, b->wd, b->we,
-                             b->wk, nullptr, s, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, b->wrench(), b->sensor()));
+    HIP_TRY(launch_step(b, actions_dev, obs_dev, reward_dev, done_dev, nullptr, s, nullptr, 3 * b->nj, 1, 0));
   HIP_TRY(hipEventRecord(e1, s));
   HIP_TRY(hipEventSynchronize(e1));
   float ms = 0.f;

@@ -51,6 +51,9 @@
 #ifndef TREX_STAMPS
 #define TREX_STAMPS 0
 #endif
+#ifndef TREX_ACT_TU
+#define TREX_ACT_TU 0   // 1: this text is compiled as trex_step_act.hip - the ACT instantiations of the step body and their launchers only
+#endif
 #ifndef TREX_PAIR_MAX
 #define TREX_PAIR_MAX 4096                   // largest (even) batch the pair form steps
 #endif
@@ -396,8 +399,19 @@ struct KernelArgs {
                           // every other argument keeps its offset
   const float *ext;       // EXT launches: the per-env external wrench [N][6][TREX_TL] (fx fy fz tx ty tz, world axes, at / about the
                           // body's COM; trex_batch_set_external_wrench); after warm for the same reason
-  float *sens;            // SENS launches: the per-env contact sensor [N][SENS_ROWS][TREX_TL] (below; trex_batch_set_contact_sensor); last
+  float *sens;            // SENS launches: the per-env contact sensor [N][SENS_ROWS][TREX_TL] (below; trex_batch_set_contact_sensor)
+  // ACT launches (the actuator model, below): the per-env motor gains [N][ACT_ROWS][TREX_TL], which body lanes' joints are VELOCITY /
+  // TORQUE controlled (bit b = body lane b; wave- and batch-uniform: scalar registers), the width of an action row - J, or 2J with
+  // stiffness actions - and the upper clip of an action's stiffness; last, so that every other argument keeps its offset
+  float *act;             // (not const: with stiffness actions the action decode writes the env-step's kp, kd into rows 4, 5)
+  unsigned act_vel, act_tor;
+  int act_cols;
+  float act_kp_max;
 };
+// ACT rows of an env, per body lane: the joint's motor kp, kd, largest impulse of a substep (max_force * dt) and max_force - the
+// gains as set -, then the kp and kd of the CURRENT env-step under stiffness actions (written by the step's action decode, read by
+// its row set-ups on the same lane: the decode has the registers for the action's address and the square root, the set-up has not)
+constexpr int ACT_GAINS = 4, ACT_ROWS = 6;
 // SENS rows of an env: 0..5 the floor-contact wrench of every body (fx fy fz tx ty tz, world axes, at / about its COM), 6..8 the
 // body's COM of the current substep relative to the base origin (written by the tree phases, read by the env's results pass)
 constexpr int SENS_ROWS = 9;
@@ -450,13 +464,26 @@ constexpr int SENS_ROWS = 9;
 // and read back after the solve: no LDS (the pair workgroup's is spent) and no register lives across the phases. The settle substep
 // of a reset (launch or episode limit) starts afresh; containment stores zeros. Every launch family has a SENS form (reset too),
 // with and without WARM and EXT; nothing the physics reads is written.
+// ACT (the batch has control modes, motor gains or stiffness actions: trex_batch_set_control_mode / _set_motor_gains /
+// _set_stiffness_actions; args.act): the actuator model. One motor row per joint stays; what changes is where its five numbers come
+// from - (target position, target velocity, kp, kd, largest impulse) - and all of it happens in the action decode at the top of an
+// env-step and in the row set-up, once per substep: the sweeps are the code they were. A POSITION joint takes kp, kd and the bound
+// from its env's gains (with stiffness actions: kp from the second half of the action row, kd = sqrt(2 kp)); a VELOCITY joint's action
+// is the row's target velocity, its kp is 0; a TORQUE joint's action (N m, clipped to +- max_force; W.st[ST_TARGET] carries it) is added
+// to the joint force of the tree dynamics on every substep of the env-step - never on the settle substep of an episode-limit reset -,
+// its motor row is a null row (bounds 0, like the rows of an env without motors) and its torque column reports the clipped command.
+// The gains are loaded from global memory where the set-up reads q, the updated rate and the target (one coalesced row each; no LDS:
+// the pair workgroup's is spent). Non-finite gains or torque commands count as a non-finite state (containment, as for EXT).
+// Non-RESET product launches only, in every combination with WARM, EXT and SENS; separate instantiations, compiled in a translation
+// unit of their own (trex_step_act.hip): the kernels without ACT are the code they were.
 #define WSYNC() do { if (PAIR) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); else __syncthreads(); } while (0)
-template <bool RESET, bool DEBUG, bool MULTI, bool PAIR = false, bool WARM = false, bool EXT = false, bool SENS = false>
+template <bool RESET, bool DEBUG, bool MULTI, bool PAIR = false, bool WARM = false, bool EXT = false, bool SENS = false, bool ACT = false>
 __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int wg_in) {   // wg_in: blockIdx.x
   static_assert(!PAIR || (!RESET && !DEBUG && !MULTI), "the pair form exists for the product step launch only");
   static_assert(!(WARM && DEBUG), "the diagnostics dump has no warm-start form");
   static_assert(!EXT || (!RESET && !DEBUG), "the external wrench exists for the product step launches only");
   static_assert(!SENS || !DEBUG, "the diagnostics dump has no contact-sensor form");
+  static_assert(!ACT || (!RESET && !DEBUG), "the actuator model exists for the product step launches only");
   __shared__ WaveLds Wpair[PAIR ? 2 : 1];
   __shared__ __attribute__((aligned(16))) unsigned char Gpair[PAIR ? sizeof(CgLds) : 16];   // PAIR: contact-generation scratch of the workgroup (wave 1)
   const int wave = PAIR ? uni((int)threadIdx.x >> 6) : 0;
@@ -757,6 +784,12 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
 #pragma unroll
       for (int c = 0; c < 6; c++) badl |= is_body && !(fabsf(xw[c * TL]) < 3.0e38f);
     }
+    if constexpr (ACT) {   // so do non-finite gains and a non-finite torque command (the rows' clamps would absorb them)
+      const float *g = args.act + (size_t)env * (ACT_ROWS * TL) + bl;
+#pragma unroll
+      for (int c = 0; c < ACT_GAINS; c++) badl |= is_joint && !(fabsf(g[c * TL]) < 3.0e38f);
+      badl |= is_joint && !(fabsf(W.st[ST_TARGET][bl]) < 3.0e38f);
+    }
     env_bad = bad || (__ballot(badl) != 0ull);
   };
   auto to_start_pose = [&]() {
@@ -783,8 +816,30 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
       float target = 0.f;
       if (l >= 1 && l < nb) {
         const TrexDeviceModel *Mi = Mo();
+        if constexpr (ACT) {   // the command of this joint by its mode: angle, velocity or torque, each clipped to its own range
+          const float a = args.actions[((size_t)(MULTI ? ls : 0) * args.n_envs + env) * args.act_cols + Mi->obs_slot[l]];
+          const unsigned bit = 1u << l;
+          if (args.act_vel & bit) {
+            const float vm = Mi->prm[TP_MAX_COORD_VEL];
+            target = fminf(fmaxf(a, -vm), vm);
+          } else if (args.act_tor & bit) {
+            const float F = args.act[(size_t)env * (ACT_ROWS * TL) + 3 * TL + l];
+            target = fabsf(a) < 3.0e38f ? fminf(fmaxf(a, -F), F) : a;   // (a non-finite torque is kept: the env is contained)
+          } else target = fminf(fmaxf(a, Mi->lower[l]), Mi->upper[l]);
+          if (args.act_cols > nj) {   // stiffness actions: a POSITION joint's kp from the second half of the row, critically damped
+            float *g = args.act + (size_t)env * (ACT_ROWS * TL) + l;
+            float kp = g[0], kd = g[TL];
+            if (!((args.act_vel | args.act_tor) & bit)) {
+              const float ka = args.actions[((size_t)(MULTI ? ls : 0) * args.n_envs + env) * args.act_cols + nj + Mi->obs_slot[l]];
+              kp = fminf(fmaxf(ka, 0.f), args.act_kp_max);
+              kd = sqrtf(2.f * kp);
+            }
+            g[4 * TL] = kp; g[5 * TL] = kd;
+          }
+        } else {
         const float a = args.actions[((size_t)(MULTI ? ls : 0) * args.n_envs + env) * nj + Mi->obs_slot[l]];
         target = fminf(fmaxf(a, Mi->lower[l]), Mi->upper[l]);
+        }
       }
       W.st[ST_TARGET][l] = target;
     }
@@ -1392,7 +1447,10 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
     // per level; nothing of this is carried in registers between levels. Level 0 is the base: it only sums.
     {
       const TrexDeviceModel *Mi = Mo();
-      const float tau_j = -Mi->damp[bl] * H->st[ST_QD][bl];  // explicit joint damping torque
+      float tau_j = -Mi->damp[bl] * H->st[ST_QD][bl];  // explicit joint damping torque
+      if constexpr (ACT) {   // ... and the commanded torque of a TORQUE joint (not on the settle substep of a reset)
+        if (sub < n_sub && ((args.act_tor >> bl) & 1u)) tau_j += H->st[ST_TARGET][bl];
+      }
       for (int d = maxdepth; d >= 0; d--) {
         if (depth == d) {
           float *o = H->u.t.aba[bl];
@@ -1718,11 +1776,26 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
         y = (tv - (jv + dot3(dir, pv))) * inv0;
       }
       if (mrow) {
-        const float erp = Mi->prm[TP_ERP], kp = Mi->prm[TP_MOTOR_KP], kd = Mi->prm[TP_MOTOR_KD];
-        const float max_imp = Mi->motor_max_impulse;
-        const float q = W.st[ST_Q][bl], nqd = W.st[ST_NQD][bl], target = W.st[ST_TARGET][bl];
+        const float erp = Mi->prm[TP_ERP];
+        float kp = Mi->prm[TP_MOTOR_KP], kd = Mi->prm[TP_MOTOR_KD];
+        float max_imp = Mi->motor_max_impulse;
+        const float q = W.st[ST_Q][bl], nqd = W.st[ST_NQD][bl];
+        float target = W.st[ST_TARGET][bl], vt = 0.f;
+        if constexpr (ACT) {   // this env's gains of the joint; by mode: which of them the row uses, and what its command is
+          const float *g = args.act + (size_t)env * (ACT_ROWS * TL) + bl;
+          const int so = args.act_cols > nj ? 4 * TL : 0;   // (stiffness actions: the kp, kd the action decode of this env-step left)
+          kp = g[so]; kd = g[so + TL]; max_imp = g[2 * TL];
+          const unsigned bit = 1u << bl;
+          if (args.act_vel & bit) { vt = target; target = q; kp = 0.f; }
+          else if (args.act_tor & bit) { target = q; kp = 0.f; kd = 0.f; max_imp = 0.f; }
+        }
         W.st[ST_MDG][bl] = diag;
-        // btMultiBodyJointMotor velocity target: kp*(target-q)/dt + qd + kd*(0-qd), minus current qd
+        // btMultiBodyJointMotor velocity target: kp*(target-q)/dt + qd + kd*(vt-qd), minus current qd (vt = 0 but for a VELOCITY joint)
+        if constexpr (ACT) {
+          // (the contraction is spelled out as the compiler fuses the sum below in every kernel without ACT - left to itself it fused
+          // this one the other way round in some instantiations -: gains equal to the model parameters give those kernels' rows bitwise)
+          y = __builtin_fmaf(kd, vt - nqd, kp * (target - q) * inv_dt) * inv0;
+        } else
         y = (kp * (target - q) * inv_dt + kd * (0.f - nqd)) * inv0;
         mhi = motors_on ? max_imp : 0.f;
         const float q_lo = Mi->lower[bl], q_hi = Mi->upper[bl];
@@ -2340,7 +2413,11 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
     if (lt < TL) {
       const float qd = is_joint ? W.st[ST_NQD][lt] + dv : 0.f;
       W.st[ST_QD][lt] = qd;
-      W.st[ST_TAU][lt] = (mrow && motors_on) ? lam * inv_dt : 0.f;
+      float mtau = lam * inv_dt;
+      if constexpr (ACT) {   // a TORQUE joint reports its (clipped) command
+        if ((args.act_tor >> lt) & 1u) mtau = W.st[ST_TARGET][lt];
+      }
+      W.st[ST_TAU][lt] = (mrow && motors_on) ? mtau : 0.f;
       W.st[ST_Q][lt] += qd * dt;
     }
 #pragma unroll
@@ -2481,6 +2558,7 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
   }
 }
 
+#if !TREX_ACT_TU
 template <bool RESET, bool DEBUG>
 __global__ __launch_bounds__(64, 4) void trex_step_kernel(KernelArgs args) { trex_step_body<RESET, DEBUG, false>(args, (int)blockIdx.x); }
 // two envs per workgroup with split roles between the barriers of a substep (PAIR above): even batches of at most 4096 envs
@@ -2680,6 +2758,24 @@ __global__ void trex_copy_wrench_kernel(const float *src, float *dst, int n, int
   const int e = i / (6 * TL), c = (i / TL) % 6, l = i % TL;
   dst[i] = l < nb ? src[((size_t)e * nb + l) * 6 + c] : 0.0f;
 }
+__global__ void trex_copy_gains_kernel(const TrexDeviceModel *M, const float *kp, const float *kd, const float *max_force, float *dst, int n) {
+  // three [N, J] arrays in observation order, each nullable = the model parameter -> the first four of [N, ACT_ROWS, 32] (row per gain: the
+  // step's body lanes load one coalesced row per gain); a negative value is clamped to 0, a non-finite one is kept (the step
+  // contains that env); max_force also as the largest impulse of a substep, the product the model's motor_max_impulse is
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * TL) return;
+  const int e = i / TL, l = i % TL, nj = M->nb - 1;
+  float v[ACT_ROWS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (l >= 1 && l < M->nb) {
+    const size_t at = (size_t)e * nj + M->obs_slot[l];
+    const float p = kp ? kp[at] : M->prm[TP_MOTOR_KP], d = kd ? kd[at] : M->prm[TP_MOTOR_KD];
+    const float f = max_force ? max_force[at] : M->prm[TP_MOTOR_MAX_FORCE];
+    v[0] = p < 0.f ? 0.f : p; v[1] = d < 0.f ? 0.f : d; v[3] = f < 0.f ? 0.f : f;
+    v[2] = v[3] * M->prm[TP_DT];
+  }
+#pragma unroll
+  for (int c = 0; c < ACT_ROWS; c++) dst[((size_t)e * ACT_ROWS + c) * TL + l] = v[c];
+}
 __global__ void trex_contact_wrench_kernel(const float *src, float *dst, int n, int nb) {
   // the sensor's rows 0..5 [N, SENS_ROWS, 32] -> [N, nb, 6]
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2838,6 +2934,12 @@ hipError_t trex_launch_contact_wrench(const float *src, float *dst, int n, int n
   hipLaunchKernelGGL(trex_contact_wrench_kernel, dim3((n * nb * 6 + 255) / 256), dim3(256), 0, stream, src, dst, n, nb);
   return hipGetLastError();
 }
+hipError_t trex_launch_copy_gains(const TrexDeviceModel *model, const float *kp, const float *kd, const float *max_force, float *dst,
+                                  int n, hipStream_t stream) {
+  hipLaunchKernelGGL(trex_copy_gains_kernel, dim3((n * TL + 255) / 256), dim3(256), 0, stream, model, kp, kd, max_force, dst, n);
+  return hipGetLastError();
+}
+int trex_actuator_floats(void) { return ACT_ROWS * TL; }   // per env: the batch's motor-gain buffer (capi.cpp)
 hipError_t trex_launch_copy_wrench(const float *src, float *dst, int n, int nb, hipStream_t stream) {
   hipLaunchKernelGGL(trex_copy_wrench_kernel, dim3((n * 6 * TL + 255) / 256), dim3(256), 0, stream, src, dst, n, nb);
   return hipGetLastError();
@@ -2847,6 +2949,81 @@ hipError_t trex_launch_copy_wrench(const float *src, float *dst, int n, int nb, 
 int trex_step_envs_per_workgroup(int n) { return trex_pair_launch(n) ? 2 : 1; }
 int trex_step_lds_bytes(int n) { return trex_step_envs_per_workgroup(n) == 2 ? (int)(2 * sizeof(WaveLds) + sizeof(CgLds)) : (int)sizeof(WaveLds); }
 int trex_contact_sensor_floats(void) { return SENS_ROWS * TL; }   // per env: the batch's contact-sensor buffer (capi.cpp)
+int trex_step_single_lds_bytes(void) { return (int)sizeof(WaveLds); }   // the single-env form's, whatever the batch size
 int trex_step_warm_lds_bytes(void) { return (int)(MAXC * sizeof(float4)); }   // per env, on top of the above in the warm kernels
 
 }  // extern "C"
+
+#elif TREX_ACT_TU == 1   // the product step launches with the actuator model (ACT above), with and without WARM, EXT and SENS
+#if !TREX_STAMPS   // (the stamped diagnostic build launches none of them and instantiates none)
+template <bool WARM, bool EXT, bool SENS>
+__global__ __launch_bounds__(64, 4) void trex_step_act_kernel(KernelArgs args) { trex_step_body<false, false, false, false, WARM, EXT, SENS, true>(args, (int)blockIdx.x); }
+// (the pair form without WARM only: with the warm-start record and the gains the pair form's row set-up no longer fits 128 registers -
+// 36 bytes of scratch per lane in three of its four instantiations -, so a warm batch with actuators steps through the single-env
+// form, whose rows are bitwise the same)
+template <bool WARM, bool EXT, bool SENS>
+__global__ __launch_bounds__(128, 4) void trex_step_pair_act_kernel(KernelArgs args) {
+  static_assert(!WARM, "no pair form with WARM and ACT");
+  trex_step_body<false, false, false, true, false, EXT, SENS, true>(args, (int)blockIdx.x);
+}
+template <bool WARM, bool EXT, bool SENS>
+__global__ __launch_bounds__(64, 4) void trex_step_many_act_kernel(KernelArgs args) { trex_step_body<false, false, true, false, WARM, EXT, SENS, true>(args, (int)blockIdx.x); }
+#define TREX_ACT_LAUNCH(K, g, b)                                                                        \
+  switch ((a.warm ? 4 : 0) | (a.ext ? 2 : 0) | (a.sens ? 1 : 0)) {                                      \
+    case 0: hipLaunchKernelGGL((K<false, false, false>), g, b, 0, stream, a); break;                    \
+    case 1: hipLaunchKernelGGL((K<false, false, true>), g, b, 0, stream, a); break;                     \
+    case 2: hipLaunchKernelGGL((K<false, true, false>), g, b, 0, stream, a); break;                     \
+    case 3: hipLaunchKernelGGL((K<false, true, true>), g, b, 0, stream, a); break;                      \
+    case 4: hipLaunchKernelGGL((K<true, false, false>), g, b, 0, stream, a); break;                     \
+    case 5: hipLaunchKernelGGL((K<true, false, true>), g, b, 0, stream, a); break;                      \
+    case 6: hipLaunchKernelGGL((K<true, true, false>), g, b, 0, stream, a); break;                      \
+    default: hipLaunchKernelGGL((K<true, true, true>), g, b, 0, stream, a); break;                      \
+  }
+#endif
+
+extern "C" {
+
+// trex_launch_step / trex_launch_step_many for a batch whose actuator model is active (capi.cpp decides): the same arguments and
+// the actuators (device_model.h); the pair form for the same batches
+hipError_t trex_launch_step_act(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions,
+                                float *obs, float *reward, uint8_t *done, float *penalties, float wd, float we,
+                                float wk, hipStream_t stream, float *done_f, int obs_stride, int scal_stride,
+                                int balance, int pen_in_rows, float *warm, const float *ext, float *sens, const TrexActuators *act) {
+  if (!act || !act->gains) return hipErrorInvalidValue;
+#if TREX_STAMPS
+  return hipErrorInvalidValue;
+#else
+  KernelArgs a{model, arr, n, actions, obs, reward, done, done_f, obs_stride, scal_stride, penalties, nullptr,
+               balance ? arr.balance : nullptr, wd, we, wk, nullptr, 1, 0, pen_in_rows, warm, ext, sens,
+               act->gains, act->vel_mask, act->tor_mask, act->action_cols, act->kp_max};
+  if (TREX_PAIR_LAUNCH && (n & 1) == 0 && n <= TREX_PAIR_MAX && !warm) {
+    switch ((a.ext ? 2 : 0) | (a.sens ? 1 : 0)) {
+      case 0: hipLaunchKernelGGL((trex_step_pair_act_kernel<false, false, false>), dim3(n / 2), dim3(128), 0, stream, a); break;
+      case 1: hipLaunchKernelGGL((trex_step_pair_act_kernel<false, false, true>), dim3(n / 2), dim3(128), 0, stream, a); break;
+      case 2: hipLaunchKernelGGL((trex_step_pair_act_kernel<false, true, false>), dim3(n / 2), dim3(128), 0, stream, a); break;
+      default: hipLaunchKernelGGL((trex_step_pair_act_kernel<false, true, true>), dim3(n / 2), dim3(128), 0, stream, a); break;
+    }
+  } else { TREX_ACT_LAUNCH(trex_step_act_kernel, dim3(n), dim3(64)) }
+  return hipGetLastError();
+#endif
+}
+
+hipError_t trex_launch_step_many_act(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions, float *rows,
+                                     int row_stride, int n_steps, float *penalties, uint8_t *done, float wd, float we, float wk,
+                                     hipStream_t stream, int balance, int nj, int pen_in_rows, float *warm, const float *ext,
+                                     float *sens, const TrexActuators *act) {
+  if (!act || !act->gains) return hipErrorInvalidValue;
+#if TREX_STAMPS
+  return hipErrorInvalidValue;
+#else
+  float *rew = rows + 3 * nj;
+  KernelArgs a{model, arr, n, actions, rows, rew, done, rew + 1, row_stride, row_stride, penalties, nullptr,
+               balance ? arr.balance : nullptr, wd, we, wk, nullptr, n_steps, (long long)n * row_stride, pen_in_rows, warm, ext, sens,
+               act->gains, act->vel_mask, act->tor_mask, act->action_cols, act->kp_max};
+  TREX_ACT_LAUNCH(trex_step_many_act_kernel, dim3(n), dim3(64))
+  return hipGetLastError();
+#endif
+}
+
+}  // extern "C"
+#endif   // TREX_ACT_TU

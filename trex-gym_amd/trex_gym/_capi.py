@@ -41,6 +41,7 @@ SYMBOLS = [
     "trex_batch_set_wave_balance", "trex_batch_forget_buffers", "trex_batch_set_penalties_in_rows",
     "trex_model_num_visuals", "trex_model_visual_info", "trex_batch_visual_transforms", "trex_batch_step_many",
     "trex_batch_render", "trex_batch_set_external_wrench", "trex_batch_set_contact_sensor", "trex_batch_contact_wrench",
+    "trex_batch_set_control_mode", "trex_batch_set_motor_gains", "trex_batch_set_stiffness_actions",
 ]
 
 # every symbol include/trex_policy.h declares (the trainer-side kernels)
@@ -92,6 +93,10 @@ lib.trex_batch_head_position.argtypes = [_vp, _vp, _vp]
 lib.trex_batch_set_domain.argtypes = [_vp, _vp, _vp, _vp]
 lib.trex_batch_set_external_wrench.argtypes = [_vp, _vp, _vp]
 lib.trex_batch_set_contact_sensor.argtypes = [_vp, C.c_int]
+if hasattr(lib, "trex_batch_set_control_mode"):   # (a TREX_LIB built from an older tree - scripts/actuator_bench.py's A/B - has no
+    lib.trex_batch_set_control_mode.argtypes = [_vp, C.POINTER(C.c_int32)]           # actuator model: using it there raises)
+    lib.trex_batch_set_motor_gains.argtypes = [_vp, _vp, _vp, _vp, _vp]
+    lib.trex_batch_set_stiffness_actions.argtypes = [_vp, C.c_int, C.c_float]
 lib.trex_batch_contact_wrench.argtypes = [_vp, _vp, _vp]
 lib.trex_model_use_primitive_collision.argtypes = [_vp, C.c_double, C.c_int, C.c_int]
 lib.trex_model_fit_hull_primitives.argtypes = [_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
@@ -276,6 +281,7 @@ class Batch:
         check(lib.trex_batch_create(model.h, self.num_envs, self.device, C.byref(h)))
         self.h = h
         self.J = model.num_joints
+        self.A = self.J                 # columns of an action row: J, or 2J with stiffness actions
         self.state_width = 13 + 2 * self.J
 
     def close(self):
@@ -331,7 +337,7 @@ class Batch:
 
     def step(self, actions, obs, reward, done, penalties=None, stream=None):
         n, J = self.num_envs, self.J
-        check(lib.trex_batch_step(self.h, self._p(actions, "float32", n * J, "actions"), self._p(obs, "float32", n * 3 * J, "obs"),
+        check(lib.trex_batch_step(self.h, self._p(actions, "float32", n * self.A, "actions"), self._p(obs, "float32", n * 3 * J, "obs"),
                                   self._p(reward, "float32", n, "reward"), self._p(done, "uint8", n, "done"),
                                   self._p(penalties, "float32", 3 * n, "penalties"), self._stream(stream)))
 
@@ -342,7 +348,7 @@ class Batch:
         n, J = self.num_envs, self.J
         if done is not None and done.dtype not in (torch.uint8, torch.bool):
             raise TrexError(E_INVALID, "done: expected dtype uint8 or bool, got %s" % done.dtype)
-        check(lib.trex_batch_step_rows(self.h, self._p(actions, "float32", n * J, "actions"),
+        check(lib.trex_batch_step_rows(self.h, self._p(actions, "float32", n * self.A, "actions"),
                                        self._p(rows, "float32", (n - 1) * rows.shape[1] + 3 * J + (5 if self.pen_in_rows else 2), "rows"), int(rows.shape[1]),
                                        self._p(penalties, "float32", 3 * n, "penalties"),
                                        _ptr(done, self.device, None, n, "done"), self._stream(stream)))
@@ -355,7 +361,7 @@ class Batch:
             raise TrexError(E_INVALID, "done: expected dtype uint8 or bool, got %s" % done.dtype)
         if rows.dim() != 3 or int(rows.shape[0]) != S or int(rows.shape[1]) != n:
             raise TrexError(E_INVALID, "rows: expected shape [%d, %d, >= %d], got %s" % (S, n, 3 * J + 2, tuple(rows.shape)))
-        check(lib.trex_batch_step_many(self.h, self._p(actions, "float32", S * n * J, "actions"),
+        check(lib.trex_batch_step_many(self.h, self._p(actions, "float32", S * n * self.A, "actions"),
                                        self._p(rows, "float32", (S * n - 1) * rows.shape[2] + 3 * J + (5 if self.pen_in_rows else 2), "rows"), int(rows.shape[2]), S,
                                        self._p(penalties, "float32", 3 * S * n, "penalties"), _ptr(done, self.device, None, S * n, "done"),
                                        self._stream(stream)))
@@ -376,7 +382,7 @@ class Batch:
 
     def debug_step(self, actions, obs, debug, stream=None):
         n, J = self.num_envs, self.J
-        check(lib.trex_batch_debug_step(self.h, self._p(actions, "float32", n * J, "actions"),
+        check(lib.trex_batch_debug_step(self.h, self._p(actions, "float32", n * self.A, "actions"),
                                         self._p(obs, "float32", n * 3 * J, "obs"), self._p(debug, "float32", 4096, "debug"),
                                         self._stream(stream)))
 
@@ -415,6 +421,43 @@ class Batch:
                 raise TrexError(E_INVALID, "wrench: expected shape %s, got %s" % (shape, tuple(wrench.shape)))
         check(lib.trex_batch_set_external_wrench(self.h, self._p(wrench, "float32", self.num_envs * self.model.num_bodies * 6,
                                                                  "wrench"), self._stream(stream)))
+
+    from .actuators import CONTROL_MODES     # TREX_CTRL_*
+
+    def set_control_mode(self, modes=None):
+        """Per-joint control modes, shared by all envs: a sequence of J ints (0 position, 1 velocity, 2 torque) or mode names
+        in observation order, or None = all position (include/trex_batch.h)."""
+        if modes is None:
+            check(lib.trex_batch_set_control_mode(self.h, None))
+            return
+        modes = list(modes)
+        if len(modes) != self.J:
+            raise TrexError(E_INVALID, "modes: expected %d entries, got %d" % (self.J, len(modes)))
+        vals = []
+        for m in modes:
+            if isinstance(m, str):
+                if m not in self.CONTROL_MODES:
+                    raise TrexError(E_INVALID, "modes: unknown control mode %r (position, velocity, torque)" % (m,))
+                m = self.CONTROL_MODES[m]
+            vals.append(int(m))
+        check(lib.trex_batch_set_control_mode(self.h, (C.c_int32 * self.J)(*vals)))
+
+    def set_motor_gains(self, kp=None, kd=None, max_force=None, stream=None):
+        """Per-env, per-joint motor gains, each [n, J] f32 on the batch's device in observation order, or None = the model
+        parameter; all three None clears (include/trex_batch.h). Copied."""
+        shape = (self.num_envs, self.J)
+        for name, t in (("kp", kp), ("kd", kd), ("max_force", max_force)):
+            if t is not None and tuple(t.shape) != shape:
+                raise TrexError(E_INVALID, "%s: expected shape %s, got %s" % (name, shape, tuple(t.shape)))
+        nJ = self.num_envs * self.J
+        check(lib.trex_batch_set_motor_gains(self.h, self._p(kp, "float32", nJ, "kp"), self._p(kd, "float32", nJ, "kd"),
+                                             self._p(max_force, "float32", nJ, "max_force"), self._stream(stream)))
+
+    def set_stiffness_actions(self, enabled=True, kp_max=1.0):
+        """On: every action row is [2J] - J targets, then J stiffnesses kp clipped to [0, kp_max], kd = sqrt(2 kp) - in step,
+        step_rows, step_many and time_steps (include/trex_batch.h); off: [J] again."""
+        check(lib.trex_batch_set_stiffness_actions(self.h, 1 if enabled else 0, float(kp_max)))
+        self.A = 2 * self.J if enabled else self.J
 
     def set_contact_sensor(self, enabled=True):
         """On: the step and reset launches record each env's floor-contact wrench per body (include/trex_batch.h);
@@ -465,7 +508,7 @@ class Batch:
     def time_steps(self, actions, obs, reward, done, steps, stream=None):
         ms = C.c_float()
         n, J = self.num_envs, self.J
-        check(lib.trex_batch_time_steps(self.h, self._p(actions, "float32", n * J, "actions"), self._p(obs, "float32", n * 3 * J, "obs"),
+        check(lib.trex_batch_time_steps(self.h, self._p(actions, "float32", n * self.A, "actions"), self._p(obs, "float32", n * 3 * J, "obs"),
                                         self._p(reward, "float32", n, "reward"), self._p(done, "uint8", n, "done"), int(steps),
                                         self._stream(stream), C.byref(ms)))
         return ms.value

@@ -157,3 +157,35 @@ class RandomPushes:
         w = torch.zeros(self.num_envs, num_bodies, 6, device=self.device)
         w[:, self.body, :3] = self.step(done)
         return w
+
+
+class RandomGains:
+    """Per-env motor strength and gain randomisation, beside RandomPushes: every env that is reset draws one scale for kp, one
+    for kd and one for max_force, uniform in the given (low, high) ranges, applied to the nominal values of all its joints
+    (domain randomisation of the actuators; sim-to-real work randomises these first). draw(mask) returns the [n, J] tensors
+    for TrexVecEnv.set_motor_gains(**...): envs with mask == 0 keep their last draw. TrexVecEnv(...).gains = RandomGains(...)
+    makes reset_tensor() draw and apply them."""
+
+    def __init__(self, num_envs, num_joints, kp=5e-3, kd=0.1, max_force=3e5, kp_scale=(0.8, 1.2), kd_scale=(0.8, 1.2),
+                 max_force_scale=(0.8, 1.2), generator=None, device=None):
+        for name, (lo, hi) in (("kp_scale", kp_scale), ("kd_scale", kd_scale), ("max_force_scale", max_force_scale)):
+            if not 0.0 <= lo <= hi:
+                raise ValueError("%s: expected 0 <= low <= high, got (%g, %g)" % (name, lo, hi))
+        self.num_envs, self.num_joints = int(num_envs), int(num_joints)
+        if device is None:
+            device = generator.device if generator is not None else torch.device("cpu")
+        self.device = torch.device(device)
+        self.generator = generator
+        self.nominal = (float(kp), float(kd), float(max_force))
+        self.ranges = (tuple(kp_scale), tuple(kd_scale), tuple(max_force_scale))
+        self.scale = torch.ones(3, self.num_envs, device=self.device)        # kp, kd, max_force scale of every env
+
+    def draw(self, mask=None):
+        u = torch.rand(3, self.num_envs, generator=self.generator, device=self.device)
+        lo = torch.tensor([r[0] for r in self.ranges], device=self.device).unsqueeze(1)
+        hi = torch.tensor([r[1] for r in self.ranges], device=self.device).unsqueeze(1)
+        new = lo + (hi - lo) * u
+        self.scale = new if mask is None else torch.where(mask.to(self.device).bool().unsqueeze(0), new, self.scale)
+        out = [(v * self.scale[k]).unsqueeze(1).expand(self.num_envs, self.num_joints).contiguous()
+               for k, v in enumerate(self.nominal)]
+        return dict(kp=out[0], kd=out[1], max_force=out[2])

@@ -25,7 +25,8 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
     }
 
     def __init__(self, urdf_path=None, action_repeat=1, distance_weight=1.0, energy_weight=0.005,
-                 drift_weight=0.002, render=False, device=None, contact_sensor=False):
+                 drift_weight=0.002, render=False, device=None, contact_sensor=False, control_mode=None,
+                 variable_stiffness=False, kp_max=1.0):
         if render:   # (the reference's render=True opens pybullet's GUI; rgb_array frames need no flag: render())
             raise NotImplementedError("render=True asks for a GUI, which this env has not; render('rgb_array') draws frames")
         self._time_step = 0.01 / NUM_SUBSTEPS
@@ -47,7 +48,8 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
         self._vec = TrexVecEnv(1, urdf_path=urdf_path, device=device, action_repeat=action_repeat,
                                distance_weight=distance_weight, energy_weight=energy_weight,
                                drift_weight=drift_weight,
-                               starting_configuration=self._starting_configuration)
+                               starting_configuration=self._starting_configuration, control_mode=control_mode,
+                               variable_stiffness=variable_stiffness, kp_max=kp_max)
         self.model = trex_robot.TrexRobot(self._vec, 0)
         self._sensor_on = bool(contact_sensor)   # (contact_wrench(); off: the default kernels)
         if self._sensor_on:
@@ -57,6 +59,8 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
         self.reset()
         action_low, action_high = self.model.get_action_limits()
         self.action_space = spaces.Box(low=action_low, high=action_high, dtype=np.float32)
+        if any(self._vec.control_modes) or self._vec.variable_stiffness:   # what the joints' modes make of an action (TrexVecEnv)
+            self.action_space = self._vec.action_space
         observation_low, observation_high = self.model.get_observation_limits()
         self.observation_space = spaces.Box(low=observation_low, high=observation_high, dtype=np.float32)
 
@@ -72,10 +76,11 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
 
     def step(self, action):
         action = np.asarray(action, dtype=np.float32).reshape(-1)
-        if action.shape[0] < self._vec.J:
+        if action.shape[0] < self._vec.A:
             raise ValueError("The action dimension is not the same as the number of motors.")
-        # only the first J entries are joint targets (trex_robot.py:418-421); the kernel clips
-        a = torch.from_numpy(action[: self._vec.J].copy()).reshape(1, -1)
+        # only the first J entries are joint targets (trex_robot.py:418-421; with variable_stiffness the next J are the
+        # stiffnesses, trex_robot.py:420); the kernel clips
+        a = torch.from_numpy(action[: self._vec.A].copy()).reshape(1, -1)
         self._vec.step_tensor(a)
         self._env_step_counter += 1
         self._observation = self.model.get_observations()
@@ -90,6 +95,10 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
         from .render import Camera
         rgb = self._vec.render_tensor([0], RENDER_WIDTH, RENDER_HEIGHT, Camera())
         return rgb[0].cpu().numpy()
+
+    def set_motor_gains(self, kp=None, kd=None, max_force=None):
+        """Motor gains per joint: scalars or [J] in observation order, None = the model parameter (TrexVecEnv.set_motor_gains)."""
+        self._vec.set_motor_gains(kp, kd, max_force)
 
     def contact_wrench(self):
         """[num_bodies, 6] numpy: the floor-contact wrench per body of the last step (force at the body's COM, torque

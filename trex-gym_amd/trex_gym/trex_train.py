@@ -14,7 +14,8 @@ import sys
 
 import torch
 
-from .perturb import RandomPushes
+from . import actuators
+from .perturb import RandomGains, RandomPushes
 from .ppo import PPO
 from .vec_env import TrexVecEnv
 
@@ -22,7 +23,11 @@ _URDF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ass
 
 
 def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0, push_force=0.0, push_interval=100,
-                      push_duration=5, push_probability=1.0, seed=0):   # (weights of trex_train.py:66)
+                      push_duration=5, push_probability=1.0, seed=0, control_mode=None, variable_stiffness=False,
+                      gain_scale=0.0):   # (weights of trex_train.py:66)
+    # control_mode: what the joints' actions mean (position / velocity / torque: J-wide, through the trainer unchanged). The
+    # 2J-wide stiffness action space is wider than the policy kernel's act_dim <= 32: refused here, not deep in a launch
+    check_action_space(control_mode, variable_stiffness)
     # warmstart > 0: the contact solver starts from that fraction of each point's impulses of the last solve (model parameter)
     params = {"warmstart": float(warmstart)} if warmstart else None
     # push_force > 0: random horizontal pushes of the base, up to push_force N, every push_interval env-steps for
@@ -33,8 +38,25 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
         gen = torch.Generator(device=dev).manual_seed(int(seed))
         pushes = RandomPushes(num_envs, body=0, interval=push_interval, probability=push_probability, max_force=push_force,
                               duration=push_duration, generator=gen, device=dev)
-    return TrexVecEnv(num_envs, urdf_path=_URDF_PATH, device=device, distance_weight=2e2, energy_weight=1e-6,
-                      drift_weight=1.0, max_episode_steps=max_episode_steps, params=params, pushes=pushes)
+    env = TrexVecEnv(num_envs, urdf_path=_URDF_PATH, device=device, distance_weight=2e2, energy_weight=1e-6,
+                     drift_weight=1.0, max_episode_steps=max_episode_steps, params=params, pushes=pushes, control_mode=control_mode)
+    if gain_scale > 0:   # every episode with motor gains and strength scaled by 1 +- gain_scale per env (RandomGains)
+        dev = torch.device(device)
+        r = (1.0 - gain_scale, 1.0 + gain_scale)
+        env.gains = RandomGains(env.num_envs, env.J, kp_scale=r, kd_scale=r, max_force_scale=r,
+                                generator=torch.Generator(device=dev).manual_seed(int(seed) + 1), device=dev)
+    return env
+
+
+POLICY_MAX_ACT_DIM = 32      # the policy kernel's widest action (csrc/policy_step.hip)
+
+
+def check_action_space(control_mode, variable_stiffness, num_joints=25):
+    if control_mode is not None and not isinstance(control_mode, (dict, list, tuple)) and control_mode not in actuators.CONTROL_MODES:
+        raise ValueError("--control_mode: expected one of %s, got %r" % (", ".join(actuators.CONTROL_MODES), control_mode))
+    if variable_stiffness and 2 * num_joints > POLICY_MAX_ACT_DIM:
+        raise ValueError("variable stiffness makes the action space %d wide; the policy kernel takes at most %d: "
+                         "not supported by this trainer" % (2 * num_joints, POLICY_MAX_ACT_DIM))
 
 
 # Hyper-parameter presets. "reference" is the ppo2.learn call of the reference's script (trex_train.py:47-60):
@@ -157,7 +179,18 @@ def parse_args(argv=None):
                     help="random horizontal pushes of the base of up to this many N (0 = off; trex_gym.perturb.RandomPushes)")
     ap.add_argument("--push_interval", type=int, default=100, help="with --push_force: env-steps between two pushes of an env")
     ap.add_argument("--push_duration", type=int, default=5, help="with --push_force: env-steps a push lasts")
+    ap.add_argument("--control_mode", choices=sorted(actuators.CONTROL_MODES), default="position",
+                    help="what an action is for every joint: target angle, target velocity or torque")
+    ap.add_argument("--variable_stiffness", action="store_true", help="[target, stiffness] actions (2J wide): refused, wider than the policy kernel")
+    ap.add_argument("--gain_scale", type=float, default=0.0, help="randomise motor kp / kd / max_force per env and episode by 1 +- this (0 = off)")
     args = ap.parse_args(argv)
+    if args.variable_stiffness:
+        try:
+            check_action_space(args.control_mode, True)
+        except ValueError as e:
+            ap.error(str(e))
+    if not 0.0 <= args.gain_scale < 1.0:
+        ap.error("--gain_scale must lie in [0, 1)")
     if args.push_force > 0 and args.graphs:   # (the pushes are drawn per step on the host's step count: not in a replayed graph)
         ap.error("--push_force cannot be combined with --graphs")
     return args
@@ -167,7 +200,8 @@ def main(argv=None):
     args = parse_args(argv)
     env = build_environment(args.num_envs, max_episode_steps=args.max_episode_steps, warmstart=args.warmstart,
                             push_force=args.push_force, push_interval=args.push_interval, push_duration=args.push_duration,
-                            seed=args.random_seed)
+                            seed=args.random_seed, control_mode=None if args.control_mode == "position" else args.control_mode,
+                            gain_scale=args.gain_scale)
     agent, _ = train(env, args.num_timesteps, args.random_seed, args.nsteps, args.noptepochs, args.save, use_graphs=args.graphs,
                      preset=args.preset)
     if args.play:

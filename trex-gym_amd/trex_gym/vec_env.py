@@ -21,7 +21,7 @@ import time
 import numpy as np
 import torch
 
-from . import _capi, sharding, spaces
+from . import _capi, actuators, sharding, spaces
 
 REWARD_DEFAULTS = dict(distance_weight=1.0, energy_weight=0.005, drift_weight=0.002)  # trex_env.py:42-44
 
@@ -33,12 +33,16 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
                  distance_weight=1.0, energy_weight=0.005, drift_weight=0.002,
                  max_episode_steps=None, starting_configuration=None, params=None,
                  rank=0, world_size=1, process_group=None, collision="hulls", primitive_max_radius=0.2, row_buffers=1,
-                 penalties_in_rows=False, pushes=None):
+                 penalties_in_rows=False, pushes=None, control_mode=None, variable_stiffness=False,
+                 kp_max=actuators.DEFAULT_KP_MAX):
         """num_envs is the GLOBAL env count; this process owns sharding.shard_range(num_envs, rank, world_size).
         row_buffers=2: successive steps write two row blocks in turn (`rows`, `obs`, `rew`, `done_f` always name the
         block of the LAST step), which lets the pipelined all-gather read a block in place.
         pushes: a trex_gym.perturb.RandomPushes over this process's n envs; step_tensor / step_wait draw its pushes before
-        each step launch and apply them, on top of the wrench of set_external_wrench / apply_external_force."""
+        each step launch and apply them, on top of the wrench of set_external_wrench / apply_external_force.
+        control_mode: "position" (default), "velocity", "torque", a sequence of J of them or {joint_name: mode} - what a joint's
+        action means (include/trex_batch.h; pybullet's setJointMotorControlArray modes). variable_stiffness: actions are [2J],
+        J commands then J stiffnesses kp in [0, kp_max] (the reference's intended action space, trex_env.py:30)."""
         self.global_num_envs = int(num_envs)
         self.rank, self.world_size, self.process_group = int(rank), int(world_size), process_group
         self.env_lo, self.env_hi = sharding.shard_range(self.global_num_envs, self.rank, self.world_size)
@@ -65,7 +69,15 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         self.batch.set_reward_weights(distance_weight, energy_weight, drift_weight)
         J = self.J = self.model.num_joints
         lo, hi = self.model.lower.astype(np.float32), self.model.upper.astype(np.float32)
-        self.action_space = spaces.Box(low=lo, high=hi, dtype=np.float32)  # trex_robot.py:424-433
+        self.control_modes = actuators.resolve_control_modes(control_mode, self.model.joint_names)
+        self.variable_stiffness, self.kp_max = bool(variable_stiffness), float(kp_max)
+        if any(self.control_modes):
+            self.batch.set_control_mode(self.control_modes)
+        if self.variable_stiffness:
+            self.batch.set_stiffness_actions(True, self.kp_max)
+        alo, ahi = actuators.action_bounds(self.control_modes, lo, hi, self.model.get_param("max_coordinate_velocity"),
+                                           self.model.get_param("motor_max_force"), self.variable_stiffness, self.kp_max)
+        self.action_space = spaces.Box(low=alo, high=ahi, dtype=np.float32)  # trex_robot.py:424-433 for position control
         big = np.full(2 * J, 1.0e12, np.float32)                            # trex_robot.py:348-357
         self.observation_space = spaces.Box(low=np.concatenate([lo, -big]), high=np.concatenate([hi, big]),
                                             dtype=np.float32)
@@ -86,6 +98,7 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         if max_episode_steps is not None:
             # the step launch itself resets an env whose episode is over (no reset launch between two steps)
             self.batch.set_episode_limit(int(max_episode_steps))
+        self.gains = None                       # a trex_gym.perturb.RandomGains: redrawn at every reset() / reset_tensor()
         self._actions = None
         self._gather_buf = None
         self._pipe = None
@@ -102,6 +115,8 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         """Reset all envs (mask=None) or those with mask != 0 (uint8 or bool [n], e.g. the `done` of the last step).
         Returns obs [n, 3J]; the reward / done columns and `done` of the envs that were reset read 0 afterwards."""
         self.batch.reset_rows(self.rows, mask)
+        if self.gains is not None:              # the envs that were reset draw new motor gains
+            self.set_motor_gains(**self.gains.draw(mask))
         if mask is None:
             self.done.zero_()
         else:
@@ -124,8 +139,8 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         that the next call overwrites."""
         if actions.dtype != torch.float32 or not actions.is_contiguous() or actions.device != self.device:
             actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
-        if tuple(actions.shape) != (self.num_envs, self.J):
-            raise ValueError("actions must have shape (%d, %d), got %s" % (self.num_envs, self.J, tuple(actions.shape)))
+        if tuple(actions.shape) != (self.num_envs, self.A):
+            raise ValueError("actions must have shape (%d, %d), got %s" % (self.num_envs, self.A, tuple(actions.shape)))
         # (with max_episode_steps the launch also resets the envs whose episode ends with this step: done = 1,
         # reward of the finished step, observation of the new episode - VecEnv semantics, no second launch)
         if self.pushes is not None:   # this step's pushes (those of envs that ended their episode last step are dropped)
@@ -142,8 +157,8 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         and `done` then hold the last step. sharding.split_rows(rows[s]) cuts a step's block into the three."""
         if actions.dtype != torch.float32 or not actions.is_contiguous() or actions.device != self.device:
             actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
-        if actions.dim() != 3 or tuple(actions.shape[1:]) != (self.num_envs, self.J):
-            raise ValueError("actions must have shape (S, %d, %d), got %s" % (self.num_envs, self.J, tuple(actions.shape)))
+        if actions.dim() != 3 or tuple(actions.shape[1:]) != (self.num_envs, self.A):
+            raise ValueError("actions must have shape (S, %d, %d), got %s" % (self.num_envs, self.A, tuple(actions.shape)))
         S = int(actions.shape[0])
         if rows is None:
             rows = torch.empty(S, self.num_envs, self.rows.shape[1], device=self.device)
@@ -156,6 +171,11 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
             self._penalties.copy_(self.penalties_many[-1])
         self.done.copy_(self.done_f != 0)
         return rows
+
+    @property
+    def A(self):
+        """columns of an action row: J, or 2J with stiffness actions (the batch's own count)"""
+        return self.batch.A
 
     def _point_at(self, k):
         J = self.J
@@ -212,7 +232,17 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         return self.reset_tensor().cpu().numpy()
 
     def step_async(self, actions):
-        self._actions = torch.as_tensor(np.asarray(actions, np.float32)).to(self.device, non_blocking=True)
+        actions = np.asarray(actions, np.float32)
+        if actions.shape != (self.num_envs, self.A):
+            raise ValueError("actions must have shape (%d, %d), got %s" % (self.num_envs, self.A, actions.shape))
+        self._actions = torch.as_tensor(actions).to(self.device, non_blocking=True)
+
+    def set_motor_gains(self, kp=None, kd=None, max_force=None):
+        """Per-env, per-joint motor gains: each a scalar, [J] or [n, J] (observation order), None = the model parameter; all
+        three None clears (trex_batch_set_motor_gains). Kept over resets."""
+        n, J = self.num_envs, self.J
+        g = [actuators.broadcast_gains(v, n, J, k) for k, v in (("kp", kp), ("kd", kd), ("max_force", max_force))]
+        self.batch.set_motor_gains(*[None if t is None else t.to(self.device).contiguous() for t in g])
 
     def step_wait(self):
         """-> obs, rewards, dones, infos as numpy / dicts. The reference wraps its env in baselines' bench.Monitor

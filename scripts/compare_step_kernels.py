@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""Is the device code of the step kernels the same in two source trees?  No GPU needed.
+
+    python scripts/compare_step_kernels.py --parent REV [--out profiles/NAME.txt] [--keep DIR]
+
+Compiles trex_step.hip and trex_step_act.hip of git revision REV and of the working tree to gfx950 assembly with the
+Makefile's flags (hipcc --cuda-device-only -S), as the product build and as the stamped build (-DTREX_STAMPS=1), and
+pairs every kernel of one side with its counterpart of the other: a step kernel by WHAT it is - (form, WARM, EXT, SENS,
+ACT), read off its demangled name under either naming, the wrapper families `trex_step{,_pair,_many}{,_warm,_ext,_sens,
+_act}_kernel` / `trex_reset_sens_kernel` or the one template `trex_step_variant_kernel<FORM, WARM, EXT, SENS, ACT>` -, a
+utility kernel by its name. A pair is IDENTICAL when the instruction text from the kernel's label to its .Lfunc_end and
+its .amdhsa_* descriptor block are the same lines, after the kernel's own symbol and the function index inside local
+labels (.LBB<n>_, .Lfunc_end<n>) are normalised and the directives that place a kernel in a section are left out. Exit
+status 0 only if every kernel has a partner, every pair is identical and no kernel of the product build has a private
+segment (scratch; the stamped diagnostic build has some, on both sides alike)."""
+import argparse
+import concurrent.futures
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = "trex-gym_amd/csrc"
+FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=fast", "-fno-slp-vectorize", "--cuda-device-only", "-S"]
+UNITS = ["trex_step", "trex_step_act"]
+BUILDS = [("product", []), ("stamped", ["-DTREX_STAMPS=1"])]
+FORMS = {0: "single", 1: "many", 2: "reset", 3: "debug", 4: "pair"}   # FORM of trex_step_variant_kernel (trex_step.hip)
+
+
+def what(name):
+    """demangled kernel name -> (form, WARM, EXT, SENS, ACT) of a step kernel, or the bare name of a utility kernel"""
+    m = re.match(r"(?:void )?(\w+?)(?:<([^>]*)>)?\(", name)
+    base, targs = m.group(1), [a.strip() for a in (m.group(2) or "").split(",") if a.strip()]
+    b = [a == "true" for a in targs]
+    if base == "trex_step_variant_kernel":
+        return (FORMS[int(re.sub(r"\D", "", targs[0]))],) + tuple(b[1:5])
+    if base == "trex_reset_sens_kernel":
+        return ("reset", b[0], False, True, False)
+    m = re.fullmatch(r"trex_step(_pair|_many)?(_warm|_ext|_sens|_act)?_kernel", base)
+    if not m:
+        return base
+    form, feat = (m.group(1) or "_single")[1:], m.group(2)
+    if feat is None:       # <RESET, DEBUG> on the single-env kernel
+        return ("reset" if b[:1] == [True] else "debug" if b[1:2] == [True] else form, False, False, False, False)
+    if feat == "_warm":    # <RESET> on the single-env kernel
+        return ("reset" if b[:1] == [True] else form, True, False, False, False)
+    if feat == "_ext":     # <WARM>
+        return (form, b[0], True, False, False)
+    if feat == "_sens":    # <WARM, EXT>
+        return (form, b[0], b[1], True, False)
+    return (form, b[0], b[1], b[2], True)   # _act: <WARM, EXT, SENS>
+
+
+def kernels(asm_path):
+    """{what: {"name", "text", "desc", figures}} of one assembly file"""
+    lines = open(asm_path).read().split("\n")
+    syms = [l.split()[1] for l in lines if l.strip().startswith(".amdhsa_kernel ")]
+    plain = subprocess.run(["c++filt"] + syms, capture_output=True, text=True, check=True).stdout.split("\n") if syms else []
+    start = {l.split(":")[0]: i for i, l in enumerate(lines) if l.startswith("_Z") and l.split(":")[0] in set(syms)}
+    out = {}
+    for sym, name in zip(syms, plain):
+        i = start[sym]
+        j = next(k for k in range(i, len(lines)) if re.fullmatch(r"\.Lfunc_end\d+:", lines[k]))
+        d0 = next(k for k in range(i, j) if lines[k].strip().startswith(".amdhsa_kernel "))
+        d1 = next(k for k in range(d0, j) if lines[k].strip() == ".end_amdhsa_kernel")
+        info = "\n".join(lines[j:j + 40])
+
+        def norm(ls):   # (and the section a kernel is placed in - .text or a comdat group of its own - is linkage, not code)
+            t = "\n".join(l for l in ls if l.split()[:1] not in ([".text"], [".section"])).replace(sym, "KERNEL")
+            t = re.sub(r"[ \t]*;", " ;", t)                                    # (comment columns move with the length of a name)
+            return re.sub(r"(\.Lfunc_end|\.Lfunc_begin|BB)\d+", r"\1", t)       # .LBB<n>_k, and BB<n>_k inside comments
+
+        def fig(pat):
+            return int(re.search(pat, info).group(1))
+
+        k = what(name)
+        assert k not in out, "two kernels are the same thing: %s" % (k,)
+        out[k] = {"name": name, "text": norm(lines[i:d0] + lines[d1 + 1:j + 1]), "desc": norm(lines[d0:d1 + 1]),
+                  "vgprs": fig(r"; NumVgprs: (\d+)"), "sgprs": fig(r"; TotalNumSgprs: (\d+)"), "scratch": fig(r"; ScratchSize: (\d+)"),
+                  "lds": fig(r"; LDSByteSize: (\d+)"), "private": int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", "\n".join(lines[d0:d1])).group(1))}
+    return out
+
+
+def compile_tree(csrc, dest):
+    jobs = []
+    for unit in UNITS:
+        for tag, extra in BUILDS:
+            out = os.path.join(dest, "%s.%s.s" % (unit, tag))
+            jobs.append((out, [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + FLAGS + extra + ["-o", out, unit + ".hip"]))
+    with concurrent.futures.ThreadPoolExecutor(len(jobs)) as ex:
+        for r in ex.map(lambda j: subprocess.run(j[1], cwd=csrc, capture_output=True, text=True), jobs):
+            if r.returncode:
+                sys.exit(r.stderr)
+
+
+def label(k):
+    return k if isinstance(k, str) else "%-6s %s" % (k[0], " ".join(n if on else "-" * len(n) for n, on in zip(("WARM", "EXT", "SENS", "ACT"), k[1:])))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", required=True, help="git revision to compare the working tree with")
+    ap.add_argument("--out", help="write the report here as well")
+    ap.add_argument("--keep", help="directory for the assembly files (kept; files already there are reused)")
+    a = ap.parse_args()
+    work = a.keep or tempfile.mkdtemp(prefix="step_kernels_")
+    sides = {}
+    for side in ("parent", "tree"):
+        dest = os.path.join(work, side)
+        if not os.path.isdir(dest):
+            os.makedirs(dest)
+            csrc = os.path.join(ROOT, CSRC)
+            if side == "parent":
+                tar = subprocess.run(["git", "-C", ROOT, "archive", a.parent, CSRC], capture_output=True, check=True).stdout
+                subprocess.run(["tar", "-x", "-C", dest], input=tar, check=True)
+                csrc = os.path.join(dest, CSRC)
+            compile_tree(csrc, dest)
+        sides[side] = dest
+    rev = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", a.parent], capture_output=True, text=True, check=True).stdout.strip()
+    rep = ["step kernels of the working tree against %s: device assembly, kernel by kernel (scripts/compare_step_kernels.py)" % rev,
+           "hipcc " + " ".join(FLAGS), ""]
+    bad = 0
+    for tag, extra in BUILDS:
+        old, new = {}, {}
+        for unit in UNITS:
+            for side, dst in (("parent", old), ("tree", new)):
+                ks = kernels(os.path.join(sides[side], "%s.%s.s" % (unit, tag)))
+                assert not set(ks) & set(dst), "a kernel in both translation units"
+                for k in ks.values():
+                    k["unit"] = unit
+                dst.update(ks)
+        steps = sorted(k for k in set(old) | set(new) if not isinstance(k, str))
+        utils = sorted(k for k in set(old) | set(new) if isinstance(k, str))
+        rep.append("== %s build%s: %d step kernels, %d utility kernels (parent: %d, %d)" % (
+            tag, " (%s)" % " ".join(extra) if extra else "", sum(not isinstance(k, str) for k in new), sum(isinstance(k, str) for k in new),
+            sum(not isinstance(k, str) for k in old), sum(isinstance(k, str) for k in old)))
+        rep.append("%-28s %-10s %5s %5s %8s %7s  %-13s parent kernel -> kernel" % ("what", "result", "VGPRs", "SGPRs", "scratch", "LDS", "unit"))
+        for k in steps + utils:
+            o, n = old.get(k), new.get(k)
+            if not o or not n:
+                res = "NO PARENT" if n else "MISSING"
+            else:
+                same = o["text"] == n["text"] and o["desc"] == n["desc"] and o["unit"] == n["unit"] and all(o[f] == n[f] for f in ("vgprs", "sgprs", "scratch", "private", "lds"))
+                res = "identical" if same else "DIFFERENT"
+            x = n or o
+            scratch_free = x["scratch"] == 0 and x["private"] == 0
+            bad += res != "identical" or (tag == "product" and not scratch_free)
+            rep.append("%-28s %-10s %5d %5d %8d %7d  %-13s %s -> %s" % (label(k), res, x["vgprs"], x["sgprs"], max(x["scratch"], x["private"]),
+                                                                   x["lds"], x["unit"], o["name"].split("(")[0] if o else "-", n["name"].split("(")[0] if n else "-"))
+        rep.append("")
+    rep.append("RESULT: %s" % ("every pair identical, no kernel of the product build with a private segment" if not bad else "%d kernel(s) differ, lack a partner or use scratch" % bad))
+    text = "\n".join(rep) + "\n"
+    sys.stdout.write(text)
+    if a.out:
+        open(a.out, "w").write(text)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

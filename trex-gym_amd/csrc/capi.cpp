@@ -14,40 +14,7 @@
 #include "internal.hpp"
 #include "model.hpp"
 #include "render.h"
-
-extern "C" {
-hipError_t trex_launch_step(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, float *, uint8_t *,
-                            float *, float, float, float, float *, hipStream_t, float *, int, int, int, int, float *,
-                            const float *, float *);
-hipError_t trex_launch_reset(const TrexDeviceModel *, TrexBatchArrays, int, const uint8_t *, float *, float, float,
-                             float, float *, hipStream_t, int, float *, float *, int, int, int, float *, float *);
-hipError_t trex_launch_step_many(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, int, int, float *, uint8_t *,
-                                 float, float, float, hipStream_t, int, int, int, float *, const float *, float *);
-hipError_t trex_launch_step_act(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, float *, uint8_t *,
-                                float *, float, float, float, hipStream_t, float *, int, int, int, int, float *,
-                                const float *, float *, const TrexActuators *);
-hipError_t trex_launch_step_many_act(const TrexDeviceModel *, TrexBatchArrays, int, const float *, float *, int, int, float *, uint8_t *,
-                                     float, float, float, hipStream_t, int, int, int, float *, const float *, float *,
-                                     const TrexActuators *);
-hipError_t trex_launch_copy_gains(const TrexDeviceModel *, const float *, const float *, const float *, float *, int, hipStream_t);
-int trex_actuator_floats(void);
-hipError_t trex_launch_pack_state(const TrexDeviceModel *, TrexBatchArrays, int, float *, int, hipStream_t);
-hipError_t trex_launch_head(const TrexDeviceModel *, TrexBatchArrays, int, float *, hipStream_t);
-hipError_t trex_launch_link_transforms(const TrexDeviceModel *, TrexBatchArrays, int, float *, hipStream_t, int);
-hipError_t trex_launch_fill(float *, float, int, hipStream_t);
-hipError_t trex_launch_scalars_get(TrexBatchArrays, int, int32_t *, float *, int32_t *, hipStream_t);
-hipError_t trex_launch_scalars_set(TrexBatchArrays, int, const int32_t *, int, int, hipStream_t);
-hipError_t trex_launch_fill_u8(uint8_t *, uint8_t, int, hipStream_t);
-hipError_t trex_launch_copy_mass_scale(const float *, float *, int, int, hipStream_t);
-hipError_t trex_launch_copy_wrench(const float *, float *, int, int, hipStream_t);
-hipError_t trex_launch_contact_wrench(const float *, float *, int, int, hipStream_t);
-int trex_contact_sensor_floats(void);
-int trex_step_lds_bytes(int);
-int trex_step_envs_per_workgroup(int);
-int trex_step_warm_lds_bytes(void);
-int trex_step_single_lds_bytes(void);
-hipError_t trex_launch_render(const TrexRenderArgs &, hipStream_t);
-}
+#include "step_launch.h"
 
 struct TrexModel {
   trex::HostModel host;
@@ -61,18 +28,18 @@ struct TrexBatch {
   float *ext = nullptr;                        // external wrench [n][6][TREX_TL] (trex_batch_set_external_wrench); first non-NULL call on
   bool ext_on = false;                         // set: the step launches take the EXT kernels
   const float *wrench() const { return ext_on ? ext : nullptr; }
-  float *sens = nullptr;                       // contact sensor [n][trex_contact_sensor_floats()] (trex_batch_set_contact_sensor); first enable
+  float *sens = nullptr;                       // contact sensor [n][TREX_SENS_FLOATS] (trex_batch_set_contact_sensor); first enable
   bool sens_on = false;                        // on: every step and reset launch takes the SENS kernels
   float *sensor() const { return sens_on ? sens : nullptr; }
   // actuator model (trex_batch_set_control_mode / _set_motor_gains / _set_stiffness_actions): while any of the three is active the
-  // step launches take the ACT kernels; the gains buffer [n][trex_actuator_floats()] exists from the first use of any of them and
+  // step launches take the ACT kernels; the gains buffer [n][TREX_ACT_FLOATS] exists from the first use of any of them and
   // then always holds what the launches are to read - the caller's gains, or the model parameters
   std::vector<int> obs_order;                  // observation slot -> body lane
-  TrexActuators act{nullptr, 0u, 0u, 0, 0.f};
-  bool single_form() const { return warm && act_on(); }   // a warm batch with actuators steps through the single-env form (trex_step.hip)
+  uint32_t vel_mask = 0u, tor_mask = 0u;       // joints under VELOCITY / TORQUE control, bit b = body lane b
+  float kp_max = 0.f;                          // upper clip of an action's stiffness
   float *gains = nullptr;
   bool gains_set = false, stiff = false;
-  bool act_on() const { return (act.vel_mask | act.tor_mask) != 0u || gains_set || stiff; }
+  bool act_on() const { return (vel_mask | tor_mask) != 0u || gains_set || stiff; }
   int action_cols() const { return stiff ? 2 * nj : nj; }
   float wd = 1.0f, we = 0.005f, wk = 0.002f;  // trex_env.py:42-44
   bool pen_in_rows = false;                    // trex_batch_set_penalties_in_rows
@@ -237,25 +204,37 @@ int ensure_gains(TrexBatch *b) {
   if (b->gains) return TREX_OK;
   DeviceGuard guard(b->device);
   void *p = nullptr;
-  HIP_TRY(hipMalloc(&p, (size_t)b->n * trex_actuator_floats() * sizeof(float)));
+  HIP_TRY(hipMalloc(&p, (size_t)b->n * TREX_ACT_FLOATS * sizeof(float)));
   b->allocs.push_back(p);
   HIP_TRY(trex_launch_copy_gains(b->dmodel, nullptr, nullptr, nullptr, (float *)p, b->n, nullptr));
   HIP_TRY(hipDeviceSynchronize());   // (in place before a launch on any stream)
   b->gains = (float *)p;
-  b->act.gains = b->gains;
   return TREX_OK;
 }
 
-// the step launch of the batch: the ACT kernels while its actuator model is active, else the launches as they were
-hipError_t launch_step(TrexBatch *b, const float *actions, float *obs, float *reward, uint8_t *done, float *penalties,
-                       hipStream_t stream, float *done_f, int obs_stride, int scal_stride, int pen_in_rows) {
+// What every launch of the batch's step kernels is given: the model, the state, the reward weights and the record / buffer of each
+// feature that is switched on - a non-null pointer IS the switch (step_launch.h). A reset takes no actions: no wave balance, no
+// external wrench, no actuator model. The caller adds the outputs and their strides.
+TrexStepArgs step_args(const TrexBatch *b, TrexStepKind kind) {
+  TrexStepArgs a{};
+  a.model = b->dmodel; a.arr = b->arr; a.n_envs = b->n;
+  a.w_distance = b->wd; a.w_energy = b->we; a.w_drift = b->wk;
+  a.obs_stride = 3 * b->nj; a.scal_stride = 1; a.n_steps = 1;
+  a.warm = b->warm; a.sens = b->sensor();
+  if (kind == TREX_KIND_RESET) return a;
+  a.bal = b->balance() ? b->arr.balance : nullptr;
+  a.ext = b->wrench();
   if (b->act_on()) {
-    b->act.action_cols = b->action_cols();
-    return trex_launch_step_act(b->dmodel, b->arr, b->n, actions, obs, reward, done, penalties, b->wd, b->we, b->wk, stream, done_f,
-                                obs_stride, scal_stride, b->balance(), pen_in_rows, b->warm, b->wrench(), b->sensor(), &b->act);
+    a.act = b->gains; a.act_vel = b->vel_mask; a.act_tor = b->tor_mask;
+    a.act_cols = b->action_cols(); a.act_kp_max = b->kp_max;
   }
-  return trex_launch_step(b->dmodel, b->arr, b->n, actions, obs, reward, done, penalties, b->wd, b->we, b->wk, nullptr, stream, done_f,
-                          obs_stride, scal_stride, b->balance(), pen_in_rows, b->warm, b->wrench(), b->sensor());
+  return a;
+}
+// the outputs as ONE row block: row e = obs | reward | done (| the three penalties) at rows + e * row_stride
+void rows_out(const TrexBatch *b, TrexStepArgs &a, float *rows, int row_stride) {
+  a.obs = rows; a.reward = rows + 3 * b->nj; a.done_f = a.reward + 1;
+  a.obs_stride = a.scal_stride = row_stride;
+  a.pen_in_rows = b->pen_in_rows ? 1 : 0;
 }
 
 int check_device_buffer(TrexBatch *b, const void *p, size_t bytes, const char *what) {
@@ -597,8 +576,9 @@ int trex_batch_reset(TrexBatch *b, const uint8_t *mask_dev, float *obs_out_dev, 
   const size_t n = (size_t)b->n;
   BUF_TRY(mask_dev, n, "trex_batch_reset: mask");
   BUF_TRY(obs_out_dev, n * 3 * b->nj * sizeof(float), "trex_batch_reset: obs_out");
-  HIP_TRY(trex_launch_reset(b->dmodel, b->arr, b->n, mask_dev, obs_out_dev, b->wd, b->we, b->wk, nullptr,
-                            (hipStream_t)stream, 3 * b->nj, nullptr, nullptr, 1, b->nj, 0, b->warm, b->sensor()));
+  TrexStepArgs a = step_args(b, TREX_KIND_RESET);
+  a.reset_mask = mask_dev; a.obs = obs_out_dev;
+  HIP_TRY(trex_launch_step(&a, TREX_KIND_RESET, (hipStream_t)stream));
   return TREX_OK;
 }
 
@@ -610,9 +590,10 @@ int trex_batch_reset_rows(TrexBatch *b, const uint8_t *mask_dev, float *rows_dev
   const size_t n = (size_t)b->n;
   BUF_TRY(mask_dev, n, "trex_batch_reset_rows: mask");
   BUF_TRY(rows_dev, ((n - 1) * row_stride + 3 * b->nj + (b->pen_in_rows ? 5 : 2)) * sizeof(float), "trex_batch_reset_rows: rows");
-  HIP_TRY(trex_launch_reset(b->dmodel, b->arr, b->n, mask_dev, rows_dev, b->wd, b->we, b->wk, nullptr,
-                            (hipStream_t)stream, row_stride, rows_dev + 3 * b->nj, rows_dev + 3 * b->nj + 1, row_stride, b->nj,
-                            b->pen_in_rows ? 1 : 0, b->warm, b->sensor()));
+  TrexStepArgs a = step_args(b, TREX_KIND_RESET);
+  a.reset_mask = mask_dev;
+  rows_out(b, a, rows_dev, row_stride);
+  HIP_TRY(trex_launch_step(&a, TREX_KIND_RESET, (hipStream_t)stream));
   return TREX_OK;
 }
 
@@ -627,7 +608,9 @@ int trex_batch_step(TrexBatch *b, const float *actions_dev, float *obs_dev, floa
   BUF_TRY(reward_dev, n * sizeof(float), "trex_batch_step: reward");
   BUF_TRY(done_dev, n, "trex_batch_step: done");
   BUF_TRY(penalties_dev, n * 3 * sizeof(float), "trex_batch_step: penalties");
-  HIP_TRY(launch_step(b, actions_dev, obs_dev, reward_dev, done_dev, penalties_dev, (hipStream_t)stream, nullptr, 3 * b->nj, 1, 0));
+  TrexStepArgs a = step_args(b, TREX_KIND_STEP);
+  a.actions = actions_dev; a.obs = obs_dev; a.reward = reward_dev; a.done = done_dev; a.penalties = penalties_dev;
+  HIP_TRY(trex_launch_step(&a, TREX_KIND_STEP, (hipStream_t)stream));
   return TREX_OK;
 }
 
@@ -642,9 +625,10 @@ int trex_batch_step_rows(TrexBatch *b, const float *actions_dev, float *rows_dev
   BUF_TRY(rows_dev, ((n - 1) * row_stride + 3 * b->nj + (b->pen_in_rows ? 5 : 2)) * sizeof(float), "trex_batch_step_rows: rows");
   BUF_TRY(penalties_dev, n * 3 * sizeof(float), "trex_batch_step_rows: penalties");
   BUF_TRY(done_dev, n, "trex_batch_step_rows: done");
-  float *rew = rows_dev + 3 * b->nj;
-  HIP_TRY(launch_step(b, actions_dev, rows_dev, rew, done_dev, penalties_dev, (hipStream_t)stream, rew + 1, row_stride, row_stride,
-                      b->pen_in_rows ? 1 : 0));
+  TrexStepArgs a = step_args(b, TREX_KIND_STEP);
+  a.actions = actions_dev; a.done = done_dev; a.penalties = penalties_dev;
+  rows_out(b, a, rows_dev, row_stride);
+  HIP_TRY(trex_launch_step(&a, TREX_KIND_STEP, (hipStream_t)stream));
   return TREX_OK;
 }
 
@@ -660,16 +644,11 @@ int trex_batch_step_many(TrexBatch *b, const float *actions_dev, float *rows_dev
   BUF_TRY(rows_dev, ((S * n - 1) * row_stride + 3 * b->nj + (b->pen_in_rows ? 5 : 2)) * sizeof(float), "trex_batch_step_many: rows");
   BUF_TRY(penalties_dev, S * n * 3 * sizeof(float), "trex_batch_step_many: penalties");
   BUF_TRY(done_dev, S * n, "trex_batch_step_many: done");
-  if (b->act_on()) {
-    b->act.action_cols = b->action_cols();
-    HIP_TRY(trex_launch_step_many_act(b->dmodel, b->arr, b->n, actions_dev, rows_dev, row_stride, num_steps, penalties_dev, done_dev,
-                                      b->wd, b->we, b->wk, (hipStream_t)stream, b->balance(), b->nj, b->pen_in_rows ? 1 : 0, b->warm,
-                                      b->wrench(), b->sensor(), &b->act));
-    return TREX_OK;
-  }
-  HIP_TRY(trex_launch_step_many(b->dmodel, b->arr, b->n, actions_dev, rows_dev, row_stride, num_steps, penalties_dev, done_dev,
-                                b->wd, b->we, b->wk, (hipStream_t)stream, b->balance(), b->nj, b->pen_in_rows ? 1 : 0, b->warm,
-                                b->wrench(), b->sensor()));
+  TrexStepArgs a = step_args(b, TREX_KIND_STEP_MANY);
+  a.actions = actions_dev; a.done = done_dev; a.penalties = penalties_dev;
+  rows_out(b, a, rows_dev, row_stride);
+  a.n_steps = num_steps; a.step_rows = (long long)b->n * row_stride;
+  HIP_TRY(trex_launch_step(&a, TREX_KIND_STEP_MANY, (hipStream_t)stream));
   return TREX_OK;
 }
 
@@ -688,8 +667,9 @@ int trex_batch_debug_step(TrexBatch *b, const float *actions_dev, float *obs_dev
     return fail(TREX_E_INVALID, "trex_batch_debug_step: not available while the contact sensor is on");
   if (b->act_on())   // (nor the actuator model)
     return fail(TREX_E_INVALID, "trex_batch_debug_step: not available while control modes, motor gains or stiffness actions are set");
-  HIP_TRY(trex_launch_step(b->dmodel, b->arr, b->n, actions_dev, obs_dev, nullptr, nullptr, nullptr, b->wd, b->we, b->wk,
-                           debug_dev, (hipStream_t)stream, nullptr, 3 * b->nj, 1, b->balance(), 0, b->warm, nullptr, nullptr));
+  TrexStepArgs a = step_args(b, TREX_KIND_STEP_DEBUG);
+  a.actions = actions_dev; a.obs = obs_dev; a.debug = debug_dev;
+  HIP_TRY(trex_launch_step(&a, TREX_KIND_STEP_DEBUG, (hipStream_t)stream));
   return TREX_OK;
 }
 
@@ -823,7 +803,7 @@ int trex_batch_set_control_mode(TrexBatch *b, const int32_t *mode_host) {
   }
   if ((vel | tor) != 0u)
     if (int c = ensure_gains(b)) return c;
-  b->act.vel_mask = vel; b->act.tor_mask = tor;
+  b->vel_mask = vel; b->tor_mask = tor;
   return TREX_OK;
 }
 
@@ -848,7 +828,7 @@ int trex_batch_set_stiffness_actions(TrexBatch *b, int enabled, float kp_max) {
   if (!enabled) { b->stiff = false; return TREX_OK; }
   if (!std::isfinite(kp_max) || kp_max < 0.f) return fail(TREX_E_INVALID, "trex_batch_set_stiffness_actions: kp_max must be finite and >= 0");
   if (int c = ensure_gains(b)) return c;
-  b->stiff = true; b->act.kp_max = kp_max;
+  b->stiff = true; b->kp_max = kp_max;
   return TREX_OK;
 }
 
@@ -857,7 +837,7 @@ int trex_batch_set_contact_sensor(TrexBatch *b, int enabled) {
   if (!enabled) { b->sens_on = false; return TREX_OK; }   // the default kernels again; the buffer stays for the next enable
   if (!b->sens) {   // first enable: a batch that never enables the sensor allocates nothing; zeros until a launch records
     DeviceGuard guard(b->device);
-    const size_t bytes = (size_t)b->n * trex_contact_sensor_floats() * sizeof(float);
+    const size_t bytes = (size_t)b->n * TREX_SENS_FLOATS * sizeof(float);
     void *p = nullptr;
     HIP_TRY(hipMalloc(&p, bytes));
     b->allocs.push_back(p);
@@ -891,12 +871,11 @@ int trex_batch_contact_stats(TrexBatch *b, int32_t *count_dev, float *normal_imp
 
 int trex_batch_launch_info(const TrexBatch *b, int *grid, int *block, int *lds_bytes, int *alg_bytes_per_env_step) {
   if (!b) return fail(TREX_E_INVALID, "null batch");
-  // (a warm batch with an active actuator model steps through the single-env form: trex_step.hip)
-  const int epw = b->single_form() ? 1 : trex_step_envs_per_workgroup(b->n);
-  if (grid) *grid = (b->n + epw - 1) / epw;
-  if (block) *block = 64 * epw;       // one wavefront per env
-  if (lds_bytes) *lds_bytes = (b->single_form() ? trex_step_single_lds_bytes() : trex_step_lds_bytes(b->n)) +
-                              (b->warm ? epw * trex_step_warm_lds_bytes() : 0);
+  // the shape the step launch of this batch takes (trex_launch_step asks the same function)
+  const TrexStepShape shape = trex_step_launch_shape(TREX_KIND_STEP, b->n, trex_step_features(step_args(b, TREX_KIND_STEP)));
+  if (grid) *grid = shape.grid;
+  if (block) *block = shape.block;
+  if (lds_bytes) *lds_bytes = shape.lds_bytes;
   // state in + out (13 + 2J floats each), action in (J), obs out (3J), reward (4 B), done (padded 4 B): SURVEY 8d
   if (alg_bytes_per_env_step) *alg_bytes_per_env_step = 4 * (2 * (13 + 2 * b->nj) + b->nj + 3 * b->nj + 1 + 1);
   return TREX_OK;
@@ -916,8 +895,9 @@ int trex_batch_time_steps(TrexBatch *b, const float *actions_dev, float *obs_dev
   HIP_TRY(hipEventCreate(&e1));
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipEventRecord(e0, s));
-  for (int i = 0; i < steps; i++)
-    HIP_TRY(launch_step(b, actions_dev, obs_dev, reward_dev, done_dev, nullptr, s, nullptr, 3 * b->nj, 1, 0));
+  TrexStepArgs a = step_args(b, TREX_KIND_STEP);
+  a.actions = actions_dev; a.obs = obs_dev; a.reward = reward_dev; a.done = done_dev;
+  for (int i = 0; i < steps; i++) HIP_TRY(trex_launch_step(&a, TREX_KIND_STEP, s));
   HIP_TRY(hipEventRecord(e1, s));
   HIP_TRY(hipEventSynchronize(e1));
   float ms = 0.f;

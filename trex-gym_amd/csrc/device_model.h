@@ -92,14 +92,3 @@ struct TrexBatchArrays {
  * PLUS ONE, as an int, 0 = empty slot; the words of the slot's three contact rows (normal, friction x, friction y: the lanes of
  * the kernel's rows 3 s .. 3 s + 2) its final impulses, unscaled; every other word 0. An all-zero row is an empty record. */
 #define TREX_WARM_WORDS 64
-/* The actuator model of a batch (trex_batch_set_control_mode / _set_motor_gains / _set_stiffness_actions), as the ACT step
- * launches take it: the per-env gains [N][4][TREX_TL] (kp, kd, max_force * dt, max_force per body lane), the joints under
- * VELOCITY / TORQUE control as bit masks by body lane, the width of an action row (J, or 2J with stiffness actions) and the
- * upper clip of an action's stiffness. The buffer is batch-owned and WRITTEN by the step launches too: with stiffness
- * actions the action decode parks the env-step's kp, kd in its last two rows. */
-struct TrexActuators {
-  float *gains;
-  uint32_t vel_mask, tor_mask;
-  int32_t action_cols;
-  float kp_max;
-};

@@ -33,3 +33,5 @@ struct TrexRenderArgs {
   float target[3], offset[3], fwd[3], right[3], up[3];
   float tan_x, tan_y, near_z, far_z, floor_z;
 };
+
+extern "C" hipError_t trex_launch_render(const TrexRenderArgs &args, hipStream_t stream);   /* render.hip */

@@ -40,8 +40,10 @@
 #include <stdint.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "device_model.h"
+#include "step_launch.h"
 
 #define TL TREX_TL
 #define MAXD TREX_MAXD
@@ -375,46 +377,7 @@ struct CgLds {
 };
 static_assert(sizeof(CgLds) <= sizeof(WaveLds::u), "contact-generation scratch fits the union area");
 
-struct KernelArgs {
-  const TrexDeviceModel *model;
-  TrexBatchArrays arr;
-  int n_envs;
-  const float *actions;   // [N, J]
-  float *obs;             // [N, 3J] nullable; row e starts at obs + e * obs_stride
-  float *reward;          // [N] nullable; element e at reward[e * scal_stride]
-  uint8_t *done;          // [N] nullable
-  float *done_f;          // done as 0.0 / 1.0 at done_f[e * scal_stride] (row-block output), nullable
-  int obs_stride, scal_stride;
-  float *penalties;       // [N, 3] nullable
-  const uint8_t *reset_mask;  // RESET only, nullable = all
-  int32_t *bal;               // rank lists of the wave balance (step launches), nullable = workgroup k runs env k
-  float w_distance, w_energy, w_drift;
-  float *debug;           // diagnostics of env 0's last substep (tests), nullable
-  // MULTI launches (trex_batch_step_many): n_steps env-steps per launch; step s reads actions + s * N * J and writes the
-  // row block at + s * step_rows floats (obs, reward, done_f alike), done bytes at + s * N, penalties at + s * 3 N
-  int n_steps;
-  long long step_rows;
-  int pen_in_rows;        // row-block launches of a batch with trex_batch_set_penalties_in_rows: the three penalties follow done in the row
-  float *warm;            // WARM launches: the per-env warm-start records [N][TREX_WARM_WORDS] (device_model.h); last, so that
-                          // every other argument keeps its offset
-  const float *ext;       // EXT launches: the per-env external wrench [N][6][TREX_TL] (fx fy fz tx ty tz, world axes, at / about the
-                          // body's COM; trex_batch_set_external_wrench); after warm for the same reason
-  float *sens;            // SENS launches: the per-env contact sensor [N][SENS_ROWS][TREX_TL] (below; trex_batch_set_contact_sensor)
-  // ACT launches (the actuator model, below): the per-env motor gains [N][ACT_ROWS][TREX_TL], which body lanes' joints are VELOCITY /
-  // TORQUE controlled (bit b = body lane b; wave- and batch-uniform: scalar registers), the width of an action row - J, or 2J with
-  // stiffness actions - and the upper clip of an action's stiffness; last, so that every other argument keeps its offset
-  float *act;             // (not const: with stiffness actions the action decode writes the env-step's kp, kd into rows 4, 5)
-  unsigned act_vel, act_tor;
-  int act_cols;
-  float act_kp_max;
-};
-// ACT rows of an env, per body lane: the joint's motor kp, kd, largest impulse of a substep (max_force * dt) and max_force - the
-// gains as set -, then the kp and kd of the CURRENT env-step under stiffness actions (written by the step's action decode, read by
-// its row set-ups on the same lane: the decode has the registers for the action's address and the square root, the set-up has not)
-constexpr int ACT_GAINS = 4, ACT_ROWS = 6;
-// SENS rows of an env: 0..5 the floor-contact wrench of every body (fx fy fz tx ty tz, world axes, at / about its COM), 6..8 the
-// body's COM of the current substep relative to the base origin (written by the tree phases, read by the env's results pass)
-constexpr int SENS_ROWS = 9;
+constexpr int ACT_GAINS = TREX_ACT_GAINS, ACT_ROWS = TREX_ACT_ROWS, SENS_ROWS = TREX_SENS_ROWS;   // their rows: step_launch.h
 
 }  // namespace
 
@@ -476,9 +439,24 @@ constexpr int SENS_ROWS = 9;
 // the pair workgroup's is spent). Non-finite gains or torque commands count as a non-finite state (containment, as for EXT).
 // Non-RESET product launches only, in every combination with WARM, EXT and SENS; separate instantiations, compiled in a translation
 // unit of their own (trex_step_act.hip): the kernels without ACT are the code they were.
+// The launch forms, and which instantiations exist - stated HERE once, for the variant table below (what does not exist is a null
+// entry: hipErrorInvalidValue) and for the choice of the pair form; the static_asserts of the body say why.
+enum { FORM_SINGLE = TREX_KIND_STEP, FORM_MANY = TREX_KIND_STEP_MANY, FORM_RESET = TREX_KIND_RESET, FORM_DEBUG = TREX_KIND_STEP_DEBUG,
+       FORM_PAIR, FORM_COUNT };
+constexpr bool trex_step_variant_exists(int form, unsigned features) {
+  const bool warm = features & TREX_FEAT_WARM, ext = features & TREX_FEAT_EXT, act = features & TREX_FEAT_ACT;
+  // the stamped diagnostic build: the kernels without a feature and their warm forms only, and no diagnostics dump
+  if (TREX_STAMPS && ((features & ~TREX_FEAT_WARM) != 0u || form == FORM_DEBUG)) return false;
+  if (form == FORM_PAIR && warm && act) return false;   // with the warm-start record and the gains the pair form's row set-up no longer
+                                                        // fits 128 registers (36 bytes of scratch per lane): such a batch steps
+                                                        // through the single-env form, whose rows are bitwise the same
+  if (form == FORM_RESET && (ext || act)) return false;
+  if (form == FORM_DEBUG && features != 0u) return false;
+  return true;
+}
 #define WSYNC() do { if (PAIR) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); else __syncthreads(); } while (0)
 template <bool RESET, bool DEBUG, bool MULTI, bool PAIR = false, bool WARM = false, bool EXT = false, bool SENS = false, bool ACT = false>
-__device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int wg_in) {   // wg_in: blockIdx.x
+__device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const int wg_in) {   // wg_in: blockIdx.x
   static_assert(!PAIR || (!RESET && !DEBUG && !MULTI), "the pair form exists for the product step launch only");
   static_assert(!(WARM && DEBUG), "the diagnostics dump has no warm-start form");
   static_assert(!EXT || (!RESET && !DEBUG), "the external wrench exists for the product step launches only");
@@ -2558,37 +2536,51 @@ __device__ __forceinline__ void trex_step_body(const KernelArgs &args, const int
   }
 }
 
+// ---------------------------------------------------------------- the step kernels and their variant table
+// Every feature variant is ONE template over (form, WARM, EXT, SENS, ACT); the launch bounds follow from the form. (Templates: what
+// trex_step_variant_exists rules out - every EXT / SENS / ACT kernel in the stamped diagnostic build - is never instantiated.)
+template <int FORM, bool WARM, bool EXT, bool SENS, bool ACT>
+__global__ __launch_bounds__(FORM == FORM_PAIR ? 128 : 64, 4) void trex_step_variant_kernel(TrexStepArgs args) {
+  static_assert(WARM || EXT || SENS || ACT, "the kernels without a feature keep their own names");
+  static_assert(trex_step_variant_exists(FORM, (WARM ? TREX_FEAT_WARM : 0u) | (EXT ? TREX_FEAT_EXT : 0u) | (SENS ? TREX_FEAT_SENS : 0u) |
+                                                   (ACT ? TREX_FEAT_ACT : 0u)), "no such variant");
+  trex_step_body<FORM == FORM_RESET, false, FORM == FORM_MANY, FORM == FORM_PAIR, WARM, EXT, SENS, ACT>(args, (int)blockIdx.x);
+}
 #if !TREX_ACT_TU
+// the kernels without a feature, under the names the profiles, bench.py and the scripts know them by
 template <bool RESET, bool DEBUG>
-__global__ __launch_bounds__(64, 4) void trex_step_kernel(KernelArgs args) { trex_step_body<RESET, DEBUG, false>(args, (int)blockIdx.x); }
+__global__ __launch_bounds__(64, 4) void trex_step_kernel(TrexStepArgs args) { trex_step_body<RESET, DEBUG, false>(args, (int)blockIdx.x); }
 // two envs per workgroup with split roles between the barriers of a substep (PAIR above): even batches of at most 4096 envs
-__global__ __launch_bounds__(128, 4) void trex_step_pair_kernel(KernelArgs args) { trex_step_body<false, false, false, true>(args, (int)blockIdx.x); }
+__global__ __launch_bounds__(128, 4) void trex_step_pair_kernel(TrexStepArgs args) { trex_step_body<false, false, false, true>(args, (int)blockIdx.x); }
 // S env-steps per launch (trex_batch_step_many)
-__global__ __launch_bounds__(64, 4) void trex_step_many_kernel(KernelArgs args) { trex_step_body<false, false, true>(args, (int)blockIdx.x); }
-// the same launches with the PGS warm start (WARM above): chosen on the host for a batch whose model has warmstart > 0
-template <bool RESET>
-__global__ __launch_bounds__(64, 4) void trex_step_warm_kernel(KernelArgs args) { trex_step_body<RESET, false, false, false, true>(args, (int)blockIdx.x); }
-__global__ __launch_bounds__(128, 4) void trex_step_pair_warm_kernel(KernelArgs args) { trex_step_body<false, false, false, true, true>(args, (int)blockIdx.x); }
-__global__ __launch_bounds__(64, 4) void trex_step_many_warm_kernel(KernelArgs args) { trex_step_body<false, false, true, false, true>(args, (int)blockIdx.x); }
-// the same product launches with the external wrench (EXT above): chosen on the host for a batch that holds one (templates: the
-// stamped diagnostic build, which launches none of them, instantiates none)
-template <bool WARM>
-__global__ __launch_bounds__(64, 4) void trex_step_ext_kernel(KernelArgs args) { trex_step_body<false, false, false, false, WARM, true>(args, (int)blockIdx.x); }
-template <bool WARM>
-__global__ __launch_bounds__(128, 4) void trex_step_pair_ext_kernel(KernelArgs args) { trex_step_body<false, false, false, true, WARM, true>(args, (int)blockIdx.x); }
-template <bool WARM>
-__global__ __launch_bounds__(64, 4) void trex_step_many_ext_kernel(KernelArgs args) { trex_step_body<false, false, true, false, WARM, true>(args, (int)blockIdx.x); }
-// every launch with the contact sensor (SENS above), with and without WARM and EXT: chosen on the host while the sensor is on
-// (templates: the stamped diagnostic build instantiates none)
-template <bool WARM, bool EXT>
-__global__ __launch_bounds__(64, 4) void trex_step_sens_kernel(KernelArgs args) { trex_step_body<false, false, false, false, WARM, EXT, true>(args, (int)blockIdx.x); }
-template <bool WARM, bool EXT>
-__global__ __launch_bounds__(128, 4) void trex_step_pair_sens_kernel(KernelArgs args) { trex_step_body<false, false, false, true, WARM, EXT, true>(args, (int)blockIdx.x); }
-template <bool WARM, bool EXT>
-__global__ __launch_bounds__(64, 4) void trex_step_many_sens_kernel(KernelArgs args) { trex_step_body<false, false, true, false, WARM, EXT, true>(args, (int)blockIdx.x); }
-template <bool WARM>
-__global__ __launch_bounds__(64, 4) void trex_reset_sens_kernel(KernelArgs args) { trex_step_body<true, false, false, false, WARM, false, true>(args, (int)blockIdx.x); }
+__global__ __launch_bounds__(64, 4) void trex_step_many_kernel(TrexStepArgs args) { trex_step_body<false, false, true>(args, (int)blockIdx.x); }
+#endif
 
+// The variant table, indexed by form and feature mask: the kernel of (FORM, F), or null where it does not exist - or lives in the
+// other translation unit: this text is compiled twice, and the ACT half of the table, which doubles the kernels, is
+// trex_step_act.hip's, so that the two long compiles run side by side.
+template <int FORM, unsigned F>
+constexpr TrexStepKernel trex_step_table_entry() {
+  if constexpr (!trex_step_variant_exists(FORM, F) || ((F & TREX_FEAT_ACT) != 0u) != (TREX_ACT_TU == 1)) return nullptr;
+#if !TREX_ACT_TU
+  else if constexpr (F == 0u)
+    return FORM == FORM_PAIR ? trex_step_pair_kernel : FORM == FORM_MANY ? trex_step_many_kernel
+                                                                         : trex_step_kernel<FORM == FORM_RESET, FORM == FORM_DEBUG>;
+#endif
+  else return trex_step_variant_kernel<FORM, (F & TREX_FEAT_WARM) != 0u, (F & TREX_FEAT_EXT) != 0u, (F & TREX_FEAT_SENS) != 0u,
+                                       (F & TREX_FEAT_ACT) != 0u>;
+}
+template <int... I>
+static TrexStepKernel trex_step_table(int form, unsigned features, std::integer_sequence<int, I...>) {
+  static constexpr TrexStepKernel table[] = {trex_step_table_entry<I / (int)TREX_FEAT_COUNT, (unsigned)I % TREX_FEAT_COUNT>()...};
+  return table[form * (int)TREX_FEAT_COUNT + (int)features];
+}
+static TrexStepKernel trex_step_variant(int form, unsigned features) {
+  if (form < 0 || form >= FORM_COUNT || features >= TREX_FEAT_COUNT) return nullptr;
+  return trex_step_table(form, features, std::make_integer_sequence<int, FORM_COUNT * (int)TREX_FEAT_COUNT>{});
+}
+
+#if !TREX_ACT_TU
 // ---------------------------------------------------------------- small utility kernels
 __global__ void trex_pack_state_kernel(const TrexDeviceModel *M, TrexBatchArrays arr, int n, float *out, int pack) {
   // pack=1: internal -> [N, 13+2J]; pack=0: [N, 13+2J] -> internal
@@ -2617,7 +2609,7 @@ __global__ void trex_pack_state_kernel(const TrexDeviceModel *M, TrexBatchArrays
   }
 }
 
-__global__ void trex_head_kernel(KernelArgs args, float *out) {
+__global__ void trex_head_kernel(TrexStepArgs args, float *out) {
   // FK only; one team per env. Reuses nothing from the step kernel to stay simple: serial per lane 0.
   const int env = blockIdx.x * blockDim.x + threadIdx.x;
   if (env >= args.n_envs) return;
@@ -2652,7 +2644,7 @@ __global__ void trex_head_kernel(KernelArgs args, float *out) {
 
 // Rollout export: world pose of every URDF link. One 64-thread block per env: lanes < nb walk their
 // body's chain from the base (<= 6 hinges) and park R, p in LDS; then the block strides over the links.
-__global__ __launch_bounds__(64) void trex_link_transforms_kernel(KernelArgs args, float *out, int L, const int *frame_body,
+__global__ __launch_bounds__(64) void trex_link_transforms_kernel(TrexStepArgs args, float *out, int L, const int *frame_body,
                                                                   const float *frame_tf) {
   __shared__ float bodyR[TL][9], bodyP[TL][3];
   const int env = blockIdx.x;
@@ -2785,107 +2777,34 @@ __global__ void trex_contact_wrench_kernel(const float *src, float *dst, int n, 
 }
 
 // ---------------------------------------------------------------- host launchers (called by capi.cpp)
-// the step launch of a batch of n envs takes the pair form (two envs per workgroup) for an even batch that is resident at once
-static bool trex_pair_launch(int n) { return TREX_PAIR_LAUNCH && (n & 1) == 0 && n <= TREX_PAIR_MAX; }
-
 extern "C" {
 
-hipError_t trex_launch_step(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions,
-                            float *obs, float *reward, uint8_t *done, float *penalties, float wd, float we,
-                            float wk, float *debug, hipStream_t stream, float *done_f, int obs_stride, int scal_stride,
-                            int balance, int pen_in_rows, float *warm, const float *ext, float *sens) {
-  // balance: the env-to-wave assignment by contact rank (trex_batch_set_wave_balance decides; capi.cpp). Diagnostics
-  // launches keep env k in workgroup k (the stamped build is balanced like the product: it reports the env of every wave)
-  int32_t *perm = ((debug && !TREX_STAMPS) || !balance) ? nullptr : arr.balance;
-  KernelArgs a{model, arr, n, actions, obs, reward, done, done_f, obs_stride, scal_stride, penalties, nullptr, perm, wd, we, wk, debug,
-               1, 0, pen_in_rows, warm, ext, sens};
-
-  const bool pair = trex_pair_launch(n);
-  if (sens) {   // (capi.cpp refuses a diagnostics step while the sensor is on; the stamped build has no SENS instantiations)
-    if (debug || TREX_STAMPS) return hipErrorInvalidValue;
-    if constexpr (!TREX_STAMPS) {
-      const dim3 g(pair ? n / 2 : n), b(pair ? 128 : 64);
-      if (pair) {
-        if (warm) { if (ext) hipLaunchKernelGGL((trex_step_pair_sens_kernel<true, true>), g, b, 0, stream, a);
-                    else hipLaunchKernelGGL((trex_step_pair_sens_kernel<true, false>), g, b, 0, stream, a); }
-        else { if (ext) hipLaunchKernelGGL((trex_step_pair_sens_kernel<false, true>), g, b, 0, stream, a);
-               else hipLaunchKernelGGL((trex_step_pair_sens_kernel<false, false>), g, b, 0, stream, a); }
-      } else {
-        if (warm) { if (ext) hipLaunchKernelGGL((trex_step_sens_kernel<true, true>), g, b, 0, stream, a);
-                    else hipLaunchKernelGGL((trex_step_sens_kernel<true, false>), g, b, 0, stream, a); }
-        else { if (ext) hipLaunchKernelGGL((trex_step_sens_kernel<false, true>), g, b, 0, stream, a);
-               else hipLaunchKernelGGL((trex_step_sens_kernel<false, false>), g, b, 0, stream, a); }
-      }
-    }
-    return hipGetLastError();
-  }
-  if (ext) {   // (capi.cpp refuses a diagnostics step of a batch with a wrench; the stamped build has no EXT instantiations)
-    if (debug || TREX_STAMPS) return hipErrorInvalidValue;
-    if constexpr (!TREX_STAMPS) {
-      if (pair) {
-        if (warm) hipLaunchKernelGGL(trex_step_pair_ext_kernel<true>, dim3(n / 2), dim3(128), 0, stream, a);
-        else hipLaunchKernelGGL(trex_step_pair_ext_kernel<false>, dim3(n / 2), dim3(128), 0, stream, a);
-      } else {
-        if (warm) hipLaunchKernelGGL(trex_step_ext_kernel<true>, dim3(n), dim3(64), 0, stream, a);
-        else hipLaunchKernelGGL(trex_step_ext_kernel<false>, dim3(n), dim3(64), 0, stream, a);
-      }
-    }
-    return hipGetLastError();
-  }
-  // the stamped diagnostic build launches the PRODUCT instantiation, stamped, for a debug pointer too (the dump of
-  // <false, true> would change its code; `if constexpr`: that build does not instantiate <false, true> at all)
-  if (debug && !TREX_STAMPS) {   // (capi.cpp refuses a diagnostics step of a warm batch: this instantiation has no record)
-    if (warm) return hipErrorInvalidValue;
-    if constexpr (!TREX_STAMPS) hipLaunchKernelGGL((trex_step_kernel<false, true>), dim3(n), dim3(64), 0, stream, a);
-  } else if (warm) {
-    if (pair) hipLaunchKernelGGL(trex_step_pair_warm_kernel, dim3(n / 2), dim3(128), 0, stream, a);
-    else hipLaunchKernelGGL(trex_step_warm_kernel<false>, dim3(n), dim3(64), 0, stream, a);
-  } else if (pair) hipLaunchKernelGGL(trex_step_pair_kernel, dim3(n / 2), dim3(128), 0, stream, a);
-  else hipLaunchKernelGGL((trex_step_kernel<false, false>), dim3(n), dim3(64), 0, stream, a);
-  return hipGetLastError();
+// THE decision of a launch's form, for the launch and for trex_batch_launch_info alike: the pair form (two envs per workgroup) for
+// the step launch of an even batch that is resident at once - where the build has it (TREX_PAIR_LAUNCH, TREX_PAIR_MAX) and it exists
+// for these features: a warm batch with actuators steps through the single-env form (trex_step_variant_exists)
+TrexStepShape trex_step_launch_shape(TrexStepKind kind, int n, unsigned features) {
+  const bool pair = kind == TREX_KIND_STEP && TREX_PAIR_LAUNCH && (n & 1) == 0 && n <= TREX_PAIR_MAX &&
+                    trex_step_variant_exists(FORM_PAIR, features);
+  const int epw = pair ? 2 : 1;
+  const size_t lds = (pair ? 2 * sizeof(WaveLds) + sizeof(CgLds) : sizeof(WaveLds)) +
+                     ((features & TREX_FEAT_WARM) ? epw * MAXC * sizeof(float4) : 0);   // (WARM: the record of every env, Wrec)
+  return {epw, (n + epw - 1) / epw, 64 * epw, (int)lds};   // one wavefront per env
 }
 
-// S env-steps per launch (open-loop action sequences): actions [S, N, J], rows [S, N, row_stride] = obs | reward | done,
-// penalties [S, N, 3] and done bytes [S, N] nullable
-hipError_t trex_launch_step_many(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions, float *rows,
-                                 int row_stride, int n_steps, float *penalties, uint8_t *done, float wd, float we, float wk,
-                                 hipStream_t stream, int balance, int nj, int pen_in_rows, float *warm, const float *ext,
-                                 float *sens) {
-  float *rew = rows + 3 * nj;
-  KernelArgs a{model, arr, n, actions, rows, rew, done, rew + 1, row_stride, row_stride, penalties, nullptr,
-               balance ? arr.balance : nullptr, wd, we, wk, nullptr, n_steps, (long long)n * row_stride, pen_in_rows, warm, ext, sens};
-  if (sens) {
-    if (TREX_STAMPS) return hipErrorInvalidValue;
-    if constexpr (!TREX_STAMPS) {
-      if (warm) { if (ext) hipLaunchKernelGGL((trex_step_many_sens_kernel<true, true>), dim3(n), dim3(64), 0, stream, a);
-                  else hipLaunchKernelGGL((trex_step_many_sens_kernel<true, false>), dim3(n), dim3(64), 0, stream, a); }
-      else { if (ext) hipLaunchKernelGGL((trex_step_many_sens_kernel<false, true>), dim3(n), dim3(64), 0, stream, a);
-             else hipLaunchKernelGGL((trex_step_many_sens_kernel<false, false>), dim3(n), dim3(64), 0, stream, a); }
-    }
-  } else if (ext) {
-    if (TREX_STAMPS) return hipErrorInvalidValue;
-    if constexpr (!TREX_STAMPS) {
-      if (warm) hipLaunchKernelGGL(trex_step_many_ext_kernel<true>, dim3(n), dim3(64), 0, stream, a);
-      else hipLaunchKernelGGL(trex_step_many_ext_kernel<false>, dim3(n), dim3(64), 0, stream, a);
-    }
-  } else if (warm) hipLaunchKernelGGL(trex_step_many_warm_kernel, dim3(n), dim3(64), 0, stream, a);
-  else hipLaunchKernelGGL(trex_step_many_kernel, dim3(n), dim3(64), 0, stream, a);
-  return hipGetLastError();
-}
-
-hipError_t trex_launch_reset(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const uint8_t *mask,
-                             float *obs, float wd, float we, float wk, float *debug, hipStream_t stream, int obs_stride,
-                             float *reward, float *done_f, int scal_stride, int nj, int pen_in_rows, float *warm, float *sens) {
-  KernelArgs a{model, arr, n, nullptr, obs, reward, nullptr, done_f, obs_stride, scal_stride, nullptr, mask, nullptr, wd, we, wk, debug,
-               1, 0, (reward && done_f && pen_in_rows) ? 1 : 0, warm, nullptr, sens};
-  if (sens) {
-    if (TREX_STAMPS) return hipErrorInvalidValue;
-    if constexpr (!TREX_STAMPS) {
-      if (warm) hipLaunchKernelGGL(trex_reset_sens_kernel<true>, dim3(n), dim3(64), 0, stream, a);
-      else hipLaunchKernelGGL(trex_reset_sens_kernel<false>, dim3(n), dim3(64), 0, stream, a);
-    }
-  } else if (warm) hipLaunchKernelGGL(trex_step_warm_kernel<true>, dim3(n), dim3(64), 0, stream, a);
-  else hipLaunchKernelGGL((trex_step_kernel<true, false>), dim3(n), dim3(64), 0, stream, a);
+// Every step launch: the kernel is the table's for the form - the kind's, or the pair form - and the features the arguments carry.
+hipError_t trex_launch_step(const TrexStepArgs *args, TrexStepKind kind, hipStream_t stream) {
+  TrexStepArgs a = *args;
+  const unsigned features = trex_step_features(a);
+  // The stamped diagnostic build runs the PRODUCT instantiation, stamped and balanced, for a diagnostics step too (the dump of
+  // <false, true> would change its code, and it reports the env of every wave); else a diagnostics step keeps env k in workgroup k.
+  if (TREX_STAMPS && kind == TREX_KIND_STEP_DEBUG) kind = TREX_KIND_STEP;
+  if (kind == TREX_KIND_STEP_DEBUG) a.bal = nullptr;
+  const TrexStepShape shape = trex_step_launch_shape(kind, a.n_envs, features);
+  const int form = shape.envs_per_workgroup == 2 ? (int)FORM_PAIR : (int)kind;
+  const TrexStepKernel kernel = (features & TREX_FEAT_ACT) ? trex_step_act_variant(form, features) : trex_step_variant(form, features);
+  if (!kernel) return hipErrorInvalidValue;   // (capi.cpp refuses what does not exist - a diagnostics step of a batch with a feature -
+                                              // before it gets here)
+  hipLaunchKernelGGL(kernel, dim3(shape.grid), dim3(shape.block), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -2896,14 +2815,14 @@ hipError_t trex_launch_pack_state(const TrexDeviceModel *model, TrexBatchArrays 
 }
 
 hipError_t trex_launch_head(const TrexDeviceModel *model, TrexBatchArrays arr, int n, float *out, hipStream_t stream) {
-  KernelArgs a{model, arr, n, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr};
+  TrexStepArgs a{model, arr, n, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr};
   hipLaunchKernelGGL(trex_head_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a, out);
   return hipGetLastError();
 }
 
 hipError_t trex_launch_link_transforms(const TrexDeviceModel *model, TrexBatchArrays arr, int n, float *out, hipStream_t stream,
                                        int visuals) {
-  KernelArgs a{model, arr, n, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr};
+  TrexStepArgs a{model, arr, n, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr};
   if (visuals) hipLaunchKernelGGL(trex_link_transforms_kernel, dim3(n), dim3(64), 0, stream, a, out, arr.num_visuals, arr.visual_body, arr.visual_tf);
   else hipLaunchKernelGGL(trex_link_transforms_kernel, dim3(n), dim3(64), 0, stream, a, out, arr.num_links, arr.link_body, arr.link_tf);
   return hipGetLastError();
@@ -2939,91 +2858,13 @@ hipError_t trex_launch_copy_gains(const TrexDeviceModel *model, const float *kp,
   hipLaunchKernelGGL(trex_copy_gains_kernel, dim3((n * TL + 255) / 256), dim3(256), 0, stream, model, kp, kd, max_force, dst, n);
   return hipGetLastError();
 }
-int trex_actuator_floats(void) { return ACT_ROWS * TL; }   // per env: the batch's motor-gain buffer (capi.cpp)
 hipError_t trex_launch_copy_wrench(const float *src, float *dst, int n, int nb, hipStream_t stream) {
   hipLaunchKernelGGL(trex_copy_wrench_kernel, dim3((n * 6 * TL + 255) / 256), dim3(256), 0, stream, src, dst, n, nb);
   return hipGetLastError();
 }
 
-// launch shape of the step launch for a batch of n envs (trex_batch_launch_info)
-int trex_step_envs_per_workgroup(int n) { return trex_pair_launch(n) ? 2 : 1; }
-int trex_step_lds_bytes(int n) { return trex_step_envs_per_workgroup(n) == 2 ? (int)(2 * sizeof(WaveLds) + sizeof(CgLds)) : (int)sizeof(WaveLds); }
-int trex_contact_sensor_floats(void) { return SENS_ROWS * TL; }   // per env: the batch's contact-sensor buffer (capi.cpp)
-int trex_step_single_lds_bytes(void) { return (int)sizeof(WaveLds); }   // the single-env form's, whatever the batch size
-int trex_step_warm_lds_bytes(void) { return (int)(MAXC * sizeof(float4)); }   // per env, on top of the above in the warm kernels
-
 }  // extern "C"
 
-#elif TREX_ACT_TU == 1   // the product step launches with the actuator model (ACT above), with and without WARM, EXT and SENS
-#if !TREX_STAMPS   // (the stamped diagnostic build launches none of them and instantiates none)
-template <bool WARM, bool EXT, bool SENS>
-__global__ __launch_bounds__(64, 4) void trex_step_act_kernel(KernelArgs args) { trex_step_body<false, false, false, false, WARM, EXT, SENS, true>(args, (int)blockIdx.x); }
-// (the pair form without WARM only: with the warm-start record and the gains the pair form's row set-up no longer fits 128 registers -
-// 36 bytes of scratch per lane in three of its four instantiations -, so a warm batch with actuators steps through the single-env
-// form, whose rows are bitwise the same)
-template <bool WARM, bool EXT, bool SENS>
-__global__ __launch_bounds__(128, 4) void trex_step_pair_act_kernel(KernelArgs args) {
-  static_assert(!WARM, "no pair form with WARM and ACT");
-  trex_step_body<false, false, false, true, false, EXT, SENS, true>(args, (int)blockIdx.x);
-}
-template <bool WARM, bool EXT, bool SENS>
-__global__ __launch_bounds__(64, 4) void trex_step_many_act_kernel(KernelArgs args) { trex_step_body<false, false, true, false, WARM, EXT, SENS, true>(args, (int)blockIdx.x); }
-#define TREX_ACT_LAUNCH(K, g, b)                                                                        \
-  switch ((a.warm ? 4 : 0) | (a.ext ? 2 : 0) | (a.sens ? 1 : 0)) {                                      \
-    case 0: hipLaunchKernelGGL((K<false, false, false>), g, b, 0, stream, a); break;                    \
-    case 1: hipLaunchKernelGGL((K<false, false, true>), g, b, 0, stream, a); break;                     \
-    case 2: hipLaunchKernelGGL((K<false, true, false>), g, b, 0, stream, a); break;                     \
-    case 3: hipLaunchKernelGGL((K<false, true, true>), g, b, 0, stream, a); break;                      \
-    case 4: hipLaunchKernelGGL((K<true, false, false>), g, b, 0, stream, a); break;                     \
-    case 5: hipLaunchKernelGGL((K<true, false, true>), g, b, 0, stream, a); break;                      \
-    case 6: hipLaunchKernelGGL((K<true, true, false>), g, b, 0, stream, a); break;                      \
-    default: hipLaunchKernelGGL((K<true, true, true>), g, b, 0, stream, a); break;                      \
-  }
-#endif
-
-extern "C" {
-
-// trex_launch_step / trex_launch_step_many for a batch whose actuator model is active (capi.cpp decides): the same arguments and
-// the actuators (device_model.h); the pair form for the same batches
-hipError_t trex_launch_step_act(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions,
-                                float *obs, float *reward, uint8_t *done, float *penalties, float wd, float we,
-                                float wk, hipStream_t stream, float *done_f, int obs_stride, int scal_stride,
-                                int balance, int pen_in_rows, float *warm, const float *ext, float *sens, const TrexActuators *act) {
-  if (!act || !act->gains) return hipErrorInvalidValue;
-#if TREX_STAMPS
-  return hipErrorInvalidValue;
-#else
-  KernelArgs a{model, arr, n, actions, obs, reward, done, done_f, obs_stride, scal_stride, penalties, nullptr,
-               balance ? arr.balance : nullptr, wd, we, wk, nullptr, 1, 0, pen_in_rows, warm, ext, sens,
-               act->gains, act->vel_mask, act->tor_mask, act->action_cols, act->kp_max};
-  if (TREX_PAIR_LAUNCH && (n & 1) == 0 && n <= TREX_PAIR_MAX && !warm) {
-    switch ((a.ext ? 2 : 0) | (a.sens ? 1 : 0)) {
-      case 0: hipLaunchKernelGGL((trex_step_pair_act_kernel<false, false, false>), dim3(n / 2), dim3(128), 0, stream, a); break;
-      case 1: hipLaunchKernelGGL((trex_step_pair_act_kernel<false, false, true>), dim3(n / 2), dim3(128), 0, stream, a); break;
-      case 2: hipLaunchKernelGGL((trex_step_pair_act_kernel<false, true, false>), dim3(n / 2), dim3(128), 0, stream, a); break;
-      default: hipLaunchKernelGGL((trex_step_pair_act_kernel<false, true, true>), dim3(n / 2), dim3(128), 0, stream, a); break;
-    }
-  } else { TREX_ACT_LAUNCH(trex_step_act_kernel, dim3(n), dim3(64)) }
-  return hipGetLastError();
-#endif
-}
-
-hipError_t trex_launch_step_many_act(const TrexDeviceModel *model, TrexBatchArrays arr, int n, const float *actions, float *rows,
-                                     int row_stride, int n_steps, float *penalties, uint8_t *done, float wd, float we, float wk,
-                                     hipStream_t stream, int balance, int nj, int pen_in_rows, float *warm, const float *ext,
-                                     float *sens, const TrexActuators *act) {
-  if (!act || !act->gains) return hipErrorInvalidValue;
-#if TREX_STAMPS
-  return hipErrorInvalidValue;
-#else
-  float *rew = rows + 3 * nj;
-  KernelArgs a{model, arr, n, actions, rows, rew, done, rew + 1, row_stride, row_stride, penalties, nullptr,
-               balance ? arr.balance : nullptr, wd, we, wk, nullptr, n_steps, (long long)n * row_stride, pen_in_rows, warm, ext, sens,
-               act->gains, act->vel_mask, act->tor_mask, act->action_cols, act->kp_max};
-  TREX_ACT_LAUNCH(trex_step_many_act_kernel, dim3(n), dim3(64))
-  return hipGetLastError();
-#endif
-}
-
-}  // extern "C"
+#else   // trex_step_act.hip: the product step launches with the actuator model (ACT above), with and without WARM, EXT and SENS
+extern "C" TrexStepKernel trex_step_act_variant(int form, unsigned features) { return trex_step_variant(form, features); }
 #endif   // TREX_ACT_TU

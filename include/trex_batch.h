@@ -355,6 +355,47 @@ int trex_batch_set_contact_sensor(TrexBatch *batch, int enabled);
  *     host memory or another device's memory returns TREX_E_INVALID before anything is launched. */
 int trex_batch_contact_wrench(TrexBatch *batch, float *out_dev, void *stream);
 
+/* ---- dynamics queries (pybullet's calculateInverseDynamics / calculateMassMatrix / calculateJacobian and what users derive from
+ *      getLinkState(computeLinkVelocity=1); no reference counterpart: gravity compensation, computed-torque and operational-space
+ *      controllers for TORQUE-mode joints, momentum / energy rewards, privileged critic inputs - without a host round trip)
+ *
+ * All four are asynchronous and ordered on `stream`, validate every device buffer like the other batch calls (host memory,
+ * another device's memory or a short buffer returns TREX_E_INVALID before anything is launched), allocate nothing and never wait
+ * for the device. The first call that sees a new caller buffer validates it with runtime queries, like every batch call; from
+ * the second call on - once the buffers have been seen - the calls are plain kernel launches, usable inside a stream capture.
+ * They read each env's current state and, once trex_batch_set_domain has set one, its per-env mass scale (mass and rotational
+ * inertia of a body scale together). They write nothing but their outputs: state, observations, the warm-start record, the
+ * contact sensor and the episode counts are untouched.
+ *
+ * Generalised velocity, D = 6 + J entries (31 for trex.urdf), in the order of the state vector: base linear velocity v(3) - of
+ * the base frame origin - and base angular velocity w(3), both in world axes, then qd(J) in observation order. Accelerations are
+ * the classical time derivatives of those (dv/dt is the acceleration of the base origin as a point, NOT the linear part of a
+ * spatial acceleration). Forces are their duals: force on the base, torque on the base about the base frame origin, joint
+ * torques. Relation to the CPU oracle (oracle/trex_oracle.c), checked in tests/test_dynamics_ref.py against oracle_get_state and
+ * oracle_minv: the oracle orders its generalised velocity [w(3), v(3), joints in BODY order] about the same point - the base
+ * origin, world axes - so the two differ by a permutation only: entries 0..2 <-> 3..5, and joint k here = body obs_order[k]
+ * there. oracle_forward_dynamics already returns the classical base acceleration as [dw/dt, dv/dt] and qdd in observation order. */
+
+/* force_dev [N, D] = M(q) a + h(q, qd) at every env's current state: the generalised force that produces the accelerations
+ * accel_dev [N, D] (NULL = zeros: h alone). Gravity is the model parameter "gravity". RIGID-BODY terms only: joint damping,
+ * "link_damping", motors, joint limits, contacts and external wrenches are NOT in it (pybullet's calculateInverseDynamics ignores
+ * them too) - a joint's share of them is the caller's to add. accel NULL on a state at rest is the gravity-compensation force. */
+int trex_batch_inverse_dynamics(TrexBatch *batch, const float *accel_dev, float *force_dev, void *stream);
+
+/* M_dev [N, D, D]: the joint-space inertia matrix M(q), full and exactly symmetric (both triangles written, bitwise equal). */
+int trex_batch_mass_matrix(TrexBatch *batch, float *M_dev, void *stream);
+
+/* J_dev [N, 6, D]: rows 0..2 map the generalised velocity to the world linear velocity of the point fixed in URDF link `link`
+ * at local_xyz (link frame; link indices and frames as trex_model_link_info and "link_tf"), rows 3..5 to the link's world angular
+ * velocity. Link and point are HOST values shared by all envs. A link outside [0, num_links) or a non-finite point returns
+ * TREX_E_INVALID. */
+int trex_batch_jacobian(TrexBatch *batch, int link, const double local_xyz[3], float *J_dev, void *stream);
+
+/* out_dev [N, 16]: [0,3) world position of the centre of mass, [3,6) its velocity, [6,9) linear momentum, [9,12) angular momentum
+ * about the centre of mass, [12] kinetic energy, [13] potential energy sum m g z (z = 0 is the world origin), [14] total mass
+ * (the env's mass scale included), [15] 0. World axes, SI units. */
+int trex_batch_centroidal(TrexBatch *batch, float *out_dev, void *stream);
+
 /* diagnostics of the last substep: contact count per env [N] i32 (nullable), summed normal
  * impulse per env [N] f32 (nullable). */
 int trex_batch_contact_stats(TrexBatch *batch, int32_t *count_dev, float *normal_impulse_dev, void *stream);

@@ -11,6 +11,7 @@
 
 #include "../../include/trex_batch.h"
 #include "device_model.h"
+#include "dynamics.h"
 #include "internal.hpp"
 #include "model.hpp"
 #include "render.h"
@@ -57,6 +58,9 @@ struct TrexBatch {
   float4 *render_plane = nullptr;
   int32_t *render_ids = nullptr;     // device copy of the env ids of the last call
   size_t render_ids_cap = 0;
+  // dynamics queries (trex_batch_jacobian): body and body<-link transform of every URDF link, host side
+  std::vector<int> link_body;
+  std::vector<trex::Tf> link_tf;
   // caller allocations already validated as memory of this device (base address, bytes known to be good):
   // the hot path pays one hash-free scan of a handful of entries, hipPointerGetAttributes only on a new one
   std::vector<TrexSeen> seen;
@@ -515,6 +519,7 @@ int trex_batch_create(const TrexModel *model, int num_envs, int device, TrexBatc
     for (int k = 0; k < 9; k++) ltf[12 * l + k] = (float)model->host.link_tf[l].R.m[k];
     ltf[12 * l + 9] = (float)model->host.link_tf[l].t.x; ltf[12 * l + 10] = (float)model->host.link_tf[l].t.y; ltf[12 * l + 11] = (float)model->host.link_tf[l].t.z;
   }
+  b->link_body = model->host.link_body; b->link_tf = model->host.link_tf;
   b->arr.num_links = (int)nl; b->arr.link_body = link_body_dev; b->arr.link_tf = link_tf_dev;
   r = hipMemcpy(link_body_dev, model->host.link_body.data(), nl * sizeof(int), hipMemcpyHostToDevice);
   if (r == hipSuccess) r = hipMemcpy(link_tf_dev, ltf.data(), ltf.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -856,6 +861,68 @@ int trex_batch_contact_wrench(TrexBatch *b, float *out_dev, void *stream) {
   DeviceGuard guard(b->device);
   BUF_TRY(out_dev, (size_t)b->n * b->nb * 6 * sizeof(float), "trex_batch_contact_wrench: out");
   HIP_TRY(trex_launch_contact_wrench(b->sens, out_dev, b->n, b->nb, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+// ---- dynamics queries (dynamics.hip): read the state, write only their outputs; nothing allocated, nothing waited for
+static TrexDynArgs dyn_args(const TrexBatch *b, float *out) {
+  TrexDynArgs a{};
+  a.model = b->dmodel; a.base = b->arr.base; a.q = b->arr.q; a.qd = b->arr.qd;
+  a.mass_scale = b->arr.domain ? b->arr.mass_scale : nullptr;
+  a.n_envs = b->n; a.nb = b->nb; a.out = out;
+  return a;
+}
+
+int trex_batch_inverse_dynamics(TrexBatch *b, const float *accel_dev, float *force_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!force_dev) return fail(TREX_E_INVALID, "trex_batch_inverse_dynamics: force is null");
+  DeviceGuard guard(b->device);
+  const size_t bytes = (size_t)b->n * (6 + b->nj) * sizeof(float);
+  BUF_TRY(accel_dev, bytes, "trex_batch_inverse_dynamics: accel");
+  BUF_TRY(force_dev, bytes, "trex_batch_inverse_dynamics: force");
+  TrexDynArgs a = dyn_args(b, force_dev);
+  a.accel = accel_dev;
+  HIP_TRY(trex_launch_dynamics(a, TREX_DYN_INVERSE_DYNAMICS, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+int trex_batch_mass_matrix(TrexBatch *b, float *M_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!M_dev) return fail(TREX_E_INVALID, "trex_batch_mass_matrix: M is null");
+  DeviceGuard guard(b->device);
+  const size_t D = 6 + (size_t)b->nj;
+  BUF_TRY(M_dev, (size_t)b->n * D * D * sizeof(float), "trex_batch_mass_matrix: M");
+  HIP_TRY(trex_launch_dynamics(dyn_args(b, M_dev), TREX_DYN_MASS_MATRIX, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+int trex_batch_jacobian(TrexBatch *b, int link, const double local_xyz[3], float *J_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!J_dev || !local_xyz) return fail(TREX_E_INVALID, "trex_batch_jacobian: null argument");
+  if (link < 0 || link >= (int)b->link_body.size())
+    return fail(TREX_E_INVALID, "trex_batch_jacobian: link " + std::to_string(link) + " out of range [0, " +
+                                    std::to_string(b->link_body.size()) + ")");
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(local_xyz[c])) return fail(TREX_E_INVALID, "trex_batch_jacobian: local_xyz is not finite");
+  DeviceGuard guard(b->device);
+  BUF_TRY(J_dev, (size_t)b->n * 6 * (6 + b->nj) * sizeof(float), "trex_batch_jacobian: J");
+  TrexDynArgs a = dyn_args(b, J_dev);
+  // the point in the frame of the link's body: body<-link transform of "link_tf"
+  const trex::Tf &t = b->link_tf[link];
+  const double tt[3] = {t.t.x, t.t.y, t.t.z};
+  a.jac_body = b->link_body[link];
+  for (int r = 0; r < 3; r++)
+    a.jac_point[r] = (float)(t.R.m[3 * r] * local_xyz[0] + t.R.m[3 * r + 1] * local_xyz[1] + t.R.m[3 * r + 2] * local_xyz[2] + tt[r]);
+  HIP_TRY(trex_launch_dynamics(a, TREX_DYN_JACOBIAN, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+int trex_batch_centroidal(TrexBatch *b, float *out_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!out_dev) return fail(TREX_E_INVALID, "trex_batch_centroidal: out is null");
+  DeviceGuard guard(b->device);
+  BUF_TRY(out_dev, (size_t)b->n * TREX_DYN_CENT_FLOATS * sizeof(float), "trex_batch_centroidal: out");
+  HIP_TRY(trex_launch_dynamics(dyn_args(b, out_dev), TREX_DYN_CENTROIDAL, (hipStream_t)stream));
   return TREX_OK;
 }
 

@@ -1,0 +1,455 @@
+// Dynamics queries on the batch state: inverse dynamics (RNEA), joint-space mass matrix (CRBA), point Jacobian of a link,
+// centroidal quantities. Read-only: nothing here writes the state. gfx950, one env per 64-lane wavefront, one body per lane,
+// four envs per workgroup so that the four outputs lie back to back and leave the chip as 16-byte stores.
+//
+// Conventions (include/trex_batch.h, "dynamics queries"): generalised velocity = base linear v(3), base angular w(3) - world
+// axes, v the velocity of the base frame origin - then qd in observation order; accelerations their classical derivatives;
+// forces the duals (force on the base, torque about the base origin, joint torques).
+//
+// Everything is written in world axes with positions RELATIVE TO THE BASE ORIGIN O (a few metres: f32 keeps its digits at any
+// world position). Unlike the step kernel's tree block, which refers every spatial quantity to one common point, the passes
+// here keep each body's quantities about ITS OWN points - forces at the COM, moments about the body's joint origin, composite
+// inertias about the composite's COM - and shift by the short lever between a body and its parent: a distal tail joint's
+// diagonal m |c - r|^2 + a.Ic a is then a sum of positive terms and not the difference of two m |r|^2 three metres out.
+#include <hip/hip_runtime.h>
+
+#include "dynamics.h"
+
+namespace {
+
+constexpr int TL = TREX_TL;
+constexpr int MAXCH = TREX_MAXCH;
+constexpr int WAVES = TREX_DYN_WAVES;
+constexpr int BLOCK = 64 * WAVES;
+
+__device__ __forceinline__ void cross3(const float *a, const float *b, float *o) {
+  const float x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
+  o[0] = x; o[1] = y; o[2] = z;
+}
+__device__ __forceinline__ float dot3(const float *a, const float *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+__device__ __forceinline__ void matvec3(const float *m, const float *v, float *o) {
+  const float x = m[0] * v[0] + m[1] * v[1] + m[2] * v[2];
+  const float y = m[3] * v[0] + m[4] * v[1] + m[5] * v[2];
+  const float z = m[6] * v[0] + m[7] * v[1] + m[8] * v[2];
+  o[0] = x; o[1] = y; o[2] = z;
+}
+__device__ __forceinline__ void matmul3(const float *a, const float *b, float *o) {
+  float t[9];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) t[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+#pragma unroll
+  for (int i = 0; i < 9; i++) o[i] = t[i];
+}
+// symmetric 3x3 (xx xy xz yy yz zz) times vector
+__device__ __forceinline__ void sym3_mul(const float *s, const float *v, float *o) {
+  const float x = s[0] * v[0] + s[1] * v[1] + s[2] * v[2];
+  const float y = s[1] * v[0] + s[3] * v[1] + s[4] * v[2];
+  const float z = s[2] * v[0] + s[4] * v[1] + s[5] * v[2];
+  o[0] = x; o[1] = y; o[2] = z;
+}
+__device__ __forceinline__ void quat_to_mat(const float *q, float *m) {
+  const float x = q[0], y = q[1], z = q[2], w = q[3];
+  m[0] = 1 - 2 * (y * y + z * z); m[1] = 2 * (x * y - z * w); m[2] = 2 * (x * z + y * w);
+  m[3] = 2 * (x * y + z * w); m[4] = 1 - 2 * (x * x + z * z); m[5] = 2 * (y * z - x * w);
+  m[6] = 2 * (x * z - y * w); m[7] = 2 * (y * z + x * w); m[8] = 1 - 2 * (x * x + y * y);
+}
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// What a lane knows of its body after walking the chain base -> body (at most MAXD hinges): pose, joint axis, and - VEL, ACC -
+// the classical velocity and acceleration of the body frame. All in world axes, positions relative to the base origin.
+struct Walk {
+  float R[9];    // world <- body
+  float r[3];    // body (= joint) origin
+  float a[3];    // joint axis
+  float w[3];    // angular velocity
+  float vo[3];   // velocity of the body origin
+  float al[3];   // angular acceleration
+  float ao[3];   // classical acceleration of the body origin, PLUS g z: gravity as the base's upward acceleration
+};
+
+// Level by level over depth: at level d every lane of depth >= d advances over its ancestor at that depth (itself at its
+// own). The lanes of one chain repeat their common ancestors' arithmetic in registers instead of waiting for them in LDS.
+template <bool VEL, bool ACC>
+__device__ __forceinline__ void walk_chain(const TrexDynArgs &A, const TrexDeviceModel *M, int env, int b, int D, Walk &k) {
+  const float *base = A.base + (size_t)env * 16;
+  const float quat[4] = {base[3], base[4], base[5], base[6]};
+  quat_to_mat(quat, k.R);
+  const float *acc = ACC && A.accel ? A.accel + (size_t)env * D : nullptr;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    k.r[c] = 0.f; k.a[c] = 0.f;
+    k.vo[c] = VEL ? base[7 + c] : 0.f; k.w[c] = VEL ? base[10 + c] : 0.f;
+    k.ao[c] = acc ? acc[c] : 0.f; k.al[c] = acc ? acc[3 + c] : 0.f;
+  }
+  if (ACC) k.ao[2] += M->prm[TP_GRAVITY];
+  const int maxdepth = M->maxdepth;
+  for (int d = 1; d <= maxdepth; d++) {
+    const int i = M->anc[d - 1][b];
+    if (i < 0) continue;
+    const float ax[3] = {M->axis[0][i], M->axis[1][i], M->axis[2][i]}, jp[3] = {M->jpos[0][i], M->jpos[1][i], M->jpos[2][i]};
+    float jr[9], rq[9], t[9], dw[3];
+#pragma unroll
+    for (int c = 0; c < 9; c++) jr[c] = M->jrot[c][i];
+    matvec3(k.R, jp, dw);   // parent origin -> this origin, a point of the PARENT body
+    if (VEL) {
+      float wxd[3];
+      cross3(k.w, dw, wxd);
+      if (ACC) {
+        float axd[3], wwd[3];
+        cross3(k.al, dw, axd); cross3(k.w, wxd, wwd);
+#pragma unroll
+        for (int c = 0; c < 3; c++) k.ao[c] += axd[c] + wwd[c];
+      }
+#pragma unroll
+      for (int c = 0; c < 3; c++) k.vo[c] += wxd[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) k.r[c] += dw[c];
+    const float q = A.q[(size_t)env * TL + i];
+    const float co = cosf(q), s = sinf(q), tt = 1.f - co;
+    rq[0] = tt * ax[0] * ax[0] + co;        rq[1] = tt * ax[0] * ax[1] - s * ax[2]; rq[2] = tt * ax[0] * ax[2] + s * ax[1];
+    rq[3] = tt * ax[0] * ax[1] + s * ax[2]; rq[4] = tt * ax[1] * ax[1] + co;        rq[5] = tt * ax[1] * ax[2] - s * ax[0];
+    rq[6] = tt * ax[0] * ax[2] - s * ax[1]; rq[7] = tt * ax[1] * ax[2] + s * ax[0]; rq[8] = tt * ax[2] * ax[2] + co;
+    matmul3(k.R, jr, t);
+    matmul3(t, rq, k.R);
+    matvec3(k.R, ax, k.a);
+    if (VEL) {
+      const float qd = A.qd[(size_t)env * TL + i];
+      if (ACC) {
+        // d/dt (a qd) = a qdd + (w_parent x a) qd
+        const float qdd = acc ? acc[6 + M->obs_slot[i]] : 0.f;
+        float wxa[3];
+        cross3(k.w, k.a, wxa);
+#pragma unroll
+        for (int c = 0; c < 3; c++) k.al[c] += k.a[c] * qdd + wxa[c] * qd;
+      }
+#pragma unroll
+      for (int c = 0; c < 3; c++) k.w[c] += k.a[c] * qd;
+    }
+  }
+}
+
+// mass, COM offset from the body origin and rotational inertia about the COM (world axes) of body b, the env's mass scale in
+struct Inertia { float m, cb[3], Ic[6]; };
+__device__ __forceinline__ void body_inertia(const TrexDynArgs &A, const TrexDeviceModel *M, int env, int b, const float *R, Inertia &I) {
+  const float sc = A.mass_scale ? A.mass_scale[(size_t)env * TL + b] : 1.0f;
+  I.m = M->mass[b] * sc;
+  const float comb[3] = {M->com[0][b], M->com[1][b], M->com[2][b]};
+  matvec3(R, comb, I.cb);
+  float in[6], t[9];
+#pragma unroll
+  for (int c = 0; c < 6; c++) in[c] = M->inertia[c][b];
+  const float Ib[9] = {in[0], in[1], in[2], in[1], in[3], in[4], in[2], in[4], in[5]};
+  matmul3(R, Ib, t);
+  const int ia[6] = {0, 0, 0, 1, 1, 2}, ib[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+  for (int c = 0; c < 6; c++)
+    I.Ic[c] = sc * (t[3 * ia[c]] * R[3 * ib[c]] + t[3 * ia[c] + 1] * R[3 * ib[c] + 1] + t[3 * ia[c] + 2] * R[3 * ib[c] + 2]);
+}
+
+// The workgroup's outputs - those of its (up to four) envs, back to back in LDS as in HBM - as 16-byte stores where the
+// caller's buffer allows it (four envs are a multiple of 16 bytes whatever D is: only its base address can be odd).
+__device__ __forceinline__ void block_store(float *dst, const float *src, int count) {
+  const int t = threadIdx.x;
+  if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+    const int n4 = count >> 2;
+    for (int i = t; i < n4; i += BLOCK) reinterpret_cast<float4 *>(dst)[i] = reinterpret_cast<const float4 *>(src)[i];
+    for (int i = (n4 << 2) + t; i < count; i += BLOCK) dst[i] = src[i];
+  } else {
+    for (int i = t; i < count; i += BLOCK) dst[i] = src[i];
+  }
+}
+
+template <int Q>
+__global__ __launch_bounds__(BLOCK) void trex_dynamics_kernel(TrexDynArgs A) {
+  extern __shared__ float4 lds4[];
+  float *lds = reinterpret_cast<float *>(lds4);
+  const TrexDeviceModel *M = A.model;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int env0 = blockIdx.x * WAVES, env = env0 + wave;
+  const int nb = A.nb, D = 6 + nb - 1;
+  const int per_env = trex_dyn_out_floats(Q, D);
+  const bool live = env < A.n_envs;                      // (a wave past the batch's end still meets the barriers)
+  const bool is_body = live && lane < nb;
+  const int b = is_body ? lane : 0;
+  const int e = live ? env : 0;
+  float *rec = lds + wave * TREX_DYN_BODY_FLOATS;        // [32][16] this env's per-body records
+  float *stage = lds + WAVES * TREX_DYN_BODY_FLOATS + wave * per_env;
+  const int depth = is_body ? M->depth[b] : -1;
+  const int maxdepth = M->maxdepth;
+  const int slot = is_body && b >= 1 ? 6 + M->obs_slot[b] : -1;   // this body's joint among the D velocities
+
+  if constexpr (Q == TREX_DYN_INVERSE_DYNAMICS) {
+    // ---- RNEA. Outward (in registers): classical velocity and acceleration of every body frame; the force at the COM
+    // and the moment about the body's joint origin that this motion needs.
+    Walk k;
+    walk_chain<true, true>(A, M, e, b, D, k);
+    Inertia I;
+    body_inertia(A, M, e, b, k.R, I);
+    float F[3], N[3];
+    {
+      float t0[3], t1[3], ac[3], Iw[3], Ial[3], wIw[3], cxf[3];
+      cross3(k.al, I.cb, t0);
+      cross3(k.w, I.cb, t1); cross3(k.w, t1, t1);
+#pragma unroll
+      for (int c = 0; c < 3; c++) ac[c] = k.ao[c] + t0[c] + t1[c];
+#pragma unroll
+      for (int c = 0; c < 3; c++) F[c] = I.m * ac[c];
+      sym3_mul(I.Ic, k.w, Iw); sym3_mul(I.Ic, k.al, Ial);
+      cross3(k.w, Iw, wIw); cross3(I.cb, F, cxf);
+#pragma unroll
+      for (int c = 0; c < 3; c++) N[c] = Ial[c] + wIw[c] + cxf[c];
+    }
+    // ---- inward, level by level: a body adds its children's force, and their moment shifted by the lever child -> body
+    if (is_body) {
+      float *o = rec + 16 * b;
+#pragma unroll
+      for (int c = 0; c < 3; c++) { o[c] = F[c]; o[3 + c] = N[c]; o[6 + c] = k.r[c]; }
+    }
+    __syncthreads();
+    for (int d = maxdepth - 1; d >= 0; d--) {
+      if (depth == d) {
+        bool any = false;
+        for (int kc = 0; kc < MAXCH; kc++) {
+          const int ch = M->child[kc][b];
+          if (ch < 0) break;
+          const float *o = rec + 16 * ch;
+          const float Fc[3] = {o[0], o[1], o[2]}, lever[3] = {o[6] - k.r[0], o[7] - k.r[1], o[8] - k.r[2]};
+          float lxf[3];
+          cross3(lever, Fc, lxf);
+#pragma unroll
+          for (int c = 0; c < 3; c++) { F[c] += Fc[c]; N[c] += o[3 + c] + lxf[c]; }
+          any = true;
+        }
+        if (any) {
+          float *o = rec + 16 * b;
+#pragma unroll
+          for (int c = 0; c < 3; c++) { o[c] = F[c]; o[3 + c] = N[c]; }
+        }
+      }
+      __syncthreads();
+    }
+    if (is_body) {
+      if (b == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) { stage[c] = F[c]; stage[3 + c] = N[c]; }
+      } else {
+        stage[slot] = dot3(k.a, N);
+      }
+    }
+  }
+
+  if constexpr (Q == TREX_DYN_MASS_MATRIX) {
+    // ---- CRBA. Composite rigid body of every subtree - mass, COM, rotational inertia about that COM - inward level by
+    // level (parallel-axis sums of positive terms); then every joint lane walks its ancestor chain: column j of M is the
+    // momentum of subtree j turning about joint j, row i its projection on joint i's motion.
+    Walk k;
+    walk_chain<false, false>(A, M, e, b, D, k);
+    Inertia I;
+    body_inertia(A, M, e, b, k.R, I);
+    float cm = I.m, cc[3], ci[6];
+#pragma unroll
+    for (int c = 0; c < 3; c++) cc[c] = k.r[c] + I.cb[c];
+#pragma unroll
+    for (int c = 0; c < 6; c++) ci[c] = I.Ic[c];
+    for (int i = lane; i < per_env; i += 64) stage[i] = 0.f;
+    if (is_body) {
+      float *o = rec + 16 * b;
+      o[0] = cm;
+#pragma unroll
+      for (int c = 0; c < 3; c++) { o[1 + c] = cc[c]; o[10 + c] = k.a[c]; o[13 + c] = k.r[c]; }
+#pragma unroll
+      for (int c = 0; c < 6; c++) o[4 + c] = ci[c];
+    }
+    __syncthreads();
+    for (int d = maxdepth - 1; d >= 0; d--) {
+      if (depth == d && M->child[0][b] >= 0) {
+        // total mass and COM (as an offset from the body's own COM), then every part's inertia shifted to it
+        float mt = cm, mo[3] = {0.f, 0.f, 0.f};
+        for (int kc = 0; kc < MAXCH; kc++) {
+          const int ch = M->child[kc][b];
+          if (ch < 0) break;
+          const float *o = rec + 16 * ch;
+          mt += o[0];
+#pragma unroll
+          for (int c = 0; c < 3; c++) mo[c] += o[0] * (o[1 + c] - cc[c]);
+        }
+        float ct[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) ct[c] = cc[c] + mo[c] / mt;
+        float it[6];
+        {
+          const float dv[3] = {cc[0] - ct[0], cc[1] - ct[1], cc[2] - ct[2]};
+          const float dd = dot3(dv, dv);
+          it[0] = ci[0] + cm * (dd - dv[0] * dv[0]); it[1] = ci[1] - cm * dv[0] * dv[1]; it[2] = ci[2] - cm * dv[0] * dv[2];
+          it[3] = ci[3] + cm * (dd - dv[1] * dv[1]); it[4] = ci[4] - cm * dv[1] * dv[2]; it[5] = ci[5] + cm * (dd - dv[2] * dv[2]);
+        }
+        for (int kc = 0; kc < MAXCH; kc++) {
+          const int ch = M->child[kc][b];
+          if (ch < 0) break;
+          const float *o = rec + 16 * ch;
+          const float mk = o[0], dv[3] = {o[1] - ct[0], o[2] - ct[1], o[3] - ct[2]};
+          const float dd = dot3(dv, dv);
+          it[0] += o[4] + mk * (dd - dv[0] * dv[0]); it[1] += o[5] - mk * dv[0] * dv[1]; it[2] += o[6] - mk * dv[0] * dv[2];
+          it[3] += o[7] + mk * (dd - dv[1] * dv[1]); it[4] += o[8] - mk * dv[1] * dv[2]; it[5] += o[9] + mk * (dd - dv[2] * dv[2]);
+        }
+        cm = mt;
+#pragma unroll
+        for (int c = 0; c < 3; c++) cc[c] = ct[c];
+#pragma unroll
+        for (int c = 0; c < 6; c++) ci[c] = it[c];
+        float *o = rec + 16 * b;
+        o[0] = cm;
+#pragma unroll
+        for (int c = 0; c < 3; c++) o[1 + c] = cc[c];
+#pragma unroll
+        for (int c = 0; c < 6; c++) o[4 + c] = ci[c];
+      }
+      __syncthreads();
+    }
+    // (every entry is written once, and to both triangles from the same register: the output is exactly symmetric)
+    if (is_body && b >= 1) {
+      // subtree j turning about joint j at unit rate: linear momentum p, angular momentum L about the subtree's COM
+      float lev[3] = {cc[0] - k.r[0], cc[1] - k.r[1], cc[2] - k.r[2]}, p[3], L[3], cxp[3];
+      cross3(k.a, lev, p);
+#pragma unroll
+      for (int c = 0; c < 3; c++) p[c] *= cm;
+      sym3_mul(ci, k.a, L);
+      cross3(cc, p, cxp);
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        const float lin = p[c], ang = L[c] + cxp[c];     // base rows: force, torque about the base origin
+        stage[c * D + slot] = lin; stage[slot * D + c] = lin;
+        stage[(3 + c) * D + slot] = ang; stage[slot * D + 3 + c] = ang;
+      }
+      for (int d = depth; d >= 1; d--) {
+        const int i = M->anc[d - 1][b];
+        const float *o = rec + 16 * i;
+        const float ai[3] = {o[10], o[11], o[12]}, li[3] = {cc[0] - o[13], cc[1] - o[14], cc[2] - o[15]};
+        float axl[3];
+        cross3(ai, li, axl);
+        const float v = dot3(ai, L) + dot3(axl, p);
+        const int si = 6 + M->obs_slot[i];
+        stage[si * D + slot] = v; stage[slot * D + si] = v;
+      }
+    }
+    if (is_body && b == 0) {
+      // the base block: the whole robot as one rigid body, its rotational inertia taken to the base origin
+      const float dd = dot3(cc, cc);
+      const float io[6] = {ci[0] + cm * (dd - cc[0] * cc[0]), ci[1] - cm * cc[0] * cc[1], ci[2] - cm * cc[0] * cc[2],
+                           ci[3] + cm * (dd - cc[1] * cc[1]), ci[4] - cm * cc[1] * cc[2], ci[5] + cm * (dd - cc[2] * cc[2])};
+      const float io9[9] = {io[0], io[1], io[2], io[1], io[3], io[4], io[2], io[4], io[5]};
+      // force of a unit angular velocity e_l: m (e_l x C)
+      const float cx[9] = {0.f, cm * cc[2], -cm * cc[1], -cm * cc[2], 0.f, cm * cc[0], cm * cc[1], -cm * cc[0], 0.f};
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          stage[r * D + c] = r == c ? cm : 0.f;
+          stage[(3 + r) * D + 3 + c] = io9[3 * r + c];
+          stage[r * D + 3 + c] = cx[3 * r + c]; stage[(3 + c) * D + r] = cx[3 * r + c];
+        }
+    }
+  }
+
+  if constexpr (Q == TREX_DYN_JACOBIAN) {
+    Walk k;
+    walk_chain<false, false>(A, M, e, b, D, k);
+    const int B = A.jac_body;
+    if (is_body && b == B) {
+      const float pt[3] = {A.jac_point[0], A.jac_point[1], A.jac_point[2]};
+      float o[3];
+      matvec3(k.R, pt, o);
+#pragma unroll
+      for (int c = 0; c < 3; c++) rec[c] = k.r[c] + o[c];
+    }
+    __syncthreads();
+    if (is_body) {
+      const float P[3] = {rec[0], rec[1], rec[2]};   // the point, relative to the base origin
+      if (b == 0) {
+        const float ex[9] = {0.f, P[2], -P[1], -P[2], 0.f, P[0], P[1], -P[0], 0.f};   // row r, column l: (e_l x P)_r
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            stage[r * D + c] = r == c ? 1.f : 0.f;
+            stage[r * D + 3 + c] = ex[3 * r + c];
+            stage[(3 + r) * D + c] = 0.f;
+            stage[(3 + r) * D + 3 + c] = r == c ? 1.f : 0.f;
+          }
+      } else {
+        // joint b moves the point iff b lies on the chain of the point's body
+        const bool on = M->depth[B] >= depth && M->anc[depth - 1][B] == b;
+        float lev[3] = {P[0] - k.r[0], P[1] - k.r[1], P[2] - k.r[2]}, lin[3];
+        cross3(k.a, lev, lin);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+          stage[c * D + slot] = on ? lin[c] : 0.f;
+          stage[(3 + c) * D + slot] = on ? k.a[c] : 0.f;
+        }
+      }
+    }
+  }
+
+  if constexpr (Q == TREX_DYN_CENTROIDAL) {
+    Walk k;
+    walk_chain<true, false>(A, M, e, b, D, k);
+    Inertia I;
+    body_inertia(A, M, e, b, k.R, I);
+    const float m = is_body ? I.m : 0.f;
+    float c[3], vc[3], wxc[3], Iw[3];
+    cross3(k.w, I.cb, wxc);
+    sym3_mul(I.Ic, k.w, Iw);
+#pragma unroll
+    for (int x = 0; x < 3; x++) { c[x] = k.r[x] + I.cb[x]; vc[x] = k.vo[x] + wxc[x]; }
+    const float *base = A.base + (size_t)e * 16;
+    const float mt = wave_sum(m);
+    float C[3], V[3], p[3], Lb[3], L[3];
+#pragma unroll
+    for (int x = 0; x < 3; x++) {
+      C[x] = wave_sum(m * c[x]) / mt;
+      p[x] = wave_sum(m * vc[x]);
+      V[x] = p[x] / mt;
+    }
+    const float ke = wave_sum(is_body ? 0.5f * (m * dot3(vc, vc) + dot3(k.w, Iw)) : 0.f);
+    const float pe = wave_sum(m * M->prm[TP_GRAVITY] * (base[2] + c[2]));
+    {
+      const float dc[3] = {c[0] - C[0], c[1] - C[1], c[2] - C[2]}, dv[3] = {vc[0] - V[0], vc[1] - V[1], vc[2] - V[2]};
+      cross3(dc, dv, Lb);
+#pragma unroll
+      for (int x = 0; x < 3; x++) L[x] = wave_sum(is_body ? Iw[x] + m * Lb[x] : 0.f);
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int x = 0; x < 3; x++) { stage[x] = base[x] + C[x]; stage[3 + x] = V[x]; stage[6 + x] = p[x]; stage[9 + x] = L[x]; }
+      stage[12] = ke; stage[13] = pe; stage[14] = mt; stage[15] = 0.f;
+    }
+  }
+
+  __syncthreads();
+  const int envs_here = min(WAVES, A.n_envs - env0);
+  block_store(A.out + (size_t)env0 * per_env, lds + WAVES * TREX_DYN_BODY_FLOATS, envs_here * per_env);
+}
+
+}  // namespace
+
+extern "C" hipError_t trex_launch_dynamics(const TrexDynArgs &args, int query, hipStream_t stream) {
+  if (args.n_envs <= 0 || args.nb < 1 || args.nb > TL) return hipErrorInvalidValue;
+  const int D = 6 + args.nb - 1;
+  const dim3 grid((args.n_envs + WAVES - 1) / WAVES), block(BLOCK);
+  const size_t lds = (size_t)trex_dyn_lds_bytes(query, D);
+  switch (query) {
+    case TREX_DYN_INVERSE_DYNAMICS: hipLaunchKernelGGL(trex_dynamics_kernel<TREX_DYN_INVERSE_DYNAMICS>, grid, block, lds, stream, args); break;
+    case TREX_DYN_MASS_MATRIX: hipLaunchKernelGGL(trex_dynamics_kernel<TREX_DYN_MASS_MATRIX>, grid, block, lds, stream, args); break;
+    case TREX_DYN_JACOBIAN: hipLaunchKernelGGL(trex_dynamics_kernel<TREX_DYN_JACOBIAN>, grid, block, lds, stream, args); break;
+    case TREX_DYN_CENTROIDAL: hipLaunchKernelGGL(trex_dynamics_kernel<TREX_DYN_CENTROIDAL>, grid, block, lds, stream, args); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}

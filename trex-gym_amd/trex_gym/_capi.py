@@ -42,6 +42,7 @@ SYMBOLS = [
     "trex_model_num_visuals", "trex_model_visual_info", "trex_batch_visual_transforms", "trex_batch_step_many",
     "trex_batch_render", "trex_batch_set_external_wrench", "trex_batch_set_contact_sensor", "trex_batch_contact_wrench",
     "trex_batch_set_control_mode", "trex_batch_set_motor_gains", "trex_batch_set_stiffness_actions",
+    "trex_batch_inverse_dynamics", "trex_batch_mass_matrix", "trex_batch_jacobian", "trex_batch_centroidal",
 ]
 
 # every symbol include/trex_policy.h declares (the trainer-side kernels)
@@ -98,6 +99,11 @@ if hasattr(lib, "trex_batch_set_control_mode"):   # (a TREX_LIB built from an ol
     lib.trex_batch_set_motor_gains.argtypes = [_vp, _vp, _vp, _vp, _vp]
     lib.trex_batch_set_stiffness_actions.argtypes = [_vp, C.c_int, C.c_float]
 lib.trex_batch_contact_wrench.argtypes = [_vp, _vp, _vp]
+if hasattr(lib, "trex_batch_inverse_dynamics"):   # (as above: an older TREX_LIB has no dynamics queries)
+    lib.trex_batch_inverse_dynamics.argtypes = [_vp, _vp, _vp, _vp]
+    lib.trex_batch_mass_matrix.argtypes = [_vp, _vp, _vp]
+    lib.trex_batch_jacobian.argtypes = [_vp, C.c_int, C.POINTER(C.c_double), _vp, _vp]
+    lib.trex_batch_centroidal.argtypes = [_vp, _vp, _vp]
 lib.trex_model_use_primitive_collision.argtypes = [_vp, C.c_double, C.c_int, C.c_int]
 lib.trex_model_fit_hull_primitives.argtypes = [_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
 lib.trex_model_num_links.argtypes = [_vp]
@@ -473,6 +479,50 @@ class Batch:
             out = torch.empty(self.num_envs, self.model.num_bodies, 6, dtype=torch.float32, device=self.device)
         check(lib.trex_batch_contact_wrench(self.h, self._p(out, "float32", self.num_envs * self.model.num_bodies * 6, "out"),
                                             self._stream(stream)))
+        return out
+
+    # ---- dynamics queries (include/trex_batch.h): read the state, write `out` (made when None) and return it
+    def _out(self, out, *shape):
+        import torch
+        if out is None:
+            out = torch.empty(self.num_envs, *shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != (self.num_envs,) + shape:
+            raise TrexError(E_INVALID, "out: expected shape %s, got %s" % ((self.num_envs,) + shape, tuple(out.shape)))
+        return out
+
+    def inverse_dynamics(self, accel=None, out=None, stream=None):
+        """[n, D] generalised force M a + h of accel [n, D] (None = zeros) at the current state, D = 6 + J: base force, base
+        torque about the base origin, joint torques in observation order. Rigid-body terms only."""
+        D = 6 + self.J
+        if accel is not None and tuple(accel.shape) != (self.num_envs, D):
+            raise TrexError(E_INVALID, "accel: expected shape %s, got %s" % ((self.num_envs, D), tuple(accel.shape)))
+        out = self._out(out, D)
+        check(lib.trex_batch_inverse_dynamics(self.h, self._p(accel, "float32", self.num_envs * D, "accel"),
+                                              self._p(out, "float32", self.num_envs * D, "out"), self._stream(stream)))
+        return out
+
+    def mass_matrix(self, out=None, stream=None):
+        """[n, D, D] joint-space inertia matrix, both triangles."""
+        D = 6 + self.J
+        out = self._out(out, D, D)
+        check(lib.trex_batch_mass_matrix(self.h, self._p(out, "float32", self.num_envs * D * D, "out"), self._stream(stream)))
+        return out
+
+    def jacobian(self, link, position=None, out=None, stream=None):
+        """[n, 6, D] Jacobian of the point `position` (link frame, None = the link origin) of URDF link index `link`: rows 0..2
+        its world linear velocity, rows 3..5 the link's world angular velocity, per unit generalised velocity."""
+        D = 6 + self.J
+        out = self._out(out, 6, D)
+        xyz = (C.c_double * 3)(*([0.0, 0.0, 0.0] if position is None else [float(x) for x in position]))
+        check(lib.trex_batch_jacobian(self.h, int(link), xyz, self._p(out, "float32", self.num_envs * 6 * D, "out"),
+                                      self._stream(stream)))
+        return out
+
+    def centroidal(self, out=None, stream=None):
+        """[n, 16]: COM position, COM velocity, linear momentum, angular momentum about the COM, kinetic energy, potential
+        energy, total mass, 0."""
+        out = self._out(out, 16)
+        check(lib.trex_batch_centroidal(self.h, self._p(out, "float32", self.num_envs * 16, "out"), self._stream(stream)))
         return out
 
     def contact_stats(self, count=None, normal_impulse=None, stream=None):

@@ -109,6 +109,30 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
             self._sensor_on = True
         return self._vec.contact_wrench()[0].cpu().numpy()
 
+    # dynamics queries of the one env, as numpy (TrexVecEnv has the batched ones and their conventions)
+    def inverse_dynamics(self, accel=None):
+        """[6 + J] generalised force M a + h for the accelerations accel [6 + J] (None: zeros) at the current state."""
+        if accel is not None:
+            accel = np.asarray(accel, np.float32).reshape(1, -1)
+        return self._vec.inverse_dynamics(accel)[0].cpu().numpy()
+
+    def gravity_compensation(self):
+        """[J] joint torques that hold the current state against gravity (inverse dynamics of zero accelerations)."""
+        return self._vec.gravity_compensation()[0].cpu().numpy()
+
+    def mass_matrix(self):
+        """[6 + J, 6 + J] joint-space inertia matrix."""
+        return self._vec.mass_matrix()[0].cpu().numpy()
+
+    def jacobian(self, link, position=None):
+        """[6, 6 + J] Jacobian of a point of a link (index or name; position in the link frame, None: its origin)."""
+        return self._vec.jacobian(link, position)[0].cpu().numpy()
+
+    def centroidal(self):
+        """COM, COM velocity, momentum, angular momentum about the COM, energies and mass (vec_env.Centroidal of numpy)."""
+        from .vec_env import Centroidal
+        return Centroidal(self._vec.centroidal().data[0].cpu().numpy())
+
     def should_terminate(self):
         return False
 

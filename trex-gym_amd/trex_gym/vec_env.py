@@ -26,6 +26,16 @@ from . import _capi, actuators, sharding, spaces
 REWARD_DEFAULTS = dict(distance_weight=1.0, energy_weight=0.005, drift_weight=0.002)  # trex_env.py:42-44
 
 
+class Centroidal:
+    """Named view of the [n, 16] block of trex_batch_centroidal (include/trex_batch.h); numpy or torch alike."""
+
+    def __init__(self, data):
+        self.data = data
+        self.com, self.com_velocity = data[..., 0:3], data[..., 3:6]
+        self.momentum, self.angular_momentum = data[..., 6:9], data[..., 9:12]
+        self.kinetic, self.potential, self.mass = data[..., 12], data[..., 13], data[..., 14]
+
+
 class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surface is baselines' VecEnv
     metadata = {"render.modes": ["human", "rgb_array"], "video.frames_per_second": 50}  # trex_env.py:33-36
 
@@ -396,6 +406,38 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         """[n, num_bodies, 6] on the device: floor-contact force at each body's COM and torque about it, world axes (N, N m),
         the mean over the substeps of the last step (a reset env: its settle substep; a contained env: zeros)."""
         return self.batch.contact_wrench(out)
+
+    # ---- dynamics queries (trex_batch_inverse_dynamics / _mass_matrix / _jacobian / _centroidal; no host sync)
+    # Generalised velocity [D = 6 + J]: base linear v(3), base angular w(3), world axes, then qd in observation order - the
+    # velocity part of get_state(); forces are its duals (base force, base torque about the base origin, joint torques).
+    def inverse_dynamics(self, accel=None, out=None):
+        """[n, D] generalised force M(q) a + h(q, qd) for the accelerations accel [n, D] (None: zeros) at the current state.
+        Rigid-body terms only: no joint damping, link damping, motors, limits or contacts (pybullet's calculateInverseDynamics)."""
+        if accel is not None:
+            accel = torch.as_tensor(accel).to(device=self.device, dtype=torch.float32).contiguous()
+        return self.batch.inverse_dynamics(accel, out)
+
+    def gravity_compensation(self):
+        """[n, J] joint torques of inverse_dynamics() with zero accelerations: what holds the joints against gravity (and the
+        velocity-product terms of a moving state), ready to add to the actions of TORQUE-mode joints."""
+        return self.batch.inverse_dynamics(None, None)[:, 6:]
+
+    def mass_matrix(self, out=None):
+        """[n, D, D] joint-space inertia matrix M(q), symmetric (pybullet's calculateMassMatrix)."""
+        return self.batch.mass_matrix(out)
+
+    def jacobian(self, link, position=None, out=None):
+        """[n, 6, D] Jacobian of the point `position` (link frame; None: the link origin) of link `link` (index or name):
+        rows 0..2 its world linear velocity, rows 3..5 the link's world angular velocity (pybullet's calculateJacobian)."""
+        from .perturb import LinkTable
+        if self._link_table is None:
+            self._link_table = LinkTable.from_model(self.model)
+        return self.batch.jacobian(self._link_table.index(link), position, out)
+
+    def centroidal(self, out=None):
+        """Whole-body quantities as a Centroidal of device tensors: com [n, 3], com_velocity, momentum, angular_momentum (about
+        the COM), kinetic [n], potential (sum m g z), mass (the env's mass scale included); `.data` is the [n, 16] block."""
+        return Centroidal(self.batch.centroidal(out))
 
     def contact_forces(self, links):
         """[n, K, 3] floor-contact force on URDF links: links = K entries, each a link name / index or a list of them (the

@@ -1,17 +1,19 @@
 #!/usr/bin/env python3
 """Is the device code of the step kernels the same in two source trees?  No GPU needed.
 
-    python scripts/compare_step_kernels.py --parent REV [--out profiles/NAME.txt] [--keep DIR]
+    python scripts/compare_step_kernels.py --parent REV [--out profiles/NAME.txt] [--keep DIR] [--expect-different NAME]...
 
-Compiles trex_step.hip and trex_step_act.hip of git revision REV and of the working tree to gfx950 assembly with the
-Makefile's flags (hipcc --cuda-device-only -S), as the product build and as the stamped build (-DTREX_STAMPS=1), and
+Compiles the kernel units of git revision REV and of the working tree - trex_step.hip, trex_step_act.hip, dynamics.hip and
+batch_util.hip, those a side has - to gfx950 assembly with the Makefile's flags (hipcc --cuda-device-only -S), as the product build and as the stamped build (-DTREX_STAMPS=1), and
 pairs every kernel of one side with its counterpart of the other: a step kernel by WHAT it is - (form, WARM, EXT, SENS,
 ACT), read off its demangled name under either naming, the wrapper families `trex_step{,_pair,_many}{,_warm,_ext,_sens,
 _act}_kernel` / `trex_reset_sens_kernel` or the one template `trex_step_variant_kernel<FORM, WARM, EXT, SENS, ACT>` -, a
-utility kernel by its name. A pair is IDENTICAL when the instruction text from the kernel's label to its .Lfunc_end and
+utility kernel by its name, whichever unit it lives in (a move between units is shown, `trex_step -> batch_util`, and is no
+difference; a step kernel has to stay in its unit). A pair is IDENTICAL when the instruction text from the kernel's label to its .Lfunc_end and
 its .amdhsa_* descriptor block are the same lines, after the kernel's own symbol and the function index inside local
 labels (.LBB<n>_, .Lfunc_end<n>) are normalised and the directives that place a kernel in a section are left out. Exit
-status 0 only if every kernel has a partner, every pair is identical and no kernel of the product build has a private
+status 0 only if every kernel has a partner, every pair is identical - but for the utility kernels named with --expect-different,
+which are listed with their figures on both sides and must not use scratch - and no kernel of the product build has a private
 segment (scratch; the stamped diagnostic build has some, on both sides alike)."""
 import argparse
 import concurrent.futures
@@ -24,7 +26,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "trex-gym_amd/csrc"
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=fast", "-fno-slp-vectorize", "--cuda-device-only", "-S"]
-UNITS = ["trex_step", "trex_step_act"]
+UNITS = ["trex_step", "trex_step_act", "dynamics", "batch_util"]   # those of them a side has
 BUILDS = [("product", []), ("stamped", ["-DTREX_STAMPS=1"])]
 FORMS = {0: "single", 1: "many", 2: "reset", 3: "debug", 4: "pair"}   # FORM of trex_step_variant_kernel (trex_step.hip)
 
@@ -40,7 +42,7 @@ def what(name):
         return ("reset", b[0], False, True, False)
     m = re.fullmatch(r"trex_step(_pair|_many)?(_warm|_ext|_sens|_act)?_kernel", base)
     if not m:
-        return base
+        return base + ("<%s>" % ", ".join(targs) if targs else "")
     form, feat = (m.group(1) or "_single")[1:], m.group(2)
     if feat is None:       # <RESET, DEBUG> on the single-env kernel
         return ("reset" if b[:1] == [True] else "debug" if b[1:2] == [True] else form, False, False, False, False)
@@ -61,6 +63,7 @@ def kernels(asm_path):
     start = {l.split(":")[0]: i for i, l in enumerate(lines) if l.startswith("_Z") and l.split(":")[0] in set(syms)}
     out = {}
     for sym, name in zip(syms, plain):
+        name = name.replace("(anonymous namespace)::", "")
         i = start[sym]
         j = next(k for k in range(i, len(lines)) if re.fullmatch(r"\.Lfunc_end\d+:", lines[k]))
         d0 = next(k for k in range(i, j) if lines[k].strip().startswith(".amdhsa_kernel "))
@@ -86,6 +89,8 @@ def kernels(asm_path):
 def compile_tree(csrc, dest):
     jobs = []
     for unit in UNITS:
+        if not os.path.exists(os.path.join(csrc, unit + ".hip")):
+            continue
         for tag, extra in BUILDS:
             out = os.path.join(dest, "%s.%s.s" % (unit, tag))
             jobs.append((out, [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + FLAGS + extra + ["-o", out, unit + ".hip"]))
@@ -104,6 +109,8 @@ def main():
     ap.add_argument("--parent", required=True, help="git revision to compare the working tree with")
     ap.add_argument("--out", help="write the report here as well")
     ap.add_argument("--keep", help="directory for the assembly files (kept; files already there are reused)")
+    ap.add_argument("--expect-different", action="append", default=[], metavar="NAME",
+                    help="a utility kernel that is rewritten on purpose: DIFFERENT is accepted for it, scratch is not (repeatable)")
     a = ap.parse_args()
     work = a.keep or tempfile.mkdtemp(prefix="step_kernels_")
     sides = {}
@@ -126,7 +133,10 @@ def main():
         old, new = {}, {}
         for unit in UNITS:
             for side, dst in (("parent", old), ("tree", new)):
-                ks = kernels(os.path.join(sides[side], "%s.%s.s" % (unit, tag)))
+                asm = os.path.join(sides[side], "%s.%s.s" % (unit, tag))
+                if not os.path.exists(asm):
+                    continue
+                ks = kernels(asm)
                 assert not set(ks) & set(dst), "a kernel in both translation units"
                 for k in ks.values():
                     k["unit"] = unit
@@ -136,21 +146,28 @@ def main():
         rep.append("== %s build%s: %d step kernels, %d utility kernels (parent: %d, %d)" % (
             tag, " (%s)" % " ".join(extra) if extra else "", sum(not isinstance(k, str) for k in new), sum(isinstance(k, str) for k in new),
             sum(not isinstance(k, str) for k in old), sum(isinstance(k, str) for k in old)))
-        rep.append("%-28s %-10s %5s %5s %8s %7s  %-13s parent kernel -> kernel" % ("what", "result", "VGPRs", "SGPRs", "scratch", "LDS", "unit"))
+        rep.append("%-34s %-10s %5s %5s %8s %7s  %-26s parent kernel -> kernel" % ("what", "result", "VGPRs", "SGPRs", "scratch", "LDS", "unit"))
         for k in steps + utils:
             o, n = old.get(k), new.get(k)
             if not o or not n:
                 res = "NO PARENT" if n else "MISSING"
             else:
-                same = o["text"] == n["text"] and o["desc"] == n["desc"] and o["unit"] == n["unit"] and all(o[f] == n[f] for f in ("vgprs", "sgprs", "scratch", "private", "lds"))
-                res = "identical" if same else "DIFFERENT"
+                same = o["text"] == n["text"] and o["desc"] == n["desc"] and all(o[f] == n[f] for f in ("vgprs", "sgprs", "scratch", "private", "lds"))
+                res = "identical" if same and (isinstance(k, str) or o["unit"] == n["unit"]) else "DIFFERENT"
             x = n or o
-            scratch_free = x["scratch"] == 0 and x["private"] == 0
-            bad += res != "identical" or (tag == "product" and not scratch_free)
-            rep.append("%-28s %-10s %5d %5d %8d %7d  %-13s %s -> %s" % (label(k), res, x["vgprs"], x["sgprs"], max(x["scratch"], x["private"]),
-                                                                   x["lds"], x["unit"], o["name"].split("(")[0] if o else "-", n["name"].split("(")[0] if n else "-"))
+            scratch_free = all(y["scratch"] == 0 and y["private"] == 0 for y in (o, n) if y)
+            expected = res == "DIFFERENT" and k in a.expect_different
+            bad += (res != "identical" and not expected) or ((tag == "product" or expected) and not scratch_free)
+            unit = x["unit"] if not o or not n or o["unit"] == n["unit"] else "%s -> %s" % (o["unit"], n["unit"])
+            line = "%-34s %-10s %5d %5d %8d %7d  %-26s %s -> %s" % (label(k), res, x["vgprs"], x["sgprs"], max(x["scratch"], x["private"]),
+                                                                  x["lds"], unit, o["name"].split("(")[0] if o else "-", n["name"].split("(")[0] if n else "-")
+            if res == "DIFFERENT":   # the figures of both sides
+                line += "   [parent: %d VGPRs, %d SGPRs, scratch %d, LDS %d%s]" % (o["vgprs"], o["sgprs"], max(o["scratch"], o["private"]), o["lds"],
+                                                                                 "; expected (--expect-different)" if expected else "")
+            rep.append(line)
         rep.append("")
-    rep.append("RESULT: %s" % ("every pair identical, no kernel of the product build with a private segment" if not bad else "%d kernel(s) differ, lack a partner or use scratch" % bad))
+    rep.append("RESULT: %s" % ("every pair identical%s, no kernel of the product build with a private segment" % (
+        " but the expected %s" % ", ".join(a.expect_different) if a.expect_different else "") if not bad else "%d kernel(s) differ, lack a partner or use scratch" % bad))
     text = "\n".join(rep) + "\n"
     sys.stdout.write(text)
     if a.out:

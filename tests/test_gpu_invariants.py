@@ -163,6 +163,33 @@ def test_link_transforms_match_reference_fk_and_oracle(model, oracle64):
             np.testing.assert_allclose(tm.quat_to_matrix(vis[e, k, 3:]), Rl @ tm.quat_to_matrix(quat), atol=2e-5)
 
 
+def test_head_position_matches_oracle_at_random_states(model, oracle64):
+    """head_position away from the reset pose: 257 envs - the kernel runs one env per thread in blocks of 256, so a second,
+    partial block - at the random states of the link-transform test above (base N(0,1) + [0,0,4], random unit quaternion,
+    joints uniform within their limits), every env against the f64 oracle at that test's tolerance for positions."""
+    from trex_gym.vec_env import TrexVecEnv
+    n = 257
+    rng = np.random.default_rng(5)
+    lo, hi = model["q_lower"][model["obs_order"]], model["q_upper"][model["obs_order"]]
+    st = np.zeros((n, 63), np.float32)
+    for e in range(n):
+        st[e, 0:3] = rng.normal(size=3) + [0, 0, 4]
+        q = rng.normal(size=4); st[e, 3:7] = q / np.linalg.norm(q)
+        st[e, 13:38] = rng.uniform(lo, hi)
+    v = TrexVecEnv(n, urdf_path=ASSET_URDF, device=DEV)
+    v.reset()
+    v.set_state(torch.tensor(st))
+    got = v.head_position().cpu().numpy()
+    assert got.shape == (n, 3)
+    s = oracle64.new_state()
+    want = np.empty((n, 3))
+    for e in range(n):
+        oracle64.set_state(s, st[e].astype(np.float64))
+        want[e] = oracle64.head_position(s)
+    print("head_position: largest error against the oracle %.3g" % np.abs(got - want).max())
+    np.testing.assert_allclose(got, want, atol=2e-5)
+
+
 def test_step_is_graph_capturable_and_stream_ordered():
     """The launch path allocates nothing and never syncs, so a step can be captured in a HIP graph on
     a side stream and replayed; replay == eager, bitwise."""

@@ -13,6 +13,7 @@
 // diagonal m |c - r|^2 + a.Ic a is then a sum of positive terms and not the difference of two m |r|^2 three metres out.
 #include <hip/hip_runtime.h>
 
+#include "chain_walk.h"
 #include "dynamics.h"
 
 namespace {
@@ -22,117 +23,10 @@ constexpr int MAXCH = TREX_MAXCH;
 constexpr int WAVES = TREX_DYN_WAVES;
 constexpr int BLOCK = 64 * WAVES;
 
-__device__ __forceinline__ void cross3(const float *a, const float *b, float *o) {
-  const float x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
-  o[0] = x; o[1] = y; o[2] = z;
-}
-__device__ __forceinline__ float dot3(const float *a, const float *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-__device__ __forceinline__ void matvec3(const float *m, const float *v, float *o) {
-  const float x = m[0] * v[0] + m[1] * v[1] + m[2] * v[2];
-  const float y = m[3] * v[0] + m[4] * v[1] + m[5] * v[2];
-  const float z = m[6] * v[0] + m[7] * v[1] + m[8] * v[2];
-  o[0] = x; o[1] = y; o[2] = z;
-}
-__device__ __forceinline__ void matmul3(const float *a, const float *b, float *o) {
-  float t[9];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) t[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
-#pragma unroll
-  for (int i = 0; i < 9; i++) o[i] = t[i];
-}
-// symmetric 3x3 (xx xy xz yy yz zz) times vector
-__device__ __forceinline__ void sym3_mul(const float *s, const float *v, float *o) {
-  const float x = s[0] * v[0] + s[1] * v[1] + s[2] * v[2];
-  const float y = s[1] * v[0] + s[3] * v[1] + s[4] * v[2];
-  const float z = s[2] * v[0] + s[4] * v[1] + s[5] * v[2];
-  o[0] = x; o[1] = y; o[2] = z;
-}
-__device__ __forceinline__ void quat_to_mat(const float *q, float *m) {
-  const float x = q[0], y = q[1], z = q[2], w = q[3];
-  m[0] = 1 - 2 * (y * y + z * z); m[1] = 2 * (x * y - z * w); m[2] = 2 * (x * z + y * w);
-  m[3] = 2 * (x * y + z * w); m[4] = 1 - 2 * (x * x + z * z); m[5] = 2 * (y * z - x * w);
-  m[6] = 2 * (x * z - y * w); m[7] = 2 * (y * z + x * w); m[8] = 1 - 2 * (x * x + y * y);
-}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
-}
-
-// What a lane knows of its body after walking the chain base -> body (at most MAXD hinges): pose, joint axis, and - VEL, ACC -
-// the classical velocity and acceleration of the body frame. All in world axes, positions relative to the base origin.
-struct Walk {
-  float R[9];    // world <- body
-  float r[3];    // body (= joint) origin
-  float a[3];    // joint axis
-  float w[3];    // angular velocity
-  float vo[3];   // velocity of the body origin
-  float al[3];   // angular acceleration
-  float ao[3];   // classical acceleration of the body origin, PLUS g z: gravity as the base's upward acceleration
-};
-
-// Level by level over depth: at level d every lane of depth >= d advances over its ancestor at that depth (itself at its
-// own). The lanes of one chain repeat their common ancestors' arithmetic in registers instead of waiting for them in LDS.
-template <bool VEL, bool ACC>
-__device__ __forceinline__ void walk_chain(const TrexDynArgs &A, const TrexDeviceModel *M, int env, int b, int D, Walk &k) {
-  const float *base = A.base + (size_t)env * 16;
-  const float quat[4] = {base[3], base[4], base[5], base[6]};
-  quat_to_mat(quat, k.R);
-  const float *acc = ACC && A.accel ? A.accel + (size_t)env * D : nullptr;
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    k.r[c] = 0.f; k.a[c] = 0.f;
-    k.vo[c] = VEL ? base[7 + c] : 0.f; k.w[c] = VEL ? base[10 + c] : 0.f;
-    k.ao[c] = acc ? acc[c] : 0.f; k.al[c] = acc ? acc[3 + c] : 0.f;
-  }
-  if (ACC) k.ao[2] += M->prm[TP_GRAVITY];
-  const int maxdepth = M->maxdepth;
-  for (int d = 1; d <= maxdepth; d++) {
-    const int i = M->anc[d - 1][b];
-    if (i < 0) continue;
-    const float ax[3] = {M->axis[0][i], M->axis[1][i], M->axis[2][i]}, jp[3] = {M->jpos[0][i], M->jpos[1][i], M->jpos[2][i]};
-    float jr[9], rq[9], t[9], dw[3];
-#pragma unroll
-    for (int c = 0; c < 9; c++) jr[c] = M->jrot[c][i];
-    matvec3(k.R, jp, dw);   // parent origin -> this origin, a point of the PARENT body
-    if (VEL) {
-      float wxd[3];
-      cross3(k.w, dw, wxd);
-      if (ACC) {
-        float axd[3], wwd[3];
-        cross3(k.al, dw, axd); cross3(k.w, wxd, wwd);
-#pragma unroll
-        for (int c = 0; c < 3; c++) k.ao[c] += axd[c] + wwd[c];
-      }
-#pragma unroll
-      for (int c = 0; c < 3; c++) k.vo[c] += wxd[c];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; c++) k.r[c] += dw[c];
-    const float q = A.q[(size_t)env * TL + i];
-    const float co = cosf(q), s = sinf(q), tt = 1.f - co;
-    rq[0] = tt * ax[0] * ax[0] + co;        rq[1] = tt * ax[0] * ax[1] - s * ax[2]; rq[2] = tt * ax[0] * ax[2] + s * ax[1];
-    rq[3] = tt * ax[0] * ax[1] + s * ax[2]; rq[4] = tt * ax[1] * ax[1] + co;        rq[5] = tt * ax[1] * ax[2] - s * ax[0];
-    rq[6] = tt * ax[0] * ax[2] - s * ax[1]; rq[7] = tt * ax[1] * ax[2] + s * ax[0]; rq[8] = tt * ax[2] * ax[2] + co;
-    matmul3(k.R, jr, t);
-    matmul3(t, rq, k.R);
-    matvec3(k.R, ax, k.a);
-    if (VEL) {
-      const float qd = A.qd[(size_t)env * TL + i];
-      if (ACC) {
-        // d/dt (a qd) = a qdd + (w_parent x a) qd
-        const float qdd = acc ? acc[6 + M->obs_slot[i]] : 0.f;
-        float wxa[3];
-        cross3(k.w, k.a, wxa);
-#pragma unroll
-        for (int c = 0; c < 3; c++) k.al[c] += k.a[c] * qdd + wxa[c] * qd;
-      }
-#pragma unroll
-      for (int c = 0; c < 3; c++) k.w[c] += k.a[c] * qd;
-    }
-  }
 }
 
 // mass, COM offset from the body origin and rotational inertia about the COM (world axes) of body b, the env's mass scale in
@@ -189,7 +83,7 @@ __global__ __launch_bounds__(BLOCK) void trex_dynamics_kernel(TrexDynArgs A) {
     // ---- RNEA. Outward (in registers): classical velocity and acceleration of every body frame; the force at the COM
     // and the moment about the body's joint origin that this motion needs.
     Walk k;
-    walk_chain<true, true>(A, M, e, b, D, k);
+    walk_chain<true, true>(M, A.base, A.q, A.qd, A.accel, e, b, D, k);
     Inertia I;
     body_inertia(A, M, e, b, k.R, I);
     float F[3], N[3];
@@ -250,7 +144,7 @@ __global__ __launch_bounds__(BLOCK) void trex_dynamics_kernel(TrexDynArgs A) {
     // level (parallel-axis sums of positive terms); then every joint lane walks its ancestor chain: column j of M is the
     // momentum of subtree j turning about joint j, row i its projection on joint i's motion.
     Walk k;
-    walk_chain<false, false>(A, M, e, b, D, k);
+    walk_chain<false, false>(M, A.base, A.q, A.qd, A.accel, e, b, D, k);
     Inertia I;
     body_inertia(A, M, e, b, k.R, I);
     float cm = I.m, cc[3], ci[6];
@@ -360,7 +254,7 @@ __global__ __launch_bounds__(BLOCK) void trex_dynamics_kernel(TrexDynArgs A) {
 
   if constexpr (Q == TREX_DYN_JACOBIAN) {
     Walk k;
-    walk_chain<false, false>(A, M, e, b, D, k);
+    walk_chain<false, false>(M, A.base, A.q, A.qd, A.accel, e, b, D, k);
     const int B = A.jac_body;
     if (is_body && b == B) {
       const float pt[3] = {A.jac_point[0], A.jac_point[1], A.jac_point[2]};
@@ -399,7 +293,7 @@ __global__ __launch_bounds__(BLOCK) void trex_dynamics_kernel(TrexDynArgs A) {
 
   if constexpr (Q == TREX_DYN_CENTROIDAL) {
     Walk k;
-    walk_chain<true, false>(A, M, e, b, D, k);
+    walk_chain<true, false>(M, A.base, A.q, A.qd, A.accel, e, b, D, k);
     Inertia I;
     body_inertia(A, M, e, b, k.R, I);
     const float m = is_body ? I.m : 0.f;

@@ -4,6 +4,7 @@
 // nothing but the output images.
 #include <hip/hip_runtime.h>
 
+#include "device_math.h"
 #include "render.h"
 
 namespace {
@@ -26,13 +27,6 @@ __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlan
 __device__ __forceinline__ unsigned char to_u8(float c) {
   c = fminf(fmaxf(c, 0.f), 1.f);
   return (unsigned char)(int)floorf(c * 255.f + 0.5f);
-}
-
-__device__ __forceinline__ void quat_to_mat(const float *q, float *m) {
-  const float x = q[0], y = q[1], z = q[2], w = q[3];
-  m[0] = 1 - 2 * (y * y + z * z); m[1] = 2 * (x * y - z * w); m[2] = 2 * (x * z + y * w);
-  m[3] = 2 * (x * y + z * w); m[4] = 1 - 2 * (x * x + z * z); m[5] = 2 * (y * z - x * w);
-  m[6] = 2 * (x * z - y * w); m[7] = 2 * (y * z + x * w); m[8] = 1 - 2 * (x * x + y * y);
 }
 
 }  // namespace

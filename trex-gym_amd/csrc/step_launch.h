@@ -1,5 +1,6 @@
-// The boundary between capi.cpp and the kernels of trex_step.hip / trex_step_act.hip: the step launch's argument struct, the one
-// way to ask for a step launch, and the prototype of every launcher - written here once, for the definition and the call alike.
+// The boundary between capi.cpp and the kernels of trex_step.hip / trex_step_act.hip (the step launches) and batch_util.hip (the
+// utility kernels): the step launch's argument struct, the one way to ask for a step launch, and the prototype of every launcher -
+// written here once, for the definition and the call alike.
 // Shared by the translation units of libtrex_hip.so (not installed, not part of the C-ABI).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -68,7 +69,7 @@ inline unsigned trex_step_features(const TrexStepArgs &a) {
 // launch shape of a launch of this kind for n envs with these features: what it is launched with, and what trex_batch_launch_info
 // reports of the step launch
 struct TrexStepShape { int envs_per_workgroup, grid, block, lds_bytes; };
-// a step kernel as the variant table (trex_step.hip) hands it out
+// a step kernel as the variant table (trex_step_body.h) hands it out
 typedef void (*TrexStepKernel)(TrexStepArgs);
 
 extern "C" {

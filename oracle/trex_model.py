@@ -320,6 +320,8 @@ def compile_model(urdf_path, collisions_dir=None, start_configuration=None):
     m["hull_group_start"] = np.array(hull_groups, np.int32)   # one group per original convex hull
     m["hull_radius"] = np.zeros(len(m["hull_xyz"]))           # > 0 only for fitted sphere / capsule ends
     m["sphere_center"], m["sphere_radius"] = sphere_c, sphere_r
+    if head_body < 0:   # generic URDF without the head link: the reward point is the base COM (model.cpp does the same)
+        head_body, head_point = 0, m["com"][0].copy()
     m["head_body"], m["head_point"] = head_body, head_point
 
     # observation / action order: revolute joint names sorted (trex_robot.py:311-314)

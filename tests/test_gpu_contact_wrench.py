@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import ASSET_URDF
+from parity_helpers import oracle_wrench
 from test_gpu_external_wrench import landing_states, make_vec, random_actions
 from test_gpu_parity import GOLD
 
@@ -32,35 +33,6 @@ def sensing(n, **kw):
 def weight(model, mass_scale=None, g=9.81):
     m = model["mass"] if mass_scale is None else model["mass"] * mass_scale
     return float(m.sum()) * g
-
-
-def oracle_wrench(orc, model, state, action, mass_scale=None, friction=None):
-    """One env-step restated on the oracle: the clipped action as the joint targets, motors on, `substeps` substeps; per
-    substep the contact points (body, lambda = (normal, x, y) - the oracle's row order - and world point) with the body COMs
-    of the pose the rows were built at (body_poses BEFORE the substep + R com). Returns [NB, 6] and the touched bodies."""
-    obs_order = model["obs_order"]
-    lo, hi = model["q_lower"][obs_order], model["q_upper"][obs_order]
-    s = orc.new_state()
-    orc.set_state(s, state.astype(np.float64))
-    if mass_scale is not None or friction is not None:
-        orc.set_domain(s, None if mass_scale is None else mass_scale.astype(np.float64), friction)
-    orc.set_motors_on(s, 1)
-    target = np.clip(action.astype(np.float64), lo, hi)
-    n_sub = int(orc.params["substeps"])
-    dt = orc.params["dt"]
-    W = np.zeros((NB, 6))
-    touched = set()
-    for _ in range(n_sub):
-        pos, rot = orc.body_poses(s)
-        com = pos + np.einsum("bij,bj->bi", rot, model["com"])
-        orc.substep(s, target)
-        body, lam, pt, _ = orc.contacts(s)
-        for b, l, p in zip(body, lam, pt):
-            f = np.array([l[1], l[2], l[0]])
-            W[b, :3] += f
-            W[b, 3:] += np.cross(p - com[b], f)
-            touched.add(int(b))
-    return W / (n_sub * dt), touched
 
 
 # ---------------------------------------------------------------- 1. the oracle

@@ -43,28 +43,7 @@ def make_vec(n, **kw):
     return TrexVecEnv(n, urdf_path=ASSET_URDF, device=DEV, **kw)
 
 
-def assert_step_close(g_obs, o_obs, g_rew=None, o_rew=None, what="", q_atol=1e-4, loosen=1.0):
-    J = 25
-    assert np.isfinite(g_obs).all(), what
-    np.testing.assert_allclose(g_obs[:J], o_obs[:J], atol=q_atol, rtol=0, err_msg=what + " q")
-    np.testing.assert_allclose(g_obs[J:2 * J], o_obs[J:2 * J], atol=loosen * 3e-3 * max(1.0, np.abs(o_obs[J:2 * J]).max()),
-                               rtol=0, err_msg=what + " qd")
-    # motor torque: a joint saturated in the oracle (3e5 N m, trex_robot.py:260) must be saturated with the same sign;
-    # the others are compared on the scale of the largest UNsaturated torque (a saturated neighbour must not hide
-    # an error of hundreds of N m)
-    gt, ot = g_obs[2 * J:], o_obs[2 * J:]
-    sat = np.abs(ot) >= 0.999 * 3.0e5
-    assert np.all(np.abs(gt[sat]) >= 0.999 * 3.0e5) and np.all(np.sign(gt[sat]) == np.sign(ot[sat])), what + " saturated tau"
-    if (~sat).any():
-        tscale = np.abs(ot[~sat]).max()
-        np.testing.assert_allclose(gt[~sat], ot[~sat], atol=3e-3 * tscale + 1.0, rtol=0, err_msg=what + " tau")
-    if g_rew is not None:
-        # reward = -lift - drift - w_e sum|qd tau| (trex_env.py:186-192): 2e-3 relative on the whole, plus what the
-        # stated qd / tau tolerances allow in the energy term (w_e = 0.005, the default of every test here)
-        qd_tol = 3e-3 * max(1.0, np.abs(o_obs[J:2 * J]).max())
-        tau_tol = np.where(sat, 1e-3 * 3.0e5, 3e-3 * (np.abs(ot[~sat]).max() if (~sat).any() else 0.0) + 1.0)
-        energy_tol = 0.005 * np.sum(np.abs(o_obs[J:2 * J]) * tau_tol + np.abs(ot) * qd_tol)
-        assert abs(g_rew - o_rew) <= 2e-3 * abs(o_rew) + 1e-3 + 0.1 * energy_tol, (what, g_rew, o_rew)
+from parity_helpers import assert_step_close  # noqa: E402,F401  (moved there; other test files import it from here)
 
 
 def test_native_library_is_the_one_loaded(capi):

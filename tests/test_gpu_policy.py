@@ -10,38 +10,10 @@ import pytest
 import torch
 
 from oracle import ppo_oracle as P
+from trainer_cases import _grads_to_flat, _theta_to_params
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def _theta_to_params(kern, theta):
-    """flat [in, out] vector -> the oracle's dict in nn.Sequential naming with [out, in] weights"""
-    th = theta.detach().cpu().double().numpy()
-    out = {}
-    for name, (off, shape) in kern.layout.items():
-        v = th[off:off + math.prod(shape)].reshape(shape)
-        if name == "logstd":
-            out["logstd"] = v
-            continue
-        net, what = name.split(".")
-        k = {"1": 0, "2": 2, "3": 4}[what[1]]
-        out["%s.%d.%s" % (net, k, "weight" if what[0] == "W" else "bias")] = v.T.copy() if what[0] == "W" else v
-    return out
-
-
-def _grads_to_flat(kern, grads):
-    flat = np.zeros(kern.param_count)
-    for name, (off, shape) in kern.layout.items():
-        if name == "logstd":
-            g = grads["logstd"]
-        else:
-            net, what = name.split(".")
-            k = {"1": 0, "2": 2, "3": 4}[what[1]]
-            g = grads["%s.%d.%s" % (net, k, "weight" if what[0] == "W" else "bias")]
-            g = g.T if what[0] == "W" else g
-        flat[off:off + math.prod(shape)] = np.asarray(g).reshape(-1)
-    return flat
 
 
 @pytest.mark.parametrize("n", [4096, 77])

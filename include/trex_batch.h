@@ -396,6 +396,21 @@ int trex_batch_jacobian(TrexBatch *batch, int link, const double local_xyz[3], f
  * (the env's mass scale included), [15] 0. World axes, SI units. */
 int trex_batch_centroidal(TrexBatch *batch, float *out_dev, void *stream);
 
+/* ---- the other direction (articulated-body algorithm, O(bodies) per env and right-hand side). Both calls use the conventions
+ *      above - D, the order and the axes of the generalised velocity, classical accelerations, forces as duals, the env's mass
+ *      scale, RIGID-BODY terms only - and behave like the four queries above: asynchronous on `stream`, every buffer validated,
+ *      nothing allocated or waited for, nothing written but the output, plain launches from the second call on. The output may
+ *      alias the input EXACTLY (in place); any other overlap is the caller's error and is not detected. */
+
+/* accel_dev [N, D] = M(q)^-1 (force - h(q, qd)) at every env's current state: the exact inverse of trex_batch_inverse_dynamics.
+ * force_dev [N, D] (NULL = zeros: free motion under gravity and the velocity-product forces). */
+int trex_batch_forward_dynamics(TrexBatch *batch, const float *force_dev, float *accel_dev, void *stream);
+
+/* x_dev [N, K, D] = M(q)^-1 applied to K right-hand sides per env, rhs_dev [N, K, D] (force-like rows; the layout of
+ * trex_batch_jacobian's output, so solve_mass(J) is (M^-1 J^T)^T with K = 6). rhs_dev NULL: the identity, K must be D,
+ * x = M^-1 itself. 1 <= K <= 64, otherwise TREX_E_INVALID. No gravity and no velocity terms enter: it depends on q alone. */
+int trex_batch_solve_mass(TrexBatch *batch, const float *rhs_dev, int num_rhs, float *x_dev, void *stream);
+
 /* diagnostics of the last substep: contact count per env [N] i32 (nullable), summed normal
  * impulse per env [N] f32 (nullable). */
 int trex_batch_contact_stats(TrexBatch *batch, int32_t *count_dev, float *normal_impulse_dev, void *stream);

@@ -926,6 +926,38 @@ int trex_batch_centroidal(TrexBatch *b, float *out_dev, void *stream) {
   return TREX_OK;
 }
 
+int trex_batch_forward_dynamics(TrexBatch *b, const float *force_dev, float *accel_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!accel_dev) return fail(TREX_E_INVALID, "trex_batch_forward_dynamics: accel is null");
+  DeviceGuard guard(b->device);
+  const size_t bytes = (size_t)b->n * (6 + b->nj) * sizeof(float);
+  BUF_TRY(force_dev, bytes, "trex_batch_forward_dynamics: force");
+  BUF_TRY(accel_dev, bytes, "trex_batch_forward_dynamics: accel");
+  TrexDynArgs a = dyn_args(b, accel_dev);
+  a.rhs = force_dev;
+  a.num_rhs = 1;
+  HIP_TRY(trex_launch_dynamics(a, TREX_DYN_FORWARD_DYNAMICS, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+int trex_batch_solve_mass(TrexBatch *b, const float *rhs_dev, int num_rhs, float *x_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!x_dev) return fail(TREX_E_INVALID, "trex_batch_solve_mass: x is null");
+  if (num_rhs < 1 || num_rhs > TREX_DYN_MAX_RHS)
+    return fail(TREX_E_INVALID, "trex_batch_solve_mass: num_rhs " + std::to_string(num_rhs) + " outside 1.." + std::to_string(TREX_DYN_MAX_RHS));
+  if (!rhs_dev && num_rhs != 6 + b->nj)
+    return fail(TREX_E_INVALID, "trex_batch_solve_mass: a null rhs is the identity, num_rhs must be " + std::to_string(6 + b->nj));
+  DeviceGuard guard(b->device);
+  const size_t bytes = (size_t)b->n * num_rhs * (6 + b->nj) * sizeof(float);
+  BUF_TRY(rhs_dev, bytes, "trex_batch_solve_mass: rhs");
+  BUF_TRY(x_dev, bytes, "trex_batch_solve_mass: x");
+  TrexDynArgs a = dyn_args(b, x_dev);
+  a.rhs = rhs_dev;
+  a.num_rhs = num_rhs;
+  HIP_TRY(trex_launch_dynamics(a, TREX_DYN_SOLVE_MASS, (hipStream_t)stream));
+  return TREX_OK;
+}
+
 int trex_batch_contact_stats(TrexBatch *b, int32_t *count_dev, float *normal_impulse_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
   DeviceGuard guard(b->device);

@@ -1,5 +1,5 @@
 // Dynamics queries on the batch state: inverse dynamics (RNEA), joint-space mass matrix (CRBA), point Jacobian of a link,
-// centroidal quantities. Read-only: nothing here writes the state. gfx950, one env per 64-lane wavefront, one body per lane,
+// centroidal quantities, forward dynamics and M^-1 x (ABA). Read-only: nothing here writes the state. gfx950, one env per 64-lane wavefront, one body per lane,
 // four envs per workgroup so that the four outputs lie back to back and leave the chip as 16-byte stores.
 //
 // Conventions (include/trex_batch.h, "dynamics queries"): generalised velocity = base linear v(3), base angular w(3) - world
@@ -68,13 +68,15 @@ __global__ __launch_bounds__(BLOCK) void trex_dynamics_kernel(TrexDynArgs A) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int env0 = blockIdx.x * WAVES, env = env0 + wave;
   const int nb = A.nb, D = 6 + nb - 1;
-  const int per_env = trex_dyn_out_floats(Q, D);
+  // (the two ABA queries carry one right-hand side in each half of the wave: body = lane & 31 there)
+  constexpr bool ABA = Q == TREX_DYN_FORWARD_DYNAMICS || Q == TREX_DYN_SOLVE_MASS;
+  const int per_env = trex_dyn_out_floats(Q, D, Q == TREX_DYN_SOLVE_MASS ? A.num_rhs : 1);
   const bool live = env < A.n_envs;                      // (a wave past the batch's end still meets the barriers)
-  const bool is_body = live && lane < nb;
-  const int b = is_body ? lane : 0;
+  const bool is_body = live && (ABA ? lane & 31 : lane) < nb;
+  const int b = is_body ? (ABA ? lane & 31 : lane) : 0;
   const int e = live ? env : 0;
-  float *rec = lds + wave * TREX_DYN_BODY_FLOATS;        // [32][16] this env's per-body records
-  float *stage = lds + WAVES * TREX_DYN_BODY_FLOATS + wave * per_env;
+  float *rec = lds + wave * trex_dyn_body_floats(Q);     // [32][16] this env's per-body records (ABA: [32][37])
+  float *stage = lds + WAVES * trex_dyn_body_floats(Q) + wave * per_env;
   const int depth = is_body ? M->depth[b] : -1;
   const int maxdepth = M->maxdepth;
   const int slot = is_body && b >= 1 ? 6 + M->obs_slot[b] : -1;   // this body's joint among the D velocities
@@ -326,9 +328,230 @@ __global__ __launch_bounds__(BLOCK) void trex_dynamics_kernel(TrexDynArgs A) {
     }
   }
 
+  if constexpr (ABA) {
+    // ---- ABA in classical accelerations. The acceleration of every body frame is split a = a0 + da: a0 the motion with zero
+    // base and joint accelerations (the velocity-product terms, and gravity as the base's upward acceleration - the outward
+    // pass of RNEA above), da what the unknown accelerations add. da is LINEAR in them and moves from point to point like a
+    // velocity (da_P = da_Q + dal x (P - Q)), so the three passes run on da with the body wrenches of a0 as the bias force
+    // (forward dynamics) or none (solve_mass), and the base's da IS its classical acceleration: nothing to convert.
+    // Every body's articulated inertia, bias wrench and da are about ITS OWN joint origin; a child's are shifted to the
+    // parent's origin by the short lever between the two. A wrench is (moment n, force f), a motion (angular al, linear a):
+    // n = IA al + IH a, f = IH^T al + IM a; a rigid body of mass m, COM offset c: IM = m 1, IH = m [c]x, IA = Ic - m [c]x[c]x.
+    constexpr bool FD = Q == TREX_DYN_FORWARD_DYNAMICS;
+    constexpr int RS = TREX_DYN_ABA_STRIDE, R_ORG = 21, R_SLOT = 24;
+    const int half = lane >> 5;
+    const int K = FD ? 1 : A.num_rhs;
+    const float *none = nullptr;
+    Walk k;
+    walk_chain<FD, FD>(M, A.base, A.q, A.qd, none, e, b, D, k);
+    Inertia I;
+    body_inertia(A, M, e, b, k.R, I);
+    float F[3] = {0.f, 0.f, 0.f}, N[3] = {0.f, 0.f, 0.f};      // forward dynamics: the wrench of a0 on this body (as RNEA's)
+    if constexpr (FD) {
+      float t0[3], t1[3], ac[3], Iw[3], Ial[3], wIw[3], cxf[3];
+      cross3(k.al, I.cb, t0);
+      cross3(k.w, I.cb, t1); cross3(k.w, t1, t1);
+#pragma unroll
+      for (int c = 0; c < 3; c++) ac[c] = k.ao[c] + t0[c] + t1[c];
+#pragma unroll
+      for (int c = 0; c < 3; c++) F[c] = I.m * ac[c];
+      sym3_mul(I.Ic, k.w, Iw); sym3_mul(I.Ic, k.al, Ial);
+      cross3(k.w, Iw, wIw); cross3(I.cb, F, cxf);
+#pragma unroll
+      for (int c = 0; c < 3; c++) N[c] = Ial[c] + wIw[c] + cxf[c];
+    }
+    // ---- pass 1, inward: articulated inertias, U = I^A S, 1 / d. Both halves compute, half 0 writes.
+    float IA[6], IH[9], IM[6] = {I.m, 0.f, 0.f, I.m, 0.f, I.m};
+    {
+      const float *c = I.cb, m = I.m, cc = dot3(c, c);
+      IA[0] = I.Ic[0] + m * (cc - c[0] * c[0]); IA[1] = I.Ic[1] - m * c[0] * c[1]; IA[2] = I.Ic[2] - m * c[0] * c[2];
+      IA[3] = I.Ic[3] + m * (cc - c[1] * c[1]); IA[4] = I.Ic[4] - m * c[1] * c[2]; IA[5] = I.Ic[5] + m * (cc - c[2] * c[2]);
+      IH[0] = 0.f; IH[1] = -m * c[2]; IH[2] = m * c[1];
+      IH[3] = m * c[2]; IH[4] = 0.f; IH[5] = -m * c[0];
+      IH[6] = -m * c[1]; IH[7] = m * c[0]; IH[8] = 0.f;
+    }
+    if (is_body && half == 0) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) rec[RS * b + R_ORG + c] = k.r[c];
+    }
+    __syncthreads();
+    float lev[3];                                               // parent origin -> this origin
+    {
+      const float *o = rec + RS * (b >= 1 ? M->parent[b] : 0) + R_ORG;
+#pragma unroll
+      for (int c = 0; c < 3; c++) lev[c] = k.r[c] - o[c];
+    }
+    float Un[3] = {0.f, 0.f, 0.f}, Uf[3] = {0.f, 0.f, 0.f}, dinv = 0.f;
+    for (int d = maxdepth; d >= 0; d--) {
+      if (depth == d) {
+        for (int kc = 0; kc < MAXCH; kc++) {
+          const int ch = M->child[kc][b];
+          if (ch < 0) break;
+          const float *o = rec + RS * ch;
+          const float l[3] = {o[R_ORG] - k.r[0], o[R_ORG + 1] - k.r[1], o[R_ORG + 2] - k.r[2]};
+          float cH[9], Hp[9], x1[9], x2[9];
+#pragma unroll
+          for (int c = 0; c < 9; c++) cH[c] = o[6 + c];
+          const float cM[6] = {o[15], o[16], o[17], o[18], o[19], o[20]};
+          const float Mf[9] = {cM[0], cM[1], cM[2], cM[1], cM[3], cM[4], cM[2], cM[4], cM[5]};
+          // H' = H + [l]x M;  A' = A + [l]x H^T + H' [l]x^T
+#pragma unroll
+          for (int j = 0; j < 3; j++) {
+            const float col[3] = {Mf[j], Mf[3 + j], Mf[6 + j]};
+            float t[3];
+            cross3(l, col, t);
+#pragma unroll
+            for (int i = 0; i < 3; i++) Hp[3 * i + j] = cH[3 * i + j] + t[i];
+          }
+#pragma unroll
+          for (int r = 0; r < 3; r++) { cross3(l, cH + 3 * r, x1 + 3 * r); cross3(l, Hp + 3 * r, x2 + 3 * r); }
+          const int ia[6] = {0, 0, 0, 1, 1, 2}, ib[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+          for (int c = 0; c < 6; c++) {
+            IA[c] += o[c] + x1[3 * ib[c] + ia[c]] + x2[3 * ia[c] + ib[c]];
+            IM[c] += cM[c];
+          }
+#pragma unroll
+          for (int c = 0; c < 9; c++) IH[c] += Hp[c];
+        }
+        float *o = rec + RS * b;
+        if (b >= 1) {
+          // the joint turns about k.a through the body origin: S = (a, 0)
+          sym3_mul(IA, k.a, Un);
+#pragma unroll
+          for (int j = 0; j < 3; j++) Uf[j] = IH[j] * k.a[0] + IH[3 + j] * k.a[1] + IH[6 + j] * k.a[2];
+          dinv = 1.0f / dot3(k.a, Un);
+          if (half == 0) {
+            const int ia[6] = {0, 0, 0, 1, 1, 2}, ib[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+            for (int c = 0; c < 6; c++) {
+              o[c] = IA[c] - Un[ia[c]] * Un[ib[c]] * dinv;
+              o[15 + c] = IM[c] - Uf[ia[c]] * Uf[ib[c]] * dinv;
+            }
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+#pragma unroll
+              for (int j = 0; j < 3; j++) o[6 + 3 * i + j] = IH[3 * i + j] - Un[i] * Uf[j] * dinv;
+          }
+        } else if (half == 0) {
+          // the floating base: Cholesky factor of its 6 x 6 articulated inertia [[IA, IH], [IH^T, IM]], lower triangle row by
+          // row, the diagonal as its reciprocal
+          float G[6][6], L[6][6];
+          const float Af[9] = {IA[0], IA[1], IA[2], IA[1], IA[3], IA[4], IA[2], IA[4], IA[5]};
+          const float Mf[9] = {IM[0], IM[1], IM[2], IM[1], IM[3], IM[4], IM[2], IM[4], IM[5]};
+#pragma unroll
+          for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+              G[i][j] = Af[3 * i + j]; G[3 + i][3 + j] = Mf[3 * i + j];
+              G[i][3 + j] = IH[3 * i + j]; G[3 + j][i] = IH[3 * i + j];
+            }
+#pragma unroll
+          for (int j = 0; j < 6; j++) {
+            float sd = G[j][j];
+#pragma unroll
+            for (int x = 0; x < j; x++) sd -= L[j][x] * L[j][x];
+            const float inv = 1.0f / sqrtf(sd);
+            L[j][j] = inv;
+#pragma unroll
+            for (int i = j + 1; i < 6; i++) {
+              float sv = G[i][j];
+#pragma unroll
+              for (int x = 0; x < j; x++) sv -= L[i][x] * L[j][x];
+              L[i][j] = sv * inv;
+            }
+          }
+#pragma unroll
+          for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int j = 0; j <= i; j++) o[i * (i + 1) / 2 + j] = L[i][j];
+        }
+      }
+      __syncthreads();
+    }
+    // ---- passes 2 and 3, once per right-hand side: two at a time, one in each half of the wave
+    float *my = rec + RS * b + R_SLOT + 6 * half;
+    for (int k0 = 0; k0 < K; k0 += 2) {
+      const int col = k0 + half;
+      const bool act = is_body && col < K;
+      const float *row = nullptr;
+      if constexpr (FD) row = A.rhs ? A.rhs + (size_t)e * D : nullptr;
+      else row = A.rhs ? A.rhs + ((size_t)e * K + (act ? col : 0)) * D : nullptr;
+      float tau = 0.f, bf[3] = {0.f, 0.f, 0.f}, bn[3] = {0.f, 0.f, 0.f};     // this body's share of the right-hand side
+      if (act) {
+        if (b >= 1) {
+          tau = row ? row[slot] : !FD && col == slot ? 1.f : 0.f;
+        } else {
+#pragma unroll
+          for (int c = 0; c < 3; c++) {
+            bf[c] = row ? row[c] : !FD && col == c ? 1.f : 0.f;
+            bn[c] = row ? row[3 + c] : !FD && col == 3 + c ? 1.f : 0.f;
+          }
+        }
+      }
+      // pass 2, inward: bias wrench of the subtree with its joints free, p^a = p^A + U (tau - S . p^A) / d
+      float pn[3] = {N[0], N[1], N[2]}, pf[3] = {F[0], F[1], F[2]}, u = 0.f;
+      for (int d = maxdepth; d >= 0; d--) {
+        if (depth == d && act) {
+          for (int kc = 0; kc < MAXCH; kc++) {
+            const int ch = M->child[kc][b];
+            if (ch < 0) break;
+            const float *o = rec + RS * ch;
+            const float *w = o + R_SLOT + 6 * half;
+            const float l[3] = {o[R_ORG] - k.r[0], o[R_ORG + 1] - k.r[1], o[R_ORG + 2] - k.r[2]}, fc[3] = {w[3], w[4], w[5]};
+            float lxf[3];
+            cross3(l, fc, lxf);
+#pragma unroll
+            for (int c = 0; c < 3; c++) { pf[c] += fc[c]; pn[c] += w[c] + lxf[c]; }
+          }
+          if (b >= 1) {
+            u = tau - dot3(k.a, pn);
+            const float ud = u * dinv;
+#pragma unroll
+            for (int c = 0; c < 3; c++) { my[c] = pn[c] + Un[c] * ud; my[3 + c] = pf[c] + Uf[c] * ud; }
+          } else {
+            // the base: I^A_0 da_0 = (base torque, base force) - p^A_0 by the Cholesky factor
+            const float *Lr = rec;
+            float y[6] = {bn[0] - pn[0], bn[1] - pn[1], bn[2] - pn[2], bf[0] - pf[0], bf[1] - pf[1], bf[2] - pf[2]};
+#pragma unroll
+            for (int i = 0; i < 6; i++) {
+#pragma unroll
+              for (int x = 0; x < i; x++) y[i] -= Lr[i * (i + 1) / 2 + x] * y[x];
+              y[i] *= Lr[i * (i + 1) / 2 + i];
+            }
+#pragma unroll
+            for (int i = 5; i >= 0; i--) {
+#pragma unroll
+              for (int x = i + 1; x < 6; x++) y[i] -= Lr[x * (x + 1) / 2 + i] * y[x];
+              y[i] *= Lr[i * (i + 1) / 2 + i];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; c++) { my[c] = y[c]; my[3 + c] = y[3 + c]; stage[col * D + c] = y[3 + c]; stage[col * D + 3 + c] = y[c]; }
+          }
+        }
+        __syncthreads();
+      }
+      // pass 3, outward: da of the parent moved to this origin, qdd = (u - U . da) / d, da += S qdd
+      for (int d = 1; d <= maxdepth; d++) {
+        if (depth == d && act) {
+          const float *w = rec + RS * M->parent[b] + R_SLOT + 6 * half;
+          float al[3] = {w[0], w[1], w[2]}, ap[3];
+          cross3(al, lev, ap);
+#pragma unroll
+          for (int c = 0; c < 3; c++) ap[c] += w[3 + c];
+          const float qdd = (u - dot3(Un, al) - dot3(Uf, ap)) * dinv;
+#pragma unroll
+          for (int c = 0; c < 3; c++) { my[c] = al[c] + k.a[c] * qdd; my[3 + c] = ap[c]; }
+          stage[col * D + slot] = qdd;
+        }
+        __syncthreads();
+      }
+    }
+  }
+
   __syncthreads();
   const int envs_here = min(WAVES, A.n_envs - env0);
-  block_store(A.out + (size_t)env0 * per_env, lds + WAVES * TREX_DYN_BODY_FLOATS, envs_here * per_env);
+  block_store(A.out + (size_t)env0 * per_env, lds + WAVES * trex_dyn_body_floats(Q), envs_here * per_env);
 }
 
 }  // namespace
@@ -337,12 +560,15 @@ extern "C" hipError_t trex_launch_dynamics(const TrexDynArgs &args, int query, h
   if (args.n_envs <= 0 || args.nb < 1 || args.nb > TL) return hipErrorInvalidValue;
   const int D = 6 + args.nb - 1;
   const dim3 grid((args.n_envs + WAVES - 1) / WAVES), block(BLOCK);
-  const size_t lds = (size_t)trex_dyn_lds_bytes(query, D);
+  if (query == TREX_DYN_SOLVE_MASS && (args.num_rhs < 1 || args.num_rhs > TREX_DYN_MAX_RHS)) return hipErrorInvalidValue;
+  const size_t lds = (size_t)trex_dyn_lds_bytes(query, D, args.num_rhs);
   switch (query) {
     case TREX_DYN_INVERSE_DYNAMICS: hipLaunchKernelGGL(trex_dynamics_kernel<TREX_DYN_INVERSE_DYNAMICS>, grid, block, lds, stream, args); break;
     case TREX_DYN_MASS_MATRIX: hipLaunchKernelGGL(trex_dynamics_kernel<TREX_DYN_MASS_MATRIX>, grid, block, lds, stream, args); break;
     case TREX_DYN_JACOBIAN: hipLaunchKernelGGL(trex_dynamics_kernel<TREX_DYN_JACOBIAN>, grid, block, lds, stream, args); break;
     case TREX_DYN_CENTROIDAL: hipLaunchKernelGGL(trex_dynamics_kernel<TREX_DYN_CENTROIDAL>, grid, block, lds, stream, args); break;
+    case TREX_DYN_FORWARD_DYNAMICS: hipLaunchKernelGGL(trex_dynamics_kernel<TREX_DYN_FORWARD_DYNAMICS>, grid, block, lds, stream, args); break;
+    case TREX_DYN_SOLVE_MASS: hipLaunchKernelGGL(trex_dynamics_kernel<TREX_DYN_SOLVE_MASS>, grid, block, lds, stream, args); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();

@@ -43,6 +43,7 @@ SYMBOLS = [
     "trex_batch_render", "trex_batch_set_external_wrench", "trex_batch_set_contact_sensor", "trex_batch_contact_wrench",
     "trex_batch_set_control_mode", "trex_batch_set_motor_gains", "trex_batch_set_stiffness_actions",
     "trex_batch_inverse_dynamics", "trex_batch_mass_matrix", "trex_batch_jacobian", "trex_batch_centroidal",
+    "trex_batch_forward_dynamics", "trex_batch_solve_mass",
 ]
 
 # every symbol include/trex_policy.h declares (the trainer-side kernels)
@@ -104,6 +105,9 @@ if hasattr(lib, "trex_batch_inverse_dynamics"):   # (as above: an older TREX_LIB
     lib.trex_batch_mass_matrix.argtypes = [_vp, _vp, _vp]
     lib.trex_batch_jacobian.argtypes = [_vp, C.c_int, C.POINTER(C.c_double), _vp, _vp]
     lib.trex_batch_centroidal.argtypes = [_vp, _vp, _vp]
+if hasattr(lib, "trex_batch_forward_dynamics"):
+    lib.trex_batch_forward_dynamics.argtypes = [_vp, _vp, _vp, _vp]
+    lib.trex_batch_solve_mass.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
 lib.trex_model_use_primitive_collision.argtypes = [_vp, C.c_double, C.c_int, C.c_int]
 lib.trex_model_fit_hull_primitives.argtypes = [_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
 lib.trex_model_num_links.argtypes = [_vp]
@@ -523,6 +527,35 @@ class Batch:
         energy, total mass, 0."""
         out = self._out(out, 16)
         check(lib.trex_batch_centroidal(self.h, self._p(out, "float32", self.num_envs * 16, "out"), self._stream(stream)))
+        return out
+
+    def forward_dynamics(self, force=None, out=None, stream=None):
+        """[n, D] accelerations M^-1 (force - h) for the generalised force `force` [n, D] (None = zeros) at the current state:
+        the inverse of inverse_dynamics. `out` may be `force` itself."""
+        D = 6 + self.J
+        if force is not None and tuple(force.shape) != (self.num_envs, D):
+            raise TrexError(E_INVALID, "force: expected shape %s, got %s" % ((self.num_envs, D), tuple(force.shape)))
+        out = self._out(out, D)
+        check(lib.trex_batch_forward_dynamics(self.h, self._p(force, "float32", self.num_envs * D, "force"),
+                                              self._p(out, "float32", self.num_envs * D, "out"), self._stream(stream)))
+        return out
+
+    def solve_mass(self, rhs=None, out=None, stream=None):
+        """[n, K, D] = M^-1 applied to the K rows rhs[e, k, :] of every env (None = the identity, K = D: M^-1 itself). A
+        [n, D] rhs counts as K = 1 and returns [n, D]. `out` may be `rhs` itself."""
+        D = 6 + self.J
+        if rhs is None:
+            shape = (D, D)
+        elif rhs.dim() in (2, 3) and rhs.shape[0] == self.num_envs and rhs.shape[-1] == D:
+            shape = tuple(rhs.shape[1:])
+        else:
+            raise TrexError(E_INVALID, "rhs: expected shape (%d, K, %d) or (%d, %d), got %s"
+                            % (self.num_envs, D, self.num_envs, D, tuple(rhs.shape)))
+        K = shape[0] if len(shape) == 2 else 1
+        out = self._out(out, *shape)
+        numel = self.num_envs * K * D
+        check(lib.trex_batch_solve_mass(self.h, self._p(rhs, "float32", numel, "rhs"), K,
+                                        self._p(out, "float32", numel, "out"), self._stream(stream)))
         return out
 
     def contact_stats(self, count=None, normal_impulse=None, stream=None):

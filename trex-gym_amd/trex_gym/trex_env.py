@@ -133,6 +133,29 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
         from .vec_env import Centroidal
         return Centroidal(self._vec.centroidal().data[0].cpu().numpy())
 
+    def forward_dynamics(self, force=None, tau=None):
+        """[6 + J] accelerations that the generalised force `force` [6 + J] (or the joint torques tau [J]; None: zeros)
+        produces at the current state: the inverse of inverse_dynamics."""
+        if force is not None:
+            force = np.asarray(force, np.float32).reshape(1, -1)
+        if tau is not None:
+            tau = np.asarray(tau, np.float32).reshape(1, -1)
+        return self._vec.forward_dynamics(force, tau)[0].cpu().numpy()
+
+    def solve_mass(self, rhs=None):
+        """M^-1 applied to rhs: [6 + J] -> [6 + J], [K, 6 + J] -> [K, 6 + J] row by row; None: M^-1 itself."""
+        if rhs is not None:
+            rhs = np.asarray(rhs, np.float32)[None]
+        return self._vec.solve_mass(rhs)[0].cpu().numpy()
+
+    def inverse_mass_matrix(self):
+        """[6 + J, 6 + J] inverse of the joint-space inertia matrix."""
+        return self._vec.inverse_mass_matrix()[0].cpu().numpy()
+
+    def operational_space_inertia(self, link, position=None):
+        """[6, 6] task-space inertia inv(J M^-1 J^T) of a point of a link (as jacobian())."""
+        return self._vec.operational_space_inertia(link, position)[0].cpu().numpy()
+
     def should_terminate(self):
         return False
 

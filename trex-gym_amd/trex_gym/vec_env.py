@@ -407,7 +407,8 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         the mean over the substeps of the last step (a reset env: its settle substep; a contained env: zeros)."""
         return self.batch.contact_wrench(out)
 
-    # ---- dynamics queries (trex_batch_inverse_dynamics / _mass_matrix / _jacobian / _centroidal; no host sync)
+    # ---- dynamics queries (trex_batch_inverse_dynamics / _mass_matrix / _jacobian / _centroidal / _forward_dynamics /
+    # _solve_mass; no host sync)
     # Generalised velocity [D = 6 + J]: base linear v(3), base angular w(3), world axes, then qd in observation order - the
     # velocity part of get_state(); forces are its duals (base force, base torque about the base origin, joint torques).
     def inverse_dynamics(self, accel=None, out=None):
@@ -438,6 +439,36 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         """Whole-body quantities as a Centroidal of device tensors: com [n, 3], com_velocity, momentum, angular_momentum (about
         the COM), kinetic [n], potential (sum m g z), mass (the env's mass scale included); `.data` is the [n, 16] block."""
         return Centroidal(self.batch.centroidal(out))
+
+    def forward_dynamics(self, force=None, tau=None, out=None):
+        """[n, D] accelerations M(q)^-1 (force - h(q, qd)) that the generalised force `force` [n, D] produces at the current
+        state (None: zeros - free motion under gravity): the inverse of inverse_dynamics, rigid-body terms only. tau [n, J] is
+        shorthand for a force with a zero base block; giving both is an error."""
+        if force is not None and tau is not None:
+            raise ValueError("forward_dynamics: give force or tau, not both")
+        if tau is not None:
+            tau = torch.as_tensor(tau).to(device=self.device, dtype=torch.float32)
+            force = torch.cat([torch.zeros(tau.shape[0], 6, dtype=torch.float32, device=self.device), tau], 1)
+        elif force is not None:
+            force = torch.as_tensor(force).to(device=self.device, dtype=torch.float32).contiguous()
+        return self.batch.forward_dynamics(force, out)
+
+    def solve_mass(self, rhs=None, out=None):
+        """[n, K, D] = M(q)^-1 applied to the K force-like rows rhs[e, k, :] of every env, K <= 64 ([n, D]: one row, returns
+        [n, D]); None: the identity, M^-1 itself. solve_mass(jacobian(link)) is (M^-1 J^T)^T. Depends on q alone."""
+        if rhs is not None:
+            rhs = torch.as_tensor(rhs).to(device=self.device, dtype=torch.float32).contiguous()
+        return self.batch.solve_mass(rhs, out)
+
+    def inverse_mass_matrix(self, out=None):
+        """[n, D, D] M(q)^-1 (symmetric up to rounding)."""
+        return self.batch.solve_mass(None, out)
+
+    def operational_space_inertia(self, link, position=None):
+        """[n, 6, 6] task-space inertia inv(J M^-1 J^T) of the point `position` of link `link` (as jacobian()): one Jacobian
+        launch, one solve launch and a batched 6 x 6 inverse."""
+        Jm = self.jacobian(link, position)
+        return torch.linalg.inv(Jm @ self.batch.solve_mass(Jm).transpose(1, 2))
 
     def contact_forces(self, links):
         """[n, K, 3] floor-contact force on URDF links: links = K entries, each a link name / index or a list of them (the

@@ -104,6 +104,25 @@ class Oracle:
         assert a.size == 13 + 2 * self.nj
         self.lib.oracle_set_state(self.h, s, p)
 
+    def set_warmstart(self, s, factor):
+        """PGS warm start of this state's solves (include/trex_batch.h, "warmstart"); 0 = cold, the default"""
+        self.lib.oracle_set_warmstart(s, C.c_double(factor))
+
+    def set_external_wrench(self, s, w):
+        """w [nb, 6] = fx fy fz at the COM, tx ty tz about it, world axes (the C-ABI's layout), held until replaced; None clears it"""
+        if w is None:
+            self.lib.oracle_set_external_wrench(s, None)
+        else:
+            a, p = _d(w)
+            assert a.shape == (self.nb, 6)
+            self.lib.oracle_set_external_wrench(s, p)
+
+    def warm_record(self, s):
+        """the record of the state's last solve: hull vertices [k] and (normal, friction x, friction y) impulses [k, 3], k <= 13"""
+        vert, lam = np.zeros(13, np.int32), np.zeros((13, 3))
+        k = self.lib.oracle_warm_record(s, vert.ctypes.data_as(_ip), lam.ctypes.data_as(_dp))
+        return vert[:k].copy(), lam[:k].copy()
+
     def set_motors_on(self, s, on):
         self.lib.oracle_set_motors_on(s, C.c_int(int(on)))
 

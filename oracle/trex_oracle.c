@@ -41,6 +41,7 @@ typedef double real;
 #define MAXC 64            /* hard cap on contact points kept by the oracle */
 #define MAXROWS (2 * NBMAX + 3 * MAXC)
 #define NDOF_MAX (6 + NBMAX)
+#define WARM_REC 13        /* entries of the warm-start record (include/trex_batch.h: the points of one solve, at most 13) */
 
 enum { /* params[] indices, shared with tests/oracle_binding.py */
   P_DT, P_SUBSTEPS, P_ITERATIONS, P_GRAVITY, P_MOTOR_KP, P_MOTOR_KD, P_MOTOR_MAX_FORCE,
@@ -77,6 +78,14 @@ typedef struct {
   /* diagnostics of the last substep */
   int n_contacts, n_limit_rows;
   real contact_body[MAXC], contact_lambda[MAXC][3], contact_pos[MAXC][3], contact_dist[MAXC];
+  /* PGS warm start (include/trex_batch.h, "warmstart"): the points of the last solve - hull vertex and final normal,
+   * friction-x, friction-y impulse, unscaled - and the factor the next solve starts them at (0 = cold) */
+  real warm_factor;
+  int n_rec, rec_vert[WARM_REC];
+  real rec_lambda[WARM_REC][3];
+  /* external wrench per body (trex_batch_set_external_wrench): fx fy fz at the COM, tx ty tz about it, world axes */
+  int ext_on, ext_nb; /* ext_nb: the model's body count, kept at creation */
+  real ext[NBMAX][6];
 } State;
 
 /* ------------------------------------------------------------------ small algebra */
@@ -440,7 +449,7 @@ __attribute__((visibility("default"))) void oracle_set_rows_hook(oracle_rows_hoo
 
 /* One physics substep = one pybullet stepSimulation() at dt (trex_env.py:150). target[] is the
  * position-motor target per BODY index (ignored when !motors_on). */
-static void substep(const Model *m, State *s, const real *target) {
+static void substep(const Model *m, State *s, const real *target, int with_ext) {
   static Work wk; /* oracle is single-threaded */
   static Row rows[MAXROWS];
   Work *k = &wk;
@@ -461,6 +470,8 @@ static void substep(const Model *m, State *s, const real *target) {
     real Ic[9], ms;
     body_inertia_world(m, s, k, i, Ic, &ms);
     real f[3] = {0, 0, -ms * m->prm[P_GRAVITY]}, n[3] = {0, 0, 0};
+    if (with_ext && s->ext_on) /* before the damping terms and the moment c x f */
+      for (int c = 0; c < 3; c++) { f[c] += s->ext[i][c]; n[c] += s->ext[i][3 + c]; }
     if (kd > 0) {
       real vc[3], wxc[3];
       cross3(k->vel[i], k->comw[i], wxc);
@@ -572,6 +583,19 @@ static void substep(const Model *m, State *s, const real *target) {
   /* ---- projected Gauss-Seidel on the velocity level */
   real dv[NDOF_MAX];
   for (int c = 0; c < nd; c++) dv[c] = 0;
+  /* warm start: a point whose hull vertex is in the record of the last solve starts at factor x its recorded impulses on
+   * its three rows, and dv at the velocity change those impulses make; every other row starts at 0 */
+  if (s->warm_factor != 0)
+    for (int c = 0; c < nc; c++)
+      for (int e = 0; e < s->n_rec; e++) {
+        if (s->rec_vert[e] != cts[c].vert) continue;
+        for (int a = 0; a < 3; a++) {
+          Row *r = &rows[contact_row[c] + a];
+          r->lambda = s->warm_factor * s->rec_lambda[e][a];
+          if (r->lambda != 0)
+            for (int x = 0; x < nd; x++) dv[x] += r->lambda * r->W[x];
+        }
+      }
   const int iters = (int)m->prm[P_ITERATIONS];
   for (int it = 0; it < iters; it++) {
     for (int ri = 0; ri < nr; ri++) {
@@ -593,6 +617,11 @@ static void substep(const Model *m, State *s, const real *target) {
   for (int i = 1; i < nb; i++) {
     s->qd[i] = vgen[6 + i - 1];
     s->motor_tau[i] = (motor_row[i] >= 0) ? rows[motor_row[i]].lambda / dt : 0;
+  }
+  s->n_rec = nc < WARM_REC ? nc : WARM_REC; /* every solve overwrites the record */
+  for (int c = 0; c < s->n_rec; c++) {
+    s->rec_vert[c] = cts[c].vert;
+    for (int a = 0; a < 3; a++) s->rec_lambda[c][a] = rows[contact_row[c] + a].lambda;
   }
   s->n_contacts = nc;
   for (int c = 0; c < nc; c++) {
@@ -674,6 +703,7 @@ API State *oracle_state_create(const Model *m) {
   for (int i = 0; i < NBMAX; i++) s->mass_scale[i] = 1;
   s->friction = m->prm[P_FRICTION];
   s->quat[3] = 1;
+  s->ext_nb = m->nb;
   return s;
 }
 API void oracle_state_destroy(State *s) { free(s); }
@@ -696,6 +726,21 @@ API void oracle_set_state(const Model *m, State *s, const double *in) {
   for (int c = 0; c < 3; c++) { s->pos[c] = (real)in[c]; s->v[c] = (real)in[7 + c]; s->w[c] = (real)in[10 + c]; }
   for (int c = 0; c < 4; c++) s->quat[c] = (real)in[3 + c];
   for (int k = 0; k < nj; k++) { s->q[m->obs_order[k]] = (real)in[13 + k]; s->qd[m->obs_order[k]] = (real)in[13 + nj + k]; }
+  s->n_rec = 0; /* trex_batch_set_state empties the record */
+}
+API void oracle_set_warmstart(State *s, double factor) { s->warm_factor = (real)factor; }
+/* w[nb][6], the C-ABI's layout; NULL clears it. Held until replaced: resets and oracle_set_state keep it. */
+API void oracle_set_external_wrench(State *s, const double *w) {
+  s->ext_on = w != NULL;
+  for (int i = 0; i < NBMAX; i++)
+    for (int c = 0; c < 6; c++) s->ext[i][c] = (w && i < s->ext_nb) ? (real)w[6 * i + c] : 0;
+}
+API int oracle_warm_record(const State *s, int *vert, double *lambda) {
+  for (int e = 0; e < s->n_rec; e++) {
+    vert[e] = s->rec_vert[e];
+    for (int a = 0; a < 3; a++) lambda[3 * e + a] = s->rec_lambda[e][a];
+  }
+  return s->n_rec;
 }
 API void oracle_set_motors_on(State *s, int on) { s->motors_on = on; }
 
@@ -735,15 +780,16 @@ API void oracle_reset(const Model *m, State *s) {
   for (int c = 0; c < 4; c++) s->quat[c] = m->base_quat0[c];
   for (int i = 0; i < NBMAX; i++) { s->q[i] = (i < m->nb) ? m->q_start[i] : 0; s->qd[i] = 0; s->motor_tau[i] = 0; }
   s->motors_on = 0;              /* remove_joint_control, trex_robot.py:309 */
+  s->n_rec = 0;                  /* a reset empties the record before its settle substep */
   real dummy[NBMAX] = {0};
-  substep(m, s, dummy);          /* trex_env.py:120 */
+  substep(m, s, dummy, 0);       /* trex_env.py:120; the external wrench does not act on it */
 }
 
 API void oracle_substep(const Model *m, State *s, const double *target_obs_order) {
   real tgt[NBMAX] = {0};
   if (target_obs_order)
     for (int k = 0; k < m->nb - 1; k++) tgt[m->obs_order[k]] = (real)target_obs_order[k];
-  substep(m, s, tgt);
+  substep(m, s, tgt, 1);
 }
 
 /* TrexBulletEnv.step (trex_env.py:128-154) */
@@ -759,7 +805,7 @@ API void oracle_step(const Model *m, State *s, const double *action, const doubl
   }
   s->motors_on = 1;
   int n = (int)m->prm[P_SUBSTEPS];
-  for (int i = 0; i < n; i++) substep(m, s, tgt);
+  for (int i = 0; i < n; i++) substep(m, s, tgt, 1);
   if (obs) oracle_observe(m, s, obs);
   double r = oracle_reward(m, s, weights, penalties);
   if (reward) *reward = r;

@@ -1,6 +1,7 @@
 """External wrench per env and body (trex_batch_set_external_wrench, include/trex_batch.h) on the GPU: pinned against the f64
 oracle through an exact restatement of gravity, momentum balance in free flight, bitwise identities for the zero wrench, the
-launch forms, resets and step_many, refusals, containment, and the Python surface (trex_gym.perturb, TrexVecEnv)."""
+launch forms, resets and step_many, refusals, containment, and the Python surface (trex_gym.perturb, TrexVecEnv).
+The exact comparison - one-hot forces and torques per body, in contact, against the oracle's own wrench: tests/test_gpu_feature_oracle.py."""
 import ctypes as C
 import math
 

@@ -4,7 +4,8 @@ vertex - starts the next solve at warmstart x its recorded impulses. Everything 
 Bitwise properties: warmstart = 0 is the product kernels' rows; an empty record is the cold solve; the record follows the env
 (step_many, resets, set_state, permutations, launch forms). Accuracy: against the f64 oracle at 6000 sweeps (the converged
 reference of tests/test_oracle_physics.py), warm and cold solves at 2000 sweeps agree, and at 60 sweeps on states at rest the
-warm solve is the closer one (measured numbers: profiles/r05_warmstart.txt)."""
+warm solve is the closer one (measured numbers: profiles/r05_warmstart.txt).
+The exact comparison - what a warm solve at 60 sweeps returns, env-step by env-step against the oracle: tests/test_gpu_feature_oracle.py."""
 import numpy as np
 import pytest
 import torch

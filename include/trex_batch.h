@@ -264,6 +264,39 @@ typedef struct TrexCamera {
 int trex_batch_render(TrexBatch *batch, const TrexCamera *camera, int width, int height, const int32_t *env_ids,
                       int num_views, uint8_t *rgb_dev, float *depth_dev, int32_t *seg_dev, void *stream);
 
+/* ---- ray casts (pybullet's rayTestBatch; no reference counterpart): range sensors - height scanners, lidar fans on a link,
+ *      foot clearance, line of sight. R segments per env against the geometry trex_batch_render draws, at the current state.
+ *
+ * rays_dev [N, R, 6] f32 device, or [R, 6] when shared != 0 (one pattern for every env): from xyz, to xyz of each segment.
+ * link: the coordinates are in the frame of URDF link `link` (indices and frames as trex_model_link_info and "link_tf", as in
+ *   trex_batch_jacobian), evaluated at each env's current state; -1: the world frame. A HOST value shared by all envs.
+ * body_mask: bit b set = body b may be hit (0xFFFFFFFF: every body); hit_floor != 0: the floor half-space z <= floor_z may be
+ *   hit. body_mask 0 without hit_floor is legal: everything misses. Masked bodies cost no work.
+ * Geometry: exactly what trex_batch_render draws - the hull planes ("hull_plane"), after trex_model_use_primitive_collision the
+ *   spheres, the floor plane - from the table the two calls share (made by whichever comes first; more than 512 primitives:
+ *   TREX_E_UNSUPPORTED). The hulls are the COLLISION hulls, not pybullet's visual meshes.
+ * Outputs, device; fraction_dev is required, the other three are nullable; every element of every non-NULL output is written:
+ *   fraction_dev [N, R] f32     t in [0, 1] along from -> to of the hit; 1.0 on a miss (pybullet's value)
+ *   body_dev     [N, R] i32     body index, -1 the floor (the renderer's seg code); -2 on a miss
+ *   position_dev [N, R, 3] f32  world hit point; the world `to` point on a miss
+ *   normal_dev   [N, R, 3] f32  world unit normal - the entered face of a hull, radial for a sphere, (0, 0, 1) for the floor;
+ *                               zeros on a miss
+ * Hit rule: the nearest ENTRY point with 0 <= t <= 1. A primitive that contains `from` (its entry lies behind the origin,
+ *   t_enter < 0) is not hit by that ray - a hull, a sphere, and the floor when from.z < floor_z: a sensor placed inside the head
+ *   hull looks out of it. This is Bullet's behaviour AS RECALLED (a ray that starts inside a convex shape does not report it);
+ *   it is NOT pinned against pybullet, which is not available here. Ties go to the floor first, then to the lower primitive
+ *   index, as in the renderer.
+ * Ray values are not validated: a zero-length or non-finite ray is a miss (fraction 1, body -2, zero normal; its position is
+ *   whatever its `to` transforms to) and disturbs no other ray.
+ * Like the dynamics queries: asynchronous on `stream`; every device buffer validated (host memory, foreign memory or a short
+ *   buffer: TREX_E_INVALID before any launch); nothing but the outputs written - state, warm-start record, contact sensor and
+ *   episode counts stay bitwise untouched. The first call may allocate the table; from the second call with known buffers it is
+ *   one plain kernel launch, usable in a single-stream capture. TREX_E_INVALID also for num_rays outside [1, 16384], link
+ *   outside [-1, num_links), rays_dev or fraction_dev NULL. */
+int trex_batch_ray_test(TrexBatch *batch, const float *rays_dev, int num_rays, int shared, int link, uint32_t body_mask,
+                        int hit_floor, float *fraction_dev, int32_t *body_dev, float *position_dev, float *normal_dev,
+                        void *stream);
+
 /* domain randomisation (BASELINE config 5; no reference counterpart): per-env mass scale of each
  * moving body [N, num_bodies] and per-env friction coefficient [N]; either may be NULL. */
 int trex_batch_set_domain(TrexBatch *batch, const float *mass_scale_dev, const float *friction_dev,

@@ -14,6 +14,7 @@
 #include "dynamics.h"
 #include "internal.hpp"
 #include "model.hpp"
+#include "raycast.h"
 #include "render.h"
 #include "step_launch.h"
 
@@ -1007,6 +1008,34 @@ int trex_batch_time_steps(TrexBatch *b, const float *actions_dev, float *obs_dev
   return TREX_OK;
 }
 
+// The primitive / plane table the renderer and the ray casts share (render.cpp), once per batch and made by whichever call comes
+// first (trex_model_load stays as fast as it was). `who`: the calling entry point, for the message.
+static int ensure_render_table(TrexBatch *b, const char *who) {
+  if (b->render_ready) return TREX_OK;
+  trex::HostModel hm;
+  hm.nb = b->nb;
+  hm.hull_xyz = b->hull_xyz; hm.hull_radius = b->hull_radius; hm.hull_start = b->hull_start; hm.hull_group_start = b->hull_group_start;
+  std::vector<TrexRenderPrim> prims;
+  std::vector<float> planes;
+  const int np = trex::render_table(hm, prims, planes);
+  if (np > TREX_RENDER_MAXPRIM)
+    return fail(TREX_E_UNSUPPORTED, std::string(who) + ": the model has " + std::to_string(np) + " drawable primitives, the renderer " +
+                                        std::to_string(TREX_RENDER_MAXPRIM));
+  if (planes.empty()) planes.assign(4, 0.f);
+  if (prims.empty()) prims.resize(1);
+  void *pp = nullptr, *pl = nullptr;
+  HIP_TRY(hipMalloc(&pp, prims.size() * sizeof(TrexRenderPrim)));
+  b->allocs.push_back(pp);
+  HIP_TRY(hipMalloc(&pl, planes.size() * sizeof(float)));
+  b->allocs.push_back(pl);
+  HIP_TRY(hipMemcpy(pp, prims.data(), prims.size() * sizeof(TrexRenderPrim), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(pl, planes.data(), planes.size() * sizeof(float), hipMemcpyHostToDevice));
+  b->render_prim = (TrexRenderPrim *)pp; b->render_plane = (float4 *)pl; b->render_nprim = np;
+  b->render_ready = true;
+  return TREX_OK;
+}
+
+
 int trex_batch_render(TrexBatch *b, const TrexCamera *cam, int width, int height, const int32_t *env_ids, int num_views,
                       uint8_t *rgb_dev, float *depth_dev, int32_t *seg_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
@@ -1037,28 +1066,7 @@ int trex_batch_render(TrexBatch *b, const TrexCamera *cam, int width, int height
   BUF_TRY(depth_dev, px * sizeof(float), "trex_batch_render: depth");
   BUF_TRY(seg_dev, px * sizeof(int32_t), "trex_batch_render: seg");
   hipStream_t s = (hipStream_t)stream;
-  if (!b->render_ready) {   // the primitive / plane table, once per batch (trex_model_load stays as fast as it was)
-    trex::HostModel hm;
-    hm.nb = b->nb;
-    hm.hull_xyz = b->hull_xyz; hm.hull_radius = b->hull_radius; hm.hull_start = b->hull_start; hm.hull_group_start = b->hull_group_start;
-    std::vector<TrexRenderPrim> prims;
-    std::vector<float> planes;
-    const int np = trex::render_table(hm, prims, planes);
-    if (np > TREX_RENDER_MAXPRIM)
-      return fail(TREX_E_UNSUPPORTED, "trex_batch_render: the model has " + std::to_string(np) + " drawable primitives, the renderer " +
-                                          std::to_string(TREX_RENDER_MAXPRIM));
-    if (planes.empty()) planes.assign(4, 0.f);
-    if (prims.empty()) prims.resize(1);
-    void *pp = nullptr, *pl = nullptr;
-    HIP_TRY(hipMalloc(&pp, prims.size() * sizeof(TrexRenderPrim)));
-    b->allocs.push_back(pp);
-    HIP_TRY(hipMalloc(&pl, planes.size() * sizeof(float)));
-    b->allocs.push_back(pl);
-    HIP_TRY(hipMemcpy(pp, prims.data(), prims.size() * sizeof(TrexRenderPrim), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pl, planes.data(), planes.size() * sizeof(float), hipMemcpyHostToDevice));
-    b->render_prim = (TrexRenderPrim *)pp; b->render_plane = (float4 *)pl; b->render_nprim = np;
-    b->render_ready = true;
-  }
+  if (int c = ensure_render_table(b, "trex_batch_render")) return c;
   if (env_ids) {
     if (b->render_ids_cap < (size_t)num_views) {   // (grows rarely: the old buffer may still be read by an earlier call)
       HIP_TRY(hipDeviceSynchronize());
@@ -1095,6 +1103,42 @@ int trex_batch_render(TrexBatch *b, const TrexCamera *cam, int width, int height
   a.near_z = cam->near_z; a.far_z = cam->far_z;
   a.floor_z = (float)b->floor_z;
   HIP_TRY(trex_launch_render(a, s));
+  return TREX_OK;
+}
+
+int trex_batch_ray_test(TrexBatch *b, const float *rays_dev, int num_rays, int shared, int link, uint32_t body_mask, int hit_floor,
+                        float *fraction_dev, int32_t *body_dev, float *position_dev, float *normal_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!rays_dev || !fraction_dev) return fail(TREX_E_INVALID, "trex_batch_ray_test: rays or fraction is null");
+  if (num_rays < 1 || num_rays > TREX_RAY_MAXRAYS)
+    return fail(TREX_E_INVALID, "trex_batch_ray_test: num_rays " + std::to_string(num_rays) + " outside [1, " +
+                                    std::to_string(TREX_RAY_MAXRAYS) + "]");
+  if (link < -1 || link >= (int)b->link_body.size())
+    return fail(TREX_E_INVALID, "trex_batch_ray_test: link " + std::to_string(link) + " out of range [-1, " +
+                                    std::to_string(b->link_body.size()) + ")");
+  DeviceGuard guard(b->device);
+  const size_t nr = (size_t)b->n * num_rays;
+  BUF_TRY(rays_dev, (shared ? (size_t)num_rays : nr) * 6 * sizeof(float), "trex_batch_ray_test: rays");
+  BUF_TRY(fraction_dev, nr * sizeof(float), "trex_batch_ray_test: fraction");
+  BUF_TRY(body_dev, nr * sizeof(int32_t), "trex_batch_ray_test: body");
+  BUF_TRY(position_dev, nr * 3 * sizeof(float), "trex_batch_ray_test: position");
+  BUF_TRY(normal_dev, nr * 3 * sizeof(float), "trex_batch_ray_test: normal");
+  if (int c = ensure_render_table(b, "trex_batch_ray_test")) return c;
+  TrexRayArgs a{};
+  a.model = b->dmodel; a.base = b->arr.base; a.q = b->arr.q;
+  a.rays = rays_dev; a.fraction = fraction_dev; a.body = body_dev; a.position = position_dev; a.normal = normal_dev;
+  a.n_envs = b->n; a.num_rays = num_rays; a.shared = shared != 0;
+  a.link_body = -1;
+  if (link >= 0) {   // the frame of the link in its body: body <- link of "link_tf"
+    const trex::Tf &t = b->link_tf[link];
+    a.link_body = b->link_body[link];
+    for (int k = 0; k < 9; k++) a.link_tf[k] = (float)t.R.m[k];
+    a.link_tf[9] = (float)t.t.x; a.link_tf[10] = (float)t.t.y; a.link_tf[11] = (float)t.t.z;
+  }
+  a.nprim = b->render_nprim; a.hit_floor = hit_floor != 0;
+  a.body_mask = b->nb >= 32 ? body_mask : body_mask & ((1u << b->nb) - 1u);   // (bits beyond the model's bodies mean nothing)
+  a.floor_z = (float)b->floor_z;
+  HIP_TRY(trex_launch_ray_test(a, b->render_prim, b->render_plane, (hipStream_t)stream));
   return TREX_OK;
 }
 

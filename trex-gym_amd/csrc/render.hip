@@ -6,6 +6,7 @@
 
 #include "device_math.h"
 #include "render.h"
+#include "render_pose.h"
 
 namespace {
 
@@ -44,28 +45,9 @@ __global__ __launch_bounds__(256) void trex_render_kernel(TrexRenderArgs a) {
   const int t = threadIdx.x;
   const float *b = a.base + (size_t)env * 16;
 
-  // ---- body poses: lane t < nb composes the base pose with the hinges of its chain (anc: ancestor per depth)
+  // ---- body poses: lane t < nb composes the base pose with the hinges of its chain (render_pose.h)
   if (t < M->nb) {
-    const float quat[4] = {b[3], b[4], b[5], b[6]};
-    float R[9], p[3] = {b[0], b[1], b[2]};
-    quat_to_mat(quat, R);
-    const int dep = M->depth[t];
-    for (int d = 1; d <= dep; d++) {
-      const int i = M->anc[d - 1][t];
-      const float ax[3] = {M->axis[0][i], M->axis[1][i], M->axis[2][i]}, jp[3] = {M->jpos[0][i], M->jpos[1][i], M->jpos[2][i]};
-      float jr[9], rq[9], tmp[9];
-      for (int c = 0; c < 9; c++) jr[c] = M->jrot[c][i];
-      const float q = a.q[(size_t)env * TL + i];
-      const float c = cosf(q), s = sinf(q), tt = 1.f - c;
-      rq[0] = tt * ax[0] * ax[0] + c;         rq[1] = tt * ax[0] * ax[1] - s * ax[2]; rq[2] = tt * ax[0] * ax[2] + s * ax[1];
-      rq[3] = tt * ax[0] * ax[1] + s * ax[2]; rq[4] = tt * ax[1] * ax[1] + c;         rq[5] = tt * ax[1] * ax[2] - s * ax[0];
-      rq[6] = tt * ax[0] * ax[2] - s * ax[1]; rq[7] = tt * ax[1] * ax[2] + s * ax[0]; rq[8] = tt * ax[2] * ax[2] + c;
-      for (int r = 0; r < 3; r++) p[r] += R[3 * r] * jp[0] + R[3 * r + 1] * jp[1] + R[3 * r + 2] * jp[2];
-      for (int r = 0; r < 3; r++)
-        for (int k = 0; k < 3; k++) tmp[3 * r + k] = R[3 * r] * jr[k] + R[3 * r + 1] * jr[3 + k] + R[3 * r + 2] * jr[6 + k];
-      for (int r = 0; r < 3; r++)
-        for (int k = 0; k < 3; k++) R[3 * r + k] = tmp[3 * r] * rq[k] + tmp[3 * r + 1] * rq[3 + k] + tmp[3 * r + 2] * rq[6 + k];
-    }
+    TREX_BODY_WORLD_POSE(M, b, a.q, env, t, R, p)
     for (int c = 0; c < 9; c++) sPose[t][c] = R[c];
     for (int c = 0; c < 3; c++) sPose[t][9 + c] = p[c];
   }

@@ -43,7 +43,7 @@ SYMBOLS = [
     "trex_batch_render", "trex_batch_set_external_wrench", "trex_batch_set_contact_sensor", "trex_batch_contact_wrench",
     "trex_batch_set_control_mode", "trex_batch_set_motor_gains", "trex_batch_set_stiffness_actions",
     "trex_batch_inverse_dynamics", "trex_batch_mass_matrix", "trex_batch_jacobian", "trex_batch_centroidal",
-    "trex_batch_forward_dynamics", "trex_batch_solve_mass",
+    "trex_batch_forward_dynamics", "trex_batch_solve_mass", "trex_batch_ray_test",
 ]
 
 # every symbol include/trex_policy.h declares (the trainer-side kernels)
@@ -108,6 +108,8 @@ if hasattr(lib, "trex_batch_inverse_dynamics"):   # (as above: an older TREX_LIB
 if hasattr(lib, "trex_batch_forward_dynamics"):
     lib.trex_batch_forward_dynamics.argtypes = [_vp, _vp, _vp, _vp]
     lib.trex_batch_solve_mass.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
+if hasattr(lib, "trex_batch_ray_test"):
+    lib.trex_batch_ray_test.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, _vp]
 lib.trex_model_use_primitive_collision.argtypes = [_vp, C.c_double, C.c_int, C.c_int]
 lib.trex_model_fit_hull_primitives.argtypes = [_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
 lib.trex_model_num_links.argtypes = [_vp]
@@ -582,6 +584,36 @@ class Batch:
         check(lib.trex_batch_render(self.h, C.byref(cam), int(width), int(height), ids, V if env_ids is not None else 0,
                                     self._p(rgb, "uint8", 3 * px, "rgb"), self._p(depth, "float32", px, "depth"),
                                     self._p(seg, "int32", px, "seg"), self._stream(stream)))
+
+    def ray_test(self, rays, link=-1, shared=None, body_mask=0xFFFFFFFF, hit_floor=True, fraction=None, body=None, position=None,
+                 normal=None, stream=None):
+        """Ray casts against the geometry render() draws (trex_batch_ray_test): rays [n, R, 6] f32 on the batch's device, or
+        [R, 6] for one pattern shared by every env (shared defaults from the rank) - from xyz, to xyz in the frame of URDF link
+        index `link` (-1: world). body_mask: bit b = body b may be hit; hit_floor: the floor may be. Outputs, device tensors:
+        fraction [n, R] f32 (made when None, and returned), body [n, R] int32, position and normal [n, R, 3] f32, each optional."""
+        import torch
+        if not hasattr(rays, "dim") or rays.dim() not in (2, 3) or rays.shape[-1] != 6:
+            raise TrexError(E_INVALID, "rays: expected a tensor of shape [n, R, 6] or [R, 6]")
+        if shared is None:
+            shared = rays.dim() == 2
+        n, R = self.num_envs, int(rays.shape[-2])
+        want = (R, 6) if shared else (n, R, 6)
+        if tuple(rays.shape) != want:
+            raise TrexError(E_INVALID, "rays: expected shape %s, got %s" % (want, tuple(rays.shape)))
+        mask = int(body_mask)
+        if not 0 <= mask <= 0xFFFFFFFF:
+            raise TrexError(E_INVALID, "body_mask: expected a 32-bit mask, got %r" % (body_mask,))
+        if fraction is None and rays.is_cuda:
+            fraction = torch.empty(n, R, dtype=torch.float32, device=rays.device)
+        for name, t, shape in (("fraction", fraction, (n, R)), ("body", body, (n, R)), ("position", position, (n, R, 3)),
+                               ("normal", normal, (n, R, 3))):
+            if t is not None and tuple(t.shape) != shape:
+                raise TrexError(E_INVALID, "%s: expected shape %s, got %s" % (name, shape, tuple(t.shape)))
+        check(lib.trex_batch_ray_test(self.h, self._p(rays, "float32", (1 if shared else n) * R * 6, "rays"), R, 1 if shared else 0,
+                                      int(link), mask, 1 if hit_floor else 0, self._p(fraction, "float32", n * R, "fraction"),
+                                      self._p(body, "int32", n * R, "body"), self._p(position, "float32", n * R * 3, "position"),
+                                      self._p(normal, "float32", n * R * 3, "normal"), self._stream(stream)))
+        return fraction
 
     def launch_info(self):
         g, b, l, a = C.c_int(), C.c_int(), C.c_int(), C.c_int()

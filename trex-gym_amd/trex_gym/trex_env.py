@@ -51,6 +51,7 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
                                starting_configuration=self._starting_configuration, control_mode=control_mode,
                                variable_stiffness=variable_stiffness, kp_max=kp_max)
         self.model = trex_robot.TrexRobot(self._vec, 0)
+        self._ray_links = None
         self._sensor_on = bool(contact_sensor)   # (contact_wrench(); off: the default kernels)
         if self._sensor_on:
             self._vec.enable_contact_sensor(True)
@@ -155,6 +156,53 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
     def operational_space_inertia(self, link, position=None):
         """[6, 6] task-space inertia inv(J M^-1 J^T) of a point of a link (as jacobian())."""
         return self._vec.operational_space_inertia(link, position)[0].cpu().numpy()
+
+    # pybullet's body ids of this world: the robot and the floor (the ids are this env's own - the reference loads the floor first)
+    ROBOT_ID, FLOOR_ID = 0, 1
+
+    def rayTestBatch(self, rayFromPositions, rayToPositions, parentLinkIndex=-1):
+        """pybullet's rayTestBatch: one (objectUniqueId, linkIndex, hitFraction, hitPosition, hitNormal) per ray. The rays are in
+        world coordinates, or - parentLinkIndex >= 0, pybullet's joint / link index - in the frame of that link. objectUniqueId:
+        ROBOT_ID, FLOOR_ID, or -1 on a miss (then linkIndex -1, hitFraction 1.0, zeros); linkIndex: the pybullet index of the
+        hit body's own link, -1 for the base. Cast against the collision hulls, not the visual meshes; a shape that contains a
+        ray's origin is not hit by it (TrexVecEnv.ray_test, include/trex_batch.h)."""
+        frm = np.asarray(rayFromPositions, np.float32).reshape(-1, 3)
+        to = np.asarray(rayToPositions, np.float32).reshape(-1, 3)
+        if frm.shape != to.shape:
+            raise ValueError("rayFromPositions and rayToPositions differ in length")
+        if len(frm) == 0:
+            return []
+        m = self._vec.model
+        if self._ray_links is None:   # body -> pybullet link index (= the index of the joint that moves it), and back to a link name
+            body_link = [-1] * m.num_bodies
+            for k, b in enumerate(m.array("obs_order").astype(int)):
+                body_link[b] = int(m.urdf_joint_indices[k])
+            own = {}
+            ltf = m.array("link_tf").reshape(-1, 12)
+            for l, (name, b) in enumerate(m.links()):   # the body's own link: the one whose frame is the body's
+                off = np.abs(ltf[l, :9] - np.eye(3).reshape(-1)).sum() + np.abs(ltf[l, 9:]).sum()
+                if b not in own or off < own[b][0]:
+                    own[b] = (off, l)
+            self._ray_links = (body_link, {body_link[b]: own[b][1] for b in own})
+        body_link, link_of = self._ray_links
+        if parentLinkIndex not in link_of:
+            raise ValueError("parentLinkIndex %r is not a link of the robot (-1: world frame)" % (parentLinkIndex,))
+        link = None if parentLinkIndex == -1 else link_of[parentLinkIndex]
+        rays = torch.from_numpy(np.concatenate([frm, to], 1))
+        frac, body, pos, nrm = [x[0].cpu().numpy() for x in self._vec.ray_test(rays, link, positions=True, normals=True)]
+        out = []
+        for k in range(len(frm)):
+            b = int(body[k])
+            if b == -2:
+                out.append((-1, -1, 1.0, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0)))
+            else:
+                out.append((self.FLOOR_ID if b == -1 else self.ROBOT_ID, -1 if b == -1 else body_link[b], float(frac[k]),
+                            tuple(float(x) for x in pos[k]), tuple(float(x) for x in nrm[k])))
+        return out
+
+    def rayTest(self, rayFromPosition, rayToPosition):
+        """pybullet's rayTest: rayTestBatch of the one ray (a list of one tuple)."""
+        return self.rayTestBatch([rayFromPosition], [rayToPosition])
 
     def should_terminate(self):
         return False

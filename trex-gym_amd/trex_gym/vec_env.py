@@ -116,6 +116,7 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         self._ep_ret = self._ep_len = None      # episode statistics of the numpy API (step_wait)
         self._wrench = None                     # the caller's external wrench [n, num_bodies, 6] (None: none)
         self._link_table = None
+        self._ray_out = (None, None)            # ray_test's output buffers of the last (R, positions, normals)
         self.pushes = pushes
         if pushes is not None and pushes.num_envs != n:
             raise ValueError("pushes: RandomPushes over %d envs, the env has %d" % (pushes.num_envs, n))
@@ -469,6 +470,44 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         launch, one solve launch and a batched 6 x 6 inverse."""
         Jm = self.jacobian(link, position)
         return torch.linalg.inv(Jm @ self.batch.solve_mass(Jm).transpose(1, 2))
+
+    # ---- ray casts (trex_batch_ray_test: pybullet's rayTestBatch; no host sync; trex_gym.sensors builds patterns)
+    def ray_test(self, rays, link=None, positions=False, normals=False, bodies=None, floor=True):
+        """Cast rays [n, R, 6] (or [R, 6]: one pattern for every env) - from xyz, to xyz, in the frame of link `link` (name or
+        index; None: the world) - against the collision geometry render_tensor() draws, at the current state. bodies: an
+        iterable of body indices that may be hit (None: all); floor: whether the floor may be.
+        -> (fraction [n, R], body [n, R] int32[, position [n, R, 3]][, normal [n, R, 3]]) on the device: fraction of the
+        segment at the nearest hit (1.0: none), body index (-1 the floor, -2 a miss), world hit point (a miss: the segment's
+        end) and unit normal (a miss: zeros). The tensors are buffers of the env, reused by the next call of the same shape."""
+        from .perturb import LinkTable
+        if link is None:
+            k = -1
+        else:
+            if self._link_table is None:
+                self._link_table = LinkTable.from_model(self.model)
+            k = self._link_table.index(link)
+        rays = torch.as_tensor(rays)
+        if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.device != self.device:
+            rays = rays.to(device=self.device, dtype=torch.float32).contiguous()
+        if rays.dim() not in (2, 3) or rays.shape[-1] != 6:
+            raise ValueError("rays must have shape (%d, R, 6) or (R, 6), got %s" % (self.num_envs, tuple(rays.shape)))
+        mask = 0xFFFFFFFF
+        if bodies is not None:
+            mask = 0
+            for b in bodies:
+                if not 0 <= int(b) < self.model.num_bodies:
+                    raise IndexError("body index %d out of range [0, %d)" % (int(b), self.model.num_bodies))
+                mask |= 1 << int(b)
+        n, R = self.num_envs, int(rays.shape[-2])
+        key = (R, bool(positions), bool(normals))
+        if self._ray_out[0] != key:   # (one shape is kept: a caller that sweeps R does not pile up device memory)
+            self._ray_out = (None, None)
+            self._ray_out = (key, (torch.empty(n, R, device=self.device), torch.empty(n, R, dtype=torch.int32, device=self.device),
+                                   torch.empty(n, R, 3, device=self.device) if positions else None,
+                                   torch.empty(n, R, 3, device=self.device) if normals else None))
+        frac, body, pos, nrm = self._ray_out[1]
+        self.batch.ray_test(rays, k, None, mask, floor, frac, body, pos, nrm)
+        return (frac, body) + ((pos,) if positions else ()) + ((nrm,) if normals else ())
 
     def contact_forces(self, links):
         """[n, K, 3] floor-contact force on URDF links: links = K entries, each a link name / index or a list of them (the

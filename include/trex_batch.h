@@ -444,6 +444,48 @@ int trex_batch_forward_dynamics(TrexBatch *batch, const float *force_dev, float 
  * x = M^-1 itself. 1 <= K <= 64, otherwise TREX_E_INVALID. No gravity and no velocity terms enter: it depends on q alone. */
 int trex_batch_solve_mass(TrexBatch *batch, const float *rhs_dev, int num_rhs, float *x_dev, void *stream);
 
+/* ---- link kinematics (what users take from pybullet's getLinkState(computeLinkVelocity=1), and more: the acceleration of a
+ *      task point - at zero generalised accelerations the bias acceleration Jdot qd of an operational-space controller - and the
+ *      specific force an accelerometer on a link reads; no reference counterpart: foot velocities for slip penalties, body-frame
+ *      foot positions for observations, IMUs - without a host round trip and without one Jacobian launch per link)
+ *
+ * The query behaves like the dynamics queries above: asynchronous and ordered on `stream`, every device buffer validated (host
+ * memory, another device's memory or a short buffer returns TREX_E_INVALID before anything is launched), nothing allocated or
+ * waited for, nothing written but the outputs (state, observations, the warm-start record, the contact sensor and the episode
+ * counts are untouched), and from the second call with known buffers a plain kernel launch - ONE launch whatever the number of
+ * probes - usable inside a single-stream capture. It uses their conventions: D, the order and the axes of the generalised
+ * velocity, classical accelerations. The env's mass scale does not enter: this is kinematics. */
+#define TREX_AXES_WORLD 0
+#define TREX_AXES_LINK  1   /* each probe's own link frame */
+#define TREX_AXES_BASE  2   /* URDF link 0's frame */
+
+/* A probe = a point fixed in a URDF link: (link, local_xyz in the link frame; indices and frames as trex_model_link_info /
+ * "link_tf", as in trex_batch_jacobian). link_host [num_probes] and local_xyz_host [num_probes, 3] are HOST arrays, shared by all
+ * envs, validated here (link outside [0, num_links), non-finite point, set outside [0, 8), num_probes outside [0, 1024]:
+ * TREX_E_INVALID, nothing changed) and copied into a batch-owned device table; a batch holds up to 8 sets. num_probes 0 frees the
+ * set (the arrays may then be NULL). Synchronous: it waits for the device before it replaces or frees a set's table (not inside
+ * a capture), like trex_batch_set_control_mode. */
+int trex_batch_set_link_probes(TrexBatch *batch, int set, const int32_t *link_host, const double *local_xyz_host, int num_probes);
+
+/* Kinematics of every probe of `set` at every env's current state. K = the set's size. Outputs f32 device, each nullable, not all:
+ *   pose_dev         [N, K, 7]  position of the point xyz + orientation of the link frame, quaternion xyzw (w >= 0)
+ *   velocity_dev     [N, K, 6]  linear velocity of the point, angular velocity of the link
+ *   acceleration_dev [N, K, 6]  classical linear acceleration of the point (d2p/dt2), angular acceleration of the link,
+ *                               at the generalised accelerations accel_dev [N, D] (conventions of the dynamics queries);
+ *                               accel_dev NULL = zeros: the bias acceleration Jdot qd. accel_dev is read only when
+ *                               acceleration_dev is given.
+ * axes: the axes the velocity and acceleration 3-vectors are expressed in. They stay velocities / accelerations relative to
+ *   the WORLD; only their components change. pose_dev is the world pose for WORLD and LINK (for a probe at its link's origin,
+ *   the link's row of trex_batch_link_transforms); for BASE it is the pose relative to URDF link 0's frame (position in its axes
+ *   from its origin, orientation base^-1 o link).
+ * proper != 0: the linear acceleration has +g z (world) added before it is expressed in `axes`: the specific force an
+ *   accelerometer at the point reads; a body at rest reads (0, 0, g) in world axes. g = the model parameter "gravity".
+ * An empty or never-set probe set, a set outside [0, 8), axes outside 0..2 or all three outputs NULL return TREX_E_INVALID.
+ * Non-finite state values are not an error: they give non-finite outputs for that env only. The common outputs of a pose-only, a
+ * pose + velocity and a full call are bitwise equal (the smaller calls run kernels that read neither qd nor accel_dev). */
+int trex_batch_link_state(TrexBatch *batch, int set, int axes, int proper, const float *accel_dev,
+                          float *pose_dev, float *velocity_dev, float *acceleration_dev, void *stream);
+
 /* diagnostics of the last substep: contact count per env [N] i32 (nullable), summed normal
  * impulse per env [N] f32 (nullable). */
 int trex_batch_contact_stats(TrexBatch *batch, int32_t *count_dev, float *normal_impulse_dev, void *stream);

@@ -13,6 +13,7 @@
 #include "device_model.h"
 #include "dynamics.h"
 #include "internal.hpp"
+#include "link_state.h"
 #include "model.hpp"
 #include "raycast.h"
 #include "render.h"
@@ -62,6 +63,10 @@ struct TrexBatch {
   // dynamics queries (trex_batch_jacobian): body and body<-link transform of every URDF link, host side
   std::vector<int> link_body;
   std::vector<trex::Tf> link_tf;
+  // link kinematics (trex_batch_set_link_probes): per set the device table of its probes - body [K], then body<-link rotation and
+  // the point in the body frame [K][12]; freed by num_probes 0 and with the batch
+  struct ProbeSet { int n = 0; int32_t *body = nullptr; float *tf = nullptr; };
+  ProbeSet probes[TREX_LINK_SETS];
   // caller allocations already validated as memory of this device (base address, bytes known to be good):
   // the hot path pays one hash-free scan of a handful of entries, hipPointerGetAttributes only on a new one
   std::vector<TrexSeen> seen;
@@ -546,6 +551,10 @@ void trex_batch_destroy(TrexBatch *b) {
   (void)hipDeviceSynchronize();
   for (void *p : b->allocs) (void)hipFree(p);
   if (b->render_ids) (void)hipFree(b->render_ids);
+  for (auto &ps : b->probes) {
+    if (ps.body) (void)hipFree(ps.body);
+    if (ps.tf) (void)hipFree(ps.tf);
+  }
   delete b;
 }
 
@@ -1139,6 +1148,87 @@ int trex_batch_ray_test(TrexBatch *b, const float *rays_dev, int num_rays, int s
   a.body_mask = b->nb >= 32 ? body_mask : body_mask & ((1u << b->nb) - 1u);   // (bits beyond the model's bodies mean nothing)
   a.floor_z = (float)b->floor_z;
   HIP_TRY(trex_launch_ray_test(a, b->render_prim, b->render_plane, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+// ---- link kinematics (link_state.hip)
+int trex_batch_set_link_probes(TrexBatch *b, int set, const int32_t *link_host, const double *local_xyz_host, int num_probes) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (set < 0 || set >= TREX_LINK_SETS)
+    return fail(TREX_E_INVALID, "trex_batch_set_link_probes: set " + std::to_string(set) + " outside [0, " + std::to_string(TREX_LINK_SETS) + ")");
+  if (num_probes < 0 || num_probes > TREX_LINK_MAXPROBES)
+    return fail(TREX_E_INVALID, "trex_batch_set_link_probes: num_probes " + std::to_string(num_probes) + " outside [0, " +
+                                    std::to_string(TREX_LINK_MAXPROBES) + "]");
+  if (num_probes > 0 && (!link_host || !local_xyz_host)) return fail(TREX_E_INVALID, "trex_batch_set_link_probes: null argument");
+  std::vector<int32_t> body((size_t)num_probes);
+  std::vector<float> tf((size_t)num_probes * 12);
+  for (int k = 0; k < num_probes; k++) {
+    const int link = link_host[k];
+    if (link < 0 || link >= (int)b->link_body.size())
+      return fail(TREX_E_INVALID, "trex_batch_set_link_probes: probe " + std::to_string(k) + ": link " + std::to_string(link) +
+                                      " out of range [0, " + std::to_string(b->link_body.size()) + ")");
+    const double *x = local_xyz_host + 3 * (size_t)k;
+    for (int c = 0; c < 3; c++)
+      if (!std::isfinite(x[c]))
+        return fail(TREX_E_INVALID, "trex_batch_set_link_probes: probe " + std::to_string(k) + ": local_xyz is not finite");
+    // body <- link rotation, and the point in the frame of the link's body (as trex_batch_jacobian composes it)
+    const trex::Tf &t = b->link_tf[link];
+    const double tt[3] = {t.t.x, t.t.y, t.t.z};
+    body[k] = b->link_body[link];
+    for (int c = 0; c < 9; c++) tf[12 * (size_t)k + c] = (float)t.R.m[c];
+    for (int r = 0; r < 3; r++)
+      tf[12 * (size_t)k + 9 + r] = (float)(t.R.m[3 * r] * x[0] + t.R.m[3 * r + 1] * x[1] + t.R.m[3 * r + 2] * x[2] + tt[r]);
+  }
+  DeviceGuard guard(b->device);
+  int32_t *body_dev = nullptr;
+  float *tf_dev = nullptr;
+  if (num_probes > 0) {
+    HIP_TRY(hipMalloc((void **)&body_dev, body.size() * sizeof(int32_t)));
+    hipError_t e = hipMalloc((void **)&tf_dev, tf.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(body_dev, body.data(), body.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(tf_dev, tf.data(), tf.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(body_dev);
+      if (tf_dev) (void)hipFree(tf_dev);
+      return hip_fail(e, "trex_batch_set_link_probes: table");
+    }
+  }
+  HIP_TRY(hipDeviceSynchronize());   // (no launch still reads the table this one replaces; the new one is in place on every stream)
+  TrexBatch::ProbeSet &ps = b->probes[set];
+  if (ps.body) (void)hipFree(ps.body);
+  if (ps.tf) (void)hipFree(ps.tf);
+  ps.n = num_probes; ps.body = body_dev; ps.tf = tf_dev;
+  return TREX_OK;
+}
+
+int trex_batch_link_state(TrexBatch *b, int set, int axes, int proper, const float *accel_dev, float *pose_dev, float *velocity_dev,
+                          float *acceleration_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (set < 0 || set >= TREX_LINK_SETS)
+    return fail(TREX_E_INVALID, "trex_batch_link_state: set " + std::to_string(set) + " outside [0, " + std::to_string(TREX_LINK_SETS) + ")");
+  const TrexBatch::ProbeSet &ps = b->probes[set];
+  if (ps.n < 1) return fail(TREX_E_INVALID, "trex_batch_link_state: probe set " + std::to_string(set) + " is empty (trex_batch_set_link_probes)");
+  if (axes < TREX_AXES_WORLD || axes > TREX_AXES_BASE)
+    return fail(TREX_E_INVALID, "trex_batch_link_state: axes " + std::to_string(axes) + " outside 0..2");
+  if (!pose_dev && !velocity_dev && !acceleration_dev) return fail(TREX_E_INVALID, "trex_batch_link_state: all three outputs are null");
+  DeviceGuard guard(b->device);
+  const size_t nk = (size_t)b->n * ps.n;
+  if (acceleration_dev) BUF_TRY(accel_dev, (size_t)b->n * (6 + b->nj) * sizeof(float), "trex_batch_link_state: accel");
+  BUF_TRY(pose_dev, nk * 7 * sizeof(float), "trex_batch_link_state: pose");
+  BUF_TRY(velocity_dev, nk * 6 * sizeof(float), "trex_batch_link_state: velocity");
+  BUF_TRY(acceleration_dev, nk * 6 * sizeof(float), "trex_batch_link_state: acceleration");
+  TrexLinkArgs a{};
+  a.model = b->dmodel; a.base = b->arr.base; a.q = b->arr.q; a.qd = b->arr.qd;
+  a.accel = acceleration_dev ? accel_dev : nullptr;
+  a.probe_body = ps.body; a.probe_tf = ps.tf;
+  a.pose = pose_dev; a.vel = velocity_dev; a.acc = acceleration_dev;
+  a.n_envs = b->n; a.num_probes = ps.n; a.D = 6 + b->nj;
+  a.axes = axes; a.proper = proper != 0;
+  const trex::Tf &t0 = b->link_tf[0];   // URDF link 0's frame in its body
+  a.base_body = b->link_body[0];
+  for (int k = 0; k < 9; k++) a.base_tf[k] = (float)t0.R.m[k];
+  a.base_tf[9] = (float)t0.t.x; a.base_tf[10] = (float)t0.t.y; a.base_tf[11] = (float)t0.t.z;
+  HIP_TRY(trex_launch_link_state(a, (hipStream_t)stream));
   return TREX_OK;
 }
 

@@ -63,6 +63,23 @@ int main(int argc, char **argv) {
   for (int t = 0; t < steps; t++) CHECK(trex_batch_step(batch, act, obs, rew, done, nullptr, stream));
   hipStreamSynchronize(stream);
   double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  {
+    // Link kinematics: the base link as an IMU mounted at its origin sees it - pose in the world, velocity and specific force
+    // (gravity included, joint accelerations taken as zero) in the link's own axes - for every env in one launch.
+    const int32_t probe_link[1] = {0};
+    const double probe_xyz[3] = {0.0, 0.0, 0.0};
+    float *pose, *vel, *acc, h[19];
+    if (hipMalloc(&pose, sizeof(float) * n * 7) || hipMalloc(&vel, sizeof(float) * n * 6) || hipMalloc(&acc, sizeof(float) * n * 6)) return 1;
+    CHECK(trex_batch_set_link_probes(batch, 0, probe_link, probe_xyz, 1));
+    CHECK(trex_batch_link_state(batch, 0, TREX_AXES_LINK, 1, nullptr, pose, vel, acc, stream));
+    hipStreamSynchronize(stream);
+    hipMemcpy(h, pose, 7 * sizeof(float), hipMemcpyDeviceToHost);
+    hipMemcpy(h + 7, vel, 6 * sizeof(float), hipMemcpyDeviceToHost);
+    hipMemcpy(h + 13, acc, 6 * sizeof(float), hipMemcpyDeviceToHost);
+    std::printf("env 0 base link: at %.3f %.3f %.3f, gyro %.3f %.3f %.3f rad/s, accelerometer (static) %.3f %.3f %.3f m/s^2\n", h[0], h[1],
+                h[2], h[10], h[11], h[12], h[13], h[14], h[15]);
+    hipFree(pose); hipFree(vel); hipFree(acc);
+  }
   std::vector<float> o(3 * J);
   float r0;
   hipMemcpy(o.data(), obs, o.size() * sizeof(float), hipMemcpyDeviceToHost);

@@ -44,6 +44,7 @@ SYMBOLS = [
     "trex_batch_set_control_mode", "trex_batch_set_motor_gains", "trex_batch_set_stiffness_actions",
     "trex_batch_inverse_dynamics", "trex_batch_mass_matrix", "trex_batch_jacobian", "trex_batch_centroidal",
     "trex_batch_forward_dynamics", "trex_batch_solve_mass", "trex_batch_ray_test",
+    "trex_batch_set_link_probes", "trex_batch_link_state",
 ]
 
 # every symbol include/trex_policy.h declares (the trainer-side kernels)
@@ -110,6 +111,9 @@ if hasattr(lib, "trex_batch_forward_dynamics"):
     lib.trex_batch_solve_mass.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
 if hasattr(lib, "trex_batch_ray_test"):
     lib.trex_batch_ray_test.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, _vp]
+if hasattr(lib, "trex_batch_link_state"):
+    lib.trex_batch_set_link_probes.argtypes = [_vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int]
+    lib.trex_batch_link_state.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]
 lib.trex_model_use_primitive_collision.argtypes = [_vp, C.c_double, C.c_int, C.c_int]
 lib.trex_model_fit_hull_primitives.argtypes = [_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
 lib.trex_model_num_links.argtypes = [_vp]
@@ -523,6 +527,37 @@ class Batch:
         check(lib.trex_batch_jacobian(self.h, int(link), xyz, self._p(out, "float32", self.num_envs * 6 * D, "out"),
                                       self._stream(stream)))
         return out
+
+    def set_link_probes(self, set, links, positions=None):
+        """Probe set `set` (0..7) <- the points `positions` [K, 3] (link frames; None = the link origins) of the URDF link
+        indices `links` [K] (trex_batch_set_link_probes); an empty `links` frees the set. Host values, shared by all envs."""
+        links = np.ascontiguousarray(np.asarray(links, dtype=np.int64).reshape(-1))
+        K = int(links.size)
+        if K and (links.min() < np.iinfo(np.int32).min or links.max() > np.iinfo(np.int32).max):
+            raise TrexError(E_INVALID, "links: expected link indices")
+        links = links.astype(np.int32)
+        pos = np.zeros((K, 3)) if positions is None else np.ascontiguousarray(np.asarray(positions, dtype=np.float64))
+        if pos.shape != (K, 3):
+            raise TrexError(E_INVALID, "positions: expected shape %s, got %s" % ((K, 3), pos.shape))
+        check(lib.trex_batch_set_link_probes(self.h, int(set), links.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             pos.ctypes.data_as(C.POINTER(C.c_double)), K))
+
+    def link_state(self, set, axes=0, proper=False, accel=None, pose=None, velocity=None, acceleration=None, stream=None, probes=None):
+        """Kinematics of the probes of set `set` at the current state (trex_batch_link_state): pose [n, K, 7], velocity and
+        acceleration [n, K, 6] f32 device tensors, each optional, written in place; accel [n, D] or None = zeros. axes: 0 world,
+        1 link, 2 base; proper: + g z on the linear acceleration. probes: K, where the caller knows it - the sizes the buffers
+        are checked against before the call (the library checks them against the set's size either way)."""
+        n, D = self.num_envs, 6 + self.J
+        if accel is not None and tuple(accel.shape) != (n, D):
+            raise TrexError(E_INVALID, "accel: expected shape %s, got %s" % ((n, D), tuple(accel.shape)))
+        K = None if probes is None else int(probes)
+        def ptr(t, width, what):
+            if t is not None and K is not None and tuple(t.shape) != (n, K, width):
+                raise TrexError(E_INVALID, "%s: expected shape %s, got %s" % (what, (n, K, width), tuple(t.shape)))
+            return self._p(t, "float32", 0 if t is None or K is None else n * K * width, what)
+        check(lib.trex_batch_link_state(self.h, int(set), int(axes), 1 if proper else 0, self._p(accel, "float32", n * D, "accel"),
+                                        ptr(pose, 7, "pose"), ptr(velocity, 6, "velocity"), ptr(acceleration, 6, "acceleration"),
+                                        self._stream(stream)))
 
     def centroidal(self, out=None, stream=None):
         """[n, 16]: COM position, COM velocity, linear momentum, angular momentum about the COM, kinetic energy, potential

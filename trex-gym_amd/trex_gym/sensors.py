@@ -6,6 +6,10 @@ world's), shared by every env: the batch evaluates the frame at each env's curre
     fan         a lidar fan: n_yaw x n_pitch rays of one length from one origin
     grid_down   a height scanner: nx x ny vertical rays
     RaySensor   a pattern on a link of an env; read() -> distances [n, R] in metres
+
+An inertial sensor on the same env (TrexVecEnv.link_state / trex_batch_link_state):
+
+    Imu         accelerometer + gyro at a point of a link; read() -> (specific force, angular velocity) in the link's axes
 """
 import math
 
@@ -63,3 +67,51 @@ class RaySensor:
     def read(self):
         """[n, R] distances in metres along each ray to what it hits; the ray's full length where it hits nothing."""
         return self.cast()[0] * self.length
+
+
+class Imu:
+    """An accelerometer and a gyro at `position` (link frame) of link `link` (name or index) of a TrexVecEnv. It holds one of
+    the env's probe sets until close()."""
+
+    def __init__(self, env, link, position=(0.0, 0.0, 0.0)):
+        self.env = env
+        self.probes = env.link_probes(link, [float(x) for x in position])
+        self.gravity = float(env.model.get_param("gravity"))
+        self.interval = float(env.model.get_param("substeps")) * float(env.model.get_param("dt"))   # seconds per env-step
+        self._last_v = None   # [n, 3] world velocity of the point at the previous read()
+
+    def close(self):
+        self.probes.close()
+
+    def static(self):
+        """(specific_force [n, 3], angular_velocity [n, 3]) in link axes at the current state with the joint and base
+        accelerations taken as zero: gravity, centripetal and Coriolis terms only. At rest: the link's view of (0, 0, g)."""
+        s = self.env.link_state(self.probes, accel=None, axes="link", proper=True, velocity=True, acceleration=True)
+        return s.linear_acceleration[:, 0], s.angular_velocity[:, 0]
+
+    def read(self, done=None):
+        """(specific_force [n, 3], angular_velocity [n, 3]) in link axes. The specific force is the change of the point's world
+        velocity since the previous read(), over one env-step (substeps x dt), plus g z, in the link's current axes: what an
+        accelerometer integrates over the env-step, contact impulses included. On the first call, and for the envs whose `done`
+        ([n], bool or uint8: their episode has just been restarted) is set, static()'s values: no difference is taken across
+        an episode boundary. Call it once after every step."""
+        f0, gyro = self.static()
+        w = self.env.link_state(self.probes, axes="world", velocity=True)
+        v = w.linear_velocity[:, 0]
+        if self._last_v is None:
+            force = f0
+        else:
+            a = (v - self._last_v) / self.interval
+            a[:, 2] += self.gravity
+            force = (quat_rotate_inverse(w.orientation[:, 0], a))
+            if done is not None:
+                force = torch.where(torch.as_tensor(done, device=force.device).bool().view(-1, 1), f0, force)
+        self._last_v = v.clone()
+        return force, gyro
+
+
+def quat_rotate_inverse(q, v):
+    """R(q)^T v for unit quaternions q [..., 4] xyzw: a world vector in the axes of the frame q orients."""
+    u, w = -q[..., :3], q[..., 3:]
+    t = 2.0 * torch.cross(u, v, dim=-1)
+    return v + w * t + torch.cross(u, t, dim=-1)

@@ -157,6 +157,26 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
         """[6, 6] task-space inertia inv(J M^-1 J^T) of a point of a link (as jacobian())."""
         return self._vec.operational_space_inertia(link, position)[0].cpu().numpy()
 
+    def link_state(self, probes, accel=None, axes="world", proper=False, velocity=True, acceleration=False):
+        """TrexVecEnv.link_state of the one env, as a LinkState of numpy arrays: position [K, 3], orientation [K, 4] xyzw, and -
+        where asked for - linear / angular velocity and acceleration [K, 3]; probes: a link, a list of links, or a handle of
+        link_probes(). NOT pybullet's getLinkState tuple: its entries 0..3 are poses of the link's INERTIAL frame, and the model
+        keeps no inertial frame for a link merged into its parent across a fixed joint, so they cannot be honoured. The pose here
+        is the URDF link frame's (getLinkState's entries 4, 5); the velocities are those of the probe point and the link."""
+        from .vec_env import LinkState
+        if accel is not None:
+            accel = np.asarray(accel, np.float32).reshape(1, -1)
+        s = self._vec.link_state(probes, accel, axes, proper, velocity, acceleration)
+        return LinkState(*[None if t is None else t[0].cpu().numpy() for t in s])
+
+    def link_probes(self, links, positions=None):
+        """A handle for points fixed in links (TrexVecEnv.link_probes), for link_state()."""
+        return self._vec.link_probes(links, positions)
+
+    def bias_acceleration(self, link, position=None):
+        """[6] = Jdot qd of a point of a link (as jacobian(), in its row order)."""
+        return self._vec.bias_acceleration(link, position)[0].cpu().numpy()
+
     # pybullet's body ids of this world: the robot and the floor (the ids are this env's own - the reference loads the floor first)
     ROBOT_ID, FLOOR_ID = 0, 1
 

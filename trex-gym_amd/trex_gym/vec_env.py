@@ -16,6 +16,7 @@ into it; `done` holds the flags as bool, `penalties` [n, 3] the three reward ter
 Multi-GPU: one process per GPU, env ids sharded by contiguous range (trex_gym.sharding); the only
 exchange is the all-gather of that row block (all_gather_rows / all_gather_rows_pipelined).
 """
+import collections
 import time
 
 import numpy as np
@@ -34,6 +35,30 @@ class Centroidal:
         self.com, self.com_velocity = data[..., 0:3], data[..., 3:6]
         self.momentum, self.angular_momentum = data[..., 6:9], data[..., 9:12]
         self.kinetic, self.potential, self.mass = data[..., 12], data[..., 13], data[..., 14]
+
+
+LinkState = collections.namedtuple("LinkState", "position orientation linear_velocity angular_velocity linear_acceleration "
+                                                "angular_acceleration")
+AXES = {"world": 0, "link": 1, "base": 2}
+
+
+class LinkProbes:
+    """A set of points fixed in URDF links, held on the device by a TrexVecEnv (TrexVecEnv.link_probes): what link_state()
+    evaluates in one launch. links: the link indices [K]; positions: [K, 3] in the link frames. close() gives the env's set slot
+    back (an env holds 8)."""
+
+    def __init__(self, env, slot, links, positions):
+        self.env, self.slot = env, slot
+        self.links, self.positions = links, positions
+        self.num_probes = len(links)
+
+    def close(self):
+        if self.slot is not None:
+            self.env._release_probes(self)
+            self.slot = None
+
+    def __len__(self):
+        return self.num_probes
 
 
 class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surface is baselines' VecEnv
@@ -117,6 +142,8 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         self._wrench = None                     # the caller's external wrench [n, num_bodies, 6] (None: none)
         self._link_table = None
         self._ray_out = (None, None)            # ray_test's output buffers of the last (R, positions, normals)
+        self._probe_sets = [None] * 8           # the LinkProbes handle in each of the batch's probe-set slots
+        self._probe_cache = (None, None)        # link_state()'s one-off set of the last links given directly
         self.pushes = pushes
         if pushes is not None and pushes.num_envs != n:
             raise ValueError("pushes: RandomPushes over %d envs, the env has %d" % (pushes.num_envs, n))
@@ -470,6 +497,83 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         launch, one solve launch and a batched 6 x 6 inverse."""
         Jm = self.jacobian(link, position)
         return torch.linalg.inv(Jm @ self.batch.solve_mass(Jm).transpose(1, 2))
+
+    # ---- link kinematics (trex_batch_set_link_probes / trex_batch_link_state; one launch for all probes, no host sync)
+    def link_probes(self, links, positions=None):
+        """A LinkProbes handle for the points `positions` [K, 3] (link frames; None: the link origins) of the links `links` (K
+        names or indices, or one). It takes one of the env's 8 probe-set slots until its close(); RuntimeError when none is free."""
+        from .perturb import LinkTable
+        if self._link_table is None:
+            self._link_table = LinkTable.from_model(self.model)
+        if isinstance(links, (str, int, np.integer)):
+            links = [links]
+            if positions is not None:
+                positions = np.asarray(positions, np.float64).reshape(1, 3)
+        idx = [self._link_table.index(l) for l in links]
+        pos = np.zeros((len(idx), 3)) if positions is None else np.asarray(positions, np.float64)
+        if pos.shape != (len(idx), 3):
+            raise ValueError("positions must have shape (%d, 3), got %s" % (len(idx), pos.shape))
+        if not idx:
+            raise ValueError("link_probes: no link given")
+        free = [k for k, h in enumerate(self._probe_sets) if h is None]
+        if not free:
+            raise RuntimeError("link_probes: all %d probe sets of this env are in use; close() one first" % len(self._probe_sets))
+        self.batch.set_link_probes(free[0], idx, pos)
+        h = LinkProbes(self, free[0], idx, pos)
+        self._probe_sets[free[0]] = h
+        return h
+
+    def _release_probes(self, h):
+        if self._probe_sets[h.slot] is h:
+            self.batch.set_link_probes(h.slot, [])
+            self._probe_sets[h.slot] = None
+        if self._probe_cache[1] is h:
+            self._probe_cache = (None, None)
+
+    def link_state(self, probes, accel=None, axes="world", proper=False, velocity=True, acceleration=False):
+        """Kinematics of the K probes of `probes` - a LinkProbes handle, or a link / a list of links (their origins; kept as a
+        one-off set until other links are given) - at the current state, as a LinkState of device tensors:
+        position [n, K, 3] of the points and orientation [n, K, 4] (xyzw, w >= 0) of their link frames; with `velocity`
+        linear_velocity of the points and angular_velocity of the links; with `acceleration` linear_acceleration (classical,
+        d2p/dt2) and angular_acceleration at the generalised accelerations accel [n, D] (None: zeros - the bias acceleration
+        Jdot qd). Parts not asked for are None.
+        axes: "world", "link" (each probe's own link frame) or "base" (URDF link 0's frame): the axes the velocities and
+        accelerations - still relative to the world - are expressed in; with "base" the pose is relative to that frame too.
+        proper: + g z (world) on the linear acceleration: the specific force an accelerometer at the point reads."""
+        if axes not in AXES:
+            raise ValueError("axes must be one of %s" % sorted(AXES))
+        if not isinstance(probes, LinkProbes):
+            key = tuple(probes) if isinstance(probes, (list, tuple)) else (probes,)
+            if self._probe_cache[0] != key:
+                if self._probe_cache[1] is not None:
+                    self._probe_cache[1].close()
+                self._probe_cache = (key, self.link_probes(list(key)))
+            probes = self._probe_cache[1]
+        if probes.env is not self or probes.slot is None:
+            raise ValueError("link_state: the probes are closed or belong to another env")
+        n, K = self.num_envs, probes.num_probes
+        if accel is not None:
+            accel = torch.as_tensor(accel).to(device=self.device, dtype=torch.float32).contiguous()
+        pose = torch.empty(n, K, 7, device=self.device)
+        vel = torch.empty(n, K, 6, device=self.device) if velocity else None
+        acc = torch.empty(n, K, 6, device=self.device) if acceleration else None
+        self.batch.link_state(probes.slot, AXES[axes], proper, accel, pose, vel, acc, probes=K)
+        return LinkState(pose[..., :3], pose[..., 3:], None if vel is None else vel[..., :3], None if vel is None else vel[..., 3:],
+                         None if acc is None else acc[..., :3], None if acc is None else acc[..., 3:])
+
+    def bias_acceleration(self, link, position=None):
+        """[n, 6] = Jdot qd of the point `position` of link `link` (as jacobian(), and in its row order: linear, angular; world
+        axes): the point's acceleration at zero generalised accelerations - with operational_space_inertia(), jacobian() and
+        inverse_dynamics() what a task-space controller needs."""
+        key = ("bias", link, None if position is None else tuple(float(x) for x in position))
+        if self._probe_cache[0] != key:
+            if self._probe_cache[1] is not None:
+                self._probe_cache[1].close()
+            self._probe_cache = (key, self.link_probes(link, position))
+        h = self._probe_cache[1]
+        acc = torch.empty(self.num_envs, 1, 6, device=self.device)
+        self.batch.link_state(h.slot, 0, False, None, None, None, acc, probes=1)
+        return acc[:, 0]
 
     # ---- ray casts (trex_batch_ray_test: pybullet's rayTestBatch; no host sync; trex_gym.sensors builds patterns)
     def ray_test(self, rays, link=None, positions=False, normals=False, bodies=None, floor=True):

@@ -33,8 +33,8 @@ __device__ __forceinline__ unsigned char to_u8(float c) {
 }  // namespace
 
 __global__ __launch_bounds__(256) void trex_render_kernel(TrexRenderArgs a) {
-  __shared__ float sPose[TL][12];          // world R (row-major) | p of every body of the view's env
-  __shared__ float4 sSph[MAXPRIM];         // world bounding sphere of the culled primitives, list order
+  __shared__ float sPose[TL][12];          // world R (row-major) | p - base position of every body of the view's env
+  __shared__ float4 sSph[MAXPRIM];         // bounding sphere of the culled primitives (as p), list order
   __shared__ int sList[MAXPRIM];           // primitive index, ascending
   __shared__ int sKeep[MAXPRIM];
   __shared__ int sCount;
@@ -45,16 +45,20 @@ __global__ __launch_bounds__(256) void trex_render_kernel(TrexRenderArgs a) {
   const int t = threadIdx.x;
   const float *b = a.base + (size_t)env * 16;
 
-  // ---- body poses: lane t < nb composes the base pose with the hinges of its chain (render_pose.h)
+  // ---- body poses: lane t < nb composes the base pose with the hinges of its chain (render_pose.h). Everything the rays meet
+  // is held RELATIVE TO THE BASE POSITION - poses, bounding spheres, the eye, the floor: in world coordinates an env 64 m from
+  // the origin loses 8 bits of every one of them (one ulp there is 4e-6 m), and an oblique facet turns that into 1e-4 of depth
   if (t < M->nb) {
-    TREX_BODY_WORLD_POSE(M, b, a.q, env, t, R, p)
+    const float br[7] = {0.f, 0.f, 0.f, b[3], b[4], b[5], b[6]};
+    TREX_BODY_WORLD_POSE(M, br, a.q, env, t, R, p)
     for (int c = 0; c < 9; c++) sPose[t][c] = R[c];
     for (int c = 0; c < 3; c++) sPose[t][9 + c] = p[c];
   }
 
   // ---- camera of this view
   float eye[3];
-  for (int c = 0; c < 3; c++) eye[c] = (a.follow_base ? b[c] : a.target[c]) + a.offset[c];
+  for (int c = 0; c < 3; c++) eye[c] = (a.follow_base ? 0.f : a.target[c] - b[c]) + a.offset[c];
+  const float floor_z = a.floor_z - b[2];
   const int tx = blockIdx.x % a.tiles_x, ty = blockIdx.x / a.tiles_x;
   const float invW = 2.f / (float)a.width, invH = 2.f / (float)a.height;
   __syncthreads();
@@ -114,8 +118,8 @@ __global__ __launch_bounds__(256) void trex_render_kernel(TrexRenderArgs a) {
   // nearest hit so far: t = eye-space depth; kind -2 nothing, -1 floor, >= 0 list entry; `pl` the hull plane that was entered
   float best = valid ? a.far_z : -1.f;   // (an invalid lane never hits anything)
   int hit = -2, pl = -1;
-  if (dir[2] < 0.f || eye[2] < a.floor_z) {   // floor: the half-space z <= floor_z
-    const float tf = eye[2] < a.floor_z ? a.near_z : fmaxf((a.floor_z - eye[2]) / dir[2], a.near_z);
+  if (dir[2] < 0.f || eye[2] < floor_z) {   // floor: the half-space z <= floor_z
+    const float tf = eye[2] < floor_z ? a.near_z : fmaxf((floor_z - eye[2]) / dir[2], a.near_z);
     if (tf < best) { best = tf; hit = -1; }
   }
 
@@ -186,7 +190,7 @@ __global__ __launch_bounds__(256) void trex_render_kernel(TrexRenderArgs a) {
     const float *alb;
     if (hit == -1) {
       seg = -1;
-      const int parity = ((int)floorf(hp[0]) + (int)floorf(hp[1])) & 1;
+      const int parity = ((int)floorf(hp[0] + b[0]) + (int)floorf(hp[1] + b[1])) & 1;   // (the checker is the world's)
       alb = parity ? kFloorB : kFloorA;
     } else {
       const int pi = sList[hit];

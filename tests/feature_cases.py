@@ -12,6 +12,9 @@ candidate / seed; nothing is loosened.
 Wrench magnitude: doubled from START_SHARE of the model's weight until the f64 oracle's rates with and without the wrench differ
 by >= EFFECT x the qd tolerance of assert_step_close; a case in which a generalised velocity then reaches VEL_SHARE of
 max_coordinate_velocity is replaced.
+The groups warm_fallen and wrench_fallen start from the fallen states of tests/episode_cases.py (multi_step: every eighth accepted
+case of a 1000-step random-action episode, held for 3 env-steps): the root body and the cranium on the floor, contact sets that
+change from solve to solve; wrench_fallen pushes exactly those two bodies.
 """
 import os
 
@@ -316,6 +319,18 @@ def groups(directory):
     sep = [c for c in a if c.get("separates")]
     cs = [dict(make_wrench_case(t, sep, 2 * k, random_all(t), 500 + k, warm=WARM, steps=3), what="warm + random wrench %d" % k) for k in range(2)]
     out["wrench_warm"] = dict(built=t, warm=WARM, cases=cs, kind="wrench")
+    # ---- warm (f), wrench (f): from the fallen states of a 1000-step episode under random actions (tests/episode_cases.py) - the
+    # T-rex on its side or back, root body and cranium on the floor, contact sets that change from solve to solve
+    import episode_cases as ec
+    root, cranium = ec.body(t.om, ec.ROOT), ec.body(t.om, ec.CRANIUM)
+    out["warm_fallen"] = dict(built=t, warm=WARM, cases=pick_warm(t, ec.multi_step(WARM)[1], WARM, 48, n_plain=8, n_air=8), kind="warm")
+
+    def root_and_cranium(rng):
+        w = one_hot(t.nb, root, slice(0, 3), unit(rng)) + one_hot(t.nb, root, slice(3, 6), 0.3 * unit(rng))
+        return w + one_hot(t.nb, cranium, slice(0, 3), 0.3 * unit(rng)) + one_hot(t.nb, cranium, slice(3, 6), 0.1 * unit(rng))
+    down = [c for c in ec.multi_step(0.0)[1] if c["in_contact"]]
+    cs = [dict(make_wrench_case(t, down, 3 * k, root_and_cranium, 800 + k, steps=3), what="root and cranium wrench %d" % k) for k in range(12)]
+    out["wrench_fallen"] = dict(built=t, warm=0.0, cases=cs, kind="wrench")
     # ---- containment through set_state: the f64 oracle's state after one warm step, rounded to f32, set again (which empties
     # every record) with env CONTAINED's state made non-finite by the test: that env continues from the oracle's reset
     after = []

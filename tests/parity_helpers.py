@@ -29,11 +29,12 @@ def assert_step_close(g_obs, o_obs, g_rew=None, o_rew=None, what="", q_atol=1e-4
         assert abs(g_rew - o_rew) <= 2e-3 * abs(o_rew) + 1e-3 + 0.1 * energy_tol, (what, g_rew, o_rew)
 
 
-def oracle_wrench(orc, model, state, action, mass_scale=None, friction=None, oracle_state=None):
+def oracle_wrench(orc, model, state, action, mass_scale=None, friction=None, oracle_state=None, counts=None):
     """One env-step restated on the oracle: the clipped action as the joint targets, motors on, `substeps` substeps; per
     substep the contact points (body, lambda = (normal, x, y) - the oracle's row order - and world point) with the body COMs
     of the pose the rows were built at (body_poses BEFORE the substep + R com). Returns the mean wrench [nb, 6] and the touched
-    bodies. oracle_state: step THAT oracle state on, in place (state, mass_scale and friction are then not used)."""
+    bodies. oracle_state: step THAT oracle state on, in place (state, mass_scale and friction are then not used).
+    counts: a list that receives the number of contact points of every substep."""
     oo, nb = model["obs_order"], model["nb"]
     s = oracle_state
     if s is None:
@@ -51,6 +52,8 @@ def oracle_wrench(orc, model, state, action, mass_scale=None, friction=None, ora
         com = pos + np.einsum("bij,bj->bi", rot, model["com"])
         orc.substep(s, target)
         body, lam, pt, _ = orc.contacts(s)
+        if counts is not None:
+            counts.append(len(body))
         for b, l, p in zip(body, lam, pt):
             f = np.array([l[1], l[2], l[0]])
             W[b, :3] += f

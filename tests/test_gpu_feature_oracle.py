@@ -5,7 +5,8 @@ Per env and env-step: parity_helpers.assert_step_close at its stated tolerances 
 in tests/test_gpu_synthetic_models.py), the reward, the contact count; with the contact sensor on also the per-body contact wrench
 at the rule of tests/test_gpu_contact_wrench.py::test_sensor_matches_the_oracle (4 x the f32 oracle's spread over the group, floor
 1e-3 M g) - the impulses themselves, not only what they do to qd. Every group runs in the pair form (even batch) and padded to an
-odd batch (single-env form). Measured deviations: profiles/r15_feature_oracle.txt."""
+odd batch (single-env form). Measured deviations: profiles/r15_feature_oracle.txt; the groups warm_fallen and wrench_fallen (from
+the fallen states of tests/episode_cases.py): profiles/r18_episode_states.txt."""
 import numpy as np
 import pytest
 import torch
@@ -16,7 +17,7 @@ from parity_helpers import assert_step_close
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 GROUPS = ["warm_trex", "warm_factor_1.0", "warm_factor_0.3", "warm_slab", "warm_many_hulls", "warm_max_contacts_4", "warm_margin_0.5",
-          "warm_primitives", "wrench_trex", "wrench_deep_chain", "wrench_bushy", "wrench_warm"]
+          "warm_primitives", "wrench_trex", "wrench_deep_chain", "wrench_bushy", "wrench_warm", "warm_fallen", "wrench_fallen"]
 
 
 @pytest.fixture(scope="module")

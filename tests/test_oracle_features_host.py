@@ -233,6 +233,39 @@ def test_warm_cases_tell_warm_from_cold(groups):
     assert 2 * sep >= total
 
 
+def test_fallen_groups_are_what_they_claim(groups):
+    """warm_fallen / wrench_fallen (from tests/episode_cases.py): the root body and the cranium touch, the contact set changes
+    between the env-steps of a case, and the record is live - warm and cold give different rates in most cases in contact. (On
+    these thrashing states, rates of 14 rad/s and a tolerance that scales with them, warm and cold seldom separate by
+    assert_step_close: they are here for the record lookup under churning contact sets, and stay out of the share that
+    test_warm_cases_tell_warm_from_cold asserts.) The wrench acts on exactly the root body and the cranium."""
+    import episode_cases as ec
+    g = groups["warm_fallen"]
+    b = g["built"]
+    root, cranium = ec.body(b.om, ec.ROOT), ec.body(b.om, ec.CRANIUM)
+    exp = fc.expected(g)
+    n_root = sum(any(root in x["touched"] for x in e) for e in exp)
+    n_cranium = sum(any(cranium in x["touched"] for x in e) for e in exp)
+    churn = sum(e[i]["cnt"] != e[i + 1]["cnt"] or e[i]["touched"] != e[i + 1]["touched"] for e in exp for i in range(len(e) - 1))
+    live = sep = total = 0
+    for c, e in zip(g["cases"], exp):
+        if not any(x["cnt"] for x in e):
+            continue
+        cold = fc.run(b.o64, b.om, c, 0.0)
+        total += 1
+        live += any(not np.array_equal(x["obs"], y["obs"]) for x, y in zip(cold, e))
+        sep += any(not fc.close(b, x, y) for x, y in zip(cold, e))
+    print("warm_fallen: %d cases, root body touches in %d, cranium in %d, contact set changes between env-steps %d times; "
+          "warm != cold in %d of %d in contact, beyond assert_step_close in %d" % (len(exp), n_root, n_cranium, churn, live, total, sep))
+    assert len(exp) == 48 and max(c["up"] for c in g["cases"]) < 0.91 and n_root >= 10 and n_cranium >= 5 and churn >= 10
+    assert total >= 30 and 2 * live >= total       # (a point that lives for one solve only meets no record: those cases start cold)
+    w = groups["wrench_fallen"]
+    assert len(w["cases"]) == 12
+    for c in w["cases"]:
+        assert set(np.flatnonzero(np.abs(c["wrench"]).max(1) > 0)) == {root, cranium}
+    assert sum(any(root in x["touched"] for x in e) for e in fc.expected(w)) >= 6
+
+
 def test_wrenches_are_large_enough_and_bounded(groups):
     for name, g in groups.items():
         if g["kind"] != "wrench":

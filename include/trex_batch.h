@@ -486,6 +486,43 @@ int trex_batch_set_link_probes(TrexBatch *batch, int set, const int32_t *link_ho
 int trex_batch_link_state(TrexBatch *batch, int set, int axes, int proper, const float *accel_dev,
                           float *pose_dev, float *velocity_dev, float *acceleration_dev, void *stream);
 
+/* ---- proximity between bodies (what users take from pybullet's getClosestPoints between links of the robot: a self-collision
+ *      penalty or termination, leg-to-leg and tail-to-leg clearance as an observation, a filter on sampled poses; the step itself
+ *      collides the bodies with the floor only)
+ *
+ * Geometry: capsules fixed in bodies - the primitive trex_model_fit_hull_primitives fits to the hulls; a sphere is a capsule of
+ * length 0. The distance of two capsules is closed-form (segment to segment, minus the radii): no iteration.
+ *
+ * The table, one per batch: body_host [C] the body of each capsule, capsule_host [C, 7] = p0 xyz, p1 xyz, radius in that body's
+ * frame (the layout of trex_model_fit_hull_primitives), pair_host [P, 2] the bodies (A, B) of each pair to report. HOST arrays,
+ * shared by all envs, validated here and copied into batch-owned device memory. TREX_E_INVALID with nothing changed: C outside
+ * [0, 256] or P outside [1, 1024]; a body outside [0, num_bodies); a non-finite coordinate, a non-finite or negative radius; a
+ * pair with A == B; a pair one of whose bodies has no capsule; more than 65536 capsule-pair tests in all (the sum over the pairs
+ * of capsules(A) x capsules(B)). A capsule with |p1 - p0|^2 < 1e-12 m^2 is stored as a sphere (p1 = p0); coordinates are rounded
+ * to f32. num_capsules 0 frees the table (the arrays may then be NULL). Synchronous: it waits for the device before it replaces
+ * or frees the table (not inside a capture), like trex_batch_set_link_probes. */
+int trex_batch_set_proximity_shapes(TrexBatch *batch, const int32_t *body_host, const double *capsule_host, int num_capsules,
+                                    const int32_t *pair_host, int num_pairs);
+
+/* For every env and pair: the closest capsule of A and capsule of B at the env's current state. With a on the axis of A's capsule
+ * and b on the axis of B's realising the smallest segment-to-segment distance:
+ *   normal_dev   [N, P, 3]  n = (a - b) / |a - b|: from B to A (pybullet's contactNormalOnB); (0, 0, 1) where |a - b| < 1e-6 m
+ *                           (crossing axes, concentric spheres) - the points and the distance follow the same formulas there
+ *   distance_dev [N, P]     |a - b| - rA - rB: negative when the capsules overlap, then the depth. Required.
+ *   point_a_dev  [N, P, 3]  a - rA n, on A's surface, world coordinates
+ *   point_b_dev  [N, P, 3]  b + rB n, on B's surface: (point_a - point_b) . n = distance
+ *   capsule_dev  [N, P, 2]  i32: the table index of the winning capsule of A, of B
+ * Every output but distance_dev is nullable. Among capsule pairs of equal distance the one earlier in (capsule of A, capsule of B)
+ * table order wins; two calls on the same state are bitwise equal; the row of a pair does not depend on which other pairs the
+ * table holds, the row of an env not on N. There is no distance threshold: every pair of the table is reported.
+ * It behaves like the queries above: asynchronous and ordered on `stream`, every device buffer validated (TREX_E_INVALID before
+ * anything is launched), nothing allocated or waited for, nothing written but the outputs, from the second call with known
+ * buffers ONE plain kernel launch, usable inside a single-stream capture. TREX_E_INVALID when no table is set or distance_dev is
+ * NULL. A non-finite state makes that env's distances, points and normals unspecified - its capsule_dev entries still name
+ * capsules of the pair's bodies - and leaves every other env bitwise as without it. */
+int trex_batch_proximity(TrexBatch *batch, float *distance_dev, float *point_a_dev, float *point_b_dev, float *normal_dev,
+                         int32_t *capsule_dev, void *stream);
+
 /* diagnostics of the last substep: contact count per env [N] i32 (nullable), summed normal
  * impulse per env [N] f32 (nullable). */
 int trex_batch_contact_stats(TrexBatch *batch, int32_t *count_dev, float *normal_impulse_dev, void *stream);

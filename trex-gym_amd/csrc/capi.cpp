@@ -15,6 +15,7 @@
 #include "internal.hpp"
 #include "link_state.h"
 #include "model.hpp"
+#include "proximity.h"
 #include "raycast.h"
 #include "render.h"
 #include "step_launch.h"
@@ -67,6 +68,13 @@ struct TrexBatch {
   // the point in the body frame [K][12]; freed by num_probes 0 and with the batch
   struct ProbeSet { int n = 0; int32_t *body = nullptr; float *tf = nullptr; };
   ProbeSet probes[TREX_LINK_SETS];
+  // proximity queries (trex_batch_set_proximity_shapes): ONE device allocation holding the capsules [C][8], their bodies [C], the
+  // capsule-pair tests [T] and each pair's first test [P]; freed by num_capsules 0 and with the batch
+  struct ProxTable {
+    int caps = 0, pairs = 0, tests = 0;
+    void *blob = nullptr;
+    const float *cap = nullptr; const int32_t *cap_body = nullptr; const uint32_t *test = nullptr; const int32_t *pair_first = nullptr;
+  } prox;
   // caller allocations already validated as memory of this device (base address, bytes known to be good):
   // the hot path pays one hash-free scan of a handful of entries, hipPointerGetAttributes only on a new one
   std::vector<TrexSeen> seen;
@@ -555,6 +563,7 @@ void trex_batch_destroy(TrexBatch *b) {
     if (ps.body) (void)hipFree(ps.body);
     if (ps.tf) (void)hipFree(ps.tf);
   }
+  if (b->prox.blob) (void)hipFree(b->prox.blob);
   delete b;
 }
 
@@ -1229,6 +1238,109 @@ int trex_batch_link_state(TrexBatch *b, int set, int axes, int proper, const flo
   for (int k = 0; k < 9; k++) a.base_tf[k] = (float)t0.R.m[k];
   a.base_tf[9] = (float)t0.t.x; a.base_tf[10] = (float)t0.t.y; a.base_tf[11] = (float)t0.t.z;
   HIP_TRY(trex_launch_link_state(a, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+// ---- proximity queries (proximity.hip)
+int trex_batch_set_proximity_shapes(TrexBatch *b, const int32_t *body_host, const double *capsule_host, int num_capsules,
+                                    const int32_t *pair_host, int num_pairs) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  const char *me = "trex_batch_set_proximity_shapes: ";
+  if (num_capsules < 0 || num_capsules > TREX_PROX_MAXCAPS)
+    return fail(TREX_E_INVALID, me + ("num_capsules " + std::to_string(num_capsules)) + " outside [0, " + std::to_string(TREX_PROX_MAXCAPS) + "]");
+  std::vector<float> cap((size_t)num_capsules * 8, 0.f);
+  std::vector<int32_t> cap_body((size_t)num_capsules), pair_first;
+  std::vector<uint32_t> test;
+  if (num_capsules > 0) {
+    if (num_pairs < 1 || num_pairs > TREX_PROX_MAXPAIRS)
+      return fail(TREX_E_INVALID, me + ("num_pairs " + std::to_string(num_pairs)) + " outside [1, " + std::to_string(TREX_PROX_MAXPAIRS) + "]");
+    if (!body_host || !capsule_host || !pair_host) return fail(TREX_E_INVALID, std::string(me) + "null argument");
+    std::vector<std::vector<int>> of_body((size_t)b->nb);   // a body's capsules, table order
+    for (int c = 0; c < num_capsules; c++) {
+      const int body = body_host[c];
+      if (body < 0 || body >= b->nb)
+        return fail(TREX_E_INVALID, me + ("capsule " + std::to_string(c)) + ": body " + std::to_string(body) + " out of range [0, " +
+                                        std::to_string(b->nb) + ")");
+      const double *x = capsule_host + 7 * (size_t)c;
+      for (int k = 0; k < 7; k++)
+        if (!std::isfinite(x[k])) return fail(TREX_E_INVALID, me + ("capsule " + std::to_string(c)) + ": value is not finite");
+      if (x[6] < 0) return fail(TREX_E_INVALID, me + ("capsule " + std::to_string(c)) + ": negative radius");
+      const double dx = x[3] - x[0], dy = x[4] - x[1], dz = x[5] - x[2];
+      const bool sphere = dx * dx + dy * dy + dz * dz < 1e-12;   // (stored with p1 = p0: the kernel then sees a zero axis exactly)
+      float *o = cap.data() + 8 * (size_t)c;
+      for (int k = 0; k < 3; k++) { o[k] = (float)x[k]; o[4 + k] = sphere ? o[k] : (float)x[3 + k]; }
+      o[3] = (float)x[6];
+      cap_body[c] = body;
+      of_body[body].push_back(c);
+    }
+    size_t total = 0;
+    for (int p = 0; p < num_pairs; p++) {
+      const int A = pair_host[2 * p], B = pair_host[2 * p + 1];
+      if (A < 0 || A >= b->nb || B < 0 || B >= b->nb || A == B)
+        return fail(TREX_E_INVALID, me + ("pair " + std::to_string(p)) + ": bodies (" + std::to_string(A) + ", " + std::to_string(B) +
+                                        ") must be two different bodies of the model");
+      if (of_body[A].empty() || of_body[B].empty())
+        return fail(TREX_E_INVALID, me + ("pair " + std::to_string(p)) + ": a body of the pair has no capsule");
+      total += of_body[A].size() * of_body[B].size();
+    }
+    if (total > TREX_PROX_MAXTESTS)
+      return fail(TREX_E_INVALID, me + (std::to_string(total) + " capsule-pair tests, at most ") + std::to_string(TREX_PROX_MAXTESTS));
+    test.reserve(total);
+    for (int p = 0; p < num_pairs; p++) {
+      pair_first.push_back((int32_t)test.size());
+      for (int ca : of_body[pair_host[2 * p]])
+        for (int cb : of_body[pair_host[2 * p + 1]]) test.push_back(TREX_PROX_TEST(p, ca, cb));
+    }
+  }
+  DeviceGuard guard(b->device);
+  // one allocation, every part at a multiple of 16 bytes
+  auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  const size_t o_body = up(cap.size() * sizeof(float)), o_test = o_body + up(cap_body.size() * sizeof(int32_t)),
+               o_first = o_test + up(test.size() * sizeof(uint32_t)), bytes = o_first + up(pair_first.size() * sizeof(int32_t));
+  char *blob = nullptr;
+  if (num_capsules > 0) {
+    HIP_TRY(hipMalloc((void **)&blob, bytes));
+    hipError_t e = hipMemcpy(blob, cap.data(), cap.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(blob + o_body, cap_body.data(), cap_body.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(blob + o_test, test.data(), test.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(blob + o_first, pair_first.data(), pair_first.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(blob);
+      return hip_fail(e, "trex_batch_set_proximity_shapes: table");
+    }
+  }
+  HIP_TRY(hipDeviceSynchronize());   // (no launch still reads the table this one replaces; the new one is in place on every stream)
+  TrexBatch::ProxTable &pt = b->prox;
+  if (pt.blob) (void)hipFree(pt.blob);
+  pt = TrexBatch::ProxTable{};
+  if (num_capsules > 0) {
+    pt.caps = num_capsules; pt.pairs = num_pairs; pt.tests = (int)test.size();
+    pt.blob = blob;
+    pt.cap = (const float *)blob; pt.cap_body = (const int32_t *)(blob + o_body);
+    pt.test = (const uint32_t *)(blob + o_test); pt.pair_first = (const int32_t *)(blob + o_first);
+  }
+  return TREX_OK;
+}
+
+int trex_batch_proximity(TrexBatch *b, float *distance_dev, float *point_a_dev, float *point_b_dev, float *normal_dev,
+                         int32_t *capsule_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  const TrexBatch::ProxTable &pt = b->prox;
+  if (pt.caps < 1) return fail(TREX_E_INVALID, "trex_batch_proximity: no table is set (trex_batch_set_proximity_shapes)");
+  if (!distance_dev) return fail(TREX_E_INVALID, "trex_batch_proximity: distance is null");
+  DeviceGuard guard(b->device);
+  const size_t np = (size_t)b->n * pt.pairs;
+  BUF_TRY(distance_dev, np * sizeof(float), "trex_batch_proximity: distance");
+  BUF_TRY(point_a_dev, np * 3 * sizeof(float), "trex_batch_proximity: point_a");
+  BUF_TRY(point_b_dev, np * 3 * sizeof(float), "trex_batch_proximity: point_b");
+  BUF_TRY(normal_dev, np * 3 * sizeof(float), "trex_batch_proximity: normal");
+  BUF_TRY(capsule_dev, np * 2 * sizeof(int32_t), "trex_batch_proximity: capsule");
+  TrexProxArgs a{};
+  a.model = b->dmodel; a.base = b->arr.base; a.q = b->arr.q;
+  a.cap = pt.cap; a.cap_body = pt.cap_body; a.test = pt.test; a.pair_first = pt.pair_first;
+  a.distance = distance_dev; a.point_a = point_a_dev; a.point_b = point_b_dev; a.normal = normal_dev; a.capsule = capsule_dev;
+  a.n_envs = b->n; a.num_capsules = pt.caps; a.num_pairs = pt.pairs; a.num_tests = pt.tests;
+  HIP_TRY(trex_launch_proximity(a, (hipStream_t)stream));
   return TREX_OK;
 }
 

@@ -45,6 +45,7 @@ SYMBOLS = [
     "trex_batch_inverse_dynamics", "trex_batch_mass_matrix", "trex_batch_jacobian", "trex_batch_centroidal",
     "trex_batch_forward_dynamics", "trex_batch_solve_mass", "trex_batch_ray_test",
     "trex_batch_set_link_probes", "trex_batch_link_state",
+    "trex_batch_set_proximity_shapes", "trex_batch_proximity",
 ]
 
 # every symbol include/trex_policy.h declares (the trainer-side kernels)
@@ -114,6 +115,9 @@ if hasattr(lib, "trex_batch_ray_test"):
 if hasattr(lib, "trex_batch_link_state"):
     lib.trex_batch_set_link_probes.argtypes = [_vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int]
     lib.trex_batch_link_state.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]
+if hasattr(lib, "trex_batch_proximity"):
+    lib.trex_batch_set_proximity_shapes.argtypes = [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.c_int]
+    lib.trex_batch_proximity.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
 lib.trex_model_use_primitive_collision.argtypes = [_vp, C.c_double, C.c_int, C.c_int]
 lib.trex_model_fit_hull_primitives.argtypes = [_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
 lib.trex_model_num_links.argtypes = [_vp]
@@ -558,6 +562,43 @@ class Batch:
         check(lib.trex_batch_link_state(self.h, int(set), int(axes), 1 if proper else 0, self._p(accel, "float32", n * D, "accel"),
                                         ptr(pose, 7, "pose"), ptr(velocity, 6, "velocity"), ptr(acceleration, 6, "acceleration"),
                                         self._stream(stream)))
+
+    def set_proximity_shapes(self, bodies, capsules=None, pairs=None):
+        """The batch's proximity table (trex_batch_set_proximity_shapes): bodies [C] the body of each capsule, capsules [C, 7] =
+        p0 xyz, p1 xyz, radius in the body frame, pairs [P, 2] the bodies (A, B) of each pair to report. Host values, shared by all
+        envs; an empty `bodies` frees the table."""
+        bodies = np.ascontiguousarray(np.asarray(bodies, dtype=np.int64).reshape(-1))
+        Cn = int(bodies.size)
+        caps = np.zeros((Cn, 7)) if capsules is None else np.ascontiguousarray(np.asarray(capsules, dtype=np.float64))
+        if caps.shape != (Cn, 7):
+            raise TrexError(E_INVALID, "capsules: expected shape %s, got %s" % ((Cn, 7), caps.shape))
+        pr = np.zeros((0, 2), np.int64) if pairs is None else np.ascontiguousarray(np.asarray(pairs, dtype=np.int64))
+        if pr.size == 0:
+            pr = pr.reshape(0, 2)
+        if pr.ndim != 2 or pr.shape[1] != 2:
+            raise TrexError(E_INVALID, "pairs: expected shape (P, 2), got %s" % (pr.shape,))
+        for name, x in (("bodies", bodies), ("pairs", pr)):
+            if x.size and (x.min() < np.iinfo(np.int32).min or x.max() > np.iinfo(np.int32).max):
+                raise TrexError(E_INVALID, "%s: expected body indices" % name)
+        bodies, pr = bodies.astype(np.int32), np.ascontiguousarray(pr.astype(np.int32))
+        check(lib.trex_batch_set_proximity_shapes(self.h, bodies.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  caps.ctypes.data_as(C.POINTER(C.c_double)), Cn,
+                                                  pr.ctypes.data_as(C.POINTER(C.c_int32)), int(pr.shape[0])))
+
+    def proximity(self, distance, point_a=None, point_b=None, normal=None, capsule=None, stream=None, pairs=None):
+        """Closest points of every pair of the proximity table at the current state (trex_batch_proximity): distance [n, P],
+        point_a, point_b and normal [n, P, 3] f32, capsule [n, P, 2] int32 device tensors, all but distance optional, written in
+        place. pairs: P, where the caller knows it - the sizes the buffers are checked against before the call (the library
+        checks them against the table's size either way)."""
+        n = self.num_envs
+        P = None if pairs is None else int(pairs)
+        def ptr(t, width, what, dtype="float32"):
+            shape = (n, P) if width == 1 else (n, P, width)
+            if t is not None and P is not None and tuple(t.shape) != shape:
+                raise TrexError(E_INVALID, "%s: expected shape %s, got %s" % (what, shape, tuple(t.shape)))
+            return self._p(t, dtype, 0 if t is None or P is None else n * P * width, what)
+        check(lib.trex_batch_proximity(self.h, ptr(distance, 1, "distance"), ptr(point_a, 3, "point_a"), ptr(point_b, 3, "point_b"),
+                                       ptr(normal, 3, "normal"), ptr(capsule, 2, "capsule", "int32"), self._stream(stream)))
 
     def centroidal(self, out=None, stream=None):
         """[n, 16]: COM position, COM velocity, linear momentum, angular momentum about the COM, kinetic energy, potential

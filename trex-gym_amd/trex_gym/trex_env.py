@@ -52,6 +52,7 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
                                variable_stiffness=variable_stiffness, kp_max=kp_max)
         self.model = trex_robot.TrexRobot(self._vec, 0)
         self._ray_links = None
+        self._prox_cols = None                   # getClosestPoints: (body pair -> column of the proximity table, body -> pybullet link)
         self._sensor_on = bool(contact_sensor)   # (contact_wrench(); off: the default kernels)
         if self._sensor_on:
             self._vec.enable_contact_sensor(True)
@@ -223,6 +224,38 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
     def rayTest(self, rayFromPosition, rayToPosition):
         """pybullet's rayTest: rayTestBatch of the one ray (a list of one tuple)."""
         return self.rayTestBatch([rayFromPosition], [rayToPosition])
+
+    def getClosestPoints(self, bodyA, bodyB):
+        """pybullet's getClosestPoints between two bodies of the robot, bodyA and bodyB being body indices of the model (the
+        indices of TrexVecEnv.proximity_shapes' pairs; every moving link of the URDF is one): a list of one tuple in pybullet's
+        layout - (contactFlag 0, ROBOT_ID, ROBOT_ID, linkIndexA, linkIndexB, positionOnA, positionOnB, contactNormalOnB,
+        contactDistance, normalForce 0.0) - or [] when one of the two carries no collision geometry. The link indices are
+        pybullet's (-1: the base). No distance threshold: the pair is always reported. Capsules fitted to the hulls, not the
+        hulls (TrexVecEnv.closest_points, include/trex_batch.h). The first call sets the env's proximity table to ALL body pairs."""
+        m = self._vec.model
+        if self._prox_cols is None:
+            shapes = self._vec.proximity_shapes(exclude_adjacent=False, exclude_start_overlaps=False)
+            body_link = [-1] * m.num_bodies
+            for k, b in enumerate(m.array("obs_order").astype(int)):
+                body_link[b] = int(m.urdf_joint_indices[k])
+            self._prox_cols = ({(int(a), int(b)): k for k, (a, b) in enumerate(shapes.pairs)}, body_link)
+        cols, body_link = self._prox_cols
+        A, B = int(bodyA), int(bodyB)
+        for x in (A, B):
+            if not 0 <= x < m.num_bodies:
+                raise IndexError("body index %d out of range [0, %d)" % (x, m.num_bodies))
+        if A == B:
+            raise ValueError("getClosestPoints: bodyA and bodyB are the same body")
+        swap = (A, B) not in cols
+        if swap and (B, A) not in cols:
+            return []
+        k = cols[(B, A)] if swap else cols[(A, B)]
+        r = self._vec.closest_points(points=True)
+        d, pa, pb, n = (x[0, k].cpu().numpy() for x in (r.distance, r.point_a, r.point_b, r.normal))
+        if swap:   # the table holds (B, A): the same two points, the normal turned round
+            pa, pb, n = pb, pa, -n
+        return [(0, self.ROBOT_ID, self.ROBOT_ID, body_link[A], body_link[B], tuple(float(x) for x in pa),
+                 tuple(float(x) for x in pb), tuple(float(x) for x in n), float(d), 0.0)]
 
     def should_terminate(self):
         return False

@@ -40,6 +40,8 @@ class Centroidal:
 LinkState = collections.namedtuple("LinkState", "position orientation linear_velocity angular_velocity linear_acceleration "
                                                 "angular_acceleration")
 AXES = {"world": 0, "link": 1, "base": 2}
+ProximityShapes = collections.namedtuple("ProximityShapes", "bodies capsules pairs")
+ClosestPoints = collections.namedtuple("ClosestPoints", "distance point_a point_b normal capsule")
 
 
 class LinkProbes:
@@ -144,6 +146,8 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         self._ray_out = (None, None)            # ray_test's output buffers of the last (R, positions, normals)
         self._probe_sets = [None] * 8           # the LinkProbes handle in each of the batch's probe-set slots
         self._probe_cache = (None, None)        # link_state()'s one-off set of the last links given directly
+        self.collision = collision
+        self._prox, self._prox_out = None, (None, None)   # the ProximityShapes in force; closest_points()'s output buffers
         self.pushes = pushes
         if pushes is not None and pushes.num_envs != n:
             raise ValueError("pushes: RandomPushes over %d envs, the env has %d" % (pushes.num_envs, n))
@@ -574,6 +578,89 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         acc = torch.empty(self.num_envs, 1, 6, device=self.device)
         self.batch.link_state(h.slot, 0, False, None, None, None, acc, probes=1)
         return acc[:, 0]
+
+    # ---- proximity between bodies (trex_batch_set_proximity_shapes / trex_batch_proximity: pybullet's getClosestPoints between
+    # links of the robot; one launch for all pairs, no host sync)
+    def proximity_shapes(self, capsules=None, pairs=None, max_radius=0.2, max_divisions=3, min_points=4, exclude_adjacent=True,
+                         exclude_start_overlaps=True):
+        """Set the env's proximity table and return what it holds, as ProximityShapes(bodies [C], capsules [C, 7], pairs [P, 2]).
+        capsules: (bodies [C], [C, 7] = p0 xyz, p1 xyz, radius in the body frames); None: every convex hull fitted with
+        Model.fit_hull_primitives(max_radius, max_divisions, min_points) - or, with collision="primitives", the model's spheres
+        as capsules of length 0: what the physics collides with (the cylinder between a capsule's ends is absent there too).
+        pairs: [P, 2] body pairs (A, B); None: all pairs of bodies with geometry, minus parent-child pairs (exclude_adjacent),
+        minus the pairs that already overlap at the start pose (exclude_start_overlaps; found with one query on a reset batch of
+        one env). capsules=() frees the table."""
+        m = self.model
+        if capsules is None:
+            hs = m.array("hull_start").astype(int)
+            if self.collision == "primitives":
+                xyz, rad = m.array("hull_xyz").reshape(-1, 3), m.array("hull_radius")
+                bodies = np.repeat(np.arange(m.num_bodies), np.diff(hs)).astype(np.int32)
+                caps = np.concatenate([xyz, xyz, rad[:, None]], 1)
+            else:
+                gs = m.array("hull_group_start").astype(int)
+                bodies, caps = [], []
+                for b in range(m.num_bodies):
+                    for g in range(len(gs) - 1):
+                        if hs[b] <= gs[g] < hs[b + 1] and gs[g + 1] > gs[g]:
+                            for p0, p1, r in m.fit_hull_primitives(g, max_radius, max_divisions, min_points):
+                                bodies.append(b)
+                                caps.append(np.concatenate([p0, p1, [r]]))
+                bodies, caps = np.array(bodies, np.int32), np.array(caps, np.float64).reshape(-1, 7)
+        else:
+            bodies, caps = capsules if len(capsules) else ((), ())
+            bodies, caps = np.asarray(bodies, np.int32).reshape(-1), np.asarray(caps, np.float64).reshape(-1, 7)
+        if len(bodies) == 0:
+            self.batch.set_proximity_shapes([])
+            self._prox, self._prox_out = None, (None, None)
+            return None
+        if pairs is None:
+            have = sorted(set(int(b) for b in bodies))
+            parent = m.array("parent").astype(int)
+            pairs = [(a, b) for i, a in enumerate(have) for b in have[i + 1:]
+                     if not (exclude_adjacent and (parent[b] == a or parent[a] == b))]
+            if exclude_start_overlaps and pairs:
+                probe = _capi.Batch(m, 1, self.device.index)
+                try:
+                    probe.reset()
+                    probe.set_proximity_shapes(bodies, caps, pairs)
+                    d = torch.empty(1, len(pairs), device=self.device)
+                    probe.proximity(d, pairs=len(pairs))
+                    keep = (~(d[0] < 0)).cpu().numpy()
+                finally:
+                    probe.forget_buffers()
+                    probe.close()
+                pairs = [p for p, k in zip(pairs, keep) if k]
+        pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+        self.batch.set_proximity_shapes(bodies, caps, pairs)
+        self._prox, self._prox_out = ProximityShapes(bodies, caps, pairs), (None, None)
+        return self._prox
+
+    def closest_points(self, points=False):
+        """Signed distance [n, P] between the bodies of every pair of proximity_shapes() (made with its defaults on first use) at
+        the current state: the smallest over the capsules of the two bodies, negative = overlap depth. points: a ClosestPoints
+        instead, adding point_a, point_b [n, P, 3] (world; on the surfaces of A and B), normal [n, P, 3] (unit, from B to A:
+        pybullet's contactNormalOnB) and capsule [n, P, 2] int32 (table indices of the two winning capsules). The tensors are
+        buffers of the env, reused by the next call."""
+        if self._prox is None:
+            self.proximity_shapes()
+        n, P = self.num_envs, len(self._prox.pairs)
+        key = (P, bool(points))
+        if self._prox_out[0] != key:
+            f = lambda *s: torch.empty(*s, device=self.device)
+            self._prox_out = (key, (f(n, P),) + ((f(n, P, 3), f(n, P, 3), f(n, P, 3), torch.empty(n, P, 2, dtype=torch.int32, device=self.device))
+                                                 if points else (None,) * 4))
+        out = self._prox_out[1]
+        self.batch.proximity(*out, pairs=P)
+        return ClosestPoints(*out) if points else out[0]
+
+    def self_collision_distance(self):
+        """[n]: the smallest distance over the pairs of proximity_shapes(); negative: two bodies of the env overlap by that much."""
+        return self.closest_points().min(dim=1).values
+
+    def in_self_collision(self, margin=0.0):
+        """[n] bool: some pair of proximity_shapes() is closer than `margin`."""
+        return self.self_collision_distance() < margin
 
     # ---- ray casts (trex_batch_ray_test: pybullet's rayTestBatch; no host sync; trex_gym.sensors builds patterns)
     def ray_test(self, rays, link=None, positions=False, normals=False, bodies=None, floor=True):

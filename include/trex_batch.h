@@ -523,6 +523,69 @@ int trex_batch_set_proximity_shapes(TrexBatch *batch, const int32_t *body_host, 
 int trex_batch_proximity(TrexBatch *batch, float *distance_dev, float *point_a_dev, float *point_b_dev, float *normal_dev,
                          int32_t *capsule_dev, void *stream);
 
+/* ---- floor clearance per body, and fall termination inside the step (no reference counterpart: the reference's
+ * should_terminate() is constant False, trex_env.py:183-184). One kernel (csrc/termination.hip) serves both.
+ *
+ * trex_batch_body_clearance: for every env and body b, at the env's current state,
+ *   clearance_dev [N, num_bodies]     min over the body's collision points of (world z - support radius) - floor_z, metres:
+ *                                     how high the lowest point of the body stands above the floor; negative = it is that deep
+ *                                     in it. Required. +inf for a body without collision points.
+ *   lowest_dev    [N, num_bodies, 3]  world position of that lowest point, the radius subtracted along z (so that its z - floor_z
+ *                                     is the clearance, up to rounding); NaN for a body without points. Nullable.
+ * The collision points are what the physics collides with: the hull vertices (radius 0), or after
+ * trex_model_use_primitive_collision the sphere centres / capsule ends with their radii. The query is exact over them - every
+ * point of every body is evaluated, no bounding volume decides anything; among points of equal height the one earlier in the
+ * model's order is reported. It behaves like the dynamics queries: read-only, asynchronous and ordered on `stream`, every device
+ * buffer validated (TREX_E_INVALID before anything is launched), nothing allocated or waited for, from the second call with known
+ * buffers ONE plain kernel launch, usable inside a single-stream capture. A non-finite state makes that env's row unspecified
+ * and leaves every other env bitwise as without it.
+ *
+ * trex_batch_set_termination: end an env's episode when the robot falls, decided on the device after every env-step.
+ *   head_height_min   criterion 1 (TREX_TERM_HEAD): the head point (trex_batch_head_position) is lower than this above floor_z
+ *   tilt_max_rad      criterion 2 (TREX_TERM_TILT): the base is tipped further than this from its start orientation, in (0, pi]:
+ *                     cos(tilt) = z component of R_base R_start^-1 e_z, 1 at the start orientation, compared with cos(tilt_max_rad)
+ *   clear_min_host    criterion 3 (TREX_TERM_CLEARANCE) [num_bodies], host: a watched body's clearance is below its entry. NaN = the
+ *                     body is not watched; NULL = none is. With the model's contact_margin as the entry the criterion reads "a body
+ *                     that is not a foot touches the floor". Copied.
+ *   penalty           subtracted, once, from the reward of the step in which an env terminates
+ * A NaN head_height_min / tilt_max_rad switches that criterion off; all three off = the feature off: the step calls are again
+ * exactly what they are for a batch that never enabled it (same launches, same results). TREX_E_INVALID, nothing changed: an
+ * infinite head_height_min, a tilt_max_rad that is neither NaN nor in (0, pi], a non-finite penalty. Comparisons are strict (<).
+ *
+ * While a criterion is on, trex_batch_step and trex_batch_step_rows enqueue THREE launches on `stream`:
+ *   1. the step launch, exactly as without termination (every feature mix, either launch form; trex_batch_launch_info unchanged);
+ *   2. the predicate launch: per env values[0] = head z - floor_z, values[1] = cos(tilt), values[2] = min over the watched bodies of
+ *      clearance - clear_min (+inf: none watched); the reason bits of the criteria that fire; for an env with reason != 0: done = 1
+ *      in the done bytes and in the done column / array, wherever the step launch wrote them, reward -= penalty, and its
+ *      observation row - the last of the episode - copied to the batch's terminal-observation buffer. An env that the step launch
+ *      itself ended (done already 1: the episode limit, a contained non-finite env) is on its new episode's state and is NOT judged:
+ *      reason 0, reward and done untouched (its values are still written, from the state it is in). A trex_batch_step call
+      without obs_dev keeps no terminal observation; one without done_dev has the step launch write its done flags to a buffer
+      of the batch's, so that the predicate can tell;
+ *   3. the reset launch of trex_batch_reset with reason != 0 as its mask, writing observations only: the env is put to the start
+ *      pose, motors off, one un-actuated settle substep, episode count 0, warm-start record emptied, the contact sensor (if on)
+ *      recording the settle substep; its observation row is the first of the new episode; reward and done stay as 1 and 2 left
+ *      them. (For the other envs it rewrites the q, qd columns with the values they hold, as trex_batch_reset does.)
+ * No host decision is made and nothing is waited for: the three launches run whether or not an env terminates, and a linear
+ * single-stream capture of step calls may hold them from the second call on. trex_batch_step_many performs num_steps such
+ * triplets from the host; its results stay bitwise those of num_steps trex_batch_step_rows calls. trex_batch_time_steps and
+ * trex_batch_debug_step return TREX_E_INVALID while termination is on.
+ * The first enabling call allocates the batch's buffers (mask, reasons, values, terminal observations) and may wait for the
+ * device once: not inside a capture. A batch that never enables termination allocates nothing and launches nothing new.
+ * With termination on the step calls WRITE batch-owned memory: two step calls of one batch must not run on two streams at once
+ * (as with stiffness actions).
+ *
+ * trex_batch_termination_info: device-to-device copies, ordered on `stream`, of what the LAST step call left: reason_dev [N] i32,
+ * values_dev [N, 3], terminal_obs_dev [N, 3J] - the row of an env is the observation of its most recent termination (zeros
+ * before the first). Each nullable. TREX_E_INVALID for a batch that never enabled termination. */
+#define TREX_TERM_HEAD 1
+#define TREX_TERM_TILT 2
+#define TREX_TERM_CLEARANCE 4
+int trex_batch_body_clearance(TrexBatch *batch, float *clearance_dev, float *lowest_dev, void *stream);
+int trex_batch_set_termination(TrexBatch *batch, float head_height_min, float tilt_max_rad, const float *clear_min_host,
+                               float penalty);
+int trex_batch_termination_info(TrexBatch *batch, int32_t *reason_dev, float *values_dev, float *terminal_obs_dev, void *stream);
+
 /* diagnostics of the last substep: contact count per env [N] i32 (nullable), summed normal
  * impulse per env [N] f32 (nullable). */
 int trex_batch_contact_stats(TrexBatch *batch, int32_t *count_dev, float *normal_impulse_dev, void *stream);

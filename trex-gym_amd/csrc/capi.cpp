@@ -19,6 +19,7 @@
 #include "raycast.h"
 #include "render.h"
 #include "step_launch.h"
+#include "termination.h"
 
 struct TrexModel {
   trex::HostModel host;
@@ -75,6 +76,18 @@ struct TrexBatch {
     void *blob = nullptr;
     const float *cap = nullptr; const int32_t *cap_body = nullptr; const uint32_t *test = nullptr; const int32_t *pair_first = nullptr;
   } prox;
+  // fall termination (trex_batch_set_termination): the thresholds in force - a NaN is a criterion that is off - and the batch-owned
+  // buffers of the predicate launch, ONE device allocation made by the first enabling call: terminal observations [n][3J], values
+  // [n][3], reasons [n], reset mask [n], and done bytes [n] for a trex_batch_step call that passes no done buffer
+  struct Termination {
+    bool on = false, watch_any = false;
+    float head_min = NAN, cos_tilt = NAN, penalty = 0.f;
+    float clear_min[TREX_TL];
+    void *blob = nullptr;
+    float *tobs = nullptr, *values = nullptr;
+    int32_t *reason = nullptr;
+    uint8_t *mask = nullptr, *done = nullptr;
+  } term;
   // caller allocations already validated as memory of this device (base address, bytes known to be good):
   // the hot path pays one hash-free scan of a handful of entries, hipPointerGetAttributes only on a new one
   std::vector<TrexSeen> seen;
@@ -253,6 +266,31 @@ void rows_out(const TrexBatch *b, TrexStepArgs &a, float *rows, int row_stride) 
   a.obs = rows; a.reward = rows + 3 * b->nj; a.done_f = a.reward + 1;
   a.obs_stride = a.scal_stride = row_stride;
   a.pen_in_rows = b->pen_in_rows ? 1 : 0;
+}
+
+// the state and the collision points of a K8 launch (termination.hip)
+TrexTermArgs term_args(const TrexBatch *b) {
+  TrexTermArgs t{};
+  t.model = b->dmodel; t.base = b->arr.base; t.q = b->arr.q; t.hull = b->arr.hull; t.n_envs = b->n;
+  return t;
+}
+// The two launches that follow the step launch `a` of a batch with termination on: the K8 predicate on the outputs `a` names, then
+// the RESET launch with the K8 mask - observation into the caller's rows, no reward, no done, so that what the step and K8 wrote
+// there survives. Nothing is decided on the host: both run whether or not an env terminates.
+hipError_t termination_tail(const TrexBatch *b, const TrexStepArgs &a, hipStream_t stream) {
+  const TrexBatch::Termination &tm = b->term;
+  TrexTermArgs t = term_args(b);
+  t.watch_any = tm.watch_any ? 1 : 0;
+  t.head_min = tm.head_min; t.cos_tilt = tm.cos_tilt; t.penalty = tm.penalty;
+  std::memcpy(t.clear_min, tm.clear_min, sizeof t.clear_min);
+  t.mask = tm.mask; t.reason = tm.reason; t.values = tm.values; t.terminal_obs = tm.tobs;
+  t.obs = a.obs; t.reward = a.reward; t.done_f = a.done_f; t.done = a.done;
+  t.obs_stride = a.obs_stride; t.scal_stride = a.scal_stride; t.obs_cols = 3 * b->nj;
+  hipError_t e = trex_launch_termination(t, 1, stream);
+  if (e != hipSuccess) return e;
+  TrexStepArgs r = step_args(b, TREX_KIND_RESET);
+  r.reset_mask = tm.mask; r.obs = a.obs; r.obs_stride = a.obs_stride;
+  return trex_launch_step(&r, TREX_KIND_RESET, stream);
 }
 
 int check_device_buffer(TrexBatch *b, const void *p, size_t bytes, const char *what) {
@@ -564,6 +602,7 @@ void trex_batch_destroy(TrexBatch *b) {
     if (ps.tf) (void)hipFree(ps.tf);
   }
   if (b->prox.blob) (void)hipFree(b->prox.blob);
+  if (b->term.blob) (void)hipFree(b->term.blob);
   delete b;
 }
 
@@ -634,7 +673,9 @@ int trex_batch_step(TrexBatch *b, const float *actions_dev, float *obs_dev, floa
   BUF_TRY(penalties_dev, n * 3 * sizeof(float), "trex_batch_step: penalties");
   TrexStepArgs a = step_args(b, TREX_KIND_STEP);
   a.actions = actions_dev; a.obs = obs_dev; a.reward = reward_dev; a.done = done_dev; a.penalties = penalties_dev;
+  if (b->term.on && !a.done) a.done = b->term.done;   // (the predicate has to see which envs the step launch ended)
   HIP_TRY(trex_launch_step(&a, TREX_KIND_STEP, (hipStream_t)stream));
+  if (b->term.on) HIP_TRY(termination_tail(b, a, (hipStream_t)stream));
   return TREX_OK;
 }
 
@@ -653,6 +694,7 @@ int trex_batch_step_rows(TrexBatch *b, const float *actions_dev, float *rows_dev
   a.actions = actions_dev; a.done = done_dev; a.penalties = penalties_dev;
   rows_out(b, a, rows_dev, row_stride);
   HIP_TRY(trex_launch_step(&a, TREX_KIND_STEP, (hipStream_t)stream));
+  if (b->term.on) HIP_TRY(termination_tail(b, a, (hipStream_t)stream));
   return TREX_OK;
 }
 
@@ -668,6 +710,18 @@ int trex_batch_step_many(TrexBatch *b, const float *actions_dev, float *rows_dev
   BUF_TRY(rows_dev, ((S * n - 1) * row_stride + 3 * b->nj + (b->pen_in_rows ? 5 : 2)) * sizeof(float), "trex_batch_step_many: rows");
   BUF_TRY(penalties_dev, S * n * 3 * sizeof(float), "trex_batch_step_many: penalties");
   BUF_TRY(done_dev, S * n, "trex_batch_step_many: done");
+  if (b->term.on) {   // S triplets step, predicate, reset from the host: what S trex_batch_step_rows calls enqueue
+    for (size_t s = 0; s < S; s++) {
+      TrexStepArgs a = step_args(b, TREX_KIND_STEP);
+      a.actions = actions_dev + s * n * b->action_cols();
+      a.done = done_dev ? done_dev + s * n : nullptr;
+      a.penalties = penalties_dev ? penalties_dev + s * n * 3 : nullptr;
+      rows_out(b, a, rows_dev + s * n * (size_t)row_stride, row_stride);
+      HIP_TRY(trex_launch_step(&a, TREX_KIND_STEP, (hipStream_t)stream));
+      HIP_TRY(termination_tail(b, a, (hipStream_t)stream));
+    }
+    return TREX_OK;
+  }
   TrexStepArgs a = step_args(b, TREX_KIND_STEP_MANY);
   a.actions = actions_dev; a.done = done_dev; a.penalties = penalties_dev;
   rows_out(b, a, rows_dev, row_stride);
@@ -691,6 +745,8 @@ int trex_batch_debug_step(TrexBatch *b, const float *actions_dev, float *obs_dev
     return fail(TREX_E_INVALID, "trex_batch_debug_step: not available while the contact sensor is on");
   if (b->act_on())   // (nor the actuator model)
     return fail(TREX_E_INVALID, "trex_batch_debug_step: not available while control modes, motor gains or stiffness actions are set");
+  if (b->term.on)   // (nor the predicate and reset launches of fall termination)
+    return fail(TREX_E_INVALID, "trex_batch_debug_step: not available while termination is on (trex_batch_set_termination)");
   TrexStepArgs a = step_args(b, TREX_KIND_STEP_DEBUG);
   a.actions = actions_dev; a.obs = obs_dev; a.debug = debug_dev;
   HIP_TRY(trex_launch_step(&a, TREX_KIND_STEP_DEBUG, (hipStream_t)stream));
@@ -1003,6 +1059,8 @@ int trex_batch_time_steps(TrexBatch *b, const float *actions_dev, float *obs_dev
                           int steps, void *stream, float *avg_ms_out) {
   if (check_batch(b)) return TREX_E_INVALID;
   if (!actions_dev || !avg_ms_out || steps <= 0) return fail(TREX_E_INVALID, "trex_batch_time_steps: bad argument");
+  if (b->term.on)   // (it times the step launch alone: with termination on a step is three launches)
+    return fail(TREX_E_INVALID, "trex_batch_time_steps: not available while termination is on (trex_batch_set_termination)");
   DeviceGuard guard(b->device);
   BUF_TRY(actions_dev, (size_t)b->n * b->action_cols() * sizeof(float), "trex_batch_time_steps: actions");
   BUF_TRY(obs_dev, (size_t)b->n * 3 * b->nj * sizeof(float), "trex_batch_time_steps: obs");
@@ -1341,6 +1399,66 @@ int trex_batch_proximity(TrexBatch *b, float *distance_dev, float *point_a_dev, 
   a.distance = distance_dev; a.point_a = point_a_dev; a.point_b = point_b_dev; a.normal = normal_dev; a.capsule = capsule_dev;
   a.n_envs = b->n; a.num_capsules = pt.caps; a.num_pairs = pt.pairs; a.num_tests = pt.tests;
   HIP_TRY(trex_launch_proximity(a, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+// ---- floor clearance and fall termination (termination.hip)
+int trex_batch_body_clearance(TrexBatch *b, float *clearance_dev, float *lowest_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (!clearance_dev) return fail(TREX_E_INVALID, "trex_batch_body_clearance: clearance is null");
+  DeviceGuard guard(b->device);
+  const size_t nb = (size_t)b->n * b->nb;
+  BUF_TRY(clearance_dev, nb * sizeof(float), "trex_batch_body_clearance: clearance");
+  BUF_TRY(lowest_dev, nb * 3 * sizeof(float), "trex_batch_body_clearance: lowest");
+  TrexTermArgs t = term_args(b);
+  t.clearance = clearance_dev; t.lowest = lowest_dev;
+  HIP_TRY(trex_launch_termination(t, 0, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+int trex_batch_set_termination(TrexBatch *b, float head_height_min, float tilt_max_rad, const float *clear_min_host, float penalty) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  if (std::isinf(head_height_min)) return fail(TREX_E_INVALID, "trex_batch_set_termination: head_height_min is infinite (NaN = off)");
+  if (!std::isnan(tilt_max_rad) && !(tilt_max_rad > 0.f && tilt_max_rad <= 3.14159274f))
+    return fail(TREX_E_INVALID, "trex_batch_set_termination: tilt_max_rad must lie in (0, pi] (NaN = off)");
+  if (!std::isfinite(penalty)) return fail(TREX_E_INVALID, "trex_batch_set_termination: penalty is not finite");
+  bool watch = false;
+  for (int i = 0; clear_min_host && i < b->nb; i++) watch |= !std::isnan(clear_min_host[i]);
+  const bool on = !std::isnan(head_height_min) || !std::isnan(tilt_max_rad) || watch;
+  TrexBatch::Termination &tm = b->term;
+  if (on && !tm.blob) {   // first enable: a batch that never enables it allocates nothing
+    DeviceGuard guard(b->device);
+    const size_t n = (size_t)b->n, o_val = n * 3 * b->nj * sizeof(float), o_reason = o_val + n * 3 * sizeof(float),
+                 o_mask = o_reason + n * sizeof(int32_t), o_done = o_mask + n, bytes = o_done + n;
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, bytes));
+    hipError_t e = hipMemset(p, 0, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();   // (the zeros are in place before a launch on any stream)
+    if (e != hipSuccess) { (void)hipFree(p); return hip_fail(e, "trex_batch_set_termination: buffers"); }
+    char *c = (char *)p;
+    tm.blob = p; tm.tobs = (float *)c; tm.values = (float *)(c + o_val); tm.reason = (int32_t *)(c + o_reason);
+    tm.mask = (uint8_t *)(c + o_mask); tm.done = (uint8_t *)(c + o_done);
+  }
+  tm.on = on; tm.watch_any = watch;
+  tm.head_min = head_height_min; tm.penalty = penalty;
+  tm.cos_tilt = std::isnan(tilt_max_rad) ? NAN : (float)std::cos((double)tilt_max_rad);
+  for (int i = 0; i < TREX_TL; i++) tm.clear_min[i] = (clear_min_host && i < b->nb) ? clear_min_host[i] : NAN;
+  return TREX_OK;
+}
+
+int trex_batch_termination_info(TrexBatch *b, int32_t *reason_dev, float *values_dev, float *terminal_obs_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  const TrexBatch::Termination &tm = b->term;
+  if (!tm.blob) return fail(TREX_E_INVALID, "trex_batch_termination_info: termination was never enabled (trex_batch_set_termination)");
+  DeviceGuard guard(b->device);
+  const size_t n = (size_t)b->n;
+  BUF_TRY(reason_dev, n * sizeof(int32_t), "trex_batch_termination_info: reason");
+  BUF_TRY(values_dev, n * 3 * sizeof(float), "trex_batch_termination_info: values");
+  BUF_TRY(terminal_obs_dev, n * 3 * b->nj * sizeof(float), "trex_batch_termination_info: terminal_obs");
+  hipStream_t s = (hipStream_t)stream;
+  if (reason_dev) HIP_TRY(hipMemcpyAsync(reason_dev, tm.reason, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  if (values_dev) HIP_TRY(hipMemcpyAsync(values_dev, tm.values, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (terminal_obs_dev) HIP_TRY(hipMemcpyAsync(terminal_obs_dev, tm.tobs, n * 3 * b->nj * sizeof(float), hipMemcpyDeviceToDevice, s));
   return TREX_OK;
 }
 

@@ -46,6 +46,7 @@ SYMBOLS = [
     "trex_batch_forward_dynamics", "trex_batch_solve_mass", "trex_batch_ray_test",
     "trex_batch_set_link_probes", "trex_batch_link_state",
     "trex_batch_set_proximity_shapes", "trex_batch_proximity",
+    "trex_batch_body_clearance", "trex_batch_set_termination", "trex_batch_termination_info",
 ]
 
 # every symbol include/trex_policy.h declares (the trainer-side kernels)
@@ -118,6 +119,10 @@ if hasattr(lib, "trex_batch_link_state"):
 if hasattr(lib, "trex_batch_proximity"):
     lib.trex_batch_set_proximity_shapes.argtypes = [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.c_int]
     lib.trex_batch_proximity.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
+if hasattr(lib, "trex_batch_body_clearance"):
+    lib.trex_batch_body_clearance.argtypes = [_vp, _vp, _vp, _vp]
+    lib.trex_batch_set_termination.argtypes = [_vp, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_float]
+    lib.trex_batch_termination_info.argtypes = [_vp, _vp, _vp, _vp, _vp]
 lib.trex_model_use_primitive_collision.argtypes = [_vp, C.c_double, C.c_int, C.c_int]
 lib.trex_model_fit_hull_primitives.argtypes = [_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
 lib.trex_model_num_links.argtypes = [_vp]
@@ -599,6 +604,41 @@ class Batch:
             return self._p(t, dtype, 0 if t is None or P is None else n * P * width, what)
         check(lib.trex_batch_proximity(self.h, ptr(distance, 1, "distance"), ptr(point_a, 3, "point_a"), ptr(point_b, 3, "point_b"),
                                        ptr(normal, 3, "normal"), ptr(capsule, 2, "capsule", "int32"), self._stream(stream)))
+
+    def body_clearance(self, clearance=None, lowest=None, stream=None):
+        """Height of the lowest collision point of every body above the floor at the current state (trex_batch_body_clearance):
+        clearance [n, num_bodies] f32 on the batch's device (made when None, and returned; +inf for a body without points),
+        lowest [n, num_bodies, 3] optional: that point's world position."""
+        nb = self.model.num_bodies
+        clearance = self._out(clearance, nb)
+        if lowest is not None and tuple(lowest.shape) != (self.num_envs, nb, 3):
+            raise TrexError(E_INVALID, "lowest: expected shape %s, got %s" % ((self.num_envs, nb, 3), tuple(lowest.shape)))
+        check(lib.trex_batch_body_clearance(self.h, self._p(clearance, "float32", self.num_envs * nb, "clearance"),
+                                            self._p(lowest, "float32", self.num_envs * nb * 3, "lowest"), self._stream(stream)))
+        return clearance
+
+    def set_termination(self, head_height=None, max_tilt=None, clear_min=None, penalty=0.0):
+        """Fall termination inside the step calls (trex_batch_set_termination): head_height - the head point's least height above
+        the floor, max_tilt - the base's largest tilt from its start orientation, rad in (0, pi], clear_min - [num_bodies] host
+        values, the clearance each body has to keep (NaN: not watched); None switches a criterion off, all three None the
+        feature. penalty: taken from the reward of the terminating step."""
+        nan = float("nan")
+        cm = None
+        if clear_min is not None:
+            a = np.ascontiguousarray(np.asarray(clear_min, dtype=np.float32).reshape(-1))
+            if a.size != self.model.num_bodies:
+                raise TrexError(E_INVALID, "clear_min: expected %d entries, got %d" % (self.model.num_bodies, a.size))
+            cm = a.ctypes.data_as(C.POINTER(C.c_float))
+        check(lib.trex_batch_set_termination(self.h, nan if head_height is None else float(head_height),
+                                             nan if max_tilt is None else float(max_tilt), cm, float(penalty)))
+
+    def termination_info(self, reason=None, values=None, terminal_obs=None, stream=None):
+        """What the last step call's predicate left (trex_batch_termination_info), copied into the tensors given: reason [n]
+        int32 (bits 1 head, 2 tilt, 4 clearance), values [n, 3] f32 (head height, cos tilt, least clearance margin),
+        terminal_obs [n, 3J] f32."""
+        n = self.num_envs
+        check(lib.trex_batch_termination_info(self.h, self._p(reason, "int32", n, "reason"), self._p(values, "float32", 3 * n, "values"),
+                                              self._p(terminal_obs, "float32", n * 3 * self.J, "terminal_obs"), self._stream(stream)))
 
     def centroidal(self, out=None, stream=None):
         """[n, 16]: COM position, COM velocity, linear momentum, angular momentum about the COM, kinetic energy, potential

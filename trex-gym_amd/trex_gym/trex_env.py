@@ -26,7 +26,7 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
 
     def __init__(self, urdf_path=None, action_repeat=1, distance_weight=1.0, energy_weight=0.005,
                  drift_weight=0.002, render=False, device=None, contact_sensor=False, control_mode=None,
-                 variable_stiffness=False, kp_max=1.0):
+                 variable_stiffness=False, kp_max=1.0, terminate=None):
         if render:   # (the reference's render=True opens pybullet's GUI; rgb_array frames need no flag: render())
             raise NotImplementedError("render=True asks for a GUI, which this env has not; render('rgb_array') draws frames")
         self._time_step = 0.01 / NUM_SUBSTEPS
@@ -49,7 +49,8 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
                                distance_weight=distance_weight, energy_weight=energy_weight,
                                drift_weight=drift_weight,
                                starting_configuration=self._starting_configuration, control_mode=control_mode,
-                               variable_stiffness=variable_stiffness, kp_max=kp_max)
+                               variable_stiffness=variable_stiffness, kp_max=kp_max, terminate=terminate)
+        self._terminated = False                 # the last step ended the episode by a fall (terminate=dict(...): TrexVecEnv.set_termination)
         self.model = trex_robot.TrexRobot(self._vec, 0)
         self._ray_links = None
         self._prox_cols = None                   # getClosestPoints: (body pair -> column of the proximity table, body -> pybullet link)
@@ -69,6 +70,7 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
     def reset(self):
         self._vec.reset_tensor()
         self._env_step_counter = 0
+        self._terminated = False
         self._last_base_position = self.model.get_base_position()
         return self.model.get_observations()
 
@@ -86,7 +88,15 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
         self._vec.step_tensor(a)
         self._env_step_counter += 1
         self._observation = self.model.get_observations()
-        return self._observation, self.compute_reward(), self.should_terminate(), {}
+        info = {}
+        if self._vec._term_on:   # a fall: done, with the episode's last observation (the env is already on its next episode)
+            reason = int(self._vec.termination_reason[0].item())
+            self._terminated = reason != 0
+            if self._terminated:
+                self._observation = self._vec.terminal_obs[0].cpu().numpy().astype(np.float64).tolist()
+                info = {"termination": reason}
+                self._env_step_counter = 0
+        return self._observation, self.compute_reward(), self.should_terminate(), info
 
     def render(self, mode='rgb_array', close=False):
         """'rgb_array': uint8 [720, 960, 3] from the reference's camera (distance 10, yaw 90, pitch -30, fov 60, following the
@@ -257,8 +267,16 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
         return [(0, self.ROBOT_ID, self.ROBOT_ID, body_link[A], body_link[B], tuple(float(x) for x in pa),
                  tuple(float(x) for x in pb), tuple(float(x) for x in n), float(d), 0.0)]
 
+    def body_clearance(self, link=None):
+        """Height of the lowest collision point above the floor (TrexVecEnv.body_clearance), numpy: [num_bodies] for every body,
+        or the float of the body of `link` (name or index)."""
+        c = self._vec.body_clearance(link)[0].cpu().numpy()
+        return c if link is None else float(c)
+
     def should_terminate(self):
-        return False
+        # constant False in the reference (trex_env.py:183-184), and here unless the env was made with terminate=dict(...):
+        # then whether the last step ended the episode by a fall
+        return self._terminated
 
     def compute_reward(self):
         # computed inside the step kernel (trex_env.py:186-196); penalties = the three logged values

@@ -24,7 +24,7 @@ _URDF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ass
 
 def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0, push_force=0.0, push_interval=100,
                       push_duration=5, push_probability=1.0, seed=0, control_mode=None, variable_stiffness=False,
-                      gain_scale=0.0):   # (weights of trex_train.py:66)
+                      gain_scale=0.0, terminate=None):   # (weights of trex_train.py:66)
     # control_mode: what the joints' actions mean (position / velocity / torque: J-wide, through the trainer unchanged). The
     # 2J-wide stiffness action space is wider than the policy kernel's act_dim <= 32: refused here, not deep in a launch
     check_action_space(control_mode, variable_stiffness)
@@ -39,7 +39,8 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
         pushes = RandomPushes(num_envs, body=0, interval=push_interval, probability=push_probability, max_force=push_force,
                               duration=push_duration, generator=gen, device=dev)
     env = TrexVecEnv(num_envs, urdf_path=_URDF_PATH, device=device, distance_weight=2e2, energy_weight=1e-6,
-                     drift_weight=1.0, max_episode_steps=max_episode_steps, params=params, pushes=pushes, control_mode=control_mode)
+                     drift_weight=1.0, max_episode_steps=max_episode_steps, params=params, pushes=pushes, control_mode=control_mode,
+                     terminate=terminate)   # terminate: TrexVecEnv.set_termination's arguments - a fall ends the episode, on the device
     if gain_scale > 0:   # every episode with motor gains and strength scaled by 1 +- gain_scale per env (RandomGains)
         dev = torch.device(device)
         r = (1.0 - gain_scale, 1.0 + gain_scale)
@@ -183,6 +184,11 @@ def parse_args(argv=None):
                     help="what an action is for every joint: target angle, target velocity or torque")
     ap.add_argument("--variable_stiffness", action="store_true", help="[target, stiffness] actions (2J wide): refused, wider than the policy kernel")
     ap.add_argument("--gain_scale", type=float, default=0.0, help="randomise motor kp / kd / max_force per env and episode by 1 +- this (0 = off)")
+    ap.add_argument("--terminate_head_height", type=float, default=None, help="end an episode when the head is lower than this above the floor (m)")
+    ap.add_argument("--terminate_tilt", type=float, default=None, help="end an episode when the base is tipped more than this from its start orientation (rad)")
+    ap.add_argument("--terminate_contact", type=str, default=None, metavar="LINK[,LINK...]",
+                    help="end an episode when one of these links touches the floor; 'auto': every body but the feet of the start pose")
+    ap.add_argument("--fall_penalty", type=float, default=0.0, help="taken from the reward of the step in which an episode ends by a fall")
     args = ap.parse_args(argv)
     if args.variable_stiffness:
         try:
@@ -193,15 +199,38 @@ def parse_args(argv=None):
         ap.error("--gain_scale must lie in [0, 1)")
     if args.push_force > 0 and args.graphs:   # (the pushes are drawn per step on the host's step count: not in a replayed graph)
         ap.error("--push_force cannot be combined with --graphs")
+    if args.gain_scale > 0 and args.graphs and termination_args(args):   # (a fallen env draws new gains: host work per step)
+        ap.error("--gain_scale with a --terminate_* criterion cannot be combined with --graphs")
     return args
 
 
-def main(argv=None):
-    args = parse_args(argv)
+def termination_args(args):
+    """the dict for TrexVecEnv(terminate=...) of the --terminate_* flags, None when none is given"""
+    contact = [l for l in (args.terminate_contact or "").split(",") if l]
+    if args.terminate_head_height is None and args.terminate_tilt is None and not contact:
+        return None
+    return dict(head_height=args.terminate_head_height, max_tilt=args.terminate_tilt, keep_clear=contact or None,
+                penalty=args.fall_penalty)
+
+
+def environment_from_args(args):
+    """the env the flags ask for (main's; the --terminate_* flags included)"""
+    terminate = termination_args(args)
     env = build_environment(args.num_envs, max_episode_steps=args.max_episode_steps, warmstart=args.warmstart,
                             push_force=args.push_force, push_interval=args.push_interval, push_duration=args.push_duration,
                             seed=args.random_seed, control_mode=None if args.control_mode == "position" else args.control_mode,
                             gain_scale=args.gain_scale)
+    if terminate is not None:   # (set on the built env: 'auto' needs its model - every body that does not stand on the floor at the start)
+        if terminate["keep_clear"] == ["auto"]:
+            from .termination import fall_bodies
+            terminate["keep_clear"] = fall_bodies(env)
+        env.set_termination(**terminate)
+    return env
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    env = environment_from_args(args)
     agent, _ = train(env, args.num_timesteps, args.random_seed, args.nsteps, args.noptepochs, args.save, use_graphs=args.graphs,
                      preset=args.preset)
     if args.play:

@@ -71,7 +71,7 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
                  max_episode_steps=None, starting_configuration=None, params=None,
                  rank=0, world_size=1, process_group=None, collision="hulls", primitive_max_radius=0.2, row_buffers=1,
                  penalties_in_rows=False, pushes=None, control_mode=None, variable_stiffness=False,
-                 kp_max=actuators.DEFAULT_KP_MAX):
+                 kp_max=actuators.DEFAULT_KP_MAX, terminate=None):
         """num_envs is the GLOBAL env count; this process owns sharding.shard_range(num_envs, rank, world_size).
         row_buffers=2: successive steps write two row blocks in turn (`rows`, `obs`, `rew`, `done_f` always name the
         block of the LAST step), which lets the pipelined all-gather read a block in place.
@@ -79,7 +79,9 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         each step launch and apply them, on top of the wrench of set_external_wrench / apply_external_force.
         control_mode: "position" (default), "velocity", "torque", a sequence of J of them or {joint_name: mode} - what a joint's
         action means (include/trex_batch.h; pybullet's setJointMotorControlArray modes). variable_stiffness: actions are [2J],
-        J commands then J stiffnesses kp in [0, kp_max] (the reference's intended action space, trex_env.py:30)."""
+        J commands then J stiffnesses kp in [0, kp_max] (the reference's intended action space, trex_env.py:30).
+        terminate: dict(head_height=, max_tilt=, keep_clear=, penalty=) - the arguments of set_termination(): episodes end
+        when the robot falls, decided inside the step calls."""
         self.global_num_envs = int(num_envs)
         self.rank, self.world_size, self.process_group = int(rank), int(world_size), process_group
         self.env_lo, self.env_hi = sharding.shard_range(self.global_num_envs, self.rank, self.world_size)
@@ -151,6 +153,9 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         self.pushes = pushes
         if pushes is not None and pushes.num_envs != n:
             raise ValueError("pushes: RandomPushes over %d envs, the env has %d" % (pushes.num_envs, n))
+        self._term_on, self._term_buf = False, None   # fall termination: on?, (reason, values, terminal_obs) buffers of the env
+        if terminate:
+            self.set_termination(**terminate)
 
     # ---- tensor-native API (stays on device, stream-ordered, no host sync)
     def reset_tensor(self, mask=None):
@@ -190,7 +195,11 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
             self.batch.set_external_wrench(w if self._wrench is None else w + self._wrench)
         if len(self._row_blocks) > 1:
             self._point_at(1 - self._row_k)
+        # (with set_termination the call is three launches: step, fall predicate, reset of the fallen - done = 1, the reward of
+        # the finished step less the penalty, observation of the new episode)
         self.batch.step_rows(actions, self.rows, self._penalties, done=self.done)   # (None: the penalties ride in the row block)
+        if self._term_on and self.gains is not None:   # the envs that fell start their episode with new motor gains
+            self.set_motor_gains(**self.gains.draw(self.termination_reason != 0))
         return self.obs, self.rew, self.done
 
     def step_many_tensor(self, actions, rows=None):
@@ -299,6 +308,14 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         self._ep_ret += rew          # (Monitor sums Python floats: f64)
         self._ep_len += 1
         infos = [{} for _ in range(self.num_envs)]
+        if self._term_on:   # a fallen env: why, and the last observation of its episode (obs holds the new episode's first)
+            reason = self.termination_reason.cpu().numpy()
+            fallen = np.flatnonzero(reason)
+            if len(fallen):
+                tobs = self.terminal_obs.cpu().numpy()
+                for i in fallen:
+                    infos[i]["terminal_observation"] = tobs[i].copy()
+                    infos[i]["termination"] = int(reason[i])
         for i in np.flatnonzero(done):
             infos[i]["episode"] = {"r": round(float(self._ep_ret[i]), 6), "l": int(self._ep_len[i]),
                                    "t": round(time.time() - self._t_start, 6)}
@@ -661,6 +678,81 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
     def in_self_collision(self, margin=0.0):
         """[n] bool: some pair of proximity_shapes() is closer than `margin`."""
         return self.self_collision_distance() < margin
+
+    # ---- floor clearance and fall termination (trex_batch_body_clearance / trex_batch_set_termination; no host sync)
+    def _link_bodies(self, links):
+        """links: names or indices of URDF links -> their bodies [K] (numpy int64)"""
+        from .perturb import LinkTable
+        if self._link_table is None:
+            self._link_table = LinkTable.from_model(self.model)
+        return np.array([self._link_table.link_body[self._link_table.index(l)] for l in links], np.int64)
+
+    def body_clearance(self, links=None, lowest=False):
+        """Height of the lowest collision point above the floor, exact over the collision geometry of the physics, at the
+        current state: [n, num_bodies] for every body (links=None), or [n, K] for the bodies of the links `links` (names or
+        indices; one link: [n]). +inf for a body without collision geometry; negative: that deep in the floor. lowest: a tuple
+        (clearance, point [..., 3]) with the world position of that lowest point. One launch, device tensors."""
+        n, nb = self.num_envs, self.model.num_bodies
+        clr = torch.empty(n, nb, device=self.device)
+        low = torch.empty(n, nb, 3, device=self.device) if lowest else None
+        self.batch.body_clearance(clr, low)
+        if links is not None:
+            one = isinstance(links, (str, int, np.integer))
+            idx = torch.as_tensor(self._link_bodies([links] if one else list(links)), device=self.device)
+            clr = clr[:, idx[0]] if one else clr[:, idx]
+            if lowest:
+                low = low[:, idx[0]] if one else low[:, idx]
+        return (clr, low) if lowest else clr
+
+    def set_termination(self, head_height=None, max_tilt=None, keep_clear=None, penalty=0.0):
+        """End an env's episode when the robot falls (trex_batch_set_termination): the head point lower than head_height above
+        the floor; the base tipped more than max_tilt rad from its start orientation; a body of keep_clear closer to the floor
+        than allowed - keep_clear is {link name or index: least clearance} or a sequence of links, which must then stay clear of
+        the floor by the model's contact_margin: "touches" (trex_gym.termination.support_bodies names the feet to leave out).
+        Each None = off; all None switches the feature off. penalty is taken from the reward of the step in which the env falls.
+        The step calls then decide on the device: done = 1, reward less penalty, the env reset at once - its observation is the
+        new episode's first, the last of the old one is in terminal_obs."""
+        cm = None
+        if keep_clear is not None and len(keep_clear):
+            cm = np.full(self.model.num_bodies, np.nan, np.float32)
+            if isinstance(keep_clear, dict):
+                links, mins = list(keep_clear.keys()), [float(v) for v in keep_clear.values()]
+            else:
+                links = list(keep_clear)
+                mins = [self.model.get_param("contact_margin")] * len(links)
+            for b, v in zip(self._link_bodies(links), mins):
+                cm[b] = v if np.isnan(cm[b]) else max(cm[b], v)   # (two links of one body: the stricter)
+        self.batch.set_termination(head_height, max_tilt, cm, penalty)
+        self._term_on = head_height is not None or max_tilt is not None or cm is not None
+        if self._term_on and self._term_buf is None:
+            n = self.num_envs
+            self._term_buf = (torch.zeros(n, dtype=torch.int32, device=self.device), torch.zeros(n, 3, device=self.device),
+                              torch.zeros(n, 3 * self.J, device=self.device))
+
+    def _term_info(self, k):
+        if self._term_buf is None:
+            raise RuntimeError("termination is not enabled (set_termination)")
+        out = self._term_buf[k]
+        self.batch.termination_info(*[out if i == k else None for i in range(3)])
+        return out
+
+    @property
+    def termination_reason(self):
+        """[n] int32 on the device: why each env fell in the last step - bits 1 head height, 2 tilt, 4 clearance; 0: it did not.
+        A buffer of the env, rewritten by the next read."""
+        return self._term_info(0)
+
+    @property
+    def termination_values(self):
+        """[n, 3] on the device, what the last step's decision compared: head height above the floor, cos of the base's tilt,
+        least (clearance - allowed) over the watched bodies (+inf: none watched)."""
+        return self._term_info(1)
+
+    @property
+    def terminal_obs(self):
+        """[n, 3J] on the device: for an env that fell, the last observation of that episode (the row of an env that did not
+        fall in the last step holds the one of its most recent fall, zeros before the first)."""
+        return self._term_info(2)
 
     # ---- ray casts (trex_batch_ray_test: pybullet's rayTestBatch; no host sync; trex_gym.sensors builds patterns)
     def ray_test(self, rays, link=None, positions=False, normals=False, bodies=None, floor=True):

@@ -586,6 +586,59 @@ int trex_batch_set_termination(TrexBatch *batch, float head_height_min, float ti
                                float penalty);
 int trex_batch_termination_info(TrexBatch *batch, int32_t *reason_dev, float *values_dev, float *terminal_obs_dev, void *stream);
 
+/* ---- inverse kinematics (pybullet's calculateInverseKinematics / calculateInverseKinematics2; no reference counterpart: foot
+ *      placement as a task-space action, reference poses for resets and imitation rewards, posing the head or tail)
+ *
+ * Joint angles that bring the probes of `set` (trex_batch_set_link_probes: K task points, 1 <= K <= 8) to per-env targets, by
+ * damped least squares, every env in ONE launch that stays resident for all iterations. The base pose of every env is its current
+ * one and stays fixed; only joint angles are solved for. Several targets are solved together.
+ *   mode_host  [K]        HOST: 1 = the position of the point, 2 = the orientation of the link frame, 3 = both. Task rows
+ *                         M = 3 per position + 3 per orientation, M <= 24, in probe order, a probe's position rows first.
+ *   frame                 TREX_AXES_WORLD, or TREX_AXES_BASE: targets relative to URDF link 0's frame, as trex_batch_link_state
+ *                         defines its BASE pose (link 0 must belong to the base body, which every root link does).
+ *   target_dev [N, K, 7]  xyz + quaternion xyzw per env and target; the quaternion is normalised here, the parts a mode does not
+ *                         use are ignored (they may be NaN).
+ *   q_init_dev [N, J]     where the solve starts, observation order; NULL = the env's current joint angles.
+ *   joint_mask            bit k set: joint k (observation order) may move. The other joints come back bitwise as they went in.
+ *   params                NULL = the defaults of TREX_IK_DEFAULTS.
+ *   q_out_dev  [N, J]     the result; may be q_init_dev itself (no other overlap).
+ *   info_dev   [N, 4]     nullable: [0] the largest position error |p_target - p| over the position targets at q_out, metres;
+ *                         [1] the largest orientation error at q_out, radians; [2] the iterations run; [3] the Euclidean norm
+ *                         of the stacked error e at the start (q_init with the moving joints clamped to their limits).
+ * Per env, with q = q_init, the moving joints clamped to [lower, upper], and then `iterations` times:
+ *   forward kinematics at q; the error e [M]: p_target - p for a position, 2 sign(w) (x, y, z) of quat_target o quat_link^-1
+ *   for an orientation (sign(0) = +1; the rotation vector for small angles), world axes; the residuals: the largest |p_target - p|
+ *   and the largest 2 asin(min(1, |(x, y, z)|)); stop if a tolerance is positive and both residuals are at or below theirs;
+ *   A [M, J]: the joint columns of the point Jacobians (a_j x (p - r_j) and a_j for the joints on the probe's chain, zero
+ *   elsewhere and for joints that may not move); lambda2 = damping^2 + gain |e|^2; (A A^T + lambda2 I) x = e by Cholesky, a
+ *   pivot that is not positive replaced by lambda2; dq = A^T x, scaled as a whole so that max |dq| <= max_step;
+ *   q = clamp(q + dq, lower, upper) for the moving joints.
+ * The residuals of info_dev are evaluated at q_out by one more pass of kinematics.
+ * It behaves like the link kinematics query: read-only (state, observations, the warm-start record, the contact sensor and the
+ * episode counts are untouched; the env's mass scale does not enter), asynchronous and ordered on `stream`, every device buffer
+ * validated before anything is launched, nothing allocated or waited for, from the second call with known buffers ONE plain
+ * kernel launch whatever K and `iterations` are, usable inside a single-stream capture. An env's arithmetic does not depend on N,
+ * on its place in the batch or on the other envs: the same inputs give bitwise the same row. TREX_E_INVALID, nothing launched: a
+ * set outside [0, 8), empty or larger than 8 probes; a mode outside 1..3; M > 24; a frame other than the two; a joint_mask
+ * without a bit among the J joints; iterations outside 1..256; a negative or non-finite parameter; a NULL target or output.
+ * A non-finite target or q_init value gives non-finite q_out (the moving joints) and info for that env only. */
+#define TREX_IK_POSITION 1
+#define TREX_IK_ORIENTATION 2
+#define TREX_IK_MAXPROBES 8
+#define TREX_IK_MAXROWS 24
+typedef struct TrexIkParams {
+  int32_t iterations;   /* 1..256 */
+  float damping;        /* lambda2 = damping^2 + gain |e|^2 */
+  float gain;
+  float max_step;       /* largest joint step of one iteration, rad */
+  float tol_pos;        /* metres; 0 with tol_ori 0: never stop early */
+  float tol_ori;        /* radians */
+} TrexIkParams;
+#define TREX_IK_DEFAULTS {20, 0.01f, 0.1f, 0.2f, 0.0f, 0.0f}
+int trex_batch_inverse_kinematics(TrexBatch *batch, int set, const int32_t *mode_host, int frame, const float *target_dev,
+                                  const float *q_init_dev, uint32_t joint_mask, const TrexIkParams *params, float *q_out_dev,
+                                  float *info_dev, void *stream);
+
 /* diagnostics of the last substep: contact count per env [N] i32 (nullable), summed normal
  * impulse per env [N] f32 (nullable). */
 int trex_batch_contact_stats(TrexBatch *batch, int32_t *count_dev, float *normal_impulse_dev, void *stream);

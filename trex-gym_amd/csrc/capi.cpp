@@ -13,6 +13,7 @@
 #include "device_model.h"
 #include "dynamics.h"
 #include "internal.hpp"
+#include "inverse_kinematics.h"
 #include "link_state.h"
 #include "model.hpp"
 #include "proximity.h"
@@ -40,6 +41,7 @@ struct TrexBatch {
   // step launches take the ACT kernels; the gains buffer [n][TREX_ACT_FLOATS] exists from the first use of any of them and
   // then always holds what the launches are to read - the caller's gains, or the model parameters
   std::vector<int> obs_order;                  // observation slot -> body lane
+  std::vector<int> parent;                     // body -> parent body (trex_batch_inverse_kinematics: which joints carry a probe)
   uint32_t vel_mask = 0u, tor_mask = 0u;       // joints under VELOCITY / TORQUE control, bit b = body lane b
   float kp_max = 0.f;                          // upper clip of an action's stiffness
   float *gains = nullptr;
@@ -67,7 +69,8 @@ struct TrexBatch {
   std::vector<trex::Tf> link_tf;
   // link kinematics (trex_batch_set_link_probes): per set the device table of its probes - body [K], then body<-link rotation and
   // the point in the body frame [K][12]; freed by num_probes 0 and with the batch
-  struct ProbeSet { int n = 0; int32_t *body = nullptr; float *tf = nullptr; };
+  // (host_body: the bodies again, host side, for the chain masks of trex_batch_inverse_kinematics)
+  struct ProbeSet { int n = 0; int32_t *body = nullptr; float *tf = nullptr; std::vector<int32_t> host_body; };
   ProbeSet probes[TREX_LINK_SETS];
   // proximity queries (trex_batch_set_proximity_shapes): ONE device allocation holding the capsules [C][8], their bodies [C], the
   // capsule-pair tests [T] and each pair's first test [P]; freed by num_capsules 0 and with the batch
@@ -509,7 +512,7 @@ int trex_batch_create(const TrexModel *model, int num_envs, int device, TrexBatc
   if (!guard.ok) return fail(TREX_E_HIP, "hipSetDevice failed");
   auto b = std::make_unique<TrexBatch>();
   b->n = num_envs; b->device = device; b->nb = model->host.nb; b->nj = b->nb - 1;
-  b->obs_order = model->host.obs_order;
+  b->obs_order = model->host.obs_order; b->parent = model->host.parent;
   auto alloc = [&](size_t bytes, void **p) -> hipError_t {
     hipError_t r = hipMalloc(p, bytes);
     if (r == hipSuccess) { b->allocs.push_back(*p); r = hipMemset(*p, 0, bytes); }
@@ -1264,7 +1267,7 @@ int trex_batch_set_link_probes(TrexBatch *b, int set, const int32_t *link_host, 
   TrexBatch::ProbeSet &ps = b->probes[set];
   if (ps.body) (void)hipFree(ps.body);
   if (ps.tf) (void)hipFree(ps.tf);
-  ps.n = num_probes; ps.body = body_dev; ps.tf = tf_dev;
+  ps.n = num_probes; ps.body = body_dev; ps.tf = tf_dev; ps.host_body = body;
   return TREX_OK;
 }
 
@@ -1296,6 +1299,61 @@ int trex_batch_link_state(TrexBatch *b, int set, int axes, int proper, const flo
   for (int k = 0; k < 9; k++) a.base_tf[k] = (float)t0.R.m[k];
   a.base_tf[9] = (float)t0.t.x; a.base_tf[10] = (float)t0.t.y; a.base_tf[11] = (float)t0.t.z;
   HIP_TRY(trex_launch_link_state(a, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+// ---- inverse kinematics (inverse_kinematics.hip)
+int trex_batch_inverse_kinematics(TrexBatch *b, int set, const int32_t *mode_host, int frame, const float *target_dev,
+                                  const float *q_init_dev, uint32_t joint_mask, const TrexIkParams *params, float *q_out_dev,
+                                  float *info_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  const std::string me = "trex_batch_inverse_kinematics: ";
+  if (set < 0 || set >= TREX_LINK_SETS)
+    return fail(TREX_E_INVALID, me + "set " + std::to_string(set) + " outside [0, " + std::to_string(TREX_LINK_SETS) + ")");
+  const TrexBatch::ProbeSet &ps = b->probes[set];
+  if (ps.n < 1) return fail(TREX_E_INVALID, me + "probe set " + std::to_string(set) + " is empty (trex_batch_set_link_probes)");
+  if (ps.n > TREX_IK_MAXPROBES)
+    return fail(TREX_E_INVALID, me + "probe set " + std::to_string(set) + " holds " + std::to_string(ps.n) + " probes, at most " +
+                                    std::to_string(TREX_IK_MAXPROBES) + " can be targets");
+  if (!mode_host || !target_dev || !q_out_dev) return fail(TREX_E_INVALID, me + "null argument");
+  if (frame != TREX_AXES_WORLD && frame != TREX_AXES_BASE)
+    return fail(TREX_E_INVALID, me + "frame " + std::to_string(frame) + " is neither TREX_AXES_WORLD nor TREX_AXES_BASE");
+  if (frame == TREX_AXES_BASE && b->link_body[0] != 0) return fail(TREX_E_INVALID, me + "URDF link 0 does not belong to the base body");
+  TrexIkArgs a{};
+  int rows = 0;
+  for (int k = 0; k < ps.n; k++) {
+    const int m = mode_host[k];
+    if (m < 1 || m > 3) return fail(TREX_E_INVALID, me + "mode " + std::to_string(m) + " of target " + std::to_string(k) + " outside 1..3");
+    a.body[k] = (uint8_t)ps.host_body[k]; a.mode[k] = (uint8_t)m; a.row0[k] = (uint8_t)rows;
+    for (int i = ps.host_body[k]; i > 0; i = b->parent[i]) a.chain[k] |= 1u << i;
+    rows += m == 3 ? 6 : 3;
+  }
+  if (rows > TREX_IK_MAXROWS)
+    return fail(TREX_E_INVALID, me + std::to_string(rows) + " task rows, at most " + std::to_string(TREX_IK_MAXROWS));
+  for (int k = 0; k < b->nj; k++)
+    if ((joint_mask >> k) & 1u) a.move_mask |= 1u << b->obs_order[k];
+  if (!a.move_mask) return fail(TREX_E_INVALID, me + "joint_mask lets no joint move");
+  const TrexIkParams defaults = TREX_IK_DEFAULTS;
+  const TrexIkParams &p = params ? *params : defaults;
+  if (p.iterations < 1 || p.iterations > 256)
+    return fail(TREX_E_INVALID, me + "iterations " + std::to_string(p.iterations) + " outside 1..256");
+  for (float v : {p.damping, p.gain, p.max_step, p.tol_pos, p.tol_ori})
+    if (!std::isfinite(v) || v < 0.f) return fail(TREX_E_INVALID, me + "a parameter is negative or not finite");
+  DeviceGuard guard(b->device);
+  const size_t nj = (size_t)b->n * b->nj * sizeof(float);
+  BUF_TRY(target_dev, (size_t)b->n * ps.n * 7 * sizeof(float), "trex_batch_inverse_kinematics: target");
+  BUF_TRY(q_init_dev, nj, "trex_batch_inverse_kinematics: q_init");
+  BUF_TRY(q_out_dev, nj, "trex_batch_inverse_kinematics: q_out");
+  BUF_TRY(info_dev, (size_t)b->n * 4 * sizeof(float), "trex_batch_inverse_kinematics: info");
+  a.model = b->dmodel; a.base = b->arr.base; a.q = b->arr.q;
+  a.probe_tf = ps.tf; a.target = target_dev; a.q_init = q_init_dev; a.q_out = q_out_dev; a.info = info_dev;
+  a.n_envs = b->n; a.nb = b->nb; a.K = ps.n; a.M = rows; a.frame = frame;
+  const trex::Tf &t0 = b->link_tf[0];   // URDF link 0's frame in the base body
+  for (int k = 0; k < 9; k++) a.base_tf[k] = (float)t0.R.m[k];
+  a.base_tf[9] = (float)t0.t.x; a.base_tf[10] = (float)t0.t.y; a.base_tf[11] = (float)t0.t.z;
+  a.iterations = p.iterations; a.damping2 = p.damping * p.damping; a.gain = p.gain; a.max_step = p.max_step;
+  a.tol_pos = p.tol_pos; a.tol_ori = p.tol_ori;
+  HIP_TRY(trex_launch_inverse_kinematics(a, (hipStream_t)stream));
   return TREX_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "chain_walk.h"
 #include "device_math.h"
 #include "link_state.h"
+#include "quat_math.h"
 
 namespace {
 
@@ -26,28 +27,6 @@ __device__ __forceinline__ void tmatvec3(const float *m, const float *v, float *
   const float y = m[1] * v[0] + m[4] * v[1] + m[7] * v[2];
   const float z = m[2] * v[0] + m[5] * v[1] + m[8] * v[2];
   o[0] = x; o[1] = y; o[2] = z;
-}
-
-// rotation matrix -> quaternion xyzw (w >= 0): the conversion of trex_link_transforms_kernel (batch_util.hip), operation for
-// operation. (Kept here and not in device_math.h: that header is hashed into the step kernels' build id.)
-__device__ __forceinline__ void mat_to_quat(const float *R, float *q) {
-  float qx, qy, qz, qw;
-  const float tr = R[0] + R[4] + R[8];
-  if (tr > 0.f) {
-    const float s = sqrtf(tr + 1.f) * 2.f;
-    qw = 0.25f * s; qx = (R[7] - R[5]) / s; qy = (R[2] - R[6]) / s; qz = (R[3] - R[1]) / s;
-  } else if (R[0] >= R[4] && R[0] >= R[8]) {
-    const float s = sqrtf(1.f + R[0] - R[4] - R[8]) * 2.f;
-    qw = (R[7] - R[5]) / s; qx = 0.25f * s; qy = (R[1] + R[3]) / s; qz = (R[2] + R[6]) / s;
-  } else if (R[4] >= R[8]) {
-    const float s = sqrtf(1.f + R[4] - R[0] - R[8]) * 2.f;
-    qw = (R[2] - R[6]) / s; qx = (R[1] + R[3]) / s; qy = 0.25f * s; qz = (R[5] + R[7]) / s;
-  } else {
-    const float s = sqrtf(1.f + R[8] - R[0] - R[4]) * 2.f;
-    qw = (R[3] - R[1]) / s; qx = (R[2] + R[6]) / s; qy = (R[5] + R[7]) / s; qz = 0.25f * s;
-  }
-  const float sg = qw < 0.f ? -1.f : 1.f;
-  q[0] = sg * qx; q[1] = sg * qy; q[2] = sg * qz; q[3] = sg * qw;
 }
 
 }  // namespace

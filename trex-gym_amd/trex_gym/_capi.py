@@ -47,6 +47,7 @@ SYMBOLS = [
     "trex_batch_set_link_probes", "trex_batch_link_state",
     "trex_batch_set_proximity_shapes", "trex_batch_proximity",
     "trex_batch_body_clearance", "trex_batch_set_termination", "trex_batch_termination_info",
+    "trex_batch_inverse_kinematics",
 ]
 
 # every symbol include/trex_policy.h declares (the trainer-side kernels)
@@ -142,6 +143,16 @@ class TrexCamera(C.Structure):     # include/trex_batch.h
 
 
 lib.trex_batch_render.argtypes = [_vp, C.POINTER(TrexCamera), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _vp, _vp, _vp, _vp]
+
+
+class TrexIkParams(C.Structure):   # include/trex_batch.h; the defaults are TREX_IK_DEFAULTS
+    _fields_ = [("iterations", C.c_int32), ("damping", C.c_float), ("gain", C.c_float), ("max_step", C.c_float),
+                ("tol_pos", C.c_float), ("tol_ori", C.c_float)]
+
+
+if hasattr(lib, "trex_batch_inverse_kinematics"):
+    lib.trex_batch_inverse_kinematics.argtypes = [_vp, C.c_int, C.POINTER(C.c_int32), C.c_int, _vp, _vp, C.c_uint32,
+                                                  C.POINTER(TrexIkParams), _vp, _vp, _vp]
 
 
 lib.trex_policy_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]
@@ -567,6 +578,33 @@ class Batch:
         check(lib.trex_batch_link_state(self.h, int(set), int(axes), 1 if proper else 0, self._p(accel, "float32", n * D, "accel"),
                                         ptr(pose, 7, "pose"), ptr(velocity, 6, "velocity"), ptr(acceleration, 6, "acceleration"),
                                         self._stream(stream)))
+
+    def inverse_kinematics(self, set, modes, target, q_out, frame=0, q_init=None, joint_mask=None, info=None, iterations=20,
+                           damping=0.01, gain=0.1, max_step=0.2, tol_pos=0.0, tol_ori=0.0, stream=None):
+        """Joint angles that bring the K probes of set `set` to the targets target [n, K, 7] (xyz + quaternion xyzw), by damped
+        least squares in one launch (trex_batch_inverse_kinematics). modes [K] host: 1 position, 2 orientation, 3 both; frame:
+        0 world, 2 base; q_init [n, J] or None = the current joint angles; joint_mask: bit k = joint k (observation order) may
+        move, None = all; q_out [n, J] (may be q_init) and info [n, 4] (optional) are written in place."""
+        n, J = self.num_envs, self.J
+        modes = np.ascontiguousarray(np.asarray(modes, dtype=np.int64).reshape(-1))
+        K = int(modes.size)
+        if K and (modes.min() < 0 or modes.max() > 255):
+            raise TrexError(E_INVALID, "modes: expected values 1..3")
+        modes = modes.astype(np.int32)
+        if tuple(target.shape) != (n, K, 7):
+            raise TrexError(E_INVALID, "target: expected shape %s, got %s" % ((n, K, 7), tuple(target.shape)))
+        for t, what in ((q_init, "q_init"), (q_out, "q_out")):
+            if t is not None and tuple(t.shape) != (n, J):
+                raise TrexError(E_INVALID, "%s: expected shape %s, got %s" % (what, (n, J), tuple(t.shape)))
+        mask = (1 << J) - 1 if joint_mask is None else int(joint_mask)
+        if not 0 <= mask < 1 << 32:
+            raise TrexError(E_INVALID, "joint_mask: expected a 32-bit mask")
+        prm = TrexIkParams(int(iterations), float(damping), float(gain), float(max_step), float(tol_pos), float(tol_ori))
+        check(lib.trex_batch_inverse_kinematics(self.h, int(set), modes.ctypes.data_as(C.POINTER(C.c_int32)), int(frame),
+                                                self._p(target, "float32", n * K * 7, "target"),
+                                                self._p(q_init, "float32", n * J, "q_init"), mask, C.byref(prm),
+                                                self._p(q_out, "float32", n * J, "q_out"), self._p(info, "float32", n * 4, "info"),
+                                                self._stream(stream)))
 
     def set_proximity_shapes(self, bodies, capsules=None, pairs=None):
         """The batch's proximity table (trex_batch_set_proximity_shapes): bodies [C] the body of each capsule, capsules [C, 7] =

@@ -191,6 +191,49 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
     # pybullet's body ids of this world: the robot and the floor (the ids are this env's own - the reference loads the floor first)
     ROBOT_ID, FLOOR_ID = 0, 1
 
+    def _pybullet_links(self):
+        """(body -> pybullet link index, pybullet link index -> URDF link): a moving body's pybullet link index is the index of the
+        joint that moves it (-1: the base), its link the one whose frame is the body's"""
+        m = self._vec.model
+        if self._ray_links is None:
+            body_link = [-1] * m.num_bodies
+            for k, b in enumerate(m.array("obs_order").astype(int)):
+                body_link[b] = int(m.urdf_joint_indices[k])
+            own = {}
+            ltf = m.array("link_tf").reshape(-1, 12)
+            for l, (name, b) in enumerate(m.links()):   # the body's own link: the one whose frame is the body's
+                off = np.abs(ltf[l, :9] - np.eye(3).reshape(-1)).sum() + np.abs(ltf[l, 9:]).sum()
+                if b not in own or off < own[b][0]:
+                    own[b] = (off, l)
+            self._ray_links = (body_link, {body_link[b]: own[b][1] for b in own})
+        return self._ray_links
+
+    def calculateInverseKinematics2(self, endEffectorLinkIndices, targetPositions, targetOrientations=None, maxNumIterations=20):
+        """pybullet's calculateInverseKinematics2: joint angles, as a list of J floats in pybullet's joint order (ascending joint
+        index), that bring the origins of the links endEffectorLinkIndices (pybullet link indices of moving links, at most 8) to
+        targetPositions (world) - and, where given, their frames to targetOrientations (xyzw) - from the current joint angles,
+        with the base where it is. All targets are solved together by damped least squares (TrexVecEnv.inverse_kinematics,
+        include/trex_batch.h): no null-space or rest-pose terms, no per-joint damping, joint limits by clamping."""
+        _, link_of = self._pybullet_links()
+        idx = [int(i) for i in endEffectorLinkIndices]
+        for i in idx:
+            if i == -1 or i not in link_of:
+                raise ValueError("endEffectorLinkIndex %r is not a moving link of the robot" % (i,))
+        pos = np.asarray(targetPositions, np.float32).reshape(len(idx), 3)
+        ori = None if targetOrientations is None else np.asarray(targetOrientations, np.float32).reshape(len(idx), 4)
+        probes = self._vec.link_probes([link_of[i] for i in idx])
+        try:
+            q, _ = self._vec.inverse_kinematics(probes, pos, ori, iterations=int(maxNumIterations))
+            q = q[0].cpu().numpy().astype(np.float64)
+        finally:
+            probes.close()
+        return [float(q[k]) for k in np.argsort(self._vec.model.urdf_joint_indices, kind="stable")]
+
+    def calculateInverseKinematics(self, endEffectorLinkIndex, targetPosition, targetOrientation=None, maxNumIterations=20):
+        """pybullet's calculateInverseKinematics: calculateInverseKinematics2 of the one link."""
+        return self.calculateInverseKinematics2([endEffectorLinkIndex], [targetPosition],
+                                                None if targetOrientation is None else [targetOrientation], maxNumIterations)
+
     def rayTestBatch(self, rayFromPositions, rayToPositions, parentLinkIndex=-1):
         """pybullet's rayTestBatch: one (objectUniqueId, linkIndex, hitFraction, hitPosition, hitNormal) per ray. The rays are in
         world coordinates, or - parentLinkIndex >= 0, pybullet's joint / link index - in the frame of that link. objectUniqueId:
@@ -203,19 +246,7 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
             raise ValueError("rayFromPositions and rayToPositions differ in length")
         if len(frm) == 0:
             return []
-        m = self._vec.model
-        if self._ray_links is None:   # body -> pybullet link index (= the index of the joint that moves it), and back to a link name
-            body_link = [-1] * m.num_bodies
-            for k, b in enumerate(m.array("obs_order").astype(int)):
-                body_link[b] = int(m.urdf_joint_indices[k])
-            own = {}
-            ltf = m.array("link_tf").reshape(-1, 12)
-            for l, (name, b) in enumerate(m.links()):   # the body's own link: the one whose frame is the body's
-                off = np.abs(ltf[l, :9] - np.eye(3).reshape(-1)).sum() + np.abs(ltf[l, 9:]).sum()
-                if b not in own or off < own[b][0]:
-                    own[b] = (off, l)
-            self._ray_links = (body_link, {body_link[b]: own[b][1] for b in own})
-        body_link, link_of = self._ray_links
+        body_link, link_of = self._pybullet_links()
         if parentLinkIndex not in link_of:
             raise ValueError("parentLinkIndex %r is not a link of the robot (-1: world frame)" % (parentLinkIndex,))
         link = None if parentLinkIndex == -1 else link_of[parentLinkIndex]

@@ -40,6 +40,7 @@ class Centroidal:
 LinkState = collections.namedtuple("LinkState", "position orientation linear_velocity angular_velocity linear_acceleration "
                                                 "angular_acceleration")
 AXES = {"world": 0, "link": 1, "base": 2}
+IkInfo = collections.namedtuple("IkInfo", "position_error orientation_error iterations initial_error")
 ProximityShapes = collections.namedtuple("ProximityShapes", "bodies capsules pairs")
 ClosestPoints = collections.namedtuple("ClosestPoints", "distance point_a point_b normal capsule")
 
@@ -595,6 +596,82 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         acc = torch.empty(self.num_envs, 1, 6, device=self.device)
         self.batch.link_state(h.slot, 0, False, None, None, None, acc, probes=1)
         return acc[:, 0]
+
+    # ---- inverse kinematics (trex_batch_inverse_kinematics: pybullet's calculateInverseKinematics; one launch for every env, all
+    # targets and all iterations, no host sync)
+    def inverse_kinematics(self, probes, positions=None, orientations=None, frame="world", q_init=None, joints=None,
+                           iterations=20, damping=0.01, gain=0.1, max_step=0.2, tol=(0.0, 0.0)):
+        """Joint angles that bring the K <= 8 probes of `probes` (a LinkProbes of link_probes()) to per-env targets, by damped
+        least squares at the envs' current base poses: (q [n, J] in observation order, IkInfo of device tensors).
+        positions [n, K, 3] (or [K, 3], every env alike): where the probe points are to be; orientations [n, K, 4] (xyzw): the
+        orientations of their link frames; either may be None, and a row with a NaN in it means "not constrained" - rows are
+        read on the host once to find them, so every env constrains the same parts. frame: "world", or "base": targets relative
+        to URDF link 0's frame, as link_state(axes="base") reports poses. q_init [n, J]: where the solve starts (None: the
+        current joint angles). joints: the names or observation indices of the joints that may move (None: all); the others
+        come back as they went in. tol = (metres, radians): stop an env early once both residuals are at or below them.
+        info: position_error [n] and orientation_error [n] (the largest residuals at q), iterations [n], initial_error [n]
+        (the norm of the stacked error at the start). step(joint_targets_to_actions(q)) commands the result."""
+        if frame not in ("world", "base"):
+            raise ValueError("frame must be 'world' or 'base'")
+        if not isinstance(probes, LinkProbes) or probes.env is not self or probes.slot is None:
+            raise ValueError("inverse_kinematics: probes must be an open LinkProbes of this env")
+        n, J, K = self.num_envs, self.J, probes.num_probes
+        if positions is None and orientations is None:
+            raise ValueError("inverse_kinematics: give positions, orientations or both")
+
+        def rows(t, width, what):
+            if t is None:
+                return None, np.zeros(K, bool)
+            t = torch.as_tensor(t, dtype=torch.float32)
+            if t.dim() == 2:
+                t = t.unsqueeze(0).expand(n, K, width)
+            if tuple(t.shape) != (n, K, width):
+                raise ValueError("%s must have shape (%d, %d, %d) or (%d, %d), got %s" % (what, n, K, width, K, width, tuple(t.shape)))
+            t = t.to(self.device)
+            return t, (~torch.isnan(t).any(2).any(0)).cpu().numpy()
+
+        pos, has_p = rows(positions, 3, "positions")
+        ori, has_o = rows(orientations, 4, "orientations")
+        modes = has_p * 1 + has_o * 2
+        if (modes == 0).any():
+            raise ValueError("inverse_kinematics: probe %d is not constrained at all" % int(np.argmin(modes)))
+        target = torch.zeros(n, K, 7, device=self.device)
+        target[..., 6] = 1.0
+        if pos is not None:
+            target[..., :3] = pos
+        if ori is not None:
+            target[..., 3:] = ori
+        if joints is None:
+            mask = (1 << J) - 1
+        else:
+            names = self.model.joint_names
+            mask = 0
+            for j in ([joints] if isinstance(joints, (str, int, np.integer)) else joints):
+                k = names.index(j) if isinstance(j, str) else int(j)
+                if not 0 <= k < J:
+                    raise IndexError("joint index %d out of range [0, %d)" % (k, J))
+                mask |= 1 << k
+        if q_init is not None:
+            q_init = torch.as_tensor(q_init, dtype=torch.float32).to(self.device).expand(n, J).contiguous()
+        q, info = torch.empty(n, J, device=self.device), torch.empty(n, 4, device=self.device)
+        self.batch.inverse_kinematics(probes.slot, modes, target.contiguous(), q, AXES[frame], q_init, mask, info, iterations, damping,
+                                      gain, max_step, tol[0], tol[1])
+        return q, IkInfo(info[:, 0], info[:, 1], info[:, 2].to(torch.int32), info[:, 3])
+
+    def joint_targets_to_actions(self, q):
+        """Action rows [n, A] that command the joint angles q [n, J] (observation order; e.g. inverse_kinematics()' result): the
+        inverse of the env's action scaling. A POSITION-mode joint's action IS its target angle, clipped by the step to the
+        joint's limits as it is here; a VELOCITY- or TORQUE-mode joint has no position target: its column is 0. With stiffness
+        actions the J stiffness columns carry the model's motor_kp, clipped to kp_max."""
+        q = torch.as_tensor(q, dtype=torch.float32).to(self.device)
+        lo = torch.as_tensor(self.model.lower.astype(np.float32), device=self.device)
+        hi = torch.as_tensor(self.model.upper.astype(np.float32), device=self.device)
+        position = torch.as_tensor(np.asarray(self.control_modes) == 0, device=self.device)
+        a = torch.where(position, torch.minimum(torch.maximum(q, lo), hi), torch.zeros_like(q))
+        if self.variable_stiffness:
+            kp = min(float(self.model.get_param("motor_kp")), self.kp_max)
+            a = torch.cat([a, torch.full_like(a, kp)], -1)
+        return a
 
     # ---- proximity between bodies (trex_batch_set_proximity_shapes / trex_batch_proximity: pybullet's getClosestPoints between
     # links of the robot; one launch for all pairs, no host sync)

@@ -1,4 +1,4 @@
-"""The renderer (trex_batch_render: csrc/render.hip, render.cpp, the argument path of capi.cpp) at the edges of its tiling, culling
+"""The renderer (trex_batch_render: csrc/render.hip, render.cpp, the argument path of capi_queries.cpp) at the edges of its tiling, culling
 and clipping, and the pose pass it shares with the ray casts (csrc/render_pose.h) on generated models with bent joints. The cases
 are tests/render_cases.py, qualified on the reference alone by tests/test_render_cases_host.py. What each test reaches:
 
@@ -11,7 +11,7 @@ are tests/render_cases.py, qualified on the reference alone by tests/test_render
   test_exact_answers_bitwise        below_floor, all_sky, inside: the one answer every pixel must have
   test_output_subsets               the three nullable outputs, one, two and three at a time
   test_no_write_outside_the_image   ragged frames write no byte before or behind [V, H, W]
-  test_views_grow_and_reuse         render_ids through grow, reuse and NULL (capi.cpp: sync, free, reallocate)
+  test_views_grow_and_reuse         render_ids through grow, reuse and NULL (capi_queries.cpp: sync, free, reallocate)
   test_generated_models_bent        render_pose.h at tree depth 6, oblique non-unit axes, rpy on joint origins, 4 children; hulls
                                     with a dense faceted underside
   test_ray_cast_on_bent_models      the same pose pass and primitive table under trex_batch_ray_test

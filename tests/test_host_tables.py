@@ -1,0 +1,318 @@
+"""The tables of the C-ABI, on the CPU and under the sanitizers: csrc/host_tables.cpp - the arithmetic between the C-ABI's argument
+checks and its HIP calls, which decides what every kernel reads - built with csrc/model.cpp into tests/host/tables_harness.cpp by
+g++ -fsanitize=address,undefined (the flags of tests/test_host_sanitize.py; no HIP, nothing loaded into Python) and run as a child
+process, one run per case. Every table is compared with a numpy restatement written here from the oracle's model dict: integer
+tables exactly, f32 values to the bound stated at the check. No sanitizer report may appear."""
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import proximity_ref as PR
+import synthetic_models as SM
+from conftest import ASSET_URDF, ROOT
+
+CSRC = os.path.join(ROOT, "trex-gym_amd", "csrc")
+TL, MAXD, MAXCH = 32, 6, 4
+INVALID = -1          # TREX_E_INVALID
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("host_tables") / "tables_harness")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-Wall", "-o", exe,
+                           os.path.join(ROOT, "tests", "host", "tables_harness.cpp"), os.path.join(CSRC, "host_tables.cpp"),
+                           os.path.join(CSRC, "model.cpp")])
+    return exe
+
+
+def run(exe, tmp_path, urdf, builder, numbers=()):
+    """-> {table name: float64 array} of one harness run, or ('REFUSED', code, message)"""
+    args = [exe, urdf, builder]
+    if len(numbers):
+        path = os.path.join(str(tmp_path), "numbers.txt")
+        with open(path, "w") as f:
+            f.write(" ".join(repr(float(x)) for x in numbers))
+        args.append(path)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run(args, env=env, capture_output=True, text=True, timeout=120)
+    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-3000:]
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    if r.stdout.startswith("REFUSED "):
+        _, code, msg = r.stdout.rstrip("\n").split(" ", 2)
+        return ("REFUSED", int(code), msg)
+    return {line.split(" ", 1)[0]: np.array(line.split()[1:], np.float64) for line in r.stdout.splitlines()}
+
+
+def refused(out, text):
+    assert isinstance(out, tuple) and out[0] == "REFUSED", out
+    assert out[1] == INVALID and text in out[2], out
+
+
+def ulps(got, want64):
+    """|got - f32(want64)| in units of the last place of f32(want64); got holds f32 values"""
+    want = np.asarray(want64, np.float64).astype(np.float32)
+    return np.abs(np.asarray(got, np.float64) - want.astype(np.float64)) / np.spacing(np.abs(want)).astype(np.float64)
+
+
+def ints(a):
+    return np.asarray(a).astype(np.int64)
+
+
+# ---------------------------------------------------------------------------------------------------------- fill_device_model
+def chain(parent, b):
+    """b and its ancestors, the base excluded"""
+    out = []
+    while b > 0:
+        out.append(b)
+        b = int(parent[b])
+    return out
+
+
+def check_device_model(t, m):
+    nb, parent = m["nb"], m["parent"]
+    depth = [len(chain(parent, b)) for b in range(nb)]
+    assert ints(t["scalars"]).tolist() == [nb, max(depth), m["head_body"], len(m["hull_xyz"]), int(t["scalars"][4])]
+    want = np.full(TL, -1)
+    want[:nb] = parent
+    assert (ints(t["parent"]) == want).all()
+    want = np.full(TL, -1)
+    want[:nb] = depth
+    assert (ints(t["depth"]) == want).all() and (want[:nb] == m["depth"]).all()
+    anc, child = np.full((MAXD, TL), -1), np.full((MAXCH, TL), -1)
+    desc = np.zeros(TL, np.int64)
+    for b in range(nb):
+        for i in chain(parent, b):
+            anc[depth[i] - 1, b] = i
+            desc[i] |= 1 << b
+        kids = [c for c in range(1, nb) if parent[c] == b]
+        child[:len(kids), b] = kids
+    desc[nb:nb + 6] = (1 << nb) - 1
+    assert (ints(t["anc"]).reshape(MAXD, TL) == anc).all()
+    assert (ints(t["child"]).reshape(MAXCH, TL) == child).all()
+    assert (ints(t["desc_mask"]) == desc).all()
+    slot = np.full(TL, -1)
+    slot[m["obs_order"]] = np.arange(nb - 1)
+    assert (ints(t["obs_slot"]) == slot).all()
+    hs = np.asarray(m["hull_start"])
+    assert (ints(t["hull_start"]) == np.concatenate([hs, np.full(TL + 1 - len(hs), hs[-1])])).all()
+    # in-margin masks: cm_pack = offset << 8 | log2(words), by the rule restated in synthetic_models.mask_plan
+    nv = list(np.diff(hs)) + [0] * (TL - nb)
+    want = [(off << 8) | {0: 0, 8: 3, 32: 5}[words] for words, off in SM.mask_plan(nv)]
+    assert ints(t["cm_pack"]).tolist() == want
+    # scan units: their number and bodies by synthetic_models.scan_units
+    gs = np.asarray(m["hull_group_start"])
+    groups = [(g0, g1) for g0, g1 in zip(gs[:-1], gs[1:]) if g1 > g0]
+    count, per_body = SM.scan_units(nv[:nb], len(groups))
+    if per_body:
+        units = [(b, hs[b], hs[b + 1]) for b in range(nb) if hs[b + 1] > hs[b]]
+    else:
+        units = [(max(b for b in range(nb) if hs[b] <= g0 and g1 <= hs[b + 1]), g0, g1) for g0, g1 in groups]
+    assert int(t["scalars"][4]) == count == len(units)
+    pad = [0] * (TL - count)
+    assert ints(t["chunk_body"]).tolist() == [u[0] for u in units] + pad
+    assert ints(t["chunk_v0"]).tolist() == [u[1] for u in units] + pad
+    assert ints(t["chunk_v1"]).tolist() == [u[2] for u in units] + pad
+    # the conservative bounds: every f32 half extent is at least the f64 one, and a unit's f32 box contains its f64 box
+    xyz, rad = m["hull_xyz"], m["hull_radius"]
+    box = t["box_half"].reshape(3, TL)
+    for b in range(nb):
+        if hs[b + 1] > hs[b]:
+            v, r = xyz[hs[b]:hs[b + 1]], rad[hs[b]:hs[b + 1], None]
+            assert (box[:, b] >= 0.5 * ((v + r).max(0) - (v - r).min(0))).all(), b
+    cc, ch = t["chunk_c"].reshape(3, TL), t["chunk_h"].reshape(3, TL)
+    for k, (_, v0, v1) in enumerate(units):
+        lo, hi = (xyz[v0:v1] - rad[v0:v1, None]).min(0), (xyz[v0:v1] + rad[v0:v1, None]).max(0)
+        assert (ch[:, k] >= 0.5 * (hi - lo)).all(), k
+        assert (cc[:, k] - ch[:, k] <= lo).all() and (cc[:, k] + ch[:, k] >= hi).all(), k
+
+
+def test_device_model_trex(harness, tmp_path, model):
+    check_device_model(run(harness, tmp_path, ASSET_URDF, "model"), model)
+
+
+@pytest.mark.parametrize("name", sorted(SM.MODELS))
+def test_device_model_generated(harness, tmp_path, name):
+    path, props, m = SM.compile_both(name, tmp_path / name)
+    t = run(harness, tmp_path, path, "model")
+    check_device_model(t, m)
+    if name == "many_hulls":
+        assert int(t["scalars"][4]) == m["nb"]            # more than 32 hulls: one unit per body
+    if "swept" in props:
+        assert [b for b in range(m["nb"]) if np.diff(m["hull_start"])[b] and not ints(t["cm_pack"])[b] & 0xff] == props["swept"]
+
+
+# ------------------------------------------------------------------------------------------------------------------ proximity
+def prox_numbers(bodies, caps, pairs):
+    rows = np.concatenate([np.asarray(bodies, float)[:, None], np.asarray(caps, float).reshape(len(bodies), 7)], 1)
+    return np.concatenate([[len(bodies)], rows.ravel(), [len(pairs)], np.asarray(pairs, float).ravel()])
+
+
+def check_prox(t, bodies, caps, pairs):
+    bodies, caps, pairs = np.asarray(bodies), np.asarray(caps, np.float64).reshape(-1, 7), np.asarray(pairs).reshape(-1, 2)
+    C, P = len(bodies), len(pairs)
+    want = np.zeros((C, 8), np.float32)
+    want[:, :3], want[:, 3], want[:, 4:7] = caps[:, :3], caps[:, 6], caps[:, 3:6]
+    sphere = ((caps[:, 3:6] - caps[:, :3]) ** 2).sum(1) < 1e-12
+    want[sphere, 4:7] = want[sphere, :3]
+    assert (t["cap"].reshape(C, 8).astype(np.float32) == want).all()
+    assert (ints(t["cap_body"]) == bodies).all()
+    tests, first = [], []
+    for p, (A, B) in enumerate(pairs):
+        first.append(len(tests))
+        tests += [(p << 16) | (ca << 8) | cb for ca in np.flatnonzero(bodies == A) for cb in np.flatnonzero(bodies == B)]
+    assert ints(t["test"]).tolist() == tests and ints(t["pair_first"]).tolist() == first
+    caps_n, pairs_n, tests_n, o_body, o_test, o_first, size = ints(t["scalars"]).tolist()
+    assert (caps_n, pairs_n, tests_n) == (C, P, len(tests))
+    up = lambda x: (x + 15) // 16 * 16
+    assert (o_body, o_test, o_first, size) == (up(32 * C), up(32 * C) + up(4 * C), up(32 * C) + up(4 * C) + up(4 * len(tests)),
+                                               up(32 * C) + up(4 * C) + up(4 * len(tests)) + up(4 * P))
+    return tests, first
+
+
+HAND_BODIES = [0, 1, 2, 0, 2, 2]       # bodies 0, 1, 2 with 2, 1 and 3 capsules
+HAND_PAIRS = [(0, 1), (2, 0), (1, 2)]
+
+
+def hand_caps():
+    rng = np.random.default_rng(7)
+    caps = np.concatenate([rng.uniform(-0.5, 0.5, (6, 6)), rng.uniform(0.01, 0.1, (6, 1))], 1)
+    caps[4, 3:6] = caps[4, :3] + [1e-7, 0, 0]          # |p1 - p0| = 1e-7: a sphere, stored with p1 = p0
+    return caps
+
+
+def test_proximity_hand_table(harness, tmp_path):
+    caps = hand_caps()
+    t = run(harness, tmp_path, ASSET_URDF, "prox", prox_numbers(HAND_BODIES, caps, HAND_PAIRS))
+    tests, first = check_prox(t, HAND_BODIES, caps, HAND_PAIRS)
+    assert first == [0, 2, 8] and len(tests) == 2 + 6 + 3
+    cap = t["cap"].reshape(6, 8)
+    assert (cap[4, 4:7] == cap[4, :3]).all() and np.float32(caps[4, 3]) != np.float32(caps[4, 0])
+
+
+def test_proximity_default_trex_table(harness, tmp_path, model):
+    bodies, caps = PR.fitted_table(model)          # (tests/test_gpu_proximity.py::default_table: the table and all its pairs)
+    pairs = PR.all_pairs(bodies)
+    check_prox(run(harness, tmp_path, ASSET_URDF, "prox", prox_numbers(bodies, caps, pairs)), bodies, caps, pairs)
+
+
+def test_proximity_refusals(harness, tmp_path):
+    go = lambda b, c, p: run(harness, tmp_path, ASSET_URDF, "prox", prox_numbers(b, c, p))
+    caps = hand_caps()
+    refused(go(HAND_BODIES, caps, [(0, 1), (2, 2)]), "pair 1: bodies (2, 2) must be two different bodies of the model")
+    refused(go(HAND_BODIES, caps, [(0, 1), (2, 3)]), "pair 1: a body of the pair has no capsule")
+    bad = caps.copy()
+    bad[3, 6] = -0.01
+    refused(go(HAND_BODIES, bad, HAND_PAIRS), "capsule 3: negative radius")
+    bad = caps.copy()
+    bad[2, 4] = np.nan
+    refused(go(HAND_BODIES, bad, HAND_PAIRS), "capsule 2: value is not finite")
+    many = np.tile(caps[:1], (256, 1))                 # 128 x 128 tests per pair, five pairs: 81920 > 65536
+    refused(go([0] * 128 + [1] * 128, many, [(0, 1), (1, 0)] * 2 + [(0, 1)]), "81920 capsule-pair tests, at most 65536")
+
+
+# ------------------------------------------------------------------------------------------------------------------------- IK
+def ik_links(model):
+    names = model["link_names"]
+    toe = next(i for i, n in enumerate(names) if "toe" in n)
+    head = next(i for i in range(len(names)) if model["link_body"][i] == model["head_body"])
+    return [toe, head, 0]
+
+
+def ik_numbers(links, modes, joint_mask, params=None):
+    return list(links) + list(modes) + [joint_mask] + ([1] + list(params) if params is not None else [0])
+
+
+def test_ik_task(harness, tmp_path, model):
+    links = ik_links(model)
+    bodies = [int(model["link_body"][l]) for l in links]
+    assert bodies[0] > 0 and bodies[1] > 0 and bodies[2] == 0
+    t = run(harness, tmp_path, ASSET_URDF, "ik", [3] + ik_numbers(links, [1, 3, 2], 0b101, (7, 0.5, 0.25, 0.125, 1e-3, 2e-3)))
+    assert ints(t["body"]).tolist() == bodies and ints(t["mode"]).tolist() == [1, 3, 2]
+    assert ints(t["row0"]).tolist() == [0, 3, 9]
+    want = [sum(1 << i for i in chain(model["parent"], b)) for b in bodies]
+    assert ints(t["chain"]).tolist() == want and want[2] == 0 and want[0] != 0 and want[1] != 0
+    move = (1 << int(model["obs_order"][0])) | (1 << int(model["obs_order"][2]))
+    assert ints(t["scalars"]).tolist() == [12, move, 7]
+    assert (t["params"].astype(np.float32) == np.array([np.float32(0.5) * np.float32(0.5), 0.25, 0.125, 1e-3, 2e-3], np.float32)).all()
+    # no params: the defaults of TREX_IK_DEFAULTS {20, 0.01, 0.1, 0.2, 0, 0}
+    t = run(harness, tmp_path, ASSET_URDF, "ik", [3] + ik_numbers(links, [1, 3, 2], 0b101))
+    assert int(t["scalars"][2]) == 20
+    assert (t["params"].astype(np.float32) == np.array([np.float32(0.01) * np.float32(0.01), 0.1, 0.2, 0, 0], np.float32)).all()
+
+
+def test_ik_refusals(harness, tmp_path, model):
+    links = ik_links(model)
+    go = lambda n, *a: run(harness, tmp_path, ASSET_URDF, "ik", [n] + ik_numbers(*a))
+    refused(go(3, links, [1, 0, 2], 1), "mode 0 of target 1 outside 1..3")
+    refused(go(3, links, [4, 3, 2], 1), "mode 4 of target 0 outside 1..3")
+    refused(go(5, [links[0]] * 5, [3] * 5, 1), "30 task rows, at most 24")
+    refused(go(3, links, [1, 3, 2], 0), "joint_mask lets no joint move")
+    refused(go(3, links, [1, 3, 2], 1, (0, 0.01, 0.1, 0.2, 0, 0)), "iterations 0 outside 1..256")
+    refused(go(3, links, [1, 3, 2], 1, (257, 0.01, 0.1, 0.2, 0, 0)), "iterations 257 outside 1..256")
+    refused(go(3, links, [1, 3, 2], 1, (20, -0.01, 0.1, 0.2, 0, 0)), "a parameter is negative or not finite")
+
+
+# --------------------------------------------------------------------------------------------------------------------- probes
+def test_probe_table(harness, tmp_path, model):
+    links = ik_links(model)
+    pts = np.array([[0.1, -0.2, 0.3], [1.5, 0.25, -0.75], [0.0, 0.0, 0.0]])
+    t = run(harness, tmp_path, ASSET_URDF, "probes", [3] + [x for l, p in zip(links, pts) for x in [l] + list(p)])
+    assert ints(t["body"]).tolist() == [int(model["link_body"][l]) for l in links]
+    tf = t["tf"].reshape(3, 12)
+    for k, l in enumerate(links):
+        R, tr = model["link_tf"][l][:9].reshape(3, 3), model["link_tf"][l][9:]
+        assert (tf[k, :9].astype(np.float32) == R.ravel().astype(np.float32)).all()       # the rotation: exactly
+        # the point R x + t in f64, rounded to f32: the order of the f64 sum may differ, so the last f32 bit may
+        assert ulps(tf[k, 9:], R @ pts[k] + tr).max() <= 1.0, (k, tf[k, 9:], R @ pts[k] + tr)
+
+
+def test_probe_refusals(harness, tmp_path, model):
+    n = len(model["link_names"])
+    refused(run(harness, tmp_path, ASSET_URDF, "probes", [2, 0, 0, 0, 0, n, 0, 0, 0]),
+            "probe 1: link %d out of range [0, %d)" % (n, n))
+    refused(run(harness, tmp_path, ASSET_URDF, "probes", [2, 0, 0, 0, 0, -1, 0, 0, 0]), "probe 1: link -1 out of range")
+    refused(run(harness, tmp_path, ASSET_URDF, "probes", [1, 0, 0, np.inf, 0]), "probe 0: local_xyz is not finite")
+
+
+# --------------------------------------------------------------------------------------------------------------------- camera
+def camera_f64(distance, yaw, pitch, fov, width, height):
+    """include/trex_batch.h: eye = target + Rz(yaw) Rx(pitch) (0, -distance, 0), up = Rz(yaw) Rx(pitch) (0, 0, 1), looking at
+    the target; vertical fov, aspect = width / height. The inputs are the f32 values the C struct holds."""
+    y, p = math.radians(yaw), math.radians(pitch)
+    Rz = np.array([[math.cos(y), -math.sin(y), 0], [math.sin(y), math.cos(y), 0], [0, 0, 1]])
+    Rx = np.array([[1, 0, 0], [0, math.cos(p), -math.sin(p)], [0, math.sin(p), math.cos(p)]])
+    off, up0 = Rz @ Rx @ [0, -distance, 0], Rz @ Rx @ [0, 0, 1]
+    fwd = -off / np.linalg.norm(off)
+    right = np.cross(fwd, up0)
+    right /= np.linalg.norm(right)
+    ty = math.tan(math.radians(fov) / 2)
+    return dict(offset=off, fwd=fwd, right=right, up=np.cross(right, fwd), tan=np.array([ty * width / height, ty]))
+
+
+DEFAULT_CAMERA = (10.0, 90.0, -30.0, 60.0, 0.1, 100.0)        # trex_gym/render.py: Camera()
+
+
+@pytest.mark.parametrize("cam", [DEFAULT_CAMERA, (7.5, 37.0, -20.0, 60.0, 0.05, 50.0)])
+def test_camera_basis(harness, tmp_path, cam):
+    f32 = [float(np.float32(x)) for x in cam]
+    t = run(harness, tmp_path, ASSET_URDF, "camera", list(cam) + [0.5, -1.0, 2.0, 84, 48])
+    want = camera_f64(f32[0], f32[1], f32[2], f32[3], 84, 48)
+    for k, w in want.items():
+        # against the f64 formula rounded to f32: at most the last bit
+        err = np.abs(t[k] - w.astype(np.float32).astype(np.float64))
+        assert (err <= np.spacing(np.abs(w).astype(np.float32)).astype(np.float64)).all(), (k, t[k], w, err)
+    B = np.stack([t["right"], t["up"], t["fwd"]])
+    assert np.abs(B @ B.T - np.eye(3)).max() <= 1e-6
+
+
+def test_camera_refusals(harness, tmp_path):
+    go = lambda cam, target=(0, 0, 0): run(harness, tmp_path, ASSET_URDF, "camera", list(cam) + list(target) + [84, 48])
+    needs = "camera needs distance > 0, 0 < fov < 180, 0 < near < far"
+    refused(go((10.0, 90.0, -30.0, 180.0, 0.1, 100.0)), needs)
+    refused(go((10.0, 90.0, -30.0, 60.0, 100.0, 100.0)), needs)
+    refused(go((10.0, 90.0, -30.0, 60.0, 100.0, 0.1)), needs)
+    refused(go(DEFAULT_CAMERA, (0, np.nan, 0)), "camera value is not finite")

@@ -1,0 +1,128 @@
+// What capi.cpp and capi_queries.cpp share: the two handles of include/trex_batch.h, the owner of device memory, the error plumbing.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/trex_batch.h"
+#include "host_tables.hpp"
+#include "internal.hpp"
+#include "link_state.h"
+
+using DeviceGuard = TrexDeviceGuard;
+
+// One device allocation and its owner: move-only, freed by the destructor under the device it was made on. Every allocation a batch
+// owns is a DeviceBuf member of the batch (or an element of `state`), so that an error path frees by returning.
+struct DeviceBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  int device = 0;
+  DeviceBuf() = default;
+  DeviceBuf(DeviceBuf &&o) noexcept : p(o.p), bytes(o.bytes), device(o.device) { o.p = nullptr; o.bytes = 0; }
+  DeviceBuf &operator=(DeviceBuf &&o) noexcept {   // frees what it held
+    if (this != &o) { release(); p = o.p; bytes = o.bytes; device = o.device; o.p = nullptr; o.bytes = 0; }
+    return *this;
+  }
+  ~DeviceBuf() { release(); }
+  void release() {
+    if (!p) return;
+    DeviceGuard guard(device);
+    (void)hipFree(p);
+    p = nullptr; bytes = 0;
+  }
+  // `n` bytes on the CURRENT device (the caller holds a DeviceGuard), zeroed if asked; frees what it held first
+  hipError_t alloc(size_t n, bool zero) {
+    release();
+    hipError_t e = hipGetDevice(&device);
+    if (e == hipSuccess) e = hipMalloc(&p, n);
+    if (e != hipSuccess) { p = nullptr; return e; }
+    bytes = n;
+    return zero ? hipMemset(p, 0, n) : hipSuccess;
+  }
+  template <class T> T *as() const { return (T *)p; }
+  explicit operator bool() const { return p != nullptr; }
+};
+
+struct TrexModel {
+  trex::HostModel host;
+};
+
+struct TrexBatch {
+  int n = 0, device = 0, nb = 0, nj = 0;
+  // the model, the state arrays, the hull points and the link / visual tables: made by trex_batch_create, `dmodel` and `arr` point into them
+  std::vector<DeviceBuf> state;
+  TrexDeviceModel *dmodel = nullptr;
+  TrexBatchArrays arr{};
+  DeviceBuf warm;                              // PGS warm-start records [n][TREX_WARM_WORDS] (device_model.h); warmstart > 0 only
+  DeviceBuf ext;                               // external wrench [n][6][TREX_TL] (trex_batch_set_external_wrench); first non-NULL call on
+  bool ext_on = false;                         // set: the step launches take the EXT kernels
+  const float *wrench() const { return ext_on ? ext.as<float>() : nullptr; }
+  DeviceBuf sens;                              // contact sensor [n][TREX_SENS_FLOATS] (trex_batch_set_contact_sensor); first enable
+  bool sens_on = false;                        // on: every step and reset launch takes the SENS kernels
+  float *sensor() const { return sens_on ? sens.as<float>() : nullptr; }
+  // actuator model (trex_batch_set_control_mode / _set_motor_gains / _set_stiffness_actions): while any of the three is active the
+  // step launches take the ACT kernels; the gains buffer [n][TREX_ACT_FLOATS] exists from the first use of any of them and
+  // then always holds what the launches are to read - the caller's gains, or the model parameters
+  std::vector<int> obs_order;                  // observation slot -> body lane
+  std::vector<int> parent;                     // body -> parent body (trex_batch_inverse_kinematics: which joints carry a probe)
+  uint32_t vel_mask = 0u, tor_mask = 0u;       // joints under VELOCITY / TORQUE control, bit b = body lane b
+  float kp_max = 0.f;                          // upper clip of an action's stiffness
+  DeviceBuf gains;
+  bool gains_set = false, stiff = false;
+  bool act_on() const { return (vel_mask | tor_mask) != 0u || gains_set || stiff; }
+  int action_cols() const { return stiff ? 2 * nj : nj; }
+  float wd = 1.0f, we = 0.005f, wk = 0.002f;  // trex_env.py:42-44
+  bool pen_in_rows = false;                    // trex_batch_set_penalties_in_rows
+  int balance_mode = -1;                       // trex_batch_set_wave_balance: -1 auto, 0 off, 1 on
+  bool balance() const { return balance_mode < 0 ? n >= 2048 : balance_mode != 0; }
+  // renderer (trex_batch_render): the model's hull data, its primitive / plane table made on the first render call
+  std::vector<trex::Vec3> hull_xyz;
+  std::vector<double> hull_radius;
+  std::vector<int> hull_start, hull_group_start;
+  double floor_z = 0;
+  int render_nprim = 0;
+  DeviceBuf render_prim, render_plane;   // TrexRenderPrim [], float4 []: both or neither
+  DeviceBuf render_ids;                  // device copy of the env ids of the last call
+  // dynamics queries (trex_batch_jacobian): body and body<-link transform of every URDF link, host side
+  trex::Links links;
+  // link kinematics (trex_batch_set_link_probes): per set the device table of its probes - body [K], then body<-link rotation and
+  // the point in the body frame [K][12]; freed by num_probes 0 and with the batch
+  // (host_body: the bodies again, host side, for the chain masks of trex_batch_inverse_kinematics)
+  struct ProbeSet { int n = 0; DeviceBuf body, tf; std::vector<int32_t> host_body; };
+  ProbeSet probes[TREX_LINK_SETS];
+  // proximity queries (trex_batch_set_proximity_shapes): ONE device allocation laid out as trex::ProxTable says (`table`: its counts
+  // and offsets, the host blob dropped); freed by num_capsules 0 and with the batch
+  struct Prox { trex::ProxTable table; DeviceBuf blob; } prox;
+  // fall termination (trex_batch_set_termination): the thresholds in force - a NaN is a criterion that is off - and the batch-owned
+  // buffers of the predicate launch, ONE device allocation made by the first enabling call: terminal observations [n][3J], values
+  // [n][3], reasons [n], reset mask [n], and done bytes [n] for a trex_batch_step call that passes no done buffer
+  struct Termination {
+    bool on = false, watch_any = false;
+    float head_min = NAN, cos_tilt = NAN, penalty = 0.f;
+    float clear_min[TREX_TL];
+    DeviceBuf blob;
+    float *tobs = nullptr, *values = nullptr;
+    int32_t *reason = nullptr;
+    uint8_t *mask = nullptr, *done = nullptr;
+  } term;
+  // caller allocations already validated as memory of this device (base address, bytes known to be good):
+  // the hot path pays one hash-free scan of a handful of entries, hipPointerGetAttributes only on a new one
+  std::vector<TrexSeen> seen;
+};
+
+inline int fail(int code, const std::string &msg) { return trex_fail(code, msg); }
+inline int hip_fail(hipError_t e, const char *what) { return fail(TREX_E_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+#define HIP_TRY(expr)                                  \
+  do {                                                 \
+    hipError_t _e = (expr);                            \
+    if (_e != hipSuccess) return hip_fail(_e, #expr);  \
+  } while (0)
+// a caller's buffer `p` of the batch `b` in scope (trex_check_device_buffer)
+#define BUF_TRY(p, bytes, what)                                                                                  \
+  do {                                                                                                           \
+    if (int _c = trex_check_device_buffer(b->device, b->seen, (p), (size_t)(bytes), (what))) return _c;          \
+  } while (0)
+
+inline int check_batch(const TrexBatch *b) { return b ? TREX_OK : fail(TREX_E_INVALID, "null batch"); }

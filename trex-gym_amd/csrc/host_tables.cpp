@@ -1,0 +1,276 @@
+// The tables the kernels read, built on the host: see host_tables.hpp for the include rule (no HIP in here).
+#include "host_tables.hpp"
+
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstring>
+
+namespace trex {
+
+void fill_device_model(const trex::HostModel &h, TrexDeviceModel &d) {
+  std::memset(&d, 0, sizeof d);
+  d.nb = h.nb;
+  d.head_body = h.head_body;
+  d.nv = (int)h.hull_xyz.size();
+  const trex::Params &p = h.prm;
+  const double prm[TP_COUNT] = {p.dt, p.substeps, p.iterations, p.gravity, p.motor_kp, p.motor_kd, p.motor_max_force,
+                                p.floor_z, p.friction, p.erp, p.contact_erp, p.contact_margin, p.link_damping,
+                                p.max_coordinate_velocity, p.max_contacts, p.warmstart};
+  for (int i = 0; i < TP_COUNT; i++) d.prm[i] = (float)prm[i];
+  d.n_substeps = (int)p.substeps; d.n_iterations = (int)p.iterations; d.max_contacts = (int)p.max_contacts;
+  d.inv_dt = 1.0f / (float)p.dt;
+  d.motor_max_impulse = (float)p.motor_max_force * (float)p.dt;
+  d.head_point[0] = (float)h.head_point.x; d.head_point[1] = (float)h.head_point.y; d.head_point[2] = (float)h.head_point.z;
+  d.base_pos0[0] = (float)h.base_start_pos.x; d.base_pos0[1] = (float)h.base_start_pos.y; d.base_pos0[2] = (float)h.base_start_pos.z;
+  for (int c = 0; c < 4; c++) d.base_quat0[c] = (float)h.base_start_quat[c];
+  int maxdepth = 0;
+  for (int l = 0; l < TREX_TL; l++) {
+    d.parent[l] = -1; d.depth[l] = -1; d.obs_slot[l] = -1;
+    for (int k = 0; k < TREX_MAXD; k++) d.anc[k][l] = -1;
+    for (int k = 0; k < TREX_MAXCH; k++) d.child[k][l] = -1;
+    d.mass[l] = 1.0f;
+    d.jrot[0][l] = d.jrot[4][l] = d.jrot[8][l] = 1.0f;
+    d.axis[2][l] = 1.0f;
+    d.inertia[0][l] = d.inertia[3][l] = d.inertia[5][l] = 1.0f;
+  }
+  for (int b = 0; b < h.nb; b++) {
+    d.parent[b] = h.parent[b];
+    d.depth[b] = h.depth[b];
+    maxdepth = std::max(maxdepth, h.depth[b]);
+    for (int i = b; i > 0; i = h.parent[i]) d.anc[h.depth[i] - 1][b] = i;
+    if (b > 0) {
+      int p = h.parent[b];
+      for (int k = 0; k < TREX_MAXCH; k++)
+        if (d.child[k][p] < 0) { d.child[k][p] = b; break; }
+    }
+    const trex::Vec3 &a = h.joint_axis[b], &jp = h.joint_pos[b], &c = h.com[b], &sc = h.sphere_center[b];
+    d.axis[0][b] = (float)a.x; d.axis[1][b] = (float)a.y; d.axis[2][b] = (float)a.z;
+    d.jpos[0][b] = (float)jp.x; d.jpos[1][b] = (float)jp.y; d.jpos[2][b] = (float)jp.z;
+    d.com[0][b] = (float)c.x; d.com[1][b] = (float)c.y; d.com[2][b] = (float)c.z;
+    for (int k = 0; k < 9; k++) d.jrot[k][b] = (float)h.joint_rot[b].m[k];
+    for (int k = 0; k < 6; k++) d.inertia[k][b] = (float)h.inertia[b][k];
+    d.mass[b] = (float)h.mass[b];
+    d.lower[b] = (float)h.q_lower[b]; d.upper[b] = (float)h.q_upper[b]; d.damp[b] = (float)h.joint_damping[b];
+    d.q_start[b] = (float)h.q_start[b];
+    d.sphere[0][b] = (float)sc.x; d.sphere[1][b] = (float)sc.y; d.sphere[2][b] = (float)sc.z;
+    d.sphere[3][b] = (float)h.sphere_radius[b];
+    // round the half extents up one ulp-ish: the bound must stay conservative in f32
+    d.box_half[0][b] = (float)(h.box_half[b].x * (1 + 1e-6) + 1e-7); d.box_half[1][b] = (float)(h.box_half[b].y * (1 + 1e-6) + 1e-7);
+    d.box_half[2][b] = (float)(h.box_half[b].z * (1 + 1e-6) + 1e-7);
+    d.hull_start[b] = h.hull_start[b];
+  }
+  for (int b = h.nb; b <= TREX_TL; b++) d.hull_start[b] = h.hull_start[h.nb];
+  {
+    int off = 0;
+    for (int b = 0; b < TREX_TL; b++) {
+      const int nv = b < h.nb ? h.hull_start[b + 1] - h.hull_start[b] : 0;
+      int lg = nv == 0 ? 0 : (nv <= 256 ? 3 : (nv <= 1024 ? 5 : 0));
+      if (lg && off + (1 << lg) > TREX_CM_WORDS) lg = 0;          // no room left: this body is swept, not masked
+      d.cm_pack[b] = (off << 8) | lg;
+      if (lg) off += 1 << lg;
+    }
+  }
+  {
+    // scan units: the hull groups if they nest in the bodies' vertex ranges and are at most 32, else one per body
+    std::vector<std::array<int, 3>> units;   // body, v0, v1
+    bool ok = h.hull_group_start.size() >= 2;
+    if (ok)
+      for (size_t g = 0; g + 1 < h.hull_group_start.size() && ok; g++) {
+        const int g0 = h.hull_group_start[g], g1 = h.hull_group_start[g + 1];
+        if (g1 <= g0) continue;
+        int body = -1;
+        for (int b = 0; b < h.nb; b++)
+          if (h.hull_start[b] <= g0 && g1 <= h.hull_start[b + 1]) body = b;
+        if (body < 0) ok = false;
+        else units.push_back({body, g0, g1});
+      }
+    if (!ok || units.size() > TREX_TL) {
+      units.clear();
+      for (int b = 0; b < h.nb; b++)
+        if (h.hull_start[b + 1] > h.hull_start[b]) units.push_back({b, h.hull_start[b], h.hull_start[b + 1]});
+    }
+    d.nchunk = (int)units.size();
+    for (int k = 0; k < TREX_TL; k++) { d.chunk_body[k] = 0; d.chunk_v0[k] = 0; d.chunk_v1[k] = 0; }
+    for (size_t k = 0; k < units.size(); k++) {
+      const int v0 = units[k][1], v1 = units[k][2];
+      trex::Vec3 lo{1e300, 1e300, 1e300}, hi{-1e300, -1e300, -1e300};
+      for (int v = v0; v < v1; v++) {
+        const trex::Vec3 &p = h.hull_xyz[v];
+        const double r = h.hull_radius[v];
+        lo = {std::min(lo.x, p.x - r), std::min(lo.y, p.y - r), std::min(lo.z, p.z - r)};
+        hi = {std::max(hi.x, p.x + r), std::max(hi.y, p.y + r), std::max(hi.z, p.z + r)};
+      }
+      d.chunk_body[k] = units[k][0]; d.chunk_v0[k] = v0; d.chunk_v1[k] = v1;
+      d.chunk_c[0][k] = (float)(0.5 * (lo.x + hi.x)); d.chunk_c[1][k] = (float)(0.5 * (lo.y + hi.y)); d.chunk_c[2][k] = (float)(0.5 * (lo.z + hi.z));
+      // half extents rounded up: the bound must stay conservative in f32 (centre rounding included)
+      d.chunk_h[0][k] = (float)(0.5 * (hi.x - lo.x) * (1 + 1e-6) + 1e-6); d.chunk_h[1][k] = (float)(0.5 * (hi.y - lo.y) * (1 + 1e-6) + 1e-6);
+      d.chunk_h[2][k] = (float)(0.5 * (hi.z - lo.z) * (1 + 1e-6) + 1e-6);
+    }
+  }
+  d.maxdepth = maxdepth;
+  for (size_t k = 0; k < h.obs_order.size(); k++) d.obs_slot[h.obs_order[k]] = (int)k;
+  // dof lane l in chain of body b?  joint lanes: b is l or a descendant of l; base dof lanes: every body
+  for (int l = 0; l < TREX_TL; l++) {
+    unsigned m = 0;
+    if (l >= 1 && l < h.nb) {
+      for (int b = 0; b < h.nb; b++)
+        for (int i = b; i > 0; i = h.parent[i])
+          if (i == l) { m |= 1u << b; break; }
+    } else if (l >= h.nb && l < h.nb + 6) {
+      m = (h.nb >= 32) ? 0xffffffffu : ((1u << h.nb) - 1u);
+    }
+    d.desc_mask[l] = m;
+  }
+}
+
+void tf12(const Tf &t, float out[12]) {
+  for (int k = 0; k < 9; k++) out[k] = (float)t.R.m[k];
+  out[9] = (float)t.t.x; out[10] = (float)t.t.y; out[11] = (float)t.t.z;
+}
+
+LinkPoint link_point(const Links &links, int link, const double x[3]) {
+  const Tf &t = links.tf[link];   // body <- link transform of "link_tf"
+  const double tt[3] = {t.t.x, t.t.y, t.t.z};
+  LinkPoint p;
+  p.body = links.body[link];
+  for (int r = 0; r < 3; r++)
+    p.point[r] = (float)(t.R.m[3 * r] * x[0] + t.R.m[3 * r + 1] * x[1] + t.R.m[3 * r + 2] * x[2] + tt[r]);
+  return p;
+}
+
+ProbeTable build_probe_table(const Links &links, const int32_t *link_host, const double *local_xyz_host, int num_probes) {
+  ProbeTable t;
+  t.body.resize((size_t)num_probes);
+  t.tf.resize((size_t)num_probes * 12);
+  for (int k = 0; k < num_probes; k++) {
+    const int link = link_host[k];
+    if (link < 0 || link >= (int)links.body.size())
+      throw Refusal("trex_batch_set_link_probes: probe " + std::to_string(k) + ": link " + std::to_string(link) +
+                    " out of range [0, " + std::to_string(links.body.size()) + ")");
+    const double *x = local_xyz_host + 3 * (size_t)k;
+    for (int c = 0; c < 3; c++)
+      if (!std::isfinite(x[c]))
+        throw Refusal("trex_batch_set_link_probes: probe " + std::to_string(k) + ": local_xyz is not finite");
+    // body <- link rotation, and the point in the frame of the link's body
+    float *o = t.tf.data() + 12 * (size_t)k;
+    tf12(links.tf[link], o);
+    const LinkPoint p = link_point(links, link, x);
+    t.body[k] = p.body;
+    std::memcpy(o + 9, p.point, sizeof p.point);
+  }
+  return t;
+}
+
+ProxTable build_prox_table(int nb, const int32_t *body_host, const double *capsule_host, int num_capsules, const int32_t *pair_host,
+                           int num_pairs) {
+  const std::string me = "trex_batch_set_proximity_shapes: ";
+  if (num_capsules < 0 || num_capsules > TREX_PROX_MAXCAPS)
+    throw Refusal(me + "num_capsules " + std::to_string(num_capsules) + " outside [0, " + std::to_string(TREX_PROX_MAXCAPS) + "]");
+  ProxTable t;
+  if (num_capsules == 0) return t;
+  if (num_pairs < 1 || num_pairs > TREX_PROX_MAXPAIRS)
+    throw Refusal(me + "num_pairs " + std::to_string(num_pairs) + " outside [1, " + std::to_string(TREX_PROX_MAXPAIRS) + "]");
+  if (!body_host || !capsule_host || !pair_host) throw Refusal(me + "null argument");
+  std::vector<float> cap((size_t)num_capsules * 8, 0.f);
+  std::vector<int32_t> cap_body((size_t)num_capsules), pair_first;
+  std::vector<uint32_t> test;
+  std::vector<std::vector<int>> of_body((size_t)nb);   // a body's capsules, table order
+  for (int c = 0; c < num_capsules; c++) {
+    const int body = body_host[c];
+    if (body < 0 || body >= nb)
+      throw Refusal(me + "capsule " + std::to_string(c) + ": body " + std::to_string(body) + " out of range [0, " + std::to_string(nb) + ")");
+    const double *x = capsule_host + 7 * (size_t)c;
+    for (int k = 0; k < 7; k++)
+      if (!std::isfinite(x[k])) throw Refusal(me + "capsule " + std::to_string(c) + ": value is not finite");
+    if (x[6] < 0) throw Refusal(me + "capsule " + std::to_string(c) + ": negative radius");
+    const double dx = x[3] - x[0], dy = x[4] - x[1], dz = x[5] - x[2];
+    const bool sphere = dx * dx + dy * dy + dz * dz < 1e-12;   // (stored with p1 = p0: the kernel then sees a zero axis exactly)
+    float *o = cap.data() + 8 * (size_t)c;
+    for (int k = 0; k < 3; k++) { o[k] = (float)x[k]; o[4 + k] = sphere ? o[k] : (float)x[3 + k]; }
+    o[3] = (float)x[6];
+    cap_body[c] = body;
+    of_body[body].push_back(c);
+  }
+  size_t total = 0;
+  for (int p = 0; p < num_pairs; p++) {
+    const int A = pair_host[2 * p], B = pair_host[2 * p + 1];
+    if (A < 0 || A >= nb || B < 0 || B >= nb || A == B)
+      throw Refusal(me + "pair " + std::to_string(p) + ": bodies (" + std::to_string(A) + ", " + std::to_string(B) +
+                    ") must be two different bodies of the model");
+    if (of_body[A].empty() || of_body[B].empty()) throw Refusal(me + "pair " + std::to_string(p) + ": a body of the pair has no capsule");
+    total += of_body[A].size() * of_body[B].size();
+  }
+  if (total > TREX_PROX_MAXTESTS)
+    throw Refusal(me + std::to_string(total) + " capsule-pair tests, at most " + std::to_string(TREX_PROX_MAXTESTS));
+  test.reserve(total);
+  for (int p = 0; p < num_pairs; p++) {
+    pair_first.push_back((int32_t)test.size());
+    for (int ca : of_body[pair_host[2 * p]])
+      for (int cb : of_body[pair_host[2 * p + 1]]) test.push_back(TREX_PROX_TEST(p, ca, cb));
+  }
+  // one allocation, every part at a multiple of 16 bytes
+  auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  t.caps = num_capsules; t.pairs = num_pairs; t.tests = (int)test.size();
+  t.o_body = up(cap.size() * sizeof(float));
+  t.o_test = t.o_body + up(cap_body.size() * sizeof(int32_t));
+  t.o_first = t.o_test + up(test.size() * sizeof(uint32_t));
+  t.blob.assign(t.o_first + up(pair_first.size() * sizeof(int32_t)), 0);
+  std::memcpy(t.blob.data(), cap.data(), cap.size() * sizeof(float));
+  std::memcpy(t.blob.data() + t.o_body, cap_body.data(), cap_body.size() * sizeof(int32_t));
+  std::memcpy(t.blob.data() + t.o_test, test.data(), test.size() * sizeof(uint32_t));
+  std::memcpy(t.blob.data() + t.o_first, pair_first.data(), pair_first.size() * sizeof(int32_t));
+  return t;
+}
+
+IkTask build_ik_task(const std::vector<int32_t> &probe_body, const std::vector<int> &parent, const std::vector<int> &obs_order,
+                     const int32_t *mode_host, uint32_t joint_mask, const TrexIkParams *params) {
+  const std::string me = "trex_batch_inverse_kinematics: ";
+  IkTask a;
+  for (size_t k = 0; k < probe_body.size(); k++) {
+    const int m = mode_host[k];
+    if (m < 1 || m > 3) throw Refusal(me + "mode " + std::to_string(m) + " of target " + std::to_string(k) + " outside 1..3");
+    a.body[k] = (uint8_t)probe_body[k]; a.mode[k] = (uint8_t)m; a.row0[k] = (uint8_t)a.rows;
+    for (int i = probe_body[k]; i > 0; i = parent[i]) a.chain[k] |= 1u << i;
+    a.rows += m == 3 ? 6 : 3;
+  }
+  if (a.rows > TREX_IK_MAXROWS) throw Refusal(me + std::to_string(a.rows) + " task rows, at most " + std::to_string(TREX_IK_MAXROWS));
+  for (size_t k = 0; k < obs_order.size(); k++)
+    if ((joint_mask >> k) & 1u) a.move_mask |= 1u << obs_order[k];
+  if (!a.move_mask) throw Refusal(me + "joint_mask lets no joint move");
+  const TrexIkParams defaults = TREX_IK_DEFAULTS;
+  const TrexIkParams &p = params ? *params : defaults;
+  if (p.iterations < 1 || p.iterations > 256) throw Refusal(me + "iterations " + std::to_string(p.iterations) + " outside 1..256");
+  for (float v : {p.damping, p.gain, p.max_step, p.tol_pos, p.tol_ori})
+    if (!std::isfinite(v) || v < 0.f) throw Refusal(me + "a parameter is negative or not finite");
+  a.iterations = p.iterations; a.damping2 = p.damping * p.damping; a.gain = p.gain; a.max_step = p.max_step;
+  a.tol_pos = p.tol_pos; a.tol_ori = p.tol_ori;
+  return a;
+}
+
+CameraBasis camera_basis(const TrexCamera &cam, int width, int height) {
+  const float cv[] = {cam.distance, cam.yaw_deg, cam.pitch_deg, cam.fov_deg, cam.near_z, cam.far_z, cam.target[0], cam.target[1], cam.target[2]};
+  for (float x : cv)
+    if (!std::isfinite(x)) throw Refusal("trex_batch_render: camera value is not finite");
+  if (!(cam.distance > 0) || !(cam.fov_deg > 0 && cam.fov_deg < 180) || !(cam.near_z > 0 && cam.far_z > cam.near_z))
+    throw Refusal("trex_batch_render: camera needs distance > 0, 0 < fov < 180, 0 < near < far");
+  // camera (include/trex_batch.h): eye = target + Rz(yaw) Rx(pitch) (0, -distance, 0), up = Rz(yaw) Rx(pitch) (0, 0, 1)
+  const double d2r = 3.14159265358979323846 / 180.0, yw = cam.yaw_deg * d2r, pt = cam.pitch_deg * d2r;
+  const double off[3] = {cam.distance * std::cos(pt) * std::sin(yw), -cam.distance * std::cos(pt) * std::cos(yw),
+                         -cam.distance * std::sin(pt)};
+  const double up0[3] = {std::sin(pt) * std::sin(yw), -std::sin(pt) * std::cos(yw), std::cos(pt)};
+  double f[3] = {-off[0] / cam.distance, -off[1] / cam.distance, -off[2] / cam.distance};
+  double r[3] = {f[1] * up0[2] - f[2] * up0[1], f[2] * up0[0] - f[0] * up0[2], f[0] * up0[1] - f[1] * up0[0]};
+  const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  for (double &x : r) x /= rl;
+  const double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};
+  CameraBasis b;
+  for (int c = 0; c < 3; c++) {
+    b.offset[c] = (float)off[c]; b.fwd[c] = (float)f[c]; b.right[c] = (float)r[c]; b.up[c] = (float)u[c];
+  }
+  const double ty = std::tan(0.5 * cam.fov_deg * d2r);
+  b.tan_y = (float)ty; b.tan_x = (float)(ty * width / height);
+  return b;
+}
+
+}  // namespace trex

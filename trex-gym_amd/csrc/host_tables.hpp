@@ -1,0 +1,68 @@
+// The tables the kernels read, as pure host arithmetic: everything the C-ABI computes between its argument checks and its HIP calls.
+// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h and include/trex_batch.h, and nothing of HIP; it makes
+// no HIP call and knows no batch. It builds with plain g++ -std=c++17, as model.cpp does, so that tests/host/tables_harness.cpp runs
+// it under the sanitizers on a machine without a GPU. A refusal is a thrown Refusal whose text is the C-ABI's message, whole.
+#pragma once
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/trex_batch.h"
+// device_model.h names float4 in one pointer member and includes nothing for it: a unit that has the HIP runtime has the type, a
+// plain C++ unit declares the name (such a unit must not include the HIP runtime afterwards)
+#ifndef HIP_INCLUDE_HIP_AMD_DETAIL_HIP_VECTOR_TYPES_H
+struct float4;
+#endif
+#include "device_model.h"
+#include "model.hpp"
+#include "proximity_limits.h"
+
+namespace trex {
+
+struct Refusal : std::runtime_error {
+  int code;
+  explicit Refusal(const std::string &msg, int c = TREX_E_INVALID) : std::runtime_error(msg), code(c) {}
+};
+
+void fill_device_model(const HostModel &h, TrexDeviceModel &d);
+
+// rotation row-major (9) | translation (3): the [12] layout of every transform a kernel reads
+void tf12(const Tf &t, float out[12]);
+
+// every URDF link: the body it was merged into and its frame in that body's frame (HostModel::link_body / link_tf)
+struct Links { std::vector<int> body; std::vector<Tf> tf; };
+// a point given in a link's frame, in the frame of the link's body
+struct LinkPoint { int body; float point[3]; };
+LinkPoint link_point(const Links &links, int link, const double local_xyz[3]);
+
+// trex_batch_set_link_probes: body [K], and body <- link rotation (9) | the point in the body frame (3) [K][12]
+struct ProbeTable { std::vector<int32_t> body; std::vector<float> tf; };
+ProbeTable build_probe_table(const Links &links, const int32_t *link, const double *local_xyz, int num_probes);
+
+// trex_batch_set_proximity_shapes: ONE blob, every part at a multiple of 16 bytes - capsules [C][8] at 0, their bodies [C] at
+// o_body, the TREX_PROX_TEST words [T] in (pair, capsule of A, capsule of B) order at o_test, each pair's first test [P] at o_first.
+// num_capsules 0 gives the empty table.
+struct ProxTable {
+  int caps = 0, pairs = 0, tests = 0;
+  size_t o_body = 0, o_test = 0, o_first = 0;
+  std::vector<char> blob;
+};
+ProxTable build_prox_table(int nb, const int32_t *body, const double *capsule, int num_capsules, const int32_t *pair, int num_pairs);
+
+// trex_batch_inverse_kinematics: per probe its body, mode, first task row and chain mask (bit b: body b is the probe's body or an
+// ancestor of it, the base excluded); the joints that may move, by body lane; the parameters, checked, damping squared
+struct IkTask {
+  uint8_t body[TREX_IK_MAXPROBES] = {}, mode[TREX_IK_MAXPROBES] = {}, row0[TREX_IK_MAXPROBES] = {};
+  uint32_t chain[TREX_IK_MAXPROBES] = {};
+  uint32_t move_mask = 0u;
+  int rows = 0, iterations = 0;
+  float damping2 = 0.f, gain = 0.f, max_step = 0.f, tol_pos = 0.f, tol_ori = 0.f;
+};
+IkTask build_ik_task(const std::vector<int32_t> &probe_body, const std::vector<int> &parent, const std::vector<int> &obs_order,
+                     const int32_t *mode, uint32_t joint_mask, const TrexIkParams *params);
+
+// trex_batch_render: the camera of include/trex_batch.h, checked, as the renderer's basis
+struct CameraBasis { float offset[3], fwd[3], right[3], up[3], tan_x, tan_y; };
+CameraBasis camera_basis(const TrexCamera &cam, int width, int height);
+
+}  // namespace trex

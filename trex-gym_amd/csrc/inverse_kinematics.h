@@ -1,5 +1,5 @@
-// Batched inverse kinematics (trex_batch_inverse_kinematics): launch arguments shared by capi.cpp and inverse_kinematics.hip.
-// The step kernels do not see any of this; the query only reads the batch state.
+// Batched inverse kinematics (trex_batch_inverse_kinematics): launch arguments shared by capi_queries.cpp and inverse_kinematics.hip;
+// the per-probe task values are built by host_tables.cpp. The step kernels do not see any of this; the query only reads the batch state.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

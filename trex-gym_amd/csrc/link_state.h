@@ -1,5 +1,5 @@
-// Batched link kinematics (trex_batch_set_link_probes / trex_batch_link_state): launch arguments shared by capi.cpp and
-// link_state.hip. The step kernels do not see any of this; the query only reads the batch state.
+// Batched link kinematics (trex_batch_set_link_probes / trex_batch_link_state): launch arguments shared by capi_queries.cpp and
+// link_state.hip; the probe table is built by host_tables.cpp. The step kernels do not see any of this; the query only reads the batch state.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

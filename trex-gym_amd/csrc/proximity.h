@@ -1,20 +1,15 @@
 // Batched closest-point queries between bodies (trex_batch_set_proximity_shapes / trex_batch_proximity): launch arguments and the
-// table layout shared by capi.cpp and proximity.hip. The step kernels do not see any of this; the query only reads the batch state.
+// table layout shared by capi_queries.cpp and proximity.hip; the table itself is built by host_tables.cpp, which shares the limits of
+// proximity_limits.h. The step kernels do not see any of this; the query only reads the batch state.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "device_model.h"
+#include "proximity_limits.h"      /* TREX_PROX_MAXCAPS / _MAXPAIRS / _MAXTESTS, TREX_PROX_TEST */
 
 #define TREX_PROX_BLOCK 256        /* lanes per workgroup: one env per workgroup */
-#define TREX_PROX_MAXCAPS 256      /* capsules per table */
-#define TREX_PROX_MAXPAIRS 1024    /* body pairs per table */
-#define TREX_PROX_MAXTESTS 65536   /* capsule-pair tests per table: the sum over pairs of capsules(A) x capsules(B) */
 #define TREX_PROX_EPS 1e-6f        /* axis distance below which the normal is (0, 0, 1) */
-
-/* One capsule-pair test, host-built, sorted by (pair, capsule of A, capsule of B): pair << 16 | capsule of A << 8 | capsule of B
- * (capsule = index into the table). The index of a test in the list is its rank in the tie rule. */
-#define TREX_PROX_TEST(pair, ca, cb) (((uint32_t)(pair) << 16) | ((uint32_t)(ca) << 8) | (uint32_t)(cb))
 
 struct TrexProxArgs {
   const TrexDeviceModel *model;

@@ -639,6 +639,62 @@ int trex_batch_inverse_kinematics(TrexBatch *batch, int set, const int32_t *mode
                                   const float *q_init_dev, uint32_t joint_mask, const TrexIkParams *params, float *q_out_dev,
                                   float *info_dev, void *stream);
 
+/* ---- observation channels (no reference counterpart: the reference's observation is [q | qd | torque] alone): what the base does
+ * - its tilt, velocity and height -, where points of the robot are and whether a foot presses on the floor, as extra columns of
+ * the row a policy reads. The step and reset calls keep writing their own rows; ONE more launch composes the extended row
+ *   out row e = rows row e [0, 3J) | the E channel columns | rows row e [3J, 3J + tail)
+ * with tail = 2 (reward, done), or 5 with trex_batch_set_penalties_in_rows. Every channel is evaluated at the batch's CURRENT state:
+ * after a step the post-step state, and for an env the launch reset the new episode's - the instant of the 3J columns beside them.
+ *
+ * A channel: kind, link (URDF link index where the kind names one), local_xyz (a point in that link's frame) and scale - every
+ * value of the channel is multiplied by it. "Base axes" are TREX_AXES_BASE of the link kinematics: URDF link 0's frame.
+ *   PROJECTED_GRAVITY      3  world (0, 0, -1) in base axes
+ *   BASE_LINEAR_VELOCITY   3  of the origin of URDF link 0, in base axes
+ *   BASE_ANGULAR_VELOCITY  3  in base axes
+ *   BASE_HEIGHT            1  world z of the origin of URDF link 0 - floor_z
+ *   POINT_POSITION         3  the point local_xyz of `link` relative to the origin of URDF link 0, in base axes: the pose xyz of
+ *                             the link kinematics query with TREX_AXES_BASE
+ *   POINT_VELOCITY         3  its linear velocity in base axes, as that query reports it
+ *   POINT_HEIGHT           1  its world z - floor_z
+ *   CONTACT_FORCE          1  fz of the contact sensor for the body of `link` (needs trex_batch_set_contact_sensor on)
+ *   PREV_ACTION            A  the env's row of actions_dev as passed (not clipped); zeros when actions_dev is NULL and for an env
+ *                             whose done column in `rows` is non-zero: a new episode has no previous action
+ *   EXTERNAL        link = k  the next k >= 1 columns of the env's row of extern_dev, copied: ray fractions, distances, anything
+ *                             the caller computed joins the row in the same launch
+ * At most 64 channels, and 3J + E <= 512. */
+#define TREX_OBS_PROJECTED_GRAVITY 0
+#define TREX_OBS_BASE_LINEAR_VELOCITY 1
+#define TREX_OBS_BASE_ANGULAR_VELOCITY 2
+#define TREX_OBS_BASE_HEIGHT 3
+#define TREX_OBS_POINT_POSITION 4
+#define TREX_OBS_POINT_VELOCITY 5
+#define TREX_OBS_POINT_HEIGHT 6
+#define TREX_OBS_CONTACT_FORCE 7
+#define TREX_OBS_PREV_ACTION 8
+#define TREX_OBS_EXTERNAL 9
+#define TREX_OBS_KINDS 10
+typedef struct TrexObsChannel {
+  int32_t kind, link;
+  float local_xyz[3];
+  float scale;
+} TrexObsChannel;
+/* Set the batch's channels (host values, copied; synchronises the device; replaces the previous set); num_channels 0 clears.
+ * extra_dim_out (nullable) <- E. TREX_E_INVALID, nothing changed: an unknown kind, a link out of range, a local_xyz or scale that
+ * is not finite, k < 1, more than 64 channels, 3J + E > 512. PREV_ACTION takes the batch's action width of this moment: set the
+ * channels after trex_batch_set_stiffness_actions. */
+int trex_batch_set_observation(TrexBatch *batch, const TrexObsChannel *channels_host, int num_channels, int *extra_dim_out);
+/* 3J + E; 3J while no channels are set */
+int trex_batch_observation_dim(const TrexBatch *batch);
+/* Compose the extended rows (above) of all N envs into out_rows_dev (row e at + e * out_stride, out_stride >= 3J + E + tail) from
+ * rows_dev (what a step or reset call wrote; row_stride >= 3J + tail), actions_dev [N, A] (nullable) and extern_dev (row e at
+ * + e * extern_stride; nullable unless an EXTERNAL channel is set, extern_stride >= the sum of their widths). One launch,
+ * asynchronous on `stream`, capturable from the second call with the same buffers on. Reads the state, the contact sensor and its
+ * arguments; writes the 3J + E + tail columns of every out row and nothing else. TREX_E_INVALID, nothing launched: no channels
+ * set, a stride too small, a CONTACT_FORCE channel with the sensor off, a missing or short buffer, host memory, out_rows_dev
+ * overlapping rows_dev, an action width that is no longer the one the channels were set with. */
+int trex_batch_compose_rows(TrexBatch *batch, const float *rows_dev, int row_stride, const float *actions_dev,
+                            const float *extern_dev, int extern_stride, float *out_rows_dev, int out_stride, void *stream);
+
 /* diagnostics of the last substep: contact count per env [N] i32 (nullable), summed normal
  * impulse per env [N] f32 (nullable). */
 int trex_batch_contact_stats(TrexBatch *batch, int32_t *count_dev, float *normal_impulse_dev, void *stream);

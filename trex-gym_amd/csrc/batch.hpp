@@ -95,6 +95,9 @@ struct TrexBatch {
   // proximity queries (trex_batch_set_proximity_shapes): ONE device allocation laid out as trex::ProxTable says (`table`: its counts
   // and offsets, the host blob dropped); freed by num_capsules 0 and with the batch
   struct Prox { trex::ProxTable table; DeviceBuf blob; } prox;
+  // observation channels (trex_batch_set_observation): ONE device allocation laid out as trex::ObsTable says (`table`: its counts
+  // and offsets, the host blob dropped); freed by num_channels 0 and with the batch
+  struct Observation { trex::ObsTable table; DeviceBuf blob; } observation;
   // fall termination (trex_batch_set_termination): the thresholds in force - a NaN is a criterion that is off - and the batch-owned
   // buffers of the predicate launch, ONE device allocation made by the first enabling call: terminal observations [n][3J], values
   // [n][3], reasons [n], reset mask [n], and done bytes [n] for a trex_batch_step call that passes no done buffer

@@ -6,6 +6,7 @@
 #include "batch.hpp"
 #include "dynamics.h"
 #include "inverse_kinematics.h"
+#include "observation.h"
 #include "proximity.h"
 #include "raycast.h"
 #include "render.h"
@@ -425,6 +426,77 @@ int trex_batch_proximity(TrexBatch *b, float *distance_dev, float *point_a_dev, 
   a.distance = distance_dev; a.point_a = point_a_dev; a.point_b = point_b_dev; a.normal = normal_dev; a.capsule = capsule_dev;
   a.num_capsules = pt.caps; a.num_pairs = pt.pairs; a.num_tests = pt.tests;
   HIP_TRY(trex_launch_proximity(a, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+// ---- observation channels (observation.hip)
+int trex_batch_set_observation(TrexBatch *b, const TrexObsChannel *channels_host, int num_channels, int *extra_dim_out) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  trex::ObsTable t;
+  if (int c = built([&] { t = trex::build_obs_table(b->links, b->nj, b->action_cols(), channels_host, num_channels); })) return c;
+  DeviceGuard guard(b->device);
+  DeviceBuf blob;
+  if (t.channels > 0) {
+    HIP_TRY(blob.alloc(t.blob.size(), false));
+    HIP_TRY(hipMemcpy(blob.p, t.blob.data(), blob.bytes, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipDeviceSynchronize());   // (no launch still reads the table this one replaces; the new one is in place on every stream)
+  t.blob = {};
+  if (extra_dim_out) *extra_dim_out = t.extra;
+  b->observation.blob = std::move(blob);   // (frees the old table)
+  b->observation.table = std::move(t);
+  return TREX_OK;
+}
+
+int trex_batch_observation_dim(const TrexBatch *b) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  return 3 * b->nj + b->observation.table.extra;
+}
+
+int trex_batch_compose_rows(TrexBatch *b, const float *rows_dev, int row_stride, const float *actions_dev, const float *extern_dev,
+                            int extern_stride, float *out_rows_dev, int out_stride, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  const std::string me = "trex_batch_compose_rows: ";
+  const trex::ObsTable &ot = b->observation.table;
+  if (ot.channels < 1) return fail(TREX_E_INVALID, me + "no channels are set (trex_batch_set_observation)");
+  if (!rows_dev || !out_rows_dev) return fail(TREX_E_INVALID, me + "rows or out_rows is null");
+  const int nobs = 3 * b->nj, tail = b->pen_in_rows ? 5 : 2, width = nobs + ot.extra + tail;
+  if (row_stride < nobs + tail) return fail(TREX_E_INVALID, me + "row_stride < 3J + 2 (3J + 5 with penalties in rows)");
+  if (out_stride < width) return fail(TREX_E_INVALID, me + "out_stride " + std::to_string(out_stride) + " < " + std::to_string(width) +
+                                                          " = 3J + E + the tail");
+  if (ot.contact && !b->sens_on) return fail(TREX_E_INVALID, me + "a CONTACT_FORCE channel is set and the contact sensor is off (trex_batch_set_contact_sensor)");
+  if (ot.actions && ot.action_cols != b->action_cols())
+    return fail(TREX_E_INVALID, me + "the action rows are " + std::to_string(b->action_cols()) + " wide, the PREV_ACTION channel was set with " +
+                                    std::to_string(ot.action_cols) + " (set the channels again)");
+  if (ot.extern_cols > 0) {
+    if (!extern_dev) return fail(TREX_E_INVALID, me + "an EXTERNAL channel is set and extern is null");
+    if (extern_stride < ot.extern_cols)
+      return fail(TREX_E_INVALID, me + "extern_stride " + std::to_string(extern_stride) + " < " + std::to_string(ot.extern_cols) +
+                                      ", the columns of the EXTERNAL channels");
+  }
+  const size_t n = (size_t)b->n;
+  const size_t rows_bytes = ((n - 1) * row_stride + nobs + tail) * sizeof(float), out_bytes = ((n - 1) * out_stride + width) * sizeof(float);
+  {
+    const char *r = (const char *)rows_dev, *o = (const char *)out_rows_dev;
+    if (o < r + rows_bytes && r < o + out_bytes) return fail(TREX_E_INVALID, me + "out_rows overlaps rows");
+  }
+  DeviceGuard guard(b->device);
+  BUF_TRY(rows_dev, rows_bytes, "trex_batch_compose_rows: rows");
+  BUF_TRY(out_rows_dev, out_bytes, "trex_batch_compose_rows: out_rows");
+  if (ot.actions) BUF_TRY(actions_dev, n * ot.action_cols * sizeof(float), "trex_batch_compose_rows: actions");
+  if (ot.extern_cols > 0) BUF_TRY(extern_dev, ((n - 1) * extern_stride + ot.extern_cols) * sizeof(float), "trex_batch_compose_rows: extern");
+  TrexObsArgs a = query_args<TrexObsArgs>(b);
+  const char *blob = b->observation.blob.as<char>();
+  a.chan = (const TrexObsChan *)blob; a.col_chan = (const uint8_t *)(blob + ot.o_col);
+  a.rows = rows_dev; a.actions = ot.actions ? actions_dev : nullptr; a.ext = ot.extern_cols > 0 ? extern_dev : nullptr;
+  a.sens = ot.contact ? b->sens.as<float>() : nullptr;
+  a.out = out_rows_dev;
+  a.D = 6 + b->nj; a.nobs = nobs; a.extra = ot.extra; a.tail = tail;
+  a.row_stride = row_stride; a.out_stride = out_stride; a.ext_stride = extern_stride; a.act_cols = ot.action_cols;
+  a.base_body = b->links.body[0];   // URDF link 0's frame in its body
+  trex::tf12(b->links.tf[0], a.base_tf);
+  a.body_mask = ot.body_mask | (1u << a.base_body);
+  HIP_TRY(trex_launch_observation(a, (hipStream_t)stream));
   return TREX_OK;
 }
 

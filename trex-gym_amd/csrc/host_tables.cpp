@@ -248,6 +248,66 @@ IkTask build_ik_task(const std::vector<int32_t> &probe_body, const std::vector<i
   return a;
 }
 
+ObsTable build_obs_table(const Links &links, int nj, int action_cols, const TrexObsChannel *channels, int num_channels) {
+  const std::string me = "trex_batch_set_observation: ";
+  if (num_channels < 0 || num_channels > TREX_OBS_MAXCHANNELS)
+    throw Refusal(me + "num_channels " + std::to_string(num_channels) + " outside [0, " + std::to_string(TREX_OBS_MAXCHANNELS) + "]");
+  ObsTable t;
+  if (num_channels == 0) return t;
+  if (!channels) throw Refusal(me + "null argument");
+  std::vector<TrexObsChan> chan((size_t)num_channels);
+  std::vector<uint8_t> col_chan;
+  const int num_links = (int)links.body.size();
+  for (int k = 0; k < num_channels; k++) {
+    const TrexObsChannel &c = channels[k];
+    const std::string ck = me + "channel " + std::to_string(k) + ": ";
+    if (c.kind < 0 || c.kind >= TREX_OBS_KINDS) throw Refusal(ck + "unknown kind " + std::to_string(c.kind));
+    for (int i = 0; i < 3; i++)
+      if (!std::isfinite(c.local_xyz[i])) throw Refusal(ck + "local_xyz is not finite");
+    if (!std::isfinite(c.scale)) throw Refusal(ck + "scale is not finite");
+    TrexObsChan &o = chan[k];
+    std::memset(&o, 0, sizeof o);
+    o.kind = c.kind; o.scale = c.scale;
+    o.tf[0] = o.tf[4] = o.tf[8] = 1.0f;
+    const bool point = c.kind == TREX_OBS_POINT_POSITION || c.kind == TREX_OBS_POINT_VELOCITY || c.kind == TREX_OBS_POINT_HEIGHT;
+    if (point || c.kind == TREX_OBS_CONTACT_FORCE) {
+      if (c.link < 0 || c.link >= num_links)
+        throw Refusal(ck + "link " + std::to_string(c.link) + " out of range [0, " + std::to_string(num_links) + ")");
+      const double x[3] = {c.local_xyz[0], c.local_xyz[1], c.local_xyz[2]};
+      const LinkPoint p = link_point(links, c.link, x);
+      tf12(links.tf[c.link], o.tf);
+      o.body = p.body;
+      std::memcpy(o.point, p.point, sizeof p.point);
+      if (point) t.body_mask |= 1u << p.body;
+    }
+    switch (c.kind) {
+      case TREX_OBS_BASE_HEIGHT: case TREX_OBS_POINT_HEIGHT: o.width = 1; break;
+      case TREX_OBS_CONTACT_FORCE: o.width = 1; t.contact = true; break;
+      case TREX_OBS_PREV_ACTION: o.width = action_cols; t.actions = true; break;
+      case TREX_OBS_EXTERNAL:
+        if (c.link < 1) throw Refusal(ck + "an EXTERNAL channel needs link = k >= 1 columns, got " + std::to_string(c.link));
+        o.width = c.link;
+        o.body = t.extern_cols;
+        break;
+      default: o.width = 3;
+    }
+    const long long total = 3LL * nj + t.extra + o.width;   // (k may be anything up to INT_MAX)
+    if (total > TREX_OBS_MAXDIM)
+      throw Refusal(me + "3J + E = " + std::to_string(total) + " observation columns with channel " + std::to_string(k) + ", at most " +
+                    std::to_string(TREX_OBS_MAXDIM));
+    if (c.kind == TREX_OBS_EXTERNAL) t.extern_cols += o.width;
+    o.col0 = t.extra;
+    t.extra += o.width;
+    col_chan.insert(col_chan.end(), (size_t)o.width, (uint8_t)k);
+  }
+  t.channels = num_channels; t.action_cols = action_cols;
+  t.o_col = (chan.size() * sizeof(TrexObsChan) + 15) & ~(size_t)15;
+  t.blob.assign(t.o_col + ((col_chan.size() + 15) & ~(size_t)15), 0);
+  std::memcpy(t.blob.data(), chan.data(), chan.size() * sizeof(TrexObsChan));
+  std::memcpy(t.blob.data() + t.o_col, col_chan.data(), col_chan.size());
+  return t;
+}
+
 CameraBasis camera_basis(const TrexCamera &cam, int width, int height) {
   const float cv[] = {cam.distance, cam.yaw_deg, cam.pitch_deg, cam.fov_deg, cam.near_z, cam.far_z, cam.target[0], cam.target[1], cam.target[2]};
   for (float x : cv)

@@ -1,5 +1,5 @@
 // The tables the kernels read, as pure host arithmetic: everything the C-ABI computes between its argument checks and its HIP calls.
-// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h and include/trex_batch.h, and nothing of HIP; it makes
+// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h and include/trex_batch.h, and nothing of HIP; it makes
 // no HIP call and knows no batch. It builds with plain g++ -std=c++17, as model.cpp does, so that tests/host/tables_harness.cpp runs
 // it under the sanitizers on a machine without a GPU. A refusal is a thrown Refusal whose text is the C-ABI's message, whole.
 #pragma once
@@ -15,6 +15,7 @@ struct float4;
 #endif
 #include "device_model.h"
 #include "model.hpp"
+#include "observation_limits.h"
 #include "proximity_limits.h"
 
 namespace trex {
@@ -60,6 +61,20 @@ struct IkTask {
 };
 IkTask build_ik_task(const std::vector<int32_t> &probe_body, const std::vector<int> &parent, const std::vector<int> &obs_order,
                      const int32_t *mode, uint32_t joint_mask, const TrexIkParams *params);
+
+// trex_batch_set_observation: ONE blob - the channels [C] as TrexObsChan at 0, then at o_col, a multiple of 16 bytes, the channel
+// of every extra column [E] as a byte: column 3J + c of the composed row belongs to channel col_chan[c]. nj, action_cols: the
+// batch's J and the width of its action rows (what PREV_ACTION copies). num_channels 0 gives the empty table.
+struct ObsTable {
+  int channels = 0, extra = 0;          // C, E
+  int extern_cols = 0;                  // the sum of the EXTERNAL channels' widths: the columns read of a row of extern_dev
+  int action_cols = 0;                  // the action width the table was built with
+  bool contact = false, actions = false;   // a CONTACT_FORCE / PREV_ACTION channel is set
+  uint32_t body_mask = 0u;              // bit b: a channel names body b (the body of URDF link 0 not included)
+  size_t o_col = 0;
+  std::vector<char> blob;
+};
+ObsTable build_obs_table(const Links &links, int nj, int action_cols, const TrexObsChannel *channels, int num_channels);
 
 // trex_batch_render: the camera of include/trex_batch.h, checked, as the renderer's basis
 struct CameraBasis { float offset[3], fwd[3], right[3], up[3], tan_x, tan_y; };

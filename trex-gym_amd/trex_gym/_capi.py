@@ -48,6 +48,7 @@ SYMBOLS = [
     "trex_batch_set_proximity_shapes", "trex_batch_proximity",
     "trex_batch_body_clearance", "trex_batch_set_termination", "trex_batch_termination_info",
     "trex_batch_inverse_kinematics",
+    "trex_batch_set_observation", "trex_batch_observation_dim", "trex_batch_compose_rows",
 ]
 
 # every symbol include/trex_policy.h declares (the trainer-side kernels)
@@ -153,6 +154,16 @@ class TrexIkParams(C.Structure):   # include/trex_batch.h; the defaults are TREX
 if hasattr(lib, "trex_batch_inverse_kinematics"):
     lib.trex_batch_inverse_kinematics.argtypes = [_vp, C.c_int, C.POINTER(C.c_int32), C.c_int, _vp, _vp, C.c_uint32,
                                                   C.POINTER(TrexIkParams), _vp, _vp, _vp]
+
+
+class TrexObsChannel(C.Structure):   # include/trex_batch.h
+    _fields_ = [("kind", C.c_int32), ("link", C.c_int32), ("local_xyz", C.c_float * 3), ("scale", C.c_float)]
+
+
+if hasattr(lib, "trex_batch_compose_rows"):
+    lib.trex_batch_set_observation.argtypes = [_vp, C.POINTER(TrexObsChannel), C.c_int, C.POINTER(C.c_int)]
+    lib.trex_batch_observation_dim.argtypes = [_vp]
+    lib.trex_batch_compose_rows.argtypes = [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp]
 
 
 lib.trex_policy_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]
@@ -677,6 +688,40 @@ class Batch:
         n = self.num_envs
         check(lib.trex_batch_termination_info(self.h, self._p(reason, "int32", n, "reason"), self._p(values, "float32", 3 * n, "values"),
                                               self._p(terminal_obs, "float32", n * 3 * self.J, "terminal_obs"), self._stream(stream)))
+
+    def set_observation(self, channels=()):
+        """The batch's observation channels (trex_batch_set_observation): a sequence of (kind, link, local_xyz[3], scale) - kind a
+        TREX_OBS_* value, link a URDF link index (EXTERNAL: its column count). Host values, shared by all envs; an empty sequence
+        clears. -> E, the columns the channels add to a composed row."""
+        arr = (TrexObsChannel * max(len(channels), 1))()
+        for o, (kind, link, xyz, scale) in zip(arr, channels):
+            o.kind, o.link, o.scale = int(kind), int(link), float(scale)
+            o.local_xyz[:] = [float(x) for x in xyz]
+        extra = C.c_int()
+        check(lib.trex_batch_set_observation(self.h, arr, len(channels), C.byref(extra)))
+        self.obs_extra = extra.value
+        return extra.value
+
+    obs_extra = 0
+
+    def observation_dim(self):
+        """3J + E (trex_batch_observation_dim)"""
+        return check(lib.trex_batch_observation_dim(self.h))
+
+    def compose_rows(self, rows, out, actions=None, extern=None, stream=None):
+        """The extended rows obs | channels | tail (trex_batch_compose_rows) into out [n, >= 3J + E + tail] from rows [n, >= 3J +
+        tail] - what step_rows / reset_rows wrote -, actions [n, A] or None (PREV_ACTION reads zeros) and extern [n, X] or None:
+        the columns the EXTERNAL channels copy. One launch, stream-ordered; the state is only read."""
+        n, J = self.num_envs, self.J
+        tail = 5 if self.pen_in_rows else 2
+        for t, what in ((rows, "rows"), (out, "out"), (extern, "extern")):
+            if t is not None and (not hasattr(t, "dim") or t.dim() != 2 or t.shape[0] != n):
+                raise TrexError(E_INVALID, "%s: expected a tensor of shape [%d, columns]" % (what, n))
+        check(lib.trex_batch_compose_rows(self.h, self._p(rows, "float32", (n - 1) * rows.shape[1] + 3 * J + tail, "rows"), int(rows.shape[1]),
+                                          self._p(actions, "float32", n * self.A, "actions"),
+                                          self._p(extern, "float32", None, "extern"), 0 if extern is None else int(extern.shape[1]),
+                                          self._p(out, "float32", (n - 1) * out.shape[1] + 3 * J + self.obs_extra + tail, "out"),
+                                          int(out.shape[1]), self._stream(stream)))
 
     def centroidal(self, out=None, stream=None):
         """[n, 16]: COM position, COM velocity, linear momentum, angular momentum about the COM, kinetic energy, potential

@@ -25,6 +25,9 @@ from torch import nn
 
 from . import _capi
 
+POLICY_MAX_OBS_DIM = 126     # trex_policy_create (include/trex_policy.h)
+LEARNER_MAX_OBS_DIM = 96     # trex_policy_minibatch_step: the observation columns it stages per sample
+
 
 class MlpPolicy(nn.Module):
     """baselines MlpPolicy: pi and vf are separate 2 x 64 tanh MLPs, diagonal Gaussian with a free log-std. The
@@ -145,6 +148,13 @@ class PPO:
         self.clip_obs, self.clip_rew = clip_obs, clip_rew
         torch.manual_seed(seed)
         n, od, ad = env.num_envs, env.observation_space.shape[0], env.action_space.shape[0]
+        # (an env with observation channels is wider than the reference's 3J = 75: the kernels' limits are met here, by name, not
+        # as a refused launch inside the first update)
+        if od > POLICY_MAX_OBS_DIM:
+            raise ValueError("the observation is %d columns wide; the policy kernel takes at most %d" % (od, POLICY_MAX_OBS_DIM))
+        if native_learner and od > LEARNER_MAX_OBS_DIM:
+            raise ValueError("the observation is %d columns wide; the native learner stages at most %d per sample "
+                             "(native_learner=False trains up to %d)" % (od, LEARNER_MAX_OBS_DIM, POLICY_MAX_OBS_DIM))
         self.kern = _capi.Policy(n, od, ad, 64, self.dev.index)       # VecNormalize state + the kernels
         self.policy = MlpPolicy(self.kern.layout, self.kern.param_count, self.dev)
         self.adam_m = torch.zeros_like(self.policy.theta)

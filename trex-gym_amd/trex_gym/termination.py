@@ -56,6 +56,23 @@ def foot_bodies(env):
     return sorted(feet)
 
 
+def foot_links(env):
+    """One URDF link index per foot, in body order: of every limb of foot_bodies(), the first link of its first support body (the
+    T-rex: the end of the middle toe of either leg, which carries the standing robot). A foot has several bodies on the floor;
+    this names one of them - a point to follow and a body whose contact force tells a stance from a swing."""
+    parent = env.model.array("parent").astype(int)
+    nb = len(parent)
+    kids = [[k for k in range(nb) if parent[k] == b] for b in range(nb)]
+    link_body = env.model.array("link_body").astype(int)
+    first = {}                                    # top body of the limb -> its first support body
+    for b in support_bodies(env):
+        top = b
+        while parent[top] > 0 and len(kids[top]) < 2:
+            top = parent[top]
+        first.setdefault(top, b)
+    return [int(np.flatnonzero(link_body == first[top])[0]) for top in sorted(first)]
+
+
 def fall_bodies(env):
     """The bodies with collision geometry that are no part of a foot, as URDF link indices (one per body):
     keep_clear=fall_bodies(env) ends an episode when anything but a foot touches the floor."""

@@ -24,7 +24,7 @@ _URDF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ass
 
 def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0, push_force=0.0, push_interval=100,
                       push_duration=5, push_probability=1.0, seed=0, control_mode=None, variable_stiffness=False,
-                      gain_scale=0.0, terminate=None):   # (weights of trex_train.py:66)
+                      gain_scale=0.0, terminate=None, observations=None):   # (weights of trex_train.py:66)
     # control_mode: what the joints' actions mean (position / velocity / torque: J-wide, through the trainer unchanged). The
     # 2J-wide stiffness action space is wider than the policy kernel's act_dim <= 32: refused here, not deep in a launch
     check_action_space(control_mode, variable_stiffness)
@@ -32,6 +32,16 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
     params = {"warmstart": float(warmstart)} if warmstart else None
     # push_force > 0: random horizontal pushes of the base, up to push_force N, every push_interval env-steps for
     # push_duration env-steps (trex_gym.perturb.RandomPushes); 0 = none
+    # observations: a preset's name ("locomotion") or a specification of trex_gym.observations (a checkpoint's): extra
+    # observation columns composed on the device; None = the reference's 3J columns
+    if isinstance(observations, str):
+        from . import _capi, observations as O
+        if observations not in O.PRESETS:
+            raise ValueError("--observations: expected one of %s, got %r" % (", ".join(sorted(O.PRESETS)), observations))
+        observations = O.PRESETS[observations](_capi.Model(_URDF_PATH), device)
+    elif observations is not None:
+        from . import observations as O
+        observations = O.from_tuples(observations)
     pushes = None
     if push_force > 0:
         dev = torch.device(device)
@@ -40,7 +50,7 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
                               duration=push_duration, generator=gen, device=dev)
     env = TrexVecEnv(num_envs, urdf_path=_URDF_PATH, device=device, distance_weight=2e2, energy_weight=1e-6,
                      drift_weight=1.0, max_episode_steps=max_episode_steps, params=params, pushes=pushes, control_mode=control_mode,
-                     terminate=terminate)   # terminate: TrexVecEnv.set_termination's arguments - a fall ends the episode, on the device
+                     terminate=terminate, observations=observations)   # terminate: TrexVecEnv.set_termination's arguments - a fall ends the episode, on the device
     if gain_scale > 0:   # every episode with motor gains and strength scaled by 1 +- gain_scale per env (RandomGains)
         dev = torch.device(device)
         r = (1.0 - gain_scale, 1.0 + gain_scale)
@@ -85,7 +95,8 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
         st = agent.kern.get_stats()     # VecNormalize's running statistics travel with the weights (trex_train.py:93-99 restores both)
         torch.save({"theta": agent.policy.theta.detach().clone(), "obs_mean": torch.tensor(st["obs_mean"]),
                     "obs_var": torch.tensor(st["obs_var"]), "obs_count": torch.tensor(float(st["obs_count"])),
-                    "ret_var": torch.tensor(float(st["ret_var"]))}, save_path)
+                    "ret_var": torch.tensor(float(st["ret_var"])),
+                    "observations": getattr(env, "observations", None)}, save_path)   # (the channels: --play rebuilds the same row)
     return agent, hist
 
 
@@ -145,7 +156,7 @@ def load_agent(load_path, num_envs=1, device="cuda:0", max_episode_steps=1000):
     """trex_train.py:75-110 (replay): rebuild the policy from a file written by train(save_path=...) - the flat
     parameter vector and VecNormalize's statistics."""
     ck = torch.load(load_path, map_location=device, weights_only=True)
-    env = build_environment(num_envs, device=device, max_episode_steps=max_episode_steps)
+    env = build_environment(num_envs, device=device, max_episode_steps=max_episode_steps, observations=ck.get("observations"))
     agent = PPO(env, nsteps=1, nminibatches=1, noptepochs=1)
     with torch.no_grad():
         agent.policy.theta.copy_(ck["theta"])
@@ -188,6 +199,9 @@ def parse_args(argv=None):
     ap.add_argument("--terminate_tilt", type=float, default=None, help="end an episode when the base is tipped more than this from its start orientation (rad)")
     ap.add_argument("--terminate_contact", type=str, default=None, metavar="LINK[,LINK...]",
                     help="end an episode when one of these links touches the floor; 'auto': every body but the feet of the start pose")
+    ap.add_argument("--observations", choices=["locomotion"], default=None,
+                    help="extra observation columns composed on the device; locomotion: base tilt, velocity, height, the feet's contact "
+                         "force and position (18 columns; default: the reference's 75 alone)")
     ap.add_argument("--fall_penalty", type=float, default=0.0, help="taken from the reward of the step in which an episode ends by a fall")
     args = ap.parse_args(argv)
     if args.variable_stiffness:
@@ -219,7 +233,7 @@ def environment_from_args(args):
     env = build_environment(args.num_envs, max_episode_steps=args.max_episode_steps, warmstart=args.warmstart,
                             push_force=args.push_force, push_interval=args.push_interval, push_duration=args.push_duration,
                             seed=args.random_seed, control_mode=None if args.control_mode == "position" else args.control_mode,
-                            gain_scale=args.gain_scale)
+                            gain_scale=args.gain_scale, observations=args.observations)
     if terminate is not None:   # (set on the built env: 'auto' needs its model - every body that does not stand on the floor at the start)
         if terminate["keep_clear"] == ["auto"]:
             from .termination import fall_bodies

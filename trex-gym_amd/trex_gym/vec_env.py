@@ -11,7 +11,8 @@ inside the step launch itself (trex_batch_set_episode_limit).
 
 Outputs live in ONE row block `rows` [n, 3J+2] f32 = obs | reward | done (written by the kernel in that layout:
 trex_batch_step_rows; with penalties_in_rows [n, 3J+5]: the three penalties behind done); `obs`, `rew`, `done_f` are views
-into it; `done` holds the flags as bool, `penalties` [n, 3] the three reward terms.
+into it; `done` holds the flags as bool, `penalties` [n, 3] the three reward terms. With `observations=` (trex_gym.observations)
+the block is [n, 3J + E + 2]: E more observation columns, composed on the device by one more launch per step and reset.
 
 Multi-GPU: one process per GPU, env ids sharded by contiguous range (trex_gym.sharding); the only
 exchange is the all-gather of that row block (all_gather_rows / all_gather_rows_pipelined).
@@ -72,7 +73,7 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
                  max_episode_steps=None, starting_configuration=None, params=None,
                  rank=0, world_size=1, process_group=None, collision="hulls", primitive_max_radius=0.2, row_buffers=1,
                  penalties_in_rows=False, pushes=None, control_mode=None, variable_stiffness=False,
-                 kp_max=actuators.DEFAULT_KP_MAX, terminate=None):
+                 kp_max=actuators.DEFAULT_KP_MAX, terminate=None, observations=None, external=None):
         """num_envs is the GLOBAL env count; this process owns sharding.shard_range(num_envs, rank, world_size).
         row_buffers=2: successive steps write two row blocks in turn (`rows`, `obs`, `rew`, `done_f` always name the
         block of the LAST step), which lets the pipelined all-gather read a block in place.
@@ -82,7 +83,13 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         action means (include/trex_batch.h; pybullet's setJointMotorControlArray modes). variable_stiffness: actions are [2J],
         J commands then J stiffnesses kp in [0, kp_max] (the reference's intended action space, trex_env.py:30).
         terminate: dict(head_height=, max_tilt=, keep_clear=, penalty=) - the arguments of set_termination(): episodes end
-        when the robot falls, decided inside the step calls."""
+        when the robot falls, decided inside the step calls.
+        observations: a list of trex_gym.observations channels (e.g. observations.locomotion(model)): E extra observation columns
+        behind the 3J, computed on the device from the state of the row's own instant by one more launch per step and reset
+        (trex_batch_compose_rows). `rows` is then [n, 3J + E + 2 (or 5)] = obs | reward | done, `obs` its first D' = 3J + E
+        columns, and observation_space is D' wide. None (default): nothing changes - not a launch, not a byte.
+        external: with observations.external(k) channels, their columns: a tensor [n, X] read at every compose, or a callable
+        env -> such a tensor, called after every step and reset."""
         self.global_num_envs = int(num_envs)
         self.rank, self.world_size, self.process_group = int(rank), int(world_size), process_group
         self.env_lo, self.env_hi = sharding.shard_range(self.global_num_envs, self.rank, self.world_size)
@@ -131,6 +138,13 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         self.batch.set_penalties_in_rows(self._pen_in_rows)      # (explicit: a wide row stride alone writes nothing beyond column 3J + 1)
         self._row_blocks = [torch.zeros(n, 3 * J + (5 if self._pen_in_rows else 2), device=self.device) for _ in range(int(row_buffers))]
         self._penalties = None if self._pen_in_rows else torch.zeros(n, 3, device=self.device)
+        # observation channels: the step keeps writing a [n, 3J + tail] block of its own (_step_rows); the composed rows are the
+        # env's row blocks, so that everything that reads `rows` - the trainer in place, the gathers - reads the extended row
+        self.observations, self.obs_dim, self._step_rows, self._external, self._link_table = None, 3 * J, None, external, None
+        if observations is not None and len(observations):
+            self._set_observations(observations)
+        elif external is not None:
+            raise ValueError("external: there is no observations.external(k) channel to take it")
         self._row_k = 0
         self._point_at(0)
         self.done = torch.zeros(n, dtype=torch.bool, device=self.device)   # the same flags as bytes (written by the kernel too)
@@ -158,11 +172,46 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         if terminate:
             self.set_termination(**terminate)
 
+    # ---- observation channels (trex_batch_set_observation / trex_batch_compose_rows; trex_gym.observations builds specifications)
+    def _set_observations(self, spec):
+        from . import observations as O
+        from .perturb import LinkTable
+        if self._link_table is None:
+            self._link_table = LinkTable.from_model(self.model)
+        J, n = self.J, self.num_envs
+        chans, extra, contact, ext_cols = O.resolve(spec, self._link_table.index, self.A)
+        if len(chans) > O.MAX_CHANNELS or 3 * J + extra > O.MAX_DIM:
+            raise ValueError("observations: %d channels and %d columns; at most %d channels and %d columns"
+                             % (len(chans), 3 * J + extra, O.MAX_CHANNELS, O.MAX_DIM))
+        if (ext_cols > 0) != (self._external is not None):
+            raise ValueError("observations: external(k) channels and the external= argument go together")
+        if contact:
+            self.batch.set_contact_sensor(True)
+        added = self.batch.set_observation(chans)
+        assert added == extra, (added, extra)
+        self.observations = O.as_tuples(spec)
+        self.obs_dim = self.batch.observation_dim()
+        tail = 5 if self._pen_in_rows else 2
+        self._step_rows = self._row_blocks[0]
+        self._row_blocks = [torch.zeros(n, self.obs_dim + tail, device=self.device) for _ in self._row_blocks]
+        big = np.full(extra, 1.0e12, np.float32)      # the bounds of the velocity columns
+        sp = self.observation_space
+        self.observation_space = spaces.Box(low=np.concatenate([sp.low, -big]), high=np.concatenate([sp.high, big]), dtype=np.float32)
+
+    def _compose(self, actions):
+        ext = self._external(self) if callable(self._external) else self._external
+        if ext is not None and (ext.dtype != torch.float32 or not ext.is_contiguous() or ext.device != self.device):
+            ext = ext.to(device=self.device, dtype=torch.float32).contiguous()
+        self.batch.compose_rows(self._step_rows, self.rows, actions, ext)
+
     # ---- tensor-native API (stays on device, stream-ordered, no host sync)
     def reset_tensor(self, mask=None):
         """Reset all envs (mask=None) or those with mask != 0 (uint8 or bool [n], e.g. the `done` of the last step).
-        Returns obs [n, 3J]; the reward / done columns and `done` of the envs that were reset read 0 afterwards."""
-        self.batch.reset_rows(self.rows, mask)
+        Returns obs [n, 3J]; the reward / done columns and `done` of the envs that were reset read 0 afterwards.
+        With observations: obs [n, 3J + E], every env's channels recomposed at the current state, prev_action() columns zero."""
+        self.batch.reset_rows(self.rows if self._step_rows is None else self._step_rows, mask)
+        if self._step_rows is not None:
+            self._compose(None)
         if self.gains is not None:              # the envs that were reset draw new motor gains
             self.set_motor_gains(**self.gains.draw(mask))
         if mask is None:
@@ -198,7 +247,11 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
             self._point_at(1 - self._row_k)
         # (with set_termination the call is three launches: step, fall predicate, reset of the fallen - done = 1, the reward of
         # the finished step less the penalty, observation of the new episode)
-        self.batch.step_rows(actions, self.rows, self._penalties, done=self.done)   # (None: the penalties ride in the row block)
+        if self._step_rows is None:
+            self.batch.step_rows(actions, self.rows, self._penalties, done=self.done)   # (None: the penalties ride in the row block)
+        else:   # (observation channels: one more launch, after the resets of the step call - the row of the new episode's state)
+            self.batch.step_rows(actions, self._step_rows, self._penalties, done=self.done)
+            self._compose(actions)
         if self._term_on and self.gains is not None:   # the envs that fell start their episode with new motor gains
             self.set_motor_gains(**self.gains.draw(self.termination_reason != 0))
         return self.obs, self.rew, self.done
@@ -206,7 +259,10 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
     def step_many_tensor(self, actions, rows=None):
         """Open-loop rollout: actions [S, n, J] f32 on device -> rows [S, n, 3J+2] (obs | reward | done of every step), S
         env-steps in ONE launch (trex_batch_step_many; bitwise S calls of step_tensor). `rows`, `obs`, `rew`, `done_f`
-        and `done` then hold the last step. sharding.split_rows(rows[s]) cuts a step's block into the three."""
+        and `done` then hold the last step. sharding.split_rows(rows[s]) cuts a step's block into the three.
+        ValueError with observations: an open-loop launch has no compose between its steps."""
+        if self._step_rows is not None:
+            raise ValueError("step_many_tensor: not with observations - the open-loop launch has no per-step compose of the channels")
         if actions.dtype != torch.float32 or not actions.is_contiguous() or actions.device != self.device:
             actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
         if actions.dim() != 3 or tuple(actions.shape[1:]) != (self.num_envs, self.A):
@@ -230,12 +286,12 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         return self.batch.A
 
     def _point_at(self, k):
-        J = self.J
+        D = self.obs_dim        # 3J, or 3J + E with observation channels
         self._row_k = k
         self.rows = self._row_blocks[k]
-        self.obs, self.rew, self.done_f = self.rows[:, :3 * J], self.rows[:, 3 * J], self.rows[:, 3 * J + 1]
+        self.obs, self.rew, self.done_f = self.rows[:, :D], self.rows[:, D], self.rows[:, D + 1]
         # lifting_com, station_keeping, energy (trex_env.py:193-195)
-        self.penalties = self.rows[:, 3 * J + 2:3 * J + 5] if self._pen_in_rows else self._penalties
+        self.penalties = self.rows[:, D + 2:D + 5] if self._pen_in_rows else self._penalties
 
     def all_gather_rows(self, rows=None):
         """[global N, 3J+2] = obs | reward | done of EVERY env, on every rank: the one collective of the path
@@ -273,8 +329,8 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
         return self._copy_pipe.push(self.rows)
 
     def all_gather_obs(self):
-        """[global N, 3J]: the observation columns of all_gather_rows()."""
-        return self.all_gather_rows()[:, :3 * self.J]
+        """[global N, 3J] (with observations: 3J + E): the observation columns of all_gather_rows()."""
+        return self.all_gather_rows()[:, :self.obs_dim]
 
     # ---- baselines VecEnv API (host numpy in/out)
     def reset(self):
@@ -828,7 +884,8 @@ class TrexVecEnv(spaces.Env):       # gym.Env where gym is importable; the surfa
     @property
     def terminal_obs(self):
         """[n, 3J] on the device: for an env that fell, the last observation of that episode (the row of an env that did not
-        fall in the last step holds the one of its most recent fall, zeros before the first)."""
+        fall in the last step holds the one of its most recent fall, zeros before the first). With observations it stays the 3J
+        base columns: the channels of the state that fell are not kept."""
         return self._term_info(2)
 
     # ---- ray casts (trex_batch_ray_test: pybullet's rayTestBatch; no host sync; trex_gym.sensors builds patterns)

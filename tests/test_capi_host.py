@@ -25,6 +25,61 @@ def test_header_symbols_exported(capi):
         assert hasattr(capi.lib, name), name
 
 
+def _declarations(header):
+    """[(name, return type, [parameter, ...])] of every trex_* function a header declares, as normalised C text"""
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", " ", text, flags=re.M)       # preprocessor lines, continued ones too
+    out = []
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(trex_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", text):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out.append((name, " ".join(ret.split()), [] if params == ["void"] else params))
+    return out
+
+
+def _kind(c_text, is_return=False):
+    """the ctypes classes that may stand for a C parameter (or return type) - or "pointer" for any pointer or array"""
+    C_SCALARS = {"int": (C.c_int, C.c_int32), "int32_t": (C.c_int, C.c_int32), "uint32_t": (C.c_uint32,), "int64_t": (C.c_int64,),
+                 "float": (C.c_float,), "double": (C.c_double,)}
+    if "*" in c_text or "[" in c_text:
+        return "pointer"
+    words = [w for w in c_text.split() if w != "const"]
+    if not is_return:
+        assert len(words) == 2, "parameter %r: expected a type and a name" % c_text
+        words = words[:1]
+    assert len(words) == 1, c_text
+    return (None,) if words[0] == "void" else C_SCALARS[words[0]]
+
+
+def _matches(ctype, kind):
+    if kind == "pointer":
+        return ctype in (C.c_void_p, C.c_char_p) or (isinstance(ctype, type) and issubclass(ctype, C._Pointer))
+    return ctype in kind
+
+
+def test_signatures_match_the_headers(capi):
+    """Every function of both headers against the binding's restype / argtypes: the number of parameters, and per parameter
+    and for the return value the kind - a pointer for a pointer or an array, the ctypes scalar of the same width and type for
+    a scalar. An int where the library reads a device pointer would otherwise first show as a fault on the GPU."""
+    decls = _declarations("trex_batch.h") + _declarations("trex_policy.h")
+    assert len(decls) == 86 and len({d[0] for d in decls}) == 86
+    assert [d[0] for d in decls if d[0] not in capi.SYMBOLS + capi.POLICY_SYMBOLS] == []
+    wrong = []
+    for name, ret, params in decls:
+        fn = getattr(capi.lib, name)
+        argtypes = list(fn.argtypes or [])
+        if len(argtypes) != len(params):
+            wrong.append("%s: %d parameters declared, %d argtypes" % (name, len(params), len(argtypes)))
+            continue
+        for k, (p, a) in enumerate(zip(params, argtypes)):
+            if not _matches(a, _kind(p)):
+                wrong.append("%s: parameter %d `%s` is bound as %s" % (name, k, p, a))
+        if not _matches(fn.restype, _kind(ret, is_return=True)):
+            wrong.append("%s: returns `%s`, restype is %s" % (name, ret, fn.restype))
+    assert not wrong, "\n".join(wrong)
+
+
 def test_model_matches_oracle_model(capi, model):
     m = capi.Model(ASSET_URDF)
     assert m.num_bodies == 26 and m.num_joints == 25 and m.num_urdf_joints == 132

@@ -2,13 +2,18 @@
 
 There is NO CPU fallback: if the HIP library is missing, importing this module raises; if no GPU
 is present, creating a batch raises TrexError (model loading is host-only and still works).
+
+Every function's signature stands once, in the tables _BATCH_API / _POLICY_API below. A function the loaded library does
+not export is left out when they are applied: a TREX_LIB built from an older tree (scripts/actuator_bench.py's A/B run)
+still imports, and USING a function it lacks raises AttributeError - for every function now, where the ones older than the
+actuator model used to fail the import. That the product library exports them all is tests/test_capi_host.py's check.
 """
 import ctypes as C
 import os
 
 import numpy as np
-import torch  # noqa: F401  - FIRST: torch brings its own HIP runtime; loading libtrex_hip.so before it
-#                             would bind the system runtime and leave the process with two of them
+import torch  # FIRST: torch brings its own HIP runtime; loading libtrex_hip.so before it would bind the system
+#               runtime and leave the process with two of them
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TREX_LIB") or os.path.join(_HERE, "libtrex_hip.so")  # TREX_LIB: diagnostic builds
@@ -24,118 +29,6 @@ lib = C.CDLL(LIB_PATH)
 PARAM_NAMES = ["dt", "substeps", "iterations", "gravity", "motor_kp", "motor_kd", "motor_max_force",
                "floor_z", "friction", "erp", "contact_erp", "contact_margin", "link_damping",
                "max_coordinate_velocity", "max_contacts"]
-# every symbol include/trex_batch.h declares (tests/test_capi_symbols.py parses the header too)
-SYMBOLS = [
-    "trex_last_error", "trex_model_load", "trex_model_destroy", "trex_model_num_bodies",
-    "trex_model_num_joints", "trex_model_num_urdf_joints", "trex_model_num_hull_vertices",
-    "trex_model_total_mass", "trex_model_joint_info", "trex_model_set_start_angle",
-    "trex_model_set_start_pose", "trex_model_set_param", "trex_model_get_param", "trex_model_get_array",
-    "trex_batch_create", "trex_batch_destroy", "trex_batch_num_envs", "trex_batch_set_reward_weights",
-    "trex_batch_reset", "trex_batch_step", "trex_batch_get_state", "trex_batch_set_state",
-    "trex_batch_set_motors_enabled", "trex_batch_head_position", "trex_batch_set_domain",
-    "trex_batch_contact_stats", "trex_batch_debug_step", "trex_batch_launch_info", "trex_batch_time_steps",
-    "trex_model_num_links", "trex_model_link_info", "trex_batch_link_transforms",
-    "trex_model_use_primitive_collision", "trex_model_fit_hull_primitives",
-    "trex_build_id", "trex_batch_step_rows", "trex_batch_reset_rows",
-    "trex_batch_set_episode_limit", "trex_batch_get_episode_steps",
-    "trex_batch_set_wave_balance", "trex_batch_forget_buffers", "trex_batch_set_penalties_in_rows",
-    "trex_model_num_visuals", "trex_model_visual_info", "trex_batch_visual_transforms", "trex_batch_step_many",
-    "trex_batch_render", "trex_batch_set_external_wrench", "trex_batch_set_contact_sensor", "trex_batch_contact_wrench",
-    "trex_batch_set_control_mode", "trex_batch_set_motor_gains", "trex_batch_set_stiffness_actions",
-    "trex_batch_inverse_dynamics", "trex_batch_mass_matrix", "trex_batch_jacobian", "trex_batch_centroidal",
-    "trex_batch_forward_dynamics", "trex_batch_solve_mass", "trex_batch_ray_test",
-    "trex_batch_set_link_probes", "trex_batch_link_state",
-    "trex_batch_set_proximity_shapes", "trex_batch_proximity",
-    "trex_batch_body_clearance", "trex_batch_set_termination", "trex_batch_termination_info",
-    "trex_batch_inverse_kinematics",
-    "trex_batch_set_observation", "trex_batch_observation_dim", "trex_batch_compose_rows",
-]
-
-# every symbol include/trex_policy.h declares (the trainer-side kernels)
-POLICY_SYMBOLS = [
-    "trex_policy_create", "trex_policy_destroy", "trex_policy_param_count", "trex_policy_param_offsets",
-    "trex_policy_get_stats", "trex_policy_set_stats", "trex_policy_get_returns", "trex_policy_observe",
-    "trex_policy_act", "trex_policy_gae", "trex_policy_adam", "trex_policy_adam_reset",
-    "trex_policy_minibatch_stats", "trex_policy_minibatch_step", "trex_policy_minibatch_grad",
-]
-
-_vp = C.c_void_p
-lib.trex_last_error.restype = C.c_char_p
-lib.trex_build_id.restype = C.c_char_p
-lib.trex_model_load.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(_vp)]
-lib.trex_model_destroy.argtypes = [_vp]
-lib.trex_model_destroy.restype = None
-for _n in ("trex_model_num_bodies", "trex_model_num_joints", "trex_model_num_urdf_joints",
-           "trex_model_num_hull_vertices"):
-    getattr(lib, _n).argtypes = [_vp]
-lib.trex_model_total_mass.argtypes = [_vp, C.c_int]
-lib.trex_model_total_mass.restype = C.c_double
-lib.trex_model_joint_info.argtypes = [_vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int),
-                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]
-lib.trex_model_set_start_angle.argtypes = [_vp, C.c_char_p, C.c_double]
-lib.trex_model_set_start_pose.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-lib.trex_model_set_param.argtypes = [_vp, C.c_char_p, C.c_double]
-lib.trex_model_get_param.argtypes = [_vp, C.c_char_p, C.POINTER(C.c_double)]
-lib.trex_model_get_array.argtypes = [_vp, C.c_char_p, C.POINTER(C.c_double), C.c_int]
-lib.trex_batch_create.argtypes = [_vp, C.c_int, C.c_int, C.POINTER(_vp)]
-lib.trex_batch_destroy.argtypes = [_vp]
-lib.trex_batch_destroy.restype = None
-lib.trex_batch_num_envs.argtypes = [_vp]
-lib.trex_batch_set_reward_weights.argtypes = [_vp, C.c_float, C.c_float, C.c_float]
-lib.trex_batch_reset.argtypes = [_vp, _vp, _vp, _vp]
-lib.trex_batch_step.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
-lib.trex_batch_step_rows.argtypes = [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp]
-lib.trex_batch_step_many.argtypes = [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]
-lib.trex_batch_reset_rows.argtypes = [_vp, _vp, _vp, C.c_int, _vp]
-lib.trex_batch_set_episode_limit.argtypes = [_vp, C.c_int, _vp, _vp]
-lib.trex_batch_get_episode_steps.argtypes = [_vp, _vp, _vp]
-lib.trex_batch_set_wave_balance.argtypes = [_vp, C.c_int]
-lib.trex_batch_forget_buffers.argtypes = [_vp]
-lib.trex_batch_set_penalties_in_rows.argtypes = [_vp, C.c_int]
-lib.trex_batch_debug_step.argtypes = [_vp, _vp, _vp, _vp, _vp]
-lib.trex_batch_get_state.argtypes = [_vp, _vp, _vp]
-lib.trex_batch_set_state.argtypes = [_vp, _vp, _vp]
-lib.trex_batch_set_motors_enabled.argtypes = [_vp, C.c_int, _vp]
-lib.trex_batch_head_position.argtypes = [_vp, _vp, _vp]
-lib.trex_batch_set_domain.argtypes = [_vp, _vp, _vp, _vp]
-lib.trex_batch_set_external_wrench.argtypes = [_vp, _vp, _vp]
-lib.trex_batch_set_contact_sensor.argtypes = [_vp, C.c_int]
-if hasattr(lib, "trex_batch_set_control_mode"):   # (a TREX_LIB built from an older tree - scripts/actuator_bench.py's A/B - has no
-    lib.trex_batch_set_control_mode.argtypes = [_vp, C.POINTER(C.c_int32)]           # actuator model: using it there raises)
-    lib.trex_batch_set_motor_gains.argtypes = [_vp, _vp, _vp, _vp, _vp]
-    lib.trex_batch_set_stiffness_actions.argtypes = [_vp, C.c_int, C.c_float]
-lib.trex_batch_contact_wrench.argtypes = [_vp, _vp, _vp]
-if hasattr(lib, "trex_batch_inverse_dynamics"):   # (as above: an older TREX_LIB has no dynamics queries)
-    lib.trex_batch_inverse_dynamics.argtypes = [_vp, _vp, _vp, _vp]
-    lib.trex_batch_mass_matrix.argtypes = [_vp, _vp, _vp]
-    lib.trex_batch_jacobian.argtypes = [_vp, C.c_int, C.POINTER(C.c_double), _vp, _vp]
-    lib.trex_batch_centroidal.argtypes = [_vp, _vp, _vp]
-if hasattr(lib, "trex_batch_forward_dynamics"):
-    lib.trex_batch_forward_dynamics.argtypes = [_vp, _vp, _vp, _vp]
-    lib.trex_batch_solve_mass.argtypes = [_vp, _vp, C.c_int, _vp, _vp]
-if hasattr(lib, "trex_batch_ray_test"):
-    lib.trex_batch_ray_test.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, _vp]
-if hasattr(lib, "trex_batch_link_state"):
-    lib.trex_batch_set_link_probes.argtypes = [_vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int]
-    lib.trex_batch_link_state.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]
-if hasattr(lib, "trex_batch_proximity"):
-    lib.trex_batch_set_proximity_shapes.argtypes = [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int32), C.c_int]
-    lib.trex_batch_proximity.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
-if hasattr(lib, "trex_batch_body_clearance"):
-    lib.trex_batch_body_clearance.argtypes = [_vp, _vp, _vp, _vp]
-    lib.trex_batch_set_termination.argtypes = [_vp, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_float]
-    lib.trex_batch_termination_info.argtypes = [_vp, _vp, _vp, _vp, _vp]
-lib.trex_model_use_primitive_collision.argtypes = [_vp, C.c_double, C.c_int, C.c_int]
-lib.trex_model_fit_hull_primitives.argtypes = [_vp, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int]
-lib.trex_model_num_links.argtypes = [_vp]
-lib.trex_model_link_info.argtypes = [_vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int)]
-lib.trex_batch_link_transforms.argtypes = [_vp, _vp, _vp]
-lib.trex_model_num_visuals.argtypes = [_vp]
-lib.trex_model_visual_info.argtypes = [_vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-lib.trex_batch_visual_transforms.argtypes = [_vp, _vp, _vp]
-lib.trex_batch_contact_stats.argtypes = [_vp, _vp, _vp, _vp]
-lib.trex_batch_launch_info.argtypes = [_vp] + [C.POINTER(C.c_int)] * 4
-lib.trex_batch_time_steps.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.POINTER(C.c_float)]
 
 
 class TrexCamera(C.Structure):     # include/trex_batch.h
@@ -143,45 +36,125 @@ class TrexCamera(C.Structure):     # include/trex_batch.h
                 ("near_z", C.c_float), ("far_z", C.c_float), ("follow_base", C.c_int), ("target", C.c_float * 3)]
 
 
-lib.trex_batch_render.argtypes = [_vp, C.POINTER(TrexCamera), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _vp, _vp, _vp, _vp]
-
-
 class TrexIkParams(C.Structure):   # include/trex_batch.h; the defaults are TREX_IK_DEFAULTS
     _fields_ = [("iterations", C.c_int32), ("damping", C.c_float), ("gain", C.c_float), ("max_step", C.c_float),
                 ("tol_pos", C.c_float), ("tol_ori", C.c_float)]
-
-
-if hasattr(lib, "trex_batch_inverse_kinematics"):
-    lib.trex_batch_inverse_kinematics.argtypes = [_vp, C.c_int, C.POINTER(C.c_int32), C.c_int, _vp, _vp, C.c_uint32,
-                                                  C.POINTER(TrexIkParams), _vp, _vp, _vp]
 
 
 class TrexObsChannel(C.Structure):   # include/trex_batch.h
     _fields_ = [("kind", C.c_int32), ("link", C.c_int32), ("local_xyz", C.c_float * 3), ("scale", C.c_float)]
 
 
-if hasattr(lib, "trex_batch_compose_rows"):
-    lib.trex_batch_set_observation.argtypes = [_vp, C.POINTER(TrexObsChannel), C.c_int, C.POINTER(C.c_int)]
-    lib.trex_batch_observation_dim.argtypes = [_vp]
-    lib.trex_batch_compose_rows.argtypes = [_vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp]
+# The signature tables: name -> (restype, argtypes), one per header, in the order SYMBOLS / POLICY_SYMBOLS list the names.
+# tests/test_capi_host.py parses the headers and compares every entry - count, kind of each parameter, return kind.
+# _vp: a handle, a device pointer or a stream; host arrays and out-parameters are typed pointers.
+_vp, _int, _f, _d, _str = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_char_p
+_pint, _pi32, _pf, _pd, _pstr = C.POINTER(C.c_int), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_char_p)
+
+_BATCH_API = {
+    "trex_last_error": (_str, []),
+    "trex_model_load": (_int, [_str, _str, C.POINTER(_vp)]),
+    "trex_model_destroy": (None, [_vp]),
+    "trex_model_num_bodies": (_int, [_vp]),
+    "trex_model_num_joints": (_int, [_vp]),
+    "trex_model_num_urdf_joints": (_int, [_vp]),
+    "trex_model_num_hull_vertices": (_int, [_vp]),
+    "trex_model_total_mass": (_d, [_vp, _int]),
+    "trex_model_joint_info": (_int, [_vp, _int, _pstr, _pint, _pd, _pd]),
+    "trex_model_set_start_angle": (_int, [_vp, _str, _d]),
+    "trex_model_set_start_pose": (_int, [_vp, _pd, _pd]),
+    "trex_model_set_param": (_int, [_vp, _str, _d]),
+    "trex_model_get_param": (_int, [_vp, _str, _pd]),
+    "trex_model_get_array": (_int, [_vp, _str, _pd, _int]),
+    "trex_batch_create": (_int, [_vp, _int, _int, C.POINTER(_vp)]),
+    "trex_batch_destroy": (None, [_vp]),
+    "trex_batch_num_envs": (_int, [_vp]),
+    "trex_batch_set_reward_weights": (_int, [_vp, _f, _f, _f]),
+    "trex_batch_reset": (_int, [_vp, _vp, _vp, _vp]),
+    "trex_batch_step": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "trex_batch_get_state": (_int, [_vp, _vp, _vp]),
+    "trex_batch_set_state": (_int, [_vp, _vp, _vp]),
+    "trex_batch_set_motors_enabled": (_int, [_vp, _int, _vp]),
+    "trex_batch_head_position": (_int, [_vp, _vp, _vp]),
+    "trex_batch_set_domain": (_int, [_vp, _vp, _vp, _vp]),
+    "trex_batch_contact_stats": (_int, [_vp, _vp, _vp, _vp]),
+    "trex_batch_debug_step": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "trex_batch_launch_info": (_int, [_vp, _pint, _pint, _pint, _pint]),
+    "trex_batch_time_steps": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _pf]),
+    "trex_model_num_links": (_int, [_vp]),
+    "trex_model_link_info": (_int, [_vp, _int, _pstr, _pint]),
+    "trex_batch_link_transforms": (_int, [_vp, _vp, _vp]),
+    "trex_model_use_primitive_collision": (_int, [_vp, _d, _int, _int]),
+    "trex_model_fit_hull_primitives": (_int, [_vp, _int, _d, _int, _int, _pd, _int]),
+    "trex_build_id": (_str, []),
+    "trex_batch_step_rows": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    "trex_batch_reset_rows": (_int, [_vp, _vp, _vp, _int, _vp]),
+    "trex_batch_set_episode_limit": (_int, [_vp, _int, _vp, _vp]),
+    "trex_batch_get_episode_steps": (_int, [_vp, _vp, _vp]),
+    "trex_batch_set_wave_balance": (_int, [_vp, _int]),
+    "trex_batch_forget_buffers": (_int, [_vp]),
+    "trex_batch_set_penalties_in_rows": (_int, [_vp, _int]),
+    "trex_model_num_visuals": (_int, [_vp]),
+    "trex_model_visual_info": (_int, [_vp, _int, _pstr, _pint, _pd, _pd]),
+    "trex_batch_visual_transforms": (_int, [_vp, _vp, _vp]),
+    "trex_batch_step_many": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "trex_batch_render": (_int, [_vp, C.POINTER(TrexCamera), _int, _int, _pi32, _int, _vp, _vp, _vp, _vp]),
+    "trex_batch_set_external_wrench": (_int, [_vp, _vp, _vp]),
+    "trex_batch_set_contact_sensor": (_int, [_vp, _int]),
+    "trex_batch_contact_wrench": (_int, [_vp, _vp, _vp]),
+    "trex_batch_set_control_mode": (_int, [_vp, _pi32]),
+    "trex_batch_set_motor_gains": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "trex_batch_set_stiffness_actions": (_int, [_vp, _int, _f]),
+    "trex_batch_inverse_dynamics": (_int, [_vp, _vp, _vp, _vp]),
+    "trex_batch_mass_matrix": (_int, [_vp, _vp, _vp]),
+    "trex_batch_jacobian": (_int, [_vp, _int, _pd, _vp, _vp]),
+    "trex_batch_centroidal": (_int, [_vp, _vp, _vp]),
+    "trex_batch_forward_dynamics": (_int, [_vp, _vp, _vp, _vp]),
+    "trex_batch_solve_mass": (_int, [_vp, _vp, _int, _vp, _vp]),
+    "trex_batch_ray_test": (_int, [_vp, _vp, _int, _int, _int, C.c_uint32, _int, _vp, _vp, _vp, _vp, _vp]),
+    "trex_batch_set_link_probes": (_int, [_vp, _int, _pi32, _pd, _int]),
+    "trex_batch_link_state": (_int, [_vp, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "trex_batch_set_proximity_shapes": (_int, [_vp, _pi32, _pd, _int, _pi32, _int]),
+    "trex_batch_proximity": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "trex_batch_body_clearance": (_int, [_vp, _vp, _vp, _vp]),
+    "trex_batch_set_termination": (_int, [_vp, _f, _f, _pf, _f]),
+    "trex_batch_termination_info": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "trex_batch_inverse_kinematics": (_int, [_vp, _int, _pi32, _int, _vp, _vp, C.c_uint32, C.POINTER(TrexIkParams), _vp, _vp, _vp]),
+    "trex_batch_set_observation": (_int, [_vp, C.POINTER(TrexObsChannel), _int, _pint]),
+    "trex_batch_observation_dim": (_int, [_vp]),
+    "trex_batch_compose_rows": (_int, [_vp, _vp, _int, _vp, _vp, _int, _vp, _int, _vp]),
+}
+
+_POLICY_API = {   # the trainer-side kernels, SURVEY 8f-1
+    "trex_policy_create": (_int, [_int, _int, _int, _int, _int, C.POINTER(_vp)]),
+    "trex_policy_destroy": (None, [_vp]),
+    "trex_policy_param_count": (_int, [_vp]),
+    "trex_policy_param_offsets": (_int, [_vp, _pint]),
+    "trex_policy_get_stats": (_int, [_vp, _pd, _vp]),
+    "trex_policy_set_stats": (_int, [_vp, _pd, _vp]),
+    "trex_policy_get_returns": (_int, [_vp, _vp, _vp]),
+    "trex_policy_observe": (_int, [_vp, _vp, _int, _int, _f, _vp, _vp, _vp, _vp]),
+    "trex_policy_act": (_int, [_vp, _vp, _vp, _int, _f, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
+    "trex_policy_gae": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _f, _f, _f, _vp]),
+    "trex_policy_adam": (_int, [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),
+    "trex_policy_adam_reset": (_int, [_vp, _vp]),
+    "trex_policy_minibatch_stats": (_int, [_vp, _vp, C.c_int64, _vp, _int, _int, _vp, _vp]),
+    "trex_policy_minibatch_step": (_int, [_vp] * 11 + [C.c_int64, _vp, _int, _int, _vp] + [_f] * 8 + [_vp, _vp]),
+    "trex_policy_minibatch_grad": (_int, [_vp] * 9 + [C.c_int64, _vp, _int, _int, _vp] + [_f] * 4 + [_vp, _vp]),
+}
 
 
-lib.trex_policy_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]
-lib.trex_policy_destroy.argtypes = [_vp]
-lib.trex_policy_destroy.restype = None
-lib.trex_policy_param_count.argtypes = [_vp]
-lib.trex_policy_param_offsets.argtypes = [_vp, C.POINTER(C.c_int)]
-lib.trex_policy_get_stats.argtypes = [_vp, C.POINTER(C.c_double), _vp]
-lib.trex_policy_set_stats.argtypes = [_vp, C.POINTER(C.c_double), _vp]
-lib.trex_policy_get_returns.argtypes = [_vp, _vp, _vp]
-lib.trex_policy_observe.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_float, _vp, _vp, _vp, _vp]
-lib.trex_policy_act.argtypes = [_vp, _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp]
-lib.trex_policy_gae.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_float, C.c_float, C.c_float, _vp]
-lib.trex_policy_adam.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp]
-lib.trex_policy_adam_reset.argtypes = [_vp, _vp]
-lib.trex_policy_minibatch_stats.argtypes = [_vp, _vp, C.c_int64, _vp, C.c_int, C.c_int, _vp, _vp]
-lib.trex_policy_minibatch_step.argtypes = ([_vp] * 11 + [C.c_int64, _vp, C.c_int, C.c_int, _vp] + [C.c_float] * 8 + [_vp, _vp])
-lib.trex_policy_minibatch_grad.argtypes = ([_vp] * 9 + [C.c_int64, _vp, C.c_int, C.c_int, _vp] + [C.c_float] * 4 + [_vp, _vp])
+def _declare(table):
+    """Give every function of `table` that the loaded library exports its restype and argtypes; -> the table's names."""
+    for name, (restype, argtypes) in table.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    return list(table)
+
+
+SYMBOLS = _declare(_BATCH_API)            # every symbol include/trex_batch.h declares
+POLICY_SYMBOLS = _declare(_POLICY_API)    # every symbol include/trex_policy.h declares
 
 
 class TrexError(RuntimeError):
@@ -222,6 +195,21 @@ def _ptr(t, device=None, dtype=None, numel=None, what="tensor"):
     if numel is not None and t.numel() < numel:
         raise TrexError(E_INVALID, "%s: expected at least %d elements, got %d" % (what, numel, t.numel()))
     return C.c_void_p(t.data_ptr())
+
+
+def _shaped(t, shape, what):
+    """t - a tensor, an array or None - as it is, where its shape is exactly the tuple `shape`; else TREX_E_INVALID."""
+    if t is not None and tuple(t.shape) != shape:
+        raise TrexError(E_INVALID, "%s: expected shape %s, got %s" % (what, shape, tuple(t.shape)))
+    return t
+
+
+def _flags(t, what):
+    """t - a tensor of flags or None - as it is, where it is uint8 or bool (the same byte layout: the step hands `done` out as
+    bool); else TREX_E_INVALID."""
+    if t is not None and t.dtype not in (torch.uint8, torch.bool):
+        raise TrexError(E_INVALID, "%s: expected dtype uint8 or bool, got %s" % (what, t.dtype))
+    return t
 
 
 def default_urdf_path():
@@ -345,23 +333,27 @@ class Batch:
     @staticmethod
     def _stream(stream):
         if stream is None:
-            import torch
-            return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+                return C.c_void_p(torch.cuda.current_stream().cuda_stream)
         return C.c_void_p(stream)
 
     def set_reward_weights(self, distance, energy, drift):
         check(lib.trex_batch_set_reward_weights(self.h, distance, energy, drift))
 
     def _p(self, t, dtype, numel, what):
-        import torch
         return _ptr(t, self.device, getattr(torch, dtype), numel, what)
 
     def _mask(self, mask):
-        """reset mask [n]: uint8 or bool (the same byte layout; step_rows hands `done` out as bool)."""
-        import torch
-        if mask is not None and mask.dtype not in (torch.uint8, torch.bool):
-            raise TrexError(E_INVALID, "mask: expected dtype uint8 or bool, got %s" % mask.dtype)
-        return _ptr(mask, self.device, None, self.num_envs, "mask")
+        """reset mask [n]: uint8 or bool"""
+        return _ptr(_flags(mask, "mask"), self.device, None, self.num_envs, "mask")
+
+    def _rows(self, rows, what, width=None, steps=None):
+        """void* of the row block rows [n, stride] (with steps=S: [S, n, stride]), long enough for `width` columns in its last
+        row: 3J + tail where None, 3J + E + tail for the composed block; the tail is reward | done, and the three penalties
+        with penalties in the rows."""
+        if width is None:
+            width = 3 * self.J + (5 if self.pen_in_rows else 2)
+        count, stride = (self.num_envs, rows.shape[1]) if steps is None else (steps * self.num_envs, rows.shape[2])
+        return self._p(rows, "float32", (count - 1) * stride + width, what)
 
     def set_wave_balance(self, mode):
         """-1 auto (on from 2048 envs), 0 off (workgroup k runs env k), 1 on: include/trex_batch.h."""
@@ -373,8 +365,8 @@ class Batch:
     pen_in_rows = False
 
     def set_penalties_in_rows(self, enabled):
-        self.pen_in_rows = bool(enabled)
         """Row-block calls write the three penalties to columns 3J+2 .. 3J+4 (row_stride >= 3J + 5): include/trex_batch.h."""
+        self.pen_in_rows = bool(enabled)
         check(lib.trex_batch_set_penalties_in_rows(self.h, 1 if enabled else 0))
 
     def reset(self, obs_out=None, mask=None, stream=None):
@@ -391,33 +383,25 @@ class Batch:
     def step_rows(self, actions, rows, penalties=None, stream=None, done=None):
         """One step writing the [n, stride] row block obs | reward | done (stride = rows.shape[1] >= 3J + 2);
         done [n] uint8 or bool, optional: the flags once more as bytes."""
-        import torch
-        n, J = self.num_envs, self.J
-        if done is not None and done.dtype not in (torch.uint8, torch.bool):
-            raise TrexError(E_INVALID, "done: expected dtype uint8 or bool, got %s" % done.dtype)
+        n = self.num_envs
+        _flags(done, "done")
         check(lib.trex_batch_step_rows(self.h, self._p(actions, "float32", n * self.A, "actions"),
-                                       self._p(rows, "float32", (n - 1) * rows.shape[1] + 3 * J + (5 if self.pen_in_rows else 2), "rows"), int(rows.shape[1]),
-                                       self._p(penalties, "float32", 3 * n, "penalties"),
+                                       self._rows(rows, "rows"), int(rows.shape[1]), self._p(penalties, "float32", 3 * n, "penalties"),
                                        _ptr(done, self.device, None, n, "done"), self._stream(stream)))
 
     def step_many(self, actions, rows, penalties=None, done=None, stream=None):
         """S env-steps in one launch: actions [S, n, J], rows [S, n, stride] (obs | reward | done per row)."""
-        import torch
         n, J, S = self.num_envs, self.J, int(actions.shape[0])
-        if done is not None and done.dtype not in (torch.uint8, torch.bool):
-            raise TrexError(E_INVALID, "done: expected dtype uint8 or bool, got %s" % done.dtype)
+        _flags(done, "done")
         if rows.dim() != 3 or int(rows.shape[0]) != S or int(rows.shape[1]) != n:
             raise TrexError(E_INVALID, "rows: expected shape [%d, %d, >= %d], got %s" % (S, n, 3 * J + 2, tuple(rows.shape)))
         check(lib.trex_batch_step_many(self.h, self._p(actions, "float32", S * n * self.A, "actions"),
-                                       self._p(rows, "float32", (S * n - 1) * rows.shape[2] + 3 * J + (5 if self.pen_in_rows else 2), "rows"), int(rows.shape[2]), S,
+                                       self._rows(rows, "rows", steps=S), int(rows.shape[2]), S,
                                        self._p(penalties, "float32", 3 * S * n, "penalties"), _ptr(done, self.device, None, S * n, "done"),
                                        self._stream(stream)))
 
     def reset_rows(self, rows, mask=None, stream=None):
-        n, J = self.num_envs, self.J
-        check(lib.trex_batch_reset_rows(self.h, self._mask(mask),
-                                        self._p(rows, "float32", (n - 1) * rows.shape[1] + 3 * J + (5 if self.pen_in_rows else 2), "rows"),
-                                        int(rows.shape[1]), self._stream(stream)))
+        check(lib.trex_batch_reset_rows(self.h, self._mask(mask), self._rows(rows, "rows"), int(rows.shape[1]), self._stream(stream)))
 
     def set_episode_limit(self, max_episode_steps, episode_steps=None, stream=None):
         """Episode limit inside the step launch (0 = off); episode_steps [n] int32 sets the per-env counts."""
@@ -462,10 +446,7 @@ class Batch:
         """External wrench [n, num_bodies, 6] f32 on the batch's device: fx fy fz at each moving body's COM, tx ty tz about
         it, world axes (include/trex_batch.h). Copied; held for every substep of every later env-step until replaced.
         None clears it (the default kernels again)."""
-        if wrench is not None:
-            shape = (self.num_envs, self.model.num_bodies, 6)
-            if tuple(wrench.shape) != shape:
-                raise TrexError(E_INVALID, "wrench: expected shape %s, got %s" % (shape, tuple(wrench.shape)))
+        _shaped(wrench, (self.num_envs, self.model.num_bodies, 6), "wrench")
         check(lib.trex_batch_set_external_wrench(self.h, self._p(wrench, "float32", self.num_envs * self.model.num_bodies * 6,
                                                                  "wrench"), self._stream(stream)))
 
@@ -494,8 +475,7 @@ class Batch:
         parameter; all three None clears (include/trex_batch.h). Copied."""
         shape = (self.num_envs, self.J)
         for name, t in (("kp", kp), ("kd", kd), ("max_force", max_force)):
-            if t is not None and tuple(t.shape) != shape:
-                raise TrexError(E_INVALID, "%s: expected shape %s, got %s" % (name, shape, tuple(t.shape)))
+            _shaped(t, shape, name)
         nJ = self.num_envs * self.J
         check(lib.trex_batch_set_motor_gains(self.h, self._p(kp, "float32", nJ, "kp"), self._p(kd, "float32", nJ, "kd"),
                                              self._p(max_force, "float32", nJ, "max_force"), self._stream(stream)))
@@ -515,7 +495,6 @@ class Batch:
         """The contact sensor's values into out [n, num_bodies, 6] f32 on the batch's device (made when None) and returned:
         force at each body's COM and torque about it, world axes, the mean over the solves since the env's last
         observation."""
-        import torch
         if out is None:
             out = torch.empty(self.num_envs, self.model.num_bodies, 6, dtype=torch.float32, device=self.device)
         check(lib.trex_batch_contact_wrench(self.h, self._p(out, "float32", self.num_envs * self.model.num_bodies * 6, "out"),
@@ -524,19 +503,15 @@ class Batch:
 
     # ---- dynamics queries (include/trex_batch.h): read the state, write `out` (made when None) and return it
     def _out(self, out, *shape):
-        import torch
         if out is None:
-            out = torch.empty(self.num_envs, *shape, dtype=torch.float32, device=self.device)
-        elif tuple(out.shape) != (self.num_envs,) + shape:
-            raise TrexError(E_INVALID, "out: expected shape %s, got %s" % ((self.num_envs,) + shape, tuple(out.shape)))
-        return out
+            return torch.empty(self.num_envs, *shape, dtype=torch.float32, device=self.device)
+        return _shaped(out, (self.num_envs,) + shape, "out")
 
     def inverse_dynamics(self, accel=None, out=None, stream=None):
         """[n, D] generalised force M a + h of accel [n, D] (None = zeros) at the current state, D = 6 + J: base force, base
         torque about the base origin, joint torques in observation order. Rigid-body terms only."""
         D = 6 + self.J
-        if accel is not None and tuple(accel.shape) != (self.num_envs, D):
-            raise TrexError(E_INVALID, "accel: expected shape %s, got %s" % ((self.num_envs, D), tuple(accel.shape)))
+        _shaped(accel, (self.num_envs, D), "accel")
         out = self._out(out, D)
         check(lib.trex_batch_inverse_dynamics(self.h, self._p(accel, "float32", self.num_envs * D, "accel"),
                                               self._p(out, "float32", self.num_envs * D, "out"), self._stream(stream)))
@@ -568,8 +543,7 @@ class Batch:
             raise TrexError(E_INVALID, "links: expected link indices")
         links = links.astype(np.int32)
         pos = np.zeros((K, 3)) if positions is None else np.ascontiguousarray(np.asarray(positions, dtype=np.float64))
-        if pos.shape != (K, 3):
-            raise TrexError(E_INVALID, "positions: expected shape %s, got %s" % ((K, 3), pos.shape))
+        _shaped(pos, (K, 3), "positions")
         check(lib.trex_batch_set_link_probes(self.h, int(set), links.ctypes.data_as(C.POINTER(C.c_int32)),
                                              pos.ctypes.data_as(C.POINTER(C.c_double)), K))
 
@@ -579,12 +553,11 @@ class Batch:
         1 link, 2 base; proper: + g z on the linear acceleration. probes: K, where the caller knows it - the sizes the buffers
         are checked against before the call (the library checks them against the set's size either way)."""
         n, D = self.num_envs, 6 + self.J
-        if accel is not None and tuple(accel.shape) != (n, D):
-            raise TrexError(E_INVALID, "accel: expected shape %s, got %s" % ((n, D), tuple(accel.shape)))
+        _shaped(accel, (n, D), "accel")
         K = None if probes is None else int(probes)
         def ptr(t, width, what):
-            if t is not None and K is not None and tuple(t.shape) != (n, K, width):
-                raise TrexError(E_INVALID, "%s: expected shape %s, got %s" % (what, (n, K, width), tuple(t.shape)))
+            if K is not None:
+                _shaped(t, (n, K, width), what)
             return self._p(t, "float32", 0 if t is None or K is None else n * K * width, what)
         check(lib.trex_batch_link_state(self.h, int(set), int(axes), 1 if proper else 0, self._p(accel, "float32", n * D, "accel"),
                                         ptr(pose, 7, "pose"), ptr(velocity, 6, "velocity"), ptr(acceleration, 6, "acceleration"),
@@ -602,11 +575,9 @@ class Batch:
         if K and (modes.min() < 0 or modes.max() > 255):
             raise TrexError(E_INVALID, "modes: expected values 1..3")
         modes = modes.astype(np.int32)
-        if tuple(target.shape) != (n, K, 7):
-            raise TrexError(E_INVALID, "target: expected shape %s, got %s" % ((n, K, 7), tuple(target.shape)))
-        for t, what in ((q_init, "q_init"), (q_out, "q_out")):
-            if t is not None and tuple(t.shape) != (n, J):
-                raise TrexError(E_INVALID, "%s: expected shape %s, got %s" % (what, (n, J), tuple(t.shape)))
+        _shaped(target, (n, K, 7), "target")
+        _shaped(q_init, (n, J), "q_init")
+        _shaped(q_out, (n, J), "q_out")
         mask = (1 << J) - 1 if joint_mask is None else int(joint_mask)
         if not 0 <= mask < 1 << 32:
             raise TrexError(E_INVALID, "joint_mask: expected a 32-bit mask")
@@ -624,8 +595,7 @@ class Batch:
         bodies = np.ascontiguousarray(np.asarray(bodies, dtype=np.int64).reshape(-1))
         Cn = int(bodies.size)
         caps = np.zeros((Cn, 7)) if capsules is None else np.ascontiguousarray(np.asarray(capsules, dtype=np.float64))
-        if caps.shape != (Cn, 7):
-            raise TrexError(E_INVALID, "capsules: expected shape %s, got %s" % ((Cn, 7), caps.shape))
+        _shaped(caps, (Cn, 7), "capsules")
         pr = np.zeros((0, 2), np.int64) if pairs is None else np.ascontiguousarray(np.asarray(pairs, dtype=np.int64))
         if pr.size == 0:
             pr = pr.reshape(0, 2)
@@ -647,9 +617,8 @@ class Batch:
         n = self.num_envs
         P = None if pairs is None else int(pairs)
         def ptr(t, width, what, dtype="float32"):
-            shape = (n, P) if width == 1 else (n, P, width)
-            if t is not None and P is not None and tuple(t.shape) != shape:
-                raise TrexError(E_INVALID, "%s: expected shape %s, got %s" % (what, shape, tuple(t.shape)))
+            if P is not None:
+                _shaped(t, (n, P) if width == 1 else (n, P, width), what)
             return self._p(t, dtype, 0 if t is None or P is None else n * P * width, what)
         check(lib.trex_batch_proximity(self.h, ptr(distance, 1, "distance"), ptr(point_a, 3, "point_a"), ptr(point_b, 3, "point_b"),
                                        ptr(normal, 3, "normal"), ptr(capsule, 2, "capsule", "int32"), self._stream(stream)))
@@ -660,8 +629,7 @@ class Batch:
         lowest [n, num_bodies, 3] optional: that point's world position."""
         nb = self.model.num_bodies
         clearance = self._out(clearance, nb)
-        if lowest is not None and tuple(lowest.shape) != (self.num_envs, nb, 3):
-            raise TrexError(E_INVALID, "lowest: expected shape %s, got %s" % ((self.num_envs, nb, 3), tuple(lowest.shape)))
+        _shaped(lowest, (self.num_envs, nb, 3), "lowest")
         check(lib.trex_batch_body_clearance(self.h, self._p(clearance, "float32", self.num_envs * nb, "clearance"),
                                             self._p(lowest, "float32", self.num_envs * nb * 3, "lowest"), self._stream(stream)))
         return clearance
@@ -717,11 +685,10 @@ class Batch:
         for t, what in ((rows, "rows"), (out, "out"), (extern, "extern")):
             if t is not None and (not hasattr(t, "dim") or t.dim() != 2 or t.shape[0] != n):
                 raise TrexError(E_INVALID, "%s: expected a tensor of shape [%d, columns]" % (what, n))
-        check(lib.trex_batch_compose_rows(self.h, self._p(rows, "float32", (n - 1) * rows.shape[1] + 3 * J + tail, "rows"), int(rows.shape[1]),
+        check(lib.trex_batch_compose_rows(self.h, self._rows(rows, "rows"), int(rows.shape[1]),
                                           self._p(actions, "float32", n * self.A, "actions"),
                                           self._p(extern, "float32", None, "extern"), 0 if extern is None else int(extern.shape[1]),
-                                          self._p(out, "float32", (n - 1) * out.shape[1] + 3 * J + self.obs_extra + tail, "out"),
-                                          int(out.shape[1]), self._stream(stream)))
+                                          self._rows(out, "out", 3 * J + self.obs_extra + tail), int(out.shape[1]), self._stream(stream)))
 
     def centroidal(self, out=None, stream=None):
         """[n, 16]: COM position, COM velocity, linear momentum, angular momentum about the COM, kinetic energy, potential
@@ -734,8 +701,7 @@ class Batch:
         """[n, D] accelerations M^-1 (force - h) for the generalised force `force` [n, D] (None = zeros) at the current state:
         the inverse of inverse_dynamics. `out` may be `force` itself."""
         D = 6 + self.J
-        if force is not None and tuple(force.shape) != (self.num_envs, D):
-            raise TrexError(E_INVALID, "force: expected shape %s, got %s" % ((self.num_envs, D), tuple(force.shape)))
+        _shaped(force, (self.num_envs, D), "force")
         out = self._out(out, D)
         check(lib.trex_batch_forward_dynamics(self.h, self._p(force, "float32", self.num_envs * D, "force"),
                                               self._p(out, "float32", self.num_envs * D, "out"), self._stream(stream)))
@@ -790,15 +756,12 @@ class Batch:
         [R, 6] for one pattern shared by every env (shared defaults from the rank) - from xyz, to xyz in the frame of URDF link
         index `link` (-1: world). body_mask: bit b = body b may be hit; hit_floor: the floor may be. Outputs, device tensors:
         fraction [n, R] f32 (made when None, and returned), body [n, R] int32, position and normal [n, R, 3] f32, each optional."""
-        import torch
         if not hasattr(rays, "dim") or rays.dim() not in (2, 3) or rays.shape[-1] != 6:
             raise TrexError(E_INVALID, "rays: expected a tensor of shape [n, R, 6] or [R, 6]")
         if shared is None:
             shared = rays.dim() == 2
         n, R = self.num_envs, int(rays.shape[-2])
-        want = (R, 6) if shared else (n, R, 6)
-        if tuple(rays.shape) != want:
-            raise TrexError(E_INVALID, "rays: expected shape %s, got %s" % (want, tuple(rays.shape)))
+        _shaped(rays, (R, 6) if shared else (n, R, 6), "rays")
         mask = int(body_mask)
         if not 0 <= mask <= 0xFFFFFFFF:
             raise TrexError(E_INVALID, "body_mask: expected a 32-bit mask, got %r" % (body_mask,))
@@ -806,8 +769,7 @@ class Batch:
             fraction = torch.empty(n, R, dtype=torch.float32, device=rays.device)
         for name, t, shape in (("fraction", fraction, (n, R)), ("body", body, (n, R)), ("position", position, (n, R, 3)),
                                ("normal", normal, (n, R, 3))):
-            if t is not None and tuple(t.shape) != shape:
-                raise TrexError(E_INVALID, "%s: expected shape %s, got %s" % (name, shape, tuple(t.shape)))
+            _shaped(t, shape, name)
         check(lib.trex_batch_ray_test(self.h, self._p(rays, "float32", (1 if shared else n) * R * 6, "rays"), R, 1 if shared else 0,
                                       int(link), mask, 1 if hit_floor else 0, self._p(fraction, "float32", n * R, "fraction"),
                                       self._p(body, "int32", n * R, "body"), self._p(position, "float32", n * R * 3, "position"),
@@ -859,7 +821,6 @@ class Policy:
             pass
 
     def _p(self, t, numel, what, dtype="float32"):
-        import torch
         return _ptr(t, self.device, getattr(torch, dtype), numel, what)
 
     _stream = staticmethod(Batch._stream)

@@ -25,8 +25,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--envs", type=int, default=4096)
     args = ap.parse_args()
-    import test_forward_dynamics_ref as TR
-    import test_gpu_forward_dynamics as T
+    import test_forward_dynamics_ref as TR        # (for oracle32_deviation alone)
+    import test_gpu_forward_dynamics as T         # (for its deviations alone)
     from conftest import ASSET_URDF
     from oracle import oracle as O, trex_model
     from trex_gym import _capi
@@ -40,7 +40,8 @@ def main():
         d = T.deviations(o64, model, n)
         lines.append("  N = %-3d " % n + "  ".join("%s %.3g" % kv for kv in sorted(d.items())))
         print(lines[-1], flush=True)
-    ls, _ = TR.landing_states(o64, model)
+    from state_sets import landing_states
+    ls, _ = landing_states(o64, model)
     import numpy as np
     import dynamics_ref as R
     cases = [(s.astype(np.float64), None) for s in ls] + list(zip(*R.random_states(model, 8)))

@@ -88,9 +88,11 @@ def main():
             f.write("\n".join(lines) + "\n")
 
     if not args.no_deviations:
+        import ik_cases as IC
         import synthetic_models as sm
-        import test_gpu_inverse_kinematics as T
+        import test_gpu_inverse_kinematics as T       # (for its deviations alone)
         from conftest import ASSET_URDF
+        from gpu_support import case_env
         from oracle import trex_model
         model = trex_model.compile_model(ASSET_URDF)
         say("largest deviations on the cases of tests/ik_cases.py (tests/test_gpu_inverse_kinematics.py: MEASURED):")
@@ -101,8 +103,8 @@ def main():
         with tempfile.TemporaryDirectory() as tmp:
             for name in ("deep_chain", "bushy"):
                 path, props, om = sm.compile_both(name, os.path.join(tmp, name))
-                make = lambda cs, q=None: T.make_env(om, cs, q, path, props["params"])
-                w = max(T.one_iteration_deviation(om, T.form_of(om, f), 3, name, make) for f in ("pos4", "head_ori", "same_body", "one_leg"))
+                make = lambda cs, q=None: case_env(om, cs, q, path, props["params"])
+                w = max(T.one_iteration_deviation(om, IC.form_of(om, f), 3, name, make) for f in ("pos4", "head_ori", "same_body", "one_leg"))
                 say("  %-10s N = 3, one iteration: |q - q_ref|                                           %.3g rad" % (name, w))
         say("")
         flush()

@@ -82,10 +82,11 @@ def main():
     if not args.no_deviations:
         import proximity_cases as PC
         import synthetic_models as sm
-        import test_gpu_proximity as T
+        import test_gpu_proximity as T                # (for its deviations and FIGS alone)
         from conftest import ASSET_URDF
+        from gpu_support import loaded_vec
         from oracle import oracle as O, trex_model
-        from test_gpu_dynamics import case_states, loaded_vec
+        from state_sets import case_states
         model = trex_model.compile_model(ASSET_URDF)
         o64 = O.Oracle(model, precision="f64")
         T.TOL = {k: T.CAP for k in T.TOL}          # measure: the cap in force, not 4 x the figures this run is to find

@@ -23,6 +23,7 @@ import numpy as np
 import synthetic_models as sm
 from conftest import ASSET_URDF
 from parity_helpers import assert_step_close, oracle_wrench
+from state_sets import landing_states
 
 G = 9.81
 WARM = 0.85                     # Bullet's warmstartingFactor
@@ -139,19 +140,8 @@ def deviation(b, r64, r32):
 
 # ---------------------------------------------------------------- candidates
 def landing_candidates(b):
-    """the 50 states and actions along the 300-step landing of tests/test_gpu_warmstart.py::landing_states (one every 6 steps)"""
-    om, orc = b.om, b.o64
-    q0 = om["q_start"][om["obs_order"]]
-    lo, hi = om["q_lower"][om["obs_order"]], om["q_upper"][om["obs_order"]]
-    rng = np.random.default_rng(5)
-    s = orc.new_state()
-    orc.reset(s)
-    states, acts = [], []
-    for t in range(300):
-        orc.step(s, np.clip(q0 + 0.15 * rng.normal(size=b.J), lo, hi))
-        if t % 6 == 0:
-            states.append(orc.get_state(s).astype(np.float32))
-            acts.append(np.clip(q0 + 0.15 * rng.normal(size=b.J), lo, hi).astype(np.float32))
+    """the 50 states and actions along the 300-step landing of state_sets.landing_states (one every 6 steps), on b's own oracle"""
+    states, acts = landing_states(b.o64, b.om, every=6)
     return [dict(state=s, action=a, steps=3, origin="landing %d" % (6 * k)) for k, (s, a) in enumerate(zip(states, acts))]
 
 

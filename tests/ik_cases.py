@@ -71,6 +71,10 @@ def forms(model):
     ]
 
 
+def form_of(model, name):
+    return [f for f in forms(model) if f.name == name][0]
+
+
 def poses(model, state, q, form):
     """the form's probes at joint angles q: {"world": [K, 7], "base": [K, 7]}, rounded to f32"""
     s = IK.with_q(model, state, q)

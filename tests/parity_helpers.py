@@ -1,6 +1,11 @@
-"""Shared by the GPU parity tests: the one-step comparison with the f64 oracle at the tolerances stated at the top of
-tests/test_gpu_parity.py, for any joint count and motor limit, and the per-body contact wrench of one env-step restated on the oracle."""
+"""Shared by the GPU parity tests: the committed golden rollout, the one-step comparison with the f64 oracle at the tolerances stated
+at the top of tests/test_gpu_parity.py, for any joint count and motor limit, and the per-body contact wrench of one env-step restated
+on the oracle."""
+import os
+
 import numpy as np
+
+GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "oracle_rollout.npz"))
 
 
 def assert_step_close(g_obs, o_obs, g_rew=None, o_rew=None, what="", q_atol=1e-4, loosen=1.0, J=25, max_force=3.0e5,

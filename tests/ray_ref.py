@@ -186,7 +186,7 @@ def single_ray():
     return np.array([[0.02, 0.01, 4.0, 0.02, 0.01, -6.0]], np.float32)
 
 
-MARGIN = 1e-4          # metres: the renderer's own threshold (tests/test_gpu_render.py::_compare)
+MARGIN = 1e-4          # metres: the renderer's own threshold (tests/gpu_render_support.py::render_compare)
 MARGINAL_CAP = 0.02    # at most this share of a case's rays may be marginal
 HEAD_LINK, BASE_LINK = "link_cranium", "link_vertebrae_sacral"
 FOOT_LINKS = ("link_tarsometatarsus_right", "link_tarsometatarsus_left")

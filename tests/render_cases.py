@@ -4,7 +4,7 @@ view and aspect ratios; and the generated models (tests/synthetic_models.py) wit
 (csrc/render_pose.h). numpy only: tests/test_render_cases_host.py qualifies every case on the f64 reference caster
 (tests/render_ref.py) alone, before a GPU sees it; tests/test_gpu_render_edges.py renders the same cases. A helper, not a conftest.
 
-A case is (camera, frame, state). It only counts if the reference is DECIDED on it - tests/test_gpu_render.py::_compare leaves out
+A case is (camera, frame, state). It only counts if the reference is DECIDED on it - tests/gpu_render_support.py::render_compare leaves out
 the pixels whose reference margin is below 1e-4 m and allows 0.5 % of label disagreements among them, so a case made mostly of
 such pixels would pass whatever the kernel does - and if it REACHES the path it is named for. qualify() and paths_reached() state
 both conditions; a case that fails them is repaired by moving its camera, never by loosening them.
@@ -15,8 +15,8 @@ import numpy as np
 
 import render_ref as rr
 
-MARGIN = 1e-4              # m: the threshold of tests/test_gpu_render.py::_compare
-SEG_SHARE_CAP = 0.0025     # share of pixels with seg_margin < MARGIN: half of what _compare tolerates as disagreement
+MARGIN = 1e-4              # m: the threshold of tests/gpu_render_support.py::render_compare
+SEG_SHARE_CAP = 0.0025     # share of pixels with seg_margin < MARGIN: half of what render_compare tolerates as disagreement
 TINY_PIXELS, TINY_MARGIN = 400, 1e-3     # frames under 400 pixels: no pixel at all near a decision (0.5 % of them is < 2 pixels)
 RGB_PIXELS, RGB_SHARE_CAP = 1000, 0.05   # frames of 1000 pixels or more: share with rgb_margin < MARGIN
 RGB_USED_MIN = 0.93        # GPU side: share of pixels the rgb comparison uses = 1 - 5 % - 0.5 % - a little for f32 poses

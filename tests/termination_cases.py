@@ -5,7 +5,7 @@ not a conftest.
 
 States, per collision model:
   hulls       every accepted fallen state of episode_cases' groups `hulls` and `hulls_domain` (the latter with its mass scales), then
-              the start state at rest and the 33 landing / airborne states of test_gpu_dynamics.case_states;
+              the start state at rest and the 33 landing / airborne states of state_sets.case_states;
   primitives  every accepted fallen state of episode_cases' group `primitives`, then the start state.
 Thresholds, per collision model, from the reference's values on these states alone: a head height, a tilt (as its cosine) and a
 least clearance of ONE watched body, each the midpoint of a gap of at least MIN_GAP between two neighbours of the sorted values -
@@ -16,6 +16,7 @@ import numpy as np
 import episode_cases as ec
 import feature_cases as fc
 import termination_ref as TR
+from state_sets import case_states
 
 MIN_GAP = 2.5e-3
 CLEAR = 1e-3          # what the host test asserts: every state at least this far from every threshold
@@ -45,7 +46,6 @@ def states(collision):
                 for c in ec.group("hulls_domain")["cases"]]
     out.append(dict(state=fc.start_state(b.om).astype(np.float32), mass_scale=None, origin="start"))
     if collision != "primitives":
-        from test_gpu_dynamics import case_states
         for k, (s, ms) in enumerate(case_states(b.o64, b.om, 33)):
             out.append(dict(state=s.astype(np.float32), mass_scale=None if ms is None else ms.astype(np.float32),
                             origin="case_states %d" % k))

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import dynamics_ref as R
-from test_gpu_external_wrench import landing_states
+from state_sets import landing_states, oracle_state
 
 TOL = 1e-8
 G = 9.81
@@ -22,14 +22,6 @@ def cases(oracle64, model):
     out = [(s.astype(np.float64), None) for s in ls]
     out += list(zip(*R.random_states(model, 8)))
     return out
-
-
-def oracle_state(oracle64, state, scale):
-    s = oracle64.new_state()
-    if scale is not None:
-        oracle64.set_domain(s, scale)
-    oracle64.set_state(s, state)
-    return s
 
 
 def test_velocity_order_against_oracle_get_state(oracle64, model):

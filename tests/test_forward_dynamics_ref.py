@@ -11,7 +11,7 @@ import pytest
 
 import dynamics_ref as R
 import forward_dynamics_ref as F
-from test_gpu_external_wrench import landing_states
+from state_sets import landing_states, oracle_state
 
 TOL = 1e-8
 G = 9.81
@@ -21,14 +21,6 @@ G = 9.81
 def cases(oracle64, model):
     ls, _ = landing_states(oracle64, model)
     return [(s.astype(np.float64), None) for s in ls] + list(zip(*R.random_states(model, 8)))
-
-
-def oracle_state(orc, state, scale):
-    s = orc.new_state()
-    if scale is not None:
-        orc.set_domain(s, scale)
-    orc.set_state(s, state)
-    return s
 
 
 def oracle_accel(orc, state, scale, tau):

@@ -5,18 +5,13 @@ import pytest
 import torch
 
 from conftest import ASSET_URDF
-from test_gpu_external_wrench import contact_counts, landing_states, random_actions
-from test_gpu_parity import GOLD, assert_step_close
+from gpu_support import DEV, contact_counts, make_vec, random_actions
+from parity_helpers import GOLD, assert_step_close
+from state_sets import landing_states
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NB, J = 26, 25
 KP0, KD0, F0 = 5e-3, 0.1, 3e5
-
-
-def make_vec(n, **kw):
-    from trex_gym.vec_env import TrexVecEnv
-    return TrexVecEnv(n, urdf_path=ASSET_URDF, device=DEV, **kw)
 
 
 def rollout(v, acts, keep_state=True):

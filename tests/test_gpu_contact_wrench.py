@@ -9,12 +9,11 @@ import pytest
 import torch
 
 from conftest import ASSET_URDF
-from parity_helpers import oracle_wrench
-from test_gpu_external_wrench import landing_states, make_vec, random_actions
-from test_gpu_parity import GOLD
+from gpu_support import DEV, make_vec, random_actions
+from parity_helpers import GOLD, oracle_wrench
+from state_sets import landing_states
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NB, J = 26, 25
 
 

@@ -2,7 +2,7 @@
 against the f64 restatement tests/dynamics_ref.py - itself tied to the oracle by tests/test_dynamics_ref.py - and against the
 oracle and the step kernel directly; plus read-only, refusals, stream capture, containment and the product's grid sizes.
 
-States: the landing states of test_gpu_external_wrench and 8 random airborne ones (two with a per-body mass scale), cycled over
+States (state_sets.case_states): the landing states and 8 random airborne ones (two with a per-body mass scale), cycled over
 the envs with an env-specific perturbation from the second lap on, so that EVERY env has a state of its own.
 
 Tolerances (TOL): 4 x the largest deviation measured on these very states at N = 67 (scripts/dynamics_bench.py prints them;
@@ -21,76 +21,15 @@ import torch
 
 import dynamics_ref as R
 from conftest import ASSET_URDF
-from test_gpu_external_wrench import landing_states
+from gpu_support import DEV, dynamics_queries as all_queries, loaded_vec, make_vec, random_actions
+from state_sets import base_cases, case_states, oracle_state, probe_links
+from tolerances import DYNAMICS_CAPS as CAPS, DYNAMICS_MEASURED as MEASURED, DYNAMICS_TOL as TOL  # noqa: F401  (MEASURED: the docstrings' pointer)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NB, J, D = 26, 25, 31
 G = 9.81
 
-# Largest deviations measured at N = 67 on an MI355X (profiles/r12_dynamics.txt). Tolerance = 4 x measured, never above the cap;
-# no cap binds. The round trip and the step-tied check draw their torques with dynamics_ref.random_tau - every joint accelerates
-# within 10 rad/s^2 - and compare with [0, tau] itself, the rounding of the accelerations to f32 included. (Torques drawn joint
-# by joint, without regard to the coupling, throw the light links at 1e3 .. 1e5 rad/s^2; the body forces that cancel to tau
-# are then tens of times larger than tau and the round trip sat at 2.5e-5 .. 4.7e-5, half of it the f32 rounding of the input.)
-MEASURED = dict(id_zero=4.38e-7, id_roundtrip=7.56e-7, id_step=2.21e-6, mass=1.81e-6, minv=1.82e-7, jac=2.59e-7, cent=1.05e-5)
-CAPS = dict(id_zero=1e-4, id_roundtrip=1e-4, id_step=1e-4, mass=1e-5, minv=1e-5, jac=1e-4, cent=1e-4)
-TOL = {k: min(4 * v, CAPS[k]) for k, v in MEASURED.items()}
-
-
-def make_vec(n, **kw):
-    from trex_gym.vec_env import TrexVecEnv
-    return TrexVecEnv(n, urdf_path=ASSET_URDF, device=DEV, **kw)
-
-
-_CASES = {}
-
-
-def case_states(oracle64, model, n):
-    """n distinct (state f32-exact f64 [63], mass scale or None); computed once per n"""
-    if n in _CASES:
-        return _CASES[n]
-    if "base" not in _CASES:
-        ls, _ = landing_states(oracle64, model)
-        rs, sc = R.random_states(model, 8)
-        _CASES["base"] = [(s.astype(np.float64), None) for s in ls] + list(zip(rs, sc))
-    base = _CASES["base"]
-    rng = np.random.default_rng(100 + n)
-    oo = model["obs_order"]
-    lo, hi = model["q_lower"][oo], model["q_upper"][oo]
-    out = []
-    for e in range(n):
-        s, ms = base[(e * 7) % len(base)] if n < len(base) else base[e % len(base)]
-        if e >= len(base):
-            s = s.copy()
-            s[13:13 + J] = np.clip(s[13:13 + J] + 0.1 * rng.normal(size=J), lo, hi)
-            s[7:13] += 0.3 * rng.normal(size=6)
-            s[13 + J:] += 0.5 * rng.normal(size=J)
-            s = s.astype(np.float32).astype(np.float64)
-        out.append((s, ms))
-    _CASES[n] = out
-    return out
-
-
-def loaded_vec(cases, n=None, **kw):
-    """a TrexVecEnv of n envs holding cases[e % len(cases)] (mass scales included)"""
-    n = len(cases) if n is None else n
-    v = make_vec(n, **kw)
-    v.reset()
-    idx = np.arange(n) % len(cases)
-    ms = np.array([np.ones(NB) if c[1] is None else c[1] for c in cases], np.float32)
-    if any(c[1] is not None for c in cases):
-        v.set_domain(torch.tensor(ms[idx]))
-    v.set_state(torch.tensor(np.array([c[0] for c in cases], np.float32)[idx]))
-    return v
-
-
-def oracle_state(orc, state, scale):
-    s = orc.new_state()
-    if scale is not None:
-        orc.set_domain(s, scale)
-    orc.set_state(s, state)
-    return s
+# MEASURED, CAPS, TOL: tests/tolerances.py (the link-state and forward-dynamics tests read them as well)
 
 
 def cent_dev(got, want):
@@ -100,21 +39,6 @@ def cent_dev(got, want):
              (slice(6, 9), max(np.abs(want[6:9]).max(), 0.01 * m)), (slice(9, 12), max(np.abs(want[9:12]).max(), 0.01 * m)),
              (slice(12, 13), max(abs(want[12]), 0.01 * m)), (slice(13, 14), abs(want[13])), (slice(14, 15), m)]
     return max(np.abs(got[sl] - want[sl]).max() / sc for sl, sc in parts)
-
-
-LINKS = {}
-
-
-def probe_links(model):
-    """head link, one toe link, the base link"""
-    if not LINKS:
-        names = model["link_names"]
-        hb = int(model["head_body"])
-        LINKS["head"] = [l for l in range(len(names)) if model["link_body"][l] == hb][0]
-        LINKS["toe"] = [l for l in range(len(names)) if "toe" in names[l]][0]
-        LINKS["base"] = 0
-        assert model["link_body"][0] == 0
-    return LINKS
 
 
 def deviations(oracle64, model, n, envs=None, batch=None):
@@ -345,22 +269,14 @@ def model_param(model, name):
     return trex_model.default_params()[name]
 
 
-def all_queries(v, link):
-    return [v.inverse_dynamics(), v.mass_matrix(), v.jacobian(link, (0.1, 0.2, 0.3)), v.centroidal().data]
-
-
 @pytest.mark.parametrize("n", [2, 3])
 def test_queries_are_read_only(n, oracle64, model):
     """warm start, contact sensor and an external wrench active; 10 steps with all four queries between every two steps are
     bitwise the 10 steps without: rows, state, contact wrench, episode steps. N = 2 steps in the pair form, N = 3 in the single."""
     gen = torch.Generator(device=DEV).manual_seed(5)
     w = 50 * torch.randn(n, NB, 6, generator=gen, device=DEV)
-    oo = model["obs_order"]
-    lo = torch.tensor(model["q_lower"][oo], dtype=torch.float32, device=DEV)
-    hi = torch.tensor(model["q_upper"][oo], dtype=torch.float32, device=DEV)
-    acts = [lo + (hi - lo) * torch.rand(n, J, generator=gen, device=DEV) for _ in range(10)]
-    case_states(oracle64, model, 1)
-    landed = torch.tensor(np.array([_CASES["base"][k][0] for k in (20, 22, 24)[:n]], np.float32))   # standing on the floor
+    acts = [random_actions(model, n, gen) for _ in range(10)]
+    landed = torch.tensor(np.array([base_cases(oracle64, model)[k][0] for k in (20, 22, 24)[:n]], np.float32))   # standing on the floor
     pair = []
     for probe in (False, True):
         v = make_vec(n, params={"warmstart": 0.85}, max_episode_steps=50)

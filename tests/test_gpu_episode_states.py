@@ -14,29 +14,12 @@ import pytest
 import torch
 
 import episode_cases as ec
-from conftest import ASSET_URDF
+from gpu_support import DEV, action_limits as limits, contact_counts, make_vec
 from parity_helpers import assert_step_close
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NB, J = 26, 25
 EPISODE = 1000
-
-
-def make_vec(n, **kw):
-    from trex_gym.vec_env import TrexVecEnv
-    return TrexVecEnv(n, urdf_path=ASSET_URDF, device=DEV, **kw)
-
-
-def contact_counts(v):
-    cnt = torch.zeros(v.num_envs, dtype=torch.int32, device=DEV)
-    v.batch.contact_stats(cnt, None)
-    return cnt
-
-
-def limits(model):
-    oo = model["obs_order"]
-    return (torch.tensor(model["q_lower"][oo], dtype=torch.float32, device=DEV), torch.tensor(model["q_upper"][oo], dtype=torch.float32, device=DEV))
 
 
 def up_axis(state):

@@ -10,10 +10,11 @@ import pytest
 import torch
 
 from conftest import ASSET_URDF
-from test_gpu_parity import GOLD, assert_step_close
+from gpu_support import DEV, contact_counts, make_vec, random_actions
+from parity_helpers import GOLD, assert_step_close
+from state_sets import landing_states
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NB, J = 26, 25
 
 
@@ -21,38 +22,6 @@ NB, J = 26, 25
 def capi():
     from trex_gym import _capi
     return _capi
-
-
-def make_vec(n, **kw):
-    from trex_gym.vec_env import TrexVecEnv
-    return TrexVecEnv(n, urdf_path=ASSET_URDF, device=DEV, **kw)
-
-
-def landing_states(oracle64, model, every=12):
-    q0 = model["q_start"][model["obs_order"]]
-    lo, hi = model["q_lower"][model["obs_order"]], model["q_upper"][model["obs_order"]]
-    rng = np.random.default_rng(5)
-    s = oracle64.new_state()
-    oracle64.reset(s)
-    states, acts = [], []
-    for t in range(300):
-        oracle64.step(s, np.clip(q0 + 0.15 * rng.normal(size=25), lo, hi))
-        if t % every == 0:
-            states.append(oracle64.get_state(s).astype(np.float32))
-            acts.append(np.clip(q0 + 0.15 * rng.normal(size=25), lo, hi).astype(np.float32))
-    return np.array(states), np.array(acts)
-
-
-def random_actions(model, n, gen):
-    lo = torch.tensor(model["q_lower"][model["obs_order"]], dtype=torch.float32, device=DEV)
-    hi = torch.tensor(model["q_upper"][model["obs_order"]], dtype=torch.float32, device=DEV)
-    return lo + (hi - lo) * torch.rand(n, J, generator=gen, device=DEV)
-
-
-def contact_counts(v):
-    cnt = torch.zeros(v.num_envs, dtype=torch.int32, device=DEV)
-    v.batch.contact_stats(cnt, None)
-    return cnt
 
 
 # ---------------------------------------------------------------- 1. the oracle, through gravity g + delta

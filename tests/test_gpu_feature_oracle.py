@@ -12,10 +12,11 @@ import pytest
 import torch
 
 import feature_cases as fc
+import gpu_support
+from gpu_support import DEV
 from parity_helpers import assert_step_close
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 GROUPS = ["warm_trex", "warm_factor_1.0", "warm_factor_0.3", "warm_slab", "warm_many_hulls", "warm_max_contacts_4", "warm_margin_0.5",
           "warm_primitives", "wrench_trex", "wrench_deep_chain", "wrench_bushy", "wrench_warm", "warm_fallen", "wrench_fallen"]
 
@@ -26,17 +27,14 @@ def groups(tmp_path_factory):
 
 
 def make_vec(b, n, warm, **kw):
-    from trex_gym.vec_env import TrexVecEnv
     params = dict(b.params)
     if warm:
         params["warmstart"] = warm
-    return TrexVecEnv(n, urdf_path=b.urdf, device=DEV, params=params or None, collision=b.collision, **kw)
+    return gpu_support.make_vec(n, b.urdf, params=params or None, collision=b.collision, **kw)
 
 
 def contact_counts(v):
-    cnt = torch.zeros(v.num_envs, dtype=torch.int32, device=DEV)
-    v.batch.contact_stats(cnt, None)
-    return cnt.cpu().numpy()
+    return gpu_support.contact_counts(v).cpu().numpy()
 
 
 def batch_size(n_cases, form):

@@ -29,12 +29,12 @@ import torch
 
 import dynamics_ref as R
 import forward_dynamics_ref as F
-import test_gpu_dynamics as T
 from conftest import ASSET_URDF
-from test_gpu_dynamics import case_states, loaded_vec, oracle_state
+from gpu_support import DEV, dynamics_queries, loaded_vec, make_vec, random_actions
+from state_sets import base_cases, case_states, oracle_state, probe_links, query_states
+from tolerances import DYNAMICS_TOL
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NB, J, D = 26, 25, 31
 G = 9.81
 
@@ -71,7 +71,7 @@ def deviations(oracle64, model, n, envs=None, batch=None):
     envs = range(N) if envs is None else envs
     rng = np.random.default_rng(11)
     inv = np.argsort(R.perm_to_oracle(model))
-    links = T.probe_links(model)
+    links = probe_links(model)
     ref = {}
     tau = np.zeros((N, J), np.float32)
     full = np.zeros((N, D), np.float32)
@@ -158,8 +158,7 @@ def test_against_references_n4096(oracle64, model):
 def test_the_tolerance_tells_the_velocity_terms(oracle64, model):
     """the answer with the velocity-product terms dropped, M^-1 (f - g), misses the final fd_accel tolerance on every airborne
     random state (CPU arithmetic; the tolerance is the thing under test)"""
-    case_states(oracle64, model, 1)
-    for s, ms in T._CASES["base"][-8:]:
+    for s, ms in base_cases(oracle64, model)[-8:]:
         want = F.forward_dynamics(model, s, None, ms, G)
         assert F.accel_dev(F.forward_dynamics(model, s, None, ms, G, velocity_terms=False), want) > TOL["fd_accel"]
 
@@ -189,7 +188,7 @@ def test_round_trips_with_inverse_dynamics(vec67, model):
     a_fd = v.forward_dynamics(frc_t).cpu().numpy().astype(np.float64)
     a_sm = v.solve_mass(frc_t - v.inverse_dynamics()).cpu().numpy().astype(np.float64)
     f_of_a = f_of_a.cpu().numpy().astype(np.float64)
-    tol = TOL["fd_force"] + T.TOL["id_roundtrip"]          # one pass through each query, both in the same metric
+    tol = TOL["fd_force"] + DYNAMICS_TOL["id_roundtrip"]          # one pass through each query, both in the same metric
     worst = [0.0, 0.0, 0.0]
     for e, (s, ms) in enumerate(cases):
         M, h = R.mass_matrix(model, s, ms), R.inverse_dynamics(model, s, None, ms, G)
@@ -247,11 +246,10 @@ def other_tree_deviations(name, directory):
     """{fd_force, fd_accel, minv} of the generated model `name` over six of its airborne query states"""
     import synthetic_models as sm
     from oracle import oracle as O
-    from test_gpu_synthetic_models import _query_states
     from trex_gym.vec_env import TrexVecEnv
     path, props, om = sm.compile_both(name, directory)
     o64 = O.Oracle(om, params=props["params"])
-    states = _query_states(om)[:6]
+    states = query_states(om)[:6]
     nj = om["nb"] - 1
     v = TrexVecEnv(len(states), urdf_path=path, device=DEV, params=props["params"])
     v.reset()
@@ -301,15 +299,11 @@ def test_queries_are_read_only(n, oracle64, model):
     existing queries return bitwise the same before and after the new calls"""
     gen = torch.Generator(device=DEV).manual_seed(5)
     w = 50 * torch.randn(n, NB, 6, generator=gen, device=DEV)
-    oo = model["obs_order"]
-    lo = torch.tensor(model["q_lower"][oo], dtype=torch.float32, device=DEV)
-    hi = torch.tensor(model["q_upper"][oo], dtype=torch.float32, device=DEV)
-    acts = [lo + (hi - lo) * torch.rand(n, J, generator=gen, device=DEV) for _ in range(10)]
-    case_states(oracle64, model, 1)
-    landed = torch.tensor(np.array([T._CASES["base"][k][0] for k in (20, 22, 24)[:n]], np.float32))
+    acts = [random_actions(model, n, gen) for _ in range(10)]
+    landed = torch.tensor(np.array([base_cases(oracle64, model)[k][0] for k in (20, 22, 24)[:n]], np.float32))
     pair = []
     for probe in (False, True):
-        v = T.make_vec(n, params={"warmstart": 0.85}, max_episode_steps=50)
+        v = make_vec(n, params={"warmstart": 0.85}, max_episode_steps=50)
         v.enable_contact_sensor(True)
         v.reset_tensor()
         v.set_state(landed)
@@ -319,10 +313,10 @@ def test_queries_are_read_only(n, oracle64, model):
             v.step_tensor(a)
             rows.append(v.rows.clone())
             if probe:
-                before = T.all_queries(v, 5)
+                before = dynamics_queries(v, 5)
                 out = new_queries(v)
                 assert all(torch.isfinite(o).all() for o in out)
-                for x, y in zip(before, T.all_queries(v, 5)):
+                for x, y in zip(before, dynamics_queries(v, 5)):
                     assert torch.equal(x, y)
         steps = torch.zeros(n, dtype=torch.int32, device=DEV)
         v.batch.get_episode_steps(steps)
@@ -336,7 +330,7 @@ def test_queries_are_read_only(n, oracle64, model):
 def test_refusals(model):
     from trex_gym import _capi as capi
     n = 5
-    v, ref = T.make_vec(n), T.make_vec(n)
+    v, ref = make_vec(n), make_vec(n)
     v.reset_tensor()
     ref.reset_tensor()
     b, lib = v.batch, capi.lib
@@ -467,7 +461,7 @@ def test_single_env_surface(model):
     a0, at = env.forward_dynamics(), env.forward_dynamics(tau=np.zeros(J))
     af = env.forward_dynamics(force=np.zeros(D))
     x1, xk, mi = env.solve_mass(np.ones(D)), env.solve_mass(np.ones((3, D))), env.inverse_mass_matrix()
-    lam = env.operational_space_inertia(T.probe_links(model)["head"])
+    lam = env.operational_space_inertia(probe_links(model)["head"])
     for arr, shape in ((a0, (D,)), (at, (D,)), (af, (D,)), (x1, (D,)), (xk, (3, D)), (mi, (D, D)), (lam, (6, 6))):
         assert isinstance(arr, np.ndarray) and arr.dtype == np.float32 and arr.shape == shape
     assert np.array_equal(a0, at) and np.array_equal(a0, af) and np.array_equal(xk[1], x1)

@@ -7,9 +7,9 @@ import pytest
 import torch
 
 from conftest import ASSET_URDF
+from gpu_support import DEV
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 PENDULUM = """<robot name='p'>
   <link name='base'><inertial><origin xyz='0 0 0' rpy='0 0 0'/><mass value='1000'/><inertia ixx='500' iyy='500' izz='500'/></inertial></link>

@@ -9,18 +9,20 @@ profiles/r20_inverse_kinematics.txt records them), never above the caps: 1e-4 ra
 residuals of `info` against the f64 evaluation of q_out, 1 % for the final error norm of the unreachable cases. The convergence
 bound is fixed: 1e-4 m / rad, ten times what the reference leaves on the same cases."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import dynamics_ref as R
+import gpu_support
 import ik_cases as IC
 import ik_ref as IK
 import link_state_ref as L
+from gpu_support import DEV, case_env as make_env, guarded, guards_intact, random_steps, replay_equals_eager
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 N = 67
 FRAMES = {"world": 0, "base": 2}
 FORMS = ["pos4", "head_ori", "three_ori", "k1", "k8", "same_body", "one_leg", "one_leg_ori"]
@@ -35,43 +37,24 @@ CAPS = dict(one_iter=1e-4, info=1e-5, unreachable=1e-2, deep_chain=1e-4, bushy=1
 TOL = {k: min(4 * v, CAPS[k]) for k, v in MEASURED.items()}
 
 
-def form_of(model, name):
-    return [f for f in IC.forms(model) if f.name == name][0]
-
-
-def make_env(model, cases, q=None, path=None, params=None):
-    """a TrexVecEnv holding cases[e].state (its joint angles: q_start), or with the joint angles q [n, J] instead"""
-    from trex_gym.vec_env import TrexVecEnv
-    kw = {} if path is None else dict(urdf_path=path, params=params)
-    v = TrexVecEnv(len(cases), device=DEV, **kw)
-    v.reset()
-    J = model["nb"] - 1
-    st = np.array([c.state for c in cases])
-    if q is not None:
-        st[:, 13:13 + J] = q
-    v.set_state(torch.tensor(st.astype(np.float32)))
-    return v
-
-
 def bits(joints, J):
     return (1 << J) - 1 if joints is None else sum(1 << int(k) for k in joints)
 
 
 def run_ik(v, slot, form, targets, frame="world", q_init=None, joints=None, info=True, guard=64, alias=False, **prm):
-    """trex_batch_inverse_kinematics through _capi.Batch into NaN-filled buffers with `guard` floats behind each output: (q [n, J],
+    """trex_batch_inverse_kinematics through _capi.Batch into NaN-filled buffers with `guard` floats around each output: (q [n, J],
     info [n, 4] or None) as numpy; the guards must still be NaN. alias: q_out IS q_init."""
     n, J, K = v.num_envs, v.J, len(form.links)
     t = torch.tensor(np.asarray(targets, np.float32).reshape(n, K, 7), device=DEV)
-    qb = torch.full((n * J + guard,), float("nan"), device=DEV)
-    ib = torch.full((n * 4 + guard,), float("nan"), device=DEV)
-    qo, io = qb[:n * J].view(n, J), ib[:n * 4].view(n, 4)
+    (qb, qo), (ib, io) = guarded((n, J), guard, float("nan")), guarded((n, 4), guard, float("nan"))
     qi = None if q_init is None else torch.tensor(np.asarray(q_init, np.float32).reshape(n, J), device=DEV)
     if alias:
         qo.copy_(qi)
         qi = qo
     v.batch.inverse_kinematics(slot, form.modes, t, qo, FRAMES[frame], qi, bits(joints, J), io if info else None, **prm)
     torch.cuda.synchronize()
-    assert torch.isnan(qb[n * J:]).all() and torch.isnan(ib[n * 4:] if info else ib).all(), "the call wrote behind an output"
+    assert guards_intact(qb, (n, J), guard, float("nan")), "the call wrote outside q_out"
+    assert guards_intact(ib, (n, 4), guard, float("nan")) if info else torch.isnan(ib).all(), "the call wrote outside info"
     return qo.cpu().numpy(), (io.cpu().numpy() if info else None)
 
 
@@ -153,7 +136,7 @@ def deviations(model):
     """the figures TOL is set from (module docstring)"""
     d = dict(one_iter=0.0, info=0.0)
     for name in FORMS:
-        form = form_of(model, name)
+        form = IC.form_of(model, name)
         d["one_iter"] = max(d["one_iter"], one_iteration_deviation(model, form))
         for frame in FRAMES:
             _, _, info, res = converged(model, form, frame=frame)
@@ -169,7 +152,7 @@ def deviations(model):
 def test_one_iteration_against_reference(name, model):
     """q_out element by element after one iteration, damping 0.05 (a well-conditioned solve), N = 67, every env its own draw."""
     assert TOL["one_iter"] <= CAPS["one_iter"]
-    w = one_iteration_deviation(model, form_of(model, name))
+    w = one_iteration_deviation(model, IC.form_of(model, name))
     print("%s: one iteration, largest |q - q_ref| %.3g rad" % (name, w))
     assert w <= TOL["one_iter"], (name, w)
 
@@ -180,7 +163,7 @@ def test_one_iteration_against_reference(name, model):
 def test_convergence_judged_by_link_state_ref(name, frame, model):
     """30 iterations at the defaults: every residual of q_out, evaluated in f64 by link_state_ref and not by the kernel, is at or
     below 1e-4 m / rad - no case excluded - and info's residuals agree with that evaluation."""
-    form = form_of(model, name)
+    form = IC.form_of(model, name)
     cases, q, info, res = converged(model, form, frame=frame)
     res = np.array(res)
     print("%s %s: largest residual %.3g m, %.3g rad; info off by %.3g" % (name, frame, res[:, 0].max(), res[:, 1].max(),
@@ -211,7 +194,7 @@ def test_unreachable_targets(model):
 # 4 ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", FORMS)
 def test_limits_mask_and_aliasing(name, model):
-    form = form_of(model, name)
+    form = IC.form_of(model, name)
     n, J = 9, model["nb"] - 1
     cases = IC.reachable(model, form, n)
     v = make_env(model, cases)
@@ -236,7 +219,7 @@ def test_limits_mask_and_aliasing(name, model):
 def test_early_stop(model):
     tol = (1e-3, 1e-3)
     for name in FORMS:
-        form = form_of(model, name)
+        form = IC.form_of(model, name)
         cases = IC.reachable(model, form, 12)
         v = make_env(model, cases)
         v.batch.set_link_probes(0, form.links, np.array(form.points))
@@ -271,7 +254,7 @@ def test_early_stop(model):
 def test_tiling_edges(model):
     """N on both sides of the four envs of a workgroup; NaN guards behind both outputs (run_ik); env i of the N = 5 batch bitwise
     the same inputs at another place of the N = 67 batch; two calls bitwise alike"""
-    form = form_of(model, "head_ori")
+    form = IC.form_of(model, "head_ori")
     all67 = IC.reachable(model, form, 67)
     out = {}
     for n in (1, 3, 4, 5, 67):
@@ -289,13 +272,6 @@ def test_tiling_edges(model):
 
 
 # 7 ------------------------------------------------------------------------------------------------------------------------
-def _random_steps(env, steps, seed):
-    gen = torch.Generator().manual_seed(seed)
-    lo, hi = torch.tensor(env.model.lower, dtype=torch.float32), torch.tensor(env.model.upper, dtype=torch.float32)
-    for _ in range(steps):
-        env.step_tensor((lo + (hi - lo) * torch.rand(env.num_envs, env.J, generator=gen)).to(env.device))
-
-
 def test_read_only(model):
     """state, observations, episode steps and the next steps' rows are bitwise those of a batch that never made the call (the
     warm-start record is private: the next steps agree only if it was left alone); the mass scale does not enter"""
@@ -304,9 +280,9 @@ def test_read_only(model):
     envs = [TrexVecEnv(n, device=DEV, params={"warmstart": 0.85}, max_episode_steps=100) for _ in range(2)]
     for e in envs:
         e.reset_tensor()
-        _random_steps(e, 5, seed=1)
+        random_steps(e, 5, seed=1)
     before, obs = envs[0].get_state().clone(), envs[0].obs.clone()
-    form = form_of(model, "three_ori")
+    form = IC.form_of(model, "three_ori")
     h = envs[0].link_probes(form.links, form.points)
     want = envs[0].link_state(h, velocity=False)
     pos = want.position + 0.05
@@ -324,7 +300,7 @@ def test_read_only(model):
     envs[1].set_domain(mass_scale=torch.ones(n, model["nb"]))
     rows = []
     for e in envs:
-        _random_steps(e, 2, seed=2)
+        random_steps(e, 2, seed=2)
         rows.append(e.rows.cpu().numpy())
     assert rows[0].tobytes() == rows[1].tobytes()
     for e in envs:
@@ -340,7 +316,7 @@ def test_refusals(model):
     env = TrexVecEnv(n, device=DEV)
     env.reset_tensor()
     b, J = env.batch, env.J
-    form = form_of(model, "head_ori")
+    form = IC.form_of(model, "head_ori")
     K = len(form.links)
     b.set_link_probes(0, form.links, np.array(form.points))
     b.set_link_probes(1, [1] * 9, np.zeros((9, 3)))                     # K = 9
@@ -351,11 +327,11 @@ def test_refusals(model):
     info = torch.full((n, 4), float("nan"), device=DEV)
     ok = dict(set=0, modes=form.modes, target=t, q_out=q, frame=0, info=info)
 
-    def refused(**kw):
+    def attempt(**kw):
         a = dict(ok, **kw)
-        with pytest.raises(_capi.TrexError) as ei:
-            b.inverse_kinematics(a.pop("set"), a.pop("modes"), a.pop("target"), a.pop("q_out"), **a)
-        assert ei.value.code == E, kw
+        b.inverse_kinematics(a.pop("set"), a.pop("modes"), a.pop("target"), a.pop("q_out"), **a)
+
+    refused = functools.partial(gpu_support.refused, E, attempt)
 
     refused(set=3)                                                      # never set
     refused(set=8)
@@ -422,7 +398,7 @@ def test_refusals(model):
 # 9 ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("where", ["target", "q_init"])
 def test_non_finite_inputs_stay_in_their_env(where, model):
-    form = form_of(model, "three_ori")
+    form = IC.form_of(model, "three_ori")
     n = 11
     cases = IC.reachable(model, form, n)
     v = make_env(model, cases)
@@ -447,7 +423,7 @@ def test_non_finite_inputs_stay_in_their_env(where, model):
 # 10 -----------------------------------------------------------------------------------------------------------------------
 def test_stream_capture(model):
     """after a warm-up call a graph of the single launch - one stream, no branches - replays twice to the eager result, bitwise"""
-    form = form_of(model, "k8")
+    form = IC.form_of(model, "k8")
     n = 8
     cases = IC.reachable(model, form, 2 * n)
     v = make_env(model, cases[:n])
@@ -455,28 +431,13 @@ def test_stream_capture(model):
     J, K = v.J, len(form.links)
     t = torch.tensor(targets_of(cases[:n], "world").astype(np.float32), device=DEV)
     q, info = torch.empty(n, J, device=DEV), torch.empty(n, 4, device=DEV)
-    call = lambda qo, io: v.batch.inverse_kinematics(0, form.modes, t, qo, 0, None, None, io, iterations=30)
-    call(q, info)                                                   # the first call: learns the buffers
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-        with torch.cuda.graph(graph, stream=side):
-            call(q, info)                                           # the second: one launch
-    first = q.clone()
-    t.copy_(torch.tensor(targets_of(cases[n:], "world").astype(np.float32)))
-    v.set_state(torch.tensor(np.array([c.state for c in cases[n:]], np.float32)))
-    eq, ei = torch.empty_like(q), torch.empty_like(info)
-    call(eq, ei)
-    torch.cuda.synchronize()
-    for _ in range(2):
-        q.zero_()
-        info.zero_()
-        graph.replay()
-        torch.cuda.synchronize()
-        assert q.cpu().numpy().tobytes() == eq.cpu().numpy().tobytes() and info.cpu().numpy().tobytes() == ei.cpu().numpy().tobytes()
-    assert not torch.equal(q, first)
-    del graph
+    call = lambda o: v.batch.inverse_kinematics(0, form.modes, t, o[0], 0, None, None, o[1], iterations=30)
+
+    def change():
+        t.copy_(torch.tensor(targets_of(cases[n:], "world").astype(np.float32)))
+        v.set_state(torch.tensor(np.array([c.state for c in cases[n:]], np.float32)))
+
+    replay_equals_eager(call, [q, info], change, replays=2, changed=[0])
     v.close()
 
 
@@ -491,7 +452,7 @@ def test_generated_models(name, tmp_path_factory):
     make = lambda cs, q=None: make_env(om, cs, q, path, props["params"])
     worst, qualified = 0.0, 0
     for fname in ("pos4", "head_ori", "same_body", "one_leg"):
-        form = form_of(om, fname)
+        form = IC.form_of(om, fname)
         worst = max(worst, one_iteration_deviation(om, form, 3, name, make))
         cases, q, info, res = converged(om, form, 3, "base", 30, name, make)
         refs = [IC.reference(om, form, c, "base", name, iterations=30) for c in cases]
@@ -509,7 +470,7 @@ def test_generated_models(name, tmp_path_factory):
 def test_facades(model):
     from trex_gym.trex_env import TrexBulletEnv
     from trex_gym.vec_env import TrexVecEnv
-    form = form_of(model, "head_ori")
+    form = IC.form_of(model, "head_ori")
     n, J = 5, model["nb"] - 1
     cases = IC.reachable(model, form, n)
     v = make_env(model, cases)

@@ -33,19 +33,14 @@ import torch
 
 import joint_limit_states as L
 from conftest import ASSET_URDF
-from test_gpu_parity import assert_step_close
+from gpu_support import DEV, make_vec
+from parity_helpers import assert_step_close
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NB, J = 26, 25
 CASES = L.one_stop_cases()
 # section 1 only: 4 x the larger of (the kernel's measured worst, the f32 oracle's worst) over the 100 states - see MEASURED
 TIGHT_Q, TIGHT_QD = 4 * 7.34e-6, 4 * 4.11e-4
-
-
-def make_vec(n, **kw):
-    from trex_gym.vec_env import TrexVecEnv
-    return TrexVecEnv(n, urdf_path=ASSET_URDF, device=DEV, **kw)
 
 
 def gpu_step(states, acts, **kw):

@@ -3,7 +3,7 @@ restatement tests/link_state_ref.py - itself pinned by tests/test_link_state_ref
 (link_transforms, jacobian); the tiling's edges, read-only, refusals, stream capture, containment, the IMU of trex_gym.sensors
 and the single-env facade.
 
-States: those of test_gpu_dynamics.case_states - landing and airborne, two of them mass-scaled (the scale does not enter: this is
+States: those of state_sets.case_states - landing and airborne, two of them mass-scaled (the scale does not enter: this is
 kinematics), every env with a state of its own.
 
 Tolerances (TOL): 4 x the largest deviation measured on these very states at N = 67 on an MI355X (scripts/link_state_bench.py
@@ -12,44 +12,29 @@ Scales: position over max(1 m, the env's largest |p| entry); quaternion absolute
 largest |v| entry); acceleration over max(g, the env's largest |a| entry) - the entries of the reference's [K, 6] block of that
 env in the axes compared."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import dynamics_ref as R
+import gpu_support
 import link_state_ref as L
 from conftest import ASSET_URDF
-from test_gpu_dynamics import TOL as DYN_TOL, case_states, loaded_vec
+from gpu_support import DEV, guarded, guards_intact, loaded_vec, random_steps, replay_equals_eager
+from state_sets import built_models, case_states, pick_links
+from tolerances import DYNAMICS_TOL as DYN_TOL, LINK_CAPS as CAPS, LINK_MEASURED as MEASURED, LINK_TOL as TOL  # noqa: F401  (MEASURED: the docstrings' pointer)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NB, J, D = 26, 25, 31
 G = 9.81
 AXES = ("world", "link", "base")
 
-# Largest deviations measured at N = 67 on an MI355X (profiles/r17_link_state.txt): pose, velocity, the bias acceleration (accel
-# NULL) and the acceleration at a random accel (dynamics_ref.random_tau: joints within 10 rad/s^2), each over the three axes and,
-# for the accelerations, with and without `proper`. Tolerance = 4 x measured, never above the cap.
-MEASURED = dict(pose=2.06e-7, velocity=4.33e-7, bias=3.43e-7, accel=4.42e-7)
-CAPS = dict(pose=1e-5, velocity=1e-4, bias=1e-4, accel=1e-4)
-TOL = {k: min(4 * v, CAPS[k]) for k, v in MEASURED.items()}
-# ... and on the generated models at N = 3 (test_synthetic_models)
+# MEASURED, CAPS, TOL at N = 67: tests/tolerances.py (the observation and proximity tests read them as well). The largest
+# deviations on the generated models at N = 3 (test_synthetic_models), same profile:
 MEASURED_SYN = dict(deep_chain=dict(pose=2.13e-7, velocity=2.83e-7, acc=3.17e-7), big_body=dict(pose=7.9e-8, velocity=1.11e-7, acc=1.43e-7),
                     bushy=dict(pose=1.58e-7, velocity=1.32e-7, acc=1.99e-7))
-
-
-def pick_links(model):
-    """head, a toe, the base, the deepest link and the last link merged across a fixed joint with a turned link_tf"""
-    names, lb = list(model["link_names"]), np.asarray(model["link_body"], int)
-    tf = np.asarray(model["link_tf"], np.float64).reshape(-1, 12)
-    out = [0, [l for l in range(len(names)) if lb[l] == int(model["head_body"])][0],
-           [l for l in range(len(names)) if lb[l] == int(np.argmax(model["depth"]))][0]]
-    out += [l for l in range(len(names)) if "toe" in names[l]][:1]
-    turned = [l for l in range(len(names)) if np.abs(tf[l][:9] - np.eye(3).reshape(-1)).max() > 1e-3]
-    moved = [l for l in range(len(names)) if np.abs(tf[l][9:]).max() > 1e-3]
-    out += (turned or moved)[-1:]
-    return out
 
 
 def parity_probes(model):
@@ -84,29 +69,15 @@ def env_dev(got, ref, what):
 
 
 def run_query(v, slot, K, axes, proper, accel, pose=True, vel=True, acc=True, guard=64):
-    """trex_batch_link_state through _capi.Batch into NaN-filled buffers with `guard` floats behind each output: the three
+    """trex_batch_link_state through _capi.Batch into NaN-filled buffers with `guard` floats around each output: the three
     outputs as numpy (None where not asked for); the guards must still be NaN"""
-    n = v.num_envs
-    bufs, outs = [], []
-    for want, width in ((pose, 7), (vel, 6), (acc, 6)):
-        if not want:
-            bufs.append(None)
-            outs.append(None)
-            continue
-        b = torch.full((n * K * width + guard,), float("nan"), device=DEV)
-        bufs.append(b)
-        outs.append(b[:n * K * width].view(n, K, width))
+    n, nan = v.num_envs, float("nan")
+    bufs = [guarded((n, K, width), guard, nan) if want else (None, None) for want, width in ((pose, 7), (vel, 6), (acc, 6))]
     a = None if accel is None else torch.as_tensor(accel, dtype=torch.float32).to(DEV).contiguous()
-    v.batch.link_state(slot, AXES.index(axes), proper, a, *outs, probes=K)
+    v.batch.link_state(slot, AXES.index(axes), proper, a, *[o for _, o in bufs], probes=K)
     torch.cuda.synchronize()
-    res = []
-    for b, o, width in zip(bufs, outs, (7, 6, 6)):
-        if b is None:
-            res.append(None)
-            continue
-        assert torch.isnan(b[n * K * width:]).all(), "the call wrote behind an output"
-        res.append(o.cpu().numpy())
-    return res
+    assert all(guards_intact(b, o.shape, guard, nan) for b, o in bufs if b is not None), "the call wrote outside an output"
+    return [None if o is None else o.cpu().numpy() for _, o in bufs]
 
 
 def check_against_reference(v, model, cases, links, pts, slot, combos, accel, worst=None):
@@ -232,12 +203,7 @@ def test_consistent_with_link_transforms_and_jacobian(oracle64, model):
 # 4 ------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
-    import synthetic_models as sm
-    out = {}
-    for name in MEASURED_SYN:
-        path, props, om = sm.compile_both(name, tmp_path_factory.mktemp(name))
-        out[name] = dict(path=path, props=props, om=om)
-    return out
+    return built_models(MEASURED_SYN, tmp_path_factory)
 
 
 def synthetic_deviation(m, n=3):
@@ -272,13 +238,6 @@ def test_synthetic_models(name, built):
 
 
 # 5 ------------------------------------------------------------------------------------------------------------------------
-def _random_steps(env, steps, seed):
-    gen = torch.Generator().manual_seed(seed)
-    lo, hi = torch.tensor(env.model.lower, dtype=torch.float32), torch.tensor(env.model.upper, dtype=torch.float32)
-    for _ in range(steps):
-        env.step_tensor((lo + (hi - lo) * torch.rand(env.num_envs, env.J, generator=gen)).to(env.device))
-
-
 def test_read_only(model):
     """state, warm-start record, contact sensor, episode counts and the next steps' rows are bitwise those of a batch that never
     made the call (the warm-start record is private: the next steps agree only if it was left alone)"""
@@ -288,7 +247,7 @@ def test_read_only(model):
     for e in envs:
         e.enable_contact_sensor(True)
         e.reset_tensor()
-        _random_steps(e, 5, seed=1)
+        random_steps(e, 5, seed=1)
     before = envs[0].get_state().clone()
     wrench = envs[0].contact_wrench().clone()
     links, pts = spread_probes(model, 300)
@@ -303,7 +262,7 @@ def test_read_only(model):
     assert (envs[0].episode_steps == envs[1].episode_steps).all()
     rows = []
     for e in envs:
-        _random_steps(e, 2, seed=2)
+        random_steps(e, 2, seed=2)
         rows.append(e.rows.cpu().numpy())
     assert rows[0].tobytes() == rows[1].tobytes()
     assert envs[0].contact_wrench().cpu().numpy().tobytes() == envs[1].contact_wrench().cpu().numpy().tobytes()
@@ -322,12 +281,7 @@ def test_refusals(model):
     env.reset_tensor()
     b, nl = env.batch, len(model["link_names"])
     E = _capi.E_INVALID
-
-    def refused(fn, *a, **kw):
-        with pytest.raises(_capi.TrexError) as ei:
-            fn(*a, **kw)
-        assert ei.value.code == E, (a, kw)
-
+    refused = functools.partial(gpu_support.refused, E)
     b.set_link_probes(0, [1, 2, 3], np.zeros((3, 3)))
     K = 3
     pose, vel, acc = (torch.full((n, K, w), 7.0, device=DEV) for w in (7, 6, 6))
@@ -420,26 +374,7 @@ def test_stream_capture(oracle64, model):
     acc = torch.tensor(random_accels(model, cases[:n], seed=7), device=DEV)
     outs = [torch.empty(n, K, w, device=DEV) for w in (7, 6, 6)]
     call = lambda o: v.batch.link_state(h.slot, 2, True, acc, *o, probes=K)
-    call(outs)                                                      # the first call: learns the buffers
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-        with torch.cuda.graph(graph, stream=side):
-            call(outs)                                              # the second: one launch, one linear chain
-    first = [o.clone() for o in outs]
-    v.set_state(torch.tensor(np.array([c[0] for c in cases[n:]], np.float32)))
-    eager = [torch.empty_like(o) for o in outs]
-    call(eager)
-    torch.cuda.synchronize()
-    for o in outs:
-        o.zero_()
-    graph.replay()
-    torch.cuda.synchronize()
-    for o, want, old in zip(outs, eager, first):
-        assert o.cpu().numpy().tobytes() == want.cpu().numpy().tobytes()
-        assert not torch.equal(o, old)
-    del graph
+    replay_equals_eager(call, outs, lambda: v.set_state(torch.tensor(np.array([c[0] for c in cases[n:]], np.float32))))
     v.close()
 
 

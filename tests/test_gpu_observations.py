@@ -3,9 +3,9 @@ restatement tests/observation_ref.py - itself pinned by tests/test_observation_r
 (link_state, contact_wrench); the 8-env workgroups' edges, pass-through and read-only, the copied channels, what is written and
 what is not, refusals, stream capture, and the trainer on the extended row.
 
-States: those of test_gpu_dynamics.case_states - landing and airborne, every env with a state of its own - and the reset state.
+States: those of state_sets.case_states - landing and airborne, every env with a state of its own - and the reset state.
 
-Tolerances: those of tests/test_gpu_link_state.py, applied as there - TOL['pose'] for the gravity vector, positions and heights,
+Tolerances: those of tests/test_gpu_link_state.py (tolerances.LINK_TOL), applied as there - TOL['pose'] for the gravity vector, positions and heights,
 over max(1, the channel's largest |entry|); TOL['velocity'] for velocities, likewise - times the channel's |scale|. The copied
 channels (contact force, previous action, external columns) and the pass-through columns are compared bitwise."""
 import ctypes as C
@@ -16,11 +16,11 @@ import torch
 
 import observation_ref as OR
 from conftest import ASSET_URDF
-from test_gpu_dynamics import case_states, loaded_vec, make_vec
-from test_gpu_link_state import TOL
+from gpu_support import DEV, loaded_vec, make_vec
+from state_sets import case_states
+from tolerances import LINK_TOL as TOL
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NB, J = 26, 25
 Z = (0.0, 0.0, 0.0)
 POSE_KINDS = (OR.GRAVITY, OR.BASE_HEIGHT, OR.POINT_POS, OR.POINT_HEIGHT)

@@ -26,24 +26,17 @@ import pytest
 import torch
 
 from conftest import ASSET_URDF
+from gpu_support import DEV, action_limits, make_vec
+from parity_helpers import GOLD, assert_step_close
+from state_sets import landing_states
 
 pytestmark = pytest.mark.gpu
-GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "oracle_rollout.npz"))
-DEV = "cuda:0"
 
 
 @pytest.fixture(scope="module")
 def capi():
     from trex_gym import _capi
     return _capi
-
-
-def make_vec(n, **kw):
-    from trex_gym.vec_env import TrexVecEnv
-    return TrexVecEnv(n, urdf_path=ASSET_URDF, device=DEV, **kw)
-
-
-from parity_helpers import assert_step_close  # noqa: E402,F401  (moved there; other test files import it from here)
 
 
 def test_native_library_is_the_one_loaded(capi):
@@ -102,23 +95,11 @@ def test_one_step_parity_from_golden_states(name, oracle64):
 
 def test_one_step_parity_in_contact_and_at_rest(oracle64, model):
     """States sampled along a 300-step landing (contacts, friction, joint stops under load)."""
-    q0 = model["q_start"][model["obs_order"]]
-    lo, hi = model["q_lower"][model["obs_order"]], model["q_upper"][model["obs_order"]]
-    rng = np.random.default_rng(5)
-    s = oracle64.new_state()
-    oracle64.reset(s)
-    states, acts = [], []
-    for t in range(300):
-        a = np.clip(q0 + 0.15 * rng.normal(size=25), lo, hi)
-        oracle64.step(s, a)
-        if t % 6 == 0:
-            states.append(oracle64.get_state(s).astype(np.float32))
-            acts.append(np.clip(q0 + 0.15 * rng.normal(size=25), lo, hi).astype(np.float32))
-    states, acts = np.array(states), np.array(acts)
+    states, acts = landing_states(oracle64, model, every=6)
     v = make_vec(len(states))
     v.reset()
     v.set_state(torch.tensor(states))
-    obs, rew, _, _ = v.step(acts)
+    obs, rew, _, _ = v.step(acts.copy())                          # (the shared arrays are read-only; step() takes a view)
     cnt = torch.zeros(len(states), dtype=torch.int32, device=DEV)
     v.batch.contact_stats(cnt, None)
     n_contact_states = 0
@@ -237,8 +218,7 @@ N_FULL = 4096
 @pytest.fixture(scope="module")
 def full(model):
     v = make_vec(N_FULL)
-    lo = torch.tensor(model["q_lower"][model["obs_order"]], dtype=torch.float32, device=DEV)
-    hi = torch.tensor(model["q_upper"][model["obs_order"]], dtype=torch.float32, device=DEV)
+    lo, hi = action_limits(model)
     return v, lo, hi
 
 
@@ -307,8 +287,7 @@ def test_rank_lists_cover_every_env_at_ragged_sizes(n, model):
     flipped by the last wave to end; blocks of 1024 ranks, the last one partial here): over many launches, through
     landing, EVERY env must be stepped exactly once per launch - the trajectories equal those of launches that keep
     env k in workgroup k (trex_batch_set_wave_balance(0)), bitwise."""
-    lo = torch.tensor(model["q_lower"][model["obs_order"]], dtype=torch.float32, device=DEV)
-    hi = torch.tensor(model["q_upper"][model["obs_order"]], dtype=torch.float32, device=DEV)
+    lo, hi = action_limits(model)
     g = torch.Generator(device=DEV).manual_seed(5)
     acts = [(lo + (hi - lo) * torch.rand(n, 25, device=DEV, generator=g)).contiguous() for _ in range(70)]
 
@@ -520,8 +499,7 @@ def test_step_many_is_bitwise_the_same_steps_one_by_one(model):
     ending episodes inside the launch at different steps (staggered ages), per-env domain randomisation, a non-finite
     env contained in the middle, and the wave balance on (2 500 envs, ragged last block)."""
     n, S = 2500, 12
-    lo = torch.tensor(model["q_lower"][model["obs_order"]], dtype=torch.float32, device=DEV)
-    hi = torch.tensor(model["q_upper"][model["obs_order"]], dtype=torch.float32, device=DEV)
+    lo, hi = action_limits(model)
     g = torch.Generator(device=DEV).manual_seed(21)
     acts = (lo + (hi - lo) * torch.rand(S, n, 25, device=DEV, generator=g)).contiguous()
     pre = [(lo + (hi - lo) * torch.rand(n, 25, device=DEV, generator=g)).contiguous() for _ in range(40)]
@@ -666,8 +644,7 @@ def test_config4_size_on_one_gpu(oracle64, oracle32, model):
     on 64 of those states (sampled across the contact-count range)."""
     n = 32768
     v = make_vec(n)
-    lo = torch.tensor(model["q_lower"][model["obs_order"]], dtype=torch.float32, device=DEV)
-    hi = torch.tensor(model["q_upper"][model["obs_order"]], dtype=torch.float32, device=DEV)
+    lo, hi = action_limits(model)
     g = torch.Generator(device=DEV).manual_seed(11)
     v.reset_tensor()
     for t in range(60):      # through touchdown: contact counts from 0 up to the budget

@@ -9,11 +9,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import DEV
 from oracle import ppo_oracle as P
 from trainer_cases import _grads_to_flat, _theta_to_params
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 @pytest.mark.parametrize("n", [4096, 77])

@@ -3,7 +3,7 @@ f64 restatement tests/proximity_ref.py - itself pinned by tests/test_proximity_r
 geometry cases of tests/proximity_cases.py and generated models; the tiling's edges, a cross-check with link_state, read-only,
 refusals, stream capture, containment and the Python surface.
 
-States: those of test_gpu_dynamics.case_states, every env with a state of its own. Tables: f32-exact, so the batch and the
+States: those of state_sets.case_states, every env with a state of its own. Tables: f32-exact, so the batch and the
 reference hold the same capsules.
 
 What is compared, per env and pair (check_env):
@@ -18,19 +18,22 @@ What is compared, per env and pair (check_env):
   direction  n against the reference's where its axis distance exceeds 0.01 m and the winner is the reference's, to
              4 x TOL x scale / axis distance: the direction error is the point error over the lever."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import dynamics_ref as R
+import gpu_support
 import proximity_cases as PC
 import proximity_ref as PR
 from conftest import ASSET_URDF
-from test_gpu_dynamics import _CASES, case_states, loaded_vec, make_vec
+from gpu_support import DEV, guarded, guards_intact, loaded_vec, make_vec, random_actions, replay_equals_eager
+from state_sets import base_cases, built_models, case_states, pick_links
+from tolerances import LINK_TOL
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NB, J = 26, 25
 GAP = 1e-4
 CAP = 1e-5
@@ -46,26 +49,16 @@ WIDTH = dict(distance=1, point_a=3, point_b=3, normal=3, capsule=2)
 
 
 def run_query(batch, P, only=OUTS, guard=64):
-    """trex_batch_proximity through _capi.Batch into NaN-filled (capsule: -7-filled) buffers with `guard` elements behind each
+    """trex_batch_proximity through _capi.Batch into NaN-filled (capsule: -7-filled) buffers with `guard` elements around each
     output: {name: numpy} of the outputs asked for; the guards must be intact"""
     n = batch.num_envs
-    bufs, views = {}, {}
-    for name in OUTS:
-        if name not in only:
-            views[name] = None
-            continue
-        k = n * P * WIDTH[name]
-        bufs[name] = (torch.full((k + guard,), -7, dtype=torch.int32, device=DEV) if name == "capsule"
-                      else torch.full((k + guard,), float("nan"), device=DEV))
-        views[name] = bufs[name][:k].view((n, P) if WIDTH[name] == 1 else (n, P, WIDTH[name]))
-    batch.proximity(*[views[name] for name in OUTS], pairs=P)
+    fill = {name: (-7, torch.int32) if name == "capsule" else (float("nan"), torch.float32) for name in OUTS}
+    bufs = {name: guarded((n, P) if WIDTH[name] == 1 else (n, P, WIDTH[name]), guard, *fill[name]) for name in OUTS if name in only}
+    batch.proximity(*[bufs[name][1] if name in bufs else None for name in OUTS], pairs=P)
     torch.cuda.synchronize()
-    out = {}
-    for name, b in bufs.items():
-        tail = b[n * P * WIDTH[name]:]
-        assert (tail == -7).all() if name == "capsule" else torch.isnan(tail).all(), "the call wrote behind " + name
-        out[name] = views[name].cpu().numpy()
-    return out
+    for name, (whole, view) in bufs.items():
+        assert guards_intact(whole, view.shape, guard, fill[name][0]), "the call wrote outside " + name
+    return {name: view.cpu().numpy() for name, (_, view) in bufs.items()}
 
 
 def point_to_segment(x, p0, p1):
@@ -276,7 +269,6 @@ def test_tests_of_one_pair(ca, cb, oracle64, model):
 def test_consistent_with_link_state(oracle64, model):
     """spheres at link-probe points: distance + rA + rB is the distance between link_state's positions of the two points, within
     the two tolerances added"""
-    from test_gpu_link_state import TOL as LINK_TOL, pick_links
     n = 9
     cases = case_states(oracle64, model, 67)[:n]
     v = loaded_vec(cases)
@@ -319,12 +311,7 @@ SYN = ("deep_chain", "big_body", "bushy")
 
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
-    import synthetic_models as sm
-    out = {}
-    for name in SYN:
-        path, props, om = sm.compile_both(name, tmp_path_factory.mktemp(name))
-        out[name] = dict(path=path, props=props, om=om)
-    return out
+    return built_models(SYN, tmp_path_factory)
 
 
 def synthetic_deviation(m, name, n=3):
@@ -363,12 +350,8 @@ def test_read_only(n, oracle64, model):
     single."""
     gen = torch.Generator(device=DEV).manual_seed(5)
     w = 50 * torch.randn(n, NB, 6, generator=gen, device=DEV)
-    oo = model["obs_order"]
-    lo = torch.tensor(model["q_lower"][oo], dtype=torch.float32, device=DEV)
-    hi = torch.tensor(model["q_upper"][oo], dtype=torch.float32, device=DEV)
-    acts = [lo + (hi - lo) * torch.rand(n, J, generator=gen, device=DEV) for _ in range(10)]
-    case_states(oracle64, model, 1)
-    landed = torch.tensor(np.array([_CASES["base"][k][0] for k in (20, 22, 24)[:n]], np.float32))   # standing on the floor
+    acts = [random_actions(model, n, gen) for _ in range(10)]
+    landed = torch.tensor(np.array([base_cases(oracle64, model)[k][0] for k in (20, 22, 24)[:n]], np.float32))   # standing on the floor
     bodies, caps, _, chosen = default_table(model)
     pair = []
     for probe in (False, True):
@@ -406,12 +389,7 @@ def test_refusals(model):
     env.reset_tensor()
     b = env.batch
     E = _capi.E_INVALID
-
-    def refused(fn, *a, **kw):
-        with pytest.raises(_capi.TrexError) as ei:
-            fn(*a, **kw)
-        assert ei.value.code == E, (a, kw)
-
+    refused = functools.partial(gpu_support.refused, E)
     dist = torch.full((n, 2), 7.0, device=DEV)
     refused(b.proximity, dist)                                                        # no table yet
     ok_b = [3, 3, 7, 9]
@@ -494,31 +472,11 @@ def test_stream_capture(oracle64, model):
     bodies, caps, _, chosen = default_table(model)
     P = len(chosen)
     v.batch.set_proximity_shapes(bodies, caps, chosen)
-    make = lambda: [torch.empty(n, P, device=DEV)] + [torch.empty(n, P, 3, device=DEV) for _ in range(3)] + [
+    outs = [torch.empty(n, P, device=DEV)] + [torch.empty(n, P, 3, device=DEV) for _ in range(3)] + [
         torch.empty(n, P, 2, dtype=torch.int32, device=DEV)]
-    outs = make()
     call = lambda o: v.batch.proximity(*o, pairs=P)
-    call(outs)                                                      # the first call: learns the buffers
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.stream(side):
-        with torch.cuda.graph(graph, stream=side):
-            call(outs)                                              # the second: one launch, one linear chain
-    first = [o.clone() for o in outs]
-    v.set_state(torch.tensor(np.array([c[0] for c in cases[n:]], np.float32)))
-    eager = make()
-    call(eager)
-    torch.cuda.synchronize()
-    for o in outs:
-        o.zero_()
-    graph.replay()
-    torch.cuda.synchronize()
-    for o, want, old in zip(outs[:4], eager[:4], first[:4]):
-        assert o.cpu().numpy().tobytes() == want.cpu().numpy().tobytes()
-        assert not torch.equal(o, old)
-    assert torch.equal(outs[4], eager[4])
-    del graph
+    change = lambda: v.set_state(torch.tensor(np.array([c[0] for c in cases[n:]], np.float32)))
+    replay_equals_eager(call, outs, change, changed=range(4))       # (the capsule indices may well be those of the first state)
     v.close()
 
 

@@ -12,6 +12,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ray_ref as ry  # noqa: E402
 import render_ref as rr  # noqa: E402
+from gpu_render_support import ray_cast, ray_compare, ray_flat, ray_poses, ray_reference, ray_world  # noqa: E402
+from gpu_support import random_steps  # noqa: E402
 
 from trex_gym import _capi, sensors  # noqa: E402
 from trex_gym.render import Camera  # noqa: E402
@@ -23,94 +25,15 @@ N = 8
 CAMERA = Camera(distance=6.0, yaw=30.0, pitch=-20.0, fov=50.0, target=(0.0, 0.0, 1.5))   # CAMERAS[1] of test_gpu_render.py
 
 
-def _random_steps(env, steps, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    lo, hi = torch.tensor(env.model.lower, dtype=torch.float32), torch.tensor(env.model.upper, dtype=torch.float32)
-    for _ in range(steps):
-        a = lo + (hi - lo) * torch.rand(env.num_envs, env.J, generator=g)
-        env.step_tensor(a.to(env.device))
-
-
-def _poses(env, env_ids=None):
-    """per env: (R, p) of the bodies and (Rl, pl) of the links, f64, from link_transforms() as test_gpu_render.py does"""
-    lt = env.link_transforms().cpu().numpy()
-    lb, ltf = env.model.array("link_body"), env.model.array("link_tf")
-    out = {}
-    for e in (range(env.num_envs) if env_ids is None else env_ids):
-        out[e] = rr.body_poses(lt[e], lb, ltf, env.model.num_bodies) + ry.link_frames(lt[e])
-    return out
-
-
 def _link(env, name):
     return [n for n, _ in env.model.links()].index(name)
 
 
-def _cast(env, rays, link=None, **kw):
-    out = env.ray_test(torch.as_tensor(rays), link, positions=True, normals=True, **kw)
-    torch.cuda.synchronize()
-    return [x.cpu().numpy().copy() for x in out]
-
-
-def _world(env, poses, rays, link):
-    """rays [n, R, 6] or [R, 6] in a link frame (None: world) -> [(from, to)] per env, f64, from the f32 values the GPU sees"""
-    rays = np.asarray(rays, np.float32).astype(np.float64)
-    out = {}
-    for e, (_, _, Rl, pl) in poses.items():
-        r = rays if rays.ndim == 2 else rays[e]
-        out[e] = (r[:, :3], r[:, 3:]) if link is None else ry.to_world(r, Rl[link], pl[link])
-    return out
-
-
-def _compare(gpu, refs, what, stats=None):
-    """gpu: (fraction, body, position, normal) rows of the case's rays; refs: cast()'s tuple over the same rays + their lengths.
-    The renderer's thresholds (tests/test_gpu_render.py::_compare), d = fraction x length:
-    labels agree on >= 99.5 %, every disagreeing ray is marginal (< 1e-4 m), at most 2 % of the rays are marginal; on agreeing
-    non-marginal rays |d - d_ref| <= 1e-4 max(d_ref, 1 m), the position within the same bound, and the normal within 1e-4
-    where the normal margin is >= 1e-4 m."""
-    frac, body, pos, nrm = gpu
-    rf, rl, rp, rn, mg, nm, L = refs
-    agree = body == rl
-    marginal = mg < ry.MARGIN
-    d, dr = frac * L, rf * L
-    ok = agree & ~marginal
-    bound = 1e-4 * np.maximum(dr, 1.0)
-    derr = np.abs(d - dr)[ok] / bound[ok] if ok.any() else np.zeros(1)
-    perr = np.abs(pos - rp).max(axis=1)[ok] / bound[ok] if ok.any() else np.zeros(1)
-    okn = ok & (nm >= ry.MARGIN)
-    nerr = np.abs(nrm - rn).max(axis=1)[okn] if okn.any() else np.zeros(1)
-    print("ray_test %s: rays %d agree %.4f marginal %.4f d_err/bound %.3f p_err/bound %.3f n_err %.2e" %
-          (what, len(frac), agree.mean(), marginal.mean(), derr.max(), perr.max(), nerr.max()))
-    if stats is not None:
-        stats.append((what, agree.mean(), marginal.mean(), derr.max(), perr.max(), nerr.max()))
-    assert marginal.mean() <= ry.MARGINAL_CAP, (what, marginal.mean())
-    assert agree.mean() >= 0.995, (what, agree.mean())
-    assert (mg[~agree] < ry.MARGIN).all(), (what, mg[~agree].max())
-    assert derr.max() <= 1.0, (what, derr.max())
-    assert perr.max() <= 1.0, (what, perr.max())
-    assert nerr.max() <= 1e-4, (what, nerr.max())
-    assert (frac >= 0).all() and (frac <= 1).all()
-    miss = body == -2
-    assert (frac[miss] == 1.0).all() and (nrm[miss] == 0).all()
-
-
-def _reference(scene, poses, world, **kw):
-    parts = [ry.cast(scene, poses[e][0], poses[e][1], *world[e], **kw) + (np.linalg.norm(world[e][1] - world[e][0], axis=1),)
-             for e in sorted(world)]
-    return tuple(np.concatenate([p[k] for p in parts]) for k in range(7))
-
-
-def _flat(gpu, env_ids=None):
-    frac, body, pos, nrm = gpu
-    if env_ids is not None:
-        frac, body, pos, nrm = frac[env_ids], body[env_ids], pos[env_ids], nrm[env_ids]
-    return frac.reshape(-1), body.reshape(-1), pos.reshape(-1, 3), nrm.reshape(-1, 3)
-
-
 def _case(env, scene, poses, rays, link_name, what, **kw):
     link = None if link_name is None else _link(env, link_name)
-    gpu = _cast(env, rays, link_name, **kw)
-    ref = _reference(scene, poses, _world(env, poses, rays, link))
-    _compare(_flat(gpu), ref, what)
+    gpu = ray_cast(env, rays, link_name, **kw)
+    ref = ray_reference(scene, poses, ray_world(env, poses, rays, link))
+    ray_compare(ray_flat(gpu), ref, what)
     return gpu
 
 
@@ -123,9 +46,9 @@ def test_parity_with_reference(collision):
     hit_bodies = 0
     for phase in ("reset", "30 steps"):
         if phase != "reset":
-            _random_steps(env, 30)
+            random_steps(env, 30)
         torch.cuda.synchronize()
-        poses = _poses(env)
+        poses = ray_poses(env)
         base = env.get_state()[:, :3].cpu().numpy()
         g = _case(env, scene, poses, ry.random_segments(N, 300, base), None, (collision, phase, "a: random"))
         hit_bodies += int((g[1] >= 0).sum())
@@ -143,17 +66,17 @@ def test_parity_with_reference(collision):
 def test_against_the_renderer():
     env = TrexVecEnv(N, device="cuda:0")
     env.reset_tensor()
-    _random_steps(env, 10)
+    random_steps(env, 10)
     W, H, cam = 32, 24, CAMERA
     _, dep, seg = env.render_tensor(None, W, H, cam, depth=True, segmentation=True)
     dep, seg = dep.cpu().numpy().reshape(N, -1), seg.cpu().numpy().reshape(N, -1)
     eye, dirs, fwd = rr.camera_rays(cam.distance, cam.yaw, cam.pitch, cam.fov, W, H, cam.target)
     D = dirs.reshape(-1, 3)
     rays = np.concatenate([np.tile(eye, (len(D), 1)), eye + cam.far * D], 1).astype(np.float32)
-    frac, body, _, _ = _cast(env, rays)
-    scene, poses = ry.Scene.from_model(env.model), _poses(env)
+    frac, body, _, _ = ray_cast(env, rays)
+    scene, poses = ry.Scene.from_model(env.model), ray_poses(env)
     r64 = rays.astype(np.float64)
-    mg = _reference(scene, poses, {e: (r64[:, :3], r64[:, 3:]) for e in range(N)})[4].reshape(N, -1)
+    mg = ray_reference(scene, poses, {e: (r64[:, :3], r64[:, 3:]) for e in range(N)})[4].reshape(N, -1)
     length = np.linalg.norm(r64[:, 3:] - r64[:, :3], axis=1)
     along = (r64[:, 3:] - r64[:, :3]) @ fwd / length          # dir . fwd of the unit direction
     depth = frac * length * along                             # eye-space depth of the ray's hit
@@ -175,7 +98,7 @@ def test_floor_analytic():
     z1 = np.array([-0.5, 0.0, -1.0, -30.0, 0.0, fz - 0.25, fz, -0.001], np.float32)
     dx = np.array([0.0, 0.0, 3.0, -20.0, 0.5, 0.0, 1.0, 4.0], np.float32)
     rays = np.stack([dx * 0 + 7, dx * 0 - 4, z0, 7 + dx, -4 + 0.5 * dx, z1], 1).astype(np.float32)
-    frac, body, pos, nrm = _cast(env, rays, bodies=[])
+    frac, body, pos, nrm = ray_cast(env, rays, bodies=[])
     want = (z0.astype(np.float64) - float(fz)) / (z0.astype(np.float64) - z1.astype(np.float64))
     assert (body == -1).all()
     assert np.abs(frac / want - 1).max() <= 1e-6, np.abs(frac / want - 1).max()
@@ -187,11 +110,11 @@ def test_floor_analytic():
     up = rays.copy()
     up[:, 5] = fz + 0.01
     for r in (below, up):
-        frac, body, pos, nrm = _cast(env, r, bodies=[])
+        frac, body, pos, nrm = ray_cast(env, r, bodies=[])
         assert (body == -2).all() and (frac == 1.0).all() and (nrm == 0).all()
         np.testing.assert_array_equal(pos, np.broadcast_to(r[:, 3:], pos.shape))
     # nothing may be hit at all: the miss encoding everywhere
-    frac, body, pos, nrm = _cast(env, rays, bodies=[], floor=False)
+    frac, body, pos, nrm = ray_cast(env, rays, bodies=[], floor=False)
     assert (body == -2).all() and (frac == 1.0).all() and (nrm == 0).all()
     env.close()
 
@@ -200,17 +123,17 @@ def test_floor_analytic():
 def test_link_frame_equals_world_frame():
     env = TrexVecEnv(N, device="cuda:0")
     env.reset_tensor()
-    _random_steps(env, 20)
-    scene, poses = ry.Scene.from_model(env.model), _poses(env)
+    random_steps(env, 20)
+    scene, poses = ry.Scene.from_model(env.model), ray_poses(env)
     for name, rays in ((ry.BASE_LINK, ry.single_ray()), (ry.HEAD_LINK, ry.head_fan()), (ry.FOOT_LINKS[0], ry.foot_rays())):
         link = _link(env, name)
-        g_link = _cast(env, rays, name)
-        world = _world(env, poses, rays, link)
+        g_link = ray_cast(env, rays, name)
+        world = ray_world(env, poses, rays, link)
         wr = np.stack([np.concatenate(world[e], 1) for e in range(N)]).astype(np.float32)
-        g_world = _cast(env, wr)
-        ref = _reference(scene, poses, world)
-        _compare(_flat(g_link), ref, ("link frame", name))
-        _compare(_flat(g_world), ref, ("world frame", name))
+        g_world = ray_cast(env, wr)
+        ref = ray_reference(scene, poses, world)
+        ray_compare(ray_flat(g_link), ref, ("link frame", name))
+        ray_compare(ray_flat(g_world), ref, ("world frame", name))
     env.close()
 
 
@@ -218,10 +141,10 @@ def test_link_frame_equals_world_frame():
 def test_shared_equals_per_env_bitwise():
     env = TrexVecEnv(N, device="cuda:0")
     env.reset_tensor()
-    _random_steps(env, 5)
+    random_steps(env, 5)
     for name, rays in ((ry.HEAD_LINK, ry.head_fan()), (None, ry.random_segments(1, 300, [[0, 0, 0]])[0])):
-        a = _cast(env, rays, name)
-        b = _cast(env, np.broadcast_to(rays, (N,) + rays.shape).copy(), name)
+        a = ray_cast(env, rays, name)
+        b = ray_cast(env, np.broadcast_to(rays, (N,) + rays.shape).copy(), name)
         for x, y in zip(a, b):
             assert x.tobytes() == y.tobytes()
     env.close()
@@ -231,13 +154,13 @@ def test_shared_equals_per_env_bitwise():
 def test_body_mask():
     env = TrexVecEnv(N, device="cuda:0")
     env.reset_tensor()
-    _random_steps(env, 5)
+    random_steps(env, 5)
     rays = ry.random_segments(N, 300, env.get_state()[:, :3].cpu().numpy(), seed=3)
-    full = _cast(env, rays)
+    full = ray_cast(env, rays)
     hit = np.bincount(full[1][full[1] >= 0], minlength=env.model.num_bodies)
     b = int(np.argmax(hit))
     assert hit[b] > 0
-    part = _cast(env, rays, bodies=[k for k in range(env.model.num_bodies) if k != b])
+    part = ray_cast(env, rays, bodies=[k for k in range(env.model.num_bodies) if k != b])
     assert (part[1] != b).all()
     keep = full[1] != b
     for x, y in zip(full, part):
@@ -250,7 +173,7 @@ def test_body_mask():
 def test_origin_inside(collision):
     env = TrexVecEnv(N, device="cuda:0", collision=collision)
     env.reset_tensor()
-    scene, poses = ry.Scene.from_model(env.model), _poses(env)
+    scene, poses = ry.Scene.from_model(env.model), ray_poses(env)
     R, p = poses[0][:2]
     checked = 0
     for k, prim in enumerate(scene.prims):
@@ -269,7 +192,7 @@ def test_origin_inside(collision):
                                      body_mask=1 << body, hit_floor=False)
         if rl[0] != -2 or mg[0] < 1e-3:
             continue
-        frac, lab, _, _ = _cast(env, rays, bodies=[body], floor=False)
+        frac, lab, _, _ = ray_cast(env, rays, bodies=[body], floor=False)
         assert lab[0, 0] == -2 and frac[0, 0] == 1.0, (k, body)
         checked += 1
         if checked == 6:
@@ -282,9 +205,9 @@ def test_origin_inside(collision):
 def test_bad_rays():
     env = TrexVecEnv(N, device="cuda:0")
     env.reset_tensor()
-    _random_steps(env, 5)
+    random_steps(env, 5)
     good = ry.random_segments(N, 96, env.get_state()[:, :3].cpu().numpy(), seed=5)
-    ref = _cast(env, good)
+    ref = ray_cast(env, good)
     mixed = np.repeat(good, 2, axis=1)                          # lane by lane: good, bad, good, bad ...
     bad = mixed[:, 1::2]
     kinds = np.arange(bad.shape[1]) % 4
@@ -292,7 +215,7 @@ def test_bad_rays():
     bad[:, kinds == 1, 4] = np.inf
     bad[:, kinds == 2, 3:] = bad[:, kinds == 2, :3]             # zero length
     bad[:, kinds == 3, :] = -np.inf
-    out = _cast(env, mixed)
+    out = ray_cast(env, mixed)
     for x, y in zip(ref, out):
         assert x.tobytes() == np.ascontiguousarray(y[:, 0::2]).tobytes()
     assert (out[0][:, 1::2] == 1.0).all() and (out[1][:, 1::2] == -2).all() and (out[3][:, 1::2] == 0).all()
@@ -309,7 +232,7 @@ def test_tiling_edges(n):
     128, 129: 2, 1; 255, 256, 257: one env in 1, 1, 2 workgroups; n = 1, 5, 33 leave the last workgroup partly filled."""
     env = TrexVecEnv(n, device="cuda:0")
     env.reset_tensor()
-    _random_steps(env, 3)
+    random_steps(env, 3)
     dev = env.device
     state = env.get_state()
     base = state[:, :3].cpu().numpy()
@@ -338,7 +261,7 @@ def test_tiling_edges(n):
         one.set_state(state[e:e + 1])
         for R, rays in sets.items():
             for r0 in range(0, R, 64):
-                part = _cast(one, rays[e:e + 1, r0:r0 + 64])
+                part = ray_cast(one, rays[e:e + 1, r0:r0 + 64])
                 for x, y in zip(got[R], part):
                     assert np.ascontiguousarray(x[e, r0:r0 + 64]).tobytes() == y[0].tobytes(), (n, R, e, r0)
     one.close()
@@ -353,15 +276,15 @@ def test_determinism_and_no_side_effects(n, params, sensor):
         if sensor:
             e.enable_contact_sensor(True)
         e.reset_tensor()
-        _random_steps(e, 5, seed=1)
+        random_steps(e, 5, seed=1)
     before = envs[0].get_state().clone()
     wrench = envs[0].contact_wrench().clone() if sensor else None
     rays = ry.random_segments(n, 40, before[:, :3].cpu().numpy(), seed=2)
-    a = _cast(envs[0], rays)
-    b = _cast(envs[0], rays)
+    a = ray_cast(envs[0], rays)
+    b = ray_cast(envs[0], rays)
     for x, y in zip(a, b):
         assert x.tobytes() == y.tobytes()
-    _cast(envs[0], ry.head_fan(), ry.HEAD_LINK)
+    ray_cast(envs[0], ry.head_fan(), ry.HEAD_LINK)
     assert envs[0].get_state().cpu().numpy().tobytes() == before.cpu().numpy().tobytes()
     if sensor:
         assert envs[0].contact_wrench().cpu().numpy().tobytes() == wrench.cpu().numpy().tobytes()
@@ -385,7 +308,7 @@ def test_determinism_and_no_side_effects(n, params, sensor):
 def test_stream_capture():
     env = TrexVecEnv(N, device="cuda:0")
     env.reset_tensor()
-    _random_steps(env, 5)
+    random_steps(env, 5)
     dev = env.device
     rays = torch.as_tensor(ry.head_fan()).to(dev)
     link = _link(env, ry.HEAD_LINK)
@@ -474,19 +397,19 @@ def test_argument_checks():
 def test_scale_4096_envs():
     env = TrexVecEnv(4096, device="cuda:0")
     env.reset_tensor()
-    _random_steps(env, 3)
+    random_steps(env, 3)
     ids = [0, 1000, 2047, 4095]
     base = env.get_state()[:, :3].cpu().numpy()
     rays = ry.random_segments(4096, 16, base, seed=7)
     rays[:, 8:, :3] = base[:, None] + np.float32([0.0, 0.0, 2.0])         # half of them start above the base
     rays[:, 8:, 3:5] = base[:, None, :2] + (rays[:, 8:, 3:5] - base[:, None, :2]) * np.float32(0.2)   # and end under the floor,
     rays[:, 8:, 5] = -0.5                                                 # through the body or beside it
-    gpu = _cast(env, rays)
+    gpu = ray_cast(env, rays)
     assert gpu[0].shape == (4096, 16) and gpu[1].shape == (4096, 16) and gpu[2].shape == gpu[3].shape == (4096, 16, 3)
-    poses = _poses(env, ids)
-    ref = _reference(ry.Scene.from_model(env.model), poses, _world(env, poses, rays, None))
-    frac, body, pos, nrm = _flat(gpu, ids)
-    _compare((frac, body, pos, nrm), ref, "scale")
+    poses = ray_poses(env, ids)
+    ref = ray_reference(ry.Scene.from_model(env.model), poses, ray_world(env, poses, rays, None))
+    frac, body, pos, nrm = ray_flat(gpu, ids)
+    ray_compare((frac, body, pos, nrm), ref, "scale")
     assert (gpu[1] >= 0).any() and (gpu[1] == -1).any()
     env.close()
 
@@ -498,7 +421,7 @@ def test_facade():
     x, y, z = env.model.get_base_position()
     # a vertical ray through a point inside a hull (the line through the base's origin passes between the hulls of this
     # robot): the reference names the body it meets first
-    scene, (R, p) = ry.Scene.from_model(env._vec.model), _poses(env._vec)[0][:2]
+    scene, (R, p) = ry.Scene.from_model(env._vec.model), ray_poses(env._vec)[0][:2]
     hx, hy, _ = next(R[prim[1]] @ prim[4] + p[prim[1]] for prim in scene.prims
                      if prim[0] == "hull" and (prim[2] @ prim[4] - prim[3]).max() < -1e-2)
     frm = [[hx, hy, z + 5.0], [x + 20.0, y, 2.0], [x + 20.0, y, 2.0]]

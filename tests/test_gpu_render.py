@@ -9,6 +9,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import render_ref as rr  # noqa: E402
+from gpu_render_support import render_all, render_compare, render_reference  # noqa: E402
+from gpu_support import random_steps  # noqa: E402
 
 from trex_gym import _capi  # noqa: E402
 from trex_gym.render import Camera  # noqa: E402
@@ -18,46 +20,6 @@ pytestmark = pytest.mark.gpu
 
 CAMERAS = [Camera(), Camera(distance=6.0, yaw=30.0, pitch=-20.0, fov=50.0, target=(0.0, 0.0, 1.5)),
            Camera(distance=4.0, yaw=200.0, pitch=-60.0, fov=70.0, near=0.5, far=30.0, target=(0.5, -0.3, 1.0))]
-
-
-def _random_steps(env, steps, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    lo, hi = torch.tensor(env.model.lower, dtype=torch.float32), torch.tensor(env.model.upper, dtype=torch.float32)
-    for _ in range(steps):
-        a = lo + (hi - lo) * torch.rand(env.num_envs, env.J, generator=g)
-        env.step_tensor(a.to(env.device))
-
-
-def _reference(env, scene, cam, W, H, env_ids):
-    lt = env.link_transforms().cpu().numpy()
-    st = env.get_state().cpu().numpy()
-    lb, ltf = env.model.array("link_body"), env.model.array("link_tf")
-    out = []
-    for e in env_ids:
-        R, p = rr.body_poses(lt[e], lb, ltf, env.model.num_bodies)
-        target = st[e, :3] if cam.target is None else cam.target
-        eye, dirs, _ = rr.camera_rays(cam.distance, cam.yaw, cam.pitch, cam.fov, W, H, target)
-        out.append(rr.render(scene, R, p, eye, dirs, cam.near, cam.far))
-    return out
-
-
-def _compare(gpu, ref, what):
-    rgb, dep, seg = gpu
-    rseg, rdep, rrgb, sm, rm = ref
-    agree = seg == rseg
-    assert agree.mean() >= 0.995, (what, agree.mean())
-    assert (sm[~agree] < 1e-4).all(), (what, sm[~agree].max())
-    ok = agree & (sm >= 1e-4)
-    rel = np.abs(dep[ok] - rdep[ok]) / np.maximum(rdep[ok], 1e-6)
-    assert rel.max() <= 1e-4, (what, rel.max())
-    okc = ok & (rm >= 1e-4)
-    diff = np.abs(rgb[okc].astype(int) - rrgb[okc].astype(int))
-    assert diff.max() <= 2, (what, diff.max())
-
-
-def _render_all(env, cam, W, H, env_ids=None):
-    rgb, dep, seg = env.render_tensor(env_ids, W, H, cam, depth=True, segmentation=True)
-    return rgb.cpu().numpy(), dep.cpu().numpy(), seg.cpu().numpy()
 
 
 def test_single_env_rgb_array_frame():
@@ -83,13 +45,13 @@ def test_parity_with_reference(collision):
     env.reset_tensor()
     for phase in ("reset", "30 steps"):
         if phase != "reset":
-            _random_steps(env, 30)
+            random_steps(env, 30)
         torch.cuda.synchronize()
         for ci, cam in enumerate(CAMERAS):
-            rgb, dep, seg = _render_all(env, cam, W, H)
-            refs = _reference(env, scene, cam, W, H, range(8))
+            rgb, dep, seg = render_all(env, cam, W, H)
+            refs = render_reference(env, scene, cam, W, H, range(8))
             for e in range(8):
-                _compare((rgb[e], dep[e], seg[e]), refs[e], (collision, phase, ci, e))
+                render_compare((rgb[e], dep[e], seg[e]), refs[e], (collision, phase, ci, e))
             assert (seg >= 0).any()
     env.close()
 
@@ -97,12 +59,12 @@ def test_parity_with_reference(collision):
 def test_determinism_and_view_selection():
     env = TrexVecEnv(8, device="cuda:0")
     env.reset_tensor()
-    _random_steps(env, 10)
-    a = _render_all(env, CAMERAS[0], 80, 60)
-    b = _render_all(env, CAMERAS[0], 80, 60)
+    random_steps(env, 10)
+    a = render_all(env, CAMERAS[0], 80, 60)
+    b = render_all(env, CAMERAS[0], 80, 60)
     for x, y in zip(a, b):
         assert x.tobytes() == y.tobytes()
-    c = _render_all(env, CAMERAS[0], 80, 60, env_ids=[7, 3, 3])
+    c = render_all(env, CAMERAS[0], 80, 60, env_ids=[7, 3, 3])
     for x, y in zip(a, c):
         assert x[[7, 3, 3]].tobytes() == y.tobytes()
     # pre-filled buffers come back fully written
@@ -123,7 +85,7 @@ def test_render_has_no_side_effects(n, params):
     envs = [TrexVecEnv(n, device="cuda:0", params=params) for _ in range(2)]
     for e in envs:
         e.reset_tensor()
-        _random_steps(e, 5, seed=1)
+        random_steps(e, 5, seed=1)
     before = envs[0].get_state().clone()
     envs[0].render_tensor(None, 64, 48, Camera(), depth=True, segmentation=True)
     envs[0].render_tensor([0, n - 1], 32, 32, CAMERAS[2])
@@ -179,14 +141,14 @@ def test_argument_checks():
 def test_scale_4096_envs():
     env = TrexVecEnv(4096, device="cuda:0")
     env.reset_tensor()
-    _random_steps(env, 3)
+    random_steps(env, 3)
     rgb, dep, seg = env.render_tensor(None, 64, 64, Camera(), depth=True, segmentation=True)
     assert rgb.shape == (4096, 64, 64, 3) and dep.shape == (4096, 64, 64) and seg.shape == (4096, 64, 64)
     ids = [0, 1000, 2047, 4095]
-    refs = _reference(env, rr.Scene.from_model(env.model), Camera(), 64, 64, ids)
+    refs = render_reference(env, rr.Scene.from_model(env.model), Camera(), 64, 64, ids)
     r, d, s = rgb.cpu().numpy(), dep.cpu().numpy(), seg.cpu().numpy()
     for k, e in enumerate(ids):
-        _compare((r[e], d[e], s[e]), refs[k], e)
+        render_compare((r[e], d[e], s[e]), refs[k], e)
     env.close()
 
 

@@ -16,7 +16,7 @@ are tests/render_cases.py, qualified on the reference alone by tests/test_render
                                     with a dense faceted underside
   test_ray_cast_on_bent_models      the same pose pass and primitive table under trex_batch_ray_test
 
-Tolerances: those of tests/test_gpu_render.py::_compare and tests/test_gpu_ray_test.py::_compare, unchanged. On top of them, the
+Tolerances: those of render_compare and ray_compare (tests/gpu_render_support.py), unchanged. On top of them, the
 share of pixels the rgb comparison uses is bounded from below (render_cases.RGB_USED_MIN), and the rgb margin of a floor pixel is
 reduced by the f32 resolution of its hit point (render_cases.condition): both only take pixels OUT of what may pass unseen.
 The reference sees the poses the kernel's own state gives, read back through link_transforms (as everywhere in the renderer's
@@ -37,17 +37,17 @@ import ray_ref as ry  # noqa: E402
 import render_cases as rc  # noqa: E402
 import render_ref as rr  # noqa: E402
 import synthetic_models as sm  # noqa: E402
-import test_gpu_ray_test as trt  # noqa: E402
-from test_gpu_render import _compare, _reference, _render_all  # noqa: E402
+from gpu_render_support import (ray_cast, ray_compare, ray_flat, ray_poses, ray_reference, ray_world, render_all,  # noqa: E402
+                                render_compare, render_reference)
+from gpu_support import DEV  # noqa: E402
 
 from trex_gym.vec_env import TrexVecEnv  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 def _body_poses(env):
-    """per env (R [nb, 3, 3], p [nb, 3]) from link_transforms, as _reference does"""
+    """per env (R [nb, 3, 3], p [nb, 3]) from link_transforms, as render_reference does"""
     lt = env.link_transforms().cpu().numpy()
     lb, ltf = env.model.array("link_body"), env.model.array("link_tf")
     return [rr.body_poses(lt[e], lb, ltf, env.model.num_bodies) for e in range(env.num_envs)]
@@ -80,14 +80,14 @@ def _calls(cam, poses):
 
 
 def _conditioned(env, refs, c, W, H, ids):
-    """the references of _reference with the rgb margin of floor pixels reduced by the f32 resolution of the hit point
+    """the references of render_reference with the rgb margin of floor pixels reduced by the f32 resolution of the hit point
     (render_cases.condition): far out on the floor f32 cannot tell which checker square a point lies in"""
     base = env.get_state()[:, :3].cpu().numpy()
     return [rc.condition(r, *rc.view_rays(c, W, H, base[e])) for r, e in zip(refs, ids)]
 
 
 def _figures(gpu, ref):
-    """what _compare looks at, as numbers: (pixels, share left out by seg margin, share left out by rgb margin, label agreement,
+    """what render_compare looks at, as numbers: (pixels, share left out by seg margin, share left out by rgb margin, label agreement,
     worst relative depth error, worst rgb difference, share of pixels the rgb comparison uses)"""
     rgb, dep, seg = gpu
     rseg, rdep, rrgb, smg, rmg = ref
@@ -103,9 +103,9 @@ def _check_view(gpu, ref, what, rgb_used=True):
     f = _figures(gpu, ref)
     print("render %s: pixels %d out by seg margin %.4f by rgb margin %.4f agree %.4f depth rel %.2e rgb diff %d rgb used %.4f"
           % ((what,) + f))
-    _compare(gpu, ref, what)
+    render_compare(gpu, ref, what)
     if rgb_used and f[0] >= rc.RGB_PIXELS:
-        # the rgb comparison of _compare skips what it cannot judge; it must not skip its way to a pass
+        # the rgb comparison of render_compare skips what it cannot judge; it must not skip its way to a pass
         assert f[6] >= rc.RGB_USED_MIN, (what, f[6])
 
 
@@ -116,9 +116,9 @@ def test_parity_over_the_cases(collision, name, trex):
     for (W, H) in rc.frames(name):
         cam = rc.case_camera(name, collision, (W, H))
         for ids, c in _calls(cam, poses):
-            rgb, dep, seg = _render_all(env, c, W, H, ids)
+            rgb, dep, seg = render_all(env, c, W, H, ids)
             assert rgb.shape == (len(ids), H, W, 3) and dep.shape == seg.shape == (len(ids), H, W)
-            refs = _conditioned(env, _reference(env, scene, c, W, H, ids), c, W, H, ids)
+            refs = _conditioned(env, render_reference(env, scene, c, W, H, ids), c, W, H, ids)
             for j, k in enumerate(ids):
                 what = (collision, name, W, H, rc.STATE_NAMES[k])
                 _check_view((rgb[j], dep[j], seg[j]), refs[j], what)
@@ -136,7 +136,7 @@ def test_exact_answers_bitwise(name, trex):
     cam = rc.case_camera(name)
     near, far = np.float32(cam[4]), np.float32(cam[5])
     for (W, H) in rc.EXACT_FRAMES:
-        rgb, dep, seg = _render_all(env, rc.resolve(cam), W, H)
+        rgb, dep, seg = render_all(env, rc.resolve(cam), W, H)
         if name == "below_floor":
             assert (seg == -1).all() and (_bits(dep) == _bits(near)).all()
         elif name == "all_sky":
@@ -203,8 +203,8 @@ def test_views_grow_and_reuse(oracle64):
     cam = rc.resolve(rc.case_camera("far_view", "hulls", (W, H)))
     lists = [[2, 0], [(k * k + k // 7) % 3 for k in range(70)], [1, 1, 2, 0, 1]]
     assert set(lists[1]) == {0, 1, 2} and any(a == b for a, b in zip(lists[1], lists[1][1:]))
-    got = [_render_all(env, cam, W, H, ids) for ids in lists]
-    every = _render_all(env, cam, W, H, None)
+    got = [render_all(env, cam, W, H, ids) for ids in lists]
+    every = render_all(env, cam, W, H, None)
     assert every[0].shape == (3, H, W, 3)
     assert not (every[2][0] == every[2][1]).all()                          # the envs' pictures differ
     for ids, g in zip(lists, got):
@@ -236,7 +236,7 @@ def synth(tmp_path_factory):
 
 @pytest.mark.parametrize("name", rc.SYNTH_MODELS)
 def test_generated_models_bent(name, synth):
-    """_compare on both states and both cameras. The rgb-share condition of test_parity_over_the_cases does not apply: the
+    """render_compare on both states and both cameras. The rgb-share condition of test_parity_over_the_cases does not apply: the
     jittered undersides of big_body and full_masks are many nearly coplanar facets, and up to 40 % of their pixels lie within
     1e-4 m of an edge between two of them (the rgb comparison leaves those out; seg and depth are compared on all of them)."""
     m = synth(name)
@@ -246,8 +246,8 @@ def test_generated_models_bent(name, synth):
     hulled = {b for b in range(om["nb"]) if om["hull_start"][b + 1] > om["hull_start"][b]}
     for cname, cam in m["cams"].items():
         for ids, c in _calls(cam, poses):
-            rgb, dep, seg = _render_all(env, c, W, H, ids)
-            refs = _conditioned(env, _reference(env, m["scene"], c, W, H, ids), c, W, H, ids)
+            rgb, dep, seg = render_all(env, c, W, H, ids)
+            refs = _conditioned(env, render_reference(env, m["scene"], c, W, H, ids), c, W, H, ids)
             for j, e in enumerate(ids):
                 what = (name, cname, ("sampled", "bent")[e])
                 _check_view((rgb[j], dep[j], seg[j]), refs[j], what, rgb_used=False)
@@ -267,10 +267,10 @@ def test_ray_cast_on_bent_models(name, synth):
     the comparison of tests/test_gpu_ray_test.py."""
     m = synth(name)
     env = m["env"]
-    scene, poses = ry.Scene.from_model(env.model), trt._poses(env)
+    scene, poses = ry.Scene.from_model(env.model), ray_poses(env)
     base = env.get_state()[:, :3].cpu().numpy()
     rays = rc.synth_segments(base, rc.synth_extent(m["om"]))
-    gpu = trt._cast(env, rays)
-    ref = trt._reference(scene, poses, trt._world(env, poses, rays, None))
-    trt._compare(trt._flat(gpu), ref, (name, "bent and sampled"))
+    gpu = ray_cast(env, rays)
+    ref = ray_reference(scene, poses, ray_world(env, poses, rays, None))
+    ray_compare(ray_flat(gpu), ref, (name, "bent and sampled"))
     assert (gpu[1][1] >= 0).sum() >= rc.SYNTH_RAY_HITS, (gpu[1][1] >= 0).sum()        # the bent state's bodies are hit

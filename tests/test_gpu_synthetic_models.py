@@ -13,11 +13,13 @@ import pytest
 import torch
 
 import dynamics_ref as R
+import gpu_support
 import synthetic_models as sm
+from gpu_support import DEV
 from parity_helpers import assert_step_close, oracle_wrench
+from state_sets import query_states
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 G = 9.81
 
 # largest deviations on an MI355X over the states of test_queries_outside_the_step (profiles/r14_synthetic_models.txt)
@@ -41,9 +43,8 @@ def built(tmp_path_factory):
 
 
 def make_vec(m, n, **kw):
-    from trex_gym.vec_env import TrexVecEnv
     params = dict(m["params"], **kw.pop("params", {}))
-    return TrexVecEnv(n, urdf_path=m["path"], device=DEV, params=params, **kw)
+    return gpu_support.make_vec(n, m["path"], params=params, **kw)
 
 
 def loaded(m, n=None, **kw):
@@ -215,11 +216,6 @@ def test_features_leave_the_physics_bitwise_unchanged(name, built):
 
 
 # ---------------------------------------------------------------- 3. kernels outside the step
-def _query_states(om, count=12):
-    states, _ = R.random_states(om, count, seed=31)
-    return [s for s in states]
-
-
 def _cent_dev(got, want):
     mt = want[14]
     parts = [(slice(0, 3), max(np.abs(want[0:3]).max(), 1.0)), (slice(3, 6), max(np.abs(want[3:6]).max(), 0.01)),
@@ -236,7 +232,7 @@ def test_queries_outside_the_step(name, built):
     from oracle import trex_model as tm
     m = built[name]
     om, o64 = m["om"], m["o64"]
-    states = _query_states(om)
+    states = query_states(om)
     v = make_vec(m, len(states))
     v.reset()
     v.set_state(torch.tensor(np.array(states, np.float32)))
@@ -281,7 +277,7 @@ def test_render_of_many_hulls(built):
     """depth and segmentation of the 36-hull model against tests/render_ref.py at one small frame, resting on the floor"""
     import render_ref as rr
     from trex_gym.render import Camera
-    from test_gpu_render import _compare
+    from gpu_render_support import render_compare
     m = built["many_hulls"]
     v, _ = loaded(m, 2)
     v.set_state(torch.tensor(m["states"][[-1, len(m["states"]) // 2]]))
@@ -295,7 +291,7 @@ def test_render_of_many_hulls(built):
     for e in range(2):
         Rb, pb = rr.body_poses(lt[e], lb, ltf, v.model.num_bodies)
         eye, dirs, _ = rr.camera_rays(cam.distance, cam.yaw, cam.pitch, cam.fov, W, H, st[e, :3])
-        _compare((rgb[e], dep[e], seg[e]), rr.render(scene, Rb, pb, eye, dirs, cam.near, cam.far), ("many_hulls", e))
+        render_compare((rgb[e], dep[e], seg[e]), rr.render(scene, Rb, pb, eye, dirs, cam.near, cam.far), ("many_hulls", e))
         assert len(set(seg[e][seg[e] >= 0])) >= 4 and (seg[e] == -1).sum() > 100
     v.close()
 

@@ -13,18 +13,21 @@ reference there. A judged state within the tolerance of a threshold could be dec
 none instead of leaving one out. On the qualified states themselves the decision is checked through the query: the kernel's
 clearances, the head position and the tilt put every one of them on the reference's side of every threshold."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import gpu_support
 import termination_cases as TC
 import termination_ref as TR
 from conftest import ASSET_URDF
+from gpu_support import DEV, guarded, guards_intact
+from state_sets import built_models
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NB, J = 26, 25
 
 # Largest deviations measured on an MI355X (profiles/r19_termination.txt), over the N = 67 samples of both collision models, the
@@ -36,8 +39,7 @@ NEVER = dict(head_height=-1.0e3, max_tilt=float(np.pi))     # thresholds in forc
 
 
 def make_vec(n, collision="hulls", urdf=ASSET_URDF, **kw):
-    from trex_gym.vec_env import TrexVecEnv
-    return TrexVecEnv(n, urdf_path=urdf, device=DEV, collision=collision, **kw)
+    return gpu_support.make_vec(n, urdf, collision=collision, **kw)
 
 
 def load(v, cases, idx=None):
@@ -53,18 +55,6 @@ def load(v, cases, idx=None):
 
 def scale_of(state):
     return max(1.0, float(np.abs(np.asarray(state)[:3]).max()))
-
-
-def guarded(shape, guard=64):
-    """a device buffer with `guard` floats of 7.0 on either side of the block the kernel may write: (whole, view)"""
-    numel = int(np.prod(shape))
-    whole = torch.full((numel + 2 * guard,), 7.0, device=DEV)
-    return whole, whole[guard:guard + numel].view(*shape)
-
-
-def guards_intact(whole, shape, guard=64):
-    numel = int(np.prod(shape))
-    return bool((whole[:guard] == 7.0).all() and (whole[guard + numel:] == 7.0).all())
 
 
 def query(v, lowest=True):
@@ -464,10 +454,7 @@ SYNTHETIC = ("deep_chain", "big_body", "many_hulls")
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
     import synthetic_models as sm
-    out = {}
-    for name in SYNTHETIC:
-        path, props, om = sm.compile_both(name, tmp_path_factory.mktemp(name))
-        out[name] = dict(path=path, props=props, om=om)
+    out = built_models(SYNTHETIC, tmp_path_factory)
     # a root with a hull, a link without a collision point, a link with ONE
     b = sm.Builder(tmp_path_factory.mktemp("few_points"), "few_points")
     rng = np.random.default_rng(4)
@@ -567,12 +554,7 @@ def test_refusals():
     env.reset_tensor()
     b = env.batch
     E = _capi.E_INVALID
-
-    def refused(fn, *a, **kw):
-        with pytest.raises(_capi.TrexError) as ei:
-            fn(*a, **kw)
-        assert ei.value.code == E, (a, kw)
-
+    refused = functools.partial(gpu_support.refused, E)
     clr = torch.full((n, NB), 7.0, device=DEV)
     low = torch.full((n, NB, 3), 7.0, device=DEV)
     refused(b.body_clearance, clr.cpu())

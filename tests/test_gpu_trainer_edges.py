@@ -16,10 +16,10 @@ import pytest
 import torch
 
 import trainer_cases as tc
+from gpu_support import DEV
 from oracle import ppo_oracle as P
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 GUARD = 64
 SENT = -12345.0
 LR, EPS, MAXN = tc.LR, tc.ADAM_EPS, tc.MAX_GRAD_NORM

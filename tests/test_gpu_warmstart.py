@@ -10,26 +10,19 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ASSET_URDF
+import gpu_support
+import state_sets
+from gpu_support import DEV, random_action_steps as rand_actions
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 J = 25
 
 
 def make_vec(n, warm=None, max_episode_steps=None, **params):
-    from trex_gym.vec_env import TrexVecEnv
     prm = dict(params)
     if warm is not None:
         prm["warmstart"] = warm
-    return TrexVecEnv(n, urdf_path=ASSET_URDF, device=DEV, params=prm or None, max_episode_steps=max_episode_steps)
-
-
-def rand_actions(model, steps, n, seed):
-    lo = torch.tensor(model["q_lower"][model["obs_order"]], dtype=torch.float32, device=DEV)
-    hi = torch.tensor(model["q_upper"][model["obs_order"]], dtype=torch.float32, device=DEV)
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    return lo + (hi - lo) * torch.rand(steps, n, J, device=DEV, generator=g)
+    return gpu_support.make_vec(n, params=prm or None, max_episode_steps=max_episode_steps)
 
 
 def run_rows(v, acts):
@@ -57,19 +50,7 @@ def oracle_step(orc, state, action):
 @pytest.fixture(scope="module")
 def landing_states(oracle64, model):
     """The 50 states along a 300-step landing that tests/test_gpu_parity.py::test_one_step_parity_in_contact_and_at_rest uses."""
-    q0 = model["q_start"][model["obs_order"]]
-    lo, hi = model["q_lower"][model["obs_order"]], model["q_upper"][model["obs_order"]]
-    rng = np.random.default_rng(5)
-    s = oracle64.new_state()
-    oracle64.reset(s)
-    states, acts = [], []
-    for t in range(300):
-        a = np.clip(q0 + 0.15 * rng.normal(size=25), lo, hi)
-        oracle64.step(s, a)
-        if t % 6 == 0:
-            states.append(oracle64.get_state(s).astype(np.float32))
-            acts.append(np.clip(q0 + 0.15 * rng.normal(size=25), lo, hi).astype(np.float32))
-    return np.array(states), np.array(acts)
+    return state_sets.landing_states(oracle64, model, every=6)
 
 
 # ---------------------------------------------------------------- bitwise properties

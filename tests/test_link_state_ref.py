@@ -12,7 +12,7 @@ import pytest
 import dynamics_ref as R
 import link_state_ref as L
 import synthetic_models as sm
-from test_gpu_external_wrench import landing_states
+from state_sets import landing_states
 
 G = 9.81
 H = 1e-5

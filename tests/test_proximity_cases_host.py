@@ -8,6 +8,7 @@ import pytest
 import dynamics_ref as R
 import proximity_cases as PC
 import proximity_ref as PR
+from state_sets import case_states
 
 CASES = PC.cases()
 
@@ -64,7 +65,6 @@ def test_case_is_in_its_region(case, model, state):
 def test_no_case_state_has_its_minimum_near_zero(oracle64, model):
     """the reference's smallest distance over the default pairs, on the 67 case states of the GPU tests: none within 1e-4 m of 0
     (the GPU tolerance is 1e-5 x the env's scale, a few 1e-5 m)"""
-    from test_gpu_dynamics import case_states
     bodies, caps = PR.fitted_table(model)
     pairs = PR.default_pairs(model, bodies, caps)
     mins = [min(r["distance"] for r in PR.proximity(model, s, bodies, caps, pairs)) for s, _ in case_states(oracle64, model, 67)]

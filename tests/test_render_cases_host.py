@@ -2,7 +2,7 @@
 (camera, frame, state) is DECIDED - few pixels near a change of label or colour, none at all in a tiny frame - and REACHES the path
 it is named for. Poses by the f64 oracle, the scene by qhull on the oracle model's hull arrays (tests/render_ref.py).
 
-What tests/test_gpu_render_edges.py compares on the GPU is only as good as these cases: _compare leaves out the pixels whose
+What tests/test_gpu_render_edges.py compares on the GPU is only as good as these cases: render_compare leaves out the pixels whose
 reference margin is below 1e-4 m, so a case is fair only if that leaves nearly all of them in."""
 import os
 import sys

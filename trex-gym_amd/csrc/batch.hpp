@@ -82,6 +82,7 @@ struct TrexBatch {
   std::vector<double> hull_radius;
   std::vector<int> hull_start, hull_group_start;
   double floor_z = 0;
+  double step_seconds = 0;                // dt * substeps: what an env-step advances time by (the reward terms' Ts)
   int render_nprim = 0;
   DeviceBuf render_prim, render_plane;   // TrexRenderPrim [], float4 []: both or neither
   DeviceBuf render_ids;                  // device copy of the env ids of the last call
@@ -98,6 +99,15 @@ struct TrexBatch {
   // observation channels (trex_batch_set_observation): ONE device allocation laid out as trex::ObsTable says (`table`: its counts
   // and offsets, the host blob dropped); freed by num_channels 0 and with the batch
   struct Observation { trex::ObsTable table; DeviceBuf blob; } observation;
+  // reward terms (trex_batch_set_reward): the term table, ONE device allocation laid out as trex::RewTable says, and the history
+  // of its terms, ONE more, zeroed by every set: previous actions [n][A] | previous qd [n][J] | timers [n][T] | held values
+  // [n][T] | valid flags [n]; both freed by num_terms 0 and with the batch
+  struct Reward {
+    trex::RewTable table;
+    DeviceBuf blob, hist;
+    float *prev_act = nullptr, *prev_qd = nullptr, *timer = nullptr, *held = nullptr;
+    int32_t *valid = nullptr;
+  } reward;
   // fall termination (trex_batch_set_termination): the thresholds in force - a NaN is a criterion that is off - and the batch-owned
   // buffers of the predicate launch, ONE device allocation made by the first enabling call: terminal observations [n][3J], values
   // [n][3], reasons [n], reset mask [n], and done bytes [n] for a trex_batch_step call that passes no done buffer

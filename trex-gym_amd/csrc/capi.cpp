@@ -324,6 +324,7 @@ int trex_batch_create(const TrexModel *model, int num_envs, int device, TrexBatc
   b->arr.max_episode_steps = 0;
   b->arr.domain = 0;
   b->floor_z = h.prm.floor_z;
+  b->step_seconds = h.prm.dt * h.prm.substeps;
   b->hull_xyz = h.hull_xyz; b->hull_radius = h.hull_radius;
   b->hull_start = h.hull_start; b->hull_group_start = h.hull_group_start;
   b->links.body = h.link_body; b->links.tf = h.link_tf;

@@ -1,5 +1,6 @@
 // C-ABI of include/trex_batch.h, the queries: every call that only reads the batch's state and writes caller buffers, and the setters
-// of the tables such calls read (link probes, proximity shapes). Nothing here changes what a step launch does; that is capi.cpp.
+// of the tables such calls read (link probes, proximity shapes) - and the reward terms, which read the state likewise and keep a
+// history of their own in the batch. Nothing here changes what a step launch does; that is capi.cpp.
 #include <cstring>
 #include <type_traits>
 
@@ -10,6 +11,7 @@
 #include "proximity.h"
 #include "raycast.h"
 #include "render.h"
+#include "reward.h"
 #include "step_launch.h"
 #include "termination.h"
 
@@ -497,6 +499,87 @@ int trex_batch_compose_rows(TrexBatch *b, const float *rows_dev, int row_stride,
   trex::tf12(b->links.tf[0], a.base_tf);
   a.body_mask = ot.body_mask | (1u << a.base_body);
   HIP_TRY(trex_launch_observation(a, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+// ---- reward terms (reward.hip)
+int trex_batch_set_reward(TrexBatch *b, const TrexRewardTerm *terms_host, int num_terms) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  trex::RewTable t;
+  if (int c = built([&] { t = trex::build_reward_table(b->links, b->obs_order, b->nb, b->action_cols(), terms_host, num_terms); })) return c;
+  DeviceGuard guard(b->device);
+  DeviceBuf blob, hist;
+  const size_t n = (size_t)b->n, A = (size_t)t.action_cols, J = (size_t)b->nj, T = (size_t)t.terms;
+  if (t.terms > 0) {
+    HIP_TRY(blob.alloc(t.blob.size(), false));
+    HIP_TRY(hipMemcpy(blob.p, t.blob.data(), blob.bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hist.alloc(n * (A + J + 2 * T + 1) * sizeof(float), true));
+  }
+  HIP_TRY(hipDeviceSynchronize());   // (no launch still reads the table this one replaces; the new one is in place on every stream)
+  t.blob = {};
+  TrexBatch::Reward &r = b->reward;
+  r.blob = std::move(blob);   // (frees the old table and its history)
+  r.hist = std::move(hist);
+  r.table = std::move(t);
+  r.prev_act = r.prev_qd = r.timer = r.held = nullptr; r.valid = nullptr;
+  if (r.hist) {
+    r.prev_act = r.hist.as<float>();
+    r.prev_qd = r.prev_act + n * A; r.timer = r.prev_qd + n * J; r.held = r.timer + n * T;
+    r.valid = (int32_t *)(r.held + n * T);
+  }
+  return TREX_OK;
+}
+
+int trex_batch_reward_terms(const TrexBatch *b) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  return b->reward.table.terms;
+}
+
+int trex_batch_compose_reward(TrexBatch *b, float *rows_dev, int row_stride, const float *actions_dev, const float *command_dev,
+                              float *terms_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  const std::string me = "trex_batch_compose_reward: ";
+  const TrexBatch::Reward &r = b->reward;
+  const trex::RewTable &rt = r.table;
+  if (rt.terms < 1) return fail(TREX_E_INVALID, me + "no terms are set (trex_batch_set_reward)");
+  if (!rows_dev) return fail(TREX_E_INVALID, me + "rows is null");
+  const int nobs = 3 * b->nj, tail = b->pen_in_rows ? 5 : 2;
+  if (row_stride < nobs + tail) return fail(TREX_E_INVALID, me + "row_stride < 3J + 2 (3J + 5 with penalties in rows)");
+  if (rt.contact && !b->sens_on) return fail(TREX_E_INVALID, me + "a contact term is set and the contact sensor is off (trex_batch_set_contact_sensor)");
+  if (rt.command && !command_dev) return fail(TREX_E_INVALID, me + "a tracking term is set and command is null");
+  if (rt.actions && !actions_dev) return fail(TREX_E_INVALID, me + "ACTION_RATE is set and actions is null");
+  if (rt.actions && rt.action_cols != b->action_cols())
+    return fail(TREX_E_INVALID, me + "the action rows are " + std::to_string(b->action_cols()) + " wide, ACTION_RATE was set with " +
+                                    std::to_string(rt.action_cols) + " (set the terms again)");
+  const size_t n = (size_t)b->n;
+  DeviceGuard guard(b->device);
+  BUF_TRY(rows_dev, ((n - 1) * row_stride + nobs + tail) * sizeof(float), "trex_batch_compose_reward: rows");
+  if (rt.actions) BUF_TRY(actions_dev, n * rt.action_cols * sizeof(float), "trex_batch_compose_reward: actions");
+  if (rt.command) BUF_TRY(command_dev, n * 3 * sizeof(float), "trex_batch_compose_reward: command");
+  BUF_TRY(terms_dev, n * rt.terms * sizeof(float), "trex_batch_compose_reward: terms");
+  TrexRewArgs a = query_args<TrexRewArgs>(b);
+  const char *blob = r.blob.as<char>();
+  a.term = (const TrexRewTerm *)blob; a.joint_body = (const int32_t *)(blob + rt.o_joint);
+  a.rows = rows_dev; a.actions = rt.actions ? actions_dev : nullptr; a.command = rt.command ? command_dev : nullptr;
+  a.sens = rt.contact ? b->sens.as<float>() : nullptr;
+  a.terms_out = terms_dev;
+  a.prev_act = r.prev_act; a.prev_qd = r.prev_qd; a.timer = r.timer; a.held = r.held; a.valid = r.valid;
+  a.D = 6 + b->nj; a.nj = b->nj; a.num_terms = rt.terms; a.row_stride = row_stride; a.act_cols = rt.action_cols;
+  a.Ts = (float)b->step_seconds;
+  a.base_body = b->links.body[0];   // URDF link 0's frame in its body
+  trex::tf12(b->links.tf[0], a.base_tf);
+  a.body_mask = rt.body_mask | (1u << a.base_body);
+  HIP_TRY(trex_launch_reward(a, (hipStream_t)stream));
+  return TREX_OK;
+}
+
+int trex_batch_reward_reset(TrexBatch *b, const uint8_t *mask_dev, void *stream) {
+  if (check_batch(b)) return TREX_E_INVALID;
+  const TrexBatch::Reward &r = b->reward;
+  if (r.table.terms < 1) return fail(TREX_E_INVALID, "trex_batch_reward_reset: no terms are set (trex_batch_set_reward)");
+  DeviceGuard guard(b->device);
+  BUF_TRY(mask_dev, (size_t)b->n, "trex_batch_reward_reset: mask");
+  HIP_TRY(trex_launch_reward_reset(mask_dev, b->n, r.table.terms, r.timer, r.held, r.valid, (hipStream_t)stream));
   return TREX_OK;
 }
 

@@ -308,6 +308,71 @@ ObsTable build_obs_table(const Links &links, int nj, int action_cols, const Trex
   return t;
 }
 
+RewTable build_reward_table(const Links &links, const std::vector<int> &obs_order, int nb, int action_cols, const TrexRewardTerm *terms,
+                            int num_terms) {
+  const std::string me = "trex_batch_set_reward: ";
+  if (num_terms < 0 || num_terms > TREX_REW_MAXTERMS)
+    throw Refusal(me + "num_terms " + std::to_string(num_terms) + " outside [0, " + std::to_string(TREX_REW_MAXTERMS) + "]");
+  RewTable t;
+  if (num_terms == 0) return t;
+  if (!terms) throw Refusal(me + "null argument");
+  const int nj = (int)obs_order.size(), num_links = (int)links.body.size();
+  auto low_bits = [](int n) { return n >= 32 ? 0xffffffffu : ((1u << n) - 1u); };
+  std::vector<TrexRewTerm> out((size_t)num_terms);
+  for (int k = 0; k < num_terms; k++) {
+    const TrexRewardTerm &c = terms[k];
+    const std::string ck = me + "term " + std::to_string(k) + ": ";
+    if (c.kind < 0 || c.kind >= TREX_REW_KINDS) throw Refusal(ck + "unknown kind " + std::to_string(c.kind));
+    for (int i = 0; i < 3; i++)
+      if (!std::isfinite(c.local_xyz[i])) throw Refusal(ck + "local_xyz is not finite");
+    if (!std::isfinite(c.weight) || !std::isfinite(c.p0) || !std::isfinite(c.p1)) throw Refusal(ck + "weight, p0 or p1 is not finite");
+    TrexRewTerm &o = out[k];
+    std::memset(&o, 0, sizeof o);
+    o.kind = c.kind; o.weight = c.weight; o.p0 = c.p0; o.p1 = c.p1;
+    o.tf[0] = o.tf[4] = o.tf[8] = 1.0f;
+    switch (c.kind) {
+      case TREX_REW_TRACK_LIN_VEL: case TREX_REW_TRACK_ANG_VEL:
+        if (!(c.p0 > 0.f)) throw Refusal(ck + "a tracking term needs p0 > 0");
+        t.command = true;
+        break;
+      case TREX_REW_POINT_HEIGHT: case TREX_REW_FOOT_AIR_TIME: case TREX_REW_FOOT_SLIP: {
+        if (c.link < 0 || c.link >= num_links)
+          throw Refusal(ck + "link " + std::to_string(c.link) + " out of range [0, " + std::to_string(num_links) + ")");
+        const double x[3] = {c.local_xyz[0], c.local_xyz[1], c.local_xyz[2]};
+        const LinkPoint p = link_point(links, c.link, x);
+        tf12(links.tf[c.link], o.tf);
+        o.body = p.body;
+        std::memcpy(o.point, p.point, sizeof p.point);
+        if (c.kind != TREX_REW_FOOT_AIR_TIME) t.body_mask |= 1u << p.body;
+        if (c.kind != TREX_REW_POINT_HEIGHT) t.contact = true;
+        break;
+      }
+      case TREX_REW_JOINT_LIMIT:
+        if (!(c.p0 > 0.f && c.p0 <= 1.f)) throw Refusal(ck + "JOINT_LIMIT needs 0 < p0 <= 1");
+        [[fallthrough]];
+      case TREX_REW_TORQUE: case TREX_REW_JOINT_VEL: case TREX_REW_JOINT_ACC: case TREX_REW_POWER: case TREX_REW_JOINT_POSE:
+        if (c.mask & ~low_bits(nj)) throw Refusal(ck + "a mask bit at or beyond J = " + std::to_string(nj));
+        o.mask = c.mask ? c.mask : low_bits(nj);
+        break;
+      case TREX_REW_CONTACT_COUNT:
+        if (c.mask & ~low_bits(nb)) throw Refusal(ck + "a mask bit at or beyond the body count " + std::to_string(nb));
+        o.mask = c.mask;
+        t.contact = true;
+        break;
+      case TREX_REW_ACTION_RATE: t.actions = true; break;
+      default: break;
+    }
+  }
+  int32_t joint_body[TREX_TL] = {};
+  for (int j = 0; j < nj && j < TREX_TL; j++) joint_body[j] = obs_order[j];
+  t.terms = num_terms; t.action_cols = action_cols;
+  t.o_joint = (out.size() * sizeof(TrexRewTerm) + 15) & ~(size_t)15;
+  t.blob.assign(t.o_joint + sizeof joint_body, 0);
+  std::memcpy(t.blob.data(), out.data(), out.size() * sizeof(TrexRewTerm));
+  std::memcpy(t.blob.data() + t.o_joint, joint_body, sizeof joint_body);
+  return t;
+}
+
 CameraBasis camera_basis(const TrexCamera &cam, int width, int height) {
   const float cv[] = {cam.distance, cam.yaw_deg, cam.pitch_deg, cam.fov_deg, cam.near_z, cam.far_z, cam.target[0], cam.target[1], cam.target[2]};
   for (float x : cv)

@@ -1,5 +1,5 @@
 // The tables the kernels read, as pure host arithmetic: everything the C-ABI computes between its argument checks and its HIP calls.
-// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h and include/trex_batch.h, and nothing of HIP; it makes
+// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h and include/trex_batch.h, and nothing of HIP; it makes
 // no HIP call and knows no batch. It builds with plain g++ -std=c++17, as model.cpp does, so that tests/host/tables_harness.cpp runs
 // it under the sanitizers on a machine without a GPU. A refusal is a thrown Refusal whose text is the C-ABI's message, whole.
 #pragma once
@@ -17,6 +17,7 @@ struct float4;
 #include "model.hpp"
 #include "observation_limits.h"
 #include "proximity_limits.h"
+#include "reward_limits.h"
 
 namespace trex {
 
@@ -75,6 +76,21 @@ struct ObsTable {
   std::vector<char> blob;
 };
 ObsTable build_obs_table(const Links &links, int nj, int action_cols, const TrexObsChannel *channels, int num_channels);
+
+// trex_batch_set_reward: ONE blob - the terms [T] as TrexRewTerm at 0, then at o_joint, a multiple of 16 bytes, the body lane of
+// every joint in observation order [32] as int32 (what the kernel's lane j reads the limits and the start angle of joint j by).
+// obs_order: observation slot -> body; nb: the body count; action_cols: the width of the batch's action rows (what ACTION_RATE
+// sums over). num_terms 0 gives the empty table.
+struct RewTable {
+  int terms = 0;                        // T
+  int action_cols = 0;                  // the action width the table was built with
+  bool contact = false, actions = false, command = false;   // a contact kind / ACTION_RATE / a tracking term is set
+  uint32_t body_mask = 0u;              // bit b: a term names body b (the body of URDF link 0 not included)
+  size_t o_joint = 0;
+  std::vector<char> blob;
+};
+RewTable build_reward_table(const Links &links, const std::vector<int> &obs_order, int nb, int action_cols, const TrexRewardTerm *terms,
+                            int num_terms);
 
 // trex_batch_render: the camera of include/trex_batch.h, checked, as the renderer's basis
 struct CameraBasis { float offset[3], fwd[3], right[3], up[3], tan_x, tan_y; };

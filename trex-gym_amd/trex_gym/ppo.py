@@ -181,6 +181,14 @@ class PPO:
         self.b_adv = torch.empty(T, n, device=self.dev)
         self.b_ret = torch.empty(T, n, device=self.dev)
         self._raw_sum = 0.0
+        # reward terms (TrexVecEnv(rewards=...)): the weighted value of every term summed over the rollout, on the device
+        rt = getattr(env, "reward_terms", None)
+        self.term_names = list(getattr(env, "reward_names", [])) if rt is not None else []
+        # (the env's compose launch writes each step's breakdown straight into b_terms[t]: no launch per step is added; ONE sum per
+        # rollout folds them)
+        self.b_terms = torch.zeros(nsteps, n, rt.shape[1], device=self.dev) if rt is not None else None
+        self.term_sum = torch.zeros(rt.shape[1], device=self.dev) if rt is not None else None
+        self.mean_terms = None
         env.reset_tensor()
         self.kern.observe(env.rows, with_reward=False)           # VecNormalize.reset: the statistics see the first obs
 
@@ -199,8 +207,12 @@ class PPO:
         for t in range(T):
             k.act(th, env.rows, self.noise[t], self.actions, self.b_obs[t], self.b_act[t], self.b_logp[t], self.b_val[t],
                   clip_obs=self.clip_obs)
+            if self.b_terms is not None:
+                env.reward_terms = self.b_terms[t]
             env.step_tensor(self.actions)       # the env clips to the joint limits (trex_env.py:147)
             k.observe(env.rows, True, self.gamma, self.b_rew[t], self.b_done[t], self.b_scale[t:t + 1])
+        if self.b_terms is not None:
+            torch.sum(self.b_terms, dim=(0, 1), out=self.term_sum)
         k.act(th, env.rows, None, None, value_out=self.b_val[T], clip_obs=self.clip_obs, value_only=True)
         k.gae(self.b_rew, self.b_scale, self.b_done, self.b_val, self.b_adv, self.b_ret, self.gamma, self.lam, self.clip_rew)
 
@@ -224,6 +236,8 @@ class PPO:
         flat = lambda x: x.reshape(T * n, *x.shape[2:])
         raw = self.kern.get_stats()["raw_reward_sum"]            # (the one host read-back per rollout)
         mean_rew, self._raw_sum = (raw - self._raw_sum) / (T * n), raw
+        if self.term_sum is not None:                            # (behind that read-back: the stream is drained, one small copy)
+            self.mean_terms = [x / (T * n) for x in self.term_sum.tolist()]
         return (flat(self.b_obs), flat(self.b_act), flat(self.b_logp), flat(self.b_val[:T]), flat(self.b_adv), flat(self.b_ret),
                 mean_rew)
 
@@ -359,4 +373,8 @@ class PPO:
                 log("it %3d  env-steps %9d  mean reward/step %12.4f  pg %.4f  vf %.4f  ent %.3f  %.0f env-steps/s"
                     % (it, info["env_steps"], info["mean_step_reward"], info["policy_loss"], info["value_loss"],
                        info["entropy"], info["env_steps_per_s"]))
+            if self.mean_terms is not None:
+                info["reward_terms"] = dict(zip(self.term_names, self.mean_terms))
+                if log:
+                    log("        reward terms/step  " + "  ".join("%s %.4g" % kv for kv in info["reward_terms"].items()))
         return history

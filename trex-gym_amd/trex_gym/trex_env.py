@@ -26,7 +26,7 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
 
     def __init__(self, urdf_path=None, action_repeat=1, distance_weight=1.0, energy_weight=0.005,
                  drift_weight=0.002, render=False, device=None, contact_sensor=False, control_mode=None,
-                 variable_stiffness=False, kp_max=1.0, terminate=None):
+                 variable_stiffness=False, kp_max=1.0, terminate=None, rewards=None, command=None):
         if render:   # (the reference's render=True opens pybullet's GUI; rgb_array frames need no flag: render())
             raise NotImplementedError("render=True asks for a GUI, which this env has not; render('rgb_array') draws frames")
         self._time_step = 0.01 / NUM_SUBSTEPS
@@ -49,7 +49,11 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
                                distance_weight=distance_weight, energy_weight=energy_weight,
                                drift_weight=drift_weight,
                                starting_configuration=self._starting_configuration, control_mode=control_mode,
-                               variable_stiffness=variable_stiffness, kp_max=kp_max, terminate=terminate)
+                               variable_stiffness=variable_stiffness, kp_max=kp_max, terminate=terminate, rewards=rewards)
+        if command is not None and self._vec.commands is None:
+            raise ValueError("command: there are no reward terms to track it (rewards=[...])")
+        if command is not None:   # (vx, vy, yaw rate) the tracking terms of `rewards` (trex_gym.rewards) compare the base's velocity with
+            self._vec.commands[0] = torch.tensor([float(x) for x in command], device=self._vec.device)
         self._terminated = False                 # the last step ended the episode by a fall (terminate=dict(...): TrexVecEnv.set_termination)
         self.model = trex_robot.TrexRobot(self._vec, 0)
         self._ray_links = None
@@ -96,6 +100,8 @@ class TrexBulletEnv(spaces.Env):     # gym.Env where gym is importable (trex_env
                 self._observation = self._vec.terminal_obs[0].cpu().numpy().astype(np.float64).tolist()
                 info = {"termination": reason}
                 self._env_step_counter = 0
+        if self._vec.reward_terms is not None:   # rewards=[...] (trex_gym.rewards): the breakdown of this step's reward, weight x value per term
+            info["reward_terms"] = dict(zip(self._vec.reward_names, self._vec.reward_terms[0].cpu().numpy().astype(np.float64).tolist()))
         return self._observation, self.compute_reward(), self.should_terminate(), info
 
     def render(self, mode='rgb_array', close=False):

@@ -24,7 +24,7 @@ _URDF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ass
 
 def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0, push_force=0.0, push_interval=100,
                       push_duration=5, push_probability=1.0, seed=0, control_mode=None, variable_stiffness=False,
-                      gain_scale=0.0, terminate=None, observations=None):   # (weights of trex_train.py:66)
+                      gain_scale=0.0, terminate=None, observations=None, rewards=None, command=None):   # (weights of trex_train.py:66)
     # control_mode: what the joints' actions mean (position / velocity / torque: J-wide, through the trainer unchanged). The
     # 2J-wide stiffness action space is wider than the policy kernel's act_dim <= 32: refused here, not deep in a launch
     check_action_space(control_mode, variable_stiffness)
@@ -42,6 +42,23 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
     elif observations is not None:
         from . import observations as O
         observations = O.from_tuples(observations)
+    # rewards: a preset's name ("locomotion") or a specification of trex_gym.rewards (a checkpoint's): the reward column composed
+    # on the device from its terms; command: (vx, vy, yaw rate) for every env, and - with observations - three more observation
+    # columns, so that the policy sees what it is rewarded for; None = the step's own reward
+    if isinstance(rewards, str):
+        from . import _capi, rewards as R
+        if rewards not in R.PRESETS:
+            raise ValueError("--rewards: expected one of %s, got %r" % (", ".join(sorted(R.PRESETS)), rewards))
+        rewards = R.PRESETS[rewards](_capi.Model(_URDF_PATH), device)
+    elif rewards is not None:
+        from . import rewards as R
+        rewards = R.from_tuples(rewards)
+    external = None
+    if rewards is not None and observations is not None:
+        from . import observations as O
+        observations = list(observations) + O.external(3)
+        external = lambda env: env.commands
+    command_columns = external is not None
     pushes = None
     if push_force > 0:
         dev = torch.device(device)
@@ -50,7 +67,13 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
                               duration=push_duration, generator=gen, device=dev)
     env = TrexVecEnv(num_envs, urdf_path=_URDF_PATH, device=device, distance_weight=2e2, energy_weight=1e-6,
                      drift_weight=1.0, max_episode_steps=max_episode_steps, params=params, pushes=pushes, control_mode=control_mode,
-                     terminate=terminate, observations=observations)   # terminate: TrexVecEnv.set_termination's arguments - a fall ends the episode, on the device
+                     terminate=terminate, observations=observations, external=external, rewards=rewards)   # terminate: TrexVecEnv.set_termination's arguments - a fall ends the episode, on the device
+    env.command_columns = command_columns   # the last channel is the commands': a checkpoint stores the channels without it
+    if command is not None:
+        if rewards is None:
+            raise ValueError("--command: there are no reward terms to track it (--rewards)")
+        env.commands[:] = torch.tensor([float(x) for x in command], device=env.device)
+    env.command = None if command is None else [float(x) for x in command]
     if gain_scale > 0:   # every episode with motor gains and strength scaled by 1 +- gain_scale per env (RandomGains)
         dev = torch.device(device)
         r = (1.0 - gain_scale, 1.0 + gain_scale)
@@ -96,8 +119,18 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
         torch.save({"theta": agent.policy.theta.detach().clone(), "obs_mean": torch.tensor(st["obs_mean"]),
                     "obs_var": torch.tensor(st["obs_var"]), "obs_count": torch.tensor(float(st["obs_count"])),
                     "ret_var": torch.tensor(float(st["ret_var"])),
-                    "observations": getattr(env, "observations", None)}, save_path)   # (the channels: --play rebuilds the same row)
+                    "observations": _own_channels(env), "rewards": getattr(env, "rewards", None),
+                    "command": getattr(env, "command", None)}, save_path)   # (the channels and terms: --play rebuilds the same row)
     return agent, hist
+
+
+def _own_channels(env):
+    """the env's observation channels as a checkpoint stores them: without the three command columns build_environment adds
+    behind them when rewards are set (env.command_columns says that it did) (it adds them again on loading)"""
+    obs = getattr(env, "observations", None)
+    if obs is not None and getattr(env, "command_columns", False):
+        obs = obs[:-1]
+    return obs
 
 
 def _png_writer():
@@ -156,7 +189,8 @@ def load_agent(load_path, num_envs=1, device="cuda:0", max_episode_steps=1000):
     """trex_train.py:75-110 (replay): rebuild the policy from a file written by train(save_path=...) - the flat
     parameter vector and VecNormalize's statistics."""
     ck = torch.load(load_path, map_location=device, weights_only=True)
-    env = build_environment(num_envs, device=device, max_episode_steps=max_episode_steps, observations=ck.get("observations"))
+    env = build_environment(num_envs, device=device, max_episode_steps=max_episode_steps, observations=ck.get("observations"),
+                            rewards=ck.get("rewards"), command=ck.get("command"))
     agent = PPO(env, nsteps=1, nminibatches=1, noptepochs=1)
     with torch.no_grad():
         agent.policy.theta.copy_(ck["theta"])
@@ -202,6 +236,11 @@ def parse_args(argv=None):
     ap.add_argument("--observations", choices=["locomotion"], default=None,
                     help="extra observation columns composed on the device; locomotion: base tilt, velocity, height, the feet's contact "
                          "force and position (18 columns; default: the reference's 75 alone)")
+    ap.add_argument("--rewards", choices=["locomotion"], default=None,
+                    help="reward terms composed on the device; locomotion: velocity tracking, a quiet upright base, small torques, "
+                         "smooth actions, swinging feet that do not slide, nothing but the feet on the floor (default: the step's reward)")
+    ap.add_argument("--command", type=float, nargs=3, default=None, metavar=("VX", "VY", "WZ"),
+                    help="with --rewards: the velocity every env is to track - forward, sideways (m/s, base axes), yaw rate (rad/s)")
     ap.add_argument("--fall_penalty", type=float, default=0.0, help="taken from the reward of the step in which an episode ends by a fall")
     args = ap.parse_args(argv)
     if args.variable_stiffness:
@@ -209,6 +248,8 @@ def parse_args(argv=None):
             check_action_space(args.control_mode, True)
         except ValueError as e:
             ap.error(str(e))
+    if args.command is not None and args.rewards is None:
+        ap.error("--command needs --rewards")
     if not 0.0 <= args.gain_scale < 1.0:
         ap.error("--gain_scale must lie in [0, 1)")
     if args.push_force > 0 and args.graphs:   # (the pushes are drawn per step on the host's step count: not in a replayed graph)
@@ -233,7 +274,7 @@ def environment_from_args(args):
     env = build_environment(args.num_envs, max_episode_steps=args.max_episode_steps, warmstart=args.warmstart,
                             push_force=args.push_force, push_interval=args.push_interval, push_duration=args.push_duration,
                             seed=args.random_seed, control_mode=None if args.control_mode == "position" else args.control_mode,
-                            gain_scale=args.gain_scale, observations=args.observations)
+                            gain_scale=args.gain_scale, observations=args.observations, rewards=args.rewards, command=args.command)
     if terminate is not None:   # (set on the built env: 'auto' needs its model - every body that does not stand on the floor at the start)
         if terminate["keep_clear"] == ["auto"]:
             from .termination import fall_bodies

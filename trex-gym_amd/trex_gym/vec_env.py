@@ -12,7 +12,8 @@ inside the step launch itself (trex_batch_set_episode_limit).
 Outputs live in ONE row block `rows` [n, 3J+2] f32 = obs | reward | done (written by the kernel in that layout:
 trex_batch_step_rows; with penalties_in_rows [n, 3J+5]: the three penalties behind done); `obs`, `rew`, `done_f` are views
 into it; `done` holds the flags as bool, `penalties` [n, 3] the three reward terms. With `observations=` (trex_gym.observations)
-the block is [n, 3J + E + 2]: E more observation columns, composed on the device by one more launch per step and reset.
+the block is [n, 3J + E + 2]: E more observation columns, composed on the device by one more launch per step and reset. With `rewards=` (trex_gym.rewards) the reward column is
+composed on the device from a specification of terms, by one more launch per step: `reward_terms` [n, T] holds the breakdown.
 
 Multi-GPU: one process per GPU, env ids sharded by contiguous range (trex_gym.sharding); the only
 exchange is the all-gather of that row block (all_gather_rows / all_gather_rows_pipelined).
@@ -42,7 +43,7 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
                  max_episode_steps=None, starting_configuration=None, params=None,
                  rank=0, world_size=1, process_group=None, collision="hulls", primitive_max_radius=0.2, row_buffers=1,
                  penalties_in_rows=False, pushes=None, control_mode=None, variable_stiffness=False,
-                 kp_max=actuators.DEFAULT_KP_MAX, terminate=None, observations=None, external=None):
+                 kp_max=actuators.DEFAULT_KP_MAX, terminate=None, observations=None, external=None, rewards=None):
         """num_envs is the GLOBAL env count; this process owns sharding.shard_range(num_envs, rank, world_size).
         row_buffers=2: successive steps write two row blocks in turn (`rows`, `obs`, `rew`, `done_f` always name the
         block of the LAST step), which lets the pipelined all-gather read a block in place.
@@ -58,7 +59,13 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         (trex_batch_compose_rows). `rows` is then [n, 3J + E + 2 (or 5)] = obs | reward | done, `obs` its first D' = 3J + E
         columns, and observation_space is D' wide. None (default): nothing changes - not a launch, not a byte.
         external: with observations.external(k) channels, their columns: a tensor [n, X] read at every compose, or a callable
-        env -> such a tensor, called after every step and reset."""
+        env -> such a tensor, called after every step and reset.
+        rewards: a list of trex_gym.rewards terms (e.g. rewards.locomotion(model)): the reward column becomes the sum of weight *
+        value over the terms, evaluated on the device at the row's own instant by one more launch per step
+        (trex_batch_compose_reward) that runs after the step and before the channels are composed. `commands` [n, 3] (vx, vy in
+        base axes, yaw rate; zeros) is a device tensor to write in place, `reward_terms` [n, T] the weighted value of every term
+        at the last step (a tensor the caller may replace by another [n, T] block, e.g. a slice of a rollout buffer), `reward_names` their names, `reward_api` the batch's calls (reward_capi.BatchRewards). The commands join the observations through
+        observations.external(3) with external=lambda env: env.commands. None (default): nothing changes - not a launch, not a byte."""
         self.global_num_envs = int(num_envs)
         self.rank, self.world_size, self.process_group = int(rank), int(world_size), process_group
         self.env_lo, self.env_hi = sharding.shard_range(self.global_num_envs, self.rank, self.world_size)
@@ -110,12 +117,17 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         # observation channels: the step keeps writing a [n, 3J + tail] block of its own (_step_rows); the composed rows are the
         # env's row blocks, so that everything that reads `rows` - the trainer in place, the gathers - reads the extended row
         self.observations, self.obs_dim, self._step_rows, self._external = None, 3 * J, None, external
+        self.rewards, self.reward_names, self.reward_terms, self.reward_api = None, [], None, None
+        self.commands = None                    # [n, 3] with rewards: made by _set_rewards
+        self._rew_actions = False
         self.collision = collision
         self._init_queries()                    # the link table and the caches of the read-only queries (vec_queries.py)
         if observations is not None and len(observations):
             self._set_observations(observations)
         elif external is not None:
             raise ValueError("external: there is no observations.external(k) channel to take it")
+        if rewards is not None and len(rewards):
+            self._set_rewards(rewards)
         self._row_k = 0
         self._point_at(0)
         self.done = torch.zeros(n, dtype=torch.bool, device=self.device)   # the same flags as bytes (written by the kernel too)
@@ -164,6 +176,24 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         ext = self._external(self) if callable(self._external) else self._external
         self.batch.compose_rows(self._step_rows, self.rows, actions, None if ext is None else self._dev(ext))
 
+    # ---- reward terms (trex_batch_set_reward / trex_batch_compose_reward; trex_gym.rewards builds specifications)
+    def _set_rewards(self, spec):
+        from . import reward_capi, rewards as R
+        L = self._links
+        names = list(self.model.joint_names)
+        terms, contact, _, self._rew_actions = R.resolve(spec, L.index, lambda j: names.index(j) if isinstance(j, str) else int(j),
+                                                         lambda l: int(L.link_body[l]))
+        if contact:
+            self.batch.set_contact_sensor(True)
+        self.reward_api = reward_capi.BatchRewards(self.batch)    # (trex_batch_set_reward and its kin: include/trex_reward.h)
+        self.reward_api.set_reward(terms)
+        self.rewards, self.reward_names = R.as_tuples(spec), R.names(spec)
+        self.reward_terms = torch.zeros(self.num_envs, len(terms), device=self.device)
+        self.commands = torch.zeros(self.num_envs, 3, device=self.device)
+
+    def _compose_reward(self, rows, actions):
+        self.reward_api.compose_reward(rows, actions if self._rew_actions else None, self.commands, self.reward_terms)
+
     def _dev(self, t, dtype=torch.float32):
         """t as a contiguous `dtype` tensor on the env's device: t ITSELF where it is one already - no copy, no launch."""
         if t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
@@ -178,6 +208,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self.batch.reset_rows(self.rows if self._step_rows is None else self._step_rows, mask)
         if self._step_rows is not None:
             self._compose(None)
+        if self.rewards is not None:            # the envs that were reset have no previous step: their reward history starts afresh
+            self.reward_api.reward_reset(mask)
         if self.gains is not None:              # the envs that were reset draw new motor gains
             self.set_motor_gains(**self.gains.draw(mask))
         if mask is None:
@@ -212,10 +244,16 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
             self._point_at(1 - self._row_k)
         # (with set_termination the call is three launches: step, fall predicate, reset of the fallen - done = 1, the reward of
         # the finished step less the penalty, observation of the new episode)
+        # (reward terms: one more launch behind the step call, on the rows it wrote - before the channels' compose, which carries
+        # the composed reward along in the tail)
         if self._step_rows is None:
             self.batch.step_rows(actions, self.rows, self._penalties, done=self.done)   # (None: the penalties ride in the row block)
+            if self.rewards is not None:
+                self._compose_reward(self.rows, actions)
         else:   # (observation channels: one more launch, after the resets of the step call - the row of the new episode's state)
             self.batch.step_rows(actions, self._step_rows, self._penalties, done=self.done)
+            if self.rewards is not None:
+                self._compose_reward(self._step_rows, actions)
             self._compose(actions)
         if self._term_on and self.gains is not None:   # the envs that fell start their episode with new motor gains
             self.set_motor_gains(**self.gains.draw(self.termination_reason != 0))
@@ -225,7 +263,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         """Open-loop rollout: actions [S, n, J] f32 on device -> rows [S, n, 3J+2] (obs | reward | done of every step), S
         env-steps in ONE launch (trex_batch_step_many; bitwise S calls of step_tensor). `rows`, `obs`, `rew`, `done_f`
         and `done` then hold the last step. sharding.split_rows(rows[s]) cuts a step's block into the three.
-        ValueError with observations: an open-loop launch has no compose between its steps."""
+        ValueError with observations or rewards: an open-loop launch has no compose between its steps."""
+        if self.rewards is not None:
+            raise ValueError("step_many_tensor: not with rewards - the open-loop launch has no per-step compose of the reward terms")
         if self._step_rows is not None:
             raise ValueError("step_many_tensor: not with observations - the open-loop launch has no per-step compose of the channels")
         actions = self._dev(actions)

@@ -725,5 +725,8 @@ int trex_batch_time_steps(TrexBatch *batch, const float *actions_dev, float *obs
 /* The reward terms of a batch - a specification of terms, one launch per step that composes them into the reward column of
  * the rows a step call wrote - are declared in a header of their own, with the conventions above: */
 #include "trex_reward.h"
+/* So is the motion clip of a batch - reference poses that depend on time, tracking terms against them, and resets to an instant of
+ * the clip: */
+#include "trex_motion.h"
 
 #endif /* TREX_BATCH_H */

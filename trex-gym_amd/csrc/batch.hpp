@@ -108,6 +108,20 @@ struct TrexBatch {
     float *prev_act = nullptr, *prev_qd = nullptr, *timer = nullptr, *held = nullptr;
     int32_t *valid = nullptr;
   } reward;
+  // motion clip (trex_batch_set_motion, include/trex_motion.h): the clip table, ONE device allocation laid out as
+  // trex::MotionTable says (`table`: its counts and constants, the host rows dropped); the clocks, ONE more: start times [n] f32 |
+  // step counts [n] i32, zeroed by every set; the terms of trex_batch_set_motion_reward, host side - they travel in the launch
+  // arguments - and their held values [n][T]. q_lower, q_upper: the joint limits by body, what the builder checks a clip against.
+  // probe_set, probes: the end effectors' set and its size when the clip was set (-1, 0: none)
+  struct Motion {
+    trex::MotionTable table;
+    DeviceBuf blob, clock, held;
+    std::vector<TrexMotTerm> terms;
+    float step_weight = 1.f;
+    int probe_set = -1, probes = 0;
+    std::vector<double> q_lower, q_upper;
+    float *t0() const { return clock.as<float>(); }
+  } motion;
   // fall termination (trex_batch_set_termination): the thresholds in force - a NaN is a criterion that is off - and the batch-owned
   // buffers of the predicate launch, ONE device allocation made by the first enabling call: terminal observations [n][3J], values
   // [n][3], reasons [n], reset mask [n], and done bytes [n] for a trex_batch_step call that passes no done buffer

@@ -293,6 +293,7 @@ int trex_batch_create(const TrexModel *model, int num_envs, int device, TrexBatc
   auto b = std::make_unique<TrexBatch>();   // (an error return below frees, through the DeviceBufs, what was allocated so far)
   b->n = num_envs; b->device = device; b->nb = model->host.nb; b->nj = b->nb - 1;
   b->obs_order = model->host.obs_order; b->parent = model->host.parent;
+  b->motion.q_lower = model->host.q_lower; b->motion.q_upper = model->host.q_upper;
   const trex::HostModel &h = model->host;
   hipError_t r = hipSuccess;
   // zeroed device memory owned by the batch, `data` (if any) copied in

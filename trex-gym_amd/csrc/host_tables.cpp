@@ -373,6 +373,110 @@ RewTable build_reward_table(const Links &links, const std::vector<int> &obs_orde
   return t;
 }
 
+MotionTable build_motion_table(const std::vector<double> &q_lower, const std::vector<double> &q_upper, const std::vector<int> &obs_order,
+                               const double *frames, const double *velocities, int num_frames, double frame_dt, int loop) {
+  const std::string me = "trex_batch_set_motion: ";
+  MotionTable t;
+  if (num_frames == 0) return t;
+  if (num_frames < 2 || num_frames > TREX_MOT_MAXFRAMES)
+    throw Refusal(me + "num_frames " + std::to_string(num_frames) + " outside [2, " + std::to_string(TREX_MOT_MAXFRAMES) + "] (0 clears)");
+  if (!frames) throw Refusal(me + "null argument");
+  if (!std::isfinite(frame_dt) || !(frame_dt > 0.0) || !((float)frame_dt > 0.f) || !std::isfinite((float)(1.0 / (double)(float)frame_dt)))
+    throw Refusal(me + "frame_dt must be positive and finite");
+  const int F = num_frames, J = (int)obs_order.size(), wf = 7 + J, wv = 6 + J;
+  for (size_t i = 0; i < (size_t)F * wf; i++)
+    if (!std::isfinite(frames[i])) throw Refusal(me + "frame " + std::to_string(i / wf) + ": a value is not finite");
+  if (velocities)
+    for (size_t i = 0; i < (size_t)F * wv; i++)
+      if (!std::isfinite(velocities[i])) throw Refusal(me + "frame " + std::to_string(i / wv) + ": a velocity is not finite");
+  // the quaternions: unit length, one hemisphere frame after frame
+  std::vector<std::array<double, 4>> quat((size_t)F);
+  for (int k = 0; k < F; k++) {
+    const double *q = frames + (size_t)k * wf + 3;
+    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (!(n > 0.0) || !std::isfinite(n)) throw Refusal(me + "frame " + std::to_string(k) + ": a quaternion of norm 0");
+    double sign = 1.0;
+    if (k > 0) {
+      const std::array<double, 4> &p = quat[k - 1];
+      if ((q[0] * p[0] + q[1] * p[1] + q[2] * p[2] + q[3] * p[3]) < 0.0) sign = -1.0;
+    }
+    for (int c = 0; c < 4; c++) quat[k][c] = sign * q[c] / n;
+  }
+  for (int k = 0; k < F; k++)
+    for (int j = 0; j < J; j++) {
+      const double q = frames[(size_t)k * wf + 7 + j], lo = q_lower[obs_order[j]], hi = q_upper[obs_order[j]];
+      if (q < lo - 1e-6 || q > hi + 1e-6)
+        throw Refusal(me + "frame " + std::to_string(k) + ": joint " + std::to_string(j) + " outside its limits");
+    }
+  t.frames = F; t.nj = J; t.stride = TREX_MOT_STRIDE(J); t.loop = loop != 0;
+  t.frame_dt = (float)frame_dt;
+  t.inv_dt = (float)(1.0 / (double)t.frame_dt);
+  t.duration = (float)((double)(F - 1) * (double)t.frame_dt);
+  t.inv_duration = (float)(1.0 / (double)t.duration);
+  const double disp[3] = {frames[(size_t)(F - 1) * wf] - frames[0], frames[(size_t)(F - 1) * wf + 1] - frames[1], 0.0};
+  t.disp[0] = (float)disp[0]; t.disp[1] = (float)disp[1];
+  t.rows.assign((size_t)F * t.stride, 0.f);
+  for (int k = 0; k < F; k++) {
+    float *row = t.rows.data() + (size_t)k * t.stride;
+    const double *f = frames + (size_t)k * wf;
+    for (int c = 0; c < 3; c++) row[c] = (float)f[c];
+    for (int c = 0; c < 4; c++) row[3 + c] = (float)quat[k][c];
+    for (int j = 0; j < J; j++) row[13 + j] = (float)f[7 + j];
+    if (velocities) {
+      const double *v = velocities + (size_t)k * wv;
+      for (int c = 0; c < 6; c++) row[7 + c] = (float)v[c];
+      for (int j = 0; j < J; j++) row[13 + J + j] = (float)v[6 + j];
+      continue;
+    }
+    // derived: the frames km and kp around k, kp - km frame intervals apart; on a looping clip frame F-1 is frame 0 of the next
+    // cycle, so the neighbour beyond an end is frame F-2 of the cycle before (position less the cycle's displacement) or frame 1
+    // of the cycle after (plus it)
+    int km = k > 0 ? k - 1 : 0, kp = k < F - 1 ? k + 1 : F - 1;
+    double om = 0.0, op = 0.0;   // cycles of displacement on the two neighbours' positions
+    if (t.loop && k == 0) { km = F - 2; om = -1.0; }
+    if (t.loop && k == F - 1) { kp = 1; op = 1.0; }
+    const double span = (t.loop ? 2.0 : (double)(kp - km)) * frame_dt;
+    const double *fm = frames + (size_t)km * wf, *fp = frames + (size_t)kp * wf;
+    for (int c = 0; c < 3; c++) row[7 + c] = (float)(((fp[c] + op * disp[c]) - (fm[c] + om * disp[c])) / span);
+    for (int j = 0; j < J; j++) row[13 + J + j] = (float)((fp[7 + j] - fm[7 + j]) / span);
+    // world-frame rotation vector of quat[kp] o quat[km]^-1, the shorter way round
+    const std::array<double, 4> &a = quat[kp], &b = quat[km];
+    double d[4] = {-a[3] * b[0] + a[0] * b[3] - a[1] * b[2] + a[2] * b[1], -a[3] * b[1] + a[0] * b[2] + a[1] * b[3] - a[2] * b[0],
+                   -a[3] * b[2] - a[0] * b[1] + a[1] * b[0] + a[2] * b[3], a[3] * b[3] + a[0] * b[0] + a[1] * b[1] + a[2] * b[2]};
+    if (d[3] < 0.0)
+      for (double &x : d) x = -x;
+    const double s = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    const double angle = 2.0 * std::atan2(s, d[3]), scale = s > 0.0 ? angle / s / span : 0.0;
+    for (int c = 0; c < 3; c++) row[10 + c] = (float)(d[c] * scale);
+  }
+  return t;
+}
+
+std::vector<TrexMotTerm> build_motion_terms(int nj, bool has_probes, const TrexMotionTerm *terms, int num_terms, float step_weight) {
+  const std::string me = "trex_batch_set_motion_reward: ";
+  if (num_terms < 0 || num_terms > TREX_MOT_MAXTERMS)
+    throw Refusal(me + "num_terms " + std::to_string(num_terms) + " outside [0, " + std::to_string(TREX_MOT_MAXTERMS) + "]");
+  std::vector<TrexMotTerm> out((size_t)num_terms);
+  if (num_terms == 0) return out;
+  if (!terms) throw Refusal(me + "null argument");
+  if (!std::isfinite(step_weight)) throw Refusal(me + "step_weight is not finite");
+  const uint32_t all = nj >= 32 ? 0xffffffffu : ((1u << nj) - 1u);
+  for (int k = 0; k < num_terms; k++) {
+    const TrexMotionTerm &c = terms[k];
+    const std::string ck = me + "term " + std::to_string(k) + ": ";
+    if (c.kind < 0 || c.kind >= TREX_MOT_KINDS) throw Refusal(ck + "unknown kind " + std::to_string(c.kind));
+    if (!std::isfinite(c.weight) || !std::isfinite(c.scale) || !std::isfinite(c.aux)) throw Refusal(ck + "weight, scale or aux is not finite");
+    if (!(c.scale > 0.f)) throw Refusal(ck + "scale must be positive");
+    if (c.aux < 0.f) throw Refusal(ck + "aux must not be negative");
+    if (c.mask & ~all) throw Refusal(ck + "a mask bit at or beyond J = " + std::to_string(nj));
+    if (c.kind == TREX_MOT_END_EFFECTOR && !has_probes) throw Refusal(ck + "END_EFFECTOR needs a clip set with a probe set");
+    TrexMotTerm &o = out[k];
+    std::memset(&o, 0, sizeof o);
+    o.kind = c.kind; o.mask = c.mask ? c.mask : all; o.weight = c.weight; o.scale = c.scale; o.aux = c.aux;
+  }
+  return out;
+}
+
 CameraBasis camera_basis(const TrexCamera &cam, int width, int height) {
   const float cv[] = {cam.distance, cam.yaw_deg, cam.pitch_deg, cam.fov_deg, cam.near_z, cam.far_z, cam.target[0], cam.target[1], cam.target[2]};
   for (float x : cv)

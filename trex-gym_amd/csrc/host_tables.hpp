@@ -1,5 +1,5 @@
 // The tables the kernels read, as pure host arithmetic: everything the C-ABI computes between its argument checks and its HIP calls.
-// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h and include/trex_batch.h, and nothing of HIP; it makes
+// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h, motion_limits.h and include/trex_batch.h, and nothing of HIP; it makes
 // no HIP call and knows no batch. It builds with plain g++ -std=c++17, as model.cpp does, so that tests/host/tables_harness.cpp runs
 // it under the sanitizers on a machine without a GPU. A refusal is a thrown Refusal whose text is the C-ABI's message, whole.
 #pragma once
@@ -15,6 +15,7 @@ struct float4;
 #endif
 #include "device_model.h"
 #include "model.hpp"
+#include "motion_limits.h"
 #include "observation_limits.h"
 #include "proximity_limits.h"
 #include "reward_limits.h"
@@ -91,6 +92,23 @@ struct RewTable {
 };
 RewTable build_reward_table(const Links &links, const std::vector<int> &obs_order, int nb, int action_cols, const TrexRewardTerm *terms,
                             int num_terms);
+
+// trex_batch_set_motion: the clip as the kernels read it - F rows of TREX_MOT_STRIDE(J) floats, the state layout of
+// trex_batch_get_state in f32 (quaternions normalised and brought into one hemisphere frame after frame, velocities as given or
+// derived in f64: include/trex_motion.h) - and the f32 constants of the time mapping. q_lower, q_upper: by body; obs_order:
+// observation slot -> body. num_frames 0 gives the empty table.
+struct MotionTable {
+  int frames = 0, nj = 0, stride = 0;
+  bool loop = false;
+  float frame_dt = 0.f, inv_dt = 0.f, duration = 0.f, inv_duration = 0.f;   // dt, 1 / dt, T = (F - 1) dt, 1 / T
+  float disp[2] = {0.f, 0.f};                                               // pos[F-1] - pos[0], x and y
+  std::vector<float> rows;
+};
+MotionTable build_motion_table(const std::vector<double> &q_lower, const std::vector<double> &q_upper, const std::vector<int> &obs_order,
+                               const double *frames, const double *velocities, int num_frames, double frame_dt, int loop);
+// trex_batch_set_motion_reward: the terms checked and as the kernel reads them (a mask of 0 as all J bits). has_probes: the clip
+// names end effectors.
+std::vector<TrexMotTerm> build_motion_terms(int nj, bool has_probes, const TrexMotionTerm *terms, int num_terms, float step_weight);
 
 // trex_batch_render: the camera of include/trex_batch.h, checked, as the renderer's basis
 struct CameraBasis { float offset[3], fwd[3], right[3], up[3], tan_x, tan_y; };

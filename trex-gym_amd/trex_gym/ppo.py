@@ -189,6 +189,12 @@ class PPO:
         self.b_terms = torch.zeros(nsteps, n, rt.shape[1], device=self.dev) if rt is not None else None
         self.term_sum = torch.zeros(rt.shape[1], device=self.dev) if rt is not None else None
         self.mean_terms = None
+        # motion terms (trex_gym.motion.attach): the same, in a block of their own
+        mt = getattr(env, "motion_terms", None)
+        self.motion_names = list(getattr(env, "motion_names", [])) if mt is not None else []
+        self.b_motion = torch.zeros(nsteps, n, mt.shape[1], device=self.dev) if mt is not None else None
+        self.motion_sum = torch.zeros(mt.shape[1], device=self.dev) if mt is not None else None
+        self.mean_motion = None
         env.reset_tensor()
         self.kern.observe(env.rows, with_reward=False)           # VecNormalize.reset: the statistics see the first obs
 
@@ -209,10 +215,14 @@ class PPO:
                   clip_obs=self.clip_obs)
             if self.b_terms is not None:
                 env.reward_terms = self.b_terms[t]
+            if self.b_motion is not None:
+                env.motion_terms = self.b_motion[t]
             env.step_tensor(self.actions)       # the env clips to the joint limits (trex_env.py:147)
             k.observe(env.rows, True, self.gamma, self.b_rew[t], self.b_done[t], self.b_scale[t:t + 1])
         if self.b_terms is not None:
             torch.sum(self.b_terms, dim=(0, 1), out=self.term_sum)
+        if self.b_motion is not None:
+            torch.sum(self.b_motion, dim=(0, 1), out=self.motion_sum)
         k.act(th, env.rows, None, None, value_out=self.b_val[T], clip_obs=self.clip_obs, value_only=True)
         k.gae(self.b_rew, self.b_scale, self.b_done, self.b_val, self.b_adv, self.b_ret, self.gamma, self.lam, self.clip_rew)
 
@@ -238,6 +248,8 @@ class PPO:
         mean_rew, self._raw_sum = (raw - self._raw_sum) / (T * n), raw
         if self.term_sum is not None:                            # (behind that read-back: the stream is drained, one small copy)
             self.mean_terms = [x / (T * n) for x in self.term_sum.tolist()]
+        if self.motion_sum is not None:
+            self.mean_motion = [x / (T * n) for x in self.motion_sum.tolist()]
         return (flat(self.b_obs), flat(self.b_act), flat(self.b_logp), flat(self.b_val[:T]), flat(self.b_adv), flat(self.b_ret),
                 mean_rew)
 
@@ -375,6 +387,9 @@ class PPO:
                        info["entropy"], info["env_steps_per_s"]))
             if self.mean_terms is not None:
                 info["reward_terms"] = dict(zip(self.term_names, self.mean_terms))
-                if log:
-                    log("        reward terms/step  " + "  ".join("%s %.4g" % kv for kv in info["reward_terms"].items()))
+            if self.mean_motion is not None:
+                info["motion_terms"] = dict(zip(self.motion_names, self.mean_motion))
+            if log and (self.mean_terms is not None or self.mean_motion is not None):   # (the motion terms beside the reward terms)
+                both = list(info.get("reward_terms", {}).items()) + list(info.get("motion_terms", {}).items())
+                log("        reward terms/step  " + "  ".join("%s %.4g" % kv for kv in both))
         return history

@@ -24,7 +24,7 @@ _URDF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ass
 
 def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0, push_force=0.0, push_interval=100,
                       push_duration=5, push_probability=1.0, seed=0, control_mode=None, variable_stiffness=False,
-                      gain_scale=0.0, terminate=None, observations=None, rewards=None, command=None):   # (weights of trex_train.py:66)
+                      gain_scale=0.0, terminate=None, observations=None, rewards=None, command=None, motion=None):   # (weights of trex_train.py:66)
     # control_mode: what the joints' actions mean (position / velocity / torque: J-wide, through the trainer unchanged). The
     # 2J-wide stiffness action space is wider than the policy kernel's act_dim <= 32: refused here, not deep in a launch
     check_action_space(control_mode, variable_stiffness)
@@ -53,12 +53,20 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
     elif rewards is not None:
         from . import rewards as R
         rewards = R.from_tuples(rewards)
+    # motion: dict(clip=path of a Clip.save() file, rsi=, weight=, terms=) - a reference motion on the device, its tracking terms
+    # (trex_gym.motion.imitation, their weights times `weight`; or a checkpoint's) added to the reward column, with rsi every new
+    # episode started at a random instant of the clip, and - with observations - sin and cos of the clip's phase as two more
+    # observation columns behind the commands'
     external = None
-    if rewards is not None and observations is not None:
-        from . import observations as O
-        observations = list(observations) + O.external(3)
-        external = lambda env: env.commands
-    command_columns = external is not None
+    command_columns = rewards is not None and observations is not None
+    phase_columns = motion is not None and observations is not None
+    if command_columns or phase_columns:
+        from . import motion as M, observations as O
+        observations = list(observations) + (O.external(3) if command_columns else []) + (O.external(2) if phase_columns else [])
+        if command_columns and phase_columns:
+            external = lambda env: torch.cat([env.commands, M.phase_columns(env)], 1)
+        else:
+            external = (lambda env: env.commands) if command_columns else M.phase_columns
     pushes = None
     if push_force > 0:
         dev = torch.device(device)
@@ -69,6 +77,19 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
                      drift_weight=1.0, max_episode_steps=max_episode_steps, params=params, pushes=pushes, control_mode=control_mode,
                      terminate=terminate, observations=observations, external=external, rewards=rewards)   # terminate: TrexVecEnv.set_termination's arguments - a fall ends the episode, on the device
     env.command_columns = command_columns   # the last channel is the commands': a checkpoint stores the channels without it
+    env.phase_columns = phase_columns       # and behind it the phase's, likewise
+    env.motion_config = None
+    if motion is not None:
+        from . import motion as M
+        from .termination import foot_links
+        weight = float(motion.get("weight", 1.0))
+        feet = [(l, (0.0, 0.0, 0.0)) for l in foot_links(env)][:M.MAX_END_EFFECTORS]
+        terms = M.imitation(env.model, end_effectors=bool(feet)) if motion.get("terms") is None else M.from_tuples(motion["terms"])
+        if motion.get("terms") is None:
+            terms = [t._replace(weight=t.weight * weight) for t in terms]
+        M.attach(env, motion["clip"], terms=terms, end_effectors=feet, rsi=bool(motion.get("rsi", False)), seed=seed)
+        # what a checkpoint stores: the clip's path, the terms as set (the weight is in them), the rsi flag
+        env.motion_config = dict(clip=str(motion["clip"]), rsi=bool(motion.get("rsi", False)), weight=1.0, terms=M.as_tuples(terms))
     if command is not None:
         if rewards is None:
             raise ValueError("--command: there are no reward terms to track it (--rewards)")
@@ -120,16 +141,19 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
                     "obs_var": torch.tensor(st["obs_var"]), "obs_count": torch.tensor(float(st["obs_count"])),
                     "ret_var": torch.tensor(float(st["ret_var"])),
                     "observations": _own_channels(env), "rewards": getattr(env, "rewards", None),
-                    "command": getattr(env, "command", None)}, save_path)   # (the channels and terms: --play rebuilds the same row)
+                    "command": getattr(env, "command", None), "motion": getattr(env, "motion_config", None)},
+                   save_path)   # (the channels, the terms and the clip: --play rebuilds the same row)
     return agent, hist
 
 
 def _own_channels(env):
-    """the env's observation channels as a checkpoint stores them: without the three command columns build_environment adds
-    behind them when rewards are set (env.command_columns says that it did) (it adds them again on loading)"""
+    """the env's observation channels as a checkpoint stores them: without the three command columns and the two phase columns
+    build_environment adds behind them when rewards or a motion clip are set (env.command_columns and env.phase_columns say
+    that it did) (it adds them again on loading)"""
     obs = getattr(env, "observations", None)
-    if obs is not None and getattr(env, "command_columns", False):
-        obs = obs[:-1]
+    added = int(getattr(env, "command_columns", False)) + int(getattr(env, "phase_columns", False))
+    if obs is not None and added:
+        obs = obs[:-added]
     return obs
 
 
@@ -190,7 +214,7 @@ def load_agent(load_path, num_envs=1, device="cuda:0", max_episode_steps=1000):
     parameter vector and VecNormalize's statistics."""
     ck = torch.load(load_path, map_location=device, weights_only=True)
     env = build_environment(num_envs, device=device, max_episode_steps=max_episode_steps, observations=ck.get("observations"),
-                            rewards=ck.get("rewards"), command=ck.get("command"))
+                            rewards=ck.get("rewards"), command=ck.get("command"), motion=ck.get("motion"))
     agent = PPO(env, nsteps=1, nminibatches=1, noptepochs=1)
     with torch.no_grad():
         agent.policy.theta.copy_(ck["theta"])
@@ -241,6 +265,12 @@ def parse_args(argv=None):
                          "smooth actions, swinging feet that do not slide, nothing but the feet on the floor (default: the step's reward)")
     ap.add_argument("--command", type=float, nargs=3, default=None, metavar=("VX", "VY", "WZ"),
                     help="with --rewards: the velocity every env is to track - forward, sideways (m/s, base axes), yaw rate (rad/s)")
+    ap.add_argument("--motion", type=str, default=None, metavar="CLIP.npz",
+                    help="a reference motion (trex_gym.motion.Clip.save): DeepMimic's tracking terms against it are added to the reward on "
+                         "the device; with --observations, sin and cos of the clip's phase join the observation (with --observations "
+                         "locomotion and --rewards that is 93 + 3 + 2 = 98 columns, more than the learner's 96: not supported)")
+    ap.add_argument("--rsi", action="store_true", help="with --motion: every new episode starts at a random instant of the clip")
+    ap.add_argument("--motion_weight", type=float, default=1.0, help="with --motion: a factor on the weights of the tracking terms")
     ap.add_argument("--fall_penalty", type=float, default=0.0, help="taken from the reward of the step in which an episode ends by a fall")
     args = ap.parse_args(argv)
     if args.variable_stiffness:
@@ -250,6 +280,10 @@ def parse_args(argv=None):
             ap.error(str(e))
     if args.command is not None and args.rewards is None:
         ap.error("--command needs --rewards")
+    if args.motion is None and (args.rsi or args.motion_weight != 1.0):
+        ap.error("--rsi and --motion_weight need --motion")
+    if args.rsi and args.graphs:   # (the instants are drawn per step by a generator of the env's own: not in a replayed graph)
+        ap.error("--rsi cannot be combined with --graphs")
     if not 0.0 <= args.gain_scale < 1.0:
         ap.error("--gain_scale must lie in [0, 1)")
     if args.push_force > 0 and args.graphs:   # (the pushes are drawn per step on the host's step count: not in a replayed graph)
@@ -274,7 +308,8 @@ def environment_from_args(args):
     env = build_environment(args.num_envs, max_episode_steps=args.max_episode_steps, warmstart=args.warmstart,
                             push_force=args.push_force, push_interval=args.push_interval, push_duration=args.push_duration,
                             seed=args.random_seed, control_mode=None if args.control_mode == "position" else args.control_mode,
-                            gain_scale=args.gain_scale, observations=args.observations, rewards=args.rewards, command=args.command)
+                            gain_scale=args.gain_scale, observations=args.observations, rewards=args.rewards, command=args.command,
+                            motion=None if args.motion is None else dict(clip=args.motion, rsi=args.rsi, weight=args.motion_weight))
     if terminate is not None:   # (set on the built env: 'auto' needs its model - every body that does not stand on the floor at the start)
         if terminate["keep_clear"] == ["auto"]:
             from .termination import fall_bodies

@@ -65,7 +65,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         (trex_batch_compose_reward) that runs after the step and before the channels are composed. `commands` [n, 3] (vx, vy in
         base axes, yaw rate; zeros) is a device tensor to write in place, `reward_terms` [n, T] the weighted value of every term
         at the last step (a tensor the caller may replace by another [n, T] block, e.g. a slice of a rollout buffer), `reward_names` their names, `reward_api` the batch's calls (reward_capi.BatchRewards). The commands join the observations through
-        observations.external(3) with external=lambda env: env.commands. None (default): nothing changes - not a launch, not a byte."""
+        observations.external(3) with external=lambda env: env.commands. None (default): nothing changes - not a launch, not a byte.
+        A motion clip with its tracking terms is attached to a constructed env by trex_gym.motion.attach(env, clip, ...)."""
         self.global_num_envs = int(num_envs)
         self.rank, self.world_size, self.process_group = int(rank), int(world_size), process_group
         self.env_lo, self.env_hi = sharding.shard_range(self.global_num_envs, self.rank, self.world_size)
@@ -120,6 +121,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self.rewards, self.reward_names, self.reward_terms, self.reward_api = None, [], None, None
         self.commands = None                    # [n, 3] with rewards: made by _set_rewards
         self._rew_actions = False
+        self.motion, self.motion_api, self.motion_terms, self.motion_names = None, None, None, []
+        self._rsi = False
         self.collision = collision
         self._init_queries()                    # the link table and the caches of the read-only queries (vec_queries.py)
         if observations is not None and len(observations):
@@ -194,6 +197,61 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
     def _compose_reward(self, rows, actions):
         self.reward_api.compose_reward(rows, actions if self._rew_actions else None, self.commands, self.reward_terms)
 
+    # ---- motion clip (trex_batch_set_motion and its kin, include/trex_motion.h; trex_gym.motion builds clips and specifications)
+    def _set_motion(self, clip, terms=None, end_effectors=(), rsi=False, step_weight=1.0, probe_set=7, seed=0):
+        """What trex_gym.motion.attach(env, ...) does (the constructor's signature is a recorded one and takes no `motion`):
+        clip - a trex_gym.motion.Clip or the path of a saved one - goes to the device, and the tracking terms against it
+        (trex_gym.motion; default motion.imitation) are added to the reward column by one more launch per step
+        (trex_batch_compose_motion_reward) behind the rewards' compose: reward = step_weight * the column found + the weighted
+        terms. end_effectors: [(link name or index, xyz in the link frame)], at most 8, kept as link-probe set probe_set.
+        rsi: an env whose episode ends starts the next one at an instant of the clip drawn uniformly in [0, T) by a generator
+        of the env's own seeded with `seed` - one more launch per step (trex_batch_motion_reset), before the channels are
+        composed. `motion` then is the Clip, `motion_api` the batch's calls (motion_capi.BatchMotion), `motion_terms` [n, T] the
+        weighted value of every term at the last step, `motion_names` their names. clip None clears the batch's clip and takes
+        all of this off the env again. Never called, or cleared: nothing changes - not a launch, not a byte."""
+        from . import motion as M, motion_capi
+        if clip is None:
+            if self.motion_api is not None:
+                self.motion_api.set_motion(None)
+            self.motion, self.motion_api, self.motion_terms, self.motion_names, self._rsi = None, None, None, [], False
+            return
+        if isinstance(clip, str):
+            clip = M.Clip.load(clip)
+        if clip.num_joints != self.J:
+            raise ValueError("motion: the clip has %d joints, the model %d" % (clip.num_joints, self.J))
+        end_effectors = list(end_effectors or ())
+        if len(end_effectors) > M.MAX_END_EFFECTORS:
+            raise ValueError("motion: %d end effectors, at most %d" % (len(end_effectors), M.MAX_END_EFFECTORS))
+        if end_effectors:
+            self.batch.set_link_probes(int(probe_set), [self._links.index(l) for l, _ in end_effectors], [xyz for _, xyz in end_effectors])
+        spec = M.imitation(self.model, end_effectors=bool(end_effectors)) if terms is None else M.flatten(terms)
+        names = list(self.model.joint_names)
+        resolved, effectors = M.resolve(spec, lambda j: names.index(j) if isinstance(j, str) else int(j))
+        if effectors and not end_effectors:
+            raise ValueError("motion: an end_effector term and no end_effectors")
+        self.motion_api = motion_capi.BatchMotion(self.batch)
+        self.motion_api.set_motion(clip.frames, clip.frame_dt, clip.loop, clip.velocities, int(probe_set) if end_effectors else -1)
+        self.motion_api.set_reward(resolved, step_weight)
+        self.motion, self.motion_names = clip, M.names(spec)
+        self.motion_terms = torch.zeros(self.num_envs, len(resolved), device=self.device)
+        self._motion_spec = M.as_tuples(spec)
+        self._rsi = bool(rsi)
+        self._rsi_gen = torch.Generator(device=self.device).manual_seed(int(seed))
+        self._rsi_time = torch.zeros(self.num_envs, device=self.device)   # the instants the envs drew last
+        self._rsi_span = self.motion_api.info()["duration"]
+
+    def _motion_step(self, rows):
+        """behind the step call and the rewards' compose: the tracking terms into the reward column; with rsi, the envs whose
+        episode ended start at an instant of the clip"""
+        if self.motion_terms.shape[1]:
+            self.motion_api.compose_reward(rows, self.motion_terms)
+        if self._rsi:
+            self._motion_rsi(rows, self.done)
+
+    def _motion_rsi(self, rows, mask):
+        self._rsi_time.uniform_(0.0, self._rsi_span, generator=self._rsi_gen)
+        self.motion_api.reset(mask, self._rsi_time, rows)
+
     def _dev(self, t, dtype=torch.float32):
         """t as a contiguous `dtype` tensor on the env's device: t ITSELF where it is one already - no copy, no launch."""
         if t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
@@ -205,7 +263,12 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         """Reset all envs (mask=None) or those with mask != 0 (uint8 or bool [n], e.g. the `done` of the last step).
         Returns obs [n, 3J]; the reward / done columns and `done` of the envs that were reset read 0 afterwards.
         With observations: obs [n, 3J + E], every env's channels recomposed at the current state, prev_action() columns zero."""
-        self.batch.reset_rows(self.rows if self._step_rows is None else self._step_rows, mask)
+        rows = self.rows if self._step_rows is None else self._step_rows
+        if self.motion is not None and not self._rsi:     # clocks and held values of the envs to 0 (the state it writes is replaced next)
+            self.motion_api.reset(mask)
+        self.batch.reset_rows(rows, mask)
+        if self._rsi:
+            self._motion_rsi(rows, mask)
         if self._step_rows is not None:
             self._compose(None)
         if self.rewards is not None:            # the envs that were reset have no previous step: their reward history starts afresh
@@ -250,10 +313,14 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
             self.batch.step_rows(actions, self.rows, self._penalties, done=self.done)   # (None: the penalties ride in the row block)
             if self.rewards is not None:
                 self._compose_reward(self.rows, actions)
+            if self.motion is not None:
+                self._motion_step(self.rows)
         else:   # (observation channels: one more launch, after the resets of the step call - the row of the new episode's state)
             self.batch.step_rows(actions, self._step_rows, self._penalties, done=self.done)
             if self.rewards is not None:
                 self._compose_reward(self._step_rows, actions)
+            if self.motion is not None:           # (before the channels' compose, which then sees the state RSI wrote)
+                self._motion_step(self._step_rows)
             self._compose(actions)
         if self._term_on and self.gains is not None:   # the envs that fell start their episode with new motor gains
             self.set_motor_gains(**self.gains.draw(self.termination_reason != 0))
@@ -263,7 +330,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         """Open-loop rollout: actions [S, n, J] f32 on device -> rows [S, n, 3J+2] (obs | reward | done of every step), S
         env-steps in ONE launch (trex_batch_step_many; bitwise S calls of step_tensor). `rows`, `obs`, `rew`, `done_f`
         and `done` then hold the last step. sharding.split_rows(rows[s]) cuts a step's block into the three.
-        ValueError with observations or rewards: an open-loop launch has no compose between its steps."""
+        ValueError with observations, rewards or motion: an open-loop launch has no compose between its steps."""
+        if self.motion is not None:
+            raise ValueError("step_many_tensor: not with motion - the open-loop launch has no per-step compose of the tracking terms")
         if self.rewards is not None:
             raise ValueError("step_many_tensor: not with rewards - the open-loop launch has no per-step compose of the reward terms")
         if self._step_rows is not None:

@@ -13,6 +13,9 @@ The rules of trex-gym_amd/csrc/device_model.h that the models aim at, restated (
   * scan units: one per convex hull if there are at most 32 hulls, else one per body that has vertices;
   * tree: at most 26 bodies, depth at most 6, at most 4 moving children per body.
 
+MODELS is the catalogue the step-parity tests run over; KINEMATIC_MODELS holds models for the kernels outside the step (link
+kinematics, observation, reward, motion: tests/row_kernel_cases.py), which compile_both and state_set take as well.
+
 state_set(name, ...) rolls the f64 oracle from start poses ABOVE the floor (a drop, the landing, rest) and samples the states
 the GPU tests step from; deterministic, a few seconds on the CPU for all models.
 """
@@ -267,6 +270,36 @@ def slab(directory):
 MODELS = dict(deep_chain=deep_chain, big_body=big_body, full_masks=full_masks, many_hulls=many_hulls, bushy=bushy, slab=slab)
 
 
+def mount_first(directory):
+    """6 links, 5 bodies: the FIRST <link> of the document is a small "imu", welded by a fixed joint - its origin turned about all
+    three axes and moved - to the second segment of a chain trunk -> s_c -> s_a -> s_b; one side link on the trunk. URDF link 0, whose
+    frame is "the base axes" of the observation, reward and motion kernels and of link_state(axes="base"), therefore lies in body
+    2 at depth 2, not in the root. The joint names sort differently from the body order; the axes are oblique."""
+    rng = np.random.default_rng(909)
+    b = Builder(directory, "mount_first")
+    ih = (0.03, 0.02, 0.01)
+    b.link("imu", 0.1, ih, hulls=[(box_verts(rng, ih), (0, 0, 0), (0, 0, 0))])                  # written first: URDF link 0
+    half = (0.15, 0.10, 0.05)
+    b.link("trunk", 4.0, half, com=(0.01, -0.02, 0.0), com_rpy=(0.1, -0.05, 0.2), hulls=[(box_verts(rng, half), (0, 0, 0), (0, 0, 0))])
+    lh = (0.11, 0.03, 0.025)
+    parent = "trunk"
+    for k, n in enumerate(["s_c", "s_a", "s_b"]):
+        b.link(n, 1.5 - 0.25 * k, lh, com=(0.11, 0.005, -0.004), com_rpy=(0.1, 0.2, -0.1), hulls=[(box_verts(rng, lh), (0.11, 0, 0), (0, 0, 0))])
+        axis = rng.uniform(0.5, 1.5) * (np.array([0.0, 1.0, 0.0]) + rng.uniform(-0.5, 0.5, 3))
+        b.joint("j_" + n, parent, n, xyz=(0.15 if k == 0 else 0.22, 0.01 * (k + 1), 0.0), rpy=tuple(rng.uniform(-0.4, 0.4, 3) + 0.05), axis=axis,
+                lower=-1.0 + 0.15 * k, upper=1.0 - 0.1 * k, damping=0.01 * k)               # every joint its own limits
+        parent = n
+    b.link("side", 1.0, lh, com=(0.1, 0, 0), hulls=[(box_verts(rng, lh), (0.1, 0, 0), (0, 0, 0))])
+    b.joint("j_side", "trunk", "side", xyz=(-0.1, 0.1, 0), rpy=(0.1, -0.2, 2.0), axis=(0.3, 1.0, -0.2), lower=-0.9, upper=0.95)
+    b.joint("w_imu", "s_a", "imu", xyz=(0.05, 0.02, 0.03), rpy=(0.4, -0.3, 0.9), kind="fixed")
+    return b.write(), dict(nb=5, depth=3, link0_body=2, link0_depth=2, link0_turned=True, permuted_obs_order=True, params=SMALL_PARAMS)
+
+
+# Models for the kernels outside the step (link kinematics, observation, reward, motion): not in MODELS, which parametrizes the
+# step-parity tests and their per-model recorded tolerances.
+KINEMATIC_MODELS = dict(mount_first=mount_first)
+
+
 # ---------------------------------------------------------------- refusals
 def refused(directory, kind):
     """models one step outside the limits: 'depth7', 'children5', 'bodies27'; and 'one_link' (no joints)"""
@@ -295,7 +328,7 @@ def refused(directory, kind):
 def compile_both(name, directory):
     """-> (urdf path, props, oracle model dict)"""
     from oracle import trex_model as tm
-    path, props = MODELS[name](directory)
+    path, props = (MODELS.get(name) or KINEMATIC_MODELS[name])(directory)
     return path, props, tm.compile_model(path)
 
 

@@ -35,6 +35,10 @@ AXES = ("world", "link", "base")
 # deviations on the generated models at N = 3 (test_synthetic_models), same profile:
 MEASURED_SYN = dict(deep_chain=dict(pose=2.13e-7, velocity=2.83e-7, acc=3.17e-7), big_body=dict(pose=7.9e-8, velocity=1.11e-7, acc=1.43e-7),
                     bushy=dict(pose=1.58e-7, velocity=1.32e-7, acc=1.99e-7))
+# mount_first (URDF link 0 in a moving body at depth 2: the base axes of axes="base") has no recorded entry: it is no deeper and no
+# larger than the models above, and takes the largest entry per quantity
+SYN_MODELS = list(MEASURED_SYN) + ["mount_first"]
+SYN_LARGEST = {k: max(m[k] for m in MEASURED_SYN.values()) for k in ("pose", "velocity", "acc")}
 
 
 def parity_probes(model):
@@ -203,7 +207,7 @@ def test_consistent_with_link_transforms_and_jacobian(oracle64, model):
 # 4 ------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
-    return built_models(MEASURED_SYN, tmp_path_factory)
+    return built_models(SYN_MODELS, tmp_path_factory)
 
 
 def synthetic_deviation(m, n=3):
@@ -225,14 +229,15 @@ def synthetic_deviation(m, n=3):
     return w
 
 
-@pytest.mark.parametrize("name", list(MEASURED_SYN))
+@pytest.mark.parametrize("name", SYN_MODELS)
 def test_synthetic_models(name, built):
     """deep_chain (depth 6, oblique axes that are no unit vectors), big_body (the swept plate) and bushy (26 bodies, four children,
-    six merged links) at N = 3: every link at its origin and the picked ones at an offset point, all axes, against the reference.
-    Tolerance: 4 x the deviations measured on these states (MEASURED_SYN), under the same caps."""
+    six merged links) and mount_first (link 0 welded to body 2 behind a turned frame) at N = 3: every link at its origin and the
+    picked ones at an offset point, all axes, against the reference.
+    Tolerance: 4 x the deviations measured on these states (MEASURED_SYN; mount_first: the largest of them), under the same caps."""
     w = synthetic_deviation(built[name])
     print("%s link_state deviations: %s" % (name, {k: "%.3g" % x for k, x in w.items()}))
-    ms = MEASURED_SYN[name]
+    ms = MEASURED_SYN.get(name, SYN_LARGEST)
     for k, cap in (("pose", CAPS["pose"]), ("velocity", CAPS["velocity"]), ("acc", CAPS["accel"])):
         assert w[k] <= min(4 * ms[k], cap), (name, k, w[k])
 

@@ -56,9 +56,9 @@ def set_clip(v, model, frames, loop=False, K=0, velocities=None, dt=MC.DT, probe
     return MR.device_table(MR.build_table(model, frames, velocities, dt, loop)), probes
 
 
-def sample(v, times, K=0):
+def sample(v, times, K=0, J=J):
     """motion_sample into guarded buffers -> (state, points or None, phase) as numpy"""
-    n = v.num_envs
+    n, W = v.num_envs, 13 + 2 * J
     ws, s = guarded((n, W), fill=float("nan"))
     wp, p = guarded((n, max(K, 1), 3), fill=float("nan"))
     wf, f = guarded((n,), fill=float("nan"))
@@ -69,7 +69,7 @@ def sample(v, times, K=0):
     return s.clone(), (p.clone() if K else None), f.clone()
 
 
-def check_sample(model, tab, probes, times, state, points, phase, what="sample"):
+def check_sample(model, tab, probes, times, state, points, phase, what="sample", J=J):
     state, phase = state.cpu().numpy().astype(np.float64), phase.cpu().numpy()
     assert np.isfinite(state).all()
     for e, t in enumerate(np.asarray(times, np.float32)):
@@ -201,7 +201,7 @@ def compose(v, rows, T, pad=3, with_terms=True):
     return r[:, :Wr].clone(), t.clone(), ok and (with_terms or bool((t == 7.0).all()))
 
 
-def check_compose(model, tab, probes, spec, step_weight, before, after, terms, state, clocks, helds, Ts, prev_terms=None):
+def check_compose(model, tab, probes, spec, step_weight, before, after, terms, state, clocks, helds, Ts, prev_terms=None, J=J):
     """every env and term against the reference (advancing clocks and held values); the column against the breakdown, bitwise"""
     before, after, terms = before.cpu().numpy(), after.cpu().numpy(), terms.cpu().numpy()
     n, T = terms.shape

@@ -46,7 +46,7 @@ def full_spec(model):
             (OR.POINT_VEL, deepest, Z, 1.0), (OR.POINT_HEIGHT, head, (0.3, 0.0, 0.1), 1.0), (OR.EXTERNAL, 4, Z, 1.0)]
 
 
-def inputs(n, seed, ext_cols=7, ext_stride=9):
+def inputs(n, seed, ext_cols=7, ext_stride=9, J=J):
     """actions far outside the joint limits and external columns in a buffer wider than the channels read"""
     gen = torch.Generator().manual_seed(seed)
     act = (10.0 * torch.randn(n, J, generator=gen)).to(DEV)
@@ -54,7 +54,7 @@ def inputs(n, seed, ext_cols=7, ext_stride=9):
     return act, ext
 
 
-def compose(v, rows, act, ext, extra, pad=0, guard_rows=0, fill=float("nan")):
+def compose(v, rows, act, ext, extra, pad=0, guard_rows=0, fill=float("nan"), J=J):
     """compose_rows into a fresh buffer prefilled with `fill`, `pad` columns wider than the row and `guard_rows` longer -> tensor"""
     tail = 5 if v._pen_in_rows else 2
     out = torch.full((v.num_envs + guard_rows, 3 * J + extra + tail + pad), fill, device=DEV)
@@ -63,7 +63,7 @@ def compose(v, rows, act, ext, extra, pad=0, guard_rows=0, fill=float("nan")):
     return out
 
 
-def check_rows(model, spec, out, rows, state, act, ext, fz, envs=None, factor=1.0):
+def check_rows(model, spec, out, rows, state, act, ext, fz, envs=None, factor=1.0, J=J, floor_z=OR.FLOOR_Z):
     """every env of `envs` (all): pass-through bitwise, copied channels bitwise, computed channels within the tolerances"""
     n = rows.shape[0]
     out, rows, state = out.cpu().numpy(), rows.cpu().numpy(), state.cpu().numpy().astype(np.float64)
@@ -75,7 +75,7 @@ def check_rows(model, spec, out, rows, state, act, ext, fz, envs=None, factor=1.
     worst = dict(pose=0.0, velocity=0.0)
     for e in (range(n) if envs is None else envs):
         want = OR.channels(model, state[e], spec, action=None if act is None else act[e], extern=ext[e], contact_fz=fz[e],
-                           done=rows[e, 3 * J + 1])
+                           done=rows[e, 3 * J + 1], floor_z=floor_z)
         got = out[e, 3 * J:3 * J + E]
         assert np.isfinite(got).all()
         for (kind, _, _, scale), (c0, w) in zip(spec, OR.columns(spec, J)):

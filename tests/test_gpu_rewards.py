@@ -89,7 +89,7 @@ def sensed_cases(oracle64, model, n, **kw):
     return v
 
 
-def inputs(n, seed):
+def inputs(n, seed, J=J):
     """actions well outside the joint limits (ACTION_RATE takes them as passed) and commands"""
     gen = torch.Generator().manual_seed(seed)
     return (3.0 * torch.randn(n, J, generator=gen)).to(DEV), torch.randn(n, 3, generator=gen).to(DEV)
@@ -112,7 +112,7 @@ def compose(v, rows, act, cmd, T, pad=3):
     return r[:, :W].clone(), t.clone(), ok
 
 
-def check(model, spec, before, after, terms, state, force, hists, Ts, act, cmd, prev_terms=None):
+def check(model, spec, before, after, terms, state, force, hists, Ts, act, cmd, prev_terms=None, J=J, floor_z=RR.FLOOR_Z):
     """every env and term against the reference (advancing `hists`); the column against the breakdown, bitwise"""
     before, after, terms = before.cpu().numpy(), after.cpu().numpy(), terms.cpu().numpy()
     act, cmd = act.cpu().numpy(), cmd.cpu().numpy()
@@ -122,7 +122,7 @@ def check(model, spec, before, after, terms, state, force, hists, Ts, act, cmd, 
     assert after[:, 3 * J].tobytes() == RR.ordered_sum(terms).tobytes()                   # the ordered f32 sum, bitwise
     assert np.isfinite(terms).all()
     for e in range(n):
-        v, cases = RR.evaluate(model, spec, state[e], before[e], hists[e], Ts, action=act[e], command=cmd[e], force=force[e])
+        v, cases = RR.evaluate(model, spec, state[e], before[e], hists[e], Ts, action=act[e], command=cmd[e], force=force[e], floor_z=floor_z)
         for t, (s, case) in enumerate(zip(spec, cases)):
             kind, w = s[0], float(np.float32(s[4]))
             if case["held"]:
@@ -142,7 +142,7 @@ def report():
     print("reward deviation / bound, largest per kind: " + "  ".join("%s %.3f" % (KIND_NAMES[k], WORST[k]) for k in sorted(WORST)))
 
 
-def histories(n, T):
+def histories(n, T, J=J):
     return [RR.new_history(T, J, J) for _ in range(n)]
 
 

@@ -31,12 +31,12 @@ def harness(tmp_path_factory):
     return exe
 
 
-def run_numbers(exe, tmp_path, numbers):
+def run_numbers(exe, tmp_path, numbers, urdf=ASSET_URDF):
     path = os.path.join(str(tmp_path), "numbers.txt")
     with open(path, "w") as f:
         f.write(" ".join(repr(float(x)) for x in numbers))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, ASSET_URDF, path], env=env, capture_output=True, text=True, timeout=120)
+    r = subprocess.run([exe, urdf, path], env=env, capture_output=True, text=True, timeout=120)
     assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-3000:]
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     if r.stdout.startswith("REFUSED "):
@@ -45,10 +45,10 @@ def run_numbers(exe, tmp_path, numbers):
     return {line.split(" ", 1)[0]: np.array(line.split()[1:], np.float64) for line in r.stdout.splitlines()}
 
 
-def table(exe, tmp_path, frames, frame_dt=MC.DT, loop=False, velocities=None, F=None):
+def table(exe, tmp_path, frames, frame_dt=MC.DT, loop=False, velocities=None, F=None, urdf=ASSET_URDF):
     frames = np.asarray(frames, np.float64)
     n = [0, len(frames) if F is None else F, frame_dt, int(loop), int(velocities is not None)] + list(frames.reshape(-1))
-    return run_numbers(exe, tmp_path, n + ([] if velocities is None else list(np.asarray(velocities, np.float64).reshape(-1))))
+    return run_numbers(exe, tmp_path, n + ([] if velocities is None else list(np.asarray(velocities, np.float64).reshape(-1))), urdf)
 
 
 def terms(exe, tmp_path, spec, has_probes=True, step_weight=1.0):
@@ -60,7 +60,9 @@ def refused(out, text):
     assert out[1] == INVALID and text in out[2], out
 
 
-def check_table(t, model, frames, frame_dt, loop, velocities=None):
+def check_table(t, model, frames, frame_dt, loop, velocities=None, J=J):
+    COLS = 13 + 2 * J
+    STRIDE = (COLS + 3) // 4 * 4
     w = MR.build_table(model, frames, velocities, frame_dt, loop)
     F = len(frames)
     assert t["scalars"].astype(np.int64).tolist() == [F, J, STRIDE, int(loop), F * STRIDE]
@@ -174,3 +176,30 @@ def test_terms(harness, tmp_path):
         refused(go([spec[0]], step_weight=bad), "step_weight is not finite")
     refused(go([(MR.VELOCITY, 1 << J, 1.0, 1.0, 0.0)]), "term 0: a mask bit at or beyond J = %d" % J)
     refused(go([spec[3]], has_probes=False), "term 0: END_EFFECTOR needs a clip set with a probe set")
+
+
+@pytest.mark.parametrize("name", ["mount_first", "deep_chain"])
+def test_table_on_generated_models(name, harness, tmp_path):
+    """the recorded clip of tests/row_kernel_cases.py, with its velocities, on models of J = 4 and J = 6 whose joints sort differently
+    from their bodies; on mount_first every joint has limits of its own, and a frame is refused by the limits of ITS joint"""
+    import row_kernel_cases as RK
+    import synthetic_models as sm
+    path, props, om = sm.compile_both(name, tmp_path / "model")
+    nj = om["nb"] - 1
+    frames, vel = RK.clip(om, RK.oracle_of(name, om, RK.params_of(props)))
+    go = lambda f, **kw: table(harness, tmp_path, f, frame_dt=RK.DT, urdf=path, **kw)
+    rows, _ = check_table(go(frames, velocities=vel), om, frames, RK.DT, False, vel, J=nj)
+    assert rows.shape == (RK.FRAMES, (13 + 2 * nj + 3) // 4 * 4)
+    check_table(go(frames), om, frames, RK.DT, False, J=nj)
+    if name == "mount_first":
+        oo = om["obs_order"]
+        lo, hi = om["q_lower"][oo], om["q_upper"][oo]
+        wide, narrow = int(np.argmax(hi)), int(np.argmin(hi))
+        g = frames.copy()
+        g[2, 7 + wide] = hi[wide]                       # inside its own limits, outside every other joint's
+        assert hi[wide] > np.delete(hi, wide).max() + 1e-3 and not isinstance(go(g), tuple)
+        g = frames.copy()
+        g[2, 7 + narrow] = hi[narrow] + 2e-6            # outside its own, inside every other joint's
+        refused(go(g), "frame 2: joint %d outside its limits" % narrow)
+        g[2, 7 + narrow] = lo[narrow]
+        assert not isinstance(go(g), tuple)

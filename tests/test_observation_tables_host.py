@@ -27,14 +27,14 @@ def harness(tmp_path_factory):
     return exe
 
 
-def run(exe, tmp_path, spec, action_cols=J):
+def run(exe, tmp_path, spec, action_cols=J, urdf=ASSET_URDF):
     """-> {part: float64 array} of one harness run, or ('REFUSED', code, message)"""
     path = os.path.join(str(tmp_path), "numbers.txt")
     numbers = [action_cols, len(spec)] + [x for k, l, xyz, s in spec for x in [k, l] + list(xyz) + [s]]
     with open(path, "w") as f:
         f.write(" ".join(repr(float(x)) for x in numbers))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, ASSET_URDF, path], env=env, capture_output=True, text=True, timeout=120)
+    r = subprocess.run([exe, urdf, path], env=env, capture_output=True, text=True, timeout=120)
     assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-3000:]
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     if r.stdout.startswith("REFUSED "):
@@ -124,3 +124,20 @@ def test_refusals(harness, tmp_path, model):
     refused(go([(OR.EXTERNAL, 512 - 3 * J, z, 1.0), (OR.BASE_HEIGHT, 0, z, 1.0)]), "3J + E = 513 observation columns with channel 1")
     refused(go([(OR.EXTERNAL, 2 ** 31 - 1, z, 1.0)]), "at most 512")
     refused(go([(OR.EXTERNAL, 0, z, 1.0)]), "channel 0: an EXTERNAL channel needs link = k >= 1 columns, got 0")
+
+
+@pytest.mark.parametrize("name", ["mount_first", "deep_chain"])
+def test_table_on_generated_models(name, harness, tmp_path):
+    """the channels of tests/row_kernel_cases.py on a model whose URDF link 0 lies in body 2 behind a turned frame, and on one of
+    J = 6: body, body-frame point and link frame of every channel, the body mask"""
+    import row_kernel_cases as RK
+    import synthetic_models as sm
+    path, props, om = sm.compile_both(name, tmp_path / "model")
+    nj = om["nb"] - 1
+    spec = RK.obs_spec(om, RK.link_of_body(om, om["nb"] - 1))
+    t = run(harness, tmp_path, spec, action_cols=nj, urdf=path)
+    check_table(t, om, spec, nj)
+    body = t["body"].astype(int)
+    assert body[5] == body[6] == body[7] == int(om["link_body"][0]) == props.get("link0_body", 0)     # the channels on URDF link 0
+    if name == "mount_first":
+        assert np.abs(t["tf"].reshape(len(spec), 12)[5][:9] - np.eye(3).reshape(-1)).max() > 1e-2 and np.abs(t["point"].reshape(-1, 3)[5]).max() > 1e-2

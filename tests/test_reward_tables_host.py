@@ -28,14 +28,14 @@ def harness(tmp_path_factory):
     return exe
 
 
-def run(exe, tmp_path, spec, action_cols=J):
+def run(exe, tmp_path, spec, action_cols=J, urdf=ASSET_URDF):
     """-> {part: float64 array} of one harness run, or ('REFUSED', code, message)"""
     path = os.path.join(str(tmp_path), "numbers.txt")
     numbers = [action_cols, len(spec)] + [x for k, l, m, xyz, w, p0, p1 in spec for x in [k, l, m] + list(xyz) + [w, p0, p1]]
     with open(path, "w") as f:
         f.write(" ".join(repr(float(x)) for x in numbers))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe, ASSET_URDF, path], env=env, capture_output=True, text=True, timeout=120)
+    r = subprocess.run([exe, urdf, path], env=env, capture_output=True, text=True, timeout=120)
     assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-3000:]
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     if r.stdout.startswith("REFUSED "):
@@ -138,3 +138,19 @@ def test_refusals(harness, tmp_path, model):
     refused(go([term(RR.TORQUE, mask=1 << 31)]), "a mask bit at or beyond J")
     refused(go([term(RR.CONTACT_COUNT, mask=1 << NB)]), "term 0: a mask bit at or beyond the body count %d" % NB)
     refused(go([term(RR.ALIVE)] * 33), "num_terms 33 outside [0, 32]")
+
+
+@pytest.mark.parametrize("name", ["mount_first", "deep_chain"])
+def test_table_on_generated_models(name, harness, tmp_path):
+    """the 32 terms of tests/row_kernel_cases.py on a model whose URDF link 0 lies in body 2 and whose joints sort differently from
+    its bodies, and on one of J = 6: body, body-frame point, masks, and joint_body = the observation order, zero past J"""
+    import row_kernel_cases as RK
+    import synthetic_models as sm
+    path, props, om = sm.compile_both(name, tmp_path / "model")
+    nj = om["nb"] - 1
+    spec = RK.reward_spec(om, RK.link_of_body(om, om["nb"] - 1))
+    t = run(harness, tmp_path, spec, action_cols=nj, urdf=path)
+    check_table(t, om, spec, nj)
+    jb = t["joint_body"].astype(int)
+    assert jb[:nj].tolist() == list(om["obs_order"]) != sorted(om["obs_order"]) and (jb[nj:] == 0).all()
+    assert t["mask"].astype(np.int64)[9] == (1 << nj) - 1

@@ -23,7 +23,7 @@ def capi():
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
     """name -> (urdf path, props, oracle model)"""
-    return {n: sm.compile_both(n, tmp_path_factory.mktemp(n)) for n in sm.MODELS}
+    return {n: sm.compile_both(n, tmp_path_factory.mktemp(n)) for n in list(sm.MODELS) + list(sm.KINEMATIC_MODELS)}
 
 
 @pytest.fixture(scope="module")
@@ -42,7 +42,7 @@ def contacts(built, sets):
     return out
 
 
-@pytest.mark.parametrize("name", list(sm.MODELS))
+@pytest.mark.parametrize("name", list(sm.MODELS) + list(sm.KINEMATIC_MODELS))
 def test_loader_matches_the_oracle_compiler(name, capi, built):
     path, props, om = built[name]
     m = capi.Model(path)

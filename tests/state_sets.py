@@ -11,16 +11,17 @@ J = 25
 _LANDING = {}
 
 
-def landing_states(oracle64, model, every=12):
+def landing_states(oracle64, model, every=12, seed=5):
     """(states f32 [k, 63], actions f32 [k, 25]) sampled every `every` steps along a 300-step landing under noisy actions around
     the start pose: free fall, impact, standing (contacts, friction, joint stops under load). every=6 gives the 50 states of
-    tests/test_gpu_parity.py::test_one_step_parity_in_contact_and_at_rest. Rolled out once per oracle and `every`; the arrays are
-    read-only, so that one caller cannot change another's."""
-    key = (id(oracle64), every)
+    tests/test_gpu_parity.py::test_one_step_parity_in_contact_and_at_rest. The oracle may carry other engine parameters than the
+    defaults (tests/param_cases.py): the landing is then that oracle's own; `seed` draws other noise. Rolled out once per oracle,
+    `every` and `seed`; the arrays are read-only, so that one caller cannot change another's."""
+    key = (id(oracle64), every, seed)
     if key not in _LANDING:
         q0 = model["q_start"][model["obs_order"]]
         lo, hi = model["q_lower"][model["obs_order"]], model["q_upper"][model["obs_order"]]
-        rng = np.random.default_rng(5)
+        rng = np.random.default_rng(seed)
         s = oracle64.new_state()
         oracle64.reset(s)
         states, acts = [], []

@@ -3,7 +3,11 @@
 us per launch of each query at 256, 4 096 and 32 768 envs (hipEvents around `iters` back-to-back launches after a warm-up, the
 median of `repeats` such groups) next to the step launch of the same batch, and the largest deviations from the f64 reference
 on the states of tests/test_gpu_dynamics.py - the figures its tolerances are set from. Writes profiles/r12_dynamics.txt
-(--out). No gate hangs on the timings: they are recorded so that the next reader knows the cost."""
+(--out). No gate hangs on the timings: they are recorded so that the next reader knows the cost.
+
+--models: no timings; per generated model of tests/dynamics_model_cases.py the deviation d32 of the reference's f32 run, the bound
+it sets and the GPU's deviation, for every metric and every identity of tests/test_gpu_dynamics_models.py. Writes
+profiles/r27_dynamics_models.txt (--out)."""
 import argparse
 import os
 import statistics
@@ -32,13 +36,59 @@ def time_us(fn, iters, repeats, warmup=20):
     return statistics.median(out), min(out), max(out)
 
 
+class _TmpDirs:
+    """what state_sets.built_models asks of pytest's tmp_path_factory"""
+
+    def mktemp(self, name):
+        import tempfile
+        return tempfile.mkdtemp(prefix=name + "_")
+
+
+def models_report(out_path):
+    import dynamics_model_cases as DC
+    import test_gpu_dynamics_models as T
+    from state_sets import built_models
+    from trex_gym import _capi
+    lines = ["dynamics queries on the generated models: the reference's f32 run, the bound it sets, the GPU",
+             "device: %s   kernel build id: %s" % (torch.cuda.get_device_name(0), _capi.build_id()),
+             "%d states per model (dynamics_ref.random_states, seed 31; the last two with a per-body mass scale); the Jacobian at every"
+             % DC.N, "URDF link, at its origin and at (0.3, -0.2, 0.1). d32: the largest deviation of the reference run in float32 from the same",
+             "reference in float64, in the metric. bound = min(cap, max(T-rex tolerance, 4 x d32)): from the reference alone, no GPU",
+             "figure enters it. Identities: the residual of the f32 run's own outputs takes the place of d32.", ""]
+    built = built_models(DC.MODELS, _TmpDirs())
+    worst = 0.0
+    for name in DC.MODELS:
+        c = DC.case(name, built[name])
+        v = T.env_of(built[name], c["cases"])
+        got = T.as_numpy(T.device_outputs(v, c["om"], c["acc"]))
+        v.close()
+        dev, res = DC.metric_devs(c["taus"], got, c["ref"]), DC.identity_devs(c["om"], c["cases"], c["acc"], got)
+        lines.append("%s   (D = %d, %d links)" % (name, 6 + c["om"]["nb"] - 1, len(c["om"]["link_names"])))
+        lines.append("  %-13s %10s %10s %10s %8s" % ("", "d32", "bound", "GPU", "GPU/bound"))
+        rows = [(k, c["d32"][k], c["bound"][k], dev[k]) for k in DC.METRICS] + [(k, c["res32"][k], c["id_bound"][k], res[k]) for k in DC.IDENTITIES]
+        for k, d, b, g in rows:
+            lines.append("  %-13s %10.3g %10.3g %10.3g %8.2f" % (k, d, b, g, g / b))
+            worst = max(worst, g / b)
+        lines.append("")
+        print("\n".join(lines[-len(rows) - 3:]), flush=True)
+    lines.append("largest GPU deviation over its bound: %.2f" % worst)
+    print(lines[-1], flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12_dynamics.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--models", action="store_true")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--no-deviations", action="store_true")
     args = ap.parse_args()
+    if args.models:
+        return models_report(args.out or os.path.join(ROOT, "profiles", "r27_dynamics_models.txt"))
+    args.out = args.out or os.path.join(ROOT, "profiles", "r12_dynamics.txt")
     from trex_gym import _capi
     from trex_gym.vec_env import TrexVecEnv
     lines = ["dynamics queries: cost per launch and deviation from the f64 reference",

@@ -16,13 +16,14 @@ def make_vec(n, urdf=ASSET_URDF, **kw):
     return TrexVecEnv(n, urdf_path=urdf, device=DEV, **kw)
 
 
-def loaded_vec(cases, n=None, **kw):
-    """a TrexVecEnv of n envs holding cases[e % len(cases)] of state_sets.case_states (mass scales included)"""
+def loaded_vec(cases, n=None, urdf=ASSET_URDF, params=None, nb=NB, **kw):
+    """a TrexVecEnv of n envs holding cases[e % len(cases)] of state_sets.case_states (mass scales included); of the model at `urdf`
+    with `nb` bodies, under the engine parameters `params` (the T-rex asset and the defaults)"""
     n = len(cases) if n is None else n
-    v = make_vec(n, **kw)
+    v = make_vec(n, urdf=urdf, params=params, **kw)
     v.reset()
     idx = np.arange(n) % len(cases)
-    ms = np.array([np.ones(NB) if c[1] is None else c[1] for c in cases], np.float32)
+    ms = np.array([np.ones(nb) if c[1] is None else c[1] for c in cases], np.float32)
     if any(c[1] is not None for c in cases):
         v.set_domain(torch.tensor(ms[idx]))
     v.set_state(torch.tensor(np.array([c[0] for c in cases], np.float32)[idx]))

@@ -14,7 +14,8 @@ The rules of trex-gym_amd/csrc/device_model.h that the models aim at, restated (
   * tree: at most 26 bodies, depth at most 6, at most 4 moving children per body.
 
 MODELS is the catalogue the step-parity tests run over; KINEMATIC_MODELS holds models for the kernels outside the step (link
-kinematics, observation, reward, motion: tests/row_kernel_cases.py), which compile_both and state_set take as well.
+kinematics, observation, reward, motion: tests/row_kernel_cases.py; the dynamics queries: tests/dynamics_model_cases.py), which
+compile_both and state_set take as well.
 
 state_set(name, ...) rolls the f64 oracle from start poses ABOVE the floor (a drop, the landing, rest) and samples the states
 the GPU tests step from; deterministic, a few seconds on the CPU for all models.

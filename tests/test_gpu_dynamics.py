@@ -21,6 +21,7 @@ import torch
 
 import dynamics_ref as R
 from conftest import ASSET_URDF
+from dynamics_model_cases import cent_dev     # (the centroidal metric of the module docstring: one text, shared with the generated models)
 from gpu_support import DEV, dynamics_queries as all_queries, loaded_vec, make_vec, random_actions
 from state_sets import base_cases, case_states, oracle_state, probe_links
 from tolerances import DYNAMICS_CAPS as CAPS, DYNAMICS_MEASURED as MEASURED, DYNAMICS_TOL as TOL  # noqa: F401  (MEASURED: the docstrings' pointer)
@@ -30,15 +31,6 @@ NB, J, D = 26, 25, 31
 G = 9.81
 
 # MEASURED, CAPS, TOL: tests/tolerances.py (the link-state and forward-dynamics tests read them as well)
-
-
-def cent_dev(got, want):
-    """largest relative deviation over the centroidal quantities (module docstring)"""
-    m = want[14]
-    parts = [(slice(0, 3), max(np.abs(want[0:3]).max(), 1.0)), (slice(3, 6), max(np.abs(want[3:6]).max(), 0.01)),
-             (slice(6, 9), max(np.abs(want[6:9]).max(), 0.01 * m)), (slice(9, 12), max(np.abs(want[9:12]).max(), 0.01 * m)),
-             (slice(12, 13), max(abs(want[12]), 0.01 * m)), (slice(13, 14), abs(want[13])), (slice(14, 15), m)]
-    return max(np.abs(got[sl] - want[sl]).max() / sc for sl, sc in parts)
 
 
 def deviations(oracle64, model, n, envs=None, batch=None):

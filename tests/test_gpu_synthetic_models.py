@@ -15,6 +15,7 @@ import torch
 import dynamics_ref as R
 import gpu_support
 import synthetic_models as sm
+from dynamics_model_cases import cent_dev
 from gpu_support import DEV
 from parity_helpers import assert_step_close, oracle_wrench
 from state_sets import query_states
@@ -216,14 +217,6 @@ def test_features_leave_the_physics_bitwise_unchanged(name, built):
 
 
 # ---------------------------------------------------------------- 3. kernels outside the step
-def _cent_dev(got, want):
-    mt = want[14]
-    parts = [(slice(0, 3), max(np.abs(want[0:3]).max(), 1.0)), (slice(3, 6), max(np.abs(want[3:6]).max(), 0.01)),
-             (slice(6, 9), max(np.abs(want[6:9]).max(), 0.01 * mt)), (slice(9, 12), max(np.abs(want[9:12]).max(), 0.01 * mt)),
-             (slice(12, 13), max(abs(want[12]), 0.01 * mt)), (slice(13, 14), abs(want[13])), (slice(14, 15), mt)]
-    return max(np.abs(got[sl] - want[sl]).max() / sc for sl, sc in parts)
-
-
 @pytest.mark.parametrize("name", ["deep_chain", "bushy"])
 def test_queries_outside_the_step(name, built):
     """link_transforms and head_position against the oracle's body poses; inverse_dynamics, mass_matrix, jacobian (the deepest link,
@@ -266,7 +259,7 @@ def test_queries_outside_the_step(name, built):
         for Jg, p in zip(jac, ((0.0, 0.0, 0.0), loc)):
             Jr = R.jacobian(om, s, link, p)
             dev["jac"] = max(dev["jac"], np.abs(Jg[e] - Jr).max() / np.abs(Jr).max())
-        dev["cent"] = max(dev["cent"], _cent_dev(c_gpu[e], R.centroidal(om, s, None, G)))
+        dev["cent"] = max(dev["cent"], cent_dev(c_gpu[e], R.centroidal(om, s, None, G)))
     print("%s queries, largest deviations: %s" % (name, {k: "%.3g" % x for k, x in dev.items()}))
     for k, x in dev.items():
         assert x <= min(4 * MEASURED[name][k], CAPS[k]), (name, k, x)

@@ -728,5 +728,8 @@ int trex_batch_time_steps(TrexBatch *batch, const float *actions_dev, float *obs
 /* So is the motion clip of a batch - reference poses that depend on time, tracking terms against them, and resets to an instant of
  * the clip: */
 #include "trex_motion.h"
+/* So is the sensor model of a batch - noise, bias, resolution and latency on the observation columns of the row the policy reads,
+ * latency on the actions: */
+#include "trex_sensing.h"
 
 #endif /* TREX_BATCH_H */

@@ -122,6 +122,21 @@ struct TrexBatch {
     std::vector<double> q_lower, q_upper;
     float *t0() const { return clock.as<float>(); }
   } motion;
+  // sensor model (trex_batch_set_sensing, include/trex_sensing.h): the group table, ONE device allocation laid out as
+  // sensing_limits.h says (`table`: its counts and maps, the blob dropped); the counters, ONE more, zeroed by every set: episode
+  // counts [n] u32 | row counts [n] u32 | started flags [n] u32 | drawn delays [n][G] i32; the history [9][n][delayed], only while
+  // a group can be late. seed, env_offset: of the last set, kept by a clear. The action delay (trex_batch_set_action_delay): its
+  // range, the action width it was set for, its counters [n] x 4 (ep | k | started | delay) and its history [9][n][cols]
+  struct Sensing {
+    trex::SenseTable table;
+    DeviceBuf blob, state, hist;
+    uint64_t seed = 0;
+    uint32_t env_offset = 0;
+    int act_min = 0, act_max = 0, act_cols = 0;
+    DeviceBuf act_state, act_hist;
+    uint32_t *ep() const { return state.as<uint32_t>(); }
+    uint32_t *act_ep() const { return act_state.as<uint32_t>(); }
+  } sensing;
   // fall termination (trex_batch_set_termination): the thresholds in force - a NaN is a criterion that is off - and the batch-owned
   // buffers of the predicate launch, ONE device allocation made by the first enabling call: terminal observations [n][3J], values
   // [n][3], reasons [n], reset mask [n], and done bytes [n] for a trex_batch_step call that passes no done buffer

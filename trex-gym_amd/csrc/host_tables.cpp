@@ -477,6 +477,56 @@ std::vector<TrexMotTerm> build_motion_terms(int nj, bool has_probes, const TrexM
   return out;
 }
 
+void check_sense_delay(const std::string &who, int delay_min, int delay_max) {
+  if (delay_min < 0 || delay_max > TREX_SENSE_MAXDELAY || delay_min > delay_max)
+    throw Refusal(who + "delays [" + std::to_string(delay_min) + ", " + std::to_string(delay_max) + "] outside 0 <= delay_min <= delay_max <= " +
+                  std::to_string(TREX_SENSE_MAXDELAY));
+}
+
+SenseTable build_sense_table(int obs_dim, const TrexSenseGroup *groups, int num_groups) {
+  const std::string me = "trex_batch_set_sensing: ";
+  SenseTable t;
+  if (num_groups == 0) return t;
+  if (num_groups < 0 || num_groups > TREX_SENSE_MAXGROUPS)
+    throw Refusal(me + "num_groups " + std::to_string(num_groups) + " outside [0, " + std::to_string(TREX_SENSE_MAXGROUPS) + "]");
+  if (!groups) throw Refusal(me + "null argument");
+  if (obs_dim < 1 || obs_dim > TREX_SENSE_MAXCOLS) throw Refusal(me + "the observation dimension " + std::to_string(obs_dim) + " is outside [1, " + std::to_string(TREX_SENSE_MAXCOLS) + "]");
+  t.groups = num_groups; t.obs_dim = obs_dim;
+  t.group.resize((size_t)num_groups);
+  t.col_group.assign((size_t)obs_dim, (int16_t)-1);
+  t.col_hist.assign((size_t)obs_dim, (int16_t)-1);
+  for (int g = 0; g < num_groups; g++) {
+    const TrexSenseGroup &c = groups[g];
+    const std::string ck = me + "group " + std::to_string(g) + ": ";
+    if (c.width < 1 || c.col0 < 0 || c.col0 >= obs_dim || c.width > obs_dim - c.col0)
+      throw Refusal(ck + "columns [" + std::to_string(c.col0) + ", " + std::to_string((long long)c.col0 + c.width) + ") outside [0, " + std::to_string(obs_dim) + ")");
+    if (c.noise_kind < 0 || c.noise_kind >= TREX_SENSE_KINDS) throw Refusal(ck + "unknown noise_kind " + std::to_string(c.noise_kind));
+    if (!std::isfinite(c.noise) || !std::isfinite(c.bias) || !std::isfinite(c.quantum)) throw Refusal(ck + "noise, bias or quantum is not finite");
+    if (c.noise < 0.f || c.bias < 0.f || c.quantum < 0.f) throw Refusal(ck + "noise, bias or quantum is negative");
+    const float inv = c.quantum > 0.f ? (float)(1.0 / (double)c.quantum) : 0.f;
+    if (!std::isfinite(inv)) throw Refusal(ck + "the inverse of quantum is not finite in f32");
+    check_sense_delay(ck, c.delay_min, c.delay_max);
+    for (int col = c.col0; col < c.col0 + c.width; col++) {
+      if (t.col_group[col] >= 0) throw Refusal(ck + "column " + std::to_string(col) + " is in group " + std::to_string(t.col_group[col]) + " already");
+      t.col_group[col] = (int16_t)g;
+    }
+    TrexSenseGrp &o = t.group[g];
+    std::memset(&o, 0, sizeof o);
+    o.col0 = c.col0; o.width = c.width; o.kind = c.noise_kind;
+    o.noise = c.noise; o.bias = c.bias; o.quantum = c.quantum; o.inv_quantum = inv;
+    o.delay_min = c.delay_min; o.delay_max = c.delay_max;
+  }
+  for (int col = 0; col < obs_dim; col++)   // the delayed columns, packed in column order
+    if (t.col_group[col] >= 0 && t.group[t.col_group[col]].delay_max > 0) t.col_hist[col] = (int16_t)t.delayed++;
+  t.o_col_group = t.group.size() * sizeof(TrexSenseGrp);
+  t.o_col_hist = t.o_col_group + (size_t)obs_dim * sizeof(int16_t);
+  t.blob.assign(t.o_col_hist + (size_t)obs_dim * sizeof(int16_t), 0);
+  std::memcpy(t.blob.data(), t.group.data(), t.o_col_group);
+  std::memcpy(t.blob.data() + t.o_col_group, t.col_group.data(), (size_t)obs_dim * sizeof(int16_t));
+  std::memcpy(t.blob.data() + t.o_col_hist, t.col_hist.data(), (size_t)obs_dim * sizeof(int16_t));
+  return t;
+}
+
 CameraBasis camera_basis(const TrexCamera &cam, int width, int height) {
   const float cv[] = {cam.distance, cam.yaw_deg, cam.pitch_deg, cam.fov_deg, cam.near_z, cam.far_z, cam.target[0], cam.target[1], cam.target[2]};
   for (float x : cv)

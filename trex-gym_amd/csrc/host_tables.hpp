@@ -1,5 +1,5 @@
 // The tables the kernels read, as pure host arithmetic: everything the C-ABI computes between its argument checks and its HIP calls.
-// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h, motion_limits.h and include/trex_batch.h, and nothing of HIP; it makes
+// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h, motion_limits.h, sensing_limits.h and include/trex_batch.h, and nothing of HIP; it makes
 // no HIP call and knows no batch. It builds with plain g++ -std=c++17, as model.cpp does, so that tests/host/tables_harness.cpp runs
 // it under the sanitizers on a machine without a GPU. A refusal is a thrown Refusal whose text is the C-ABI's message, whole.
 #pragma once
@@ -19,6 +19,7 @@ struct float4;
 #include "observation_limits.h"
 #include "proximity_limits.h"
 #include "reward_limits.h"
+#include "sensing_limits.h"
 
 namespace trex {
 
@@ -109,6 +110,20 @@ MotionTable build_motion_table(const std::vector<double> &q_lower, const std::ve
 // trex_batch_set_motion_reward: the terms checked and as the kernel reads them (a mask of 0 as all J bits). has_probes: the clip
 // names end effectors.
 std::vector<TrexMotTerm> build_motion_terms(int nj, bool has_probes, const TrexMotionTerm *terms, int num_terms, float step_weight);
+
+// trex_batch_set_sensing: the groups checked and as the kernel reads them, the column -> group map and the packing of the delayed
+// columns (those of a group with delay_max > 0, in column order: the rows of the history), and the blob the device holds, laid out
+// as sensing_limits.h says. obs_dim: 3J + E, the columns a group may cover. num_groups 0 gives the empty table.
+struct SenseTable {
+  int groups = 0, obs_dim = 0, delayed = 0;
+  std::vector<TrexSenseGrp> group;
+  std::vector<int16_t> col_group, col_hist;
+  size_t o_col_group = 0, o_col_hist = 0;
+  std::vector<char> blob;
+};
+SenseTable build_sense_table(int obs_dim, const TrexSenseGroup *groups, int num_groups);
+// trex_batch_set_action_delay, and the delays of a group: the range checked
+void check_sense_delay(const std::string &who, int delay_min, int delay_max);
 
 // trex_batch_render: the camera of include/trex_batch.h, checked, as the renderer's basis
 struct CameraBasis { float offset[3], fwd[3], right[3], up[3], tan_x, tan_y; };

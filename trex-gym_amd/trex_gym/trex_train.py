@@ -24,7 +24,7 @@ _URDF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ass
 
 def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0, push_force=0.0, push_interval=100,
                       push_duration=5, push_probability=1.0, seed=0, control_mode=None, variable_stiffness=False,
-                      gain_scale=0.0, terminate=None, observations=None, rewards=None, command=None, motion=None):   # (weights of trex_train.py:66)
+                      gain_scale=0.0, terminate=None, observations=None, rewards=None, command=None, motion=None, sensing=None):   # (weights of trex_train.py:66)
     # control_mode: what the joints' actions mean (position / velocity / torque: J-wide, through the trainer unchanged). The
     # 2J-wide stiffness action space is wider than the policy kernel's act_dim <= 32: refused here, not deep in a launch
     check_action_space(control_mode, variable_stiffness)
@@ -90,6 +90,25 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
         M.attach(env, motion["clip"], terms=terms, end_effectors=feet, rsi=bool(motion.get("rsi", False)), seed=seed)
         # what a checkpoint stores: the clip's path, the terms as set (the weight is in them), the rsi flag
         env.motion_config = dict(clip=str(motion["clip"]), rsi=bool(motion.get("rsi", False)), weight=1.0, terms=M.as_tuples(terms))
+    # sensing: dict(preset="typical" or None, scale=, obs_delay=(min, max), action_delay=(min, max)) as the flags give it, or
+    # dict(groups=, action_delay=, seed=) - a checkpoint's, the recorded specification of trex_gym.sensing.attach: the policy reads
+    # its observations through sensors (noise, bias, resolution, latency, on the device) and its actions reach the motors late
+    env.sensing_config = None
+    if sensing is not None:
+        from . import sensing as S
+        if "groups" in sensing:
+            spec, sense_seed = S.from_tuples(sensing["groups"]), sensing.get("seed", seed)
+        else:
+            sense_seed, delay = seed, tuple(sensing.get("obs_delay") or (0, 0))
+            if sensing.get("preset") is not None:
+                if sensing["preset"] not in S.PRESETS:
+                    raise ValueError("--sensing: expected one of %s, got %r" % (", ".join(sorted(S.PRESETS)), sensing["preset"]))
+                spec = S.PRESETS[sensing["preset"]](env, scale=float(sensing.get("scale", 1.0)), delay=delay)
+            else:   # (a latency alone: on q, qd and every channel the env composes itself)
+                spec = S.latency([(0, 2 * env.J)] + ([(3 * env.J, env.obs_dim - 3 * env.J)] if env.obs_dim > 3 * env.J else []), delay) \
+                    if delay[1] > 0 else []
+        S.attach(env, spec, action_delay=tuple(sensing.get("action_delay") or (0, 0)), seed=sense_seed)
+        env.sensing_config = env.sensing     # what a checkpoint stores: the groups as set, the action delay, the seed
     if command is not None:
         if rewards is None:
             raise ValueError("--command: there are no reward terms to track it (--rewards)")
@@ -141,8 +160,9 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
                     "obs_var": torch.tensor(st["obs_var"]), "obs_count": torch.tensor(float(st["obs_count"])),
                     "ret_var": torch.tensor(float(st["ret_var"])),
                     "observations": _own_channels(env), "rewards": getattr(env, "rewards", None),
-                    "command": getattr(env, "command", None), "motion": getattr(env, "motion_config", None)},
-                   save_path)   # (the channels, the terms and the clip: --play rebuilds the same row)
+                    "command": getattr(env, "command", None), "motion": getattr(env, "motion_config", None),
+                    "sensing": getattr(env, "sensing_config", None)},
+                   save_path)   # (the channels, the terms, the clip and the sensor model: --play rebuilds the same row)
     return agent, hist
 
 
@@ -209,12 +229,13 @@ def play(agent, num_play_timesteps, export_path=None, env_index=0, log=print, de
     return np.stack(frames), np.array(rewards)
 
 
-def load_agent(load_path, num_envs=1, device="cuda:0", max_episode_steps=1000):
+def load_agent(load_path, num_envs=1, device="cuda:0", max_episode_steps=1000, sensing=True):
     """trex_train.py:75-110 (replay): rebuild the policy from a file written by train(save_path=...) - the flat
-    parameter vector and VecNormalize's statistics."""
+    parameter vector and VecNormalize's statistics. sensing=False: without the sensor model the checkpoint was trained with."""
     ck = torch.load(load_path, map_location=device, weights_only=True)
     env = build_environment(num_envs, device=device, max_episode_steps=max_episode_steps, observations=ck.get("observations"),
-                            rewards=ck.get("rewards"), command=ck.get("command"), motion=ck.get("motion"))
+                            rewards=ck.get("rewards"), command=ck.get("command"), motion=ck.get("motion"),
+                            sensing=ck.get("sensing") if sensing else None)
     agent = PPO(env, nsteps=1, nminibatches=1, noptepochs=1)
     with torch.no_grad():
         agent.policy.theta.copy_(ck["theta"])
@@ -271,6 +292,15 @@ def parse_args(argv=None):
                          "locomotion and --rewards that is 93 + 3 + 2 = 98 columns, more than the learner's 96: not supported)")
     ap.add_argument("--rsi", action="store_true", help="with --motion: every new episode starts at a random instant of the clip")
     ap.add_argument("--motion_weight", type=float, default=1.0, help="with --motion: a factor on the weights of the tracking terms")
+    ap.add_argument("--sensing", choices=["typical"], default=None,
+                    help="the policy reads its observations through sensors, on the device; typical: white noise on q, qd, the base's "
+                         "tilt, velocities and height, a bias per episode on q, tilt and gyro, a 12-bit encoder (trex_gym.sensing.typical)")
+    ap.add_argument("--sense_scale", type=float, default=1.0, help="with --sensing: a factor on the preset's noise and bias")
+    ap.add_argument("--obs_delay", type=int, nargs=2, default=None, metavar=("MIN", "MAX"),
+                    help="sensing latency in env-steps, drawn per env and episode in [MIN, MAX] (at most 8)")
+    ap.add_argument("--action_delay", type=int, nargs=2, default=None, metavar=("MIN", "MAX"),
+                    help="actuation latency in env-steps, drawn per env and episode in [MIN, MAX] (at most 8)")
+    ap.add_argument("--no_sensing", action="store_true", help="with --play: run the policy without the sensor model it was trained with")
     ap.add_argument("--fall_penalty", type=float, default=0.0, help="taken from the reward of the step in which an episode ends by a fall")
     args = ap.parse_args(argv)
     if args.variable_stiffness:
@@ -284,6 +314,14 @@ def parse_args(argv=None):
         ap.error("--rsi and --motion_weight need --motion")
     if args.rsi and args.graphs:   # (the instants are drawn per step by a generator of the env's own: not in a replayed graph)
         ap.error("--rsi cannot be combined with --graphs")
+    if args.sensing is None and args.sense_scale != 1.0:
+        ap.error("--sense_scale needs --sensing")
+    if not (args.sense_scale >= 0.0):
+        ap.error("--sense_scale must not be negative")
+    for name in ("obs_delay", "action_delay"):
+        d = getattr(args, name)
+        if d is not None and not 0 <= d[0] <= d[1] <= 8:
+            ap.error("--%s: 0 <= MIN <= MAX <= 8" % name)
     if not 0.0 <= args.gain_scale < 1.0:
         ap.error("--gain_scale must lie in [0, 1)")
     if args.push_force > 0 and args.graphs:   # (the pushes are drawn per step on the host's step count: not in a replayed graph)
@@ -291,6 +329,14 @@ def parse_args(argv=None):
     if args.gain_scale > 0 and args.graphs and termination_args(args):   # (a fallen env draws new gains: host work per step)
         ap.error("--gain_scale with a --terminate_* criterion cannot be combined with --graphs")
     return args
+
+
+def sensing_args(args):
+    """the dict for build_environment(sensing=...) of the --sensing, --sense_scale, --obs_delay and --action_delay flags, None when
+    none is given"""
+    if args.sensing is None and args.obs_delay is None and args.action_delay is None:
+        return None
+    return dict(preset=args.sensing, scale=args.sense_scale, obs_delay=args.obs_delay, action_delay=args.action_delay)
 
 
 def termination_args(args):
@@ -309,7 +355,8 @@ def environment_from_args(args):
                             push_force=args.push_force, push_interval=args.push_interval, push_duration=args.push_duration,
                             seed=args.random_seed, control_mode=None if args.control_mode == "position" else args.control_mode,
                             gain_scale=args.gain_scale, observations=args.observations, rewards=args.rewards, command=args.command,
-                            motion=None if args.motion is None else dict(clip=args.motion, rsi=args.rsi, weight=args.motion_weight))
+                            motion=None if args.motion is None else dict(clip=args.motion, rsi=args.rsi, weight=args.motion_weight),
+                            sensing=sensing_args(args))
     if terminate is not None:   # (set on the built env: 'auto' needs its model - every body that does not stand on the floor at the start)
         if terminate["keep_clear"] == ["auto"]:
             from .termination import fall_bodies
@@ -324,6 +371,9 @@ def main(argv=None):
     agent, _ = train(env, args.num_timesteps, args.random_seed, args.nsteps, args.noptepochs, args.save, use_graphs=args.graphs,
                      preset=args.preset)
     if args.play:
+        if args.no_sensing and env.sense_api is not None:     # (the env the policy was trained in, its sensors taken off)
+            from . import sensing as S
+            S.attach(env, None)
         play(agent, args.num_play_timesteps, args.export, deterministic=args.play_deterministic, update_stats=not args.play_deterministic,
              frames_dir=args.frames)
 

@@ -66,7 +66,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         base axes, yaw rate; zeros) is a device tensor to write in place, `reward_terms` [n, T] the weighted value of every term
         at the last step (a tensor the caller may replace by another [n, T] block, e.g. a slice of a rollout buffer), `reward_names` their names, `reward_api` the batch's calls (reward_capi.BatchRewards). The commands join the observations through
         observations.external(3) with external=lambda env: env.commands. None (default): nothing changes - not a launch, not a byte.
-        A motion clip with its tracking terms is attached to a constructed env by trex_gym.motion.attach(env, clip, ...)."""
+        A motion clip with its tracking terms is attached to a constructed env by trex_gym.motion.attach(env, clip, ...), a sensor
+        model - noise, bias, resolution and latency on what the policy reads, latency on its actions - by
+        trex_gym.sensing.attach(env, spec, ...)."""
         self.global_num_envs = int(num_envs)
         self.rank, self.world_size, self.process_group = int(rank), int(world_size), process_group
         self.env_lo, self.env_hi = sharding.shard_range(self.global_num_envs, self.rank, self.world_size)
@@ -123,6 +125,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self._rew_actions = False
         self.motion, self.motion_api, self.motion_terms, self.motion_names = None, None, None, []
         self._rsi = False
+        self.sensing, self.sense_api, self.clean_rows, self.clean_obs = None, None, None, None
+        self._clean_block, self._delayed_actions = None, None
         self.collision = collision
         self._init_queries()                    # the link table and the caches of the read-only queries (vec_queries.py)
         if observations is not None and len(observations):
@@ -175,9 +179,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         sp = self.observation_space
         self.observation_space = spaces.Box(low=np.concatenate([sp.low, -big]), high=np.concatenate([sp.high, big]), dtype=np.float32)
 
-    def _compose(self, actions):
+    def _compose(self, actions, out=None):
         ext = self._external(self) if callable(self._external) else self._external
-        self.batch.compose_rows(self._step_rows, self.rows, actions, None if ext is None else self._dev(ext))
+        self.batch.compose_rows(self._step_rows, self.rows if out is None else out, actions, None if ext is None else self._dev(ext))
 
     # ---- reward terms (trex_batch_set_reward / trex_batch_compose_reward; trex_gym.rewards builds specifications)
     def _set_rewards(self, spec):
@@ -252,6 +256,39 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self._rsi_time.uniform_(0.0, self._rsi_span, generator=self._rsi_gen)
         self.motion_api.reset(mask, self._rsi_time, rows)
 
+    # ---- sensor model (trex_batch_set_sensing and its kin, include/trex_sensing.h; trex_gym.sensing builds specifications)
+    def _set_sensing(self, spec, action_delay=0, seed=0):
+        """What trex_gym.sensing.attach(env, ...) does (the constructor's signature is a recorded one and takes no `sensing`):
+        the groups of `spec` (trex_gym.sensing; merged) go to the batch, and every row the env composes passes through them by
+        one more launch per step and reset (trex_batch_apply_sensing) behind the last compose: the env composes into a block of
+        its own, `clean_rows` (`clean_obs` its observation columns), and `rows` / `obs` - what the policy, the trainer and the
+        gathers read - hold the sensors' view. action_delay - steps or (min, max) - delays the actions by one more launch before
+        the step call (trex_batch_delay_actions); the reward terms and the prev_action channel keep reading the policy's own
+        action. `sense_api` is the batch's calls (sensing_capi.BatchSensing), `sensing` the recorded specification:
+        dict(groups=, action_delay=, seed=). The Philox key is `seed`, the env offset `env_lo`. An empty spec sets only the action
+        delay (`clean_rows` is `rows` then). spec None clears the batch's groups and delay and takes all of this off the env
+        again. Never called, or cleared: nothing changes - not a launch, not a byte."""
+        from . import sensing as S, sensing_capi
+        if spec is None:
+            if self.sense_api is not None:
+                self.sense_api.set_sensing(())
+                self.sense_api.set_action_delay(0, 0)
+            self.sensing, self.sense_api, self.clean_rows, self.clean_obs = None, None, None, None
+            self._clean_block, self._delayed_actions = None, None
+            return
+        groups = S.merge(spec)
+        lo, hi = S.delay_range(action_delay)
+        api = sensing_capi.BatchSensing(self.batch)
+        api.set_sensing([tuple(g) for g in groups], seed, self.env_lo)
+        api.set_action_delay(lo, hi)
+        self.sense_api = api
+        self.sensing = dict(groups=S.as_tuples(groups), action_delay=[lo, hi], seed=int(seed))
+        self._clean_block = torch.zeros_like(self.rows) if groups else None
+        self._delayed_actions = torch.zeros(self.num_envs, self.A, device=self.device) if hi > 0 else None
+        if self._clean_block is not None:
+            self._clean_block.copy_(self.rows)
+        self._point_at(self._row_k)
+
     def _dev(self, t, dtype=torch.float32):
         """t as a contiguous `dtype` tensor on the env's device: t ITSELF where it is one already - no copy, no launch."""
         if t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
@@ -263,14 +300,19 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         """Reset all envs (mask=None) or those with mask != 0 (uint8 or bool [n], e.g. the `done` of the last step).
         Returns obs [n, 3J]; the reward / done columns and `done` of the envs that were reset read 0 afterwards.
         With observations: obs [n, 3J + E], every env's channels recomposed at the current state, prev_action() columns zero."""
-        rows = self.rows if self._step_rows is None else self._step_rows
+        out = self.rows if self._clean_block is None else self._clean_block      # (with sensing: the clean block)
+        rows = out if self._step_rows is None else self._step_rows
         if self.motion is not None and not self._rsi:     # clocks and held values of the envs to 0 (the state it writes is replaced next)
             self.motion_api.reset(mask)
         self.batch.reset_rows(rows, mask)
         if self._rsi:
             self._motion_rsi(rows, mask)
         if self._step_rows is not None:
-            self._compose(None)
+            self._compose(None, out)
+        if self._clean_block is not None or self._delayed_actions is not None:   # the envs that were reset start an episode of their sensors and of their action history
+            self.sense_api.reset(mask)
+            if self._clean_block is not None:   # the sensors' view of the clean block into the block the policy reads
+                self.sense_api.apply(out, self.rows)
         if self.rewards is not None:            # the envs that were reset have no previous step: their reward history starts afresh
             self.reward_api.reward_reset(mask)
         if self.gains is not None:              # the envs that were reset draw new motor gains
@@ -309,19 +351,28 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         # the finished step less the penalty, observation of the new episode)
         # (reward terms: one more launch behind the step call, on the rows it wrote - before the channels' compose, which carries
         # the composed reward along in the tail)
+        # (sensing: the motors get the action of some steps ago - `done` still holds the flags of the step before -, the launches
+        # below compose the clean block, and one more launch behind them writes the sensors' view into `rows`)
+        applied = actions
+        if self._delayed_actions is not None:
+            self.sense_api.delay_actions(actions, self._delayed_actions, self.done)
+            applied = self._delayed_actions
+        out = self.rows if self._clean_block is None else self._clean_block
         if self._step_rows is None:
-            self.batch.step_rows(actions, self.rows, self._penalties, done=self.done)   # (None: the penalties ride in the row block)
+            self.batch.step_rows(applied, out, self._penalties, done=self.done)   # (None: the penalties ride in the row block)
             if self.rewards is not None:
-                self._compose_reward(self.rows, actions)
+                self._compose_reward(out, actions)
             if self.motion is not None:
-                self._motion_step(self.rows)
+                self._motion_step(out)
         else:   # (observation channels: one more launch, after the resets of the step call - the row of the new episode's state)
-            self.batch.step_rows(actions, self._step_rows, self._penalties, done=self.done)
+            self.batch.step_rows(applied, self._step_rows, self._penalties, done=self.done)
             if self.rewards is not None:
                 self._compose_reward(self._step_rows, actions)
             if self.motion is not None:           # (before the channels' compose, which then sees the state RSI wrote)
                 self._motion_step(self._step_rows)
-            self._compose(actions)
+            self._compose(actions, out)
+        if self._clean_block is not None:       # behind the last compose: the sensors' view into the block the policy reads
+            self.sense_api.apply(out, self.rows)
         if self._term_on and self.gains is not None:   # the envs that fell start their episode with new motor gains
             self.set_motor_gains(**self.gains.draw(self.termination_reason != 0))
         return self.obs, self.rew, self.done
@@ -330,7 +381,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         """Open-loop rollout: actions [S, n, J] f32 on device -> rows [S, n, 3J+2] (obs | reward | done of every step), S
         env-steps in ONE launch (trex_batch_step_many; bitwise S calls of step_tensor). `rows`, `obs`, `rew`, `done_f`
         and `done` then hold the last step. sharding.split_rows(rows[s]) cuts a step's block into the three.
-        ValueError with observations, rewards or motion: an open-loop launch has no compose between its steps."""
+        ValueError with observations, rewards, motion or sensing: an open-loop launch has no compose between its steps."""
+        if self.sense_api is not None:
+            raise ValueError("step_many_tensor: not with sensing - the open-loop launch has no per-step launch of the sensor model")
         if self.motion is not None:
             raise ValueError("step_many_tensor: not with motion - the open-loop launch has no per-step compose of the tracking terms")
         if self.rewards is not None:
@@ -365,6 +418,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self.obs, self.rew, self.done_f = self.rows[:, :D], self.rows[:, D], self.rows[:, D + 1]
         # lifting_com, station_keeping, energy (trex_env.py:193-195)
         self.penalties = self.rows[:, D + 2:D + 5] if self._pen_in_rows else self._penalties
+        if self.sense_api is not None:          # (with sensing: the block the env composes, before the sensors)
+            self.clean_rows = self.rows if self._clean_block is None else self._clean_block
+            self.clean_obs = self.clean_rows[:, :D]
 
     def all_gather_rows(self, rows=None):
         """[global N, 3J+2] = obs | reward | done of EVERY env, on every rank: the one collective of the path

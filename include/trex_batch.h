@@ -731,5 +731,8 @@ int trex_batch_time_steps(TrexBatch *batch, const float *actions_dev, float *obs
 /* So is the sensor model of a batch - noise, bias, resolution and latency on the observation columns of the row the policy reads,
  * latency on the actions: */
 #include "trex_sensing.h"
+/* So is the episode randomisation of a batch - mass scale, friction, motor gains, pushes and the velocity command, redrawn on the
+ * device when an episode starts or at an interval inside it: */
+#include "trex_randomize.h"
 
 #endif /* TREX_BATCH_H */

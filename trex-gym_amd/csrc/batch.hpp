@@ -10,6 +10,7 @@
 #include "host_tables.hpp"
 #include "internal.hpp"
 #include "link_state.h"
+#include "randomize.h"
 
 using DeviceGuard = TrexDeviceGuard;
 
@@ -137,6 +138,18 @@ struct TrexBatch {
     uint32_t *ep() const { return state.as<uint32_t>(); }
     uint32_t *act_ep() const { return act_state.as<uint32_t>(); }
   } sensing;
+  // episode randomisation (trex_batch_set_randomization, include/trex_randomize.h): the term table (`table`: host side; `blob`: the
+  // TrexRandTable of randomize.h on the device); the state, ONE allocation zeroed by every set, laid out as `st` points into it
+  // (TrexRandState); the snapshots taken at the set - the gains buffer (`nominal`, with a KP / KD / MAX_FORCE term), the mass
+  // scale and the friction (with a term of that kind) - and the switches as they stood then: what a clear puts back
+  struct Randomization {
+    trex::RandTable table;
+    DeviceBuf blob, state, nominal, mass0, friction0;
+    TrexRandState st{};
+    uint64_t seed = 0;
+    uint32_t env_offset = 0;
+    bool was_domain = false, was_gains_set = false, was_ext_on = false;
+  } random;
   // fall termination (trex_batch_set_termination): the thresholds in force - a NaN is a criterion that is off - and the batch-owned
   // buffers of the predicate launch, ONE device allocation made by the first enabling call: terminal observations [n][3J], values
   // [n][3], reasons [n], reset mask [n], and done bytes [n] for a trex_batch_step call that passes no done buffer
@@ -166,5 +179,8 @@ inline int hip_fail(hipError_t e, const char *what) { return fail(TREX_E_HIP, st
   do {                                                                                                           \
     if (int _c = trex_check_device_buffer(b->device, b->seen, (p), (size_t)(bytes), (what))) return _c;          \
   } while (0)
+
+// the gains buffer of a batch whose actuator model is about to be used: allocated on first use, holding the model parameters (capi.cpp)
+int ensure_gains(TrexBatch *b);
 
 inline int check_batch(const TrexBatch *b) { return b ? TREX_OK : fail(TREX_E_INVALID, "null batch"); }

@@ -12,18 +12,6 @@ namespace {
 
 thread_local std::string g_error;
 
-// the gains buffer of a batch whose actuator model is about to be used: allocated on first use, holding the model parameters
-int ensure_gains(TrexBatch *b) {
-  if (b->gains) return TREX_OK;
-  DeviceGuard guard(b->device);
-  DeviceBuf g;
-  HIP_TRY(g.alloc((size_t)b->n * TREX_ACT_FLOATS * sizeof(float), false));
-  HIP_TRY(trex_launch_copy_gains(b->dmodel, nullptr, nullptr, nullptr, g.as<float>(), b->n, nullptr));
-  HIP_TRY(hipDeviceSynchronize());   // (in place before a launch on any stream)
-  b->gains = std::move(g);
-  return TREX_OK;
-}
-
 // What every launch of the batch's step kernels is given: the model, the state, the reward weights and the record / buffer of each
 // feature that is switched on - a non-null pointer IS the switch (step_launch.h). A reset takes no actions: no wave balance, no
 // external wrench, no actuator model. The caller adds the outputs and their strides.
@@ -82,6 +70,18 @@ hipError_t termination_tail(const TrexBatch *b, const TrexStepArgs &a, hipStream
 }
 
 }  // namespace
+
+// (declared in batch.hpp: capi_randomize.cpp needs it too)
+int ensure_gains(TrexBatch *b) {
+  if (b->gains) return TREX_OK;
+  DeviceGuard guard(b->device);
+  DeviceBuf g;
+  HIP_TRY(g.alloc((size_t)b->n * TREX_ACT_FLOATS * sizeof(float), false));
+  HIP_TRY(trex_launch_copy_gains(b->dmodel, nullptr, nullptr, nullptr, g.as<float>(), b->n, nullptr));
+  HIP_TRY(hipDeviceSynchronize());   // (in place before a launch on any stream)
+  b->gains = std::move(g);
+  return TREX_OK;
+}
 
 int trex_fail(int code, const std::string &msg) {
   g_error = msg;
@@ -588,12 +588,18 @@ int trex_batch_set_domain(TrexBatch *b, const float *mass_scale_dev, const float
 
 int trex_batch_set_external_wrench(TrexBatch *b, const float *wrench_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
-  if (!wrench_dev) { b->ext_on = false; return TREX_OK; }   // the default kernels again; the buffer stays for the next call
+  const TrexBatch::Randomization &rd = b->random;
+  const int pushes = rd.table.pushes;   // PUSH terms of the episode randomisation: the wrench stays on, this call sets its base
+  if (!wrench_dev && pushes == 0) { b->ext_on = false; return TREX_OK; }   // the default kernels again; the buffer stays for the next call
   DeviceGuard guard(b->device);
   BUF_TRY(wrench_dev, (size_t)b->n * b->nb * 6 * sizeof(float), "trex_batch_set_external_wrench: wrench");
   if (!b->ext)   // first use: a batch that never sets a wrench allocates nothing
     HIP_TRY(b->ext.alloc((size_t)b->n * 6 * TREX_TL * sizeof(float), false));
-  HIP_TRY(trex_launch_copy_wrench(wrench_dev, b->ext.as<float>(), b->n, b->nb, (hipStream_t)stream));
+  if (wrench_dev) HIP_TRY(trex_launch_copy_wrench(wrench_dev, b->ext.as<float>(), b->n, b->nb, (hipStream_t)stream));
+  else HIP_TRY(trex_launch_fill(b->ext.as<float>(), 0.f, b->n * 6 * TREX_TL, (hipStream_t)stream));
+  if (pushes > 0)   // the push bodies' columns: the caller's into the batch's copy, base + the force in effect into the buffer
+    HIP_TRY(trex_launch_randomize_rebase(rd.blob.as<TrexRandTable>(), rd.st, wrench_dev, b->ext.as<float>(), b->n, b->nb, pushes, 0,
+                                         (hipStream_t)stream));
   b->ext_on = true;
   return TREX_OK;
 }

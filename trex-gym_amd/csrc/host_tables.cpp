@@ -527,6 +527,61 @@ SenseTable build_sense_table(int obs_dim, const TrexSenseGroup *groups, int num_
   return t;
 }
 
+RandTable build_random_table(int nb, int nj, bool stiffness, const TrexRandomTerm *terms, int num_terms) {
+  const std::string me = "trex_batch_set_randomization: ";
+  RandTable t;
+  for (int &s : t.push_slot) s = -1;
+  if (num_terms == 0) return t;
+  if (num_terms < 0 || num_terms > TREX_RAND_MAXTERMS)
+    throw Refusal(me + "num_terms " + std::to_string(num_terms) + " outside [0, " + std::to_string(TREX_RAND_MAXTERMS) + "]");
+  if (!terms) throw Refusal(me + "null argument");
+  uint32_t covered[TREX_RAND_KINDS] = {};   // per kind: the elements (PUSH: the bodies, COMMAND: the components) taken so far
+  t.term.assign(terms, terms + num_terms);
+  for (int i = 0; i < num_terms; i++) {
+    TrexRandomTerm &c = t.term[i];
+    const std::string ck = me + "term " + std::to_string(i) + ": ";
+    if (c.kind < 0 || c.kind >= TREX_RAND_KINDS) throw Refusal(ck + "unknown kind " + std::to_string(c.kind));
+    if (!std::isfinite(c.lo) || !std::isfinite(c.hi)) throw Refusal(ck + "lo or hi is not finite");
+    if (c.lo > c.hi) throw Refusal(ck + "lo > hi");
+    if (!(c.probability >= 0.f && c.probability <= 1.f)) throw Refusal(ck + "probability outside [0, 1]");
+    uint32_t bits = 0u;
+    switch (c.kind) {
+      case TREX_RAND_MASS: case TREX_RAND_KP: case TREX_RAND_KD: case TREX_RAND_MAX_FORCE: {
+        const int count = c.kind == TREX_RAND_MASS ? nb : nj;
+        const uint32_t all = count >= 32 ? 0xFFFFFFFFu : (1u << count) - 1u;
+        if (c.mask & ~all) throw Refusal(ck + "a mask bit beyond the model's " + std::to_string(count) + (c.kind == TREX_RAND_MASS ? " bodies" : " joints"));
+        if ((c.kind == TREX_RAND_KP || c.kind == TREX_RAND_KD) && stiffness)
+          throw Refusal(ck + "KP and KD terms are refused while stiffness actions are on (the step launches write those columns)");
+        bits = c.mask ? c.mask : all;
+        c.mask = bits; c.shared = c.shared != 0;
+        if (c.kind == TREX_RAND_MASS) t.mass = true; else t.gains = true;
+        break;
+      }
+      case TREX_RAND_FRICTION:
+        bits = 1u; c.mask = 1u; c.shared = 1;
+        t.friction = true;
+        break;
+      case TREX_RAND_PUSH:
+        if (c.index < 0 || c.index >= nb) throw Refusal(ck + "body " + std::to_string(c.index) + " outside [0, " + std::to_string(nb) + ")");
+        if (c.interval < 1 || c.duration < 1) throw Refusal(ck + "a PUSH term needs interval >= 1 and duration >= 1");
+        if (t.pushes >= TREX_RAND_MAXPUSHES) throw Refusal(ck + "more than " + std::to_string(TREX_RAND_MAXPUSHES) + " PUSH terms");
+        bits = 1u << c.index; c.mask = 0u;
+        break;
+      default:   // TREX_RAND_COMMAND
+        if (c.index < 0 || c.index > 2) throw Refusal(ck + "command component " + std::to_string(c.index) + " outside [0, 2]");
+        if (c.interval < 0) throw Refusal(ck + "a COMMAND term needs interval >= 0");
+        bits = 1u << c.index; c.mask = 1u; c.shared = 1;
+        t.command = true;
+        break;
+    }
+    if (covered[c.kind] & bits) throw Refusal(ck + "overlaps an earlier term of its kind");
+    covered[c.kind] |= bits;
+    if (c.kind == TREX_RAND_PUSH) t.push_slot[i] = t.pushes++;
+  }
+  t.terms = num_terms;
+  return t;
+}
+
 CameraBasis camera_basis(const TrexCamera &cam, int width, int height) {
   const float cv[] = {cam.distance, cam.yaw_deg, cam.pitch_deg, cam.fov_deg, cam.near_z, cam.far_z, cam.target[0], cam.target[1], cam.target[2]};
   for (float x : cv)

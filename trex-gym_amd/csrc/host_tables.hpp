@@ -125,6 +125,18 @@ SenseTable build_sense_table(int obs_dim, const TrexSenseGroup *groups, int num_
 // trex_batch_set_action_delay, and the delays of a group: the range checked
 void check_sense_delay(const std::string &who, int delay_min, int delay_max);
 
+// trex_batch_set_randomization: the terms checked and as the kernel reads them - a mask of 0 as all the model's bodies (MASS) or
+// joints (KP, KD, MAX_FORCE), FRICTION and COMMAND as element 0 alone, PUSH as no element -, push_slot[t]: the index of term t
+// among the PUSH terms, -1 for another kind; what the terms need of the batch. nb, nj: the model's bodies and joints; stiffness:
+// stiffness actions are on. num_terms 0 gives the empty table.
+struct RandTable {
+  int terms = 0, pushes = 0;
+  std::vector<TrexRandomTerm> term;
+  int push_slot[TREX_RAND_MAXTERMS];
+  bool mass = false, friction = false, gains = false, command = false;
+};
+RandTable build_random_table(int nb, int nj, bool stiffness, const TrexRandomTerm *terms, int num_terms);
+
 // trex_batch_render: the camera of include/trex_batch.h, checked, as the renderer's basis
 struct CameraBasis { float offset[3], fwd[3], right[3], up[3], tan_x, tan_y; };
 CameraBasis camera_basis(const TrexCamera &cam, int width, int height);

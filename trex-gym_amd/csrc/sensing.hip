@@ -10,28 +10,15 @@
 #include "sensing.h"
 
 #include "../../include/trex_sensing.h"
+#include "philox.h"
 
 namespace {
 
 constexpr int BLOCK = TREX_SENSE_BLOCK;
 constexpr float TWO_PI = 6.2831855f;
 
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: Parallel random numbers: as easy as 1, 2, 3, SC 2011)
-__device__ __forceinline__ void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&r)[4]) {
-#pragma unroll
-  for (int round = 0; round < 10; round++) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
-
-__device__ __forceinline__ float u_half_open(uint32_t r) { return (float)(r >> 8) * 5.9604644775390625e-8f; }          // [0, 1)
-__device__ __forceinline__ float u_open_closed(uint32_t r) { return (float)((r >> 8) + 1u) * 5.9604644775390625e-8f; }  // (0, 1]
+// (philox, u_half_open, u_open_closed, draw_int: philox.h)
 __device__ __forceinline__ float symmetric(uint32_t r) { return __fsub_rn(__fmul_rn(2.f, u_half_open(r)), 1.f); }       // 2u - 1, exact
-__device__ __forceinline__ int draw_int(uint32_t r, int lo, int hi) { return lo + (int)__umulhi(r, (uint32_t)(hi - lo + 1)); }
 
 // column j of a block's four standard normals
 __device__ __forceinline__ float normal(const uint32_t (&r)[4], int j) {

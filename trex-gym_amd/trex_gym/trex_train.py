@@ -24,7 +24,8 @@ _URDF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ass
 
 def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0, push_force=0.0, push_interval=100,
                       push_duration=5, push_probability=1.0, seed=0, control_mode=None, variable_stiffness=False,
-                      gain_scale=0.0, terminate=None, observations=None, rewards=None, command=None, motion=None, sensing=None):   # (weights of trex_train.py:66)
+                      gain_scale=0.0, terminate=None, observations=None, rewards=None, command=None, motion=None, sensing=None,
+                      randomize=None):   # (weights of trex_train.py:66)
     # control_mode: what the joints' actions mean (position / velocity / torque: J-wide, through the trainer unchanged). The
     # 2J-wide stiffness action space is wider than the policy kernel's act_dim <= 32: refused here, not deep in a launch
     check_action_space(control_mode, variable_stiffness)
@@ -114,6 +115,27 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
             raise ValueError("--command: there are no reward terms to track it (--rewards)")
         env.commands[:] = torch.tensor([float(x) for x in command], device=env.device)
     env.command = None if command is None else [float(x) for x in command]
+    # randomize: dict(preset="typical", scale=, push=, command_range=, command_interval=) as the flags give it, or dict(terms=, seed=)
+    # - a checkpoint's, the recorded specification of trex_gym.randomize.attach: mass scale, friction, motor gains, pushes and the
+    # command redrawn on the device when an episode starts or at an interval inside it (behind --command: the terms overwrite it)
+    env.randomize_config = None
+    if randomize is not None:
+        from . import randomize as Z
+        if "terms" in randomize:
+            spec, rand_seed = Z.from_tuples(randomize["terms"]), randomize.get("seed", seed)
+        else:
+            if randomize.get("preset") not in Z.PRESETS:
+                raise ValueError("--randomize: expected one of %s, got %r" % (", ".join(sorted(Z.PRESETS)), randomize.get("preset")))
+            kw = {}
+            if randomize.get("push") is not None:
+                kw["push_force"] = float(randomize["push"])
+            if randomize.get("command_interval") is not None:
+                kw["command_interval"] = int(randomize["command_interval"])
+            if randomize.get("command_range") is not None:
+                kw["command_range"] = tuple(float(x) for x in randomize["command_range"])
+            spec, rand_seed = Z.PRESETS[randomize["preset"]](env, scale=float(randomize.get("scale", 1.0)), **kw), seed
+        Z.attach(env, spec, seed=rand_seed)
+        env.randomize_config = env.randomization     # what a checkpoint stores: the terms as set, the seed
     if gain_scale > 0:   # every episode with motor gains and strength scaled by 1 +- gain_scale per env (RandomGains)
         dev = torch.device(device)
         r = (1.0 - gain_scale, 1.0 + gain_scale)
@@ -161,7 +183,7 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
                     "ret_var": torch.tensor(float(st["ret_var"])),
                     "observations": _own_channels(env), "rewards": getattr(env, "rewards", None),
                     "command": getattr(env, "command", None), "motion": getattr(env, "motion_config", None),
-                    "sensing": getattr(env, "sensing_config", None)},
+                    "sensing": getattr(env, "sensing_config", None), "randomize": getattr(env, "randomize_config", None)},
                    save_path)   # (the channels, the terms, the clip and the sensor model: --play rebuilds the same row)
     return agent, hist
 
@@ -229,13 +251,14 @@ def play(agent, num_play_timesteps, export_path=None, env_index=0, log=print, de
     return np.stack(frames), np.array(rewards)
 
 
-def load_agent(load_path, num_envs=1, device="cuda:0", max_episode_steps=1000, sensing=True):
+def load_agent(load_path, num_envs=1, device="cuda:0", max_episode_steps=1000, sensing=True, randomize=True):
     """trex_train.py:75-110 (replay): rebuild the policy from a file written by train(save_path=...) - the flat
-    parameter vector and VecNormalize's statistics. sensing=False: without the sensor model the checkpoint was trained with."""
+    parameter vector and VecNormalize's statistics. sensing=False: without the sensor model the checkpoint was trained with; randomize=False:
+    without its episode randomisation."""
     ck = torch.load(load_path, map_location=device, weights_only=True)
     env = build_environment(num_envs, device=device, max_episode_steps=max_episode_steps, observations=ck.get("observations"),
                             rewards=ck.get("rewards"), command=ck.get("command"), motion=ck.get("motion"),
-                            sensing=ck.get("sensing") if sensing else None)
+                            sensing=ck.get("sensing") if sensing else None, randomize=ck.get("randomize") if randomize else None)
     agent = PPO(env, nsteps=1, nminibatches=1, noptepochs=1)
     with torch.no_grad():
         agent.policy.theta.copy_(ck["theta"])
@@ -301,6 +324,17 @@ def parse_args(argv=None):
     ap.add_argument("--action_delay", type=int, nargs=2, default=None, metavar=("MIN", "MAX"),
                     help="actuation latency in env-steps, drawn per env and episode in [MIN, MAX] (at most 8)")
     ap.add_argument("--no_sensing", action="store_true", help="with --play: run the policy without the sensor model it was trained with")
+    ap.add_argument("--randomize", choices=["typical"], default=None,
+                    help="episode randomisation on the device, redrawn whenever an episode starts: typical: mass scale, friction, "
+                         "motor gains, a push of the base and - with --rewards - the command (trex_gym.randomize.typical)")
+    ap.add_argument("--rand_scale", type=float, default=1.0, help="with --randomize: a factor on the width of the preset's ranges")
+    ap.add_argument("--rand_push", type=float, default=None, metavar="N",
+                    help="with --randomize: the largest push in newtons; 0 drops the preset's push term")
+    ap.add_argument("--command_range", type=float, nargs=3, default=None, metavar=("VX", "VY", "WZ"),
+                    help="with --randomize: the half-widths the command's components are drawn in")
+    ap.add_argument("--command_interval", type=int, default=None, metavar="K",
+                    help="with --randomize: env-steps between two draws of the command inside an episode (0: per episode only)")
+    ap.add_argument("--no_randomize", action="store_true", help="with --play: run the policy without the episode randomisation it was trained with")
     ap.add_argument("--fall_penalty", type=float, default=0.0, help="taken from the reward of the step in which an episode ends by a fall")
     args = ap.parse_args(argv)
     if args.variable_stiffness:
@@ -322,6 +356,17 @@ def parse_args(argv=None):
         d = getattr(args, name)
         if d is not None and not 0 <= d[0] <= d[1] <= 8:
             ap.error("--%s: 0 <= MIN <= MAX <= 8" % name)
+    if args.randomize is None and (args.rand_scale != 1.0 or args.rand_push is not None or args.command_range is not None
+                                   or args.command_interval is not None):
+        ap.error("--rand_scale, --rand_push, --command_range and --command_interval need --randomize")
+    if not (args.rand_scale >= 0.0) or (args.rand_push is not None and not args.rand_push >= 0.0):
+        ap.error("--rand_scale and --rand_push must not be negative")
+    if args.command_range is not None and not all(x >= 0.0 for x in args.command_range):
+        ap.error("--command_range: half-widths must not be negative")
+    if args.command_interval is not None and args.command_interval < 0:
+        ap.error("--command_interval must not be negative")
+    if args.randomize is not None and (args.push_force > 0 or args.gain_scale > 0):   # (one owner per buffer)
+        ap.error("--randomize cannot be combined with --push_force or --gain_scale")
     if not 0.0 <= args.gain_scale < 1.0:
         ap.error("--gain_scale must lie in [0, 1)")
     if args.push_force > 0 and args.graphs:   # (the pushes are drawn per step on the host's step count: not in a replayed graph)
@@ -337,6 +382,15 @@ def sensing_args(args):
     if args.sensing is None and args.obs_delay is None and args.action_delay is None:
         return None
     return dict(preset=args.sensing, scale=args.sense_scale, obs_delay=args.obs_delay, action_delay=args.action_delay)
+
+
+def randomize_args(args):
+    """the dict for build_environment(randomize=...) of the --randomize, --rand_scale, --rand_push, --command_range and
+    --command_interval flags, None when --randomize is not given"""
+    if args.randomize is None:
+        return None
+    return dict(preset=args.randomize, scale=args.rand_scale, push=args.rand_push, command_range=args.command_range,
+                command_interval=args.command_interval)
 
 
 def termination_args(args):
@@ -356,7 +410,7 @@ def environment_from_args(args):
                             seed=args.random_seed, control_mode=None if args.control_mode == "position" else args.control_mode,
                             gain_scale=args.gain_scale, observations=args.observations, rewards=args.rewards, command=args.command,
                             motion=None if args.motion is None else dict(clip=args.motion, rsi=args.rsi, weight=args.motion_weight),
-                            sensing=sensing_args(args))
+                            sensing=sensing_args(args), randomize=randomize_args(args))
     if terminate is not None:   # (set on the built env: 'auto' needs its model - every body that does not stand on the floor at the start)
         if terminate["keep_clear"] == ["auto"]:
             from .termination import fall_bodies
@@ -374,6 +428,9 @@ def main(argv=None):
         if args.no_sensing and env.sense_api is not None:     # (the env the policy was trained in, its sensors taken off)
             from . import sensing as S
             S.attach(env, None)
+        if args.no_randomize and env.random_api is not None:  # (likewise its episode randomisation)
+            from . import randomize as Z
+            Z.attach(env, None)
         play(agent, args.num_play_timesteps, args.export, deterministic=args.play_deterministic, update_stats=not args.play_deterministic,
              frames_dir=args.frames)
 

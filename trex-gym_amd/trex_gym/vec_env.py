@@ -68,7 +68,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         observations.external(3) with external=lambda env: env.commands. None (default): nothing changes - not a launch, not a byte.
         A motion clip with its tracking terms is attached to a constructed env by trex_gym.motion.attach(env, clip, ...), a sensor
         model - noise, bias, resolution and latency on what the policy reads, latency on its actions - by
-        trex_gym.sensing.attach(env, spec, ...)."""
+        trex_gym.sensing.attach(env, spec, ...), episode randomisation - mass scale, friction, motor gains, pushes and commands
+        redrawn on the device - by trex_gym.randomize.attach(env, spec, ...)."""
         self.global_num_envs = int(num_envs)
         self.rank, self.world_size, self.process_group = int(rank), int(world_size), process_group
         self.env_lo, self.env_hi = sharding.shard_range(self.global_num_envs, self.rank, self.world_size)
@@ -127,6 +128,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self._rsi = False
         self.sensing, self.sense_api, self.clean_rows, self.clean_obs = None, None, None, None
         self._clean_block, self._delayed_actions = None, None
+        self.randomization, self.random_api, self.random_values = None, None, None
+        self._no_done = None
         self.collision = collision
         self._init_queries()                    # the link table and the caches of the read-only queries (vec_queries.py)
         if observations is not None and len(observations):
@@ -155,6 +158,41 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self._term_on, self._term_buf = False, None   # fall termination: on?, (reason, values, terminal_obs) buffers of the env
         if terminate:
             self.set_termination(**terminate)
+
+    # ---- episode randomisation (trex_batch_set_randomization and its kin, include/trex_randomize.h; trex_gym.randomize builds
+    # specifications)
+    def _set_randomization(self, spec, seed=0):
+        """What trex_gym.randomize.attach(env, ...) does (the constructor's signature is a recorded one): the terms of `spec`
+        (trex_gym.randomize; merged, link names of push terms resolved to bodies) go to the batch, and one more launch per step
+        (trex_batch_apply_randomization) - behind the step call, the reward compose and the motion step, before the channels'
+        compose - redraws them for the envs whose done column is set: the finished step is rewarded against the old command, the
+        first row of the new episode shows the new one. reset_tensor marks the envs it resets and applies at the same place.
+        `random_api` is the batch's calls (randomize_capi.BatchRandomization), `random_values` a [n, T, 32] tensor for its info(),
+        `randomization` the recorded specification: dict(terms=, seed=). Command terms write `commands` (made here where the env has
+        none). The Philox key is `seed`, the env offset `env_lo`. ValueError while the env has `pushes` or `gains`: one owner per
+        buffer. spec None clears the batch's terms - gains, wrench, mass scale and friction go back - and takes all of this off
+        the env again. Never called, or cleared: nothing changes - not a launch, not a byte."""
+        from . import randomize as R, randomize_capi
+        if spec is None:
+            if self.random_api is not None:
+                self.random_api.set(())
+            self.randomization, self.random_api, self.random_values, self._no_done = None, None, None, None
+            return
+        if self.pushes is not None or self.gains is not None:
+            raise ValueError("randomisation: the env has pushes or gains of trex_gym.perturb - one owner per buffer")
+        terms = []
+        for t in R.merge(spec):
+            if isinstance(t.index, str):
+                t = t._replace(index=int(self._links.link_body[self._links.index(t.index)]))
+            terms.append(t)
+        api = randomize_capi.BatchRandomization(self.batch)
+        api.set([tuple(t) for t in terms], seed, self.env_lo)
+        self.random_api = api
+        self.randomization = dict(terms=R.as_tuples(terms), seed=int(seed))
+        self.random_values = torch.zeros(self.num_envs, max(len(terms), 1), randomize_capi.ELEMENTS, device=self.device)
+        self._no_done = torch.zeros(self.num_envs, device=self.device)      # what a reset applies with: only the marked envs start
+        if self.commands is None and any(t.kind == randomize_capi.COMMAND for t in terms):
+            self.commands = torch.zeros(self.num_envs, 3, device=self.device)
 
     # ---- observation channels (trex_batch_set_observation / trex_batch_compose_rows; trex_gym.observations builds specifications)
     def _set_observations(self, spec):
@@ -307,6 +345,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self.batch.reset_rows(rows, mask)
         if self._rsi:
             self._motion_rsi(rows, mask)
+        if self.random_api is not None:         # the envs that were reset start an episode: their draws, before the compose shows them
+            self.random_api.reset(mask)
+            self.random_api.apply(self._no_done, self.commands)
         if self._step_rows is not None:
             self._compose(None, out)
         if self._clean_block is not None or self._delayed_actions is not None:   # the envs that were reset start an episode of their sensors and of their action history
@@ -342,6 +383,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
             raise ValueError("actions must have shape (%d, %d), got %s" % (self.num_envs, self.A, tuple(actions.shape)))
         # (with max_episode_steps the launch also resets the envs whose episode ends with this step: done = 1,
         # reward of the finished step, observation of the new episode - VecEnv semantics, no second launch)
+        if self.random_api is not None and (self.pushes is not None or self.gains is not None):
+            raise ValueError("randomisation: the env has pushes or gains of trex_gym.perturb - one owner per buffer")
         if self.pushes is not None:   # this step's pushes (those of envs that ended their episode last step are dropped)
             w = self.pushes.wrench(self.model.num_bodies, self.done).to(self.device)
             self.batch.set_external_wrench(w if self._wrench is None else w + self._wrench)
@@ -364,12 +407,16 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
                 self._compose_reward(out, actions)
             if self.motion is not None:
                 self._motion_step(out)
+            if self.random_api is not None:
+                self.random_api.apply(out, self.commands, 3 * self.J + 1)
         else:   # (observation channels: one more launch, after the resets of the step call - the row of the new episode's state)
             self.batch.step_rows(applied, self._step_rows, self._penalties, done=self.done)
             if self.rewards is not None:
                 self._compose_reward(self._step_rows, actions)
             if self.motion is not None:           # (before the channels' compose, which then sees the state RSI wrote)
                 self._motion_step(self._step_rows)
+            if self.random_api is not None:       # (the done column of the step's rows; the compose then shows the new command)
+                self.random_api.apply(self._step_rows, self.commands, 3 * self.J + 1)
             self._compose(actions, out)
         if self._clean_block is not None:       # behind the last compose: the sensors' view into the block the policy reads
             self.sense_api.apply(out, self.rows)
@@ -381,7 +428,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         """Open-loop rollout: actions [S, n, J] f32 on device -> rows [S, n, 3J+2] (obs | reward | done of every step), S
         env-steps in ONE launch (trex_batch_step_many; bitwise S calls of step_tensor). `rows`, `obs`, `rew`, `done_f`
         and `done` then hold the last step. sharding.split_rows(rows[s]) cuts a step's block into the three.
-        ValueError with observations, rewards, motion or sensing: an open-loop launch has no compose between its steps."""
+        ValueError with observations, rewards, motion, sensing or randomisation: an open-loop launch has no compose between its steps."""
+        if self.random_api is not None:
+            raise ValueError("step_many_tensor: not with randomisation - the open-loop launch has no per-step launch of the redraws")
         if self.sense_api is not None:
             raise ValueError("step_many_tensor: not with sensing - the open-loop launch has no per-step launch of the sensor model")
         if self.motion is not None:

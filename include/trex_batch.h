@@ -734,5 +734,8 @@ int trex_batch_time_steps(TrexBatch *batch, const float *actions_dev, float *obs
 /* So is the episode randomisation of a batch - mass scale, friction, motor gains, pushes and the velocity command, redrawn on the
  * device when an episode starts or at an interval inside it: */
 #include "trex_randomize.h"
+/* So is the episode monitor of a batch - the return, the length and the end reason of every finished episode, the window of the
+ * last W of them and its summary, kept on the device: */
+#include "trex_monitor.h"
 
 #endif /* TREX_BATCH_H */

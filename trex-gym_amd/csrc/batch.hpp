@@ -10,6 +10,7 @@
 #include "host_tables.hpp"
 #include "internal.hpp"
 #include "link_state.h"
+#include "monitor.h"
 #include "randomize.h"
 
 using DeviceGuard = TrexDeviceGuard;
@@ -150,6 +151,15 @@ struct TrexBatch {
     uint32_t env_offset = 0;
     bool was_domain = false, was_gains_set = false, was_ext_on = false;
   } random;
+  // episode monitor (trex_batch_set_monitor, include/trex_monitor.h): its shape and the layout of its state (`layout`: host side,
+  // window 0 = no monitor), the state itself, ONE allocation zeroed by every set, as `st` points into it (TrexMonState), and the
+  // global index of env 0; all freed by window 0 and with the batch
+  struct Monitor {
+    trex::MonitorLayout layout;
+    DeviceBuf state;
+    TrexMonState st{};
+    uint32_t env_offset = 0;
+  } monitor;
   // fall termination (trex_batch_set_termination): the thresholds in force - a NaN is a criterion that is off - and the batch-owned
   // buffers of the predicate launch, ONE device allocation made by the first enabling call: terminal observations [n][3J], values
   // [n][3], reasons [n], reset mask [n], and done bytes [n] for a trex_batch_step call that passes no done buffer

@@ -582,6 +582,49 @@ RandTable build_random_table(int nb, int nj, bool stiffness, const TrexRandomTer
   return t;
 }
 
+MonitorLayout monitor_layout(int n_envs, int window, int cols_a, int cols_b, uint32_t env_offset, int block) {
+  const std::string me = "trex_batch_set_monitor: ";
+  MonitorLayout m;
+  if (window == 0) return m;
+  if (window < 1 || window > TREX_MON_MAXWINDOW)
+    throw Refusal(me + "window " + std::to_string(window) + " outside [0, " + std::to_string(TREX_MON_MAXWINDOW) + "]");
+  if (cols_a < 0 || cols_b < 0) throw Refusal(me + "a negative column count");
+  if ((long long)cols_a + (long long)cols_b > TREX_MON_MAXCOLS)
+    throw Refusal(me + std::to_string((long long)cols_a + (long long)cols_b) + " columns, at most " + std::to_string(TREX_MON_MAXCOLS));
+  if (n_envs < 1) throw Refusal(me + "a batch without envs");
+  if ((uint64_t)env_offset + (uint64_t)n_envs > (1ull << 32)) throw Refusal(me + "env_offset + N is beyond 2^32");
+  m.window = window; m.cols_a = cols_a; m.cols_b = cols_b; m.cols = cols_a + cols_b;
+  while (m.team < m.cols) m.team *= 2;
+  const int per = block / m.team;
+  m.groups = (n_envs + per - 1) / per;
+  const size_t n = (size_t)n_envs, C = (size_t)m.cols, W = (size_t)window;
+  size_t at = 0;
+  auto take = [&at](size_t &member, size_t count, size_t size) { member = at; at += count * size; };
+  take(m.ret, n, 8); take(m.col, n * C, 8); take(m.total, 1, 8); take(m.by_reason, 4, 8);
+  take(m.len, n, 4); take(m.episodes, n, 4); take(m.fin, n, 4);
+  take(m.last_return, n, 4); take(m.last_length, n, 4); take(m.last_reason, n, 4); take(m.last_t, n, 4); take(m.last_cols, n * C, 4);
+  take(m.t, 1, 4);
+  take(m.ring_return, W, 4); take(m.ring_length, W, 4); take(m.ring_reason, W, 4); take(m.ring_env, W, 4); take(m.ring_t, W, 4);
+  take(m.ring_cols, W * C, 4);
+  take(m.counts, (size_t)m.groups, 4);
+  m.bytes = at;
+  return m;
+}
+
+void check_monitor_apply(const MonitorLayout &m, bool reward, int reward_stride, bool done, int done_stride, bool block_a, int stride_a,
+                         bool block_b, int stride_b) {
+  const std::string me = "trex_batch_monitor_apply: ";
+  if (m.window < 1) throw Refusal(me + "no monitor is set (trex_batch_set_monitor)");
+  if (!reward) throw Refusal(me + "reward is null");
+  if (!done) throw Refusal(me + "done is null");
+  if (reward_stride < 1) throw Refusal(me + "reward_stride below 1");
+  if (done_stride < 1) throw Refusal(me + "done_stride below 1");
+  if (m.cols_a > 0 && !block_a) throw Refusal(me + "cols_a is null and its width is " + std::to_string(m.cols_a));
+  if (m.cols_b > 0 && !block_b) throw Refusal(me + "cols_b is null and its width is " + std::to_string(m.cols_b));
+  if (m.cols_a > 0 && stride_a < m.cols_a) throw Refusal(me + "stride_a " + std::to_string(stride_a) + " below the width " + std::to_string(m.cols_a));
+  if (m.cols_b > 0 && stride_b < m.cols_b) throw Refusal(me + "stride_b " + std::to_string(stride_b) + " below the width " + std::to_string(m.cols_b));
+}
+
 CameraBasis camera_basis(const TrexCamera &cam, int width, int height) {
   const float cv[] = {cam.distance, cam.yaw_deg, cam.pitch_deg, cam.fov_deg, cam.near_z, cam.far_z, cam.target[0], cam.target[1], cam.target[2]};
   for (float x : cv)

@@ -137,6 +137,21 @@ struct RandTable {
 };
 RandTable build_random_table(int nb, int nj, bool stiffness, const TrexRandomTerm *terms, int num_terms);
 
+// trex_batch_set_monitor: the shape checked, the team of lanes an env takes in the accumulate launch (the smallest power of two
+// that holds the C columns, at least 1), the workgroups of that launch, and the layout of the ONE allocation that is the
+// monitor's state - byte offsets, 8-byte members first, in the order of TrexMonState (monitor.h). block: the lanes of an
+// accumulate workgroup. window 0 gives the empty layout (bytes 0).
+struct MonitorLayout {
+  int window = 0, cols_a = 0, cols_b = 0, cols = 0, team = 1, groups = 0;
+  size_t ret = 0, col = 0, total = 0, by_reason = 0, len = 0, episodes = 0, fin = 0, last_return = 0, last_length = 0, last_reason = 0,
+         last_t = 0, last_cols = 0, t = 0, ring_return = 0, ring_length = 0, ring_reason = 0, ring_env = 0, ring_t = 0, ring_cols = 0,
+         counts = 0, bytes = 0;
+};
+MonitorLayout monitor_layout(int n_envs, int window, int cols_a, int cols_b, uint32_t env_offset, int block);
+// trex_batch_monitor_apply: the strides against the widths; the pointers as "is it there" flags
+void check_monitor_apply(const MonitorLayout &m, bool reward, int reward_stride, bool done, int done_stride, bool block_a, int stride_a,
+                         bool block_b, int stride_b);
+
 // trex_batch_render: the camera of include/trex_batch.h, checked, as the renderer's basis
 struct CameraBasis { float offset[3], fwd[3], right[3], up[3], tan_x, tan_y; };
 CameraBasis camera_basis(const TrexCamera &cam, int width, int height);

@@ -195,6 +195,7 @@ class PPO:
         self.b_motion = torch.zeros(nsteps, n, mt.shape[1], device=self.dev) if mt is not None else None
         self.motion_sum = torch.zeros(mt.shape[1], device=self.dev) if mt is not None else None
         self.mean_motion = None
+        self.episode_stats, self._monitor_out = None, None      # the episode monitor's window (trex_gym.monitor.attach), per rollout
         env.reset_tensor()
         self.kern.observe(env.rows, with_reward=False)           # VecNormalize.reset: the statistics see the first obs
 
@@ -250,6 +251,14 @@ class PPO:
             self.mean_terms = [x / (T * n) for x in self.term_sum.tolist()]
         if self.motion_sum is not None:
             self.mean_motion = [x / (T * n) for x in self.motion_sum.tolist()]
+        mon = getattr(self.env, "monitor_api", None)
+        if mon is not None:     # (the episode monitor's window: one launch and one small copy; its applies ran inside the rollout)
+            self._monitor_out = mon.summary(self._monitor_out)
+            summary = self._monitor_out.tolist()
+            if self.world > 1:
+                summary = self._merge_monitor(summary)
+            from . import monitor
+            self.episode_stats = monitor.stats_from_summary(summary, monitor.column_names(self.env))
         return (flat(self.b_obs), flat(self.b_act), flat(self.b_logp), flat(self.b_val[:T]), flat(self.b_adv), flat(self.b_ret),
                 mean_rew)
 
@@ -274,6 +283,15 @@ class PPO:
             st.update(ret_mean=float(rm), ret_var=float(rv), ret_count=rc)
         self.kern.set_stats(st)
         self._stats_prefix = {k: (np.array(st[k], np.float64) if hasattr(st[k], "__len__") else float(st[k])) for k in mine}
+
+    def _merge_monitor(self, summary):
+        """Once per rollout, beside _merge_statistics: the window of the episode monitor is per rank; every rank's window sums,
+        counts and extrema merged into one summary (trex_gym.monitor.merge_summaries)."""
+        import torch.distributed as dist
+        from . import monitor
+        everyone = [None] * self.world
+        dist.all_gather_object(everyone, list(summary), group=self.group)
+        return monitor.merge_summaries(everyone)
 
     def _dp_minibatch_stats(self, adv, perm, mb):
         dp_minibatch_stats(adv, perm, self.nminibatches, mb, self.world, self.mb_stats, self.group)
@@ -392,4 +410,11 @@ class PPO:
             if log and (self.mean_terms is not None or self.mean_motion is not None):   # (the motion terms beside the reward terms)
                 both = list(info.get("reward_terms", {}).items()) + list(info.get("motion_terms", {}).items())
                 log("        reward terms/step  " + "  ".join("%s %.4g" % kv for kv in both))
+            stats = self.episode_stats
+            if stats is not None:       # (baselines' eprewmean / eplenmean, and why the window's episodes ended)
+                info.update(eprewmean=stats["eprewmean"], eplenmean=stats["eplenmean"], episodes=stats["episodes"],
+                            end_reasons=stats["end_reasons"])
+                if log:
+                    log("        eprewmean %.4f  eplenmean %.2f  episodes %d  ended by  " % (stats["eprewmean"], stats["eplenmean"], stats["episodes"])
+                        + "  ".join("%s %.3f" % kv for kv in stats["end_reasons"].items()))
         return history

@@ -25,7 +25,7 @@ _URDF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ass
 def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0, push_force=0.0, push_interval=100,
                       push_duration=5, push_probability=1.0, seed=0, control_mode=None, variable_stiffness=False,
                       gain_scale=0.0, terminate=None, observations=None, rewards=None, command=None, motion=None, sensing=None,
-                      randomize=None):   # (weights of trex_train.py:66)
+                      randomize=None, monitor=None):   # (weights of trex_train.py:66)
     # control_mode: what the joints' actions mean (position / velocity / torque: J-wide, through the trainer unchanged). The
     # 2J-wide stiffness action space is wider than the policy kernel's act_dim <= 32: refused here, not deep in a launch
     check_action_space(control_mode, variable_stiffness)
@@ -141,6 +141,13 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
         r = (1.0 - gain_scale, 1.0 + gain_scale)
         env.gains = RandomGains(env.num_envs, env.J, kp_scale=r, kd_scale=r, max_force_scale=r,
                                 generator=torch.Generator(device=dev).manual_seed(int(seed) + 1), device=dev)
+    # monitor: dict(window=, terms=) - the flag's, or a checkpoint's: the episode monitor of trex_gym.monitor.attach, behind the
+    # rewards and the motion clip, whose term blocks it sums per episode
+    env.monitor_config = None
+    if monitor is not None:
+        from . import monitor as monitoring
+        monitoring.attach(env, window=int(monitor.get("window", 100)), terms=bool(monitor.get("terms", True)))
+        env.monitor_config = env.monitor             # what a checkpoint stores: settings only
     return env
 
 
@@ -183,7 +190,8 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
                     "ret_var": torch.tensor(float(st["ret_var"])),
                     "observations": _own_channels(env), "rewards": getattr(env, "rewards", None),
                     "command": getattr(env, "command", None), "motion": getattr(env, "motion_config", None),
-                    "sensing": getattr(env, "sensing_config", None), "randomize": getattr(env, "randomize_config", None)},
+                    "sensing": getattr(env, "sensing_config", None), "randomize": getattr(env, "randomize_config", None),
+                    "monitor": getattr(env, "monitor_config", None)},
                    save_path)   # (the channels, the terms, the clip and the sensor model: --play rebuilds the same row)
     return agent, hist
 
@@ -244,6 +252,12 @@ def play(agent, num_play_timesteps, export_path=None, env_index=0, log=print, de
             rgb = env.render_tensor([env_index], frame_size[0], frame_size[1], camera)[0].cpu().numpy()
             Image.fromarray(rgb).save(os.path.join(frames_dir, "%05d-of-%05d.png" % (len(rewards) - 1, num_play_timesteps)))
     log("Episode reward: %.3f over %d frames" % (sum(rewards), len(rewards)))
+    if getattr(env, "monitor_api", None) is not None:   # (the episode monitor's view: the last episode the env finished)
+        from . import monitor as monitoring
+        last = monitoring.last_episode(env)
+        log("Last finished episode: return %.3f, length %d, end reason %d; %d finished; running: return %.3f, length %d"
+            % (float(last["return"][env_index]), int(last["length"][env_index]), int(last["reason"][env_index]),
+               int(last["episodes"][env_index]), float(last["running_return"][env_index]), int(last["running_length"][env_index])))
     if export_path:
         table = env.model.visuals()
         np.savez_compressed(export_path, mesh_files=np.array([t[0] for t in table]), mesh_links=np.array([t[1] for t in table]),
@@ -258,7 +272,8 @@ def load_agent(load_path, num_envs=1, device="cuda:0", max_episode_steps=1000, s
     ck = torch.load(load_path, map_location=device, weights_only=True)
     env = build_environment(num_envs, device=device, max_episode_steps=max_episode_steps, observations=ck.get("observations"),
                             rewards=ck.get("rewards"), command=ck.get("command"), motion=ck.get("motion"),
-                            sensing=ck.get("sensing") if sensing else None, randomize=ck.get("randomize") if randomize else None)
+                            sensing=ck.get("sensing") if sensing else None, randomize=ck.get("randomize") if randomize else None,
+                            monitor=ck.get("monitor"))
     agent = PPO(env, nsteps=1, nminibatches=1, noptepochs=1)
     with torch.no_grad():
         agent.policy.theta.copy_(ck["theta"])
@@ -334,6 +349,9 @@ def parse_args(argv=None):
                     help="with --randomize: the half-widths the command's components are drawn in")
     ap.add_argument("--command_interval", type=int, default=None, metavar="K",
                     help="with --randomize: env-steps between two draws of the command inside an episode (0: per episode only)")
+    ap.add_argument("--monitor", type=int, nargs="?", const=100, default=None, metavar="WINDOW",
+                    help="episode monitor on the device: eprewmean, eplenmean and the end reasons of the last WINDOW (100) finished "
+                         "episodes per iteration (trex_gym.monitor)")
     ap.add_argument("--no_randomize", action="store_true", help="with --play: run the policy without the episode randomisation it was trained with")
     ap.add_argument("--fall_penalty", type=float, default=0.0, help="taken from the reward of the step in which an episode ends by a fall")
     args = ap.parse_args(argv)
@@ -356,6 +374,8 @@ def parse_args(argv=None):
         d = getattr(args, name)
         if d is not None and not 0 <= d[0] <= d[1] <= 8:
             ap.error("--%s: 0 <= MIN <= MAX <= 8" % name)
+    if args.monitor is not None and not 1 <= args.monitor <= 65536:
+        ap.error("--monitor: a window of 1 to 65536 episodes")
     if args.randomize is None and (args.rand_scale != 1.0 or args.rand_push is not None or args.command_range is not None
                                    or args.command_interval is not None):
         ap.error("--rand_scale, --rand_push, --command_range and --command_interval need --randomize")
@@ -384,6 +404,13 @@ def sensing_args(args):
     return dict(preset=args.sensing, scale=args.sense_scale, obs_delay=args.obs_delay, action_delay=args.action_delay)
 
 
+def monitor_args(args):
+    """the dict for build_environment(monitor=...) of the --monitor flag, None when it is not given"""
+    if args.monitor is None:
+        return None
+    return dict(window=args.monitor, terms=True)
+
+
 def randomize_args(args):
     """the dict for build_environment(randomize=...) of the --randomize, --rand_scale, --rand_push, --command_range and
     --command_interval flags, None when --randomize is not given"""
@@ -410,7 +437,7 @@ def environment_from_args(args):
                             seed=args.random_seed, control_mode=None if args.control_mode == "position" else args.control_mode,
                             gain_scale=args.gain_scale, observations=args.observations, rewards=args.rewards, command=args.command,
                             motion=None if args.motion is None else dict(clip=args.motion, rsi=args.rsi, weight=args.motion_weight),
-                            sensing=sensing_args(args), randomize=randomize_args(args))
+                            sensing=sensing_args(args), randomize=randomize_args(args), monitor=monitor_args(args))
     if terminate is not None:   # (set on the built env: 'auto' needs its model - every body that does not stand on the floor at the start)
         if terminate["keep_clear"] == ["auto"]:
             from .termination import fall_bodies

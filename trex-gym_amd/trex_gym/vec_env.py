@@ -130,6 +130,7 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self._clean_block, self._delayed_actions = None, None
         self.randomization, self.random_api, self.random_values = None, None, None
         self._no_done = None
+        self.monitor, self.monitor_api = None, None
         self.collision = collision
         self._init_queries()                    # the link table and the caches of the read-only queries (vec_queries.py)
         if observations is not None and len(observations):
@@ -193,6 +194,30 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self._no_done = torch.zeros(self.num_envs, device=self.device)      # what a reset applies with: only the marked envs start
         if self.commands is None and any(t.kind == randomize_capi.COMMAND for t in terms):
             self.commands = torch.zeros(self.num_envs, 3, device=self.device)
+
+    # ---- episode monitor (trex_batch_set_monitor and its kin, include/trex_monitor.h; trex_gym.monitor reads it)
+    def _set_monitor(self, window=100, terms=True):
+        """What trex_gym.monitor.attach(env, ...) does (the constructor's signature is a recorded one): the batch keeps every
+        episode's return, length, end reason and - with terms - the per-episode sums of the env's `reward_terms` and `motion_terms`
+        blocks, and a window of the last `window` finished episodes. Two more launches per step (trex_batch_monitor_apply) behind
+        the step call, the reward compose and the motion step read the step's own rows - columns 3J and 3J + 1 - and the two
+        blocks as they are at that call: the trainer points them at its rollout buffers, so they are arguments, not settings.
+        reset_tensor(mask) abandons the running episode of the envs it resets. `monitor_api` is the batch's calls
+        (monitor_capi.BatchMonitor), `monitor` the recorded settings: dict(window=, terms=). The env offset is `env_lo`. window
+        None or 0 clears the batch's monitor and takes all of this off the env again. Never called, or cleared: nothing changes -
+        not a launch, not a byte."""
+        from . import monitor_capi
+        if not window:
+            if self.monitor_api is not None:
+                self.monitor_api.set(0)
+            self.monitor, self.monitor_api = None, None
+            return
+        cols_a = int(self.reward_terms.shape[1]) if terms and self.reward_terms is not None else 0
+        cols_b = int(self.motion_terms.shape[1]) if terms and self.motion_terms is not None else 0
+        api = monitor_capi.BatchMonitor(self.batch)
+        api.set(int(window), cols_a, cols_b, self.env_lo)
+        self.monitor_api = api
+        self.monitor = dict(window=int(window), terms=bool(terms))
 
     # ---- observation channels (trex_batch_set_observation / trex_batch_compose_rows; trex_gym.observations builds specifications)
     def _set_observations(self, spec):
@@ -358,6 +383,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
             self.reward_api.reward_reset(mask)
         if self.gains is not None:              # the envs that were reset draw new motor gains
             self.set_motor_gains(**self.gains.draw(mask))
+        if self.monitor_api is not None:        # the running episode of the envs that were reset is abandoned, not recorded
+            self.monitor_api.reset(mask)
         if mask is None:
             self.done.zero_()
         else:
@@ -409,6 +436,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
                 self._motion_step(out)
             if self.random_api is not None:
                 self.random_api.apply(out, self.commands, 3 * self.J + 1)
+            if self.monitor_api is not None:
+                self.monitor_api.apply(out, out, None, self.reward_terms, self.motion_terms, 3 * self.J, 3 * self.J + 1)
         else:   # (observation channels: one more launch, after the resets of the step call - the row of the new episode's state)
             self.batch.step_rows(applied, self._step_rows, self._penalties, done=self.done)
             if self.rewards is not None:
@@ -417,6 +446,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
                 self._motion_step(self._step_rows)
             if self.random_api is not None:       # (the done column of the step's rows; the compose then shows the new command)
                 self.random_api.apply(self._step_rows, self.commands, 3 * self.J + 1)
+            if self.monitor_api is not None:      # (the reward and done columns of the step's rows: what the compose carries along)
+                self.monitor_api.apply(self._step_rows, self._step_rows, None, self.reward_terms, self.motion_terms, 3 * self.J, 3 * self.J + 1)
             self._compose(actions, out)
         if self._clean_block is not None:       # behind the last compose: the sensors' view into the block the policy reads
             self.sense_api.apply(out, self.rows)
@@ -428,9 +459,12 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         """Open-loop rollout: actions [S, n, J] f32 on device -> rows [S, n, 3J+2] (obs | reward | done of every step), S
         env-steps in ONE launch (trex_batch_step_many; bitwise S calls of step_tensor). `rows`, `obs`, `rew`, `done_f`
         and `done` then hold the last step. sharding.split_rows(rows[s]) cuts a step's block into the three.
-        ValueError with observations, rewards, motion, sensing or randomisation: an open-loop launch has no compose between its steps."""
+        ValueError with observations, rewards, motion, sensing or randomisation: an open-loop launch has no compose between its steps.
+        With a monitor attached its applies follow the launch, one per step block (not together with fall termination)."""
         if self.random_api is not None:
             raise ValueError("step_many_tensor: not with randomisation - the open-loop launch has no per-step launch of the redraws")
+        if self.monitor_api is not None and self._term_on:
+            raise ValueError("step_many_tensor: not with a monitor and fall termination - the batch keeps the last step's reasons only")
         if self.sense_api is not None:
             raise ValueError("step_many_tensor: not with sensing - the open-loop launch has no per-step launch of the sensor model")
         if self.motion is not None:
@@ -449,6 +483,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         # then holds the last step's, like the other views - it used to keep the values from BEFORE the call)
         self.penalties_many = None if self._pen_in_rows else torch.empty(S, self.num_envs, 3, device=self.device)
         self.batch.step_many(actions, rows, self.penalties_many)
+        if self.monitor_api is not None:        # once per step block, behind the launch: the monitor needs nothing between the steps
+            for s in range(S):
+                self.monitor_api.apply(rows[s], rows[s], None, None, None, 3 * self.J, 3 * self.J + 1)
         self.rows.copy_(rows[-1])
         if not self._pen_in_rows:
             self._penalties.copy_(self.penalties_many[-1])

@@ -124,4 +124,6 @@ int trex_policy_minibatch_step(TrexPolicy *policy, float *theta_dev, float *grad
 #ifdef __cplusplus
 }
 #endif
+/* the privileged critic of a policy object: a value net with an input row, a width and moments of its own */
+#include "trex_policy_critic.h"
 #endif /* TREX_POLICY_H */

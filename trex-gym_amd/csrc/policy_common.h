@@ -18,12 +18,12 @@ constexpr int MAXD = 128;      // LDS row of the observation tile (obs_dim + pad
 constexpr int OBS_ROWS = 64;   // rows per workgroup of observe_kernel
 constexpr float LOG_2PI = 1.8378770664093453f;
 
-struct Layout {   // offsets into theta, trex_policy.h order
-  int D, A;
+struct Layout {   // offsets into theta, trex_policy.h order (D: the policy net's input width; a critic's own width Dv only
+  int D, A;       // sizes vf.W1 and travels beside the layout: include/trex_policy_critic.h)
   int pW1, pb1, pW2, pb2, pW3, pb3, vW1, vb1, vW2, vb2, vW3, vb3, logstd, count;
 };
 
-__host__ __device__ inline Layout make_layout(int D, int A) {
+__host__ __device__ inline Layout make_layout(int D, int A, int Dv = 0) {      // Dv = 0: the value net reads the policy's row
   // every region starts on a multiple of 4 floats (16-byte loads when the kernels stage the parameters in LDS); the
   // pad elements are ordinary, unused parameters: zero gradient, never read
   Layout l{};
@@ -31,7 +31,7 @@ __host__ __device__ inline Layout make_layout(int D, int A) {
   int o = 0;
   auto take = [&](int n) { const int at = o; o = (o + n + 3) & ~3; return at; };
   l.pW1 = take(D * HID); l.pb1 = take(HID); l.pW2 = take(HID * HID); l.pb2 = take(HID); l.pW3 = take(HID * A); l.pb3 = take(A);
-  l.vW1 = take(D * HID); l.vb1 = take(HID); l.vW2 = take(HID * HID); l.vb2 = take(HID); l.vW3 = take(HID); l.vb3 = take(1);
+  l.vW1 = take((Dv ? Dv : D) * HID); l.vb1 = take(HID); l.vW2 = take(HID * HID); l.vb2 = take(HID); l.vW3 = take(HID); l.vb3 = take(1);
   l.logstd = take(A);
   l.count = o;
   return l;
@@ -82,6 +82,12 @@ struct TrexPolicy {
   unsigned *counter = nullptr;
   int *adam_step = nullptr;
   float epsilon = 1e-8f;        // VecNormalize's
+  // privileged critic (include/trex_policy_critic.h): Dv = 0 is none. Its moments have the observation block's shape - mean [Dv],
+  // var [Dv], count, then four slots the statistics kernels never touch without a reward -, with partial sums and an f32 image of
+  // their own; all three are allocated once, for the widest critic, by the first set
+  int Dv = 0;
+  double *stats_v = nullptr, *partial_v = nullptr;
+  float *norm_v = nullptr;
   // learner workspace (ppo_learner.hip), allocated on first use: per-tile gradient partials [tiles][count4]
   float *grad_partial = nullptr;
   int grad_tiles = 0;

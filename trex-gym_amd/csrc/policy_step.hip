@@ -25,6 +25,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/trex_batch.h"
@@ -42,6 +43,14 @@ struct ActArgs {
   float clip_obs;
   Layout lay;
 };
+// With a privileged critic (include/trex_policy_critic.h) the value net has a row block, a width, moments and a rollout copy of its
+// own: a per-net choice of pointers and of D in the vf workgroups (CRITIC = true). The plain launch is the CRITIC = false instantiation,
+// whose argument block and instructions are the ones it had before the template (profiles/r31_critic.txt).
+struct ActArgsV : ActArgs {
+  const float *rows_v, *norm_v;
+  float *obs_v_out;
+  int stride_v, Dv;
+};
 
 // One workgroup = (tile of 32 envs, net): 2 waves, each owning one HALF of the 64 neurons of a hidden layer (u = wave: 32
 // output rows = one MFMA tile); grid (tiles, 2) = 256 workgroups at 4096 envs - the whole chip (until round 4: 64 workgroups of
@@ -57,11 +66,22 @@ constexpr int ACT_XS = MAXD + 1, ACT_TS = TILE + 1;
 __host__ __device__ inline int act_lds_floats(const Layout &lay) {
   return ((lay.count + 3) & ~3) + TILE * ACT_XS + 2 * HID * ACT_TS + 32;      // theta image | X | H1, H2 parked | sd per action
 }
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) void act_kernel(ActArgs g) {      // (one wave per SIMD: the whole register file, no spills)
+template <bool CRITIC>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) void act_kernel(std::conditional_t<CRITIC, ActArgsV, ActArgs> g) {      // (one wave per SIMD: the whole register file, no spills)
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, u = tid >> 6, net = blockIdx.y;      // net 0: policy, 1: value
   if (g.value_only && net == 0) return;
-  const int D = g.lay.D, A = g.lay.A;
+  // this net's input: width, row block, moments, rollout copy. With a critic the value net has its own. (Chosen on the members
+  // of the argument block in place: handed by reference to a helper, the block lost the compiler's no-clobber marks on its loads
+  // and the plain kernel came out four instructions longer.)
+  int D = g.lay.D, row_stride = g.row_stride;
+  const float *rows = g.rows, *norm = g.norm;
+  float *obs_keep = g.obs_out;
+  bool keeps = net == 0;
+  if constexpr (CRITIC) {
+    if (net) { D = g.Dv; row_stride = g.stride_v; rows = g.rows_v; norm = g.norm_v; obs_keep = g.obs_v_out; keeps = true; }
+  }
+  const int A = g.lay.A;
   const int Dp8 = (D + 7) & ~7;         // K of the first layer, padded to four MFMA k-steps (k = 2 each); X is zero from column D on
   float *th = lds;                                       // parameters, theta's own layout (the other net's part stays unwritten)
   float *X = lds + ((g.lay.count + 3) & ~3);             // [TILE][MAXD + 1] normalised observations (+ zero pad)
@@ -75,8 +95,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   for (int q = 0; q < ACT_UX; q++) {
     const int idx = min(tid + 128 * q, TILE * Dp8 - 1), ii = idx / Dp8, kk = idx - ii * Dp8;
     const int kc = kk < D ? kk : D - 1, er = min(e0 + ii, g.n - 1);
-    raw[q] = g.rows[(size_t)er * g.row_stride + kc];
-    mean[q] = g.norm[kc]; rstd[q] = g.norm[D + kc];
+    raw[q] = rows[(size_t)er * row_stride + kc];
+    mean[q] = norm[kc]; rstd[q] = norm[D + kc];
   }
   float tpx[ACT_UF], tpy[ACT_UF], tpz[ACT_UF], tpw[ACT_UF];     // (as one float4 array the compiler kept it in scratch)
   const float4 *s4 = reinterpret_cast<const float4 *>(g.theta);
@@ -105,7 +125,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int idx = tid + 128 * q, ii = idx / Dp8, kk = idx - ii * Dp8;
     const bool in = idx < TILE * Dp8, ok = in && kk < D && e0 + ii < g.n;
     const float x = ok ? fminf(fmaxf((raw[q] - mean[q]) * rstd[q], -g.clip_obs), g.clip_obs) : 0.f;
-    if (ok && net == 0 && g.obs_out) g.obs_out[(size_t)(e0 + ii) * D + kk] = x;
+    if (ok && keeps && obs_keep) obs_keep[(size_t)(e0 + ii) * D + kk] = x;
     X[in ? ii * ACT_XS + kk : TILE * ACT_XS - 1] = in ? x : 0.f;         // (the dump slot is a pad column: never read)
   }
 #pragma unroll
@@ -571,6 +591,7 @@ int trex_policy_act(TrexPolicy *p, const float *theta_dev, const float *rows_dev
                     const float *noise_dev, float *actions_dev, float *obs_out, float *act_out, float *logp_out, float *value_out,
                     int value_only, void *stream) {
   if (!p || !theta_dev || !rows_dev) return trex_fail(TREX_E_INVALID, "trex_policy_act: null argument");
+  if (p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_act: the policy has a critic width set (trex_policy_critic_act takes its row)");
   if (!value_only && (!noise_dev || !actions_dev)) return trex_fail(TREX_E_INVALID, "trex_policy_act: noise / actions are null");
   if (value_only && !value_out) return trex_fail(TREX_E_INVALID, "trex_policy_act: value_out is null");
   if (row_stride < p->D) return trex_fail(TREX_E_INVALID, "trex_policy_act: row_stride < obs_dim");
@@ -587,7 +608,128 @@ int trex_policy_act(TrexPolicy *p, const float *theta_dev, const float *rows_dev
   ActArgs a{theta_dev, rows_dev, p->norm, noise_dev, actions_dev, obs_out, act_out, logp_out, value_out,
             p->n, row_stride, value_only ? 1 : 0, clip_obs, p->lay};
   const size_t lds_bytes = (size_t)act_lds_floats(p->lay) * sizeof(float);
-  hipLaunchKernelGGL(act_kernel, dim3((p->n + TILE - 1) / TILE, 2), dim3(128), lds_bytes, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(act_kernel<false>, dim3((p->n + TILE - 1) / TILE, 2), dim3(128), lds_bytes, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return TREX_OK;
+}
+
+// ---------------------------------------------------------------- privileged critic (include/trex_policy_critic.h)
+int trex_policy_set_critic(TrexPolicy *p, int critic_dim, void *stream) {
+  if (!p) return trex_fail(TREX_E_INVALID, "trex_policy_set_critic: null policy");
+  if (critic_dim < 0 || critic_dim > MAXD - 2) return trex_fail(TREX_E_INVALID, "trex_policy_set_critic: critic_dim must be in [0, 126] (0 clears)");
+  TrexDeviceGuard guard(p->device);
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  HIP_TRY(hipDeviceSynchronize());
+  if (critic_dim && !p->stats_v) {      // once, for the widest critic: a later set never allocates
+    constexpr int W = MAXD - 2;
+    double *st = nullptr, *pa = nullptr;
+    float *nm = nullptr;
+    hipError_t r = hipMalloc((void **)&st, (2 * W + 5) * sizeof(double));
+    if (r == hipSuccess) r = hipMalloc((void **)&pa, (size_t)p->G * (W + 2) * 2 * sizeof(double));
+    if (r == hipSuccess) r = hipMalloc((void **)&nm, (2 * W + 2) * sizeof(float));
+    if (r != hipSuccess) {
+      (void)hipFree(st); (void)hipFree(pa); (void)hipFree(nm);
+      return trex_fail(TREX_E_HIP, std::string("trex_policy_set_critic: hipMalloc: ") + hipGetErrorString(r));
+    }
+    p->stats_v = st; p->partial_v = pa; p->norm_v = nm;
+    p->allocs.push_back(st); p->allocs.push_back(pa); p->allocs.push_back(nm);
+  }
+  // the learner workspace's row stride is the parameter count: dropped, the next minibatch call makes its own
+  if (p->grad_partial) {
+    for (size_t i = 0; i < p->allocs.size(); i++)
+      if (p->allocs[i] == p->grad_partial) { p->allocs.erase(p->allocs.begin() + i); break; }
+    (void)hipFree(p->grad_partial);
+    p->grad_partial = nullptr; p->grad_tiles = 0;
+  }
+  p->Dv = critic_dim;
+  p->lay = make_layout(p->D, p->A, critic_dim);
+  if (critic_dim) {
+    const int Dv = critic_dim;
+    std::vector<double> st(2 * Dv + 5, 0.0);          // RunningMeanStd(epsilon = 1e-4), as init_stats
+    for (int k = 0; k < Dv; k++) st[Dv + k] = 1.0;
+    st[2 * Dv] = 1e-4; st[2 * Dv + 2] = 1.0; st[2 * Dv + 3] = 1e-4;
+    HIP_TRY(hipMemcpy(p->stats_v, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(refresh_norm_kernel, dim3(1), dim3(128), 0, (hipStream_t)stream, p->stats_v, p->norm_v, Dv, p->epsilon);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  }
+  return TREX_OK;
+}
+
+int trex_policy_critic_dim(const TrexPolicy *p) { return p ? p->Dv : trex_fail(TREX_E_INVALID, "null policy"); }
+
+int trex_policy_critic_get_stats(TrexPolicy *p, double *host, void *stream) {
+  if (!p || !host) return trex_fail(TREX_E_INVALID, "trex_policy_critic_get_stats: null argument");
+  if (!p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_critic_get_stats: no critic width is set (trex_policy_set_critic)");
+  TrexDeviceGuard guard(p->device);
+  HIP_TRY(hipMemcpyAsync(host, p->stats_v, (2 * p->Dv + 1) * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  return TREX_OK;
+}
+
+int trex_policy_critic_set_stats(TrexPolicy *p, const double *host, void *stream) {
+  if (!p || !host) return trex_fail(TREX_E_INVALID, "trex_policy_critic_set_stats: null argument");
+  if (!p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_critic_set_stats: no critic width is set (trex_policy_set_critic)");
+  TrexDeviceGuard guard(p->device);
+  HIP_TRY(hipMemcpyAsync(p->stats_v, host, (2 * p->Dv + 1) * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  hipLaunchKernelGGL(refresh_norm_kernel, dim3(1), dim3(128), 0, (hipStream_t)stream, p->stats_v, p->norm_v, p->Dv, p->epsilon);
+  HIP_TRY(hipGetLastError());
+  return TREX_OK;
+}
+
+// The observation statistics' two launches on the critic's block, with_reward = 0. Read in observe_kernel above: without a reward
+// the only loads from the rows are `g.rows[r * row_stride + c]` under `c < D` (the thread c == D is gated by with_reward), the
+// return buffer, the reward sum and slots [2 D + 1, 2 D + 5) of the statistics are written under with_reward alone, and the three
+// optional outputs are never touched - so pointed at (stats_v, partial_v, norm_v, Dv) they read columns [0, Dv) and nothing else.
+int trex_policy_critic_observe(TrexPolicy *p, const float *rows_v_dev, int stride_v, void *stream) {
+  if (!p || !rows_v_dev) return trex_fail(TREX_E_INVALID, "trex_policy_critic_observe: null argument");
+  if (!p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_critic_observe: no critic width is set (trex_policy_set_critic)");
+  if (stride_v < p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_critic_observe: stride_v < critic_dim");
+  TrexDeviceGuard guard(p->device);
+  const size_t n = (size_t)p->n;
+  BUF_TRY(rows_v_dev, ((n - 1) * stride_v + p->Dv) * sizeof(float), "trex_policy_critic_observe: rows_v");
+  ObserveArgs a{rows_v_dev, p->stats_v, p->partial_v, p->norm_v, nullptr, nullptr, nullptr, nullptr, p->counter,
+                p->n, stride_v, p->Dv, 0, 0.f, p->epsilon};
+  hipLaunchKernelGGL(observe_kernel<false>, dim3(p->G), dim3(128 * OBS_GROUPS), 0, (hipStream_t)stream, a, p->G);
+  hipLaunchKernelGGL(observe_kernel<true>, dim3(1), dim3(128 * OBS_GROUPS), 0, (hipStream_t)stream, a, p->G);
+  HIP_TRY(hipGetLastError());
+  return TREX_OK;
+}
+
+int trex_policy_critic_act(TrexPolicy *p, const float *theta_dev, const float *rows_dev, int row_stride, const float *rows_v_dev,
+                           int stride_v, float clip_obs, const float *noise_dev, float *actions_dev, float *obs_out, float *obs_v_out,
+                           float *act_out, float *logp_out, float *value_out, int value_only, void *stream) {
+  if (!p || !theta_dev) return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: null argument");
+  if (!p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: no critic width is set (trex_policy_set_critic)");
+  if (value_only) {
+    if (!rows_v_dev || !value_out) return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: value_only needs rows_v and value_out");
+  } else {
+    if (!rows_dev || !noise_dev || !actions_dev) return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: rows / noise / actions are null");
+    if (!rows_v_dev && (value_out || obs_v_out))
+      return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: without rows_v only the policy runs: value_out and obs_v_out must be null");
+  }
+  if (rows_dev && row_stride < p->D) return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: row_stride < obs_dim");
+  if (rows_v_dev && stride_v < p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: stride_v < critic_dim");
+  TrexDeviceGuard guard(p->device);
+  const size_t n = (size_t)p->n;
+  BUF_TRY(theta_dev, (size_t)p->lay.count * sizeof(float), "trex_policy_critic_act: theta");
+  BUF_TRY(rows_dev, ((n - 1) * row_stride + p->D) * sizeof(float), "trex_policy_critic_act: rows");
+  BUF_TRY(rows_v_dev, ((n - 1) * stride_v + p->Dv) * sizeof(float), "trex_policy_critic_act: rows_v");
+  BUF_TRY(noise_dev, n * p->A * sizeof(float), "trex_policy_critic_act: noise");
+  BUF_TRY(actions_dev, n * p->A * sizeof(float), "trex_policy_critic_act: actions");
+  BUF_TRY(obs_out, n * p->D * sizeof(float), "trex_policy_critic_act: obs_out");
+  BUF_TRY(obs_v_out, n * p->Dv * sizeof(float), "trex_policy_critic_act: obs_v_out");
+  BUF_TRY(act_out, n * p->A * sizeof(float), "trex_policy_critic_act: act_out");
+  BUF_TRY(logp_out, n * sizeof(float), "trex_policy_critic_act: logp_out");
+  BUF_TRY(value_out, n * sizeof(float), "trex_policy_critic_act: value_out");
+  // (value_only never reads the policy's row and writes the values alone: the pi workgroups return at once)
+  ActArgsV a{};
+  static_cast<ActArgs &>(a) = ActArgs{theta_dev, rows_dev, p->norm, noise_dev, actions_dev, value_only ? nullptr : obs_out, act_out, logp_out,
+                                     value_out, p->n, row_stride, value_only ? 1 : 0, clip_obs, p->lay};
+  a.rows_v = rows_v_dev; a.norm_v = p->norm_v; a.obs_v_out = value_only ? nullptr : obs_v_out; a.stride_v = stride_v; a.Dv = p->Dv;
+  const size_t lds_bytes = (size_t)act_lds_floats(p->lay) * sizeof(float);
+  hipLaunchKernelGGL(act_kernel<true>, dim3((p->n + TILE - 1) / TILE, rows_v_dev ? 2 : 1), dim3(128), lds_bytes, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return TREX_OK;
 }

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "../../include/trex_policy.h"
 #include "policy_common.h"
@@ -68,6 +69,16 @@ struct LearnArgs {
   float cliprange, vf_coef;
   Layout lay;
 };
+// With a privileged critic (include/trex_policy_critic.h) the vf workgroups read a rollout buffer and a width of their own (CRITIC =
+// true); the plain launch is the CRITIC = false instantiation, the kernel as it was before the template (profiles/r31_critic.txt).
+struct LearnArgsV : LearnArgs {
+  const float *obs_v;
+  int Dv;
+};
+__device__ __forceinline__ int net_D(const LearnArgs &g, int) { return g.lay.D; }
+__device__ __forceinline__ int net_D(const LearnArgsV &g, int net) { return net ? g.Dv : g.lay.D; }
+__device__ __forceinline__ const float *net_obs(const LearnArgs &g, int) { return g.obs; }
+__device__ __forceinline__ const float *net_obs(const LearnArgsV &g, int net) { return net ? g.obs_v : g.obs; }
 
 // sum over the 32 lanes of a half wave (same h), result on all of them: four DPP steps inside the 16-lane rows, then
 // gfx950's v_permlane16_swap (rows 0<->1, 2<->3)
@@ -104,11 +115,13 @@ __device__ unsigned long long learn_stamps[512 * 12];
 #else
 #define LSTAMP(i) do {} while (0)
 #endif
-__global__ __launch_bounds__(256) void learn_grad_kernel(LearnArgs g) {
+template <bool CRITIC>
+__global__ __launch_bounds__(256) void learn_grad_kernel(std::conditional_t<CRITIC, LearnArgsV, LearnArgs> g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   LSTAMP(0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, net = blockIdx.y;     // net 0: policy, 1: value
-  const int D = g.lay.D, A = g.lay.A;
+  const int D = net_D(g, net), A = g.lay.A;       // (D and obs: per net with a critic)
+  const float *obs = net_obs(g, net);
   const LdsLayout L = make_lds_layout(g.lay);
   // ---- staging. Three global round trips feed the first barrier - the tile's sample rows (perm), this net's parameters, the
   // observation rows of those samples (which need the perm values) - and they are issued so that they overlap: perm first, the
@@ -151,7 +164,7 @@ __global__ __launch_bounds__(256) void learn_grad_kernel(LearnArgs g) {
   for (int u = 0; u < UX; u++) {
     const int idx = tid + 256 * u, ii = idx / XC, kk = idx - ii * XC;
     const long long row = tile_rows[ii];
-    const float v = g.obs[(size_t)(row >= 0 ? row : 0) * D + (kk < D ? kk : D - 1)];
+    const float v = obs[(size_t)(row >= 0 ? row : 0) * D + (kk < D ? kk : D - 1)];
     raw[u] = (kk < D && row >= 0) ? v : 0.f;
   }
   const int col = lane & 31, h = lane >> 5;
@@ -642,14 +655,19 @@ int trex_policy_minibatch_stats(TrexPolicy *p, const float *adv_dev, int64_t num
 
 // gradient of one minibatch: learn_grad_kernel + learn_reduce_kernel -> grad_dev (UNclipped, times grad_scale)
 static int launch_minibatch_grad(TrexPolicy *p, const char *who, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev,
-                                 const float *obs_dev, const float *act_dev, const float *logp_dev, const float *val_dev,
-                                 const float *adv_dev, const float *ret_dev, int64_t num_samples, const int64_t *perm_dev, int first,
-                                 int mb, const float *adv_stats_dev, float cliprange, float ent_coef, float vf_coef, float lr,
+                                 const float *obs_dev, const float *obs_v_dev, const float *act_dev, const float *logp_dev,
+                                 const float *val_dev, const float *adv_dev, const float *ret_dev, int64_t num_samples,
+                                 const int64_t *perm_dev, int first, int mb, const float *adv_stats_dev, float cliprange, float ent_coef, float vf_coef, float lr,
                                  float beta1, float beta2, float eps, float max_grad_norm, float grad_scale, int advance,
                                  float *loss_sums_dev, void *stream, ApplyArgs *out_args, int *out_groups) {
   if (!p || !theta_dev || !grad_dev || !obs_dev || !act_dev || !logp_dev || !val_dev || !adv_dev || !ret_dev || !perm_dev || !adv_stats_dev)
     return trex_fail(TREX_E_INVALID, std::string(who) + ": null argument");
   if (mb <= 0 || first < 0 || num_samples <= 0) return trex_fail(TREX_E_INVALID, std::string(who) + ": bad sizes");
+  // obs_v_dev: the critic entry points pass it, the plain ones do not; either kind refuses an object of the other kind by name
+  if (!obs_v_dev && p->Dv)
+    return trex_fail(TREX_E_INVALID, std::string(who) + ": the policy has a critic width set (the trex_policy_critic_minibatch calls take obs_v)");
+  if (obs_v_dev && !p->Dv) return trex_fail(TREX_E_INVALID, std::string(who) + ": no critic width is set (trex_policy_set_critic)");
+  if (p->Dv > 96) return trex_fail(TREX_E_INVALID, std::string(who) + ": the learner stages 96 observation columns (critic_dim <= 96)");
   if (p->D > 96) return trex_fail(TREX_E_INVALID, std::string(who) + ": the learner stages 96 observation columns (obs_dim <= 96)");
   if ((p->lay.vW1 + (p->lay.count - p->lay.logstd)) / 4 > 256 * LEARN_UF || (p->lay.logstd - p->lay.vW1) / 4 > 256 * LEARN_UF)
     return trex_fail(TREX_E_INVALID, std::string(who) + ": the learner stages one net's parameters in one trip of 256 x 13 float4s");
@@ -659,6 +677,7 @@ static int launch_minibatch_grad(TrexPolicy *p, const char *who, float *theta_de
   BUF_TRY(m_dev, P * sizeof(float), "minibatch step: m");
   BUF_TRY(v_dev, P * sizeof(float), "minibatch step: v");
   BUF_TRY(obs_dev, N * p->D * sizeof(float), "minibatch step: obs");
+  BUF_TRY(obs_v_dev, N * p->Dv * sizeof(float), "minibatch step: obs_v");
   BUF_TRY(act_dev, N * p->A * sizeof(float), "minibatch step: act");
   BUF_TRY(logp_dev, N * sizeof(float), "minibatch step: logp");
   BUF_TRY(val_dev, N * sizeof(float), "minibatch step: val");
@@ -687,7 +706,14 @@ static int launch_minibatch_grad(TrexPolicy *p, const char *who, float *theta_de
   const LdsLayout L = make_lds_layout(p->lay);
   LearnArgs a{theta_dev, obs_dev, act_dev, logp_dev, val_dev, adv_dev, ret_dev, reinterpret_cast<const long long *>(perm_dev),
               adv_stats_dev, p->grad_partial, first, mb, stride, cliprange, vf_coef, p->lay};
-  hipLaunchKernelGGL(learn_grad_kernel, dim3(tiles, 2), dim3(256), (size_t)L.total * sizeof(float), (hipStream_t)stream, a);
+  if (obs_v_dev) {
+    LearnArgsV av{};
+    static_cast<LearnArgs &>(av) = a;
+    av.obs_v = obs_v_dev; av.Dv = p->Dv;
+    hipLaunchKernelGGL(learn_grad_kernel<true>, dim3(tiles, 2), dim3(256), (size_t)L.total * sizeof(float), (hipStream_t)stream, av);
+  } else {
+    hipLaunchKernelGGL(learn_grad_kernel<false>, dim3(tiles, 2), dim3(256), (size_t)L.total * sizeof(float), (hipStream_t)stream, a);
+  }
   HIP_TRY(hipGetLastError());
   ApplyArgs b{p->grad_partial, theta_dev, grad_dev, m_dev, v_dev, loss_sums_dev, p->learn_red, p->learn_counter, p->adam_step,
               tiles, stride, p->lay.count, p->lay.logstd, p->A, ent_coef, lr, beta1, beta2, eps, max_grad_norm, 1.0f / (float)mb,
@@ -708,7 +734,7 @@ int trex_policy_minibatch_step(TrexPolicy *p, float *theta_dev, float *grad_dev,
   TrexDeviceGuard guard(p->device);
   ApplyArgs b{};
   int groups = 0;
-  if (int rc = launch_minibatch_grad(p, "trex_policy_minibatch_step", theta_dev, grad_dev, m_dev, v_dev, obs_dev, act_dev, logp_dev,
+  if (int rc = launch_minibatch_grad(p, "trex_policy_minibatch_step", theta_dev, grad_dev, m_dev, v_dev, obs_dev, nullptr, act_dev, logp_dev,
                                      val_dev, adv_dev, ret_dev, num_samples, perm_dev, first, mb, adv_stats_dev, cliprange, ent_coef,
                                      vf_coef, lr, beta1, beta2, eps, max_grad_norm, 1.0f, 1, loss_sums_dev, stream, &b, &groups))
     return rc;
@@ -724,7 +750,39 @@ int trex_policy_minibatch_grad(TrexPolicy *p, const float *theta_dev, float *gra
   if (!p) return trex_fail(TREX_E_INVALID, "trex_policy_minibatch_grad: null argument");
   TrexDeviceGuard guard(p->device);
   return launch_minibatch_grad(p, "trex_policy_minibatch_grad", const_cast<float *>(theta_dev), grad_dev, nullptr, nullptr, obs_dev,
-                               act_dev, logp_dev, val_dev, adv_dev, ret_dev, num_samples, perm_dev, first, mb, adv_stats_dev,
+                               nullptr, act_dev, logp_dev, val_dev, adv_dev, ret_dev, num_samples, perm_dev, first, mb, adv_stats_dev,
+                               cliprange, ent_coef, vf_coef, 0.f, 0.9f, 0.999f, 1e-5f, 0.f, grad_scale, 0, loss_sums_dev, stream,
+                               nullptr, nullptr);
+}
+
+// ---- with a privileged critic (include/trex_policy_critic.h): the same launches, the vf workgroups on obs_v_dev
+int trex_policy_critic_minibatch_step(TrexPolicy *p, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev, const float *obs_dev,
+                                      const float *obs_v_dev, const float *act_dev, const float *logp_dev, const float *val_dev,
+                                      const float *adv_dev, const float *ret_dev, int64_t num_samples, const int64_t *perm_dev, int first,
+                                      int mb, const float *adv_stats_dev, float cliprange, float ent_coef, float vf_coef, float lr,
+                                      float beta1, float beta2, float eps, float max_grad_norm, float *loss_sums_dev, void *stream) {
+  if (!p || !m_dev || !v_dev || !obs_v_dev) return trex_fail(TREX_E_INVALID, "trex_policy_critic_minibatch_step: null argument");
+  TrexDeviceGuard guard(p->device);
+  ApplyArgs b{};
+  int groups = 0;
+  if (int rc = launch_minibatch_grad(p, "trex_policy_critic_minibatch_step", theta_dev, grad_dev, m_dev, v_dev, obs_dev, obs_v_dev, act_dev,
+                                     logp_dev, val_dev, adv_dev, ret_dev, num_samples, perm_dev, first, mb, adv_stats_dev, cliprange,
+                                     ent_coef, vf_coef, lr, beta1, beta2, eps, max_grad_norm, 1.0f, 1, loss_sums_dev, stream, &b, &groups))
+    return rc;
+  hipLaunchKernelGGL(learn_adam_kernel, dim3(((p->lay.count >> 2) + 255) / 256), dim3(256), 0, (hipStream_t)stream, b, groups);
+  HIP_TRY(hipGetLastError());
+  return TREX_OK;
+}
+
+int trex_policy_critic_minibatch_grad(TrexPolicy *p, const float *theta_dev, float *grad_dev, const float *obs_dev, const float *obs_v_dev,
+                                      const float *act_dev, const float *logp_dev, const float *val_dev, const float *adv_dev,
+                                      const float *ret_dev, int64_t num_samples, const int64_t *perm_dev, int first, int mb,
+                                      const float *adv_stats_dev, float cliprange, float ent_coef, float vf_coef, float grad_scale,
+                                      float *loss_sums_dev, void *stream) {
+  if (!p || !obs_v_dev) return trex_fail(TREX_E_INVALID, "trex_policy_critic_minibatch_grad: null argument");
+  TrexDeviceGuard guard(p->device);
+  return launch_minibatch_grad(p, "trex_policy_critic_minibatch_grad", const_cast<float *>(theta_dev), grad_dev, nullptr, nullptr, obs_dev,
+                               obs_v_dev, act_dev, logp_dev, val_dev, adv_dev, ret_dev, num_samples, perm_dev, first, mb, adv_stats_dev,
                                cliprange, ent_coef, vf_coef, 0.f, 0.9f, 0.999f, 1e-5f, 0.f, grad_scale, 0, loss_sums_dev, stream,
                                nullptr, nullptr);
 }

@@ -32,7 +32,8 @@ LEARNER_MAX_OBS_DIM = 96     # trex_policy_minibatch_step: the observation colum
 class MlpPolicy(nn.Module):
     """baselines MlpPolicy: pi and vf are separate 2 x 64 tanh MLPs, diagonal Gaussian with a free log-std. The
     parameters are views into ONE flat f32 vector laid out as include/trex_policy.h says (weights [in, out]); their
-    gradients are views into a second flat vector, so that the optimiser step is one kernel over both."""
+    gradients are views into a second flat vector, so that the optimiser step is one kernel over both. With a privileged
+    critic the layout's vf.W1 has Dv rows (critic_capi.PolicyCritic.layout) and value() takes the critic observation."""
 
     def __init__(self, layout, param_count, device):
         super().__init__()
@@ -65,6 +66,7 @@ class MlpPolicy(nn.Module):
         return torch.distributions.Normal(self.mean(obs), self.logstd.exp(), validate_args=False)   # the check syncs: not capturable
 
     def value(self, obs):
+        """obs: what the value net reads - the policy's observation, or the critic observation [.., Dv] of an asymmetric layout"""
         return self._mlp("vf", obs).squeeze(-1)
 
 
@@ -123,13 +125,17 @@ def dp_minibatch_step(kern, theta, grad, m, v, srcs, perm, first, mb, stats_row,
 class PPO:
     def __init__(self, env, nsteps=32, nminibatches=32, noptepochs=4, gamma=0.99, lam=0.95, lr=3e-4,
                  cliprange=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, clip_obs=10.0, clip_rew=10.0,
-                 seed=0, use_graphs=False, native_learner=True):
+                 seed=0, use_graphs=False, native_learner=True, critic=None):
         """native_learner: the minibatch step is three HIP launches (trex_policy_minibatch_step: forward + analytic
         backward on the matrix cores, then ordered partial sums, then clip + Adam) instead of ~90 autograd kernels; False keeps
         the PyTorch autograd path (the f32 reference the native step is tested against).
         use_graphs: capture the whole nsteps rollout (policy kernel + env step + statistics kernel per step) and
         one epoch of minibatch updates as HIP graphs and replay them - everything launched is stream-ordered, so it
-        is capture-safe (tests/test_gpu_invariants.py)."""
+        is capture-safe (tests/test_gpu_invariants.py).
+        critic: True trains an asymmetric actor-critic (include/trex_policy_critic.h): the value net reads env.critic_rows
+        (trex_gym.critic.attach), normalised by running moments of its own, the policy net keeps env.rows; `b_obs_v` is the second
+        rollout buffer. Single process only: the moment merge of a data-parallel run is not written. No training benefit is
+        claimed: that takes long runs nobody has made."""
         self.env = env
         self.dev = env.device
         # DATA-PARALLEL (BASELINE config 3 on N GPUs; SURVEY 8e: "only PPO gradient all-reduce remains"): one process per GPU, env
@@ -156,7 +162,21 @@ class PPO:
             raise ValueError("the observation is %d columns wide; the native learner stages at most %d per sample "
                              "(native_learner=False trains up to %d)" % (od, LEARNER_MAX_OBS_DIM, POLICY_MAX_OBS_DIM))
         self.kern = _capi.Policy(n, od, ad, 64, self.dev.index)       # VecNormalize state + the kernels
-        self.policy = MlpPolicy(self.kern.layout, self.kern.param_count, self.dev)
+        self.crit, self.critic_dim = None, 0
+        if critic:
+            from . import critic_capi
+            if self.world > 1:
+                raise ValueError("critic: the data-parallel trainer does not merge the critic moments across ranks (world_size 1 only)")
+            if getattr(env, "critic_rows", None) is None:
+                raise ValueError("critic: the env has no critic row (trex_gym.critic.attach)")
+            dv = int(env.critic_rows.shape[1])
+            if native_learner and dv > critic_capi.LEARNER_MAX_CRITIC_DIM:
+                raise ValueError("the critic row is %d columns wide; the native learner stages at most %d per sample "
+                                 "(native_learner=False trains up to %d)" % (dv, critic_capi.LEARNER_MAX_CRITIC_DIM, critic_capi.MAX_CRITIC_DIM))
+            self.crit, self.critic_dim = critic_capi.PolicyCritic(self.kern), dv
+            self.crit.set(dv)
+        lay, count = (self.crit.layout, self.crit.param_count) if self.crit else (self.kern.layout, self.kern.param_count)
+        self.policy = MlpPolicy(lay, count, self.dev)
         self.adam_m = torch.zeros_like(self.policy.theta)
         self.adam_v = torch.zeros_like(self.policy.theta)
         self.use_graphs, self.native_learner = use_graphs, native_learner
@@ -172,6 +192,7 @@ class PPO:
         self.noise = torch.empty(T, n, ad, device=self.dev)
         self.actions = torch.empty(n, ad, device=self.dev)
         self.b_obs = torch.empty(T, n, od, device=self.dev)
+        self.b_obs_v = torch.empty(T, n, self.critic_dim, device=self.dev) if self.crit else None   # the NORMALISED critic observation
         self.b_act = torch.empty(T, n, ad, device=self.dev)
         self.b_logp = torch.empty(T, n, device=self.dev)
         self.b_val = torch.empty(T + 1, n, device=self.dev)
@@ -198,6 +219,8 @@ class PPO:
         self.episode_stats, self._monitor_out = None, None      # the episode monitor's window (trex_gym.monitor.attach), per rollout
         env.reset_tensor()
         self.kern.observe(env.rows, with_reward=False)           # VecNormalize.reset: the statistics see the first obs
+        if self.crit:
+            self.crit.observe(env.critic_rows)
 
     @property
     def obs(self):
@@ -209,22 +232,31 @@ class PPO:
         """nsteps env steps with the current policy + GAE, everything into the preallocated buffers. Per step: ONE
         policy launch (normalise, both MLPs on the matrix cores, sample, log-prob), the env's step launch, ONE
         statistics launch (VecNormalize)."""
-        T, env, k, th = self.nsteps, self.env, self.kern, self.policy.theta
+        T, env, k, th, c = self.nsteps, self.env, self.kern, self.policy.theta, self.crit
         self.noise.normal_()
         for t in range(T):
-            k.act(th, env.rows, self.noise[t], self.actions, self.b_obs[t], self.b_act[t], self.b_logp[t], self.b_val[t],
-                  clip_obs=self.clip_obs)
+            if c:       # (the same launch shape: the vf workgroups read the critic row and its moments)
+                c.act(th, env.rows, env.critic_rows, self.noise[t], self.actions, self.b_obs[t], self.b_obs_v[t], self.b_act[t],
+                      self.b_logp[t], self.b_val[t], clip_obs=self.clip_obs)
+            else:
+                k.act(th, env.rows, self.noise[t], self.actions, self.b_obs[t], self.b_act[t], self.b_logp[t], self.b_val[t],
+                      clip_obs=self.clip_obs)
             if self.b_terms is not None:
                 env.reward_terms = self.b_terms[t]
             if self.b_motion is not None:
                 env.motion_terms = self.b_motion[t]
             env.step_tensor(self.actions)       # the env clips to the joint limits (trex_env.py:147)
             k.observe(env.rows, True, self.gamma, self.b_rew[t], self.b_done[t], self.b_scale[t:t + 1])
+            if c:
+                c.observe(env.critic_rows)
         if self.b_terms is not None:
             torch.sum(self.b_terms, dim=(0, 1), out=self.term_sum)
         if self.b_motion is not None:
             torch.sum(self.b_motion, dim=(0, 1), out=self.motion_sum)
-        k.act(th, env.rows, None, None, value_out=self.b_val[T], clip_obs=self.clip_obs, value_only=True)
+        if c:
+            c.act(th, None, env.critic_rows, None, None, value_out=self.b_val[T], clip_obs=self.clip_obs, value_only=True)
+        else:
+            k.act(th, env.rows, None, None, value_out=self.b_val[T], clip_obs=self.clip_obs, value_only=True)
         k.gae(self.b_rew, self.b_scale, self.b_done, self.b_val, self.b_adv, self.b_ret, self.gamma, self.lam, self.clip_rew)
 
     @torch.no_grad()
@@ -300,30 +332,30 @@ class PPO:
         dp_minibatch_step(self.kern, self.policy.theta, self.policy.grad, self.adam_m, self.adam_v, srcs, perm, first, mb, stats_row,
                           self.world, self.group, self.cliprange, self.ent_coef, self.vf_coef, self.lr, self.max_grad_norm, self.loss_sums)
 
-    def _loss(self, obs, act, logp0, val0, adv, ret):
+    def _loss(self, obs, act, logp0, val0, adv, ret, obs_v=None):
         a = (adv - adv.mean()) / (adv.std(unbiased=False) + 1e-8)       # numpy's std: population
         d = self.policy.dist(obs)
         logp = d.log_prob(act).sum(-1)
         ratio = (logp - logp0).exp()
         pg = torch.max(-a * ratio, -a * ratio.clamp(1 - self.cliprange, 1 + self.cliprange)).mean()
-        v = self.policy.value(obs)
+        v = self.policy.value(obs if obs_v is None else obs_v)
         vclip = val0 + (v - val0).clamp(-self.cliprange, self.cliprange)
         vf = 0.5 * torch.max((v - ret) ** 2, (vclip - ret) ** 2).mean()
         ent = d.entropy().sum(-1).mean()
         return pg - self.ent_coef * ent + self.vf_coef * vf, pg, vf, ent
 
-    def _minibatch_step(self, obs, act, logp0, val0, adv, ret):
-        loss, pg, vf, ent = self._loss(obs, act, logp0, val0, adv, ret)
+    def _minibatch_step(self, obs, act, logp0, val0, adv, ret, obs_v=None):
+        loss, pg, vf, ent = self._loss(obs, act, logp0, val0, adv, ret, obs_v)
         loss.backward()          # accumulates into the flat gradient vector (zeroed by the optimiser kernel)
-        self.kern.adam(self.policy.theta, self.policy.grad, self.adam_m, self.adam_v, lr=self.lr, eps=1e-5,
-                       max_grad_norm=self.max_grad_norm)
+        (self.crit or self.kern).adam(self.policy.theta, self.policy.grad, self.adam_m, self.adam_v, lr=self.lr, eps=1e-5,
+                                      max_grad_norm=self.max_grad_norm)     # (with a critic: lengths of the layout in force)
         return pg.detach(), vf.detach(), ent.detach()
 
     def _epoch(self, srcs, N, mb):
         """One epoch: a fresh permutation, nminibatches optimiser steps; returns the summed (pg, vf, ent)."""
         perm = torch.rand(N, device=self.dev).argsort()     # (capturable: no host round trip, unlike randperm's size logic)
         if self.native_learner:
-            obs, act, logp0, val0, adv, ret = srcs
+            obs, act, logp0, val0, adv, ret = srcs[:6]
             k, pol = self.kern, self.policy
             self.loss_sums.zero_()
             if self.world > 1:
@@ -336,6 +368,11 @@ class PPO:
                 return torch.cat([self.loss_sums, ent.reshape(1)])
             k.minibatch_stats(adv, perm, self.nminibatches, mb, self.mb_stats)
             for i in range(self.nminibatches):
+                if self.crit:
+                    self.crit.minibatch_step(pol.theta, pol.grad, self.adam_m, self.adam_v, obs, srcs[6], act, logp0, val0, adv, ret,
+                                             perm, i * mb, mb, self.mb_stats[i], self.cliprange, self.ent_coef, self.vf_coef, self.lr,
+                                             0.9, 0.999, 1e-5, self.max_grad_norm, self.loss_sums)
+                    continue
                 k.minibatch_step(pol.theta, pol.grad, self.adam_m, self.adam_v, obs, act, logp0, val0, adv, ret, perm, i * mb, mb,
                                  self.mb_stats[i], self.cliprange, self.ent_coef, self.vf_coef, self.lr, 0.9, 0.999, 1e-5,
                                  self.max_grad_norm, self.loss_sums)
@@ -351,6 +388,8 @@ class PPO:
     def update(self, batch):
         obs, act, logp0, val0, adv, ret, _ = batch
         srcs = (obs, act, logp0, val0, adv, ret)
+        if self.crit:       # (the critic observation of the same samples: the second rollout buffer, behind the six)
+            srcs += (self.b_obs_v.reshape(-1, self.critic_dim),)
         N = obs.shape[0]
         mb = N // self.nminibatches
         if self.use_graphs:

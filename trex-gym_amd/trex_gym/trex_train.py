@@ -25,7 +25,7 @@ _URDF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ass
 def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0, push_force=0.0, push_interval=100,
                       push_duration=5, push_probability=1.0, seed=0, control_mode=None, variable_stiffness=False,
                       gain_scale=0.0, terminate=None, observations=None, rewards=None, command=None, motion=None, sensing=None,
-                      randomize=None, monitor=None):   # (weights of trex_train.py:66)
+                      randomize=None, monitor=None, critic=None):   # (weights of trex_train.py:66)
     # control_mode: what the joints' actions mean (position / velocity / torque: J-wide, through the trainer unchanged). The
     # 2J-wide stiffness action space is wider than the policy kernel's act_dim <= 32: refused here, not deep in a launch
     check_action_space(control_mode, variable_stiffness)
@@ -148,6 +148,15 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
         from . import monitor as monitoring
         monitoring.attach(env, window=int(monitor.get("window", 100)), terms=bool(monitor.get("terms", True)))
         env.monitor_config = env.monitor             # what a checkpoint stores: settings only
+    # critic: a preset's name of trex_gym.critic ("clean", "privileged"): the row the value net of an asymmetric actor-critic reads,
+    # attached last - behind the sensor model and the randomisation whose draws it reads
+    env.critic_config = None
+    if critic is not None:
+        from . import critic as critics
+        if critic not in critics.PRESETS:
+            raise ValueError("--critic: expected one of %s, got %r" % (", ".join(sorted(critics.PRESETS)), critic))
+        critics.PRESETS[critic](env)
+        env.critic_config = dict(preset=critic, spec=env.critic_spec, names=list(env.critic_names))    # what a checkpoint stores
     return env
 
 
@@ -178,7 +187,7 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
     hp = dict(PRESETS[preset])
     if noptepochs is not None:
         hp["noptepochs"] = noptepochs
-    agent = PPO(env, nsteps=nsteps, seed=seed, use_graphs=use_graphs, **hp)
+    agent = PPO(env, nsteps=nsteps, seed=seed, use_graphs=use_graphs, critic=getattr(env, "critic_config", None) is not None, **hp)
     log("Number of actions: %d; number of joints: %d; model mass: %.2f; nsteps %d x %d envs; preset %s, noptepochs %d"
         % (env.action_space.shape[0], env.model.num_joints, env.model.total_mass(False), nsteps, env.num_envs, preset,
            hp["noptepochs"]))
@@ -191,9 +200,21 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
                     "observations": _own_channels(env), "rewards": getattr(env, "rewards", None),
                     "command": getattr(env, "command", None), "motion": getattr(env, "motion_config", None),
                     "sensing": getattr(env, "sensing_config", None), "randomize": getattr(env, "randomize_config", None),
-                    "monitor": getattr(env, "monitor_config", None)},
+                    "monitor": getattr(env, "monitor_config", None), "critic": critic_checkpoint(agent)},
                    save_path)   # (the channels, the terms, the clip and the sensor model: --play rebuilds the same row)
     return agent, hist
+
+
+def critic_checkpoint(agent):
+    """what a checkpoint stores of a privileged critic - None without one: the width (theta's vf.W1 has that many rows), the
+    recorded sources and column names, and the critic's running moments. Playing needs the width alone."""
+    if getattr(agent, "crit", None) is None:
+        return None
+    st = agent.crit.get_stats()
+    cfg = getattr(agent.env, "critic_config", None) or dict(preset=None, spec=getattr(agent.env, "critic_spec", None),
+                                                            names=list(getattr(agent.env, "critic_names", [])))
+    return dict(dim=int(agent.critic_dim), preset=cfg["preset"], spec=cfg["spec"], names=cfg["names"],
+                mean=torch.tensor(st["mean"]), var=torch.tensor(st["var"]), count=torch.tensor(float(st["count"]), dtype=torch.float64))
 
 
 def _own_channels(env):
@@ -242,7 +263,10 @@ def play(agent, num_play_timesteps, export_path=None, env_index=0, log=print, de
     for _ in range(num_play_timesteps):
         if not deterministic:
             noise.normal_(generator=gen)
-        k.act(agent.policy.theta, env.rows, noise, agent.actions, clip_obs=agent.clip_obs)
+        if getattr(agent, "crit", None) is not None:    # (trained with a privileged critic: the policy alone, no critic row)
+            agent.crit.act(agent.policy.theta, env.rows, None, noise, agent.actions, clip_obs=agent.clip_obs)
+        else:
+            k.act(agent.policy.theta, env.rows, noise, agent.actions, clip_obs=agent.clip_obs)
         env.step_tensor(agent.actions)
         if update_stats:
             k.observe(env.rows)       # (VecNormalize.step_wait: the observation moments AND the return moments move on)
@@ -275,6 +299,15 @@ def load_agent(load_path, num_envs=1, device="cuda:0", max_episode_steps=1000, s
                             sensing=ck.get("sensing") if sensing else None, randomize=ck.get("randomize") if randomize else None,
                             monitor=ck.get("monitor"))
     agent = PPO(env, nsteps=1, nminibatches=1, noptepochs=1)
+    cr = ck.get("critic")
+    if cr is not None:      # theta has the critic's layout; the env gets no critic row: playing runs the policy alone
+        from . import critic_capi
+        from .ppo import MlpPolicy
+        agent.crit, agent.critic_dim = critic_capi.PolicyCritic(agent.kern), int(cr["dim"])
+        agent.crit.set(agent.critic_dim)
+        agent.crit.set_stats(dict(mean=cr["mean"].cpu().numpy(), var=cr["var"].cpu().numpy(), count=float(cr["count"])))
+        agent.policy = MlpPolicy(agent.crit.layout, agent.crit.param_count, agent.dev)
+        agent.critic_config = {k: cr[k] for k in ("preset", "spec", "names")}
     with torch.no_grad():
         agent.policy.theta.copy_(ck["theta"])
     st = agent.kern.get_stats()
@@ -354,6 +387,10 @@ def parse_args(argv=None):
                          "episodes per iteration (trex_gym.monitor)")
     ap.add_argument("--no_randomize", action="store_true", help="with --play: run the policy without the episode randomisation it was trained with")
     ap.add_argument("--fall_penalty", type=float, default=0.0, help="taken from the reward of the step in which an episode ends by a fall")
+    ap.add_argument("--critic", choices=["clean", "privileged"], default=None,
+                    help="asymmetric actor-critic: the value net reads a row of its own - the observation before the sensor model "
+                         "(clean), plus friction, push force, mass scale and foot contact forces where the env has them (privileged) - "
+                         "during training only (trex_gym.critic)")
     args = ap.parse_args(argv)
     if args.variable_stiffness:
         try:
@@ -437,7 +474,7 @@ def environment_from_args(args):
                             seed=args.random_seed, control_mode=None if args.control_mode == "position" else args.control_mode,
                             gain_scale=args.gain_scale, observations=args.observations, rewards=args.rewards, command=args.command,
                             motion=None if args.motion is None else dict(clip=args.motion, rsi=args.rsi, weight=args.motion_weight),
-                            sensing=sensing_args(args), randomize=randomize_args(args), monitor=monitor_args(args))
+                            sensing=sensing_args(args), randomize=randomize_args(args), monitor=monitor_args(args), critic=args.critic)
     if terminate is not None:   # (set on the built env: 'auto' needs its model - every body that does not stand on the floor at the start)
         if terminate["keep_clear"] == ["auto"]:
             from .termination import fall_bodies
@@ -452,7 +489,10 @@ def main(argv=None):
     agent, _ = train(env, args.num_timesteps, args.random_seed, args.nsteps, args.noptepochs, args.save, use_graphs=args.graphs,
                      preset=args.preset)
     if args.play:
-        if args.no_sensing and env.sense_api is not None:     # (the env the policy was trained in, its sensors taken off)
+        if env.critic_rows is not None:         # (playing runs the policy alone: the critic row is no longer filled)
+            from . import critic as critics
+            critics.attach(env, None)
+        if args.no_sensing and env.sense_api is not None:    # (the env the policy was trained in, its sensors taken off)
             from . import sensing as S
             S.attach(env, None)
         if args.no_randomize and env.random_api is not None:  # (likewise its episode randomisation)

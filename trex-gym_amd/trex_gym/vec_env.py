@@ -131,6 +131,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self.randomization, self.random_api, self.random_values = None, None, None
         self._no_done = None
         self.monitor, self.monitor_api = None, None
+        # the privileged critic row (trex_gym.critic.attach): [n, Dv], its column names, the recorded sources, and the call that
+        # refills it behind every step and reset
+        self.critic_rows, self.critic_names, self.critic_spec, self._critic_fill = None, [], None, None
         self.collision = collision
         self._init_queries()                    # the link table and the caches of the read-only queries (vec_queries.py)
         if observations is not None and len(observations):
@@ -379,6 +382,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
             self.sense_api.reset(mask)
             if self._clean_block is not None:   # the sensors' view of the clean block into the block the policy reads
                 self.sense_api.apply(out, self.rows)
+        if self._critic_fill is not None:       # behind the sensing launch: the critic's row of the reset state
+            self._critic_fill()
         if self.rewards is not None:            # the envs that were reset have no previous step: their reward history starts afresh
             self.reward_api.reward_reset(mask)
         if self.gains is not None:              # the envs that were reset draw new motor gains
@@ -451,6 +456,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
             self._compose(actions, out)
         if self._clean_block is not None:       # behind the last compose: the sensors' view into the block the policy reads
             self.sense_api.apply(out, self.rows)
+        if self._critic_fill is not None:       # behind the sensing launch: the critic's row of this step
+            self._critic_fill()
         if self._term_on and self.gains is not None:   # the envs that fell start their episode with new motor gains
             self.set_motor_gains(**self.gains.draw(self.termination_reason != 0))
         return self.obs, self.rew, self.done

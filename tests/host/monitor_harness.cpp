@@ -8,15 +8,14 @@
 //   n window cols_a cols_b env_offset block, then optionally the apply's arguments:
 //   reward(0/1) reward_stride done(0/1) done_stride block_a(0/1) stride_a block_b(0/1) stride_b.
 // Output: one line per part, "name value value ...", or the single line "REFUSED <code> <message>" (exit code 0: a refusal is an
-// answer). With the layout the harness makes the allocation on the host, writes every member's first and last byte and checks that
-// no two members share one: an overlap or an overrun is the sanitizer's to report. Exit code 2: bad usage.
+// answer). The layout line is layout_check.hpp's, over the members the layout lists itself. Exit code 2: bad usage.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <string>
 #include <vector>
 
-#include "../../trex-gym_amd/csrc/host_tables.hpp"
+#include "layout_check.hpp"
 
 int main(int argc, char **argv) {
   if (argc < 2) { std::fprintf(stderr, "usage: monitor_harness <numbers file>\n"); return 2; }
@@ -34,30 +33,7 @@ int main(int argc, char **argv) {
     if (in.size() == 14)
       trex::check_monitor_apply(m, in[6] != 0, (int)in[7], in[8] != 0, (int)in[9], in[10] != 0, (int)in[11], in[12] != 0, (int)in[13]);
     std::printf("shape %d %d %d %d %d %d\n", m.window, m.cols_a, m.cols_b, m.cols, m.team, m.groups);
-    const size_t N = (size_t)n, C = (size_t)m.cols, W = (size_t)m.window;
-    struct Member { const char *name; size_t at, bytes, align; };
-    const std::vector<Member> members = {
-        {"ret", m.ret, N * 8, 8}, {"col", m.col, N * C * 8, 8}, {"total", m.total, 8, 8}, {"by_reason", m.by_reason, 32, 8},
-        {"len", m.len, N * 4, 4}, {"episodes", m.episodes, N * 4, 4}, {"fin", m.fin, N * 4, 4},
-        {"last_return", m.last_return, N * 4, 4}, {"last_length", m.last_length, N * 4, 4}, {"last_reason", m.last_reason, N * 4, 4},
-        {"last_t", m.last_t, N * 4, 4}, {"last_cols", m.last_cols, N * C * 4, 4}, {"t", m.t, 4, 4},
-        {"ring_return", m.ring_return, W * 4, 4}, {"ring_length", m.ring_length, W * 4, 4}, {"ring_reason", m.ring_reason, W * 4, 4},
-        {"ring_env", m.ring_env, W * 4, 4}, {"ring_t", m.ring_t, W * 4, 4}, {"ring_cols", m.ring_cols, W * C * 4, 4},
-        {"counts", m.counts, (size_t)m.groups * 4, 4}};
-    std::vector<unsigned char> state(m.bytes, 0);
-    long long clashes = 0, misaligned = 0;
-    if (m.window > 0) {
-      for (const Member &k : members) {
-        if (k.at % k.align) misaligned++;
-        for (size_t i = 0; i < k.bytes; i++) {
-          if (state.at(k.at + i)) clashes++;
-          state[k.at + i] = 1;
-        }
-      }
-    }
-    long long unused = 0;
-    for (unsigned char c : state) unused += c ? 0 : 1;
-    std::printf("layout %lld %lld %lld %lld\n", (long long)m.bytes, clashes, misaligned, unused);
+    check_layout("layout", m);
   } catch (const trex::Refusal &r) {
     std::printf("REFUSED %d %s\n", r.code, r.what());
   }

@@ -9,13 +9,18 @@
 //   1 has_probes step_weight T, then T x (kind mask weight scale aux).
 // Output: one line per part, "name value value ..." (floats with 9 digits: every f32 exactly), or the single line
 // "REFUSED <code> <message>" (exit code 0: a refusal is an answer). Exit code 2: bad usage, or the model does not load.
+//
+//   motion_harness layout <numbers file>
+//
+// The numbers file holds n T: the layouts of the clocks (motion_clock_layout) and of the terms' held values (motion_held_layout),
+// a line each as layout_check.hpp prints it.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <string>
 #include <vector>
 
-#include "../../trex-gym_amd/csrc/host_tables.hpp"
+#include "layout_check.hpp"
 
 namespace {
 
@@ -39,6 +44,12 @@ int main(int argc, char **argv) {
     std::ifstream f(argv[2]);
     std::string tok;
     while (f >> tok) in.push_back(std::strtod(tok.c_str(), nullptr));
+  }
+  if (std::string(argv[1]) == "layout") {
+    if (in.size() != 2) { std::fprintf(stderr, "numbers file: n T\n"); return 2; }
+    check_layout("clock", trex::motion_clock_layout((int)in[0]));
+    check_layout("held", trex::motion_held_layout((int)in[0], (int)in[1]));
+    return 0;
   }
   trex::HostModel h;
   try {

@@ -8,13 +8,17 @@
 //   nb nj stiffness T, then T x (kind mask index shared lo hi interval duration probability).
 // Output: one line per part, "name value value ..." (floats with 9 digits: every f32 exactly), or the single line
 // "REFUSED <code> <message>" (exit code 0: a refusal is an answer). Exit code 2: bad usage.
+//
+//   randomize_harness layout <numbers file>
+//
+// The numbers file holds n T P: the layout of the state (rand_state_layout), as layout_check.hpp prints it.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <string>
 #include <vector>
 
-#include "../../trex-gym_amd/csrc/host_tables.hpp"
+#include "layout_check.hpp"
 
 namespace {
 
@@ -33,11 +37,17 @@ void floats(const char *name, const std::vector<float> &v) {
 
 int main(int argc, char **argv) {
   if (argc < 2) { std::fprintf(stderr, "usage: randomize_harness <numbers file>\n"); return 2; }
+  const bool layout = argc > 2 && std::string(argv[1]) == "layout";
   std::vector<double> in;
   {
-    std::ifstream f(argv[1]);
+    std::ifstream f(argv[layout ? 2 : 1]);
     std::string tok;
     while (f >> tok) in.push_back(std::strtod(tok.c_str(), nullptr));
+  }
+  if (layout) {
+    if (in.size() != 3) { std::fprintf(stderr, "numbers file: n T P\n"); return 2; }
+    check_layout("layout", trex::rand_state_layout((int)in[0], (int)in[1], (int)in[2]));
+    return 0;
   }
   if (in.size() < 4) { std::fprintf(stderr, "numbers file: nb nj stiffness T, then T x 9 values\n"); return 2; }
   try {

@@ -6,13 +6,17 @@
 // The numbers file holds white-space separated numbers ("nan" and "inf" included): action_cols, T, then T x (kind link mask x y z
 // weight p0 p1). Output: one line per part of the table, "name value value ..." (floats with 9 digits: every f32 exactly), or the
 // single line "REFUSED <code> <message>" (exit code 0: a refusal is an answer). Exit code 2: bad usage, or the model does not load.
+//
+//   reward_harness layout <numbers file>
+//
+// The numbers file holds n A J T: the layout of the terms' history (reward_hist_layout), as layout_check.hpp prints it.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <string>
 #include <vector>
 
-#include "../../trex-gym_amd/csrc/host_tables.hpp"
+#include "layout_check.hpp"
 
 namespace {
 
@@ -36,6 +40,11 @@ int main(int argc, char **argv) {
     std::ifstream f(argv[2]);
     std::string tok;
     while (f >> tok) in.push_back(std::strtod(tok.c_str(), nullptr));
+  }
+  if (std::string(argv[1]) == "layout") {
+    if (in.size() != 4) { std::fprintf(stderr, "numbers file: n A J T\n"); return 2; }
+    check_layout("layout", trex::reward_hist_layout((int)in[0], (int)in[1], (int)in[2], (int)in[3]));
+    return 0;
   }
   if (in.size() < 2 || in.size() != 2 + 9 * (size_t)in[1]) { std::fprintf(stderr, "numbers file: action_cols, T, T x 9 numbers\n"); return 2; }
   trex::HostModel h;

@@ -9,6 +9,11 @@
 //   1 delay_min delay_max   (the range check of trex_batch_set_action_delay).
 // Output: one line per part, "name value value ..." (floats with 9 digits: every f32 exactly), or the single line
 // "REFUSED <code> <message>" (exit code 0: a refusal is an answer). Exit code 2: bad usage.
+//
+//   sensing_harness layout <numbers file>
+//
+// The numbers file holds n G delayed action_delay(0/1) action_cols: the layouts of the groups' counters and history and of the
+// action delay's (sense_counter_layout, sense_hist_layout), a line each as layout_check.hpp prints it.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,7 +21,7 @@
 #include <string>
 #include <vector>
 
-#include "../../trex-gym_amd/csrc/host_tables.hpp"
+#include "layout_check.hpp"
 
 namespace {
 
@@ -35,11 +40,21 @@ void floats(const char *name, const std::vector<float> &v) {
 
 int main(int argc, char **argv) {
   if (argc < 2) { std::fprintf(stderr, "usage: sensing_harness <numbers file>\n"); return 2; }
+  const bool layout = argc > 2 && std::string(argv[1]) == "layout";
   std::vector<double> in;
   {
-    std::ifstream f(argv[1]);
+    std::ifstream f(argv[layout ? 2 : 1]);
     std::string tok;
     while (f >> tok) in.push_back(std::strtod(tok.c_str(), nullptr));
+  }
+  if (layout) {
+    if (in.size() != 5) { std::fprintf(stderr, "numbers file: n G delayed action_delay(0/1) action_cols\n"); return 2; }
+    const int n = (int)in[0], on = in[3] != 0.0;
+    check_layout("counters", trex::sense_counter_layout(n, (int)in[1]));
+    check_layout("hist", trex::sense_hist_layout(n, (int)in[2]));
+    check_layout("act_counters", trex::sense_counter_layout(n, on ? 1 : 0));   // (what trex_batch_set_action_delay asks for)
+    check_layout("act_hist", trex::sense_hist_layout(n, on ? (int)in[4] : 0));
+    return 0;
   }
   try {
     if (in.size() >= 3 && in[0] == 0.0) {

@@ -9,6 +9,8 @@
 //   prox     C, then C x (body p0 xyz p1 xyz radius), P, then P x (A B)  build_prox_table
 //   ik       K, K links, K modes, joint_mask, with_params (0 / 1), iterations damping gain max_step tol_pos tol_ori   build_ik_task
 //   camera   distance yaw pitch fov near far target xyz width height    camera_basis
+//   rows     n stride width                                             row_block_bytes
+//   overlap  a na b nb (two byte ranges, the addresses as numbers)       ranges_overlap
 // Output: one line per table, "name value value ..." (floats with 9 digits: every f32 exactly), or the single line
 // "REFUSED <code> <message>" (exit code 0: a refusal is an answer). Exit code 2: bad usage, or the model does not load.
 #include <cstdio>
@@ -136,6 +138,18 @@ int main(int argc, char **argv) {
       floats("offset", b.offset, 3); floats("fwd", b.fwd, 3); floats("right", b.right, 3); floats("up", b.up, 3);
       const float tn[] = {b.tan_x, b.tan_y};
       floats("tan", tn, 2);
+    } else if (what == "rows") {
+      const size_t n = (size_t)in.next();
+      const int stride = in.next_int(), width = in.next_int();
+      const long long bytes[] = {(long long)trex::row_block_bytes(n, stride, width)};
+      ints("bytes", bytes, 1);
+    } else if (what == "overlap") {   // (addresses as numbers: the predicate compares, it never reads)
+      const uintptr_t a = (uintptr_t)in.next();
+      const size_t na = (size_t)in.next();
+      const uintptr_t b = (uintptr_t)in.next();
+      const size_t nb = (size_t)in.next();
+      const int share[] = {trex::ranges_overlap((const void *)a, na, (const void *)b, nb) ? 1 : 0};
+      ints("overlap", share, 1);
     } else {
       std::fprintf(stderr, "unknown builder '%s'\n", what.c_str());
       return 2;

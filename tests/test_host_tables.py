@@ -316,3 +316,29 @@ def test_camera_refusals(harness, tmp_path):
     refused(go((10.0, 90.0, -30.0, 60.0, 100.0, 100.0)), needs)
     refused(go((10.0, 90.0, -30.0, 60.0, 100.0, 0.1)), needs)
     refused(go(DEFAULT_CAMERA, (0, np.nan, 0)), "camera value is not finite")
+
+
+def test_row_block_bytes(harness, tmp_path):
+    """n rows of `width` floats, `stride` floats apart, end with the last row's width: one row is its width whatever the stride,
+    and the product is formed in 64 bits (2^31 - 1 rows of the widest row the limits allow, 512 + 5)"""
+    go = lambda n, stride, width: int(run(harness, tmp_path, ASSET_URDF, "rows", (n, stride, width))["bytes"][0])
+    for stride in (80, 517, 1, 2 ** 31 - 1):
+        assert go(1, stride, 80) == 80 * 4
+    assert go(3, 80, 80) == 3 * 80 * 4                      # stride == width: dense
+    assert go(3, 96, 80) == (2 * 96 + 80) * 4               # stride > width: the padding of the last row is not part
+    assert go(4096, 1, 1) == 4096 * 4
+    assert go(2 ** 31 - 1, 517, 517) == (2 ** 31 - 1) * 517 * 4 > 2 ** 40
+    assert go(2 ** 31 - 1, 517, 80) == ((2 ** 31 - 2) * 517 + 80) * 4
+
+
+def test_ranges_overlap(harness, tmp_path):
+    go = lambda a, na, b, nb: int(run(harness, tmp_path, ASSET_URDF, "overlap", (a, na, b, nb))["overlap"][0])
+    A = 1 << 40
+    assert go(A, 320, A, 320) == 1                          # the identical range
+    assert go(A, 320, A + 320, 320) == 0 and go(A + 320, 320, A, 320) == 0      # adjacent, either order
+    assert go(A, 321, A + 320, 320) == 1 and go(A + 320, 320, A, 321) == 1      # one byte shared at the end of the first ...
+    assert go(A + 319, 320, A, 320) == 1 and go(A, 320, A + 319, 320) == 1      # ... and at the start of it
+    assert go(A, 1000, A + 100, 8) == 1 and go(A + 100, 8, A, 1000) == 1         # one inside the other
+    assert go(A, 320, A + 4096, 320) == 0
+    big = (2 ** 31 - 1) * 517 * 4                           # a block whose extent needs 64 bits
+    assert go(A, big, A + big - 1, 4) == 1 and go(A, big, A + big, 4) == 0

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import layout_cases as LC
 import motion_cases as MC
 import motion_ref as MR
 from conftest import ASSET_URDF, ROOT
@@ -203,3 +204,15 @@ def test_table_on_generated_models(name, harness, tmp_path):
         refused(go(g), "frame 2: joint %d outside its limits" % narrow)
         g[2, 7 + narrow] = lo[narrow]
         assert not isinstance(go(g), tuple)
+
+
+@pytest.mark.parametrize("case", LC.MOTION, ids=lambda c: "n%d-T%d" % c)
+def test_the_layouts_of_clocks_and_held_values(case, harness, tmp_path):
+    n, T = case
+    got = LC.run_layout(harness, tmp_path, n, T)
+    LC.sound(got["clock"], n * 8)
+    LC.sound(got["held"], n * T * 4)
+
+
+def test_the_empty_held_values(harness, tmp_path):
+    LC.sound(LC.run_layout(harness, tmp_path, 3, 0)["held"], 0)

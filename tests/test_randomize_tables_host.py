@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import layout_cases as LC
 import randomize_cases as RC
 from conftest import ROOT
 from randomize_ref import COMMAND, FRICTION, KD, KP, MASS, MAX_FORCE, PUSH
@@ -134,3 +135,12 @@ def test_refusals(harness, tmp_path):
         refused(go([change(mass, kind=kind)], stiffness=1), "KP and KD terms are refused while stiffness actions are on")
     assert not isinstance(go([change(mass, kind=MAX_FORCE)], stiffness=1), tuple)
     # (env_offset + N beyond 2^32 is the C entry's own check: tests/test_gpu_randomize.py)
+
+
+@pytest.mark.parametrize("case", LC.RANDOM, ids=lambda c: "n%d-T%d-P%d" % c)
+def test_the_layout_of_the_state(case, harness, tmp_path):
+    LC.sound(LC.run_layout(harness, tmp_path, *case)["layout"], LC.random_bytes(*case))
+
+
+def test_the_empty_state(harness, tmp_path):
+    LC.sound(LC.run_layout(harness, tmp_path, 3, 0, 0)["layout"], 0)

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import layout_cases as LC
 import reward_ref as RR
 from conftest import ASSET_URDF, ROOT
 
@@ -154,3 +155,12 @@ def test_table_on_generated_models(name, harness, tmp_path):
     jb = t["joint_body"].astype(int)
     assert jb[:nj].tolist() == list(om["obs_order"]) != sorted(om["obs_order"]) and (jb[nj:] == 0).all()
     assert t["mask"].astype(np.int64)[9] == (1 << nj) - 1
+
+
+@pytest.mark.parametrize("case", LC.REWARD, ids=lambda c: "n%d-A%d-J%d-T%d" % c)
+def test_the_layout_of_the_history(case, harness, tmp_path):
+    LC.sound(LC.run_layout(harness, tmp_path, *case)["layout"], LC.reward_bytes(*case))
+
+
+def test_the_empty_history(harness, tmp_path):
+    LC.sound(LC.run_layout(harness, tmp_path, 3, 25, 25, 0)["layout"], 0)

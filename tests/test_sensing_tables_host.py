@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import layout_cases as LC
 import sensing_cases as SC
 from conftest import ROOT
 
@@ -117,3 +118,16 @@ def test_refusals(harness, tmp_path):
     for lo, hi in ((-1, 0), (0, 9), (3, 2)):
         refused(run_numbers(harness, tmp_path, [1, lo, hi]), "trex_batch_set_action_delay: delays [%d, %d] outside" % (lo, hi))
     assert run_numbers(harness, tmp_path, [1, 0, 8])["ok"].tolist() == [1]
+
+
+@pytest.mark.parametrize("case", LC.SENSING, ids=lambda c: "n%d-G%d-delayed%d-act%d-cols%d" % c)
+def test_the_layouts_of_counters_and_histories(case, harness, tmp_path):
+    got = LC.run_layout(harness, tmp_path, *case)
+    for line, size in LC.sensing_bytes(*case).items():
+        LC.sound(got[line], size)
+
+
+def test_the_empty_counters(harness, tmp_path):
+    got = LC.run_layout(harness, tmp_path, 3, 0, 0, 0, 25)
+    for line in ("counters", "hist", "act_counters", "act_hist"):
+        LC.sound(got[line], 0)

@@ -102,33 +102,33 @@ struct TrexBatch {
   // and offsets, the host blob dropped); freed by num_channels 0 and with the batch
   struct Observation { trex::ObsTable table; DeviceBuf blob; } observation;
   // reward terms (trex_batch_set_reward): the term table, ONE device allocation laid out as trex::RewTable says, and the history
-  // of its terms, ONE more, zeroed by every set: previous actions [n][A] | previous qd [n][J] | timers [n][T] | held values
-  // [n][T] | valid flags [n]; both freed by num_terms 0 and with the batch
+  // of its terms, ONE more, zeroed by every set and laid out by trex::reward_hist_layout, as `st` points into it; both freed by
+  // num_terms 0 and with the batch
   struct Reward {
     trex::RewTable table;
     DeviceBuf blob, hist;
-    float *prev_act = nullptr, *prev_qd = nullptr, *timer = nullptr, *held = nullptr;
-    int32_t *valid = nullptr;
+    struct Hist { float *prev_act, *prev_qd, *timer, *held; int32_t *valid; } st{};
   } reward;
   // motion clip (trex_batch_set_motion, include/trex_motion.h): the clip table, ONE device allocation laid out as
-  // trex::MotionTable says (`table`: its counts and constants, the host rows dropped); the clocks, ONE more: start times [n] f32 |
-  // step counts [n] i32, zeroed by every set; the terms of trex_batch_set_motion_reward, host side - they travel in the launch
-  // arguments - and their held values [n][T]. q_lower, q_upper: the joint limits by body, what the builder checks a clip against.
-  // probe_set, probes: the end effectors' set and its size when the clip was set (-1, 0: none)
+  // trex::MotionTable says (`table`: its counts and constants, the host rows dropped); the clocks, ONE more, zeroed by every set
+  // and laid out by trex::motion_clock_layout, as `st` points into it; the terms of trex_batch_set_motion_reward, host side - they
+  // travel in the launch arguments - and their held values (trex::motion_held_layout). q_lower, q_upper: the joint limits by
+  // body, what the builder checks a clip against. probe_set, probes: the end effectors' set and its size when the clip was set
+  // (-1, 0: none)
   struct Motion {
     trex::MotionTable table;
     DeviceBuf blob, clock, held;
+    struct Clock { float *t0; int32_t *k; } st{};
     std::vector<TrexMotTerm> terms;
     float step_weight = 1.f;
     int probe_set = -1, probes = 0;
     std::vector<double> q_lower, q_upper;
-    float *t0() const { return clock.as<float>(); }
   } motion;
   // sensor model (trex_batch_set_sensing, include/trex_sensing.h): the group table, ONE device allocation laid out as
-  // sensing_limits.h says (`table`: its counts and maps, the blob dropped); the counters, ONE more, zeroed by every set: episode
-  // counts [n] u32 | row counts [n] u32 | started flags [n] u32 | drawn delays [n][G] i32; the history [9][n][delayed], only while
-  // a group can be late. seed, env_offset: of the last set, kept by a clear. The action delay (trex_batch_set_action_delay): its
-  // range, the action width it was set for, its counters [n] x 4 (ep | k | started | delay) and its history [9][n][cols]
+  // sensing_limits.h says (`table`: its counts and maps, the blob dropped); the counters, ONE more, zeroed by every set and laid
+  // out by trex::sense_counter_layout, as `st` points into it; the history (trex::sense_hist_layout), only while a group can be
+  // late. seed, env_offset: of the last set, kept by a clear. The action delay (trex_batch_set_action_delay): its range, the
+  // action width it was set for, its counters (the same layout with one group, `act_st`) and its history
   struct Sensing {
     trex::SenseTable table;
     DeviceBuf blob, state, hist;
@@ -136,12 +136,11 @@ struct TrexBatch {
     uint32_t env_offset = 0;
     int act_min = 0, act_max = 0, act_cols = 0;
     DeviceBuf act_state, act_hist;
-    uint32_t *ep() const { return state.as<uint32_t>(); }
-    uint32_t *act_ep() const { return act_state.as<uint32_t>(); }
+    struct Counters { uint32_t *ep, *k, *started; int32_t *delay; } st{}, act_st{};
   } sensing;
   // episode randomisation (trex_batch_set_randomization, include/trex_randomize.h): the term table (`table`: host side; `blob`: the
-  // TrexRandTable of randomize.h on the device); the state, ONE allocation zeroed by every set, laid out as `st` points into it
-  // (TrexRandState); the snapshots taken at the set - the gains buffer (`nominal`, with a KP / KD / MAX_FORCE term), the mass
+  // TrexRandTable of randomize.h on the device); the state, ONE allocation zeroed by every set, laid out by
+  // trex::rand_state_layout, as `st` points into it (TrexRandState); the snapshots taken at the set - the gains buffer (`nominal`, with a KP / KD / MAX_FORCE term), the mass
   // scale and the friction (with a term of that kind) - and the switches as they stood then: what a clear puts back
   struct Randomization {
     trex::RandTable table;
@@ -194,3 +193,40 @@ inline int hip_fail(hipError_t e, const char *what) { return fail(TREX_E_HIP, st
 int ensure_gains(TrexBatch *b);
 
 inline int check_batch(const TrexBatch *b) { return b ? TREX_OK : fail(TREX_E_INVALID, "null batch"); }
+
+// runs a table builder, a layout or a check of host_tables.cpp: its refusal - message and code - becomes the call's
+template <class F> int built(F &&build) {
+  try {
+    build();
+    return TREX_OK;
+  } catch (const trex::Refusal &r) {
+    return fail(r.code, r.what());
+  }
+}
+
+// the member at byte `offset` of a state allocation, as a layout of host_tables.cpp places it
+template <class T> T *member_at(const DeviceBuf &buf, size_t offset) { return (T *)(buf.as<char>() + offset); }
+
+// URDF link 0's frame in its body, into the launch arguments that carry it; returns the body's bit of a body mask
+template <class A> uint32_t fill_base(const TrexBatch *b, A &a) {
+  a.base_body = b->links.body[0];
+  trex::tf12(b->links.tf[0], a.base_tf);
+  return 1u << a.base_body;
+}
+
+// One output of an *_info call: `bytes` of the batch's state at `src` for the caller's `dst` (NULL: not asked for). A NULL src is
+// state that is not set: asking for it is refused as "<who><asked> asked for and <unset>" (asked NULL: the name).
+struct InfoCopy { void *dst; const void *src; size_t bytes; const char *name, *unset, *asked; };
+// refuses what is asked for and not set, validates every output as memory of the batch's device, then issues the copies on `stream`
+template <size_t N> int info_copies(const TrexBatch *b, const std::string &who, const InfoCopy (&copies)[N], void *stream) {
+  for (const InfoCopy &c : copies)
+    if (c.dst && !c.src) return fail(TREX_E_INVALID, who + (c.asked ? c.asked : c.name) + " asked for and " + c.unset);
+  DeviceGuard guard(b->device);
+  TrexBatch *mb = const_cast<TrexBatch *>(b);   // (the cache of validated buffers is the batch's)
+  for (const InfoCopy &c : copies)
+    if (c.dst)
+      if (int code = trex_check_device_buffer(mb->device, mb->seen, c.dst, c.bytes, (who + c.name).c_str())) return code;
+  for (const InfoCopy &c : copies)
+    if (c.dst && c.bytes) HIP_TRY(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return TREX_OK;
+}

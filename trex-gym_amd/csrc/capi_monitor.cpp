@@ -29,11 +29,7 @@ extern "C" {
 int trex_batch_set_monitor(TrexBatch *b, int window, int cols_a, int cols_b, uint32_t env_offset) {
   if (check_batch(b)) return TREX_E_INVALID;
   trex::MonitorLayout m;
-  try {
-    m = trex::monitor_layout(b->n, window, cols_a, cols_b, env_offset, TREX_MON_BLOCK);
-  } catch (const trex::Refusal &r) {
-    return fail(r.code, r.what());
-  }
+  if (int c = built([&] { m = trex::monitor_layout(b->n, window, cols_a, cols_b, env_offset, TREX_MON_BLOCK); })) return c;
   DeviceGuard guard(b->device);
   HIP_TRY(hipDeviceSynchronize());   // (no launch still reads the state this call replaces)
   DeviceBuf state;
@@ -55,19 +51,18 @@ int trex_batch_monitor_apply(TrexBatch *b, const float *reward_dev, int reward_s
   if (check_batch(b)) return TREX_E_INVALID;
   const TrexBatch::Monitor &mon = b->monitor;
   const trex::MonitorLayout &m = mon.layout;
-  try {
-    trex::check_monitor_apply(m, reward_dev != nullptr, reward_stride, done_dev != nullptr, done_stride, cols_a_dev != nullptr, stride_a,
-                              cols_b_dev != nullptr, stride_b);
-  } catch (const trex::Refusal &r) {
-    return fail(r.code, r.what());
-  }
+  if (int c = built([&] {
+        trex::check_monitor_apply(m, reward_dev != nullptr, reward_stride, done_dev != nullptr, done_stride, cols_a_dev != nullptr, stride_a,
+                                  cols_b_dev != nullptr, stride_b);
+      }))
+    return c;
   const size_t n = (size_t)b->n;
   DeviceGuard guard(b->device);
-  BUF_TRY(reward_dev, ((n - 1) * reward_stride + 1) * sizeof(float), "trex_batch_monitor_apply: reward");
-  BUF_TRY(done_dev, ((n - 1) * done_stride + 1) * sizeof(float), "trex_batch_monitor_apply: done");
+  BUF_TRY(reward_dev, trex::row_block_bytes(n, reward_stride, 1), "trex_batch_monitor_apply: reward");
+  BUF_TRY(done_dev, trex::row_block_bytes(n, done_stride, 1), "trex_batch_monitor_apply: done");
   BUF_TRY(reason_dev, n * sizeof(int32_t), "trex_batch_monitor_apply: reason");
-  if (m.cols_a > 0) BUF_TRY(cols_a_dev, ((n - 1) * stride_a + m.cols_a) * sizeof(float), "trex_batch_monitor_apply: cols_a");
-  if (m.cols_b > 0) BUF_TRY(cols_b_dev, ((n - 1) * stride_b + m.cols_b) * sizeof(float), "trex_batch_monitor_apply: cols_b");
+  if (m.cols_a > 0) BUF_TRY(cols_a_dev, trex::row_block_bytes(n, stride_a, m.cols_a), "trex_batch_monitor_apply: cols_a");
+  if (m.cols_b > 0) BUF_TRY(cols_b_dev, trex::row_block_bytes(n, stride_b, m.cols_b), "trex_batch_monitor_apply: cols_b");
   TrexMonArgs a{};
   a.st = mon.st;
   a.reward = reward_dev; a.done = done_dev;
@@ -111,35 +106,26 @@ int trex_batch_monitor_info(const TrexBatch *b, int *window, int *cols, float *r
   const trex::MonitorLayout &m = mon.layout;
   const TrexMonState &s = mon.st;
   const size_t n = (size_t)b->n, W = (size_t)m.window, C = (size_t)m.cols;
-  struct Copy { void *dst; const void *src; size_t bytes; const char *what; };
-  const Copy copies[] = {
-      {ring_return_dev, s.ring_return, W * 4, "trex_batch_monitor_info: ring_return"},
-      {ring_length_dev, s.ring_length, W * 4, "trex_batch_monitor_info: ring_length"},
-      {ring_reason_dev, s.ring_reason, W * 4, "trex_batch_monitor_info: ring_reason"},
-      {ring_env_dev, s.ring_env, W * 4, "trex_batch_monitor_info: ring_env"},
-      {ring_t_dev, s.ring_t, W * 4, "trex_batch_monitor_info: ring_t"},
-      {ring_cols_dev, s.ring_cols, W * C * 4, "trex_batch_monitor_info: ring_cols"},
-      {ret_dev, s.ret, n * 8, "trex_batch_monitor_info: ret"},
-      {len_dev, s.len, n * 4, "trex_batch_monitor_info: len"},
-      {episodes_dev, s.episodes, n * 4, "trex_batch_monitor_info: episodes"},
-      {last_return_dev, s.last_return, n * 4, "trex_batch_monitor_info: last_return"},
-      {last_length_dev, s.last_length, n * 4, "trex_batch_monitor_info: last_length"},
-      {last_reason_dev, s.last_reason, n * 4, "trex_batch_monitor_info: last_reason"},
-      {last_t_dev, s.last_t, n * 4, "trex_batch_monitor_info: last_t"},
-      {last_cols_dev, s.last_cols, n * C * 4, "trex_batch_monitor_info: last_cols"},
+  const char *none = "no monitor is set";   // (st holds nulls then)
+  const InfoCopy copies[] = {
+      {ring_return_dev, s.ring_return, W * 4, "ring_return", none},
+      {ring_length_dev, s.ring_length, W * 4, "ring_length", none},
+      {ring_reason_dev, s.ring_reason, W * 4, "ring_reason", none},
+      {ring_env_dev, s.ring_env, W * 4, "ring_env", none},
+      {ring_t_dev, s.ring_t, W * 4, "ring_t", none},
+      {ring_cols_dev, s.ring_cols, W * C * 4, "ring_cols", none},
+      {ret_dev, s.ret, n * 8, "ret", none},
+      {len_dev, s.len, n * 4, "len", none},
+      {episodes_dev, s.episodes, n * 4, "episodes", none},
+      {last_return_dev, s.last_return, n * 4, "last_return", none},
+      {last_length_dev, s.last_length, n * 4, "last_length", none},
+      {last_reason_dev, s.last_reason, n * 4, "last_reason", none},
+      {last_t_dev, s.last_t, n * 4, "last_t", none},
+      {last_cols_dev, s.last_cols, n * C * 4, "last_cols", none},
   };
-  for (const Copy &c : copies)
-    if (c.dst && m.window < 1) return fail(TREX_E_INVALID, std::string(c.what) + " asked for and no monitor is set");
-  DeviceGuard guard(b->device);
-  {
-    TrexBatch *mb = const_cast<TrexBatch *>(b);   // (the cache of validated buffers is the batch's)
-    for (const Copy &c : copies)
-      if (int code = trex_check_device_buffer(mb->device, mb->seen, c.dst, c.bytes, c.what)) return code;
-  }
+  if (int c = info_copies(b, "trex_batch_monitor_info: ", copies, stream)) return c;
   if (window) *window = m.window;
   if (cols) *cols = m.cols;
-  for (const Copy &c : copies)
-    if (c.dst && c.bytes) HIP_TRY(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return TREX_OK;
 }
 

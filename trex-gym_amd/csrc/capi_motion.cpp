@@ -7,16 +7,6 @@
 
 namespace {
 
-// runs a table builder of host_tables.cpp: its refusal - message and code - becomes the call's
-template <class F> int built(F &&build) {
-  try {
-    build();
-    return TREX_OK;
-  } catch (const trex::Refusal &r) {
-    return fail(r.code, r.what());
-  }
-}
-
 // the launch arguments every motion launch shares; `who`: the call, for the refusal of a probe set that changed its size
 int motion_args(TrexBatch *b, const std::string &who, TrexMotArgs &a) {
   const TrexBatch::Motion &m = b->motion;
@@ -28,7 +18,7 @@ int motion_args(TrexBatch *b, const std::string &who, TrexMotArgs &a) {
   a = TrexMotArgs{};
   a.model = b->dmodel; a.table = m.blob.as<float>();
   a.base = b->arr.base; a.q = b->arr.q; a.qd = b->arr.qd;
-  a.t0 = m.t0(); a.k = (int32_t *)(m.t0() + b->n);
+  a.t0 = m.st.t0; a.k = m.st.k;
   a.held = m.held.as<float>();
   if (m.probe_set >= 0) {
     a.probe_body = b->probes[m.probe_set].body.as<int32_t>();
@@ -40,8 +30,7 @@ int motion_args(TrexBatch *b, const std::string &who, TrexMotArgs &a) {
   a.frame_dt = t.frame_dt; a.inv_dt = t.inv_dt; a.duration = t.duration; a.inv_duration = t.inv_duration;
   a.disp[0] = t.disp[0]; a.disp[1] = t.disp[1];
   a.Ts = (float)b->step_seconds; a.step_weight = m.step_weight;
-  a.base_body = b->links.body[0];   // URDF link 0's frame in its body
-  trex::tf12(b->links.tf[0], a.base_tf);
+  fill_base(b, a);
   return TREX_OK;
 }
 
@@ -55,7 +44,11 @@ int trex_batch_set_motion(TrexBatch *b, const double *frames_host, const double 
   const std::string me = "trex_batch_set_motion: ";
   TrexBatch::Motion &m = b->motion;
   trex::MotionTable t;
-  if (int c = built([&] { t = trex::build_motion_table(m.q_lower, m.q_upper, b->obs_order, frames_host, velocities_host, num_frames, frame_dt, loop); }))
+  trex::MotionClockLayout l;
+  if (int c = built([&] {
+        t = trex::build_motion_table(m.q_lower, m.q_upper, b->obs_order, frames_host, velocities_host, num_frames, frame_dt, loop);
+        l = trex::motion_clock_layout(b->n);
+      }))
     return c;
   int probes = 0;
   if (t.frames > 0 && probe_set != -1) {
@@ -72,12 +65,14 @@ int trex_batch_set_motion(TrexBatch *b, const double *frames_host, const double 
   if (t.frames > 0) {
     HIP_TRY(blob.alloc(t.rows.size() * sizeof(float), false));
     HIP_TRY(hipMemcpy(blob.p, t.rows.data(), blob.bytes, hipMemcpyHostToDevice));
-    HIP_TRY(clock.alloc((size_t)b->n * (sizeof(float) + sizeof(int32_t)), true));
+    HIP_TRY(clock.alloc(l.bytes, true));
   }
   HIP_TRY(hipDeviceSynchronize());   // (no launch still reads the table this one replaces; the new one is in place on every stream)
   t.rows = {};
   m.blob = std::move(blob);   // (frees the old table)
   m.clock = std::move(clock);
+  m.st = {};
+  if (m.clock) m.st = {member_at<float>(m.clock, l.t0), member_at<int32_t>(m.clock, l.k)};
   m.held.release();
   m.terms.clear();
   m.step_weight = 1.f;
@@ -120,10 +115,15 @@ int trex_batch_set_motion_reward(TrexBatch *b, const TrexMotionTerm *terms_host,
   TrexBatch::Motion &m = b->motion;
   if (m.table.frames < 2 && num_terms != 0) return fail(TREX_E_INVALID, "trex_batch_set_motion_reward: no clip is set (trex_batch_set_motion)");
   std::vector<TrexMotTerm> terms;
-  if (int c = built([&] { terms = trex::build_motion_terms(b->nj, m.probes > 0, terms_host, num_terms, step_weight); })) return c;
+  trex::Layout l;
+  if (int c = built([&] {
+        terms = trex::build_motion_terms(b->nj, m.probes > 0, terms_host, num_terms, step_weight);
+        l = trex::motion_held_layout(b->n, (int)terms.size());
+      }))
+    return c;
   DeviceGuard guard(b->device);
   DeviceBuf held;
-  if (!terms.empty()) HIP_TRY(held.alloc((size_t)b->n * terms.size() * sizeof(float), true));
+  if (l.bytes > 0) HIP_TRY(held.alloc(l.bytes, true));
   HIP_TRY(hipDeviceSynchronize());   // (no launch still writes the held values this call replaces)
   m.held = std::move(held);
   m.terms = std::move(terms);
@@ -142,7 +142,7 @@ int trex_batch_compose_motion_reward(TrexBatch *b, float *rows_dev, int row_stri
   if (row_stride < nobs + tail) return fail(TREX_E_INVALID, me + "row_stride < 3J + 2 (3J + 5 with penalties in rows)");
   const size_t n = (size_t)b->n;
   DeviceGuard guard(b->device);
-  BUF_TRY(rows_dev, ((n - 1) * row_stride + nobs + tail) * sizeof(float), "trex_batch_compose_motion_reward: rows");
+  BUF_TRY(rows_dev, trex::row_block_bytes(n, row_stride, nobs + tail), "trex_batch_compose_motion_reward: rows");
   BUF_TRY(terms_dev, n * a.num_terms * sizeof(float), "trex_batch_compose_motion_reward: terms");
   a.rows = rows_dev; a.row_stride = row_stride; a.terms_out = terms_dev;
   HIP_TRY(trex_launch_motion_compose(a, (hipStream_t)stream));
@@ -160,7 +160,7 @@ int trex_batch_motion_reset(TrexBatch *b, const uint8_t *mask_dev, const float *
   DeviceGuard guard(b->device);
   BUF_TRY(mask_dev, n, "trex_batch_motion_reset: mask");
   BUF_TRY(time_dev, n * sizeof(float), "trex_batch_motion_reset: time");
-  BUF_TRY(rows_dev, ((n - 1) * row_stride + nobs + tail) * sizeof(float), "trex_batch_motion_reset: rows");
+  BUF_TRY(rows_dev, trex::row_block_bytes(n, row_stride, nobs + tail), "trex_batch_motion_reset: rows");
   a.mask = mask_dev; a.time = time_dev; a.rows = rows_dev; a.row_stride = row_stride;
   a.warm = b->warm.as<float>();
   HIP_TRY(trex_launch_motion_reset(a, (hipStream_t)stream));

@@ -46,16 +46,6 @@ int check_probe_set(const TrexBatch *b, const char *who, int set) {
   return TREX_OK;
 }
 
-// runs a table builder of host_tables.cpp: its refusal - message and code - becomes the call's
-template <class F> int built(F &&build) {
-  try {
-    build();
-    return TREX_OK;
-  } catch (const trex::Refusal &r) {
-    return fail(r.code, r.what());
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -347,8 +337,7 @@ int trex_batch_link_state(TrexBatch *b, int set, int axes, int proper, const flo
   a.pose = pose_dev; a.vel = velocity_dev; a.acc = acceleration_dev;
   a.num_probes = ps.n; a.D = 6 + b->nj;
   a.axes = axes; a.proper = proper != 0;
-  a.base_body = b->links.body[0];   // URDF link 0's frame in its body
-  trex::tf12(b->links.tf[0], a.base_tf);
+  fill_base(b, a);
   HIP_TRY(trex_launch_link_state(a, (hipStream_t)stream));
   return TREX_OK;
 }
@@ -477,16 +466,13 @@ int trex_batch_compose_rows(TrexBatch *b, const float *rows_dev, int row_stride,
                                       ", the columns of the EXTERNAL channels");
   }
   const size_t n = (size_t)b->n;
-  const size_t rows_bytes = ((n - 1) * row_stride + nobs + tail) * sizeof(float), out_bytes = ((n - 1) * out_stride + width) * sizeof(float);
-  {
-    const char *r = (const char *)rows_dev, *o = (const char *)out_rows_dev;
-    if (o < r + rows_bytes && r < o + out_bytes) return fail(TREX_E_INVALID, me + "out_rows overlaps rows");
-  }
+  const size_t rows_bytes = trex::row_block_bytes(n, row_stride, nobs + tail), out_bytes = trex::row_block_bytes(n, out_stride, width);
+  if (trex::ranges_overlap(rows_dev, rows_bytes, out_rows_dev, out_bytes)) return fail(TREX_E_INVALID, me + "out_rows overlaps rows");
   DeviceGuard guard(b->device);
   BUF_TRY(rows_dev, rows_bytes, "trex_batch_compose_rows: rows");
   BUF_TRY(out_rows_dev, out_bytes, "trex_batch_compose_rows: out_rows");
   if (ot.actions) BUF_TRY(actions_dev, n * ot.action_cols * sizeof(float), "trex_batch_compose_rows: actions");
-  if (ot.extern_cols > 0) BUF_TRY(extern_dev, ((n - 1) * extern_stride + ot.extern_cols) * sizeof(float), "trex_batch_compose_rows: extern");
+  if (ot.extern_cols > 0) BUF_TRY(extern_dev, trex::row_block_bytes(n, extern_stride, ot.extern_cols), "trex_batch_compose_rows: extern");
   TrexObsArgs a = query_args<TrexObsArgs>(b);
   const char *blob = b->observation.blob.as<char>();
   a.chan = (const TrexObsChan *)blob; a.col_chan = (const uint8_t *)(blob + ot.o_col);
@@ -495,9 +481,7 @@ int trex_batch_compose_rows(TrexBatch *b, const float *rows_dev, int row_stride,
   a.out = out_rows_dev;
   a.D = 6 + b->nj; a.nobs = nobs; a.extra = ot.extra; a.tail = tail;
   a.row_stride = row_stride; a.out_stride = out_stride; a.ext_stride = extern_stride; a.act_cols = ot.action_cols;
-  a.base_body = b->links.body[0];   // URDF link 0's frame in its body
-  trex::tf12(b->links.tf[0], a.base_tf);
-  a.body_mask = ot.body_mask | (1u << a.base_body);
+  a.body_mask = ot.body_mask | fill_base(b, a);
   HIP_TRY(trex_launch_observation(a, (hipStream_t)stream));
   return TREX_OK;
 }
@@ -506,14 +490,18 @@ int trex_batch_compose_rows(TrexBatch *b, const float *rows_dev, int row_stride,
 int trex_batch_set_reward(TrexBatch *b, const TrexRewardTerm *terms_host, int num_terms) {
   if (check_batch(b)) return TREX_E_INVALID;
   trex::RewTable t;
-  if (int c = built([&] { t = trex::build_reward_table(b->links, b->obs_order, b->nb, b->action_cols(), terms_host, num_terms); })) return c;
+  trex::RewardHistLayout l;
+  if (int c = built([&] {
+        t = trex::build_reward_table(b->links, b->obs_order, b->nb, b->action_cols(), terms_host, num_terms);
+        l = trex::reward_hist_layout(b->n, t.action_cols, b->nj, t.terms);
+      }))
+    return c;
   DeviceGuard guard(b->device);
   DeviceBuf blob, hist;
-  const size_t n = (size_t)b->n, A = (size_t)t.action_cols, J = (size_t)b->nj, T = (size_t)t.terms;
   if (t.terms > 0) {
     HIP_TRY(blob.alloc(t.blob.size(), false));
     HIP_TRY(hipMemcpy(blob.p, t.blob.data(), blob.bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hist.alloc(n * (A + J + 2 * T + 1) * sizeof(float), true));
+    HIP_TRY(hist.alloc(l.bytes, true));
   }
   HIP_TRY(hipDeviceSynchronize());   // (no launch still reads the table this one replaces; the new one is in place on every stream)
   t.blob = {};
@@ -521,12 +509,10 @@ int trex_batch_set_reward(TrexBatch *b, const TrexRewardTerm *terms_host, int nu
   r.blob = std::move(blob);   // (frees the old table and its history)
   r.hist = std::move(hist);
   r.table = std::move(t);
-  r.prev_act = r.prev_qd = r.timer = r.held = nullptr; r.valid = nullptr;
-  if (r.hist) {
-    r.prev_act = r.hist.as<float>();
-    r.prev_qd = r.prev_act + n * A; r.timer = r.prev_qd + n * J; r.held = r.timer + n * T;
-    r.valid = (int32_t *)(r.held + n * T);
-  }
+  r.st = {};
+  if (r.hist)
+    r.st = {member_at<float>(r.hist, l.prev_act), member_at<float>(r.hist, l.prev_qd), member_at<float>(r.hist, l.timer),
+            member_at<float>(r.hist, l.held), member_at<int32_t>(r.hist, l.valid)};
   return TREX_OK;
 }
 
@@ -553,7 +539,7 @@ int trex_batch_compose_reward(TrexBatch *b, float *rows_dev, int row_stride, con
                                     std::to_string(rt.action_cols) + " (set the terms again)");
   const size_t n = (size_t)b->n;
   DeviceGuard guard(b->device);
-  BUF_TRY(rows_dev, ((n - 1) * row_stride + nobs + tail) * sizeof(float), "trex_batch_compose_reward: rows");
+  BUF_TRY(rows_dev, trex::row_block_bytes(n, row_stride, nobs + tail), "trex_batch_compose_reward: rows");
   if (rt.actions) BUF_TRY(actions_dev, n * rt.action_cols * sizeof(float), "trex_batch_compose_reward: actions");
   if (rt.command) BUF_TRY(command_dev, n * 3 * sizeof(float), "trex_batch_compose_reward: command");
   BUF_TRY(terms_dev, n * rt.terms * sizeof(float), "trex_batch_compose_reward: terms");
@@ -563,12 +549,10 @@ int trex_batch_compose_reward(TrexBatch *b, float *rows_dev, int row_stride, con
   a.rows = rows_dev; a.actions = rt.actions ? actions_dev : nullptr; a.command = rt.command ? command_dev : nullptr;
   a.sens = rt.contact ? b->sens.as<float>() : nullptr;
   a.terms_out = terms_dev;
-  a.prev_act = r.prev_act; a.prev_qd = r.prev_qd; a.timer = r.timer; a.held = r.held; a.valid = r.valid;
+  a.prev_act = r.st.prev_act; a.prev_qd = r.st.prev_qd; a.timer = r.st.timer; a.held = r.st.held; a.valid = r.st.valid;
   a.D = 6 + b->nj; a.nj = b->nj; a.num_terms = rt.terms; a.row_stride = row_stride; a.act_cols = rt.action_cols;
   a.Ts = (float)b->step_seconds;
-  a.base_body = b->links.body[0];   // URDF link 0's frame in its body
-  trex::tf12(b->links.tf[0], a.base_tf);
-  a.body_mask = rt.body_mask | (1u << a.base_body);
+  a.body_mask = rt.body_mask | fill_base(b, a);
   HIP_TRY(trex_launch_reward(a, (hipStream_t)stream));
   return TREX_OK;
 }
@@ -579,7 +563,7 @@ int trex_batch_reward_reset(TrexBatch *b, const uint8_t *mask_dev, void *stream)
   if (r.table.terms < 1) return fail(TREX_E_INVALID, "trex_batch_reward_reset: no terms are set (trex_batch_set_reward)");
   DeviceGuard guard(b->device);
   BUF_TRY(mask_dev, (size_t)b->n, "trex_batch_reward_reset: mask");
-  HIP_TRY(trex_launch_reward_reset(mask_dev, b->n, r.table.terms, r.timer, r.held, r.valid, (hipStream_t)stream));
+  HIP_TRY(trex_launch_reward_reset(mask_dev, b->n, r.table.terms, r.st.timer, r.st.held, r.st.valid, (hipStream_t)stream));
   return TREX_OK;
 }
 

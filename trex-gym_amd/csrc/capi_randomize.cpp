@@ -36,21 +36,21 @@ extern "C" {
 
 int trex_batch_set_randomization(TrexBatch *b, const TrexRandomTerm *terms_host, int num_terms, uint64_t seed, uint32_t env_offset) {
   if (check_batch(b)) return TREX_E_INVALID;
-  const std::string me = "trex_batch_set_randomization: ";
-  if ((uint64_t)env_offset + (uint64_t)b->n > (1ull << 32)) return fail(TREX_E_INVALID, me + "env_offset + N is beyond 2^32");
   trex::RandTable t;
-  try {
-    t = trex::build_random_table(b->nb, b->nj, b->stiff, terms_host, num_terms);
-  } catch (const trex::Refusal &r) {
-    return fail(r.code, r.what());
-  }
+  trex::RandStateLayout l;
+  if (int c = built([&] {
+        trex::check_env_offset("trex_batch_set_randomization: ", env_offset, b->n);
+        t = trex::build_random_table(b->nb, b->nj, b->stiff, terms_host, num_terms);
+        l = trex::rand_state_layout(b->n, t.terms, t.pushes);
+      }))
+    return c;
   DeviceGuard guard(b->device);
   HIP_TRY(hipDeviceSynchronize());   // (no launch still reads the table or the state this call replaces)
   if (int c = clear_randomization(b)) return c;
   TrexBatch::Randomization &r = b->random;
   r.seed = seed; r.env_offset = env_offset;
   if (t.terms == 0) return TREX_OK;
-  const size_t n = (size_t)b->n, T = (size_t)t.terms, P = (size_t)t.pushes;
+  const size_t n = (size_t)b->n;
   DeviceBuf blob, state, nominal, mass0, friction0;
   TrexRandTable tab;
   std::memset(&tab, 0, sizeof tab);
@@ -61,13 +61,11 @@ int trex_batch_set_randomization(TrexBatch *b, const TrexRandomTerm *terms_host,
   std::memcpy(tab.push_slot, t.push_slot, sizeof tab.push_slot);
   HIP_TRY(blob.alloc(sizeof tab, false));
   HIP_TRY(hipMemcpy(blob.p, &tab, sizeof tab, hipMemcpyHostToDevice));
-  // ep | k | started | off [P] | push_left [P] | push_force [P][3] | push_base [P][6] | values [T][32], each [n] outermost
-  const size_t words = n * (3 + P + P + 3 * P + 6 * P + T * TREX_TL);
-  HIP_TRY(state.alloc(words * sizeof(uint32_t), true));
-  TrexRandState st{};
-  st.ep = state.as<uint32_t>(); st.k = st.ep + n; st.started = st.k + n;
-  st.off = (int32_t *)(st.started + n); st.push_left = st.off + n * P;
-  st.push_force = (float *)(st.push_left + n * P); st.push_base = st.push_force + n * P * 3; st.values = st.push_base + n * P * 6;
+  HIP_TRY(state.alloc(l.bytes, true));
+  const TrexRandState st = {member_at<uint32_t>(state, l.ep),       member_at<uint32_t>(state, l.k),
+                            member_at<uint32_t>(state, l.started),  member_at<int32_t>(state, l.off),
+                            member_at<int32_t>(state, l.push_left), member_at<float>(state, l.push_force),
+                            member_at<float>(state, l.push_base),   member_at<float>(state, l.values)};
   if (t.gains) {
     if (int c = ensure_gains(b)) return c;
     HIP_TRY(nominal.alloc(b->gains.bytes, false));
@@ -108,7 +106,7 @@ int trex_batch_apply_randomization(TrexBatch *b, const float *done_dev, int done
   if (r.table.command && !command_dev) return fail(TREX_E_INVALID, me + "a COMMAND term is set and command is null");
   const size_t n = (size_t)b->n;
   DeviceGuard guard(b->device);
-  BUF_TRY(done_dev, ((n - 1) * done_stride + 1) * sizeof(float), "trex_batch_apply_randomization: done");
+  BUF_TRY(done_dev, trex::row_block_bytes(n, done_stride, 1), "trex_batch_apply_randomization: done");
   BUF_TRY(command_dev, n * 3 * sizeof(float), "trex_batch_apply_randomization: command");
   TrexRandArgs a{};
   a.table = r.blob.as<TrexRandTable>(); a.model = b->dmodel; a.st = r.st;
@@ -134,23 +132,16 @@ int trex_batch_randomization_reset(TrexBatch *b, const uint8_t *mask_dev, void *
 int trex_batch_randomization_info(const TrexBatch *b, int *num_terms, float *values_dev, float *push_force_dev, int32_t *push_left_dev,
                                   void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
-  const std::string me = "trex_batch_randomization_info: ";
   const TrexBatch::Randomization &r = b->random;
-  if (values_dev && r.table.terms < 1) return fail(TREX_E_INVALID, me + "values asked for and no terms are set");
-  if ((push_force_dev || push_left_dev) && r.table.pushes < 1) return fail(TREX_E_INVALID, me + "push state asked for and no PUSH terms are set");
-  const size_t n = (size_t)b->n, vbytes = n * r.table.terms * TREX_TL * sizeof(float);
-  const size_t fbytes = n * r.table.pushes * 3 * sizeof(float), lbytes = n * r.table.pushes * sizeof(int32_t);
-  DeviceGuard guard(b->device);
-  {
-    TrexBatch *mb = const_cast<TrexBatch *>(b);   // (the cache of validated buffers is the batch's)
-    if (int c = trex_check_device_buffer(mb->device, mb->seen, values_dev, vbytes, "trex_batch_randomization_info: values")) return c;
-    if (int c = trex_check_device_buffer(mb->device, mb->seen, push_force_dev, fbytes, "trex_batch_randomization_info: push_force")) return c;
-    if (int c = trex_check_device_buffer(mb->device, mb->seen, push_left_dev, lbytes, "trex_batch_randomization_info: push_left")) return c;
-  }
+  const size_t n = (size_t)b->n, P = (size_t)r.table.pushes;
+  const bool pushes = P > 0;   // (without PUSH terms the push members are empty, not absent)
+  const InfoCopy copies[] = {
+      {values_dev, r.st.values, n * r.table.terms * TREX_TL * sizeof(float), "values", "no terms are set"},
+      {push_force_dev, pushes ? r.st.push_force : nullptr, n * P * 3 * sizeof(float), "push_force", "no PUSH terms are set", "push state"},
+      {push_left_dev, pushes ? r.st.push_left : nullptr, n * P * sizeof(int32_t), "push_left", "no PUSH terms are set", "push state"},
+  };
+  if (int c = info_copies(b, "trex_batch_randomization_info: ", copies, stream)) return c;
   if (num_terms) *num_terms = r.table.terms;
-  if (values_dev) HIP_TRY(hipMemcpyAsync(values_dev, r.st.values, vbytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  if (push_force_dev) HIP_TRY(hipMemcpyAsync(push_force_dev, r.st.push_force, fbytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  if (push_left_dev) HIP_TRY(hipMemcpyAsync(push_left_dev, r.st.push_left, lbytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return TREX_OK;
 }
 

@@ -7,20 +7,14 @@
 
 namespace {
 
-// runs a table builder of host_tables.cpp: its refusal - message and code - becomes the call's
-template <class F> int built(F &&build) {
-  try {
-    build();
-    return TREX_OK;
-  } catch (const trex::Refusal &r) {
-    return fail(r.code, r.what());
-  }
-}
-
-// true when the byte ranges [a, a + na) and [b, b + nb) share a byte
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-  const char *p = (const char *)a, *q = (const char *)b;
-  return p < q + nb && q < p + na;
+// `bytes` of counters, zeroed, and the pointers into them; an empty layout: no allocation, null pointers
+int make_counters(const trex::SenseCounterLayout &l, DeviceBuf &state, TrexBatch::Sensing::Counters &st) {
+  st = {};
+  if (l.bytes == 0) return TREX_OK;
+  HIP_TRY(state.alloc(l.bytes, true));
+  st = {member_at<uint32_t>(state, l.ep), member_at<uint32_t>(state, l.k), member_at<uint32_t>(state, l.started),
+        member_at<int32_t>(state, l.delay)};
+  return TREX_OK;
 }
 
 }  // namespace
@@ -29,25 +23,32 @@ extern "C" {
 
 int trex_batch_set_sensing(TrexBatch *b, const TrexSenseGroup *groups_host, int num_groups, uint64_t seed, uint32_t env_offset) {
   if (check_batch(b)) return TREX_E_INVALID;
-  const std::string me = "trex_batch_set_sensing: ";
-  if ((uint64_t)env_offset + (uint64_t)b->n > (1ull << 32)) return fail(TREX_E_INVALID, me + "env_offset + N is beyond 2^32");
   trex::SenseTable t;
-  if (int c = built([&] { t = trex::build_sense_table(3 * b->nj + b->observation.table.extra, groups_host, num_groups); })) return c;
+  trex::SenseCounterLayout counters;
+  trex::Layout history;
+  if (int c = built([&] {
+        trex::check_env_offset("trex_batch_set_sensing: ", env_offset, b->n);
+        t = trex::build_sense_table(3 * b->nj + b->observation.table.extra, groups_host, num_groups);
+        counters = trex::sense_counter_layout(b->n, t.groups);
+        history = trex::sense_hist_layout(b->n, t.delayed);
+      }))
+    return c;
   DeviceGuard guard(b->device);
   DeviceBuf blob, state, hist;
-  const size_t n = (size_t)b->n;
+  TrexBatch::Sensing::Counters st;
   if (t.groups > 0) {
     HIP_TRY(blob.alloc(t.blob.size(), false));
     HIP_TRY(hipMemcpy(blob.p, t.blob.data(), blob.bytes, hipMemcpyHostToDevice));
-    HIP_TRY(state.alloc(n * (3 + (size_t)t.groups) * sizeof(uint32_t), true));
-    if (t.delayed > 0) HIP_TRY(hist.alloc((size_t)TREX_SENSE_SLOTS * n * t.delayed * sizeof(float), true));
   }
+  if (int c = make_counters(counters, state, st)) return c;
+  if (history.bytes > 0) HIP_TRY(hist.alloc(history.bytes, true));
   HIP_TRY(hipDeviceSynchronize());   // (no launch still reads the table this one replaces; the new one is in place on every stream)
   t.blob = {};
   TrexBatch::Sensing &s = b->sensing;
   s.blob = std::move(blob);   // (frees the old table, counters and history)
   s.state = std::move(state);
   s.hist = std::move(hist);
+  s.st = st;
   s.table = std::move(t);
   s.seed = seed; s.env_offset = env_offset;
   return TREX_OK;
@@ -67,10 +68,10 @@ int trex_batch_apply_sensing(TrexBatch *b, const float *rows_dev, int row_stride
   if (row_stride < width || out_stride < width)
     return fail(TREX_E_INVALID, me + "a stride below " + std::to_string(width) + " = 3J + E + the tail");
   const size_t n = (size_t)b->n;
-  const size_t rows_bytes = ((n - 1) * row_stride + width) * sizeof(float), out_bytes = ((n - 1) * out_stride + width) * sizeof(float);
+  const size_t rows_bytes = trex::row_block_bytes(n, row_stride, width), out_bytes = trex::row_block_bytes(n, out_stride, width);
   if (rows_dev == out_rows_dev) {
     if (row_stride != out_stride) return fail(TREX_E_INVALID, me + "in place, and the two strides differ");
-  } else if (overlap(rows_dev, rows_bytes, out_rows_dev, out_bytes)) {
+  } else if (trex::ranges_overlap(rows_dev, rows_bytes, out_rows_dev, out_bytes)) {
     return fail(TREX_E_INVALID, me + "out_rows overlaps rows in part");
   }
   DeviceGuard guard(b->device);
@@ -80,7 +81,7 @@ int trex_batch_apply_sensing(TrexBatch *b, const float *rows_dev, int row_stride
   const char *blob = s.blob.as<char>();
   a.group = (const TrexSenseGrp *)blob; a.col_group = (const int16_t *)(blob + t.o_col_group); a.col_hist = (const int16_t *)(blob + t.o_col_hist);
   a.rows = rows_dev; a.out = out_rows_dev;
-  a.ep = s.ep(); a.k = a.ep + n; a.started = a.k + n; a.delay = (int32_t *)(a.started + n);
+  a.ep = s.st.ep; a.k = s.st.k; a.started = s.st.started; a.delay = s.st.delay;
   a.hist = s.hist.as<float>();
   a.n_envs = b->n; a.obs_dim = D; a.tail = tail; a.num_groups = t.groups; a.delayed = t.delayed;
   a.row_stride = row_stride; a.out_stride = out_stride;
@@ -99,27 +100,34 @@ int trex_batch_sensing_reset(TrexBatch *b, const uint8_t *mask_dev, void *stream
   const size_t n = (size_t)b->n;
   DeviceGuard guard(b->device);
   BUF_TRY(mask_dev, n, "trex_batch_sensing_reset: mask");
-  HIP_TRY(trex_launch_sensing_reset(mask_dev, b->n, s.state ? s.ep() + 2 * n : nullptr, s.act_state ? s.act_ep() + 2 * n : nullptr,
-                                    (hipStream_t)stream));
+  HIP_TRY(trex_launch_sensing_reset(mask_dev, b->n, s.st.started, s.act_st.started, (hipStream_t)stream));
   return TREX_OK;
 }
 
 int trex_batch_set_action_delay(TrexBatch *b, int delay_min, int delay_max) {
   if (check_batch(b)) return TREX_E_INVALID;
-  if (int c = built([&] { trex::check_sense_delay("trex_batch_set_action_delay: ", delay_min, delay_max); })) return c;
+  const int cols = b->action_cols();
+  trex::SenseCounterLayout counters;
+  trex::Layout history;
+  if (int c = built([&] {
+        trex::check_sense_delay("trex_batch_set_action_delay: ", delay_min, delay_max);
+        if (delay_max > 0) {   // the counters of one group, the history of the action's columns
+          counters = trex::sense_counter_layout(b->n, 1);
+          history = trex::sense_hist_layout(b->n, cols);
+        }
+      }))
+    return c;
+  if (cols > 64) return fail(TREX_E_INVALID, "trex_batch_set_action_delay: action rows wider than 64 columns");   // (the launch's 64 lanes per env)
   DeviceGuard guard(b->device);
   DeviceBuf state, hist;
-  const size_t n = (size_t)b->n;
-  const int cols = b->action_cols();
-  if (cols > 64) return fail(TREX_E_INVALID, "trex_batch_set_action_delay: action rows wider than 64 columns");   // (the launch's 64 lanes per env)
-  if (delay_max > 0) {
-    HIP_TRY(state.alloc(n * 4 * sizeof(uint32_t), true));
-    HIP_TRY(hist.alloc((size_t)TREX_SENSE_SLOTS * n * cols * sizeof(float), true));
-  }
+  TrexBatch::Sensing::Counters st;
+  if (int c = make_counters(counters, state, st)) return c;
+  if (history.bytes > 0) HIP_TRY(hist.alloc(history.bytes, true));
   HIP_TRY(hipDeviceSynchronize());   // (no launch still writes the history this call replaces)
   TrexBatch::Sensing &s = b->sensing;
   s.act_state = std::move(state);
   s.act_hist = std::move(hist);
+  s.act_st = st;
   s.act_min = delay_min; s.act_max = delay_max; s.act_cols = delay_max > 0 ? cols : 0;
   return TREX_OK;
 }
@@ -134,7 +142,7 @@ int trex_batch_delay_actions(TrexBatch *b, const float *actions_dev, const uint8
                                     std::to_string(s.act_cols) + " (set the delay again)");
   if (!actions_dev || !out_actions_dev) return fail(TREX_E_INVALID, me + "actions or out_actions is null");
   const size_t n = (size_t)b->n, bytes = n * s.act_cols * sizeof(float);
-  if (actions_dev != out_actions_dev && overlap(actions_dev, bytes, out_actions_dev, bytes))
+  if (actions_dev != out_actions_dev && trex::ranges_overlap(actions_dev, bytes, out_actions_dev, bytes))
     return fail(TREX_E_INVALID, me + "out_actions overlaps actions in part");
   DeviceGuard guard(b->device);
   BUF_TRY(actions_dev, bytes, "trex_batch_delay_actions: actions");
@@ -142,7 +150,7 @@ int trex_batch_delay_actions(TrexBatch *b, const float *actions_dev, const uint8
   BUF_TRY(done_prev_dev, n, "trex_batch_delay_actions: done_prev");
   TrexActDelayArgs a{};
   a.actions = actions_dev; a.done_prev = done_prev_dev; a.out = out_actions_dev;
-  a.ep = s.act_ep(); a.k = a.ep + n; a.started = a.k + n; a.delay = (int32_t *)(a.started + n);
+  a.ep = s.act_st.ep; a.k = s.act_st.k; a.started = s.act_st.started; a.delay = s.act_st.delay;
   a.hist = s.act_hist.as<float>();
   a.n_envs = b->n; a.cols = s.act_cols; a.delay_min = s.act_min; a.delay_max = s.act_max;
   a.key0 = (uint32_t)s.seed; a.key1 = (uint32_t)(s.seed >> 32); a.env_offset = s.env_offset;
@@ -153,25 +161,17 @@ int trex_batch_delay_actions(TrexBatch *b, const float *actions_dev, const uint8
 int trex_batch_sensing_info(const TrexBatch *b, int *num_groups, int *delayed_columns, int *action_delay_min, int *action_delay_max,
                             int32_t *delays_dev, int32_t *action_delay_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
-  const std::string me = "trex_batch_sensing_info: ";
   const TrexBatch::Sensing &s = b->sensing;
-  if (delays_dev && s.table.groups < 1) return fail(TREX_E_INVALID, me + "delays asked for and no groups are set");
-  if (action_delay_dev && !s.act_state) return fail(TREX_E_INVALID, me + "action delays asked for and no action delay is set");
   const size_t n = (size_t)b->n;
-  DeviceGuard guard(b->device);
-  {
-    TrexBatch *mb = const_cast<TrexBatch *>(b);   // (the cache of validated buffers is the batch's)
-    if (int c = trex_check_device_buffer(mb->device, mb->seen, delays_dev, n * s.table.groups * sizeof(int32_t), "trex_batch_sensing_info: delays")) return c;
-    if (int c = trex_check_device_buffer(mb->device, mb->seen, action_delay_dev, n * sizeof(int32_t), "trex_batch_sensing_info: action_delay")) return c;
-  }
+  const InfoCopy copies[] = {
+      {delays_dev, s.st.delay, n * s.table.groups * sizeof(int32_t), "delays", "no groups are set"},
+      {action_delay_dev, s.act_st.delay, n * sizeof(int32_t), "action_delay", "no action delay is set", "action delays"},
+  };
+  if (int c = info_copies(b, "trex_batch_sensing_info: ", copies, stream)) return c;
   if (num_groups) *num_groups = s.table.groups;
   if (delayed_columns) *delayed_columns = s.table.delayed;
   if (action_delay_min) *action_delay_min = s.act_min;
   if (action_delay_max) *action_delay_max = s.act_max;
-  if (delays_dev)
-    HIP_TRY(hipMemcpyAsync(delays_dev, s.ep() + 3 * n, n * s.table.groups * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  if (action_delay_dev)
-    HIP_TRY(hipMemcpyAsync(action_delay_dev, s.act_ep() + 3 * n, n * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return TREX_OK;
 }
 

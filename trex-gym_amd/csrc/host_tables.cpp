@@ -4,9 +4,76 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 
 namespace trex {
+
+size_t row_block_bytes(size_t n, int stride, int width) { return ((n - 1) * (size_t)stride + (size_t)width) * sizeof(float); }
+
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+  const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+  return p < q + nb && q < p + na;
+}
+
+void check_env_offset(const std::string &who, uint32_t env_offset, int n_envs) {
+  if ((uint64_t)env_offset + (uint64_t)n_envs > (1ull << 32)) throw Refusal(who + "env_offset + N is beyond 2^32");
+}
+
+size_t Layout::take(const char *name, size_t member_bytes, size_t align) {
+  const size_t at = (bytes + align - 1) / align * align;
+  members.push_back({name, at, member_bytes, align});
+  bytes = at + member_bytes;
+  return at;
+}
+
+RewardHistLayout reward_hist_layout(int n_envs, int A_cols, int J_joints, int T_terms) {
+  RewardHistLayout l;
+  if (T_terms == 0) return l;
+  const size_t n = (size_t)n_envs, A = (size_t)A_cols, J = (size_t)J_joints, T = (size_t)T_terms;
+  l.prev_act = l.take("prev_act", n * A * 4, 4); l.prev_qd = l.take("prev_qd", n * J * 4, 4);
+  l.timer = l.take("timer", n * T * 4, 4); l.held = l.take("held", n * T * 4, 4);
+  l.valid = l.take("valid", n * 4, 4);
+  return l;
+}
+
+MotionClockLayout motion_clock_layout(int n_envs) {
+  MotionClockLayout l;
+  l.t0 = l.take("t0", (size_t)n_envs * 4, 4); l.k = l.take("k", (size_t)n_envs * 4, 4);
+  return l;
+}
+
+Layout motion_held_layout(int n_envs, int T_terms) {
+  Layout l;
+  if (T_terms > 0) l.take("held", (size_t)n_envs * (size_t)T_terms * 4, 4);
+  return l;
+}
+
+SenseCounterLayout sense_counter_layout(int n_envs, int G_groups) {
+  SenseCounterLayout l;
+  if (G_groups == 0) return l;
+  const size_t n = (size_t)n_envs;
+  l.ep = l.take("ep", n * 4, 4); l.k = l.take("k", n * 4, 4); l.started = l.take("started", n * 4, 4);
+  l.delay = l.take("delay", n * (size_t)G_groups * 4, 4);
+  return l;
+}
+
+Layout sense_hist_layout(int n_envs, int cols) {
+  Layout l;
+  if (cols > 0) l.take("hist", (size_t)TREX_SENSE_SLOTS * (size_t)n_envs * (size_t)cols * 4, 4);
+  return l;
+}
+
+RandStateLayout rand_state_layout(int n_envs, int T_terms, int P_pushes) {
+  RandStateLayout l;
+  if (T_terms == 0) return l;
+  const size_t n = (size_t)n_envs, T = (size_t)T_terms, P = (size_t)P_pushes;
+  l.ep = l.take("ep", n * 4, 4); l.k = l.take("k", n * 4, 4); l.started = l.take("started", n * 4, 4);
+  l.off = l.take("off", n * P * 4, 4); l.push_left = l.take("push_left", n * P * 4, 4);
+  l.push_force = l.take("push_force", n * P * 3 * 4, 4); l.push_base = l.take("push_base", n * P * 6 * 4, 4);
+  l.values = l.take("values", n * T * TREX_TL * 4, 4);
+  return l;
+}
 
 void fill_device_model(const trex::HostModel &h, TrexDeviceModel &d) {
   std::memset(&d, 0, sizeof d);
@@ -592,22 +659,23 @@ MonitorLayout monitor_layout(int n_envs, int window, int cols_a, int cols_b, uin
   if ((long long)cols_a + (long long)cols_b > TREX_MON_MAXCOLS)
     throw Refusal(me + std::to_string((long long)cols_a + (long long)cols_b) + " columns, at most " + std::to_string(TREX_MON_MAXCOLS));
   if (n_envs < 1) throw Refusal(me + "a batch without envs");
-  if ((uint64_t)env_offset + (uint64_t)n_envs > (1ull << 32)) throw Refusal(me + "env_offset + N is beyond 2^32");
+  check_env_offset(me, env_offset, n_envs);
   m.window = window; m.cols_a = cols_a; m.cols_b = cols_b; m.cols = cols_a + cols_b;
   while (m.team < m.cols) m.team *= 2;
   const int per = block / m.team;
   m.groups = (n_envs + per - 1) / per;
   const size_t n = (size_t)n_envs, C = (size_t)m.cols, W = (size_t)window;
-  size_t at = 0;
-  auto take = [&at](size_t &member, size_t count, size_t size) { member = at; at += count * size; };
-  take(m.ret, n, 8); take(m.col, n * C, 8); take(m.total, 1, 8); take(m.by_reason, 4, 8);
-  take(m.len, n, 4); take(m.episodes, n, 4); take(m.fin, n, 4);
-  take(m.last_return, n, 4); take(m.last_length, n, 4); take(m.last_reason, n, 4); take(m.last_t, n, 4); take(m.last_cols, n * C, 4);
-  take(m.t, 1, 4);
-  take(m.ring_return, W, 4); take(m.ring_length, W, 4); take(m.ring_reason, W, 4); take(m.ring_env, W, 4); take(m.ring_t, W, 4);
-  take(m.ring_cols, W * C, 4);
-  take(m.counts, (size_t)m.groups, 4);
-  m.bytes = at;
+  m.ret = m.take("ret", n * 8, 8); m.col = m.take("col", n * C * 8, 8);
+  m.total = m.take("total", 8, 8); m.by_reason = m.take("by_reason", 4 * 8, 8);
+  m.len = m.take("len", n * 4, 4); m.episodes = m.take("episodes", n * 4, 4); m.fin = m.take("fin", n * 4, 4);
+  m.last_return = m.take("last_return", n * 4, 4); m.last_length = m.take("last_length", n * 4, 4);
+  m.last_reason = m.take("last_reason", n * 4, 4); m.last_t = m.take("last_t", n * 4, 4);
+  m.last_cols = m.take("last_cols", n * C * 4, 4);
+  m.t = m.take("t", 4, 4);
+  m.ring_return = m.take("ring_return", W * 4, 4); m.ring_length = m.take("ring_length", W * 4, 4);
+  m.ring_reason = m.take("ring_reason", W * 4, 4); m.ring_env = m.take("ring_env", W * 4, 4); m.ring_t = m.take("ring_t", W * 4, 4);
+  m.ring_cols = m.take("ring_cols", W * C * 4, 4);
+  m.counts = m.take("counts", (size_t)m.groups * 4, 4);
   return m;
 }
 

@@ -1,4 +1,5 @@
-// The tables the kernels read, as pure host arithmetic: everything the C-ABI computes between its argument checks and its HIP calls.
+// The tables the kernels read and the layouts of the per-env state they write, as pure host arithmetic: everything the C-ABI computes
+// between its argument checks and its HIP calls.
 // INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h, motion_limits.h, sensing_limits.h and include/trex_batch.h, and nothing of HIP; it makes
 // no HIP call and knows no batch. It builds with plain g++ -std=c++17, as model.cpp does, so that tests/host/tables_harness.cpp runs
 // it under the sanitizers on a machine without a GPU. A refusal is a thrown Refusal whose text is the C-ABI's message, whole.
@@ -29,6 +30,45 @@ struct Refusal : std::runtime_error {
 };
 
 void fill_device_model(const HostModel &h, TrexDeviceModel &d);
+
+// The byte extent of n rows of `width` floats, `stride` floats apart: the last row ends at its width, not at its stride (n 1:
+// width * 4 whatever the stride). Formed in size_t. The caller has refused a stride below the width.
+size_t row_block_bytes(size_t n, int stride, int width);
+// true when the byte ranges [a, a + na) and [b, b + nb) share a byte
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb);
+// a batch of n envs whose env 0 has the global index env_offset: every global index fits 32 bits. who: the call, for the refusal
+void check_env_offset(const std::string &who, uint32_t env_offset, int n_envs);
+
+// The layout of ONE allocation that holds a piece of per-env state: the members in the order they were taken, each at the first
+// multiple of its alignment behind the one before, and the bytes of the whole. Every state layout below is built with take(), so
+// it lists its own members: what tests/host/layout_check.hpp walks. A layout is computed from counts alone; the HIP units
+// allocate `bytes` and point into the allocation once.
+struct Layout {
+  struct Member { const char *name; size_t at, bytes, align; };
+  std::vector<Member> members;
+  size_t bytes = 0;
+  size_t take(const char *name, size_t member_bytes, size_t align);   // the member's offset
+};
+// trex_batch_set_reward: the history of the terms - previous actions [n][A] | previous qd [n][J] | timers [n][T] | held values
+// [n][T] | valid flags [n]. T 0 gives the empty layout (bytes 0).
+struct RewardHistLayout : Layout { size_t prev_act = 0, prev_qd = 0, timer = 0, held = 0, valid = 0; };
+RewardHistLayout reward_hist_layout(int n, int A, int J, int T);
+// trex_batch_set_motion: the clocks - start times [n] f32 | step counts [n] i32
+struct MotionClockLayout : Layout { size_t t0 = 0, k = 0; };
+MotionClockLayout motion_clock_layout(int n);
+// trex_batch_set_motion_reward: the held values [n][T]. T 0 gives the empty layout.
+Layout motion_held_layout(int n, int T);
+// trex_batch_set_sensing: the counters - episode counts [n] u32 | row counts [n] u32 | started flags [n] u32 | drawn delays [n][G]
+// i32. trex_batch_set_action_delay: the same with G = 1. G 0 gives the empty layout.
+struct SenseCounterLayout : Layout { size_t ep = 0, k = 0, started = 0, delay = 0; };
+SenseCounterLayout sense_counter_layout(int n, int G);
+// the history of the delayed columns [TREX_SENSE_SLOTS][n][cols] f32: cols is the table's `delayed` (sensing) or the action
+// width (action delay). cols 0 gives the empty layout.
+Layout sense_hist_layout(int n, int cols);
+// trex_batch_set_randomization: the state, in the order of TrexRandState (randomize.h), each member [n] outermost - ep | k |
+// started | off [P] | push_left [P] | push_force [P][3] | push_base [P][6] | values [T][TREX_TL]. T 0 gives the empty layout.
+struct RandStateLayout : Layout { size_t ep = 0, k = 0, started = 0, off = 0, push_left = 0, push_force = 0, push_base = 0, values = 0; };
+RandStateLayout rand_state_layout(int n, int T, int P);
 
 // rotation row-major (9) | translation (3): the [12] layout of every transform a kernel reads
 void tf12(const Tf &t, float out[12]);
@@ -141,11 +181,11 @@ RandTable build_random_table(int nb, int nj, bool stiffness, const TrexRandomTer
 // that holds the C columns, at least 1), the workgroups of that launch, and the layout of the ONE allocation that is the
 // monitor's state - byte offsets, 8-byte members first, in the order of TrexMonState (monitor.h). block: the lanes of an
 // accumulate workgroup. window 0 gives the empty layout (bytes 0).
-struct MonitorLayout {
+struct MonitorLayout : Layout {
   int window = 0, cols_a = 0, cols_b = 0, cols = 0, team = 1, groups = 0;
   size_t ret = 0, col = 0, total = 0, by_reason = 0, len = 0, episodes = 0, fin = 0, last_return = 0, last_length = 0, last_reason = 0,
          last_t = 0, last_cols = 0, t = 0, ring_return = 0, ring_length = 0, ring_reason = 0, ring_env = 0, ring_t = 0, ring_cols = 0,
-         counts = 0, bytes = 0;
+         counts = 0;
 };
 MonitorLayout monitor_layout(int n_envs, int window, int cols_a, int cols_b, uint32_t env_offset, int block);
 // trex_batch_monitor_apply: the strides against the widths; the pointers as "is it there" flags

@@ -134,6 +134,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         # the privileged critic row (trex_gym.critic.attach): [n, Dv], its column names, the recorded sources, and the call that
         # refills it behind every step and reset
         self.critic_rows, self.critic_names, self.critic_spec, self._critic_fill = None, [], None, None
+        # the joint force/torque sensor (trex_gym.joint_sensor.attach): the batch's calls, the readings [n, J, 6] and [n, 6], and the
+        # call that refreshes them behind every step and reset
+        self.joint_api, self.joint_reaction, self.joint_base_residual, self._joint_fill = None, None, None, None
         self.collision = collision
         self._init_queries()                    # the link table and the caches of the read-only queries (vec_queries.py)
         if observations is not None and len(observations):
@@ -376,6 +379,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         if self.random_api is not None:         # the envs that were reset start an episode: their draws, before the compose shows them
             self.random_api.reset(mask)
             self.random_api.apply(self._no_done, self.commands)
+        if self._joint_fill is not None:        # the joint sensor at the state the reset left: before the compose and the critic's row, which may read it
+            self._joint_fill(None)
         if self._step_rows is not None:
             self._compose(None, out)
         if self._clean_block is not None or self._delayed_actions is not None:   # the envs that were reset start an episode of their sensors and of their action history
@@ -443,6 +448,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
                 self.random_api.apply(out, self.commands, 3 * self.J + 1)
             if self.monitor_api is not None:
                 self.monitor_api.apply(out, out, None, self.reward_terms, self.motion_terms, 3 * self.J, 3 * self.J + 1)
+            if self._joint_fill is not None:      # the joint sensor: behind the last launch that writes the state
+                self._joint_fill(out)
         else:   # (observation channels: one more launch, after the resets of the step call - the row of the new episode's state)
             self.batch.step_rows(applied, self._step_rows, self._penalties, done=self.done)
             if self.rewards is not None:
@@ -453,6 +460,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
                 self.random_api.apply(self._step_rows, self.commands, 3 * self.J + 1)
             if self.monitor_api is not None:      # (the reward and done columns of the step's rows: what the compose carries along)
                 self.monitor_api.apply(self._step_rows, self._step_rows, None, self.reward_terms, self.motion_terms, 3 * self.J, 3 * self.J + 1)
+            if self._joint_fill is not None:      # the joint sensor: before the channels' compose, whose external columns may read it
+                self._joint_fill(self._step_rows)
             self._compose(actions, out)
         if self._clean_block is not None:       # behind the last compose: the sensors' view into the block the policy reads
             self.sense_api.apply(out, self.rows)
@@ -466,12 +475,14 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         """Open-loop rollout: actions [S, n, J] f32 on device -> rows [S, n, 3J+2] (obs | reward | done of every step), S
         env-steps in ONE launch (trex_batch_step_many; bitwise S calls of step_tensor). `rows`, `obs`, `rew`, `done_f`
         and `done` then hold the last step. sharding.split_rows(rows[s]) cuts a step's block into the three.
-        ValueError with observations, rewards, motion, sensing or randomisation: an open-loop launch has no compose between its steps.
+        ValueError with observations, rewards, motion, sensing, randomisation or the joint sensor: an open-loop launch has no compose between its steps.
         With a monitor attached its applies follow the launch, one per step block (not together with fall termination)."""
         if self.random_api is not None:
             raise ValueError("step_many_tensor: not with randomisation - the open-loop launch has no per-step launch of the redraws")
         if self.monitor_api is not None and self._term_on:
             raise ValueError("step_many_tensor: not with a monitor and fall termination - the batch keeps the last step's reasons only")
+        if self._joint_fill is not None:
+            raise ValueError("step_many_tensor: not with the joint sensor - the open-loop launch has no per-step launch of its query")
         if self.sense_api is not None:
             raise ValueError("step_many_tensor: not with sensing - the open-loop launch has no per-step launch of the sensor model")
         if self.motion is not None:

@@ -737,6 +737,9 @@ int trex_batch_time_steps(TrexBatch *batch, const float *actions_dev, float *obs
 /* So is the episode monitor of a batch - the return, the length and the end reason of every finished episode, the window of the
  * last W of them and its summary, kept on the device: */
 #include "trex_monitor.h"
+/* So are the first-order derivatives of the inverse dynamics along the configuration tangent and the generalised velocity, a
+ * read-only query beside the dynamics queries: */
+#include "trex_dynamics_derivatives.h"
 /* So is the joint force/torque sensor - the 6-D wrench every joint transmits, a read-only query beside the dynamics queries - and
  * the generalised velocity with its backward difference: */
 #include "trex_joint_wrench.h"

@@ -124,6 +124,8 @@ int trex_policy_minibatch_step(TrexPolicy *policy, float *theta_dev, float *grad
 #ifdef __cplusplus
 }
 #endif
+/* policy distillation: the learner with a regression loss onto a teacher's action distribution */
+#include "trex_policy_distill.h"
 /* the privileged critic of a policy object: a value net with an input row, a width and moments of its own */
 #include "trex_policy_critic.h"
 #endif /* TREX_POLICY_H */

@@ -69,6 +69,15 @@ __device__ __forceinline__ void tanh16(f32x16 &v) {
 // lgkmcnt(0), MFMA, 170 - 190 cycles per step instead of the MFMA's 64 (scripts/learn_phases.py: layer 1 7.8 k cycles for 40 steps).
 #define LDS_ISSUED() asm volatile("" ::: "memory")
 
+// Adam's two moments of one element, the rounding stated: m = fma(b1, m, (1 - b1) g), v = fma(b2, v, ((1 - b2) g) g). Left as
+// `b2 * v + (1 - b2) * g * g` the compiler contracted the second one differently in adam_kernel (policy_step.hip) and in
+// learn_adam_kernel (ppo_learner.hip: the form above, which both now state), and a minibatch step differed from the same gradient
+// followed by trex_policy_adam by one unit in the last place of v (tests/test_gpu_distill.py holds them bitwise equal).
+__device__ __forceinline__ void adam_moments(float g, float b1, float b2, float &m, float &v) {
+  m = __builtin_fmaf(b1, m, (1.f - b1) * g);
+  v = __builtin_fmaf(b2, v, ((1.f - b2) * g) * g);
+}
+
 // row of accumulator register `reg` on a lane of half h = lane >> 5 (C/D layout of the 32x32 MFMA forms)
 __device__ __forceinline__ constexpr int rowmap(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 

@@ -446,8 +446,7 @@ __global__ __launch_bounds__(1024) void adam_kernel(float *theta, float *grad, f
   }
   auto upd = [&](float g, float &mi, float &vi, float &th) {
     const float gi = g * scale;
-    mi = b1 * mi + (1.f - b1) * gi;
-    vi = b2 * vi + (1.f - b2) * gi * gi;
+    adam_moments(gi, b1, b2, mi, vi);
     th -= lr_t * mi / (sqrtf(vi) + eps);
   };
 #pragma unroll

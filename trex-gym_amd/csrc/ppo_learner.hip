@@ -48,7 +48,7 @@ __host__ __device__ inline LdsLayout make_lds_layout(const Layout &lay) {
   o = (o + 3) & ~3;
   l.X = o; o += TILE * XS;
   l.buf = o; o += (4 * HID + 2 * TILE) * TS;  // parked tiles [row][env]: H1, H2 [64] | D3 [32] | D2, D1 [64] | DL [32]
-  l.vec = o; o += 128;                        // per-env loss terms [32] | 1 / sd per action [32] | sum of logstd [1]
+  l.vec = o; o += 128;                        // per-env loss terms [32] | 1 / sd per action [32] | sum of logstd [1] (the kernel's VEC)
   l.total = o;
   return l;
 }
@@ -75,6 +75,17 @@ struct LearnArgsV : LearnArgs {
   const float *obs_v;
   int Dv;
 };
+// The loss at the output layer is a template parameter beside CRITIC: LOSS_PPO is the clipped surrogate + clipped value loss, the
+// head as it was before that parameter (profiles/r34_distill.txt); LOSS_DISTILL (include/trex_policy_distill.h) regresses onto a
+// teacher - `act` carries the teacher's mean, `ret` its value, and logp0 / val0 / adv / adv_stats are null and never loaded.
+constexpr int LOSS_PPO = 0, LOSS_DISTILL = 1;
+struct LearnArgsD : LearnArgs {
+  const float *teacher_logstd;   // [A] (MSE: any A readable floats, not used)
+  int kind;                      // TREX_DISTILL_MSE / _KL
+  int has_value;                 // 0: `ret` is a stand-in address, the value head's target is its own output
+};
+template <bool CRITIC, int LOSS>
+using LearnArgsOf = std::conditional_t<LOSS == LOSS_DISTILL, LearnArgsD, std::conditional_t<CRITIC, LearnArgsV, LearnArgs>>;
 __device__ __forceinline__ int net_D(const LearnArgs &g, int) { return g.lay.D; }
 __device__ __forceinline__ int net_D(const LearnArgsV &g, int net) { return net ? g.Dv : g.lay.D; }
 __device__ __forceinline__ const float *net_obs(const LearnArgs &g, int) { return g.obs; }
@@ -115,8 +126,9 @@ __device__ unsigned long long learn_stamps[512 * 12];
 #else
 #define LSTAMP(i) do {} while (0)
 #endif
-template <bool CRITIC>
-__global__ __launch_bounds__(256) void learn_grad_kernel(std::conditional_t<CRITIC, LearnArgsV, LearnArgs> g) {
+template <bool CRITIC, int LOSS = LOSS_PPO>
+__global__ __launch_bounds__(256) void learn_grad_kernel(LearnArgsOf<CRITIC, LOSS> g) {
+  static_assert(LOSS == LOSS_PPO || !CRITIC, "distillation is instantiated without a critic");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   LSTAMP(0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, net = blockIdx.y;     // net 0: policy, 1: value
@@ -174,6 +186,7 @@ __global__ __launch_bounds__(256) void learn_grad_kernel(std::conditional_t<CRIT
   // barrier, a full round trip in the middle of the chain): their round trips hide behind the staging
   f32x16 act_in;
   float adv_in, logp0_in, val0_in, ret_in, advm, advr;
+  float lt_raw = 0.f;                   // (distillation) the teacher's logstd of action `lane`
   {
     const long long sidx_raw = tile_rows[col];
     const long long sidx = sidx_raw >= 0 ? sidx_raw : 0;
@@ -182,10 +195,17 @@ __global__ __launch_bounds__(256) void learn_grad_kernel(std::conditional_t<CRIT
       const int a = rowmap(r, h);
       act_in[r] = g.act[(size_t)sidx * A + (a < A ? a : A - 1)];
     }
-    adv_in = g.adv[sidx]; logp0_in = g.logp0[sidx]; val0_in = g.val0[sidx]; ret_in = g.ret[sidx];
-    advm = g.adv_stats[0]; advr = g.adv_stats[1];
+    if constexpr (LOSS == LOSS_PPO) {
+      adv_in = g.adv[sidx]; logp0_in = g.logp0[sidx]; val0_in = g.val0[sidx]; ret_in = g.ret[sidx];
+      advm = g.adv_stats[0]; advr = g.adv_stats[1];
+    } else {          // (compile time: still no control flow) the teacher's value; its logstd
+      ret_in = g.ret[sidx];
+      lt_raw = g.teacher_logstd[lane < A ? lane : A - 1];
+    }
   }
-  float *VEC = lds + L.vec;             // [0..31] per-env loss term | [32..63] 1 / sd per action | [64] sum of logstd | [96..99] dump slot
+  // VEC: [0..31] per-env loss term | [32..63] 1 / sd per action | [64] sum of logstd | [96..99] dump slot; distillation keeps the
+  // teacher's variance per action in [64..95] (the sum of logstd is not needed there) and the loss's constant part in [100]
+  float *VEC = lds + L.vec;
   const float ls_raw = g.theta[g.lay.logstd + (lane < A ? lane : A - 1)];      // (policy net, wave 3 uses it) logstd of action `lane`
   LDS_ISSUED();
 #pragma unroll
@@ -199,7 +219,8 @@ __global__ __launch_bounds__(256) void learn_grad_kernel(std::conditional_t<CRIT
     X[ii * XS + kk] = raw[u];
   }
   // (the loss inputs are pinned to registers HERE - without this the compiler sinks the loads to their use)
-  asm volatile("" : "+v"(act_in), "+v"(adv_in), "+v"(logp0_in), "+v"(val0_in), "+v"(ret_in));
+  if constexpr (LOSS == LOSS_PPO) asm volatile("" : "+v"(act_in), "+v"(adv_in), "+v"(logp0_in), "+v"(val0_in), "+v"(ret_in));
+  else asm volatile("" : "+v"(act_in), "+v"(ret_in), "+v"(lt_raw));
   __syncthreads();
   LSTAMP(1);
   const float *W1 = lds + lds_of(g.lay, net ? g.lay.vW1 : g.lay.pW1), *b1 = lds + lds_of(g.lay, net ? g.lay.vb1 : g.lay.pb1);
@@ -276,11 +297,25 @@ __global__ __launch_bounds__(256) void learn_grad_kernel(std::conditional_t<CRIT
     for (int r = 0; r < 16; r++) H1[(32 * u + rowmap(r, h)) * TS + col] = h1o[r];
   }
   if (net == 0 && wave == 3) {
-    // 1 / sd of every action and the sum of logstd, once per workgroup (until round 4 the loss took 16 expf per lane)
-    const float ls_in = lane < A ? ls_raw : 0.f;
-    if (lane < 32) VEC[32 + lane] = lane < A ? expf(-ls_in) : 0.f;
-    const float sl = half_sum(lane < 32 ? ls_in : 0.f);
-    if (lane == 0) VEC[64] = sl;
+    if constexpr (LOSS == LOSS_PPO) {
+      // 1 / sd of every action and the sum of logstd, once per workgroup (until round 4 the loss took 16 expf per lane)
+      const float ls_in = lane < A ? ls_raw : 0.f;
+      if (lane < 32) VEC[32 + lane] = lane < A ? expf(-ls_in) : 0.f;
+      const float sl = half_sum(lane < 32 ? ls_in : 0.f);
+      if (lane == 0) VEC[64] = sl;
+    } else {
+      // distillation, once per workgroup: 1 / sd_s and sd_t^2 of every action, and the part of the loss that no sample moves,
+      // sum_a (ls_s - ls_t - 1/2). The squared error is the same head with sd_s = 1, sd_t = 0 and no constant (selects on the
+      // kind, which is uniform: no branch)
+      const bool on = g.kind == TREX_DISTILL_KL && lane < A;
+      const float ls_in = on ? ls_raw : 0.f, lt_in = on ? lt_raw : 0.f;
+      if (lane < 32) {
+        VEC[32 + lane] = lane < A ? (on ? expf(-ls_in) : 1.f) : 0.f;
+        VEC[64 + lane] = on ? expf(2.f * lt_in) : 0.f;
+      }
+      const float cl = half_sum(lane < 32 && on ? (ls_in - lt_in) - 0.5f : 0.f);
+      if (lane == 0) VEC[100] = cl;
+    }
   }
   __syncthreads();     // ---- B1: H1 is parked
   LSTAMP(2);
@@ -329,36 +364,69 @@ __global__ __launch_bounds__(256) void learn_grad_kernel(std::conditional_t<CRIT
 #pragma unroll
       for (int s = 0; s < 16; s++) mu = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[16 + s], hb[s], mu, 0, 0, 0);
       LSTAMP(8);
-      f32x16 z, isd;
-      float zz = 0.f;
+      if constexpr (LOSS == LOSS_DISTILL) {
+        // KL(teacher || student) of diagonal Gaussians, per sample sum_a [ls_s - ls_t + (sd_t^2 + (mu_t - mu_s)^2) / (2 sd_s^2) - 1/2],
+        // or half the squared error (sd_s = 1, sd_t = 0, no constant: the vectors wave 3 staged): dL/dmu_s = (mu_s - mu_t) / sd_s^2 / mb,
+        // dL/dls_s = (1 - (sd_t^2 + (mu_t - mu_s)^2) / sd_s^2) / mb (KL alone). No expf, no ratio, no clip. The means are
+        // compared as the nets give them, unclipped. An invalid sample (ragged last tile) has mu_t = mu_s and no logstd term.
+        const bool kl = g.kind == TREX_DISTILL_KL;
+        f32x16 i2, q;
+        float term = 0.f;
 #pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int a = rowmap(r, h);
-        isd[r] = VEC[32 + a];                           // 0 beyond the last action
-        const float ac = valid ? act_in[r] : mu[r];
-        z[r] = (ac - mu[r]) * isd[r];
-        zz = __builtin_fmaf(z[r], z[r], zz);
-      }
-      zz += __shfl_xor(zz, 32, 64);
-      const float sum_ls = VEC[64];
-      const float logp = -0.5f * zz - sum_ls - 0.5f * LOG_2PI * (float)A;
-      const float an = valid ? (adv_in - advm) * advr : 0.f;
-      const float ratio = valid ? expf(logp - logp0_in) : 1.f;
-      const float rc = fminf(fmaxf(ratio, 1.f - g.cliprange), 1.f + g.cliprange);
-      const float l1 = -an * ratio, l2 = -an * rc;
-      const bool through = l1 >= l2 || rc == ratio;      // the branch of max() that carries a gradient w.r.t. ratio
-      const float dlogp = valid && through ? -an * ratio * inv_mb : 0.f;     // dL/dlogp = dL/dratio * ratio
-      // L_pg = mean(max(-a r, -a clip(r))), r = exp(logp - logp0): dL/dlogp = (-a) r / mb on the live branch;
-      // dlogp/dmu = z / sd; dlogp/dlogstd = z^2 - 1. The sums over the tile's samples (grad b3, grad logstd, the surrogate term)
-      // are taken by the helper waves from the parked tiles, beside delta 2 (until round 4: 35 DPP reductions right here)
+        for (int r = 0; r < 16; r++) {       // (all LDS reads before the first write, as in the PPO head)
+          const int a = rowmap(r, h);
+          i2[r] = VEC[32 + a];
+          q[r] = VEC[64 + a];
+        }
 #pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int a = rowmap(r, h);
-        d3[r] = dlogp * z[r] * isd[r];
-        D3[a * TS + col] = d3[r];
-        DL[a * TS + col] = a < A ? dlogp * (z[r] * z[r] - 1.f) : 0.f;
+        for (int r = 0; r < 16; r++) {
+          i2[r] *= i2[r];                                  // 1 / sd_s^2; 0 beyond the last action
+          const float dm = valid ? mu[r] - act_in[r] : 0.f;
+          q[r] = (q[r] + dm * dm) * i2[r];
+          term = __builtin_fmaf(0.5f, q[r], term);
+          d3[r] = dm * i2[r] * inv_mb;
+        }
+        const float lw = kl && valid ? inv_mb : 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          const int a = rowmap(r, h);
+          D3[a * TS + col] = d3[r];
+          DL[a * TS + col] = a < A ? (1.f - q[r]) * lw : 0.f;
+        }
+        term += __shfl_xor(term, 32, 64);
+        if (h == 0) VEC[col] = valid ? term + VEC[100] : 0.f;
+      } else {
+        f32x16 z, isd;
+        float zz = 0.f;
+  #pragma unroll
+        for (int r = 0; r < 16; r++) {
+          const int a = rowmap(r, h);
+          isd[r] = VEC[32 + a];                           // 0 beyond the last action
+          const float ac = valid ? act_in[r] : mu[r];
+          z[r] = (ac - mu[r]) * isd[r];
+          zz = __builtin_fmaf(z[r], z[r], zz);
+        }
+        zz += __shfl_xor(zz, 32, 64);
+        const float sum_ls = VEC[64];
+        const float logp = -0.5f * zz - sum_ls - 0.5f * LOG_2PI * (float)A;
+        const float an = valid ? (adv_in - advm) * advr : 0.f;
+        const float ratio = valid ? expf(logp - logp0_in) : 1.f;
+        const float rc = fminf(fmaxf(ratio, 1.f - g.cliprange), 1.f + g.cliprange);
+        const float l1 = -an * ratio, l2 = -an * rc;
+        const bool through = l1 >= l2 || rc == ratio;      // the branch of max() that carries a gradient w.r.t. ratio
+        const float dlogp = valid && through ? -an * ratio * inv_mb : 0.f;     // dL/dlogp = dL/dratio * ratio
+        // L_pg = mean(max(-a r, -a clip(r))), r = exp(logp - logp0): dL/dlogp = (-a) r / mb on the live branch;
+        // dlogp/dmu = z / sd; dlogp/dlogstd = z^2 - 1. The sums over the tile's samples (grad b3, grad logstd, the surrogate term)
+        // are taken by the helper waves from the parked tiles, beside delta 2 (until round 4: 35 DPP reductions right here)
+  #pragma unroll
+        for (int r = 0; r < 16; r++) {
+          const int a = rowmap(r, h);
+          d3[r] = dlogp * z[r] * isd[r];
+          D3[a * TS + col] = d3[r];
+          DL[a * TS + col] = a < A ? dlogp * (z[r] * z[r] - 1.f) : 0.f;
+        }
+        if (h == 0) VEC[col] = valid ? fmaxf(l1, l2) : 0.f;
       }
-      if (h == 0) VEC[col] = valid ? fmaxf(l1, l2) : 0.f;
     } else {
       // ---- value head: v = w . h2 + b (k ascending); clipped value loss; its gradients are rank-1 in the sample
       float v = 0.f;
@@ -368,14 +436,22 @@ __global__ __launch_bounds__(256) void learn_grad_kernel(std::conditional_t<CRIT
       for (int s = 0; s < 16; s++) v = __builtin_fmaf(H2[(32 + rowmap(s, h)) * TS + col], W3[32 + rowmap(s, h)], v);
       v += __shfl_xor(v, 32, 64);
       v += b3[0];
-      const float v0 = valid ? val0_in : v, rt = valid ? ret_in : v;
-      const float dvc = fminf(fmaxf(v - v0, -g.cliprange), g.cliprange);
-      const float vclip = v0 + dvc;
-      const float e1 = (v - rt) * (v - rt), e2 = (vclip - rt) * (vclip - rt);
-      // 0.5 mean(max(e1, e2)): gradient (v - R) on the unclipped branch, (vclip - R) [clip inactive] on the other
-      dv = e1 >= e2 ? (v - rt) : ((dvc == v - v0) ? (vclip - rt) : 0.f);
-      dv = valid ? g.vf_coef * dv * inv_mb : 0.f;
-      if (h == 0) { D3[col] = dv; VEC[col] = valid ? 0.5f * fmaxf(e1, e2) : 0.f; }     // DV[env], the env's loss term: for waves 1 - 3
+      if constexpr (LOSS == LOSS_DISTILL) {
+        // half the squared error to the teacher's value: dL/dv = vf_coef (v - v_t) / mb, the PPO head's unclipped branch in the
+        // same order of operations; vf_coef == 0 (the teacher's values may then be absent): exact zeros
+        const float rt = (valid && g.has_value) ? ret_in : v;
+        dv = (valid && g.vf_coef != 0.f) ? g.vf_coef * (v - rt) * inv_mb : 0.f;
+        if (h == 0) { D3[col] = dv; VEC[col] = 0.5f * ((v - rt) * (v - rt)); }
+      } else {
+        const float v0 = valid ? val0_in : v, rt = valid ? ret_in : v;
+        const float dvc = fminf(fmaxf(v - v0, -g.cliprange), g.cliprange);
+        const float vclip = v0 + dvc;
+        const float e1 = (v - rt) * (v - rt), e2 = (vclip - rt) * (vclip - rt);
+        // 0.5 mean(max(e1, e2)): gradient (v - R) on the unclipped branch, (vclip - R) [clip inactive] on the other
+        dv = e1 >= e2 ? (v - rt) : ((dvc == v - v0) ? (vclip - rt) : 0.f);
+        dv = valid ? g.vf_coef * dv * inv_mb : 0.f;
+        if (h == 0) { D3[col] = dv; VEC[col] = valid ? 0.5f * fmaxf(e1, e2) : 0.f; }     // DV[env], the env's loss term: for waves 1 - 3
+      }
     }
   }
   __syncthreads();     // ---- B3: D3 (policy) / dv (value) is parked
@@ -613,8 +689,7 @@ __global__ __launch_bounds__(256) void learn_adam_kernel(ApplyArgs g, int reduce
   const float lr_t = (float)g.red[LR_SLOT];       // lr sqrt(1 - b2^t) / (1 - b1^t), formed by the reduce launch
   auto upd = [&](float gr, float &mi, float &vi, float &th) {
     const float gi = gr * scale;
-    mi = g.b1 * mi + (1.f - g.b1) * gi;
-    vi = g.b2 * vi + (1.f - g.b2) * gi * gi;
+    adam_moments(gi, g.b1, g.b2, mi, vi);
     th -= lr_t * mi / (sqrtf(vi) + g.eps);
   };
   if (i < P4) {
@@ -653,6 +728,41 @@ int trex_policy_minibatch_stats(TrexPolicy *p, const float *adv_dev, int64_t num
   return TREX_OK;
 }
 
+// ---- what every loss shares on the host: the partial buffer and the launches behind learn_grad_kernel
+static int learn_stride(const TrexPolicy *p) {      // a partial row: the parameters, padded to float4, + one float4 of loss sums
+  return (int)((((size_t)p->lay.count + 3) & ~(size_t)3) + 4);
+}
+static int learn_workspace(TrexPolicy *p, int tiles, int stride) {
+  if (tiles > p->grad_tiles) {      // workspace, grown on demand (never inside a graph capture: the first call is eager)
+    float *buf = nullptr;
+    HIP_TRY(hipMalloc((void **)&buf, (size_t)tiles * stride * sizeof(float)));
+    p->allocs.push_back(buf);
+    HIP_TRY(hipMemset(buf, 0, (size_t)tiles * stride * sizeof(float)));     // (pad elements are never written: they stay 0)
+    p->grad_partial = buf; p->grad_tiles = tiles;
+    if (!p->learn_counter) {
+      HIP_TRY(hipMalloc((void **)&p->learn_counter, sizeof(unsigned)));
+      p->allocs.push_back(p->learn_counter);
+      HIP_TRY(hipMemset(p->learn_counter, 0, sizeof(unsigned)));
+      HIP_TRY(hipMalloc((void **)&p->learn_red, 4096 * sizeof(double)));
+      p->allocs.push_back(p->learn_red);
+    }
+  }
+  return TREX_OK;
+}
+static int launch_reduce(TrexPolicy *p, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev, float *loss_sums_dev, int tiles,
+                         int stride, int mb, float ent_coef, float lr, float beta1, float beta2, float eps, float max_grad_norm,
+                         float grad_scale, int advance, void *stream, ApplyArgs *out_args, int *out_groups) {
+  const int apply_groups = ((stride >> 2) + AP_COLS - 1) / AP_COLS;
+  ApplyArgs b{p->grad_partial, theta_dev, grad_dev, m_dev, v_dev, loss_sums_dev, p->learn_red, p->learn_counter, p->adam_step,
+              tiles, stride, p->lay.count, p->lay.logstd, p->A, ent_coef, lr, beta1, beta2, eps, max_grad_norm, 1.0f / (float)mb,
+              grad_scale, advance};
+  hipLaunchKernelGGL(learn_reduce_kernel, dim3(apply_groups), dim3(AP_COLS * AP_GROUPS), 0, (hipStream_t)stream, b);
+  HIP_TRY(hipGetLastError());
+  if (out_args) *out_args = b;
+  if (out_groups) *out_groups = apply_groups;
+  return TREX_OK;
+}
+
 // gradient of one minibatch: learn_grad_kernel + learn_reduce_kernel -> grad_dev (UNclipped, times grad_scale)
 static int launch_minibatch_grad(TrexPolicy *p, const char *who, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev,
                                  const float *obs_dev, const float *obs_v_dev, const float *act_dev, const float *logp_dev,
@@ -687,22 +797,8 @@ static int launch_minibatch_grad(TrexPolicy *p, const char *who, float *theta_de
   BUF_TRY(adv_stats_dev, 2 * sizeof(float), "minibatch step: adv_stats");
   BUF_TRY(loss_sums_dev, 2 * sizeof(float), "minibatch step: loss_sums");
   const int tiles = (mb + TILE - 1) / TILE;
-  const int stride = (int)(((P + 3) & ~(size_t)3) + 4);       // parameters, padded to float4, + one float4 of loss sums
-  const int apply_groups = ((stride >> 2) + AP_COLS - 1) / AP_COLS;
-  if (tiles > p->grad_tiles) {      // workspace, grown on demand (never inside a graph capture: the first call is eager)
-    float *buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&buf, (size_t)tiles * stride * sizeof(float)));
-    p->allocs.push_back(buf);
-    HIP_TRY(hipMemset(buf, 0, (size_t)tiles * stride * sizeof(float)));     // (pad elements are never written: they stay 0)
-    p->grad_partial = buf; p->grad_tiles = tiles;
-    if (!p->learn_counter) {
-      HIP_TRY(hipMalloc((void **)&p->learn_counter, sizeof(unsigned)));
-      p->allocs.push_back(p->learn_counter);
-      HIP_TRY(hipMemset(p->learn_counter, 0, sizeof(unsigned)));
-      HIP_TRY(hipMalloc((void **)&p->learn_red, 4096 * sizeof(double)));
-      p->allocs.push_back(p->learn_red);
-    }
-  }
+  const int stride = learn_stride(p);
+  if (int rc = learn_workspace(p, tiles, stride)) return rc;
   const LdsLayout L = make_lds_layout(p->lay);
   LearnArgs a{theta_dev, obs_dev, act_dev, logp_dev, val_dev, adv_dev, ret_dev, reinterpret_cast<const long long *>(perm_dev),
               adv_stats_dev, p->grad_partial, first, mb, stride, cliprange, vf_coef, p->lay};
@@ -715,14 +811,8 @@ static int launch_minibatch_grad(TrexPolicy *p, const char *who, float *theta_de
     hipLaunchKernelGGL(learn_grad_kernel<false>, dim3(tiles, 2), dim3(256), (size_t)L.total * sizeof(float), (hipStream_t)stream, a);
   }
   HIP_TRY(hipGetLastError());
-  ApplyArgs b{p->grad_partial, theta_dev, grad_dev, m_dev, v_dev, loss_sums_dev, p->learn_red, p->learn_counter, p->adam_step,
-              tiles, stride, p->lay.count, p->lay.logstd, p->A, ent_coef, lr, beta1, beta2, eps, max_grad_norm, 1.0f / (float)mb,
-              grad_scale, advance};
-  hipLaunchKernelGGL(learn_reduce_kernel, dim3(apply_groups), dim3(AP_COLS * AP_GROUPS), 0, (hipStream_t)stream, b);
-  HIP_TRY(hipGetLastError());
-  if (out_args) *out_args = b;
-  if (out_groups) *out_groups = apply_groups;
-  return TREX_OK;
+  return launch_reduce(p, theta_dev, grad_dev, m_dev, v_dev, loss_sums_dev, tiles, stride, mb, ent_coef, lr, beta1, beta2, eps,
+                       max_grad_norm, grad_scale, advance, stream, out_args, out_groups);
 }
 
 int trex_policy_minibatch_step(TrexPolicy *p, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev, const float *obs_dev,
@@ -785,6 +875,81 @@ int trex_policy_critic_minibatch_grad(TrexPolicy *p, const float *theta_dev, flo
                                obs_v_dev, act_dev, logp_dev, val_dev, adv_dev, ret_dev, num_samples, perm_dev, first, mb, adv_stats_dev,
                                cliprange, ent_coef, vf_coef, 0.f, 0.9f, 0.999f, 1e-5f, 0.f, grad_scale, 0, loss_sums_dev, stream,
                                nullptr, nullptr);
+}
+
+// ---- policy distillation (include/trex_policy_distill.h): the LOSS_DISTILL instantiation of learn_grad_kernel, then the same reduce
+static int launch_distill_grad(TrexPolicy *p, const char *who, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev,
+                               const float *obs_dev, const float *tmean_dev, const float *tvalue_dev, const float *tlogstd_dev,
+                               int64_t num_samples, const int64_t *perm_dev, int first, int mb, int kind, float vf_coef, float lr,
+                               float beta1, float beta2, float eps, float max_grad_norm, float grad_scale, int advance,
+                               float *loss_sums_dev, void *stream, ApplyArgs *out_args, int *out_groups) {
+  if (!p || !theta_dev || !grad_dev || !obs_dev || !tmean_dev || !perm_dev) return trex_fail(TREX_E_INVALID, std::string(who) + ": null argument");
+  if (mb <= 0 || first < 0 || num_samples <= 0) return trex_fail(TREX_E_INVALID, std::string(who) + ": bad sizes");
+  if (kind != TREX_DISTILL_MSE && kind != TREX_DISTILL_KL)
+    return trex_fail(TREX_E_INVALID, std::string(who) + ": unknown loss kind (TREX_DISTILL_MSE, TREX_DISTILL_KL)");
+  if (kind == TREX_DISTILL_KL && !tlogstd_dev) return trex_fail(TREX_E_INVALID, std::string(who) + ": the KL loss needs teacher_logstd");
+  if (!tvalue_dev && vf_coef != 0.f) return trex_fail(TREX_E_INVALID, std::string(who) + ": teacher_value may be null only with vf_coef == 0");
+  if (p->Dv) return trex_fail(TREX_E_INVALID, std::string(who) + ": the policy has a critic width set (a student has no privileged critic)");
+  if (p->D > 96) return trex_fail(TREX_E_INVALID, std::string(who) + ": the learner stages 96 observation columns (obs_dim <= 96)");
+  if ((p->lay.vW1 + (p->lay.count - p->lay.logstd)) / 4 > 256 * LEARN_UF || (p->lay.logstd - p->lay.vW1) / 4 > 256 * LEARN_UF)
+    return trex_fail(TREX_E_INVALID, std::string(who) + ": the learner stages one net's parameters in one trip of 256 x 13 float4s");
+  const size_t P = (size_t)p->lay.count, N = (size_t)num_samples;
+  BUF_TRY(theta_dev, P * sizeof(float), "distillation step: theta");
+  BUF_TRY(grad_dev, P * sizeof(float), "distillation step: grad");
+  BUF_TRY(m_dev, P * sizeof(float), "distillation step: m");
+  BUF_TRY(v_dev, P * sizeof(float), "distillation step: v");
+  BUF_TRY(obs_dev, N * p->D * sizeof(float), "distillation step: obs");
+  BUF_TRY(tmean_dev, N * p->A * sizeof(float), "distillation step: teacher_mean");
+  BUF_TRY(tvalue_dev, N * sizeof(float), "distillation step: teacher_value");
+  BUF_TRY(tlogstd_dev, (size_t)p->A * sizeof(float), "distillation step: teacher_logstd");
+  BUF_TRY(perm_dev, ((size_t)first + mb) * sizeof(int64_t), "distillation step: perm");
+  BUF_TRY(loss_sums_dev, 2 * sizeof(float), "distillation step: loss_sums");
+  const int tiles = (mb + TILE - 1) / TILE;
+  const int stride = learn_stride(p);
+  if (int rc = learn_workspace(p, tiles, stride)) return rc;
+  const LdsLayout L = make_lds_layout(p->lay);
+  // The kernel's staging loads are unconditional (no control flow before its first barrier), so an absent buffer gets a stand-in
+  // address that is readable and long enough - the teacher's means for its values [N <= N A], the student's own logstd for the
+  // teacher's [A] - and a flag / the kind keeps what is read there out of every result.
+  LearnArgsD a{};
+  static_cast<LearnArgs &>(a) = LearnArgs{theta_dev, obs_dev, tmean_dev, nullptr, nullptr, nullptr, tvalue_dev ? tvalue_dev : tmean_dev,
+                                          reinterpret_cast<const long long *>(perm_dev), nullptr, p->grad_partial, first, mb, stride,
+                                          0.f, vf_coef, p->lay};
+  a.teacher_logstd = tlogstd_dev ? tlogstd_dev : theta_dev + p->lay.logstd;
+  a.kind = kind;
+  a.has_value = tvalue_dev != nullptr;
+  hipLaunchKernelGGL((learn_grad_kernel<false, LOSS_DISTILL>), dim3(tiles, 2), dim3(256), (size_t)L.total * sizeof(float), (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return launch_reduce(p, theta_dev, grad_dev, m_dev, v_dev, loss_sums_dev, tiles, stride, mb, 0.f, lr, beta1, beta2, eps, max_grad_norm,
+                       grad_scale, advance, stream, out_args, out_groups);
+}
+
+int trex_policy_distill_minibatch_step(TrexPolicy *p, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev, const float *obs_dev,
+                                       const float *teacher_mean_dev, const float *teacher_value_dev, const float *teacher_logstd_dev,
+                                       int64_t num_samples, const int64_t *perm_dev, int first, int mb, int kind, float vf_coef, float lr,
+                                       float beta1, float beta2, float eps, float max_grad_norm, float *loss_sums_dev, void *stream) {
+  if (!p || !m_dev || !v_dev) return trex_fail(TREX_E_INVALID, "trex_policy_distill_minibatch_step: null argument");
+  TrexDeviceGuard guard(p->device);
+  ApplyArgs b{};
+  int groups = 0;
+  if (int rc = launch_distill_grad(p, "trex_policy_distill_minibatch_step", theta_dev, grad_dev, m_dev, v_dev, obs_dev, teacher_mean_dev,
+                                   teacher_value_dev, teacher_logstd_dev, num_samples, perm_dev, first, mb, kind, vf_coef, lr, beta1, beta2,
+                                   eps, max_grad_norm, 1.0f, 1, loss_sums_dev, stream, &b, &groups))
+    return rc;
+  hipLaunchKernelGGL(learn_adam_kernel, dim3(((p->lay.count >> 2) + 255) / 256), dim3(256), 0, (hipStream_t)stream, b, groups);
+  HIP_TRY(hipGetLastError());
+  return TREX_OK;
+}
+
+int trex_policy_distill_minibatch_grad(TrexPolicy *p, const float *theta_dev, float *grad_dev, const float *obs_dev,
+                                       const float *teacher_mean_dev, const float *teacher_value_dev, const float *teacher_logstd_dev,
+                                       int64_t num_samples, const int64_t *perm_dev, int first, int mb, int kind, float vf_coef,
+                                       float grad_scale, float *loss_sums_dev, void *stream) {
+  if (!p) return trex_fail(TREX_E_INVALID, "trex_policy_distill_minibatch_grad: null argument");
+  TrexDeviceGuard guard(p->device);
+  return launch_distill_grad(p, "trex_policy_distill_minibatch_grad", const_cast<float *>(theta_dev), grad_dev, nullptr, nullptr, obs_dev,
+                             teacher_mean_dev, teacher_value_dev, teacher_logstd_dev, num_samples, perm_dev, first, mb, kind, vf_coef, 0.f,
+                             0.9f, 0.999f, 1e-5f, 0.f, grad_scale, 0, loss_sums_dev, stream, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -183,11 +183,21 @@ PRESETS = {
 
 
 def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, log=print, use_graphs=False,
-          preset="throughput"):
+          preset="throughput", distill=None):
+    """distill: dict(teacher=PATH, rows="clean" | "critic" | "rows", loss="kl" | "mse", beta=, decay=) - the student of
+    trex_gym.distill.Distill is trained onto that teacher instead of PPO on the reward (the preset's nminibatches, noptepochs and lr
+    hold); the checkpoint is an ordinary one and records the teacher's path and row choice."""
     hp = dict(PRESETS[preset])
     if noptepochs is not None:
         hp["noptepochs"] = noptepochs
-    agent = PPO(env, nsteps=nsteps, seed=seed, use_graphs=use_graphs, critic=getattr(env, "critic_config", None) is not None, **hp)
+    if distill is not None:
+        from .distill import Distill, Teacher
+        teacher = Teacher(env, distill["teacher"], rows=distill.get("rows", "clean"))
+        agent = Distill(env, teacher, nsteps=nsteps, nminibatches=hp["nminibatches"], noptepochs=hp["noptepochs"], lr=hp["lr"],
+                        loss=distill.get("loss", "kl"), beta=float(distill.get("beta", 1.0)), beta_decay=float(distill.get("decay", 0.9)),
+                        seed=seed, use_graphs=use_graphs)
+    else:
+        agent = PPO(env, nsteps=nsteps, seed=seed, use_graphs=use_graphs, critic=getattr(env, "critic_config", None) is not None, **hp)
     log("Number of actions: %d; number of joints: %d; model mass: %.2f; nsteps %d x %d envs; preset %s, noptepochs %d"
         % (env.action_space.shape[0], env.model.num_joints, env.model.total_mass(False), nsteps, env.num_envs, preset,
            hp["noptepochs"]))
@@ -200,7 +210,9 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
                     "observations": _own_channels(env), "rewards": getattr(env, "rewards", None),
                     "command": getattr(env, "command", None), "motion": getattr(env, "motion_config", None),
                     "sensing": getattr(env, "sensing_config", None), "randomize": getattr(env, "randomize_config", None),
-                    "monitor": getattr(env, "monitor_config", None), "critic": critic_checkpoint(agent)},
+                    "monitor": getattr(env, "monitor_config", None), "critic": critic_checkpoint(agent),
+                    "distill": None if distill is None else dict(teacher=str(distill["teacher"]), rows=str(distill.get("rows", "clean")),
+                                                                 loss=str(distill.get("loss", "kl")))},
                    save_path)   # (the channels, the terms, the clip and the sensor model: --play rebuilds the same row)
     return agent, hist
 
@@ -391,7 +403,23 @@ def parse_args(argv=None):
                     help="asymmetric actor-critic: the value net reads a row of its own - the observation before the sensor model "
                          "(clean), plus friction, push force, mass scale and foot contact forces where the env has them (privileged) - "
                          "during training only (trex_gym.critic)")
+    ap.add_argument("--distill", type=str, default=None, metavar="TEACHER.ckpt",
+                    help="policy distillation: regress the student, which reads the env's (sensor) row, onto this trained teacher "
+                         "instead of running PPO on the reward (trex_gym.distill)")
+    ap.add_argument("--teacher_rows", choices=["clean", "critic", "rows"], default="clean",
+                    help="with --distill: what the teacher reads - the row before the sensor model, the critic row (--critic), the env's row")
+    ap.add_argument("--distill_loss", choices=["kl", "mse"], default="kl",
+                    help="with --distill: KL(teacher || student) of the action distributions, or half the squared error of the means")
+    ap.add_argument("--dagger_beta", type=float, nargs="+", default=None, metavar=("B", "DECAY"),
+                    help="with --distill: the probability B that an env follows the teacher during a rollout (default 1), "
+                         "multiplied by DECAY (default 0.9) after every rollout")
     args = ap.parse_args(argv)
+    if args.distill is None and (args.teacher_rows != "clean" or args.distill_loss != "kl" or args.dagger_beta is not None):
+        ap.error("--teacher_rows, --distill_loss and --dagger_beta need --distill")
+    if args.dagger_beta is not None and (len(args.dagger_beta) > 2 or not all(0.0 <= x <= 1.0 for x in args.dagger_beta)):
+        ap.error("--dagger_beta: B [DECAY], both in [0, 1]")
+    if args.distill is not None and args.teacher_rows == "critic" and args.critic is None:
+        ap.error("--teacher_rows critic needs --critic (the row the teacher reads)")
     if args.variable_stiffness:
         try:
             check_action_space(args.control_mode, True)
@@ -457,6 +485,14 @@ def randomize_args(args):
                 command_interval=args.command_interval)
 
 
+def distill_args(args):
+    """the dict for train(distill=...) of the --distill, --teacher_rows, --distill_loss and --dagger_beta flags, None without --distill"""
+    if args.distill is None:
+        return None
+    b = list(args.dagger_beta or []) + [1.0, 0.9][len(args.dagger_beta or []):]
+    return dict(teacher=args.distill, rows=args.teacher_rows, loss=args.distill_loss, beta=b[0], decay=b[1])
+
+
 def termination_args(args):
     """the dict for TrexVecEnv(terminate=...) of the --terminate_* flags, None when none is given"""
     contact = [l for l in (args.terminate_contact or "").split(",") if l]
@@ -487,7 +523,7 @@ def main(argv=None):
     args = parse_args(argv)
     env = environment_from_args(args)
     agent, _ = train(env, args.num_timesteps, args.random_seed, args.nsteps, args.noptepochs, args.save, use_graphs=args.graphs,
-                     preset=args.preset)
+                     preset=args.preset, distill=distill_args(args))
     if args.play:
         if env.critic_rows is not None:         # (playing runs the policy alone: the critic row is no longer filled)
             from . import critic as critics

@@ -209,8 +209,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         the step call, the reward compose and the motion step read the step's own rows - columns 3J and 3J + 1 - and the two
         blocks as they are at that call: the trainer points them at its rollout buffers, so they are arguments, not settings.
         reset_tensor(mask) abandons the running episode of the envs it resets. `monitor_api` is the batch's calls
-        (monitor_capi.BatchMonitor), `monitor` the recorded settings: dict(window=, terms=). The env offset is `env_lo`. window
-        None or 0 clears the batch's monitor and takes all of this off the env again. Never called, or cleared: nothing changes -
+        (monitor_capi.BatchMonitor), `monitor` the recorded settings: dict(window=, terms=). The env offset is `env_lo`. The term
+        columns are sized here, from the blocks the env has: attach the monitor BEHIND rewards and motion - attaching either behind
+        a monitor with terms is a ValueError (take the monitor off first). window None or 0 clears the batch's monitor and takes all of this off the env again. Never called, or cleared: nothing changes -
         not a launch, not a byte."""
         from . import monitor_capi
         if not window:
@@ -227,7 +228,11 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
 
     # ---- observation channels (trex_batch_set_observation / trex_batch_compose_rows; trex_gym.observations builds specifications)
     def _set_observations(self, spec):
+        """The channels are the constructor's (observations=). ValueError behind trex_gym.sensing.attach: the groups and the clean
+        block of a sensor model are sized for the row it found - attach sensing after the row has its final width."""
         from . import observations as O
+        if self.sense_api is not None:
+            raise ValueError("observations: the env has a sensor model (trex_gym.sensing.attach), set for the row as it was - attach sensing behind the channels")
         J, n = self.J, self.num_envs
         chans, extra, contact, ext_cols = O.resolve(spec, self._links.index, self.A)
         if len(chans) > O.MAX_CHANNELS or 3 * J + extra > O.MAX_DIM:
@@ -254,7 +259,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
 
     # ---- reward terms (trex_batch_set_reward / trex_batch_compose_reward; trex_gym.rewards builds specifications)
     def _set_rewards(self, spec):
+        """The reward terms are the constructor's (rewards=). ValueError behind a monitor that sums terms: see _set_monitor."""
         from . import reward_capi, rewards as R
+        self._refuse_late_terms("rewards")
         L = self._links
         names = list(self.model.joint_names)
         terms, contact, _, self._rew_actions = R.resolve(spec, L.index, lambda j: names.index(j) if isinstance(j, str) else int(j),
@@ -266,6 +273,11 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self.rewards, self.reward_names = R.as_tuples(spec), R.names(spec)
         self.reward_terms = torch.zeros(self.num_envs, len(terms), device=self.device)
         self.commands = torch.zeros(self.num_envs, 3, device=self.device)
+
+    def _refuse_late_terms(self, what):
+        if self.monitor is not None and self.monitor["terms"]:
+            raise ValueError("%s: the env has a monitor (trex_gym.monitor.attach) whose term columns were sized without them - "
+                             "attach the monitor behind rewards and motion" % what)
 
     def _compose_reward(self, rows, actions):
         self.reward_api.compose_reward(rows, actions if self._rew_actions else None, self.commands, self.reward_terms)
@@ -280,14 +292,15 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         rsi: an env whose episode ends starts the next one at an instant of the clip drawn uniformly in [0, T) by a generator
         of the env's own seeded with `seed` - one more launch per step (trex_batch_motion_reset), before the channels are
         composed. `motion` then is the Clip, `motion_api` the batch's calls (motion_capi.BatchMotion), `motion_terms` [n, T] the
-        weighted value of every term at the last step, `motion_names` their names. clip None clears the batch's clip and takes
-        all of this off the env again. Never called, or cleared: nothing changes - not a launch, not a byte."""
+        weighted value of every term at the last step, `motion_names` their names. ValueError behind a monitor that sums terms
+        (_set_monitor). clip None clears the batch's clip and takes all of this off the env again. Never called, or cleared: nothing changes - not a launch, not a byte."""
         from . import motion as M, motion_capi
         if clip is None:
             if self.motion_api is not None:
                 self.motion_api.set_motion(None)
             self.motion, self.motion_api, self.motion_terms, self.motion_names, self._rsi = None, None, None, [], False
             return
+        self._refuse_late_terms("motion")
         if isinstance(clip, str):
             clip = M.Clip.load(clip)
         if clip.num_joints != self.J:
@@ -414,7 +427,21 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
 
     def step_tensor(self, actions):
         """actions [n, J] f32 on device -> (obs [n,3J], reward [n], done [n] bool). Views into buffers
-        that the next call overwrites."""
+        that the next call overwrites.
+
+        The launch order, each launch only where its feature is attached (tests/test_gpu_pipeline.py pins it; the same with and
+        without channels, where the step's block is the clean block itself): (1) the action delay - the motors get the action of
+        some steps ago, `done` still holding the flags of the step before; (2) the step call on the delayed action: step, fall
+        predicate, reset of the envs that fell or reached the limit - done = 1, the reward of the finished step, the observation
+        of the new episode, the last one of a fallen env in terminal_obs, which no later launch touches; (3) the reward terms,
+        on the POLICY's action and the commands as they are, into the reward column; (4) the motion terms added to that column,
+        then RSI, which writes the state of the envs whose episode ended; (5) the randomisation, which redraws for those envs -
+        commands included: the finished step was rewarded against the old command, the row of the new episode shows the new one;
+        (6) the monitor, on the reward column as (3) and (4) left it, the done column and the two term blocks; (7) the joint
+        sensor, at the state (4) left; (8) the channels' compose into the clean block, with the policy's action for prev_action
+        and the commands of (5); (9) the sensor model, from the clean block - channel and command columns included - into `rows`;
+        (10) the critic's row, whose clean source is the clean block. reset_tensor runs (4)'s reset, (5), (7) - (10) in that order,
+        then starts the reward history and the monitor's episode of the envs it reset afresh."""
         actions = self._dev(actions)
         if tuple(actions.shape) != (self.num_envs, self.A):
             raise ValueError("actions must have shape (%d, %d), got %s" % (self.num_envs, self.A, tuple(actions.shape)))
@@ -429,10 +456,6 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
             self._point_at(1 - self._row_k)
         # (with set_termination the call is three launches: step, fall predicate, reset of the fallen - done = 1, the reward of
         # the finished step less the penalty, observation of the new episode)
-        # (reward terms: one more launch behind the step call, on the rows it wrote - before the channels' compose, which carries
-        # the composed reward along in the tail)
-        # (sensing: the motors get the action of some steps ago - `done` still holds the flags of the step before -, the launches
-        # below compose the clean block, and one more launch behind them writes the sensors' view into `rows`)
         applied = actions
         if self._delayed_actions is not None:
             self.sense_api.delay_actions(actions, self._delayed_actions, self.done)
@@ -448,24 +471,24 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
                 self.random_api.apply(out, self.commands, 3 * self.J + 1)
             if self.monitor_api is not None:
                 self.monitor_api.apply(out, out, None, self.reward_terms, self.motion_terms, 3 * self.J, 3 * self.J + 1)
-            if self._joint_fill is not None:      # the joint sensor: behind the last launch that writes the state
+            if self._joint_fill is not None:
                 self._joint_fill(out)
-        else:   # (observation channels: one more launch, after the resets of the step call - the row of the new episode's state)
+        else:   # (observation channels: the step keeps a block of its own, and (8) composes the env's)
             self.batch.step_rows(applied, self._step_rows, self._penalties, done=self.done)
             if self.rewards is not None:
                 self._compose_reward(self._step_rows, actions)
-            if self.motion is not None:           # (before the channels' compose, which then sees the state RSI wrote)
+            if self.motion is not None:
                 self._motion_step(self._step_rows)
-            if self.random_api is not None:       # (the done column of the step's rows; the compose then shows the new command)
+            if self.random_api is not None:
                 self.random_api.apply(self._step_rows, self.commands, 3 * self.J + 1)
-            if self.monitor_api is not None:      # (the reward and done columns of the step's rows: what the compose carries along)
+            if self.monitor_api is not None:
                 self.monitor_api.apply(self._step_rows, self._step_rows, None, self.reward_terms, self.motion_terms, 3 * self.J, 3 * self.J + 1)
-            if self._joint_fill is not None:      # the joint sensor: before the channels' compose, whose external columns may read it
+            if self._joint_fill is not None:
                 self._joint_fill(self._step_rows)
             self._compose(actions, out)
-        if self._clean_block is not None:       # behind the last compose: the sensors' view into the block the policy reads
+        if self._clean_block is not None:
             self.sense_api.apply(out, self.rows)
-        if self._critic_fill is not None:       # behind the sensing launch: the critic's row of this step
+        if self._critic_fill is not None:
             self._critic_fill()
         if self._term_on and self.gains is not None:   # the envs that fell start their episode with new motor gains
             self.set_motor_gains(**self.gains.draw(self.termination_reason != 0))

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Is the device code of the step kernels the same in two source trees?  No GPU needed.
 
-    python scripts/compare_step_kernels.py --parent REV [--out profiles/NAME.txt] [--keep DIR] [--expect-different NAME]...
+    python scripts/compare_step_kernels.py --parent REV [--units A,B] [--out profiles/NAME.txt] [--keep DIR] [--expect-different NAME]...
 
 Compiles the kernel units of git revision REV and of the working tree - trex_step.hip, trex_step_act.hip, dynamics.hip and
-batch_util.hip, those a side has - to gfx950 assembly with the Makefile's flags (hipcc --cuda-device-only -S), as the product build and as the stamped build (-DTREX_STAMPS=1), and
+batch_util.hip, those a side has, or the units named with --units (the trainer's: --units policy_step,ppo_learner) - to gfx950 assembly with the Makefile's flags (hipcc --cuda-device-only -S), as the product build and as the stamped build (-DTREX_STAMPS=1), and
 pairs every kernel of one side with its counterpart of the other: a step kernel by WHAT it is - (form, WARM, EXT, SENS,
 ACT), read off its demangled name under either naming, the wrapper families `trex_step{,_pair,_many}{,_warm,_ext,_sens,
 _act}_kernel` / `trex_reset_sens_kernel` or the one template `trex_step_variant_kernel<FORM, WARM, EXT, SENS, ACT>` -, a
@@ -14,7 +14,8 @@ its .amdhsa_* descriptor block are the same lines, after the kernel's own symbol
 labels (.LBB<n>_, .Lfunc_end<n>) are normalised and the directives that place a kernel in a section are left out. Exit
 status 0 only if every kernel has a partner, every pair is identical - but for the utility kernels named with --expect-different,
 which are listed with their figures on both sides and must not use scratch - and no kernel of the product build has a private
-segment (scratch; the stamped diagnostic build has some, on both sides alike)."""
+segment (scratch; the stamped diagnostic build has some, on both sides alike). With --units only the product build is compared
+(TREX_STAMPS is the step kernels' switch) and scratch is listed, not judged: identical is the whole question there."""
 import argparse
 import concurrent.futures
 import os
@@ -86,12 +87,12 @@ def kernels(asm_path):
     return out
 
 
-def compile_tree(csrc, dest):
+def compile_tree(csrc, dest, units, builds):
     jobs = []
-    for unit in UNITS:
+    for unit in units:
         if not os.path.exists(os.path.join(csrc, unit + ".hip")):
             continue
-        for tag, extra in BUILDS:
+        for tag, extra in builds:
             out = os.path.join(dest, "%s.%s.s" % (unit, tag))
             jobs.append((out, [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + FLAGS + extra + ["-o", out, unit + ".hip"]))
     with concurrent.futures.ThreadPoolExecutor(len(jobs)) as ex:
@@ -111,7 +112,10 @@ def main():
     ap.add_argument("--keep", help="directory for the assembly files (kept; files already there are reused)")
     ap.add_argument("--expect-different", action="append", default=[], metavar="NAME",
                     help="a utility kernel that is rewritten on purpose: DIFFERENT is accepted for it, scratch is not (repeatable)")
+    ap.add_argument("--units", help="comma-separated kernel units to compare instead of %s" % ",".join(UNITS))
     a = ap.parse_args()
+    units = a.units.split(",") if a.units else UNITS
+    builds = BUILDS[:1] if a.units else BUILDS
     work = a.keep or tempfile.mkdtemp(prefix="step_kernels_")
     sides = {}
     for side in ("parent", "tree"):
@@ -120,18 +124,18 @@ def main():
             os.makedirs(dest)
             csrc = os.path.join(ROOT, CSRC)
             if side == "parent":
-                tar = subprocess.run(["git", "-C", ROOT, "archive", a.parent, CSRC], capture_output=True, check=True).stdout
+                tar = subprocess.run(["git", "-C", ROOT, "archive", a.parent, CSRC, "include"], capture_output=True, check=True).stdout
                 subprocess.run(["tar", "-x", "-C", dest], input=tar, check=True)
                 csrc = os.path.join(dest, CSRC)
-            compile_tree(csrc, dest)
+            compile_tree(csrc, dest, units, builds)
         sides[side] = dest
     rev = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", a.parent], capture_output=True, text=True, check=True).stdout.strip()
-    rep = ["step kernels of the working tree against %s: device assembly, kernel by kernel (scripts/compare_step_kernels.py)" % rev,
+    rep = ["kernels of %s: the working tree against %s: device assembly, kernel by kernel (scripts/compare_step_kernels.py)" % (", ".join(u + ".hip" for u in units), rev),
            "hipcc " + " ".join(FLAGS), ""]
     bad = 0
-    for tag, extra in BUILDS:
+    for tag, extra in builds:
         old, new = {}, {}
-        for unit in UNITS:
+        for unit in units:
             for side, dst in (("parent", old), ("tree", new)):
                 asm = os.path.join(sides[side], "%s.%s.s" % (unit, tag))
                 if not os.path.exists(asm):
@@ -157,7 +161,7 @@ def main():
             x = n or o
             scratch_free = all(y["scratch"] == 0 and y["private"] == 0 for y in (o, n) if y)
             expected = res == "DIFFERENT" and k in a.expect_different
-            bad += (res != "identical" and not expected) or ((tag == "product" or expected) and not scratch_free)
+            bad += (res != "identical" and not expected) or ((tag == "product" or expected) and not scratch_free and not a.units)
             unit = x["unit"] if not o or not n or o["unit"] == n["unit"] else "%s -> %s" % (o["unit"], n["unit"])
             line = "%-34s %-10s %5d %5d %8d %7d  %-26s %s -> %s" % (label(k), res, x["vgprs"], x["sgprs"], max(x["scratch"], x["private"]),
                                                                   x["lds"], unit, o["name"].split("(")[0] if o else "-", n["name"].split("(")[0] if n else "-")
@@ -166,8 +170,9 @@ def main():
                                                                                  "; expected (--expect-different)" if expected else "")
             rep.append(line)
         rep.append("")
-    rep.append("RESULT: %s" % ("every pair identical%s, no kernel of the product build with a private segment" % (
-        " but the expected %s" % ", ".join(a.expect_different) if a.expect_different else "") if not bad else "%d kernel(s) differ, lack a partner or use scratch" % bad))
+    rep.append("RESULT: %s" % ("every pair identical%s%s" % (
+        " but the expected %s" % ", ".join(a.expect_different) if a.expect_different else "",
+        "" if a.units else ", no kernel of the product build with a private segment") if not bad else "%d kernel(s) differ, lack a partner or use scratch" % bad))
     text = "\n".join(rep) + "\n"
     sys.stdout.write(text)
     if a.out:

@@ -386,6 +386,131 @@ def test_refusals_by_name_with_nothing_launched():
         k.close()
 
 
+# ================================================================ the object's lifetime
+def _lifetime_inputs(n, D, A, widths, seed=11):
+    """finite inputs of a rollout of one step: bitwise comparisons only, so any numbers do"""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    r = lambda *shape: torch.randn(*shape, generator=g).to(DEV)
+    t = dict(rows=r(n, D + 2), noise=r(n, A), obs=r(n, D), act=r(n, A), logp=r(n) - 3.0, val=r(n), adv=r(n), ret=r(n),
+             tmean=r(n, A), tvalue=r(n), tlogstd=0.1 * r(A), perm=torch.randperm(n, generator=g).to(DEV),
+             stats=torch.tensor([0.1, 0.9], device=DEV))
+    for Dv in widths:
+        t["rows_v%d" % Dv], t["obs_v%d" % Dv] = r(n, Dv + 3), r(n, Dv)
+    return t
+
+
+def test_one_object_through_its_lifetime_is_a_fresh_object_at_every_stage():
+    """What the object owns - the moments of both blocks, the learner workspace, which trex_policy_set_critic drops because its
+    row is as long as the parameter vector - through a life of one policy object: a plain minibatch step; a critic of width 5
+    (observe, act, step); a critic of width 17 (the workspace goes, the moments start afresh; the same three calls); no critic
+    again (a plain step, a distillation step). After every stage theta, m, v, the gradient, the loss sums, what the act wrote and
+    the critic's moments are BITWISE those of the same calls on a freshly created object (the Adam step count of the long-lived
+    one reset, as trex_policy_adam_reset does). n = 33: two tiles, the second ragged; mb = 33.
+
+    Then 8 objects live and die, each through a critic and a 4096-sample step (a workspace of 5 MB: larger than the granule), and
+    the device's free memory is where it started, to within one allocation granule (2 MiB, the fragment the driver maps device
+    memory in; what an object of this size holds besides its workspace is below that resolution). Measured on an MI355X, with the
+    parent's library and with this one: +0 bytes after the 8 objects - and +0 while one of them lives (the figure is printed), so
+    the runtime serves allocations of this size from memory it already holds, and the check catches a leak only once it outgrows
+    that; the bitwise stages above are what pins the ownership paths."""
+    K, CC = _capi()
+    from trex_gym import distill_capi
+    n, D, A, mb = 33, 9, 3, 33
+    t = _lifetime_inputs(n, D, A, (5, 17))
+    kw = dict(cliprange=tc.CLIPRANGE, ent_coef=0.01, vf_coef=tc.VF_COEF, lr=LR, eps=EPS, max_grad_norm=MAXN)
+    dkw = dict(loss="kl", vf_coef=tc.VF_COEF, lr=LR, eps=EPS, max_grad_norm=MAXN)
+    def theta_for(count):
+        return (0.1 * torch.randn(count, generator=torch.Generator(device="cpu").manual_seed(count))).to(DEV)
+
+    def plain_step(kern):
+        return Run(kern.param_count, theta_for(kern.param_count), lambda r: kern.minibatch_step(
+            r.theta, r.grad, r.m, r.v, t["obs"], t["act"], t["logp"], t["val"], t["adv"], t["ret"], t["perm"], 0, mb, t["stats"],
+            loss_sums=r.sums, **kw))
+
+    def distill_step(kern):
+        return Run(kern.param_count, theta_for(kern.param_count), lambda r: distill_capi.PolicyDistill(kern).minibatch_step(
+            r.theta, r.grad, r.m, r.v, t["obs"], t["tmean"], t["tvalue"], t["tlogstd"], t["perm"], 0, mb, loss_sums=r.sums, **dkw))
+
+    def critic_stage(kern, crit, Dv):
+        """set, observe, act, step -> (the step's Run, the act's outputs, the moments)"""
+        assert crit.set(Dv) == Dv
+        rows_v, obs_v = t["rows_v%d" % Dv], t["obs_v%d" % Dv]
+        crit.observe(rows_v)
+        theta = theta_for(crit.param_count)
+        act = ActRun(crit, theta, t["rows"], rows_v, t["noise"], n, D, Dv, A)
+        run = Run(crit.param_count, theta, lambda r: crit.minibatch_step(
+            r.theta, r.grad, r.m, r.v, t["obs"], obs_v, t["act"], t["logp"], t["val"], t["adv"], t["ret"], t["perm"], 0, mb, t["stats"],
+            loss_sums=r.sums, **kw))
+        return run, [f for f, _ in act.fulls], crit.get_stats()
+
+    def fresh():
+        kern = K.Policy(n, D, A, 64, 0)
+        return kern, CC.PolicyCritic(kern)
+
+    def same_stage(a, b):
+        return a[0].same_as(b[0]) and all(torch.equal(x, y) for x, y in zip(a[1], b[1])) and \
+            all(np.array_equal(np.asarray(a[2][k]), np.asarray(b[2][k])) for k in a[2])
+
+    old, old_crit = fresh()
+    # 1: a plain step
+    w, _ = fresh()
+    first = plain_step(old)
+    assert first.same_as(plain_step(w)) and float((first.theta - first.theta0).abs().max()) > 0.1 * LR
+    w.close()
+    # 2, 3: a critic, then a wider one
+    for Dv in (5, 17):
+        old.adam_reset()
+        got = critic_stage(old, old_crit, Dv)
+        w, w_crit = fresh()
+        want = critic_stage(w, w_crit, Dv)
+        assert same_stage(got, want), Dv
+        assert got[2]["count"] == 1e-4 + n and float((got[0].theta - got[0].theta0).abs().max()) > 0.1 * LR
+        w.close()
+    # 4: no critic again
+    assert old_crit.set(0) == 0 and old_crit.param_count == old.param_count
+    for step in (plain_step, distill_step):
+        old.adam_reset()
+        w, _ = fresh()
+        got = step(old)
+        assert got.same_as(step(w)) and float((got.theta - got.theta0).abs().max()) > 0.1 * LR, step.__name__
+        w.close()
+    old.adam_reset()
+    assert plain_step(old).same_as(first)
+    old.close()
+
+    # ---- 8 objects live and die
+    N = 4096
+    big = _lifetime_inputs(N, D, A, (5,), seed=12)
+
+    def a_life(alive=None):
+        kern, crit = fresh()
+        crit.set(5)
+        crit.observe(t["rows_v5"])
+        count, plain = crit.param_count, kern.param_count
+        th, gr, m, v = (torch.zeros(max(count, plain), device=DEV) for _ in range(4))
+        crit.minibatch_step(th[:count], gr[:count], m[:count], v[:count], big["obs"], big["obs_v5"], big["act"], big["logp"], big["val"], big["adv"], big["ret"], big["perm"],
+                            0, N, big["stats"], **kw)
+        crit.set(0)
+        kern.minibatch_step(th[:plain], gr[:plain], m[:plain], v[:plain], t["obs"], t["act"],
+                            t["logp"], t["val"], t["adv"], t["ret"], t["perm"], 0, mb, t["stats"], **kw)
+        torch.cuda.synchronize()
+        if alive is not None:
+            alive.append(torch.cuda.mem_get_info()[0])
+        kern.close()
+
+    a_life()                                   # (what the runtime allocates on a first use is not the object's)
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    alive = []
+    for _ in range(8):
+        a_life(alive)
+    torch.cuda.synchronize()
+    free1 = torch.cuda.mem_get_info()[0]
+    print("free device memory before and after 8 objects: %d -> %d bytes (%+d); while one lives: %+d" % (
+        free0, free1, free1 - free0, min(alive) - free0))
+    assert free0 - free1 <= 2 << 20
+
+
 # ================================================================ capture
 def test_act_and_observe_replay_from_a_graph():
     """act with a critic passes gpu_support.replay_equals_eager (the rows change between capture and replay); the critic observe

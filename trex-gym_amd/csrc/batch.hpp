@@ -1,4 +1,5 @@
-// What capi.cpp and capi_queries.cpp share: the two handles of include/trex_batch.h, the owner of device memory, the error plumbing.
+// What capi.cpp and capi_queries.cpp share: the two handles of include/trex_batch.h (the owner of device memory and the error
+// plumbing: internal.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,38 +15,6 @@
 #include "randomize.h"
 
 using DeviceGuard = TrexDeviceGuard;
-
-// One device allocation and its owner: move-only, freed by the destructor under the device it was made on. Every allocation a batch
-// owns is a DeviceBuf member of the batch (or an element of `state`), so that an error path frees by returning.
-struct DeviceBuf {
-  void *p = nullptr;
-  size_t bytes = 0;
-  int device = 0;
-  DeviceBuf() = default;
-  DeviceBuf(DeviceBuf &&o) noexcept : p(o.p), bytes(o.bytes), device(o.device) { o.p = nullptr; o.bytes = 0; }
-  DeviceBuf &operator=(DeviceBuf &&o) noexcept {   // frees what it held
-    if (this != &o) { release(); p = o.p; bytes = o.bytes; device = o.device; o.p = nullptr; o.bytes = 0; }
-    return *this;
-  }
-  ~DeviceBuf() { release(); }
-  void release() {
-    if (!p) return;
-    DeviceGuard guard(device);
-    (void)hipFree(p);
-    p = nullptr; bytes = 0;
-  }
-  // `n` bytes on the CURRENT device (the caller holds a DeviceGuard), zeroed if asked; frees what it held first
-  hipError_t alloc(size_t n, bool zero) {
-    release();
-    hipError_t e = hipGetDevice(&device);
-    if (e == hipSuccess) e = hipMalloc(&p, n);
-    if (e != hipSuccess) { p = nullptr; return e; }
-    bytes = n;
-    return zero ? hipMemset(p, 0, n) : hipSuccess;
-  }
-  template <class T> T *as() const { return (T *)p; }
-  explicit operator bool() const { return p != nullptr; }
-};
 
 struct TrexModel {
   trex::HostModel host;
@@ -176,36 +145,10 @@ struct TrexBatch {
   std::vector<TrexSeen> seen;
 };
 
-inline int fail(int code, const std::string &msg) { return trex_fail(code, msg); }
-inline int hip_fail(hipError_t e, const char *what) { return fail(TREX_E_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-#define HIP_TRY(expr)                                  \
-  do {                                                 \
-    hipError_t _e = (expr);                            \
-    if (_e != hipSuccess) return hip_fail(_e, #expr);  \
-  } while (0)
-// a caller's buffer `p` of the batch `b` in scope (trex_check_device_buffer)
-#define BUF_TRY(p, bytes, what)                                                                                  \
-  do {                                                                                                           \
-    if (int _c = trex_check_device_buffer(b->device, b->seen, (p), (size_t)(bytes), (what))) return _c;          \
-  } while (0)
-
 // the gains buffer of a batch whose actuator model is about to be used: allocated on first use, holding the model parameters (capi.cpp)
 int ensure_gains(TrexBatch *b);
 
 inline int check_batch(const TrexBatch *b) { return b ? TREX_OK : fail(TREX_E_INVALID, "null batch"); }
-
-// runs a table builder, a layout or a check of host_tables.cpp: its refusal - message and code - becomes the call's
-template <class F> int built(F &&build) {
-  try {
-    build();
-    return TREX_OK;
-  } catch (const trex::Refusal &r) {
-    return fail(r.code, r.what());
-  }
-}
-
-// the member at byte `offset` of a state allocation, as a layout of host_tables.cpp places it
-template <class T> T *member_at(const DeviceBuf &buf, size_t offset) { return (T *)(buf.as<char>() + offset); }
 
 // URDF link 0's frame in its body, into the launch arguments that carry it; returns the body's bit of a body mask
 template <class A> uint32_t fill_base(const TrexBatch *b, A &a) {

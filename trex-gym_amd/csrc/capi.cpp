@@ -392,8 +392,8 @@ int trex_batch_reset(TrexBatch *b, const uint8_t *mask_dev, float *obs_out_dev, 
   if (check_batch(b)) return TREX_E_INVALID;
   DeviceGuard guard(b->device);
   const size_t n = (size_t)b->n;
-  BUF_TRY(mask_dev, n, "trex_batch_reset: mask");
-  BUF_TRY(obs_out_dev, n * 3 * b->nj * sizeof(float), "trex_batch_reset: obs_out");
+  BUF_TRY(b, mask_dev, n, "trex_batch_reset: mask");
+  BUF_TRY(b, obs_out_dev, n * 3 * b->nj * sizeof(float), "trex_batch_reset: obs_out");
   TrexStepArgs a = step_args(b, TREX_KIND_RESET);
   a.reset_mask = mask_dev; a.obs = obs_out_dev;
   HIP_TRY(trex_launch_step(&a, TREX_KIND_RESET, (hipStream_t)stream));
@@ -407,8 +407,8 @@ int trex_batch_reset_rows(TrexBatch *b, const uint8_t *mask_dev, float *rows_dev
   if (int c = rows_bytes(b, "trex_batch_reset_rows", row_stride, (size_t)b->n, &rows_need)) return c;
   DeviceGuard guard(b->device);
   const size_t n = (size_t)b->n;
-  BUF_TRY(mask_dev, n, "trex_batch_reset_rows: mask");
-  BUF_TRY(rows_dev, rows_need, "trex_batch_reset_rows: rows");
+  BUF_TRY(b, mask_dev, n, "trex_batch_reset_rows: mask");
+  BUF_TRY(b, rows_dev, rows_need, "trex_batch_reset_rows: rows");
   TrexStepArgs a = step_args(b, TREX_KIND_RESET);
   a.reset_mask = mask_dev;
   rows_out(b, a, rows_dev, row_stride);
@@ -422,11 +422,11 @@ int trex_batch_step(TrexBatch *b, const float *actions_dev, float *obs_dev, floa
   if (!actions_dev) return fail(TREX_E_INVALID, "trex_batch_step: actions is null");
   DeviceGuard guard(b->device);
   const size_t n = (size_t)b->n;
-  BUF_TRY(actions_dev, n * b->action_cols() * sizeof(float), "trex_batch_step: actions");
-  BUF_TRY(obs_dev, n * 3 * b->nj * sizeof(float), "trex_batch_step: obs");
-  BUF_TRY(reward_dev, n * sizeof(float), "trex_batch_step: reward");
-  BUF_TRY(done_dev, n, "trex_batch_step: done");
-  BUF_TRY(penalties_dev, n * 3 * sizeof(float), "trex_batch_step: penalties");
+  BUF_TRY(b, actions_dev, n * b->action_cols() * sizeof(float), "trex_batch_step: actions");
+  BUF_TRY(b, obs_dev, n * 3 * b->nj * sizeof(float), "trex_batch_step: obs");
+  BUF_TRY(b, reward_dev, n * sizeof(float), "trex_batch_step: reward");
+  BUF_TRY(b, done_dev, n, "trex_batch_step: done");
+  BUF_TRY(b, penalties_dev, n * 3 * sizeof(float), "trex_batch_step: penalties");
   TrexStepArgs a = step_args(b, TREX_KIND_STEP);
   a.actions = actions_dev; a.obs = obs_dev; a.reward = reward_dev; a.done = done_dev; a.penalties = penalties_dev;
   if (b->term.on && !a.done) a.done = b->term.done;   // (the predicate has to see which envs the step launch ended)
@@ -443,10 +443,10 @@ int trex_batch_step_rows(TrexBatch *b, const float *actions_dev, float *rows_dev
   if (int c = rows_bytes(b, "trex_batch_step_rows", row_stride, (size_t)b->n, &rows_need)) return c;
   DeviceGuard guard(b->device);
   const size_t n = (size_t)b->n;
-  BUF_TRY(actions_dev, n * b->action_cols() * sizeof(float), "trex_batch_step_rows: actions");
-  BUF_TRY(rows_dev, rows_need, "trex_batch_step_rows: rows");
-  BUF_TRY(penalties_dev, n * 3 * sizeof(float), "trex_batch_step_rows: penalties");
-  BUF_TRY(done_dev, n, "trex_batch_step_rows: done");
+  BUF_TRY(b, actions_dev, n * b->action_cols() * sizeof(float), "trex_batch_step_rows: actions");
+  BUF_TRY(b, rows_dev, rows_need, "trex_batch_step_rows: rows");
+  BUF_TRY(b, penalties_dev, n * 3 * sizeof(float), "trex_batch_step_rows: penalties");
+  BUF_TRY(b, done_dev, n, "trex_batch_step_rows: done");
   TrexStepArgs a = step_args(b, TREX_KIND_STEP);
   a.actions = actions_dev; a.done = done_dev; a.penalties = penalties_dev;
   rows_out(b, a, rows_dev, row_stride);
@@ -464,10 +464,10 @@ int trex_batch_step_many(TrexBatch *b, const float *actions_dev, float *rows_dev
   if (int c = rows_bytes(b, "trex_batch_step_many", row_stride, (size_t)num_steps * b->n, &rows_need)) return c;
   DeviceGuard guard(b->device);
   const size_t n = (size_t)b->n, S = (size_t)num_steps;
-  BUF_TRY(actions_dev, S * n * b->action_cols() * sizeof(float), "trex_batch_step_many: actions");
-  BUF_TRY(rows_dev, rows_need, "trex_batch_step_many: rows");
-  BUF_TRY(penalties_dev, S * n * 3 * sizeof(float), "trex_batch_step_many: penalties");
-  BUF_TRY(done_dev, S * n, "trex_batch_step_many: done");
+  BUF_TRY(b, actions_dev, S * n * b->action_cols() * sizeof(float), "trex_batch_step_many: actions");
+  BUF_TRY(b, rows_dev, rows_need, "trex_batch_step_many: rows");
+  BUF_TRY(b, penalties_dev, S * n * 3 * sizeof(float), "trex_batch_step_many: penalties");
+  BUF_TRY(b, done_dev, S * n, "trex_batch_step_many: done");
   if (b->term.on) {   // S triplets step, predicate, reset from the host: what S trex_batch_step_rows calls enqueue
     for (size_t s = 0; s < S; s++) {
       TrexStepArgs a = step_args(b, TREX_KIND_STEP);
@@ -492,9 +492,9 @@ int trex_batch_debug_step(TrexBatch *b, const float *actions_dev, float *obs_dev
   if (check_batch(b)) return TREX_E_INVALID;
   if (!actions_dev || !debug_dev) return fail(TREX_E_INVALID, "trex_batch_debug_step: null argument");
   DeviceGuard guard(b->device);
-  BUF_TRY(actions_dev, (size_t)b->n * b->nj * sizeof(float), "trex_batch_debug_step: actions");
-  BUF_TRY(obs_dev, (size_t)b->n * 3 * b->nj * sizeof(float), "trex_batch_debug_step: obs");
-  BUF_TRY(debug_dev, 4096 * sizeof(float), "trex_batch_debug_step: debug");   // (diagnostic builds: 4096 + 16 N)
+  BUF_TRY(b, actions_dev, (size_t)b->n * b->nj * sizeof(float), "trex_batch_debug_step: actions");
+  BUF_TRY(b, obs_dev, (size_t)b->n * 3 * b->nj * sizeof(float), "trex_batch_debug_step: obs");
+  BUF_TRY(b, debug_dev, 4096 * sizeof(float), "trex_batch_debug_step: debug");   // (diagnostic builds: 4096 + 16 N)
   if (b->warm)   // (the diagnostics instantiation has no warm-start record: it would step cold without saying so)
     return fail(TREX_E_INVALID, "trex_batch_debug_step: not available for a batch with warmstart > 0");
   if (b->ext_on)   // (nor an external wrench)
@@ -515,7 +515,7 @@ int trex_batch_set_episode_limit(TrexBatch *b, int max_episode_steps, const int3
   if (check_batch(b)) return TREX_E_INVALID;
   if (max_episode_steps < 0) return fail(TREX_E_INVALID, "max_episode_steps must be >= 0 (0 = no limit)");
   DeviceGuard guard(b->device);
-  BUF_TRY(episode_steps_dev, (size_t)b->n * sizeof(int32_t), "trex_batch_set_episode_limit: episode_steps");
+  BUF_TRY(b, episode_steps_dev, (size_t)b->n * sizeof(int32_t), "trex_batch_set_episode_limit: episode_steps");
   b->arr.max_episode_steps = max_episode_steps;
   HIP_TRY(trex_launch_scalars_set(b->arr, b->n, episode_steps_dev, 1, -1, (hipStream_t)stream));
   return TREX_OK;
@@ -524,7 +524,7 @@ int trex_batch_get_episode_steps(TrexBatch *b, int32_t *episode_steps_dev, void 
   if (check_batch(b)) return TREX_E_INVALID;
   if (!episode_steps_dev) return fail(TREX_E_INVALID, "episode_steps is null");
   DeviceGuard guard(b->device);
-  BUF_TRY(episode_steps_dev, (size_t)b->n * sizeof(int32_t), "trex_batch_get_episode_steps: episode_steps");
+  BUF_TRY(b, episode_steps_dev, (size_t)b->n * sizeof(int32_t), "trex_batch_get_episode_steps: episode_steps");
   HIP_TRY(trex_launch_scalars_get(b->arr, b->n, nullptr, nullptr, episode_steps_dev, (hipStream_t)stream));
   return TREX_OK;
 }
@@ -533,7 +533,7 @@ int trex_batch_get_state(TrexBatch *b, float *state_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
   if (!state_dev) return fail(TREX_E_INVALID, "state is null");
   DeviceGuard guard(b->device);
-  BUF_TRY(state_dev, (size_t)b->n * (13 + 2 * b->nj) * sizeof(float), "trex_batch_get_state: state");
+  BUF_TRY(b, state_dev, (size_t)b->n * (13 + 2 * b->nj) * sizeof(float), "trex_batch_get_state: state");
   HIP_TRY(trex_launch_pack_state(b->dmodel, b->arr, b->n, state_dev, 1, (hipStream_t)stream));
   return TREX_OK;
 }
@@ -541,7 +541,7 @@ int trex_batch_set_state(TrexBatch *b, const float *state_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
   if (!state_dev) return fail(TREX_E_INVALID, "state is null");
   DeviceGuard guard(b->device);
-  BUF_TRY(state_dev, (size_t)b->n * (13 + 2 * b->nj) * sizeof(float), "trex_batch_set_state: state");
+  BUF_TRY(b, state_dev, (size_t)b->n * (13 + 2 * b->nj) * sizeof(float), "trex_batch_set_state: state");
   HIP_TRY(trex_launch_pack_state(b->dmodel, b->arr, b->n, const_cast<float *>(state_dev), 0, (hipStream_t)stream));
   if (b->warm)   // the recorded impulses belong to the states just replaced: every record is emptied
     HIP_TRY(hipMemsetAsync(b->warm.p, 0, (size_t)b->n * TREX_WARM_WORDS * sizeof(float), (hipStream_t)stream));
@@ -578,8 +578,8 @@ int trex_model_visual_info(const TrexModel *m, int visual, const char **mesh_fil
 int trex_batch_set_domain(TrexBatch *b, const float *mass_scale_dev, const float *friction_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
   DeviceGuard guard(b->device);
-  BUF_TRY(mass_scale_dev, (size_t)b->n * b->nb * sizeof(float), "trex_batch_set_domain: mass_scale");
-  BUF_TRY(friction_dev, (size_t)b->n * sizeof(float), "trex_batch_set_domain: friction");
+  BUF_TRY(b, mass_scale_dev, (size_t)b->n * b->nb * sizeof(float), "trex_batch_set_domain: mass_scale");
+  BUF_TRY(b, friction_dev, (size_t)b->n * sizeof(float), "trex_batch_set_domain: friction");
   if (mass_scale_dev) HIP_TRY(trex_launch_copy_mass_scale(mass_scale_dev, b->arr.mass_scale, b->n, b->nb, (hipStream_t)stream));
   if (friction_dev) HIP_TRY(hipMemcpyAsync(b->arr.friction, friction_dev, b->n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   if (mass_scale_dev || friction_dev) b->arr.domain = 1;   // from now on the step launches read the per-env arrays
@@ -592,7 +592,7 @@ int trex_batch_set_external_wrench(TrexBatch *b, const float *wrench_dev, void *
   const int pushes = rd.table.pushes;   // PUSH terms of the episode randomisation: the wrench stays on, this call sets its base
   if (!wrench_dev && pushes == 0) { b->ext_on = false; return TREX_OK; }   // the default kernels again; the buffer stays for the next call
   DeviceGuard guard(b->device);
-  BUF_TRY(wrench_dev, (size_t)b->n * b->nb * 6 * sizeof(float), "trex_batch_set_external_wrench: wrench");
+  BUF_TRY(b, wrench_dev, (size_t)b->n * b->nb * 6 * sizeof(float), "trex_batch_set_external_wrench: wrench");
   if (!b->ext)   // first use: a batch that never sets a wrench allocates nothing
     HIP_TRY(b->ext.alloc((size_t)b->n * 6 * TREX_TL * sizeof(float), false));
   if (wrench_dev) HIP_TRY(trex_launch_copy_wrench(wrench_dev, b->ext.as<float>(), b->n, b->nb, (hipStream_t)stream));
@@ -625,9 +625,9 @@ int trex_batch_set_motor_gains(TrexBatch *b, const float *kp_dev, const float *k
   if (check_batch(b)) return TREX_E_INVALID;
   DeviceGuard guard(b->device);
   const size_t bytes = (size_t)b->n * b->nj * sizeof(float);
-  BUF_TRY(kp_dev, bytes, "trex_batch_set_motor_gains: kp");
-  BUF_TRY(kd_dev, bytes, "trex_batch_set_motor_gains: kd");
-  BUF_TRY(max_force_dev, bytes, "trex_batch_set_motor_gains: max_force");
+  BUF_TRY(b, kp_dev, bytes, "trex_batch_set_motor_gains: kp");
+  BUF_TRY(b, kd_dev, bytes, "trex_batch_set_motor_gains: kd");
+  BUF_TRY(b, max_force_dev, bytes, "trex_batch_set_motor_gains: max_force");
   const bool any = kp_dev || kd_dev || max_force_dev;
   if (!any && !b->gains) { b->gains_set = false; return TREX_OK; }   // nothing was ever set: nothing to clear, nothing allocated
   if (int c = ensure_gains(b)) return c;
@@ -679,10 +679,10 @@ int trex_batch_time_steps(TrexBatch *b, const float *actions_dev, float *obs_dev
   if (b->term.on)   // (it times the step launch alone: with termination on a step is three launches)
     return fail(TREX_E_INVALID, "trex_batch_time_steps: not available while termination is on (trex_batch_set_termination)");
   DeviceGuard guard(b->device);
-  BUF_TRY(actions_dev, (size_t)b->n * b->action_cols() * sizeof(float), "trex_batch_time_steps: actions");
-  BUF_TRY(obs_dev, (size_t)b->n * 3 * b->nj * sizeof(float), "trex_batch_time_steps: obs");
-  BUF_TRY(reward_dev, (size_t)b->n * sizeof(float), "trex_batch_time_steps: reward");
-  BUF_TRY(done_dev, (size_t)b->n, "trex_batch_time_steps: done");
+  BUF_TRY(b, actions_dev, (size_t)b->n * b->action_cols() * sizeof(float), "trex_batch_time_steps: actions");
+  BUF_TRY(b, obs_dev, (size_t)b->n * 3 * b->nj * sizeof(float), "trex_batch_time_steps: obs");
+  BUF_TRY(b, reward_dev, (size_t)b->n * sizeof(float), "trex_batch_time_steps: reward");
+  BUF_TRY(b, done_dev, (size_t)b->n, "trex_batch_time_steps: done");
   struct Event {   // (destroyed on every way out)
     hipEvent_t e = nullptr;
     ~Event() { if (e) (void)hipEventDestroy(e); }

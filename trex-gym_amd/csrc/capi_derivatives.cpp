@@ -21,9 +21,9 @@ int trex_batch_inverse_dynamics_derivatives(TrexBatch *b, const float *accel_dev
   if (dfdq_dev && dfdv_dev && trex::ranges_overlap(dfdq_dev, out_bytes, dfdv_dev, out_bytes))
     return fail(TREX_E_INVALID, me + "dfdq overlaps dfdv");
   DeviceGuard guard(b->device);
-  BUF_TRY(accel_dev, row_bytes, "trex_batch_inverse_dynamics_derivatives: accel");
-  BUF_TRY(dfdq_dev, out_bytes, "trex_batch_inverse_dynamics_derivatives: dfdq");
-  BUF_TRY(dfdv_dev, out_bytes, "trex_batch_inverse_dynamics_derivatives: dfdv");
+  BUF_TRY(b, accel_dev, row_bytes, "trex_batch_inverse_dynamics_derivatives: accel");
+  BUF_TRY(b, dfdq_dev, out_bytes, "trex_batch_inverse_dynamics_derivatives: dfdq");
+  BUF_TRY(b, dfdv_dev, out_bytes, "trex_batch_inverse_dynamics_derivatives: dfdv");
   TrexDdArgs a{};
   a.model = b->dmodel; a.base = b->arr.base; a.q = b->arr.q; a.qd = b->arr.qd;
   a.mass_scale = b->arr.domain ? b->arr.mass_scale : nullptr;

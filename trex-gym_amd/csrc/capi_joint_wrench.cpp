@@ -16,11 +16,11 @@ int trex_batch_joint_wrench(TrexBatch *b, const float *accel_dev, const float *w
   if (b->nj < 1) return fail(TREX_E_INVALID, "trex_batch_joint_wrench: the model has no joint");
   DeviceGuard guard(b->device);
   const size_t n = (size_t)b->n, body_bytes = n * b->nb * 6 * sizeof(float);
-  BUF_TRY(accel_dev, n * (6 + b->nj) * sizeof(float), "trex_batch_joint_wrench: accel");
-  BUF_TRY(wrench_a_dev, body_bytes, "trex_batch_joint_wrench: wrench_a");
-  BUF_TRY(wrench_b_dev, body_bytes, "trex_batch_joint_wrench: wrench_b");
-  BUF_TRY(out_dev, n * b->nj * 6 * sizeof(float), "trex_batch_joint_wrench: out");
-  BUF_TRY(base_out_dev, n * 6 * sizeof(float), "trex_batch_joint_wrench: base_out");
+  BUF_TRY(b, accel_dev, n * (6 + b->nj) * sizeof(float), "trex_batch_joint_wrench: accel");
+  BUF_TRY(b, wrench_a_dev, body_bytes, "trex_batch_joint_wrench: wrench_a");
+  BUF_TRY(b, wrench_b_dev, body_bytes, "trex_batch_joint_wrench: wrench_b");
+  BUF_TRY(b, out_dev, n * b->nj * 6 * sizeof(float), "trex_batch_joint_wrench: out");
+  BUF_TRY(b, base_out_dev, n * 6 * sizeof(float), "trex_batch_joint_wrench: base_out");
   TrexJwArgs a{};
   a.model = b->dmodel; a.base = b->arr.base; a.q = b->arr.q; a.qd = b->arr.qd;
   a.mass_scale = b->arr.domain ? b->arr.mass_scale : nullptr;
@@ -47,10 +47,10 @@ int trex_batch_generalized_velocity(TrexBatch *b, float *vel_dev, const float *p
   if (accel_dev && ((vel_dev && trex::ranges_overlap(accel_dev, bytes, vel_dev, bytes)) || trex::ranges_overlap(accel_dev, bytes, prev_dev, bytes)))
     return fail(TREX_E_INVALID, me + "accel overlaps vel or prev");
   DeviceGuard guard(b->device);
-  BUF_TRY(vel_dev, bytes, "trex_batch_generalized_velocity: vel");
-  BUF_TRY(prev_dev, bytes, "trex_batch_generalized_velocity: prev");
-  BUF_TRY(accel_dev, bytes, "trex_batch_generalized_velocity: accel");
-  if (done_dev) BUF_TRY(done_dev, trex::row_block_bytes(n, done_stride, 1), "trex_batch_generalized_velocity: done");
+  BUF_TRY(b, vel_dev, bytes, "trex_batch_generalized_velocity: vel");
+  BUF_TRY(b, prev_dev, bytes, "trex_batch_generalized_velocity: prev");
+  BUF_TRY(b, accel_dev, bytes, "trex_batch_generalized_velocity: accel");
+  if (done_dev) BUF_TRY(b, done_dev, trex::row_block_bytes(n, done_stride, 1), "trex_batch_generalized_velocity: done");
   TrexGenVelArgs a{};
   a.model = b->dmodel; a.base = b->arr.base; a.qd = b->arr.qd;
   a.n_envs = b->n;

@@ -58,11 +58,11 @@ int trex_batch_monitor_apply(TrexBatch *b, const float *reward_dev, int reward_s
     return c;
   const size_t n = (size_t)b->n;
   DeviceGuard guard(b->device);
-  BUF_TRY(reward_dev, trex::row_block_bytes(n, reward_stride, 1), "trex_batch_monitor_apply: reward");
-  BUF_TRY(done_dev, trex::row_block_bytes(n, done_stride, 1), "trex_batch_monitor_apply: done");
-  BUF_TRY(reason_dev, n * sizeof(int32_t), "trex_batch_monitor_apply: reason");
-  if (m.cols_a > 0) BUF_TRY(cols_a_dev, trex::row_block_bytes(n, stride_a, m.cols_a), "trex_batch_monitor_apply: cols_a");
-  if (m.cols_b > 0) BUF_TRY(cols_b_dev, trex::row_block_bytes(n, stride_b, m.cols_b), "trex_batch_monitor_apply: cols_b");
+  BUF_TRY(b, reward_dev, trex::row_block_bytes(n, reward_stride, 1), "trex_batch_monitor_apply: reward");
+  BUF_TRY(b, done_dev, trex::row_block_bytes(n, done_stride, 1), "trex_batch_monitor_apply: done");
+  BUF_TRY(b, reason_dev, n * sizeof(int32_t), "trex_batch_monitor_apply: reason");
+  if (m.cols_a > 0) BUF_TRY(b, cols_a_dev, trex::row_block_bytes(n, stride_a, m.cols_a), "trex_batch_monitor_apply: cols_a");
+  if (m.cols_b > 0) BUF_TRY(b, cols_b_dev, trex::row_block_bytes(n, stride_b, m.cols_b), "trex_batch_monitor_apply: cols_b");
   TrexMonArgs a{};
   a.st = mon.st;
   a.reward = reward_dev; a.done = done_dev;
@@ -81,7 +81,7 @@ int trex_batch_monitor_reset(TrexBatch *b, const uint8_t *mask_dev, void *stream
   const TrexBatch::Monitor &mon = b->monitor;
   if (mon.layout.window < 1) return fail(TREX_E_INVALID, "trex_batch_monitor_reset: no monitor is set (trex_batch_set_monitor)");
   DeviceGuard guard(b->device);
-  BUF_TRY(mask_dev, (size_t)b->n, "trex_batch_monitor_reset: mask");
+  BUF_TRY(b, mask_dev, (size_t)b->n, "trex_batch_monitor_reset: mask");
   HIP_TRY(trex_launch_monitor_reset(mon.st, mask_dev, b->n, mon.layout.cols, (hipStream_t)stream));
   return TREX_OK;
 }
@@ -92,7 +92,7 @@ int trex_batch_monitor_summary(TrexBatch *b, double *out_dev, void *stream) {
   if (mon.layout.window < 1) return fail(TREX_E_INVALID, "trex_batch_monitor_summary: no monitor is set (trex_batch_set_monitor)");
   if (!out_dev) return fail(TREX_E_INVALID, "trex_batch_monitor_summary: out is null");
   DeviceGuard guard(b->device);
-  BUF_TRY(out_dev, (size_t)(TREX_MON_SUMMARY + mon.layout.cols) * sizeof(double), "trex_batch_monitor_summary: out");
+  BUF_TRY(b, out_dev, (size_t)(TREX_MON_SUMMARY + mon.layout.cols) * sizeof(double), "trex_batch_monitor_summary: out");
   HIP_TRY(trex_launch_monitor_summary(mon.st, mon.layout.window, mon.layout.cols, out_dev, (hipStream_t)stream));
   return TREX_OK;
 }

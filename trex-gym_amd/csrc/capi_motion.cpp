@@ -101,10 +101,10 @@ int trex_batch_motion_sample(TrexBatch *b, const float *time_dev, float *state_o
   if (points_out && a.num_probes < 1) return fail(TREX_E_INVALID, me + "points asked for and the clip has no probe set");
   const size_t n = (size_t)b->n;
   DeviceGuard guard(b->device);
-  BUF_TRY(time_dev, n * sizeof(float), "trex_batch_motion_sample: time");
-  BUF_TRY(state_out, n * TREX_MOT_COLS(b->nj) * sizeof(float), "trex_batch_motion_sample: state");
-  BUF_TRY(points_out, n * a.num_probes * 3 * sizeof(float), "trex_batch_motion_sample: points");
-  BUF_TRY(phase_out, n * sizeof(float), "trex_batch_motion_sample: phase");
+  BUF_TRY(b, time_dev, n * sizeof(float), "trex_batch_motion_sample: time");
+  BUF_TRY(b, state_out, n * TREX_MOT_COLS(b->nj) * sizeof(float), "trex_batch_motion_sample: state");
+  BUF_TRY(b, points_out, n * a.num_probes * 3 * sizeof(float), "trex_batch_motion_sample: points");
+  BUF_TRY(b, phase_out, n * sizeof(float), "trex_batch_motion_sample: phase");
   a.time = time_dev; a.state_out = state_out; a.points_out = points_out; a.phase_out = phase_out;
   HIP_TRY(trex_launch_motion_sample(a, (hipStream_t)stream));
   return TREX_OK;
@@ -142,8 +142,8 @@ int trex_batch_compose_motion_reward(TrexBatch *b, float *rows_dev, int row_stri
   if (row_stride < nobs + tail) return fail(TREX_E_INVALID, me + "row_stride < 3J + 2 (3J + 5 with penalties in rows)");
   const size_t n = (size_t)b->n;
   DeviceGuard guard(b->device);
-  BUF_TRY(rows_dev, trex::row_block_bytes(n, row_stride, nobs + tail), "trex_batch_compose_motion_reward: rows");
-  BUF_TRY(terms_dev, n * a.num_terms * sizeof(float), "trex_batch_compose_motion_reward: terms");
+  BUF_TRY(b, rows_dev, trex::row_block_bytes(n, row_stride, nobs + tail), "trex_batch_compose_motion_reward: rows");
+  BUF_TRY(b, terms_dev, n * a.num_terms * sizeof(float), "trex_batch_compose_motion_reward: terms");
   a.rows = rows_dev; a.row_stride = row_stride; a.terms_out = terms_dev;
   HIP_TRY(trex_launch_motion_compose(a, (hipStream_t)stream));
   return TREX_OK;
@@ -158,9 +158,9 @@ int trex_batch_motion_reset(TrexBatch *b, const uint8_t *mask_dev, const float *
   if (rows_dev && row_stride < nobs + tail) return fail(TREX_E_INVALID, me + "row_stride < 3J + 2 (3J + 5 with penalties in rows)");
   const size_t n = (size_t)b->n;
   DeviceGuard guard(b->device);
-  BUF_TRY(mask_dev, n, "trex_batch_motion_reset: mask");
-  BUF_TRY(time_dev, n * sizeof(float), "trex_batch_motion_reset: time");
-  BUF_TRY(rows_dev, trex::row_block_bytes(n, row_stride, nobs + tail), "trex_batch_motion_reset: rows");
+  BUF_TRY(b, mask_dev, n, "trex_batch_motion_reset: mask");
+  BUF_TRY(b, time_dev, n * sizeof(float), "trex_batch_motion_reset: time");
+  BUF_TRY(b, rows_dev, trex::row_block_bytes(n, row_stride, nobs + tail), "trex_batch_motion_reset: rows");
   a.mask = mask_dev; a.time = time_dev; a.rows = rows_dev; a.row_stride = row_stride;
   a.warm = b->warm.as<float>();
   HIP_TRY(trex_launch_motion_reset(a, (hipStream_t)stream));

@@ -54,7 +54,7 @@ int trex_batch_head_position(TrexBatch *b, float *out_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
   if (!out_dev) return fail(TREX_E_INVALID, "out is null");
   DeviceGuard guard(b->device);
-  BUF_TRY(out_dev, (size_t)b->n * 3 * sizeof(float), "trex_batch_head_position: out");
+  BUF_TRY(b, out_dev, (size_t)b->n * 3 * sizeof(float), "trex_batch_head_position: out");
   HIP_TRY(trex_launch_head(b->dmodel, b->arr, b->n, out_dev, (hipStream_t)stream));
   return TREX_OK;
 }
@@ -63,7 +63,7 @@ int trex_batch_link_transforms(TrexBatch *b, float *out_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
   if (!out_dev) return fail(TREX_E_INVALID, "out is null");
   DeviceGuard guard(b->device);
-  BUF_TRY(out_dev, (size_t)b->n * b->arr.num_links * 7 * sizeof(float), "trex_batch_link_transforms: out");
+  BUF_TRY(b, out_dev, (size_t)b->n * b->arr.num_links * 7 * sizeof(float), "trex_batch_link_transforms: out");
   HIP_TRY(trex_launch_link_transforms(b->dmodel, b->arr, b->n, out_dev, (hipStream_t)stream, 0));
   return TREX_OK;
 }
@@ -73,7 +73,7 @@ int trex_batch_visual_transforms(TrexBatch *b, float *out_dev, void *stream) {
   if (!out_dev) return fail(TREX_E_INVALID, "out is null");
   if (b->arr.num_visuals == 0) return fail(TREX_E_INVALID, "the model has no <visual> meshes");
   DeviceGuard guard(b->device);
-  BUF_TRY(out_dev, (size_t)b->n * b->arr.num_visuals * 7 * sizeof(float), "trex_batch_visual_transforms: out");
+  BUF_TRY(b, out_dev, (size_t)b->n * b->arr.num_visuals * 7 * sizeof(float), "trex_batch_visual_transforms: out");
   HIP_TRY(trex_launch_link_transforms(b->dmodel, b->arr, b->n, out_dev, (hipStream_t)stream, 1));
   return TREX_OK;
 }
@@ -83,7 +83,7 @@ int trex_batch_contact_wrench(TrexBatch *b, float *out_dev, void *stream) {
   if (!b->sens_on) return fail(TREX_E_INVALID, "trex_batch_contact_wrench: the contact sensor is off (trex_batch_set_contact_sensor)");
   if (!out_dev) return fail(TREX_E_INVALID, "trex_batch_contact_wrench: out is null");
   DeviceGuard guard(b->device);
-  BUF_TRY(out_dev, (size_t)b->n * b->nb * 6 * sizeof(float), "trex_batch_contact_wrench: out");
+  BUF_TRY(b, out_dev, (size_t)b->n * b->nb * 6 * sizeof(float), "trex_batch_contact_wrench: out");
   HIP_TRY(trex_launch_contact_wrench(b->sens.as<float>(), out_dev, b->n, b->nb, (hipStream_t)stream));
   return TREX_OK;
 }
@@ -101,8 +101,8 @@ int trex_batch_inverse_dynamics(TrexBatch *b, const float *accel_dev, float *for
   if (!force_dev) return fail(TREX_E_INVALID, "trex_batch_inverse_dynamics: force is null");
   DeviceGuard guard(b->device);
   const size_t bytes = (size_t)b->n * (6 + b->nj) * sizeof(float);
-  BUF_TRY(accel_dev, bytes, "trex_batch_inverse_dynamics: accel");
-  BUF_TRY(force_dev, bytes, "trex_batch_inverse_dynamics: force");
+  BUF_TRY(b, accel_dev, bytes, "trex_batch_inverse_dynamics: accel");
+  BUF_TRY(b, force_dev, bytes, "trex_batch_inverse_dynamics: force");
   TrexDynArgs a = dyn_args(b, force_dev);
   a.accel = accel_dev;
   HIP_TRY(trex_launch_dynamics(a, TREX_DYN_INVERSE_DYNAMICS, (hipStream_t)stream));
@@ -114,7 +114,7 @@ int trex_batch_mass_matrix(TrexBatch *b, float *M_dev, void *stream) {
   if (!M_dev) return fail(TREX_E_INVALID, "trex_batch_mass_matrix: M is null");
   DeviceGuard guard(b->device);
   const size_t D = 6 + (size_t)b->nj;
-  BUF_TRY(M_dev, (size_t)b->n * D * D * sizeof(float), "trex_batch_mass_matrix: M");
+  BUF_TRY(b, M_dev, (size_t)b->n * D * D * sizeof(float), "trex_batch_mass_matrix: M");
   HIP_TRY(trex_launch_dynamics(dyn_args(b, M_dev), TREX_DYN_MASS_MATRIX, (hipStream_t)stream));
   return TREX_OK;
 }
@@ -126,7 +126,7 @@ int trex_batch_jacobian(TrexBatch *b, int link, const double local_xyz[3], float
   for (int c = 0; c < 3; c++)
     if (!std::isfinite(local_xyz[c])) return fail(TREX_E_INVALID, "trex_batch_jacobian: local_xyz is not finite");
   DeviceGuard guard(b->device);
-  BUF_TRY(J_dev, (size_t)b->n * 6 * (6 + b->nj) * sizeof(float), "trex_batch_jacobian: J");
+  BUF_TRY(b, J_dev, (size_t)b->n * 6 * (6 + b->nj) * sizeof(float), "trex_batch_jacobian: J");
   TrexDynArgs a = dyn_args(b, J_dev);
   const trex::LinkPoint p = trex::link_point(b->links, link, local_xyz);   // the point in the frame of the link's body
   a.jac_body = p.body;
@@ -139,7 +139,7 @@ int trex_batch_centroidal(TrexBatch *b, float *out_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
   if (!out_dev) return fail(TREX_E_INVALID, "trex_batch_centroidal: out is null");
   DeviceGuard guard(b->device);
-  BUF_TRY(out_dev, (size_t)b->n * TREX_DYN_CENT_FLOATS * sizeof(float), "trex_batch_centroidal: out");
+  BUF_TRY(b, out_dev, (size_t)b->n * TREX_DYN_CENT_FLOATS * sizeof(float), "trex_batch_centroidal: out");
   HIP_TRY(trex_launch_dynamics(dyn_args(b, out_dev), TREX_DYN_CENTROIDAL, (hipStream_t)stream));
   return TREX_OK;
 }
@@ -149,8 +149,8 @@ int trex_batch_forward_dynamics(TrexBatch *b, const float *force_dev, float *acc
   if (!accel_dev) return fail(TREX_E_INVALID, "trex_batch_forward_dynamics: accel is null");
   DeviceGuard guard(b->device);
   const size_t bytes = (size_t)b->n * (6 + b->nj) * sizeof(float);
-  BUF_TRY(force_dev, bytes, "trex_batch_forward_dynamics: force");
-  BUF_TRY(accel_dev, bytes, "trex_batch_forward_dynamics: accel");
+  BUF_TRY(b, force_dev, bytes, "trex_batch_forward_dynamics: force");
+  BUF_TRY(b, accel_dev, bytes, "trex_batch_forward_dynamics: accel");
   TrexDynArgs a = dyn_args(b, accel_dev);
   a.rhs = force_dev;
   a.num_rhs = 1;
@@ -167,8 +167,8 @@ int trex_batch_solve_mass(TrexBatch *b, const float *rhs_dev, int num_rhs, float
     return fail(TREX_E_INVALID, "trex_batch_solve_mass: a null rhs is the identity, num_rhs must be " + std::to_string(6 + b->nj));
   DeviceGuard guard(b->device);
   const size_t bytes = (size_t)b->n * num_rhs * (6 + b->nj) * sizeof(float);
-  BUF_TRY(rhs_dev, bytes, "trex_batch_solve_mass: rhs");
-  BUF_TRY(x_dev, bytes, "trex_batch_solve_mass: x");
+  BUF_TRY(b, rhs_dev, bytes, "trex_batch_solve_mass: rhs");
+  BUF_TRY(b, x_dev, bytes, "trex_batch_solve_mass: x");
   TrexDynArgs a = dyn_args(b, x_dev);
   a.rhs = rhs_dev;
   a.num_rhs = num_rhs;
@@ -179,8 +179,8 @@ int trex_batch_solve_mass(TrexBatch *b, const float *rhs_dev, int num_rhs, float
 int trex_batch_contact_stats(TrexBatch *b, int32_t *count_dev, float *normal_impulse_dev, void *stream) {
   if (check_batch(b)) return TREX_E_INVALID;
   DeviceGuard guard(b->device);
-  BUF_TRY(count_dev, (size_t)b->n * sizeof(int32_t), "trex_batch_contact_stats: count");
-  BUF_TRY(normal_impulse_dev, (size_t)b->n * sizeof(float), "trex_batch_contact_stats: normal_impulse");
+  BUF_TRY(b, count_dev, (size_t)b->n * sizeof(int32_t), "trex_batch_contact_stats: count");
+  BUF_TRY(b, normal_impulse_dev, (size_t)b->n * sizeof(float), "trex_batch_contact_stats: normal_impulse");
   if (count_dev || normal_impulse_dev)
     HIP_TRY(trex_launch_scalars_get(b->arr, b->n, count_dev, normal_impulse_dev, nullptr, (hipStream_t)stream));
   return TREX_OK;
@@ -232,9 +232,9 @@ int trex_batch_render(TrexBatch *b, const TrexCamera *cam, int width, int height
   if (num_views > 65535) return fail(TREX_E_INVALID, "trex_batch_render: at most 65535 views per call");
   DeviceGuard guard(b->device);
   const size_t px = (size_t)num_views * height * width;
-  BUF_TRY(rgb_dev, px * 3, "trex_batch_render: rgb");
-  BUF_TRY(depth_dev, px * sizeof(float), "trex_batch_render: depth");
-  BUF_TRY(seg_dev, px * sizeof(int32_t), "trex_batch_render: seg");
+  BUF_TRY(b, rgb_dev, px * 3, "trex_batch_render: rgb");
+  BUF_TRY(b, depth_dev, px * sizeof(float), "trex_batch_render: depth");
+  BUF_TRY(b, seg_dev, px * sizeof(int32_t), "trex_batch_render: seg");
   hipStream_t s = (hipStream_t)stream;
   if (int c = ensure_render_table(b, "trex_batch_render")) return c;
   if (env_ids) {
@@ -271,11 +271,11 @@ int trex_batch_ray_test(TrexBatch *b, const float *rays_dev, int num_rays, int s
   if (int c = check_link(b, "trex_batch_ray_test", link, -1)) return c;
   DeviceGuard guard(b->device);
   const size_t nr = (size_t)b->n * num_rays;
-  BUF_TRY(rays_dev, (shared ? (size_t)num_rays : nr) * 6 * sizeof(float), "trex_batch_ray_test: rays");
-  BUF_TRY(fraction_dev, nr * sizeof(float), "trex_batch_ray_test: fraction");
-  BUF_TRY(body_dev, nr * sizeof(int32_t), "trex_batch_ray_test: body");
-  BUF_TRY(position_dev, nr * 3 * sizeof(float), "trex_batch_ray_test: position");
-  BUF_TRY(normal_dev, nr * 3 * sizeof(float), "trex_batch_ray_test: normal");
+  BUF_TRY(b, rays_dev, (shared ? (size_t)num_rays : nr) * 6 * sizeof(float), "trex_batch_ray_test: rays");
+  BUF_TRY(b, fraction_dev, nr * sizeof(float), "trex_batch_ray_test: fraction");
+  BUF_TRY(b, body_dev, nr * sizeof(int32_t), "trex_batch_ray_test: body");
+  BUF_TRY(b, position_dev, nr * 3 * sizeof(float), "trex_batch_ray_test: position");
+  BUF_TRY(b, normal_dev, nr * 3 * sizeof(float), "trex_batch_ray_test: normal");
   if (int c = ensure_render_table(b, "trex_batch_ray_test")) return c;
   TrexRayArgs a = query_args<TrexRayArgs>(b);
   a.rays = rays_dev; a.fraction = fraction_dev; a.body = body_dev; a.position = position_dev; a.normal = normal_dev;
@@ -327,10 +327,10 @@ int trex_batch_link_state(TrexBatch *b, int set, int axes, int proper, const flo
   if (!pose_dev && !velocity_dev && !acceleration_dev) return fail(TREX_E_INVALID, "trex_batch_link_state: all three outputs are null");
   DeviceGuard guard(b->device);
   const size_t nk = (size_t)b->n * ps.n;
-  if (acceleration_dev) BUF_TRY(accel_dev, (size_t)b->n * (6 + b->nj) * sizeof(float), "trex_batch_link_state: accel");
-  BUF_TRY(pose_dev, nk * 7 * sizeof(float), "trex_batch_link_state: pose");
-  BUF_TRY(velocity_dev, nk * 6 * sizeof(float), "trex_batch_link_state: velocity");
-  BUF_TRY(acceleration_dev, nk * 6 * sizeof(float), "trex_batch_link_state: acceleration");
+  if (acceleration_dev) BUF_TRY(b, accel_dev, (size_t)b->n * (6 + b->nj) * sizeof(float), "trex_batch_link_state: accel");
+  BUF_TRY(b, pose_dev, nk * 7 * sizeof(float), "trex_batch_link_state: pose");
+  BUF_TRY(b, velocity_dev, nk * 6 * sizeof(float), "trex_batch_link_state: velocity");
+  BUF_TRY(b, acceleration_dev, nk * 6 * sizeof(float), "trex_batch_link_state: acceleration");
   TrexLinkArgs a = query_args<TrexLinkArgs>(b);
   a.accel = acceleration_dev ? accel_dev : nullptr;
   a.probe_body = ps.body.as<int32_t>(); a.probe_tf = ps.tf.as<float>();
@@ -361,10 +361,10 @@ int trex_batch_inverse_kinematics(TrexBatch *b, int set, const int32_t *mode_hos
   if (int c = built([&] { t = trex::build_ik_task(ps.host_body, b->parent, b->obs_order, mode_host, joint_mask, params); })) return c;
   DeviceGuard guard(b->device);
   const size_t nj = (size_t)b->n * b->nj * sizeof(float);
-  BUF_TRY(target_dev, (size_t)b->n * ps.n * 7 * sizeof(float), "trex_batch_inverse_kinematics: target");
-  BUF_TRY(q_init_dev, nj, "trex_batch_inverse_kinematics: q_init");
-  BUF_TRY(q_out_dev, nj, "trex_batch_inverse_kinematics: q_out");
-  BUF_TRY(info_dev, (size_t)b->n * 4 * sizeof(float), "trex_batch_inverse_kinematics: info");
+  BUF_TRY(b, target_dev, (size_t)b->n * ps.n * 7 * sizeof(float), "trex_batch_inverse_kinematics: target");
+  BUF_TRY(b, q_init_dev, nj, "trex_batch_inverse_kinematics: q_init");
+  BUF_TRY(b, q_out_dev, nj, "trex_batch_inverse_kinematics: q_out");
+  BUF_TRY(b, info_dev, (size_t)b->n * 4 * sizeof(float), "trex_batch_inverse_kinematics: info");
   TrexIkArgs a = query_args<TrexIkArgs>(b);
   a.probe_tf = ps.tf.as<float>(); a.target = target_dev; a.q_init = q_init_dev; a.q_out = q_out_dev; a.info = info_dev;
   a.nb = b->nb; a.K = ps.n; a.M = t.rows; a.frame = frame;
@@ -405,11 +405,11 @@ int trex_batch_proximity(TrexBatch *b, float *distance_dev, float *point_a_dev, 
   if (!distance_dev) return fail(TREX_E_INVALID, "trex_batch_proximity: distance is null");
   DeviceGuard guard(b->device);
   const size_t np = (size_t)b->n * pt.pairs;
-  BUF_TRY(distance_dev, np * sizeof(float), "trex_batch_proximity: distance");
-  BUF_TRY(point_a_dev, np * 3 * sizeof(float), "trex_batch_proximity: point_a");
-  BUF_TRY(point_b_dev, np * 3 * sizeof(float), "trex_batch_proximity: point_b");
-  BUF_TRY(normal_dev, np * 3 * sizeof(float), "trex_batch_proximity: normal");
-  BUF_TRY(capsule_dev, np * 2 * sizeof(int32_t), "trex_batch_proximity: capsule");
+  BUF_TRY(b, distance_dev, np * sizeof(float), "trex_batch_proximity: distance");
+  BUF_TRY(b, point_a_dev, np * 3 * sizeof(float), "trex_batch_proximity: point_a");
+  BUF_TRY(b, point_b_dev, np * 3 * sizeof(float), "trex_batch_proximity: point_b");
+  BUF_TRY(b, normal_dev, np * 3 * sizeof(float), "trex_batch_proximity: normal");
+  BUF_TRY(b, capsule_dev, np * 2 * sizeof(int32_t), "trex_batch_proximity: capsule");
   TrexProxArgs a = query_args<TrexProxArgs>(b);
   const char *blob = b->prox.blob.as<char>();
   a.cap = (const float *)blob; a.cap_body = (const int32_t *)(blob + pt.o_body);
@@ -469,10 +469,10 @@ int trex_batch_compose_rows(TrexBatch *b, const float *rows_dev, int row_stride,
   const size_t rows_bytes = trex::row_block_bytes(n, row_stride, nobs + tail), out_bytes = trex::row_block_bytes(n, out_stride, width);
   if (trex::ranges_overlap(rows_dev, rows_bytes, out_rows_dev, out_bytes)) return fail(TREX_E_INVALID, me + "out_rows overlaps rows");
   DeviceGuard guard(b->device);
-  BUF_TRY(rows_dev, rows_bytes, "trex_batch_compose_rows: rows");
-  BUF_TRY(out_rows_dev, out_bytes, "trex_batch_compose_rows: out_rows");
-  if (ot.actions) BUF_TRY(actions_dev, n * ot.action_cols * sizeof(float), "trex_batch_compose_rows: actions");
-  if (ot.extern_cols > 0) BUF_TRY(extern_dev, trex::row_block_bytes(n, extern_stride, ot.extern_cols), "trex_batch_compose_rows: extern");
+  BUF_TRY(b, rows_dev, rows_bytes, "trex_batch_compose_rows: rows");
+  BUF_TRY(b, out_rows_dev, out_bytes, "trex_batch_compose_rows: out_rows");
+  if (ot.actions) BUF_TRY(b, actions_dev, n * ot.action_cols * sizeof(float), "trex_batch_compose_rows: actions");
+  if (ot.extern_cols > 0) BUF_TRY(b, extern_dev, trex::row_block_bytes(n, extern_stride, ot.extern_cols), "trex_batch_compose_rows: extern");
   TrexObsArgs a = query_args<TrexObsArgs>(b);
   const char *blob = b->observation.blob.as<char>();
   a.chan = (const TrexObsChan *)blob; a.col_chan = (const uint8_t *)(blob + ot.o_col);
@@ -539,10 +539,10 @@ int trex_batch_compose_reward(TrexBatch *b, float *rows_dev, int row_stride, con
                                     std::to_string(rt.action_cols) + " (set the terms again)");
   const size_t n = (size_t)b->n;
   DeviceGuard guard(b->device);
-  BUF_TRY(rows_dev, trex::row_block_bytes(n, row_stride, nobs + tail), "trex_batch_compose_reward: rows");
-  if (rt.actions) BUF_TRY(actions_dev, n * rt.action_cols * sizeof(float), "trex_batch_compose_reward: actions");
-  if (rt.command) BUF_TRY(command_dev, n * 3 * sizeof(float), "trex_batch_compose_reward: command");
-  BUF_TRY(terms_dev, n * rt.terms * sizeof(float), "trex_batch_compose_reward: terms");
+  BUF_TRY(b, rows_dev, trex::row_block_bytes(n, row_stride, nobs + tail), "trex_batch_compose_reward: rows");
+  if (rt.actions) BUF_TRY(b, actions_dev, n * rt.action_cols * sizeof(float), "trex_batch_compose_reward: actions");
+  if (rt.command) BUF_TRY(b, command_dev, n * 3 * sizeof(float), "trex_batch_compose_reward: command");
+  BUF_TRY(b, terms_dev, n * rt.terms * sizeof(float), "trex_batch_compose_reward: terms");
   TrexRewArgs a = query_args<TrexRewArgs>(b);
   const char *blob = r.blob.as<char>();
   a.term = (const TrexRewTerm *)blob; a.joint_body = (const int32_t *)(blob + rt.o_joint);
@@ -562,7 +562,7 @@ int trex_batch_reward_reset(TrexBatch *b, const uint8_t *mask_dev, void *stream)
   const TrexBatch::Reward &r = b->reward;
   if (r.table.terms < 1) return fail(TREX_E_INVALID, "trex_batch_reward_reset: no terms are set (trex_batch_set_reward)");
   DeviceGuard guard(b->device);
-  BUF_TRY(mask_dev, (size_t)b->n, "trex_batch_reward_reset: mask");
+  BUF_TRY(b, mask_dev, (size_t)b->n, "trex_batch_reward_reset: mask");
   HIP_TRY(trex_launch_reward_reset(mask_dev, b->n, r.table.terms, r.st.timer, r.st.held, r.st.valid, (hipStream_t)stream));
   return TREX_OK;
 }
@@ -573,8 +573,8 @@ int trex_batch_body_clearance(TrexBatch *b, float *clearance_dev, float *lowest_
   if (!clearance_dev) return fail(TREX_E_INVALID, "trex_batch_body_clearance: clearance is null");
   DeviceGuard guard(b->device);
   const size_t nb = (size_t)b->n * b->nb;
-  BUF_TRY(clearance_dev, nb * sizeof(float), "trex_batch_body_clearance: clearance");
-  BUF_TRY(lowest_dev, nb * 3 * sizeof(float), "trex_batch_body_clearance: lowest");
+  BUF_TRY(b, clearance_dev, nb * sizeof(float), "trex_batch_body_clearance: clearance");
+  BUF_TRY(b, lowest_dev, nb * 3 * sizeof(float), "trex_batch_body_clearance: lowest");
   TrexTermArgs t = query_args<TrexTermArgs>(b);
   t.hull = b->arr.hull;
   t.clearance = clearance_dev; t.lowest = lowest_dev;
@@ -588,9 +588,9 @@ int trex_batch_termination_info(TrexBatch *b, int32_t *reason_dev, float *values
   if (!tm.blob) return fail(TREX_E_INVALID, "trex_batch_termination_info: termination was never enabled (trex_batch_set_termination)");
   DeviceGuard guard(b->device);
   const size_t n = (size_t)b->n;
-  BUF_TRY(reason_dev, n * sizeof(int32_t), "trex_batch_termination_info: reason");
-  BUF_TRY(values_dev, n * 3 * sizeof(float), "trex_batch_termination_info: values");
-  BUF_TRY(terminal_obs_dev, n * 3 * b->nj * sizeof(float), "trex_batch_termination_info: terminal_obs");
+  BUF_TRY(b, reason_dev, n * sizeof(int32_t), "trex_batch_termination_info: reason");
+  BUF_TRY(b, values_dev, n * 3 * sizeof(float), "trex_batch_termination_info: values");
+  BUF_TRY(b, terminal_obs_dev, n * 3 * b->nj * sizeof(float), "trex_batch_termination_info: terminal_obs");
   hipStream_t s = (hipStream_t)stream;
   if (reason_dev) HIP_TRY(hipMemcpyAsync(reason_dev, tm.reason, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   if (values_dev) HIP_TRY(hipMemcpyAsync(values_dev, tm.values, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));

@@ -106,8 +106,8 @@ int trex_batch_apply_randomization(TrexBatch *b, const float *done_dev, int done
   if (r.table.command && !command_dev) return fail(TREX_E_INVALID, me + "a COMMAND term is set and command is null");
   const size_t n = (size_t)b->n;
   DeviceGuard guard(b->device);
-  BUF_TRY(done_dev, trex::row_block_bytes(n, done_stride, 1), "trex_batch_apply_randomization: done");
-  BUF_TRY(command_dev, n * 3 * sizeof(float), "trex_batch_apply_randomization: command");
+  BUF_TRY(b, done_dev, trex::row_block_bytes(n, done_stride, 1), "trex_batch_apply_randomization: done");
+  BUF_TRY(b, command_dev, n * 3 * sizeof(float), "trex_batch_apply_randomization: command");
   TrexRandArgs a{};
   a.table = r.blob.as<TrexRandTable>(); a.model = b->dmodel; a.st = r.st;
   a.done = done_dev; a.done_stride = done_stride; a.command = command_dev;
@@ -124,7 +124,7 @@ int trex_batch_randomization_reset(TrexBatch *b, const uint8_t *mask_dev, void *
   const TrexBatch::Randomization &r = b->random;
   if (r.table.terms < 1) return fail(TREX_E_INVALID, "trex_batch_randomization_reset: no terms are set (trex_batch_set_randomization)");
   DeviceGuard guard(b->device);
-  BUF_TRY(mask_dev, (size_t)b->n, "trex_batch_randomization_reset: mask");
+  BUF_TRY(b, mask_dev, (size_t)b->n, "trex_batch_randomization_reset: mask");
   HIP_TRY(trex_launch_randomize_reset(mask_dev, b->n, r.st.started, (hipStream_t)stream));
   return TREX_OK;
 }

@@ -75,8 +75,8 @@ int trex_batch_apply_sensing(TrexBatch *b, const float *rows_dev, int row_stride
     return fail(TREX_E_INVALID, me + "out_rows overlaps rows in part");
   }
   DeviceGuard guard(b->device);
-  BUF_TRY(rows_dev, rows_bytes, "trex_batch_apply_sensing: rows");
-  BUF_TRY(out_rows_dev, out_bytes, "trex_batch_apply_sensing: out_rows");
+  BUF_TRY(b, rows_dev, rows_bytes, "trex_batch_apply_sensing: rows");
+  BUF_TRY(b, out_rows_dev, out_bytes, "trex_batch_apply_sensing: out_rows");
   TrexSenseArgs a{};
   const char *blob = s.blob.as<char>();
   a.group = (const TrexSenseGrp *)blob; a.col_group = (const int16_t *)(blob + t.o_col_group); a.col_hist = (const int16_t *)(blob + t.o_col_hist);
@@ -99,7 +99,7 @@ int trex_batch_sensing_reset(TrexBatch *b, const uint8_t *mask_dev, void *stream
     return fail(TREX_E_INVALID, "trex_batch_sensing_reset: neither groups nor an action delay are set (trex_batch_set_sensing, trex_batch_set_action_delay)");
   const size_t n = (size_t)b->n;
   DeviceGuard guard(b->device);
-  BUF_TRY(mask_dev, n, "trex_batch_sensing_reset: mask");
+  BUF_TRY(b, mask_dev, n, "trex_batch_sensing_reset: mask");
   HIP_TRY(trex_launch_sensing_reset(mask_dev, b->n, s.st.started, s.act_st.started, (hipStream_t)stream));
   return TREX_OK;
 }
@@ -145,9 +145,9 @@ int trex_batch_delay_actions(TrexBatch *b, const float *actions_dev, const uint8
   if (actions_dev != out_actions_dev && trex::ranges_overlap(actions_dev, bytes, out_actions_dev, bytes))
     return fail(TREX_E_INVALID, me + "out_actions overlaps actions in part");
   DeviceGuard guard(b->device);
-  BUF_TRY(actions_dev, bytes, "trex_batch_delay_actions: actions");
-  BUF_TRY(out_actions_dev, bytes, "trex_batch_delay_actions: out_actions");
-  BUF_TRY(done_prev_dev, n, "trex_batch_delay_actions: done_prev");
+  BUF_TRY(b, actions_dev, bytes, "trex_batch_delay_actions: actions");
+  BUF_TRY(b, out_actions_dev, bytes, "trex_batch_delay_actions: out_actions");
+  BUF_TRY(b, done_prev_dev, n, "trex_batch_delay_actions: done_prev");
   TrexActDelayArgs a{};
   a.actions = actions_dev; a.done_prev = done_prev_dev; a.out = out_actions_dev;
   a.ep = s.act_st.ep; a.k = s.act_st.k; a.started = s.act_st.started; a.delay = s.act_st.delay;

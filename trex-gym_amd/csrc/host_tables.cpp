@@ -1,6 +1,8 @@
 // The tables the kernels read, built on the host: see host_tables.hpp for the include rule (no HIP in here).
 #include "host_tables.hpp"
 
+#include "../../include/trex_policy.h"
+
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -691,6 +693,87 @@ void check_monitor_apply(const MonitorLayout &m, bool reward, int reward_stride,
   if (m.cols_b > 0 && !block_b) throw Refusal(me + "cols_b is null and its width is " + std::to_string(m.cols_b));
   if (m.cols_a > 0 && stride_a < m.cols_a) throw Refusal(me + "stride_a " + std::to_string(stride_a) + " below the width " + std::to_string(m.cols_a));
   if (m.cols_b > 0 && stride_b < m.cols_b) throw Refusal(me + "stride_b " + std::to_string(stride_b) + " below the width " + std::to_string(m.cols_b));
+}
+
+// ---- the trainer. The message of a refusal is formed when it is thrown: these run on every call of a rollout.
+void check_policy_create(int num_envs, int obs_dim, int act_dim, int hidden) {
+  using namespace trex_policy;
+  if (num_envs <= 0) throw Refusal("num_envs must be positive");
+  if (hidden != HID) throw Refusal("the policy kernel is written for hidden = 64 (baselines' MlpPolicy)", TREX_E_UNSUPPORTED);
+  if (act_dim < 1 || act_dim > POLICY_MAX_ACT) throw Refusal("act_dim must be in [1, 32]", TREX_E_UNSUPPORTED);
+  if (obs_dim < 1 || obs_dim > POLICY_MAX_OBS) throw Refusal("obs_dim must be in [1, 126]", TREX_E_UNSUPPORTED);
+}
+
+void check_policy_set_critic(const PolicyShape *p, int critic_dim) {
+  if (!p) throw Refusal("trex_policy_set_critic: null policy");
+  if (critic_dim < 0 || critic_dim > trex_policy::POLICY_MAX_OBS)
+    throw Refusal("trex_policy_set_critic: critic_dim must be in [0, 126] (0 clears)");
+}
+
+void check_policy_has_critic(const char *who, const PolicyShape *p, bool arg) {
+  if (!p || !arg) throw Refusal(std::string(who) + ": null argument");
+  if (!p->Dv) throw Refusal(std::string(who) + ": no critic width is set (trex_policy_set_critic)");
+}
+
+void check_policy_observe(const PolicyShape *p, bool rows, int row_stride, bool with_reward) {
+  if (!p || !rows) throw Refusal("trex_policy_observe: null argument");
+  if (row_stride < p->D + (with_reward ? 2 : 0)) throw Refusal("trex_policy_observe: row_stride too small");
+}
+
+void check_policy_critic_observe(const PolicyShape *p, bool rows_v, int stride_v) {
+  check_policy_has_critic("trex_policy_critic_observe", p, rows_v);
+  if (stride_v < p->Dv) throw Refusal("trex_policy_critic_observe: stride_v < critic_dim");
+}
+
+void check_policy_act(const PolicyShape *p, const PolicyActCall &c) {
+  if (!p || !c.theta || !c.rows) throw Refusal("trex_policy_act: null argument");
+  if (p->Dv) throw Refusal("trex_policy_act: the policy has a critic width set (trex_policy_critic_act takes its row)");
+  if (!c.value_only && (!c.noise || !c.actions)) throw Refusal("trex_policy_act: noise / actions are null");
+  if (c.value_only && !c.value_out) throw Refusal("trex_policy_act: value_out is null");
+  if (c.row_stride < p->D) throw Refusal("trex_policy_act: row_stride < obs_dim");
+}
+
+void check_policy_critic_act(const PolicyShape *p, const PolicyActCall &c) {
+  check_policy_has_critic("trex_policy_critic_act", p, c.theta);
+  if (c.value_only) {
+    if (!c.rows_v || !c.value_out) throw Refusal("trex_policy_critic_act: value_only needs rows_v and value_out");
+  } else {
+    if (!c.rows || !c.noise || !c.actions) throw Refusal("trex_policy_critic_act: rows / noise / actions are null");
+    if (!c.rows_v && (c.value_out || c.obs_v_out))
+      throw Refusal("trex_policy_critic_act: without rows_v only the policy runs: value_out and obs_v_out must be null");
+  }
+  if (c.rows && c.row_stride < p->D) throw Refusal("trex_policy_critic_act: row_stride < obs_dim");
+  if (c.rows_v && c.stride_v < p->Dv) throw Refusal("trex_policy_critic_act: stride_v < critic_dim");
+}
+
+void check_policy_gae(const PolicyShape *p, bool buffers, int T) {
+  if (!p || !buffers || T <= 0) throw Refusal("trex_policy_gae: bad argument");
+}
+
+void check_policy_minibatch_stats(const PolicyShape *p, bool buffers, int num_minibatches, int mb, int64_t num_samples) {
+  if (!p || !buffers || num_minibatches <= 0 || mb <= 0 || num_samples <= 0) throw Refusal("trex_policy_minibatch_stats: bad argument");
+}
+
+void check_policy_minibatch(const PolicyShape *p, const PolicyMinibatchCall &c) {
+  using namespace trex_policy;
+  const auto no = [&](const char *why) { return Refusal(std::string(c.who) + why); };
+  if (!p || !c.buffers) throw no(": null argument");
+  if (c.mb <= 0 || c.first < 0 || c.num_samples <= 0) throw no(": bad sizes");
+  if (c.distill) {
+    if (c.kind != TREX_DISTILL_MSE && c.kind != TREX_DISTILL_KL) throw no(": unknown loss kind (TREX_DISTILL_MSE, TREX_DISTILL_KL)");
+    if (c.kind == TREX_DISTILL_KL && !c.teacher_logstd) throw no(": the KL loss needs teacher_logstd");
+    if (!c.teacher_value && c.vf_coef != 0.f) throw no(": teacher_value may be null only with vf_coef == 0");
+    if (p->Dv) throw no(": the policy has a critic width set (a student has no privileged critic)");
+  } else {
+    // the critic entry points pass obs_v, the plain ones do not; either kind refuses an object of the other kind by name
+    if (!c.critic && p->Dv) throw no(": the policy has a critic width set (the trex_policy_critic_minibatch calls take obs_v)");
+    if (c.critic && !p->Dv) throw no(": no critic width is set (trex_policy_set_critic)");
+    if (p->Dv > LEARN_MAX_OBS) throw no(": the learner stages 96 observation columns (critic_dim <= 96)");
+  }
+  if (p->D > LEARN_MAX_OBS) throw no(": the learner stages 96 observation columns (obs_dim <= 96)");
+  const PolicyLayout &l = p->lay;
+  if ((l.vW1 + (l.count - l.logstd)) / 4 > 256 * LEARN_UF || (l.logstd - l.vW1) / 4 > 256 * LEARN_UF)
+    throw no(": the learner stages one net's parameters in one trip of 256 x 13 float4s");
 }
 
 CameraBasis camera_basis(const TrexCamera &cam, int width, int height) {

@@ -1,6 +1,6 @@
 // The tables the kernels read and the layouts of the per-env state they write, as pure host arithmetic: everything the C-ABI computes
 // between its argument checks and its HIP calls.
-// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h, motion_limits.h, sensing_limits.h and include/trex_batch.h, and nothing of HIP; it makes
+// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h, motion_limits.h, sensing_limits.h, policy_limits.h and include/trex_batch.h, and nothing of HIP; it makes
 // no HIP call and knows no batch. It builds with plain g++ -std=c++17, as model.cpp does, so that tests/host/tables_harness.cpp runs
 // it under the sanitizers on a machine without a GPU. A refusal is a thrown Refusal whose text is the C-ABI's message, whole.
 #pragma once
@@ -18,6 +18,7 @@ struct float4;
 #include "model.hpp"
 #include "motion_limits.h"
 #include "observation_limits.h"
+#include "policy_limits.h"
 #include "proximity_limits.h"
 #include "reward_limits.h"
 #include "sensing_limits.h"
@@ -191,6 +192,35 @@ MonitorLayout monitor_layout(int n_envs, int window, int cols_a, int cols_b, uin
 // trex_batch_monitor_apply: the strides against the widths; the pointers as "is it there" flags
 void check_monitor_apply(const MonitorLayout &m, bool reward, int reward_stride, bool done, int done_stride, bool block_a, int stride_a,
                          bool block_b, int stride_b);
+
+// The trainer (include/trex_policy.h, trex_policy_critic.h, trex_policy_distill.h): what its C-ABI refuses before any HIP call, as
+// functions of sizes, strides and of which pointers are there (a bool per pointer, or one for "all that the call requires").
+// PolicyShape is the policy as the checks see it - env count, widths (Dv 0: no critic), parameter layout -; a null one is refused
+// by every check that takes it, with the call's own words. The first refusal of a call that is wrong twice is the one listed first.
+struct PolicyShape { int n = 0, D = 0, A = 0, Dv = 0; trex_policy::PolicyLayout lay{}; };
+void check_policy_create(int num_envs, int obs_dim, int act_dim, int hidden);
+void check_policy_set_critic(const PolicyShape *p, int critic_dim);
+// a call of trex_policy_critic.h that needs a critic: the policy and `arg`, the call's one required pointer, then the width
+void check_policy_has_critic(const char *who, const PolicyShape *p, bool arg);
+void check_policy_observe(const PolicyShape *p, bool rows, int row_stride, bool with_reward);
+void check_policy_critic_observe(const PolicyShape *p, bool rows_v, int stride_v);
+struct PolicyActCall { bool theta, rows, rows_v, noise, actions, value_out, obs_v_out; int row_stride, stride_v; bool value_only; };
+void check_policy_act(const PolicyShape *p, const PolicyActCall &c);          // (rows_v, obs_v_out, stride_v: not looked at)
+void check_policy_critic_act(const PolicyShape *p, const PolicyActCall &c);
+void check_policy_gae(const PolicyShape *p, bool buffers, int T);
+void check_policy_minibatch_stats(const PolicyShape *p, bool buffers, int num_minibatches, int mb, int64_t num_samples);
+// one of the six minibatch entry points. critic: an entry point of trex_policy_critic.h (it passes obs_v); distill: one of
+// trex_policy_distill.h, whose kind, teacher_logstd, teacher_value and vf_coef are looked at for it alone
+struct PolicyMinibatchCall {
+  const char *who;
+  bool distill, critic, buffers;
+  int mb, first;
+  int64_t num_samples;
+  int kind;
+  bool teacher_logstd, teacher_value;
+  float vf_coef;
+};
+void check_policy_minibatch(const PolicyShape *p, const PolicyMinibatchCall &c);
 
 // trex_batch_render: the camera of include/trex_batch.h, checked, as the renderer's basis
 struct CameraBasis { float offset[3], fwd[3], right[3], up[3], tan_x, tan_y; };

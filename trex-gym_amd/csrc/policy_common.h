@@ -1,41 +1,16 @@
-// Shared by policy_step.hip and ppo_learner.hip (the trainer-side kernels of include/trex_policy.h).
+// What policy_step.hip and ppo_learner.hip (the trainer-side kernels of include/trex_policy.h) share on the device.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <string>
-#include <vector>
-
-#include "../../include/trex_batch.h"
-#include "internal.hpp"
+#include "policy_launch.h"
 
 namespace {
 
+using namespace trex_policy;   // the limits and the parameter layout (policy_limits.h)
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int HID = 64;        // hidden width (two 32-row MFMA tiles)
-constexpr int TILE = 32;       // envs per workgroup of act_kernel
-constexpr int MAXD = 128;      // LDS row of the observation tile (obs_dim + pad <= MAXD)
-constexpr int OBS_ROWS = 64;   // rows per workgroup of observe_kernel
 constexpr float LOG_2PI = 1.8378770664093453f;
-
-struct Layout {   // offsets into theta, trex_policy.h order (D: the policy net's input width; a critic's own width Dv only
-  int D, A;       // sizes vf.W1 and travels beside the layout: include/trex_policy_critic.h)
-  int pW1, pb1, pW2, pb2, pW3, pb3, vW1, vb1, vW2, vb2, vW3, vb3, logstd, count;
-};
-
-__host__ __device__ inline Layout make_layout(int D, int A, int Dv = 0) {      // Dv = 0: the value net reads the policy's row
-  // every region starts on a multiple of 4 floats (16-byte loads when the kernels stage the parameters in LDS); the
-  // pad elements are ordinary, unused parameters: zero gradient, never read
-  Layout l{};
-  l.D = D; l.A = A;
-  int o = 0;
-  auto take = [&](int n) { const int at = o; o = (o + n + 3) & ~3; return at; };
-  l.pW1 = take(D * HID); l.pb1 = take(HID); l.pW2 = take(HID * HID); l.pb2 = take(HID); l.pW3 = take(HID * A); l.pb3 = take(A);
-  l.vW1 = take((Dv ? Dv : D) * HID); l.vb1 = take(HID); l.vW2 = take(HID * HID); l.vb2 = take(HID); l.vW3 = take(HID); l.vb3 = take(1);
-  l.logstd = take(A);
-  l.count = o;
-  return l;
-}
 
 // tanh in ~10 instructions, |error| <= 2e-7 absolute (libm's tanhf expands to ~50 with branches; the policy step
 // evaluates 128 per lane): 1 - 2 / (exp(2|x|) + 1) away from 0, the odd series below |x| = 0.1 where that form cancels
@@ -82,36 +57,3 @@ __device__ __forceinline__ void adam_moments(float g, float b1, float b2, float 
 __device__ __forceinline__ constexpr int rowmap(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 }  // namespace
-
-struct TrexPolicy {
-  int n = 0, D = 0, A = 0, device = 0, G = 0;
-  Layout lay{};
-  double *stats = nullptr, *partial = nullptr;
-  float *norm = nullptr, *ret = nullptr;
-  unsigned *counter = nullptr;
-  int *adam_step = nullptr;
-  float epsilon = 1e-8f;        // VecNormalize's
-  // privileged critic (include/trex_policy_critic.h): Dv = 0 is none. Its moments have the observation block's shape - mean [Dv],
-  // var [Dv], count, then four slots the statistics kernels never touch without a reward -, with partial sums and an f32 image of
-  // their own; all three are allocated once, for the widest critic, by the first set
-  int Dv = 0;
-  double *stats_v = nullptr, *partial_v = nullptr;
-  float *norm_v = nullptr;
-  // learner workspace (ppo_learner.hip), allocated on first use: per-tile gradient partials [tiles][count4]
-  float *grad_partial = nullptr;
-  int grad_tiles = 0;
-  unsigned *learn_counter = nullptr;
-  double *learn_red = nullptr;
-  std::vector<void *> allocs;
-  std::vector<TrexSeen> seen;
-};
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) return trex_fail(TREX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-#define BUF_TRY(ptr, bytes, what)                                                                       \
-  do {                                                                                                  \
-    if (int _c = trex_check_device_buffer(p->device, p->seen, (ptr), (size_t)(bytes), (what))) return _c; \
-  } while (0)

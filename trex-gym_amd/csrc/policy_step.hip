@@ -22,36 +22,14 @@
 #include <stdint.h>
 
 #include <cmath>
-#include <cstring>
-#include <memory>
-#include <string>
 #include <type_traits>
-#include <vector>
 
-#include "../../include/trex_batch.h"
-#include "../../include/trex_policy.h"
-#include "internal.hpp"
 #include "policy_common.h"
 
 namespace {
 
 // ---------------------------------------------------------------- act
-struct ActArgs {
-  const float *theta, *rows, *norm, *noise;
-  float *actions, *obs_out, *act_out, *logp_out, *value_out;
-  int n, row_stride, value_only;
-  float clip_obs;
-  Layout lay;
-};
-// With a privileged critic (include/trex_policy_critic.h) the value net has a row block, a width, moments and a rollout copy of its
-// own: a per-net choice of pointers and of D in the vf workgroups (CRITIC = true). The plain launch is the CRITIC = false instantiation,
-// whose argument block and instructions are the ones it had before the template (profiles/r31_critic.txt).
-struct ActArgsV : ActArgs {
-  const float *rows_v, *norm_v;
-  float *obs_v_out;
-  int stride_v, Dv;
-};
-
+// (the argument blocks ActArgs / ActArgsV: policy_launch.h)
 // One workgroup = (tile of 32 envs, net): 2 waves, each owning one HALF of the 64 neurons of a hidden layer (u = wave: 32
 // output rows = one MFMA tile); grid (tiles, 2) = 256 workgroups at 4096 envs - the whole chip (until round 4: 64 workgroups of
 // four waves, a wave running one net of one tile alone: 22.8 us, 176 MFMAs in a row on 64 CUs). The layers are the learner's
@@ -63,7 +41,7 @@ struct ActArgsV : ActArgs {
 constexpr int ACT_UF = 29;             // float4s of theta per thread of the staging trip (128 threads: obs_dim <= 126, actions <= 32)
 constexpr int ACT_UX = 32;             // observation elements per thread (32 rows x <= 128 columns)
 constexpr int ACT_XS = MAXD + 1, ACT_TS = TILE + 1;
-__host__ __device__ inline int act_lds_floats(const Layout &lay) {
+__host__ __device__ inline int act_lds_floats(const PolicyLayout &lay) {
   return ((lay.count + 3) & ~3) + TILE * ACT_XS + 2 * HID * ACT_TS + 32;      // theta image | X | H1, H2 parked | sd per action
 }
 template <bool CRITIC>
@@ -256,17 +234,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 
 // ---------------------------------------------------------------- observe (VecNormalize)
-// stats (f64): [0, D) obs mean, [D, 2D) obs var, [2D] obs count, [2D+1] ret mean, [2D+2] ret var, [2D+3] ret count,
-//              [2D+4] sum of raw rewards.  norm (f32): [0, D) mean, [D, 2D) 1/sqrt(var + eps), [2D] reward scale.
-struct ObserveArgs {
-  const float *rows;
-  double *stats, *partial;     // partial [G][D + 2][2]: per workgroup and column: sum and sum of squares about the running mean
-  float *norm, *ret, *raw_rew_out, *done_out, *rew_scale_out;
-  unsigned *counter;
-  int n, row_stride, D, with_reward;
-  float gamma, epsilon;
-};
-
+// (the argument block ObserveArgs and the layout of the statistics: policy_launch.h)
 // One workgroup = OBS_ROWS rows x 4 row groups of 128 threads (thread c of a group: column c); every thread takes 8 rows
 // per trip with the 8 loads in flight together. (Version 1 walked 64 rows one dependent load after the other and merged
 // 64 partials the same way: 48 us per launch.)
@@ -468,311 +436,39 @@ __global__ __launch_bounds__(1024) void adam_kernel(float *theta, float *grad, f
 
 }  // namespace
 
-// ---------------------------------------------------------------- C-ABI
-namespace {
-int init_stats(TrexPolicy *p, hipStream_t s) {
-  // RunningMeanStd(epsilon = 1e-4): mean 0, var 1, count 1e-4 (both)
-  std::vector<double> st(2 * p->D + 5, 0.0);
-  for (int k = 0; k < p->D; k++) st[p->D + k] = 1.0;
-  st[2 * p->D] = 1e-4; st[2 * p->D + 2] = 1.0; st[2 * p->D + 3] = 1e-4;
-  HIP_TRY(hipMemcpyAsync(p->stats, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  hipLaunchKernelGGL(refresh_norm_kernel, dim3(1), dim3(128), 0, s, p->stats, p->norm, p->D, p->epsilon);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int trex_policy_create(int num_envs, int obs_dim, int act_dim, int hidden, int device, TrexPolicy **out) {
-  if (!out) return trex_fail(TREX_E_INVALID, "trex_policy_create: null argument");
-  *out = nullptr;
-  if (num_envs <= 0) return trex_fail(TREX_E_INVALID, "num_envs must be positive");
-  if (hidden != HID) return trex_fail(TREX_E_UNSUPPORTED, "the policy kernel is written for hidden = 64 (baselines' MlpPolicy)");
-  if (act_dim < 1 || act_dim > 32) return trex_fail(TREX_E_UNSUPPORTED, "act_dim must be in [1, 32]");
-  if (obs_dim < 1 || obs_dim > MAXD - 2) return trex_fail(TREX_E_UNSUPPORTED, "obs_dim must be in [1, 126]");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return trex_fail(TREX_E_HIP, "no HIP device available (the policy step has no CPU fallback)");
-  if (device < 0 || device >= count) return trex_fail(TREX_E_INVALID, "device index out of range");
-  TrexDeviceGuard guard(device);
-  if (!guard.ok) return trex_fail(TREX_E_HIP, "hipSetDevice failed");
-  auto p = std::make_unique<TrexPolicy>();
-  p->n = num_envs; p->D = obs_dim; p->A = act_dim; p->device = device;
-  p->G = (num_envs + OBS_ROWS - 1) / OBS_ROWS;
-  p->lay = make_layout(obs_dim, act_dim);
-  hipError_t r = hipSuccess;
-  auto A = [&](size_t bytes, void **q) {
-    if (r != hipSuccess) return;
-    r = hipMalloc(q, bytes);
-    if (r == hipSuccess) { p->allocs.push_back(*q); r = hipMemset(*q, 0, bytes); }
-  };
-  A((2 * obs_dim + 5) * sizeof(double), (void **)&p->stats);
-  A((size_t)p->G * (obs_dim + 2) * 2 * sizeof(double), (void **)&p->partial);
-  A((2 * obs_dim + 2) * sizeof(float), (void **)&p->norm);
-  A((size_t)num_envs * sizeof(float), (void **)&p->ret);
-  A(sizeof(unsigned), (void **)&p->counter);
-  A(sizeof(int), (void **)&p->adam_step);
-  if (r != hipSuccess) {
-    for (void *q : p->allocs) (void)hipFree(q);
-    return trex_fail(TREX_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(r));
-  }
-  if (int c = init_stats(p.get(), nullptr)) { for (void *q : p->allocs) (void)hipFree(q); return c; }
-  HIP_TRY(hipDeviceSynchronize());
-  *out = p.release();
-  return TREX_OK;
+// ---------------------------------------------------------------- launchers (policy_launch.h)
+extern "C" hipError_t trex_launch_policy_act(const ActArgs &args, hipStream_t stream) {
+  const size_t lds_bytes = (size_t)act_lds_floats(args.lay) * sizeof(float);
+  hipLaunchKernelGGL(act_kernel<false>, dim3((args.n + TILE - 1) / TILE, 2), dim3(128), lds_bytes, stream, args);
+  return hipGetLastError();
 }
 
-void trex_policy_destroy(TrexPolicy *p) {
-  if (!p) return;
-  TrexDeviceGuard guard(p->device);
-  (void)hipDeviceSynchronize();
-  for (void *q : p->allocs) (void)hipFree(q);
-  delete p;
+extern "C" hipError_t trex_launch_policy_critic_act(const ActArgsV &args, hipStream_t stream) {
+  const size_t lds_bytes = (size_t)act_lds_floats(args.lay) * sizeof(float);
+  hipLaunchKernelGGL(act_kernel<true>, dim3((args.n + TILE - 1) / TILE, args.rows_v ? 2 : 1), dim3(128), lds_bytes, stream, args);
+  return hipGetLastError();
 }
 
-int trex_policy_param_count(const TrexPolicy *p) { return p ? p->lay.count : trex_fail(TREX_E_INVALID, "null policy"); }
-
-int trex_policy_param_offsets(const TrexPolicy *p, int o[13]) {
-  if (!p || !o) return trex_fail(TREX_E_INVALID, "null argument");
-  const Layout &l = p->lay;
-  const int v[13] = {l.pW1, l.pb1, l.pW2, l.pb2, l.pW3, l.pb3, l.vW1, l.vb1, l.vW2, l.vb2, l.vW3, l.vb3, l.logstd};
-  std::memcpy(o, v, sizeof v);
-  return TREX_OK;
+extern "C" hipError_t trex_launch_policy_observe(const ObserveArgs &args, hipStream_t stream) {
+  const int G = (args.n + OBS_ROWS - 1) / OBS_ROWS;
+  hipLaunchKernelGGL(observe_kernel<false>, dim3(G), dim3(128 * OBS_GROUPS), 0, stream, args, G);
+  hipLaunchKernelGGL(observe_kernel<true>, dim3(1), dim3(128 * OBS_GROUPS), 0, stream, args, G);
+  return hipGetLastError();
 }
 
-int trex_policy_get_stats(TrexPolicy *p, double *host, void *stream) {
-  if (!p || !host) return trex_fail(TREX_E_INVALID, "null argument");
-  TrexDeviceGuard guard(p->device);
-  HIP_TRY(hipMemcpyAsync(host, p->stats, (2 * p->D + 5) * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return TREX_OK;
+extern "C" hipError_t trex_launch_policy_refresh_norm(const double *stats, float *norm, int D, float epsilon, hipStream_t stream) {
+  hipLaunchKernelGGL(refresh_norm_kernel, dim3(1), dim3(128), 0, stream, stats, norm, D, epsilon);
+  return hipGetLastError();
 }
 
-int trex_policy_set_stats(TrexPolicy *p, const double *host, void *stream) {
-  if (!p || !host) return trex_fail(TREX_E_INVALID, "null argument");
-  TrexDeviceGuard guard(p->device);
-  HIP_TRY(hipMemcpyAsync(p->stats, host, (2 * p->D + 5) * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  hipLaunchKernelGGL(refresh_norm_kernel, dim3(1), dim3(128), 0, (hipStream_t)stream, p->stats, p->norm, p->D, p->epsilon);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
+extern "C" hipError_t trex_launch_policy_gae(const GaeArgs &a, hipStream_t stream) {
+  hipLaunchKernelGGL(gae_kernel, dim3((a.n + 255) / 256), dim3(256), 0, stream, a.raw_rew, a.scale, a.done, a.val, a.adv, a.ret, a.T, a.n,
+                     a.gamma, a.lam, a.clip_rew);
+  return hipGetLastError();
 }
 
-int trex_policy_get_returns(TrexPolicy *p, float *ret_dev, void *stream) {
-  if (!p || !ret_dev) return trex_fail(TREX_E_INVALID, "null argument");
-  TrexDeviceGuard guard(p->device);
-  BUF_TRY(ret_dev, (size_t)p->n * sizeof(float), "trex_policy_get_returns: ret");
-  HIP_TRY(hipMemcpyAsync(ret_dev, p->ret, (size_t)p->n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return TREX_OK;
+extern "C" hipError_t trex_launch_policy_adam(const AdamArgs &a, hipStream_t stream) {
+  hipLaunchKernelGGL(adam_kernel, dim3(1), dim3(1024), 0, stream, a.theta, a.grad, a.m, a.v, a.P, a.step, a.lr, a.b1, a.b2, a.eps, a.max_norm,
+                     a.norm_out);
+  return hipGetLastError();
 }
-
-int trex_policy_observe(TrexPolicy *p, const float *rows_dev, int row_stride, int with_reward, float gamma, float *raw_rew_out,
-                        float *done_out, float *rew_scale_out, void *stream) {
-  if (!p || !rows_dev) return trex_fail(TREX_E_INVALID, "trex_policy_observe: null argument");
-  if (row_stride < p->D + (with_reward ? 2 : 0)) return trex_fail(TREX_E_INVALID, "trex_policy_observe: row_stride too small");
-  TrexDeviceGuard guard(p->device);
-  const size_t n = (size_t)p->n;
-  BUF_TRY(rows_dev, ((n - 1) * row_stride + p->D + (with_reward ? 2 : 0)) * sizeof(float), "trex_policy_observe: rows");
-  BUF_TRY(raw_rew_out, n * sizeof(float), "trex_policy_observe: raw_rew_out");
-  BUF_TRY(done_out, n * sizeof(float), "trex_policy_observe: done_out");
-  BUF_TRY(rew_scale_out, sizeof(float), "trex_policy_observe: rew_scale_out");
-  ObserveArgs a{rows_dev, p->stats, p->partial, p->norm, p->ret, raw_rew_out, done_out, rew_scale_out, p->counter,
-                p->n, row_stride, p->D, with_reward ? 1 : 0, gamma, p->epsilon};
-  hipLaunchKernelGGL(observe_kernel<false>, dim3(p->G), dim3(128 * OBS_GROUPS), 0, (hipStream_t)stream, a, p->G);
-  hipLaunchKernelGGL(observe_kernel<true>, dim3(1), dim3(128 * OBS_GROUPS), 0, (hipStream_t)stream, a, p->G);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
-}
-
-int trex_policy_act(TrexPolicy *p, const float *theta_dev, const float *rows_dev, int row_stride, float clip_obs,
-                    const float *noise_dev, float *actions_dev, float *obs_out, float *act_out, float *logp_out, float *value_out,
-                    int value_only, void *stream) {
-  if (!p || !theta_dev || !rows_dev) return trex_fail(TREX_E_INVALID, "trex_policy_act: null argument");
-  if (p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_act: the policy has a critic width set (trex_policy_critic_act takes its row)");
-  if (!value_only && (!noise_dev || !actions_dev)) return trex_fail(TREX_E_INVALID, "trex_policy_act: noise / actions are null");
-  if (value_only && !value_out) return trex_fail(TREX_E_INVALID, "trex_policy_act: value_out is null");
-  if (row_stride < p->D) return trex_fail(TREX_E_INVALID, "trex_policy_act: row_stride < obs_dim");
-  TrexDeviceGuard guard(p->device);
-  const size_t n = (size_t)p->n;
-  BUF_TRY(theta_dev, (size_t)p->lay.count * sizeof(float), "trex_policy_act: theta");
-  BUF_TRY(rows_dev, ((n - 1) * row_stride + p->D) * sizeof(float), "trex_policy_act: rows");
-  BUF_TRY(noise_dev, n * p->A * sizeof(float), "trex_policy_act: noise");
-  BUF_TRY(actions_dev, n * p->A * sizeof(float), "trex_policy_act: actions");
-  BUF_TRY(obs_out, n * p->D * sizeof(float), "trex_policy_act: obs_out");
-  BUF_TRY(act_out, n * p->A * sizeof(float), "trex_policy_act: act_out");
-  BUF_TRY(logp_out, n * sizeof(float), "trex_policy_act: logp_out");
-  BUF_TRY(value_out, n * sizeof(float), "trex_policy_act: value_out");
-  ActArgs a{theta_dev, rows_dev, p->norm, noise_dev, actions_dev, obs_out, act_out, logp_out, value_out,
-            p->n, row_stride, value_only ? 1 : 0, clip_obs, p->lay};
-  const size_t lds_bytes = (size_t)act_lds_floats(p->lay) * sizeof(float);
-  hipLaunchKernelGGL(act_kernel<false>, dim3((p->n + TILE - 1) / TILE, 2), dim3(128), lds_bytes, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
-}
-
-// ---------------------------------------------------------------- privileged critic (include/trex_policy_critic.h)
-int trex_policy_set_critic(TrexPolicy *p, int critic_dim, void *stream) {
-  if (!p) return trex_fail(TREX_E_INVALID, "trex_policy_set_critic: null policy");
-  if (critic_dim < 0 || critic_dim > MAXD - 2) return trex_fail(TREX_E_INVALID, "trex_policy_set_critic: critic_dim must be in [0, 126] (0 clears)");
-  TrexDeviceGuard guard(p->device);
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  HIP_TRY(hipDeviceSynchronize());
-  if (critic_dim && !p->stats_v) {      // once, for the widest critic: a later set never allocates
-    constexpr int W = MAXD - 2;
-    double *st = nullptr, *pa = nullptr;
-    float *nm = nullptr;
-    hipError_t r = hipMalloc((void **)&st, (2 * W + 5) * sizeof(double));
-    if (r == hipSuccess) r = hipMalloc((void **)&pa, (size_t)p->G * (W + 2) * 2 * sizeof(double));
-    if (r == hipSuccess) r = hipMalloc((void **)&nm, (2 * W + 2) * sizeof(float));
-    if (r != hipSuccess) {
-      (void)hipFree(st); (void)hipFree(pa); (void)hipFree(nm);
-      return trex_fail(TREX_E_HIP, std::string("trex_policy_set_critic: hipMalloc: ") + hipGetErrorString(r));
-    }
-    p->stats_v = st; p->partial_v = pa; p->norm_v = nm;
-    p->allocs.push_back(st); p->allocs.push_back(pa); p->allocs.push_back(nm);
-  }
-  // the learner workspace's row stride is the parameter count: dropped, the next minibatch call makes its own
-  if (p->grad_partial) {
-    for (size_t i = 0; i < p->allocs.size(); i++)
-      if (p->allocs[i] == p->grad_partial) { p->allocs.erase(p->allocs.begin() + i); break; }
-    (void)hipFree(p->grad_partial);
-    p->grad_partial = nullptr; p->grad_tiles = 0;
-  }
-  p->Dv = critic_dim;
-  p->lay = make_layout(p->D, p->A, critic_dim);
-  if (critic_dim) {
-    const int Dv = critic_dim;
-    std::vector<double> st(2 * Dv + 5, 0.0);          // RunningMeanStd(epsilon = 1e-4), as init_stats
-    for (int k = 0; k < Dv; k++) st[Dv + k] = 1.0;
-    st[2 * Dv] = 1e-4; st[2 * Dv + 2] = 1.0; st[2 * Dv + 3] = 1e-4;
-    HIP_TRY(hipMemcpy(p->stats_v, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(refresh_norm_kernel, dim3(1), dim3(128), 0, (hipStream_t)stream, p->stats_v, p->norm_v, Dv, p->epsilon);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  }
-  return TREX_OK;
-}
-
-int trex_policy_critic_dim(const TrexPolicy *p) { return p ? p->Dv : trex_fail(TREX_E_INVALID, "null policy"); }
-
-int trex_policy_critic_get_stats(TrexPolicy *p, double *host, void *stream) {
-  if (!p || !host) return trex_fail(TREX_E_INVALID, "trex_policy_critic_get_stats: null argument");
-  if (!p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_critic_get_stats: no critic width is set (trex_policy_set_critic)");
-  TrexDeviceGuard guard(p->device);
-  HIP_TRY(hipMemcpyAsync(host, p->stats_v, (2 * p->Dv + 1) * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  return TREX_OK;
-}
-
-int trex_policy_critic_set_stats(TrexPolicy *p, const double *host, void *stream) {
-  if (!p || !host) return trex_fail(TREX_E_INVALID, "trex_policy_critic_set_stats: null argument");
-  if (!p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_critic_set_stats: no critic width is set (trex_policy_set_critic)");
-  TrexDeviceGuard guard(p->device);
-  HIP_TRY(hipMemcpyAsync(p->stats_v, host, (2 * p->Dv + 1) * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  hipLaunchKernelGGL(refresh_norm_kernel, dim3(1), dim3(128), 0, (hipStream_t)stream, p->stats_v, p->norm_v, p->Dv, p->epsilon);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
-}
-
-// The observation statistics' two launches on the critic's block, with_reward = 0. Read in observe_kernel above: without a reward
-// the only loads from the rows are `g.rows[r * row_stride + c]` under `c < D` (the thread c == D is gated by with_reward), the
-// return buffer, the reward sum and slots [2 D + 1, 2 D + 5) of the statistics are written under with_reward alone, and the three
-// optional outputs are never touched - so pointed at (stats_v, partial_v, norm_v, Dv) they read columns [0, Dv) and nothing else.
-int trex_policy_critic_observe(TrexPolicy *p, const float *rows_v_dev, int stride_v, void *stream) {
-  if (!p || !rows_v_dev) return trex_fail(TREX_E_INVALID, "trex_policy_critic_observe: null argument");
-  if (!p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_critic_observe: no critic width is set (trex_policy_set_critic)");
-  if (stride_v < p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_critic_observe: stride_v < critic_dim");
-  TrexDeviceGuard guard(p->device);
-  const size_t n = (size_t)p->n;
-  BUF_TRY(rows_v_dev, ((n - 1) * stride_v + p->Dv) * sizeof(float), "trex_policy_critic_observe: rows_v");
-  ObserveArgs a{rows_v_dev, p->stats_v, p->partial_v, p->norm_v, nullptr, nullptr, nullptr, nullptr, p->counter,
-                p->n, stride_v, p->Dv, 0, 0.f, p->epsilon};
-  hipLaunchKernelGGL(observe_kernel<false>, dim3(p->G), dim3(128 * OBS_GROUPS), 0, (hipStream_t)stream, a, p->G);
-  hipLaunchKernelGGL(observe_kernel<true>, dim3(1), dim3(128 * OBS_GROUPS), 0, (hipStream_t)stream, a, p->G);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
-}
-
-int trex_policy_critic_act(TrexPolicy *p, const float *theta_dev, const float *rows_dev, int row_stride, const float *rows_v_dev,
-                           int stride_v, float clip_obs, const float *noise_dev, float *actions_dev, float *obs_out, float *obs_v_out,
-                           float *act_out, float *logp_out, float *value_out, int value_only, void *stream) {
-  if (!p || !theta_dev) return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: null argument");
-  if (!p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: no critic width is set (trex_policy_set_critic)");
-  if (value_only) {
-    if (!rows_v_dev || !value_out) return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: value_only needs rows_v and value_out");
-  } else {
-    if (!rows_dev || !noise_dev || !actions_dev) return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: rows / noise / actions are null");
-    if (!rows_v_dev && (value_out || obs_v_out))
-      return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: without rows_v only the policy runs: value_out and obs_v_out must be null");
-  }
-  if (rows_dev && row_stride < p->D) return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: row_stride < obs_dim");
-  if (rows_v_dev && stride_v < p->Dv) return trex_fail(TREX_E_INVALID, "trex_policy_critic_act: stride_v < critic_dim");
-  TrexDeviceGuard guard(p->device);
-  const size_t n = (size_t)p->n;
-  BUF_TRY(theta_dev, (size_t)p->lay.count * sizeof(float), "trex_policy_critic_act: theta");
-  BUF_TRY(rows_dev, ((n - 1) * row_stride + p->D) * sizeof(float), "trex_policy_critic_act: rows");
-  BUF_TRY(rows_v_dev, ((n - 1) * stride_v + p->Dv) * sizeof(float), "trex_policy_critic_act: rows_v");
-  BUF_TRY(noise_dev, n * p->A * sizeof(float), "trex_policy_critic_act: noise");
-  BUF_TRY(actions_dev, n * p->A * sizeof(float), "trex_policy_critic_act: actions");
-  BUF_TRY(obs_out, n * p->D * sizeof(float), "trex_policy_critic_act: obs_out");
-  BUF_TRY(obs_v_out, n * p->Dv * sizeof(float), "trex_policy_critic_act: obs_v_out");
-  BUF_TRY(act_out, n * p->A * sizeof(float), "trex_policy_critic_act: act_out");
-  BUF_TRY(logp_out, n * sizeof(float), "trex_policy_critic_act: logp_out");
-  BUF_TRY(value_out, n * sizeof(float), "trex_policy_critic_act: value_out");
-  // (value_only never reads the policy's row and writes the values alone: the pi workgroups return at once)
-  ActArgsV a{};
-  static_cast<ActArgs &>(a) = ActArgs{theta_dev, rows_dev, p->norm, noise_dev, actions_dev, value_only ? nullptr : obs_out, act_out, logp_out,
-                                     value_out, p->n, row_stride, value_only ? 1 : 0, clip_obs, p->lay};
-  a.rows_v = rows_v_dev; a.norm_v = p->norm_v; a.obs_v_out = value_only ? nullptr : obs_v_out; a.stride_v = stride_v; a.Dv = p->Dv;
-  const size_t lds_bytes = (size_t)act_lds_floats(p->lay) * sizeof(float);
-  hipLaunchKernelGGL(act_kernel<true>, dim3((p->n + TILE - 1) / TILE, rows_v_dev ? 2 : 1), dim3(128), lds_bytes, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
-}
-
-int trex_policy_gae(TrexPolicy *p, const float *raw_rew_dev, const float *rew_scale_dev, const float *done_dev,
-                    const float *values_dev, float *adv_dev, float *ret_dev, int T, float gamma, float lam, float clip_rew,
-                    void *stream) {
-  if (!p || !raw_rew_dev || !rew_scale_dev || !done_dev || !values_dev || !adv_dev || !ret_dev || T <= 0)
-    return trex_fail(TREX_E_INVALID, "trex_policy_gae: bad argument");
-  TrexDeviceGuard guard(p->device);
-  const size_t n = (size_t)p->n, tn = (size_t)T * n * sizeof(float);
-  BUF_TRY(raw_rew_dev, tn, "trex_policy_gae: raw_rew");
-  BUF_TRY(rew_scale_dev, (size_t)T * sizeof(float), "trex_policy_gae: rew_scale");
-  BUF_TRY(done_dev, tn, "trex_policy_gae: done");
-  BUF_TRY(values_dev, tn + n * sizeof(float), "trex_policy_gae: values");
-  BUF_TRY(adv_dev, tn, "trex_policy_gae: adv");
-  BUF_TRY(ret_dev, tn, "trex_policy_gae: ret");
-  hipLaunchKernelGGL(gae_kernel, dim3((p->n + 255) / 256), dim3(256), 0, (hipStream_t)stream, raw_rew_dev, rew_scale_dev, done_dev,
-                     values_dev, adv_dev, ret_dev, T, p->n, gamma, lam, clip_rew);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
-}
-
-int trex_policy_adam(TrexPolicy *p, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev, float lr, float beta1,
-                     float beta2, float eps, float max_grad_norm, float *grad_norm_out, void *stream) {
-  if (!p || !theta_dev || !grad_dev || !m_dev || !v_dev) return trex_fail(TREX_E_INVALID, "trex_policy_adam: null argument");
-  TrexDeviceGuard guard(p->device);
-  const size_t bytes = (size_t)p->lay.count * sizeof(float);
-  BUF_TRY(theta_dev, bytes, "trex_policy_adam: theta");
-  BUF_TRY(grad_dev, bytes, "trex_policy_adam: grad");
-  BUF_TRY(m_dev, bytes, "trex_policy_adam: m");
-  BUF_TRY(v_dev, bytes, "trex_policy_adam: v");
-  BUF_TRY(grad_norm_out, sizeof(float), "trex_policy_adam: grad_norm_out");
-  hipLaunchKernelGGL(adam_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, theta_dev, grad_dev, m_dev, v_dev, p->lay.count,
-                     p->adam_step, lr, beta1, beta2, eps, max_grad_norm, grad_norm_out);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
-}
-
-int trex_policy_adam_reset(TrexPolicy *p, void *stream) {
-  if (!p) return trex_fail(TREX_E_INVALID, "null policy");
-  TrexDeviceGuard guard(p->device);
-  HIP_TRY(hipMemsetAsync(p->adam_step, 0, sizeof(int), (hipStream_t)stream));
-  return TREX_OK;
-}
-
-}  // extern "C"

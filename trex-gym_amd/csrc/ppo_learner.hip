@@ -31,7 +31,6 @@
 
 namespace {
 
-constexpr int LEARN_UF = 13;           // float4s of theta per thread of learn_grad_kernel's staging trip
 constexpr int W2S = HID + 1;           // LDS row stride of W2 (transposed reads in the backward pass)
 constexpr int XS = MAXD + 1;           // LDS row stride of the observation tile
 constexpr int TS = TILE + 1;           // LDS row stride of the [row][env] transposition buffers
@@ -42,7 +41,7 @@ constexpr int TS = TILE + 1;           // LDS row stride of the [row][env] trans
 struct LdsLayout {
   int X, buf, vec, total;      // observation tile; parked tiles; small vectors; floats in all
 };
-__host__ __device__ inline LdsLayout make_lds_layout(const Layout &lay) {
+__host__ __device__ inline LdsLayout make_lds_layout(const PolicyLayout &lay) {
   LdsLayout l{};
   int o = lay.count + 2 * HID;                         // theta + the pad words of the two W2s
   o = (o + 3) & ~3;
@@ -53,37 +52,18 @@ __host__ __device__ inline LdsLayout make_lds_layout(const Layout &lay) {
   return l;
 }
 // LDS offset of the global parameter at offset i (i a multiple of 4 for the float4 path: a float4 never crosses a W2 row)
-__device__ __forceinline__ int lds_of(const Layout &lay, int i) {
+__device__ __forceinline__ int lds_of(const PolicyLayout &lay, int i) {
   int o = i;
   if (i >= lay.pW2) o += (i < lay.pb2) ? (i - lay.pW2) / HID : HID;
   if (i >= lay.vW2) o += (i < lay.vb2) ? (i - lay.vW2) / HID : HID;
   return o;
 }
 
-struct LearnArgs {
-  const float *theta, *obs, *act, *logp0, *val0, *adv, *ret;
-  const long long *perm;
-  const float *adv_stats;      // [2]: mean and 1 / (std + 1e-8) of the minibatch's advantages
-  float *partial;              // [tiles][stride]
-  int first, mb, stride;
-  float cliprange, vf_coef;
-  Layout lay;
-};
-// With a privileged critic (include/trex_policy_critic.h) the vf workgroups read a rollout buffer and a width of their own (CRITIC =
-// true); the plain launch is the CRITIC = false instantiation, the kernel as it was before the template (profiles/r31_critic.txt).
-struct LearnArgsV : LearnArgs {
-  const float *obs_v;
-  int Dv;
-};
+// (the argument blocks LearnArgs / LearnArgsV / LearnArgsD: policy_launch.h)
 // The loss at the output layer is a template parameter beside CRITIC: LOSS_PPO is the clipped surrogate + clipped value loss, the
 // head as it was before that parameter (profiles/r34_distill.txt); LOSS_DISTILL (include/trex_policy_distill.h) regresses onto a
 // teacher - `act` carries the teacher's mean, `ret` its value, and logp0 / val0 / adv / adv_stats are null and never loaded.
 constexpr int LOSS_PPO = 0, LOSS_DISTILL = 1;
-struct LearnArgsD : LearnArgs {
-  const float *teacher_logstd;   // [A] (MSE: any A readable floats, not used)
-  int kind;                      // TREX_DISTILL_MSE / _KL
-  int has_value;                 // 0: `ret` is a stand-in address, the value head's target is its own output
-};
 template <bool CRITIC, int LOSS>
 using LearnArgsOf = std::conditional_t<LOSS == LOSS_DISTILL, LearnArgsD, std::conditional_t<CRITIC, LearnArgsV, LearnArgs>>;
 __device__ __forceinline__ int net_D(const LearnArgs &g, int) { return g.lay.D; }
@@ -589,18 +569,7 @@ __global__ __launch_bounds__(1024) void adv_stats_kernel(const float *adv, const
 }
 
 // ---------------------------------------------------------------- partial sums -> gradient -> clip -> Adam
-struct ApplyArgs {
-  const float *partial;
-  float *theta, *grad, *m, *v, *losses;     // losses [2]: running sums of the surrogate / value loss MEANS per minibatch
-  double *red;                              // [workgroups] partial squared norms
-  unsigned *counter;
-  int *step;
-  int tiles, stride, count, logstd_off, A;
-  float ent_coef, lr, b1, b2, eps, max_norm, inv_mb;
-  float grad_scale;      // the gradient (entropy term included) and the loss sums are multiplied by this: 1 / ranks for a data-parallel step
-  int advance;           // != 0: workgroup 0 advances the Adam step count and forms its step size (the Adam launch follows)
-};
-
+// (the argument block ApplyArgs: policy_launch.h)
 // Two launches (measured in round 4 and not kept: ONE launch with a grid barrier between the column sums and Adam - arrival
 // count + generation word, all 83 workgroups resident - took 21 us against 4.8 + 5.0; and no last-workgroup serial tail: a single workgroup updating 21 k parameters in six dependent trips
 // behind two device-scope fences was most of the old single launch's 31 us):
@@ -609,7 +578,7 @@ struct ApplyArgs {
 //                        the Adam step count
 //   learn_adam_kernel    every workgroup sums the squared norms (workgroup order), clips and updates its 256 float4s
 constexpr int AP_COLS = 64, AP_GROUPS = 8;
-constexpr int LR_SLOT = 4095;          // learn_red[LR_SLOT]: the Adam step size of the current minibatch step (the buffer holds 4096 doubles)
+constexpr int LR_SLOT = LEARN_RED_DOUBLES - 1;      // learn_red[LR_SLOT]: the Adam step size of the current minibatch step
 __global__ __launch_bounds__(AP_COLS * AP_GROUPS) void learn_reduce_kernel(ApplyArgs g) {
   __shared__ float4 part[AP_GROUPS][AP_COLS];
   __shared__ double wred[AP_COLS * AP_GROUPS / 64];
@@ -706,250 +675,41 @@ __global__ __launch_bounds__(256) void learn_adam_kernel(ApplyArgs g, int reduce
 
 }  // namespace
 
-extern "C" {
-
 #if TREX_LEARN_STAMPS
-__attribute__((visibility("default"))) int trex_policy_debug_learn_stamps(unsigned long long *host, int n) {
+extern "C" __attribute__((visibility("default"))) int trex_policy_debug_learn_stamps(unsigned long long *host, int n) {
   return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(learn_stamps), (size_t)n * sizeof(unsigned long long));
 }
 #endif
 
-int trex_policy_minibatch_stats(TrexPolicy *p, const float *adv_dev, int64_t num_samples, const int64_t *perm_dev, int num_minibatches,
-                                int mb, float *stats_out_dev, void *stream) {
-  if (!p || !adv_dev || !perm_dev || !stats_out_dev || num_minibatches <= 0 || mb <= 0 || num_samples <= 0)
-    return trex_fail(TREX_E_INVALID, "trex_policy_minibatch_stats: bad argument");
-  TrexDeviceGuard guard(p->device);
-  BUF_TRY(perm_dev, (size_t)num_minibatches * mb * sizeof(int64_t), "trex_policy_minibatch_stats: perm");
-  BUF_TRY(stats_out_dev, (size_t)num_minibatches * 2 * sizeof(float), "trex_policy_minibatch_stats: stats_out");
-  BUF_TRY(adv_dev, (size_t)num_samples * sizeof(float), "trex_policy_minibatch_stats: adv");
-  hipLaunchKernelGGL(adv_stats_kernel, dim3(num_minibatches), dim3(1024), 0, (hipStream_t)stream, adv_dev,
-                     reinterpret_cast<const long long *>(perm_dev), mb, stats_out_dev);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
+// ---------------------------------------------------------------- launchers (policy_launch.h)
+extern "C" hipError_t trex_launch_policy_adv_stats(const float *adv, const long long *perm, int num_minibatches, int mb, float *out,
+                                                   hipStream_t stream) {
+  hipLaunchKernelGGL(adv_stats_kernel, dim3(num_minibatches), dim3(1024), 0, stream, adv, perm, mb, out);
+  return hipGetLastError();
 }
 
-// ---- what every loss shares on the host: the partial buffer and the launches behind learn_grad_kernel
-static int learn_stride(const TrexPolicy *p) {      // a partial row: the parameters, padded to float4, + one float4 of loss sums
-  return (int)((((size_t)p->lay.count + 3) & ~(size_t)3) + 4);
+template <bool CRITIC, int LOSS>
+static hipError_t launch_learn_grad(const LearnArgsOf<CRITIC, LOSS> &args, hipStream_t stream) {
+  const size_t lds_bytes = (size_t)make_lds_layout(args.lay).total * sizeof(float);
+  hipLaunchKernelGGL((learn_grad_kernel<CRITIC, LOSS>), dim3((args.mb + TILE - 1) / TILE, 2), dim3(256), lds_bytes, stream, args);
+  return hipGetLastError();
 }
-static int learn_workspace(TrexPolicy *p, int tiles, int stride) {
-  if (tiles > p->grad_tiles) {      // workspace, grown on demand (never inside a graph capture: the first call is eager)
-    float *buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&buf, (size_t)tiles * stride * sizeof(float)));
-    p->allocs.push_back(buf);
-    HIP_TRY(hipMemset(buf, 0, (size_t)tiles * stride * sizeof(float)));     // (pad elements are never written: they stay 0)
-    p->grad_partial = buf; p->grad_tiles = tiles;
-    if (!p->learn_counter) {
-      HIP_TRY(hipMalloc((void **)&p->learn_counter, sizeof(unsigned)));
-      p->allocs.push_back(p->learn_counter);
-      HIP_TRY(hipMemset(p->learn_counter, 0, sizeof(unsigned)));
-      HIP_TRY(hipMalloc((void **)&p->learn_red, 4096 * sizeof(double)));
-      p->allocs.push_back(p->learn_red);
-    }
-  }
-  return TREX_OK;
+extern "C" hipError_t trex_launch_policy_learn_grad(const LearnArgs &args, hipStream_t stream) {
+  return launch_learn_grad<false, LOSS_PPO>(args, stream);
 }
-static int launch_reduce(TrexPolicy *p, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev, float *loss_sums_dev, int tiles,
-                         int stride, int mb, float ent_coef, float lr, float beta1, float beta2, float eps, float max_grad_norm,
-                         float grad_scale, int advance, void *stream, ApplyArgs *out_args, int *out_groups) {
-  const int apply_groups = ((stride >> 2) + AP_COLS - 1) / AP_COLS;
-  ApplyArgs b{p->grad_partial, theta_dev, grad_dev, m_dev, v_dev, loss_sums_dev, p->learn_red, p->learn_counter, p->adam_step,
-              tiles, stride, p->lay.count, p->lay.logstd, p->A, ent_coef, lr, beta1, beta2, eps, max_grad_norm, 1.0f / (float)mb,
-              grad_scale, advance};
-  hipLaunchKernelGGL(learn_reduce_kernel, dim3(apply_groups), dim3(AP_COLS * AP_GROUPS), 0, (hipStream_t)stream, b);
-  HIP_TRY(hipGetLastError());
-  if (out_args) *out_args = b;
-  if (out_groups) *out_groups = apply_groups;
-  return TREX_OK;
+extern "C" hipError_t trex_launch_policy_learn_grad_critic(const LearnArgsV &args, hipStream_t stream) {
+  return launch_learn_grad<true, LOSS_PPO>(args, stream);
+}
+extern "C" hipError_t trex_launch_policy_learn_grad_distill(const LearnArgsD &args, hipStream_t stream) {
+  return launch_learn_grad<false, LOSS_DISTILL>(args, stream);
 }
 
-// gradient of one minibatch: learn_grad_kernel + learn_reduce_kernel -> grad_dev (UNclipped, times grad_scale)
-static int launch_minibatch_grad(TrexPolicy *p, const char *who, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev,
-                                 const float *obs_dev, const float *obs_v_dev, const float *act_dev, const float *logp_dev,
-                                 const float *val_dev, const float *adv_dev, const float *ret_dev, int64_t num_samples,
-                                 const int64_t *perm_dev, int first, int mb, const float *adv_stats_dev, float cliprange, float ent_coef, float vf_coef, float lr,
-                                 float beta1, float beta2, float eps, float max_grad_norm, float grad_scale, int advance,
-                                 float *loss_sums_dev, void *stream, ApplyArgs *out_args, int *out_groups) {
-  if (!p || !theta_dev || !grad_dev || !obs_dev || !act_dev || !logp_dev || !val_dev || !adv_dev || !ret_dev || !perm_dev || !adv_stats_dev)
-    return trex_fail(TREX_E_INVALID, std::string(who) + ": null argument");
-  if (mb <= 0 || first < 0 || num_samples <= 0) return trex_fail(TREX_E_INVALID, std::string(who) + ": bad sizes");
-  // obs_v_dev: the critic entry points pass it, the plain ones do not; either kind refuses an object of the other kind by name
-  if (!obs_v_dev && p->Dv)
-    return trex_fail(TREX_E_INVALID, std::string(who) + ": the policy has a critic width set (the trex_policy_critic_minibatch calls take obs_v)");
-  if (obs_v_dev && !p->Dv) return trex_fail(TREX_E_INVALID, std::string(who) + ": no critic width is set (trex_policy_set_critic)");
-  if (p->Dv > 96) return trex_fail(TREX_E_INVALID, std::string(who) + ": the learner stages 96 observation columns (critic_dim <= 96)");
-  if (p->D > 96) return trex_fail(TREX_E_INVALID, std::string(who) + ": the learner stages 96 observation columns (obs_dim <= 96)");
-  if ((p->lay.vW1 + (p->lay.count - p->lay.logstd)) / 4 > 256 * LEARN_UF || (p->lay.logstd - p->lay.vW1) / 4 > 256 * LEARN_UF)
-    return trex_fail(TREX_E_INVALID, std::string(who) + ": the learner stages one net's parameters in one trip of 256 x 13 float4s");
-  const size_t P = (size_t)p->lay.count, N = (size_t)num_samples;
-  BUF_TRY(theta_dev, P * sizeof(float), "minibatch step: theta");
-  BUF_TRY(grad_dev, P * sizeof(float), "minibatch step: grad");
-  BUF_TRY(m_dev, P * sizeof(float), "minibatch step: m");
-  BUF_TRY(v_dev, P * sizeof(float), "minibatch step: v");
-  BUF_TRY(obs_dev, N * p->D * sizeof(float), "minibatch step: obs");
-  BUF_TRY(obs_v_dev, N * p->Dv * sizeof(float), "minibatch step: obs_v");
-  BUF_TRY(act_dev, N * p->A * sizeof(float), "minibatch step: act");
-  BUF_TRY(logp_dev, N * sizeof(float), "minibatch step: logp");
-  BUF_TRY(val_dev, N * sizeof(float), "minibatch step: val");
-  BUF_TRY(adv_dev, N * sizeof(float), "minibatch step: adv");
-  BUF_TRY(ret_dev, N * sizeof(float), "minibatch step: ret");
-  BUF_TRY(perm_dev, ((size_t)first + mb) * sizeof(int64_t), "minibatch step: perm");
-  BUF_TRY(adv_stats_dev, 2 * sizeof(float), "minibatch step: adv_stats");
-  BUF_TRY(loss_sums_dev, 2 * sizeof(float), "minibatch step: loss_sums");
-  const int tiles = (mb + TILE - 1) / TILE;
-  const int stride = learn_stride(p);
-  if (int rc = learn_workspace(p, tiles, stride)) return rc;
-  const LdsLayout L = make_lds_layout(p->lay);
-  LearnArgs a{theta_dev, obs_dev, act_dev, logp_dev, val_dev, adv_dev, ret_dev, reinterpret_cast<const long long *>(perm_dev),
-              adv_stats_dev, p->grad_partial, first, mb, stride, cliprange, vf_coef, p->lay};
-  if (obs_v_dev) {
-    LearnArgsV av{};
-    static_cast<LearnArgs &>(av) = a;
-    av.obs_v = obs_v_dev; av.Dv = p->Dv;
-    hipLaunchKernelGGL(learn_grad_kernel<true>, dim3(tiles, 2), dim3(256), (size_t)L.total * sizeof(float), (hipStream_t)stream, av);
-  } else {
-    hipLaunchKernelGGL(learn_grad_kernel<false>, dim3(tiles, 2), dim3(256), (size_t)L.total * sizeof(float), (hipStream_t)stream, a);
-  }
-  HIP_TRY(hipGetLastError());
-  return launch_reduce(p, theta_dev, grad_dev, m_dev, v_dev, loss_sums_dev, tiles, stride, mb, ent_coef, lr, beta1, beta2, eps,
-                       max_grad_norm, grad_scale, advance, stream, out_args, out_groups);
+static int reduce_groups(const ApplyArgs &args) { return ((args.stride >> 2) + AP_COLS - 1) / AP_COLS; }
+extern "C" hipError_t trex_launch_policy_learn_reduce(const ApplyArgs &args, hipStream_t stream) {
+  hipLaunchKernelGGL(learn_reduce_kernel, dim3(reduce_groups(args)), dim3(AP_COLS * AP_GROUPS), 0, stream, args);
+  return hipGetLastError();
 }
-
-int trex_policy_minibatch_step(TrexPolicy *p, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev, const float *obs_dev,
-                               const float *act_dev, const float *logp_dev, const float *val_dev, const float *adv_dev,
-                               const float *ret_dev, int64_t num_samples, const int64_t *perm_dev, int first, int mb,
-                               const float *adv_stats_dev, float cliprange, float ent_coef, float vf_coef, float lr, float beta1,
-                               float beta2, float eps, float max_grad_norm, float *loss_sums_dev, void *stream) {
-  if (!p || !m_dev || !v_dev) return trex_fail(TREX_E_INVALID, "trex_policy_minibatch_step: null argument");
-  TrexDeviceGuard guard(p->device);
-  ApplyArgs b{};
-  int groups = 0;
-  if (int rc = launch_minibatch_grad(p, "trex_policy_minibatch_step", theta_dev, grad_dev, m_dev, v_dev, obs_dev, nullptr, act_dev, logp_dev,
-                                     val_dev, adv_dev, ret_dev, num_samples, perm_dev, first, mb, adv_stats_dev, cliprange, ent_coef,
-                                     vf_coef, lr, beta1, beta2, eps, max_grad_norm, 1.0f, 1, loss_sums_dev, stream, &b, &groups))
-    return rc;
-  hipLaunchKernelGGL(learn_adam_kernel, dim3(((p->lay.count >> 2) + 255) / 256), dim3(256), 0, (hipStream_t)stream, b, groups);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
+extern "C" hipError_t trex_launch_policy_learn_adam(const ApplyArgs &args, hipStream_t stream) {
+  hipLaunchKernelGGL(learn_adam_kernel, dim3(((args.count >> 2) + 255) / 256), dim3(256), 0, stream, args, reduce_groups(args));
+  return hipGetLastError();
 }
-
-int trex_policy_minibatch_grad(TrexPolicy *p, const float *theta_dev, float *grad_dev, const float *obs_dev, const float *act_dev,
-                               const float *logp_dev, const float *val_dev, const float *adv_dev, const float *ret_dev,
-                               int64_t num_samples, const int64_t *perm_dev, int first, int mb, const float *adv_stats_dev,
-                               float cliprange, float ent_coef, float vf_coef, float grad_scale, float *loss_sums_dev, void *stream) {
-  if (!p) return trex_fail(TREX_E_INVALID, "trex_policy_minibatch_grad: null argument");
-  TrexDeviceGuard guard(p->device);
-  return launch_minibatch_grad(p, "trex_policy_minibatch_grad", const_cast<float *>(theta_dev), grad_dev, nullptr, nullptr, obs_dev,
-                               nullptr, act_dev, logp_dev, val_dev, adv_dev, ret_dev, num_samples, perm_dev, first, mb, adv_stats_dev,
-                               cliprange, ent_coef, vf_coef, 0.f, 0.9f, 0.999f, 1e-5f, 0.f, grad_scale, 0, loss_sums_dev, stream,
-                               nullptr, nullptr);
-}
-
-// ---- with a privileged critic (include/trex_policy_critic.h): the same launches, the vf workgroups on obs_v_dev
-int trex_policy_critic_minibatch_step(TrexPolicy *p, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev, const float *obs_dev,
-                                      const float *obs_v_dev, const float *act_dev, const float *logp_dev, const float *val_dev,
-                                      const float *adv_dev, const float *ret_dev, int64_t num_samples, const int64_t *perm_dev, int first,
-                                      int mb, const float *adv_stats_dev, float cliprange, float ent_coef, float vf_coef, float lr,
-                                      float beta1, float beta2, float eps, float max_grad_norm, float *loss_sums_dev, void *stream) {
-  if (!p || !m_dev || !v_dev || !obs_v_dev) return trex_fail(TREX_E_INVALID, "trex_policy_critic_minibatch_step: null argument");
-  TrexDeviceGuard guard(p->device);
-  ApplyArgs b{};
-  int groups = 0;
-  if (int rc = launch_minibatch_grad(p, "trex_policy_critic_minibatch_step", theta_dev, grad_dev, m_dev, v_dev, obs_dev, obs_v_dev, act_dev,
-                                     logp_dev, val_dev, adv_dev, ret_dev, num_samples, perm_dev, first, mb, adv_stats_dev, cliprange,
-                                     ent_coef, vf_coef, lr, beta1, beta2, eps, max_grad_norm, 1.0f, 1, loss_sums_dev, stream, &b, &groups))
-    return rc;
-  hipLaunchKernelGGL(learn_adam_kernel, dim3(((p->lay.count >> 2) + 255) / 256), dim3(256), 0, (hipStream_t)stream, b, groups);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
-}
-
-int trex_policy_critic_minibatch_grad(TrexPolicy *p, const float *theta_dev, float *grad_dev, const float *obs_dev, const float *obs_v_dev,
-                                      const float *act_dev, const float *logp_dev, const float *val_dev, const float *adv_dev,
-                                      const float *ret_dev, int64_t num_samples, const int64_t *perm_dev, int first, int mb,
-                                      const float *adv_stats_dev, float cliprange, float ent_coef, float vf_coef, float grad_scale,
-                                      float *loss_sums_dev, void *stream) {
-  if (!p || !obs_v_dev) return trex_fail(TREX_E_INVALID, "trex_policy_critic_minibatch_grad: null argument");
-  TrexDeviceGuard guard(p->device);
-  return launch_minibatch_grad(p, "trex_policy_critic_minibatch_grad", const_cast<float *>(theta_dev), grad_dev, nullptr, nullptr, obs_dev,
-                               obs_v_dev, act_dev, logp_dev, val_dev, adv_dev, ret_dev, num_samples, perm_dev, first, mb, adv_stats_dev,
-                               cliprange, ent_coef, vf_coef, 0.f, 0.9f, 0.999f, 1e-5f, 0.f, grad_scale, 0, loss_sums_dev, stream,
-                               nullptr, nullptr);
-}
-
-// ---- policy distillation (include/trex_policy_distill.h): the LOSS_DISTILL instantiation of learn_grad_kernel, then the same reduce
-static int launch_distill_grad(TrexPolicy *p, const char *who, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev,
-                               const float *obs_dev, const float *tmean_dev, const float *tvalue_dev, const float *tlogstd_dev,
-                               int64_t num_samples, const int64_t *perm_dev, int first, int mb, int kind, float vf_coef, float lr,
-                               float beta1, float beta2, float eps, float max_grad_norm, float grad_scale, int advance,
-                               float *loss_sums_dev, void *stream, ApplyArgs *out_args, int *out_groups) {
-  if (!p || !theta_dev || !grad_dev || !obs_dev || !tmean_dev || !perm_dev) return trex_fail(TREX_E_INVALID, std::string(who) + ": null argument");
-  if (mb <= 0 || first < 0 || num_samples <= 0) return trex_fail(TREX_E_INVALID, std::string(who) + ": bad sizes");
-  if (kind != TREX_DISTILL_MSE && kind != TREX_DISTILL_KL)
-    return trex_fail(TREX_E_INVALID, std::string(who) + ": unknown loss kind (TREX_DISTILL_MSE, TREX_DISTILL_KL)");
-  if (kind == TREX_DISTILL_KL && !tlogstd_dev) return trex_fail(TREX_E_INVALID, std::string(who) + ": the KL loss needs teacher_logstd");
-  if (!tvalue_dev && vf_coef != 0.f) return trex_fail(TREX_E_INVALID, std::string(who) + ": teacher_value may be null only with vf_coef == 0");
-  if (p->Dv) return trex_fail(TREX_E_INVALID, std::string(who) + ": the policy has a critic width set (a student has no privileged critic)");
-  if (p->D > 96) return trex_fail(TREX_E_INVALID, std::string(who) + ": the learner stages 96 observation columns (obs_dim <= 96)");
-  if ((p->lay.vW1 + (p->lay.count - p->lay.logstd)) / 4 > 256 * LEARN_UF || (p->lay.logstd - p->lay.vW1) / 4 > 256 * LEARN_UF)
-    return trex_fail(TREX_E_INVALID, std::string(who) + ": the learner stages one net's parameters in one trip of 256 x 13 float4s");
-  const size_t P = (size_t)p->lay.count, N = (size_t)num_samples;
-  BUF_TRY(theta_dev, P * sizeof(float), "distillation step: theta");
-  BUF_TRY(grad_dev, P * sizeof(float), "distillation step: grad");
-  BUF_TRY(m_dev, P * sizeof(float), "distillation step: m");
-  BUF_TRY(v_dev, P * sizeof(float), "distillation step: v");
-  BUF_TRY(obs_dev, N * p->D * sizeof(float), "distillation step: obs");
-  BUF_TRY(tmean_dev, N * p->A * sizeof(float), "distillation step: teacher_mean");
-  BUF_TRY(tvalue_dev, N * sizeof(float), "distillation step: teacher_value");
-  BUF_TRY(tlogstd_dev, (size_t)p->A * sizeof(float), "distillation step: teacher_logstd");
-  BUF_TRY(perm_dev, ((size_t)first + mb) * sizeof(int64_t), "distillation step: perm");
-  BUF_TRY(loss_sums_dev, 2 * sizeof(float), "distillation step: loss_sums");
-  const int tiles = (mb + TILE - 1) / TILE;
-  const int stride = learn_stride(p);
-  if (int rc = learn_workspace(p, tiles, stride)) return rc;
-  const LdsLayout L = make_lds_layout(p->lay);
-  // The kernel's staging loads are unconditional (no control flow before its first barrier), so an absent buffer gets a stand-in
-  // address that is readable and long enough - the teacher's means for its values [N <= N A], the student's own logstd for the
-  // teacher's [A] - and a flag / the kind keeps what is read there out of every result.
-  LearnArgsD a{};
-  static_cast<LearnArgs &>(a) = LearnArgs{theta_dev, obs_dev, tmean_dev, nullptr, nullptr, nullptr, tvalue_dev ? tvalue_dev : tmean_dev,
-                                          reinterpret_cast<const long long *>(perm_dev), nullptr, p->grad_partial, first, mb, stride,
-                                          0.f, vf_coef, p->lay};
-  a.teacher_logstd = tlogstd_dev ? tlogstd_dev : theta_dev + p->lay.logstd;
-  a.kind = kind;
-  a.has_value = tvalue_dev != nullptr;
-  hipLaunchKernelGGL((learn_grad_kernel<false, LOSS_DISTILL>), dim3(tiles, 2), dim3(256), (size_t)L.total * sizeof(float), (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return launch_reduce(p, theta_dev, grad_dev, m_dev, v_dev, loss_sums_dev, tiles, stride, mb, 0.f, lr, beta1, beta2, eps, max_grad_norm,
-                       grad_scale, advance, stream, out_args, out_groups);
-}
-
-int trex_policy_distill_minibatch_step(TrexPolicy *p, float *theta_dev, float *grad_dev, float *m_dev, float *v_dev, const float *obs_dev,
-                                       const float *teacher_mean_dev, const float *teacher_value_dev, const float *teacher_logstd_dev,
-                                       int64_t num_samples, const int64_t *perm_dev, int first, int mb, int kind, float vf_coef, float lr,
-                                       float beta1, float beta2, float eps, float max_grad_norm, float *loss_sums_dev, void *stream) {
-  if (!p || !m_dev || !v_dev) return trex_fail(TREX_E_INVALID, "trex_policy_distill_minibatch_step: null argument");
-  TrexDeviceGuard guard(p->device);
-  ApplyArgs b{};
-  int groups = 0;
-  if (int rc = launch_distill_grad(p, "trex_policy_distill_minibatch_step", theta_dev, grad_dev, m_dev, v_dev, obs_dev, teacher_mean_dev,
-                                   teacher_value_dev, teacher_logstd_dev, num_samples, perm_dev, first, mb, kind, vf_coef, lr, beta1, beta2,
-                                   eps, max_grad_norm, 1.0f, 1, loss_sums_dev, stream, &b, &groups))
-    return rc;
-  hipLaunchKernelGGL(learn_adam_kernel, dim3(((p->lay.count >> 2) + 255) / 256), dim3(256), 0, (hipStream_t)stream, b, groups);
-  HIP_TRY(hipGetLastError());
-  return TREX_OK;
-}
-
-int trex_policy_distill_minibatch_grad(TrexPolicy *p, const float *theta_dev, float *grad_dev, const float *obs_dev,
-                                       const float *teacher_mean_dev, const float *teacher_value_dev, const float *teacher_logstd_dev,
-                                       int64_t num_samples, const int64_t *perm_dev, int first, int mb, int kind, float vf_coef,
-                                       float grad_scale, float *loss_sums_dev, void *stream) {
-  if (!p) return trex_fail(TREX_E_INVALID, "trex_policy_distill_minibatch_grad: null argument");
-  TrexDeviceGuard guard(p->device);
-  return launch_distill_grad(p, "trex_policy_distill_minibatch_grad", const_cast<float *>(theta_dev), grad_dev, nullptr, nullptr, obs_dev,
-                             teacher_mean_dev, teacher_value_dev, teacher_logstd_dev, num_samples, perm_dev, first, mb, kind, vf_coef, 0.f,
-                             0.9f, 0.999f, 1e-5f, 0.f, grad_scale, 0, loss_sums_dev, stream, nullptr, nullptr);
-}
-
-}  // extern "C"

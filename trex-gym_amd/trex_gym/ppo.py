@@ -5,8 +5,8 @@ TensorFlow are not installed here, so this is an equivalent that keeps the WHOLE
 advantages and the policy never leave the GPU, and the env is stepped through step_tensor() (no host sync per step).
 
 The per-step caller work - VecNormalize's running statistics, the policy / value MLPs, the Gaussian sample and its
-log-probability - runs in the hand-written HIP kernels of include/trex_policy.h (csrc/policy_step.hip: two launches
-per env step instead of ~30 framework kernels), GAE(lambda) and the optimiser step (global-norm clip + Adam in
+log-probability - runs in the hand-written HIP kernels of include/trex_policy.h (csrc/policy_step.hip, called through
+csrc/capi_policy.cpp: two launches per env step instead of ~30 framework kernels), GAE(lambda) and the optimiser step (global-norm clip + Adam in
 TensorFlow's form, as ppo2 applies it) in one launch each. There is no fallback: without libtrex_hip.so this module
 does not import. PyTorch keeps one job: autograd over the minibatch loss, on parameters that are VIEWS into the flat
 f32 vector the kernels read (weights stored [in, out]).

@@ -160,7 +160,7 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
     return env
 
 
-POLICY_MAX_ACT_DIM = 32      # the policy kernel's widest action (csrc/policy_step.hip)
+POLICY_MAX_ACT_DIM = 32      # the policy kernel's widest action (csrc/policy_limits.h)
 
 
 def check_action_space(control_mode, variable_stiffness, num_joints=25):

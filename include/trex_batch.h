@@ -734,6 +734,9 @@ int trex_batch_time_steps(TrexBatch *batch, const float *actions_dev, float *obs
 /* So is the episode randomisation of a batch - mass scale, friction, motor gains, pushes and the velocity command, redrawn on the
  * device when an episode starts or at an interval inside it: */
 #include "trex_randomize.h"
+/* So is the start-state randomisation of a batch - the state an episode starts in, perturbed on the device and placed on the
+ * floor, the counterpart of the episode randomisation: */
+#include "trex_start_state.h"
 /* So is the episode monitor of a batch - the return, the length and the end reason of every finished episode, the window of the
  * last W of them and its summary, kept on the device: */
 #include "trex_monitor.h"

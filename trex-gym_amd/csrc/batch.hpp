@@ -13,6 +13,7 @@
 #include "link_state.h"
 #include "monitor.h"
 #include "randomize.h"
+#include "start_state.h"
 
 using DeviceGuard = TrexDeviceGuard;
 
@@ -119,6 +120,17 @@ struct TrexBatch {
     uint32_t env_offset = 0;
     bool was_domain = false, was_gains_set = false, was_ext_on = false;
   } random;
+  // start-state randomisation (trex_batch_set_start_state, include/trex_start_state.h): the term table (`table`: host side, num_terms
+  // 0 = nothing set; `blob`: the same on the device); the state, ONE allocation zeroed by every set - the lowest points then set to
+  // -1 -, laid out by trex::start_state_layout, as `st` points into it (TrexStartState); seed and env_offset of the last set, kept
+  // by a clear
+  struct StartStates {
+    TrexStartTable table{};
+    DeviceBuf blob, state;
+    TrexStartState st{};
+    uint64_t seed = 0;
+    uint32_t env_offset = 0;
+  } start;
   // episode monitor (trex_batch_set_monitor, include/trex_monitor.h): its shape and the layout of its state (`layout`: host side,
   // window 0 = no monitor), the state itself, ONE allocation zeroed by every set, as `st` points into it (TrexMonState), and the
   // global index of env 0; all freed by window 0 and with the batch

@@ -77,6 +77,16 @@ RandStateLayout rand_state_layout(int n_envs, int T_terms, int P_pushes) {
   return l;
 }
 
+StartStateLayout start_state_layout(int n_envs, int T_terms) {
+  StartStateLayout l;
+  if (T_terms == 0) return l;
+  const size_t n = (size_t)n_envs, T = (size_t)T_terms;
+  l.ep = l.take("ep", n * 4, 4); l.started = l.take("started", n * 4, 4);
+  l.shift = l.take("shift", n * 4, 4); l.lowest = l.take("lowest", n * 4, 4);
+  l.values = l.take("values", n * T * TREX_TL * 4, 4);
+  return l;
+}
+
 void fill_device_model(const trex::HostModel &h, TrexDeviceModel &d) {
   std::memset(&d, 0, sizeof d);
   d.nb = h.nb;
@@ -649,6 +659,53 @@ RandTable build_random_table(int nb, int nj, bool stiffness, const TrexRandomTer
   }
   t.terms = num_terms;
   return t;
+}
+
+TrexStartTable build_start_table(int nj, const TrexStartTerm *terms, int num_terms) {
+  const std::string me = "trex_batch_set_start_state: ";
+  TrexStartTable t;
+  std::memset(&t, 0, sizeof t);
+  t.clearance_term = -1;
+  if (num_terms == 0) return t;
+  if (num_terms < 0 || num_terms > TREX_START_MAXTERMS)
+    throw Refusal(me + "num_terms " + std::to_string(num_terms) + " outside [0, " + std::to_string(TREX_START_MAXTERMS) + "]");
+  if (!terms) throw Refusal(me + "null argument");
+  uint32_t covered[TREX_START_KINDS] = {};   // per kind: the joints, or the components, taken so far
+  for (int i = 0; i < num_terms; i++) {
+    TrexStartTerm c = terms[i];
+    const std::string ck = me + "term " + std::to_string(i) + ": ";
+    if (c.kind < 0 || c.kind >= TREX_START_KINDS) throw Refusal(ck + "unknown kind " + std::to_string(c.kind));
+    if (!std::isfinite(c.lo) || !std::isfinite(c.hi)) throw Refusal(ck + "lo or hi is not finite");
+    if (c.lo > c.hi) throw Refusal(ck + "lo > hi");
+    uint32_t bits = 0u;
+    if (c.kind == TREX_START_JOINT_POSITION || c.kind == TREX_START_JOINT_VELOCITY) {
+      const uint32_t all = nj >= 32 ? 0xFFFFFFFFu : (1u << nj) - 1u;
+      if (c.mask & ~all) throw Refusal(ck + "a mask bit beyond the model's " + std::to_string(nj) + " joints");
+      bits = c.mask ? c.mask : all;
+      c.mask = bits; c.shared = c.shared != 0; c.index = 0;
+    } else if (c.kind == TREX_START_FLOOR_CLEARANCE) {
+      if (t.clearance_term >= 0) throw Refusal(ck + "a second FLOOR_CLEARANCE term");
+      t.clearance_term = i;
+      bits = 1u; c.mask = 1u; c.shared = 1; c.index = 0;
+    } else {
+      if (c.index < 0 || c.index > 2) throw Refusal(ck + "index " + std::to_string(c.index) + " outside [0, 2]");
+      if (c.kind == TREX_START_BASE_RPY) t.rotate = 1;
+      bits = 1u << c.index; c.mask = 1u; c.shared = 1;
+    }
+    if (covered[c.kind] & bits) throw Refusal(ck + "overlaps an earlier term of its kind");
+    covered[c.kind] |= bits;
+    t.term[i] = c;
+  }
+  t.num_terms = num_terms;
+  return t;
+}
+
+void check_start_apply(int num_terms, bool done, int done_stride, bool rows, int row_stride, int nj, bool pen_in_rows) {
+  const std::string me = "trex_batch_apply_start_state: ";
+  if (num_terms < 1) throw Refusal(me + "no terms are set (trex_batch_set_start_state)");
+  if (!done) throw Refusal(me + "done is null");
+  if (done_stride < 1) throw Refusal(me + "done_stride below 1");
+  if (rows && row_stride < 3 * nj + (pen_in_rows ? 5 : 2)) throw Refusal(me + "row_stride < 3J + 2 (3J + 5 with penalties in rows)");
 }
 
 MonitorLayout monitor_layout(int n_envs, int window, int cols_a, int cols_b, uint32_t env_offset, int block) {

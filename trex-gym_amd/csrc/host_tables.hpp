@@ -1,6 +1,6 @@
 // The tables the kernels read and the layouts of the per-env state they write, as pure host arithmetic: everything the C-ABI computes
 // between its argument checks and its HIP calls.
-// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h, motion_limits.h, sensing_limits.h, policy_limits.h and include/trex_batch.h, and nothing of HIP; it makes
+// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h, motion_limits.h, sensing_limits.h, start_state_limits.h, policy_limits.h and include/trex_batch.h, and nothing of HIP; it makes
 // no HIP call and knows no batch. It builds with plain g++ -std=c++17, as model.cpp does, so that tests/host/tables_harness.cpp runs
 // it under the sanitizers on a machine without a GPU. A refusal is a thrown Refusal whose text is the C-ABI's message, whole.
 #pragma once
@@ -22,6 +22,7 @@ struct float4;
 #include "proximity_limits.h"
 #include "reward_limits.h"
 #include "sensing_limits.h"
+#include "start_state_limits.h"
 
 namespace trex {
 
@@ -70,6 +71,10 @@ Layout sense_hist_layout(int n, int cols);
 // started | off [P] | push_left [P] | push_force [P][3] | push_base [P][6] | values [T][TREX_TL]. T 0 gives the empty layout.
 struct RandStateLayout : Layout { size_t ep = 0, k = 0, started = 0, off = 0, push_left = 0, push_force = 0, push_base = 0, values = 0; };
 RandStateLayout rand_state_layout(int n, int T, int P);
+// trex_batch_set_start_state: the state, in the order of TrexStartState (start_state.h), each member [n] outermost - ep | started |
+// shift | lowest | values [T][TREX_TL]. T 0 gives the empty layout.
+struct StartStateLayout : Layout { size_t ep = 0, started = 0, shift = 0, lowest = 0, values = 0; };
+StartStateLayout start_state_layout(int n, int T);
 
 // rotation row-major (9) | translation (3): the [12] layout of every transform a kernel reads
 void tf12(const Tf &t, float out[12]);
@@ -177,6 +182,13 @@ struct RandTable {
   bool mass = false, friction = false, gains = false, command = false;
 };
 RandTable build_random_table(int nb, int nj, bool stiffness, const TrexRandomTerm *terms, int num_terms);
+
+// trex_batch_set_start_state: the terms checked and as the kernel reads them (TrexStartTable, start_state_limits.h) - a joint mask
+// of 0 as all the model's joints, a base kind and FLOOR_CLEARANCE as element 0 alone, shared as 0 / 1 -, whether a BASE_RPY term
+// is among them and which term is the FLOOR_CLEARANCE one (-1: none). nj: the model's joints. num_terms 0 gives the empty table.
+TrexStartTable build_start_table(int nj, const TrexStartTerm *terms, int num_terms);
+// trex_batch_apply_start_state: the arguments against the table and the row's width; the pointers as "is it there" flags
+void check_start_apply(int num_terms, bool done, int done_stride, bool rows, int row_stride, int nj, bool pen_in_rows);
 
 // trex_batch_set_monitor: the shape checked, the team of lanes an env takes in the accumulate launch (the smallest power of two
 // that holds the C columns, at least 1), the workgroups of that launch, and the layout of the ONE allocation that is the

@@ -19,3 +19,15 @@ __device__ __forceinline__ void philox(uint32_t c0, uint32_t c1, uint32_t c2, ui
 __device__ __forceinline__ float u_half_open(uint32_t r) { return (float)(r >> 8) * 5.9604644775390625e-8f; }          // [0, 1)
 __device__ __forceinline__ float u_open_closed(uint32_t r) { return (float)((r >> 8) + 1u) * 5.9604644775390625e-8f; }  // (0, 1]
 __device__ __forceinline__ int draw_int(uint32_t r, int lo, int hi) { return lo + (int)__umulhi(r, (uint32_t)(hi - lo + 1)); }
+
+// The uniform value of include/trex_randomize.h and include/trex_start_state.h (randomize.hip, start_state.hip). The header's
+// rounded operations __fsub_rn, __fmul_rn, __fadd_rn are plain operators in this toolchain's headers, and the library is built
+// with -ffp-contract=fast, under which the compiler fuses a product that feeds a sum into an fma whatever pragma stands there (seen
+// in the ISA). Where a header orders "rounded to f32, no fma", the product passes through rounded(): an empty asm statement that
+// the value flows through, so that it exists rounded before the sum reads it.
+__device__ __forceinline__ float rounded(float x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+__device__ __forceinline__ float product(float a, float b) { return rounded(a * b); }
+__device__ __forceinline__ float uniform(float lo, float hi, uint32_t r) { return lo + product(hi - lo, u_half_open(r)); }

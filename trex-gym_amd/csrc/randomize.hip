@@ -18,16 +18,7 @@ namespace {
 constexpr int BLOCK = TREX_RAND_BLOCK, TL = TREX_TL;
 constexpr float TWO_PI = 6.2831855f;
 
-// The header's rounded operations __fsub_rn, __fmul_rn, __fadd_rn are plain operators in this toolchain's headers, and the library
-// is built with -ffp-contract=fast, under which the compiler fuses a product that feeds a sum into an fma whatever pragma stands
-// there (seen in the ISA). Where the header orders "rounded to f32, no fma", the product passes through rounded(): an empty asm
-// statement that the value flows through, so that it exists rounded before the sum reads it.
-__device__ __forceinline__ float rounded(float x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ float product(float a, float b) { return rounded(a * b); }
-__device__ __forceinline__ float uniform(float lo, float hi, uint32_t r) { return lo + product(hi - lo, u_half_open(r)); }
+// (rounded(), product(), uniform(): philox.h - the products the header orders rounded before a sum reads them)
 
 __global__ __launch_bounds__(BLOCK) void trex_randomize_kernel(TrexRandArgs a) {
   const int lane = threadIdx.x % TL, env = blockIdx.x * (BLOCK / TL) + threadIdx.x / TL;

@@ -9,6 +9,7 @@ visual meshes); --frames DIR also writes one PNG per step, ray-cast from the col
 them into a movie (the reference's ffmpeg call) stays the user's.
 """
 import argparse
+import math
 import os
 import sys
 
@@ -25,7 +26,7 @@ _URDF_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ass
 def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmstart=0.0, push_force=0.0, push_interval=100,
                       push_duration=5, push_probability=1.0, seed=0, control_mode=None, variable_stiffness=False,
                       gain_scale=0.0, terminate=None, observations=None, rewards=None, command=None, motion=None, sensing=None,
-                      randomize=None, monitor=None, critic=None):   # (weights of trex_train.py:66)
+                      randomize=None, monitor=None, critic=None, start_state=None):   # (weights of trex_train.py:66)
     # control_mode: what the joints' actions mean (position / velocity / torque: J-wide, through the trainer unchanged). The
     # 2J-wide stiffness action space is wider than the policy kernel's act_dim <= 32: refused here, not deep in a launch
     check_action_space(control_mode, variable_stiffness)
@@ -136,6 +137,23 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
             spec, rand_seed = Z.PRESETS[randomize["preset"]](env, scale=float(randomize.get("scale", 1.0)), **kw), seed
         Z.attach(env, spec, seed=rand_seed)
         env.randomize_config = env.randomization     # what a checkpoint stores: the terms as set, the seed
+    # start_state: dict(preset="typical", scale=, clearance=(lo, hi) or None) as the flags give it, or dict(terms=, seed=) - a
+    # checkpoint's, the recorded specification of trex_gym.start_state.attach: the state an episode starts in - joint angles and
+    # velocities, base attitude and velocity - perturbed on the device, on top of the reset's or RSI's state, and placed on the floor
+    env.start_state_config = None
+    if start_state is not None:
+        from . import start_state as SS
+        if "terms" in start_state:
+            spec, start_seed = SS.from_tuples(start_state["terms"]), start_state.get("seed", seed)
+        else:
+            if start_state.get("preset") not in SS.PRESETS:
+                raise ValueError("--start_noise: expected one of %s, got %r" % (", ".join(sorted(SS.PRESETS)), start_state.get("preset")))
+            clearance = start_state.get("clearance")
+            spec = SS.PRESETS[start_state["preset"]](env, scale=float(start_state.get("scale", 1.0)),
+                                                     clearance=None if clearance is None else tuple(float(x) for x in clearance))
+            start_seed = seed
+        SS.attach(env, spec, seed=start_seed)
+        env.start_state_config = env.start_state     # what a checkpoint stores: the terms as set, the seed
     if gain_scale > 0:   # every episode with motor gains and strength scaled by 1 +- gain_scale per env (RandomGains)
         dev = torch.device(device)
         r = (1.0 - gain_scale, 1.0 + gain_scale)
@@ -210,6 +228,7 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
                     "observations": _own_channels(env), "rewards": getattr(env, "rewards", None),
                     "command": getattr(env, "command", None), "motion": getattr(env, "motion_config", None),
                     "sensing": getattr(env, "sensing_config", None), "randomize": getattr(env, "randomize_config", None),
+                    "start_state": getattr(env, "start_state_config", None),
                     "monitor": getattr(env, "monitor_config", None), "critic": critic_checkpoint(agent),
                     "distill": None if distill is None else dict(teacher=str(distill["teacher"]), rows=str(distill.get("rows", "clean")),
                                                                  loss=str(distill.get("loss", "kl")))},
@@ -301,15 +320,15 @@ def play(agent, num_play_timesteps, export_path=None, env_index=0, log=print, de
     return np.stack(frames), np.array(rewards)
 
 
-def load_agent(load_path, num_envs=1, device="cuda:0", max_episode_steps=1000, sensing=True, randomize=True):
+def load_agent(load_path, num_envs=1, device="cuda:0", max_episode_steps=1000, sensing=True, randomize=True, start_state=True):
     """trex_train.py:75-110 (replay): rebuild the policy from a file written by train(save_path=...) - the flat
     parameter vector and VecNormalize's statistics. sensing=False: without the sensor model the checkpoint was trained with; randomize=False:
-    without its episode randomisation."""
+    without its episode randomisation; start_state=False: without its start-state randomisation."""
     ck = torch.load(load_path, map_location=device, weights_only=True)
     env = build_environment(num_envs, device=device, max_episode_steps=max_episode_steps, observations=ck.get("observations"),
                             rewards=ck.get("rewards"), command=ck.get("command"), motion=ck.get("motion"),
                             sensing=ck.get("sensing") if sensing else None, randomize=ck.get("randomize") if randomize else None,
-                            monitor=ck.get("monitor"))
+                            monitor=ck.get("monitor"), start_state=ck.get("start_state") if start_state else None)
     agent = PPO(env, nsteps=1, nminibatches=1, noptepochs=1)
     cr = ck.get("critic")
     if cr is not None:      # theta has the critic's layout; the env gets no critic row: playing runs the policy alone
@@ -398,6 +417,13 @@ def parse_args(argv=None):
                     help="episode monitor on the device: eprewmean, eplenmean and the end reasons of the last WINDOW (100) finished "
                          "episodes per iteration (trex_gym.monitor)")
     ap.add_argument("--no_randomize", action="store_true", help="with --play: run the policy without the episode randomisation it was trained with")
+    ap.add_argument("--start_noise", choices=["typical"], default=None,
+                    help="start-state randomisation on the device, on top of the reset's or --rsi's state: typical: joint angles and "
+                         "velocities, roll, pitch, yaw, base velocities - untuned magnitudes (trex_gym.start_state.typical)")
+    ap.add_argument("--start_scale", type=float, default=1.0, help="with --start_noise: a factor on the width of the preset's ranges")
+    ap.add_argument("--start_clearance", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="with --start_noise: place the perturbed robot with its lowest collision point LO..HI metres above the floor")
+    ap.add_argument("--no_start_noise", action="store_true", help="with --play: run the policy without the start-state randomisation it was trained with")
     ap.add_argument("--fall_penalty", type=float, default=0.0, help="taken from the reward of the step in which an episode ends by a fall")
     ap.add_argument("--critic", choices=["clean", "privileged"], default=None,
                     help="asymmetric actor-critic: the value net reads a row of its own - the observation before the sensor model "
@@ -450,6 +476,13 @@ def parse_args(argv=None):
         ap.error("--command_range: half-widths must not be negative")
     if args.command_interval is not None and args.command_interval < 0:
         ap.error("--command_interval must not be negative")
+    if args.start_noise is None and (args.start_scale != 1.0 or args.start_clearance is not None):
+        ap.error("--start_scale and --start_clearance need --start_noise")
+    if not (args.start_scale >= 0.0):
+        ap.error("--start_scale must not be negative")
+    if args.start_clearance is not None and not (math.isfinite(args.start_clearance[0]) and args.start_clearance[0] <= args.start_clearance[1]
+                                                 and math.isfinite(args.start_clearance[1])):
+        ap.error("--start_clearance: LO <= HI, both finite")
     if args.randomize is not None and (args.push_force > 0 or args.gain_scale > 0):   # (one owner per buffer)
         ap.error("--randomize cannot be combined with --push_force or --gain_scale")
     if not 0.0 <= args.gain_scale < 1.0:
@@ -485,6 +518,14 @@ def randomize_args(args):
                 command_interval=args.command_interval)
 
 
+def start_state_args(args):
+    """the dict for build_environment(start_state=...) of the --start_noise, --start_scale and --start_clearance flags, None when
+    --start_noise is not given"""
+    if args.start_noise is None:
+        return None
+    return dict(preset=args.start_noise, scale=args.start_scale, clearance=args.start_clearance)
+
+
 def distill_args(args):
     """the dict for train(distill=...) of the --distill, --teacher_rows, --distill_loss and --dagger_beta flags, None without --distill"""
     if args.distill is None:
@@ -510,7 +551,8 @@ def environment_from_args(args):
                             seed=args.random_seed, control_mode=None if args.control_mode == "position" else args.control_mode,
                             gain_scale=args.gain_scale, observations=args.observations, rewards=args.rewards, command=args.command,
                             motion=None if args.motion is None else dict(clip=args.motion, rsi=args.rsi, weight=args.motion_weight),
-                            sensing=sensing_args(args), randomize=randomize_args(args), monitor=monitor_args(args), critic=args.critic)
+                            sensing=sensing_args(args), randomize=randomize_args(args), monitor=monitor_args(args), critic=args.critic,
+                            start_state=start_state_args(args))
     if terminate is not None:   # (set on the built env: 'auto' needs its model - every body that does not stand on the floor at the start)
         if terminate["keep_clear"] == ["auto"]:
             from .termination import fall_bodies
@@ -534,6 +576,9 @@ def main(argv=None):
         if args.no_randomize and env.random_api is not None:  # (likewise its episode randomisation)
             from . import randomize as Z
             Z.attach(env, None)
+        if args.no_start_noise and env.start_api is not None:  # (likewise its start-state randomisation)
+            from . import start_state as SS
+            SS.attach(env, None)
         play(agent, args.num_play_timesteps, args.export, deterministic=args.play_deterministic, update_stats=not args.play_deterministic,
              frames_dir=args.frames)
 

@@ -69,7 +69,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         A motion clip with its tracking terms is attached to a constructed env by trex_gym.motion.attach(env, clip, ...), a sensor
         model - noise, bias, resolution and latency on what the policy reads, latency on its actions - by
         trex_gym.sensing.attach(env, spec, ...), episode randomisation - mass scale, friction, motor gains, pushes and commands
-        redrawn on the device - by trex_gym.randomize.attach(env, spec, ...)."""
+        redrawn on the device - by trex_gym.randomize.attach(env, spec, ...), start-state randomisation - the state an episode
+        starts in, perturbed on the device and placed on the floor - by trex_gym.start_state.attach(env, spec, ...)."""
         self.global_num_envs = int(num_envs)
         self.rank, self.world_size, self.process_group = int(rank), int(world_size), process_group
         self.env_lo, self.env_hi = sharding.shard_range(self.global_num_envs, self.rank, self.world_size)
@@ -130,6 +131,7 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self._clean_block, self._delayed_actions = None, None
         self.randomization, self.random_api, self.random_values = None, None, None
         self._no_done = None
+        self.start_state, self.start_api, self.start_values, self._start_no_done = None, None, None, None
         self.monitor, self.monitor_api = None, None
         # the privileged critic row (trex_gym.critic.attach): [n, Dv], its column names, the recorded sources, and the call that
         # refills it behind every step and reset
@@ -200,6 +202,36 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self._no_done = torch.zeros(self.num_envs, device=self.device)      # what a reset applies with: only the marked envs start
         if self.commands is None and any(t.kind == randomize_capi.COMMAND for t in terms):
             self.commands = torch.zeros(self.num_envs, 3, device=self.device)
+
+    # ---- start-state randomisation (trex_batch_set_start_state and its kin, include/trex_start_state.h; trex_gym.start_state builds
+    # specifications)
+    def _set_start_state(self, spec, seed=0):
+        """What trex_gym.start_state.attach(env, ...) does (the constructor's signature is a recorded one): the terms of `spec`
+        (trex_gym.start_state; merged, joint names resolved to observation slots) go to the batch, and one more launch per step
+        (trex_batch_apply_start_state) - behind the step call, the reward compose, the motion step and RSI, before the
+        randomisation - perturbs the state of the envs whose done column is set and patches the first 3J columns of their rows:
+        noise lands on the RSI state, and the monitor, the joint sensor, the channels, the sensor model and the critic's row all
+        see the final state. reset_tensor marks the envs it resets and applies at the same place. `start_api` is the batch's
+        calls (start_state_capi.BatchStartState), `start_values` a [n, T, 32] tensor for its info(), `start_state` the recorded
+        specification: dict(terms=, seed=). The Philox key is `seed`, the env offset `env_lo`. Nothing here is sized by the row
+        or by another feature: it attaches in any order with the others. spec None clears the batch's terms and takes all of
+        this off the env again. Never called, or cleared: nothing changes - not a launch, not a byte."""
+        from . import start_state as S, start_state_capi
+        if spec is None:
+            if self.start_api is not None:
+                self.start_api.set(())
+            self.start_state, self.start_api, self.start_values, self._start_no_done = None, None, None, None
+            return
+        names = list(self.model.joint_names)
+        terms = S.resolve(spec, names.index)
+        if not terms:
+            raise ValueError("start state: an empty specification (None takes the feature off)")
+        api = start_state_capi.BatchStartState(self.batch)
+        api.set([tuple(t) for t in terms], seed, self.env_lo)
+        self.start_api = api
+        self.start_state = dict(terms=S.as_tuples(terms), seed=int(seed))
+        self.start_values = torch.zeros(self.num_envs, len(terms), start_state_capi.ELEMENTS, device=self.device)
+        self._start_no_done = torch.zeros(self.num_envs, device=self.device)  # what a reset applies with: only the marked envs start
 
     # ---- episode monitor (trex_batch_set_monitor and its kin, include/trex_monitor.h; trex_gym.monitor reads it)
     def _set_monitor(self, window=100, terms=True):
@@ -389,6 +421,9 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         self.batch.reset_rows(rows, mask)
         if self._rsi:
             self._motion_rsi(rows, mask)
+        if self.start_api is not None:          # the envs that were reset start from a perturbed state: on the reset's or RSI's, before all that reads it
+            self.start_api.reset(mask)
+            self.start_api.apply(self._start_no_done, rows)
         if self.random_api is not None:         # the envs that were reset start an episode: their draws, before the compose shows them
             self.random_api.reset(mask)
             self.random_api.apply(self._no_done, self.commands)
@@ -435,12 +470,14 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         predicate, reset of the envs that fell or reached the limit - done = 1, the reward of the finished step, the observation
         of the new episode, the last one of a fallen env in terminal_obs, which no later launch touches; (3) the reward terms,
         on the POLICY's action and the commands as they are, into the reward column; (4) the motion terms added to that column,
-        then RSI, which writes the state of the envs whose episode ended; (5) the randomisation, which redraws for those envs -
+        then RSI, which writes the state of the envs whose episode ended; (4b) the start-state terms, which perturb the state of
+        those envs as the reset or RSI left it, place it on the floor and patch the first 3J columns of their rows; (5) the
+        randomisation, which redraws for those envs -
         commands included: the finished step was rewarded against the old command, the row of the new episode shows the new one;
         (6) the monitor, on the reward column as (3) and (4) left it, the done column and the two term blocks; (7) the joint
-        sensor, at the state (4) left; (8) the channels' compose into the clean block, with the policy's action for prev_action
+        sensor, at the state (4) and (4b) left; (8) the channels' compose into the clean block, with the policy's action for prev_action
         and the commands of (5); (9) the sensor model, from the clean block - channel and command columns included - into `rows`;
-        (10) the critic's row, whose clean source is the clean block. reset_tensor runs (4)'s reset, (5), (7) - (10) in that order,
+        (10) the critic's row, whose clean source is the clean block. reset_tensor runs (4)'s reset, (4b), (5), (7) - (10) in that order,
         then starts the reward history and the monitor's episode of the envs it reset afresh."""
         actions = self._dev(actions)
         if tuple(actions.shape) != (self.num_envs, self.A):
@@ -467,6 +504,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
                 self._compose_reward(out, actions)
             if self.motion is not None:
                 self._motion_step(out)
+            if self.start_api is not None:
+                self.start_api.apply(out, out, 3 * self.J + 1)
             if self.random_api is not None:
                 self.random_api.apply(out, self.commands, 3 * self.J + 1)
             if self.monitor_api is not None:
@@ -479,6 +518,8 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
                 self._compose_reward(self._step_rows, actions)
             if self.motion is not None:
                 self._motion_step(self._step_rows)
+            if self.start_api is not None:
+                self.start_api.apply(self._step_rows, self._step_rows, 3 * self.J + 1)
             if self.random_api is not None:
                 self.random_api.apply(self._step_rows, self.commands, 3 * self.J + 1)
             if self.monitor_api is not None:
@@ -498,10 +539,12 @@ class TrexVecEnv(_VecQueries, spaces.Env):   # gym.Env where gym is importable; 
         """Open-loop rollout: actions [S, n, J] f32 on device -> rows [S, n, 3J+2] (obs | reward | done of every step), S
         env-steps in ONE launch (trex_batch_step_many; bitwise S calls of step_tensor). `rows`, `obs`, `rew`, `done_f`
         and `done` then hold the last step. sharding.split_rows(rows[s]) cuts a step's block into the three.
-        ValueError with observations, rewards, motion, sensing, randomisation or the joint sensor: an open-loop launch has no compose between its steps.
+        ValueError with observations, rewards, motion, sensing, randomisation, start-state terms or the joint sensor: an open-loop launch has no compose between its steps.
         With a monitor attached its applies follow the launch, one per step block (not together with fall termination)."""
         if self.random_api is not None:
             raise ValueError("step_many_tensor: not with randomisation - the open-loop launch has no per-step launch of the redraws")
+        if self.start_api is not None:
+            raise ValueError("step_many_tensor: not with start-state terms - the open-loop launch has no per-step launch of the perturbation")
         if self.monitor_api is not None and self._term_on:
             raise ValueError("step_many_tensor: not with a monitor and fall termination - the batch keeps the last step's reasons only")
         if self._joint_fill is not None:

@@ -858,4 +858,119 @@ CameraBasis camera_basis(const TrexCamera &cam, int width, int height) {
   return b;
 }
 
+// ---- the planner (include/trex_planner.h)
+
+PlannerShape check_planner_create(int groups, int samples, int horizon, int knots, int act_dim, int interpolation) {
+  const std::string me = "trex_planner_create: ";
+  auto range = [&](const char *what, int v, int lo, int hi) {
+    if (v < lo || v > hi) throw Refusal(me + what + " " + std::to_string(v) + " outside [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
+  };
+  if (groups < 1) throw Refusal(me + "groups " + std::to_string(groups) + " below 1");
+  range("samples", samples, 1, TREX_PLAN_MAXSAMPLES);
+  range("horizon", horizon, 1, TREX_PLAN_MAXHORIZON);
+  range("knots", knots, 1, std::min(horizon, TREX_PLAN_MAXKNOTS));
+  range("act_dim", act_dim, 1, TREX_PLAN_MAXACT);
+  if (interpolation < 0 || interpolation >= TREX_PLAN_KINDS) throw Refusal(me + "unknown interpolation " + std::to_string(interpolation));
+  if ((int64_t)groups * samples * horizon * act_dim >= (int64_t)1 << 31)
+    throw Refusal(me + "groups x samples x horizon x act_dim is beyond 2^31: an index would not fit 32 bits");
+  PlannerShape p;
+  p.G = groups; p.K = samples; p.S = horizon; p.P = knots; p.A = act_dim; p.kind = interpolation; p.N = groups * samples;
+  return p;
+}
+
+TrexPlanTap plan_tap(int kind, int P, int64_t num, int64_t den) {
+  TrexPlanTap tap{};
+  double W[4] = {1.0, 0.0, 0.0, 0.0};
+  if (P == 1 || den == 0) {
+    // the constant
+  } else if (kind == TREX_PLAN_HOLD) {
+    const int j = (int)std::min<int64_t>(num / den, P - 1);
+    for (int &i : tap.i) i = j;
+  } else {
+    const int j = (int)std::min<int64_t>(num / den, P - 2);
+    const double t = (double)(num - (int64_t)j * den) / (double)den;
+    if (kind == TREX_PLAN_LINEAR) {
+      tap.i[0] = j; tap.i[1] = tap.i[2] = tap.i[3] = j + 1;
+      W[0] = 1.0 - t; W[1] = t;
+    } else {
+      tap.i[0] = std::max(j - 1, 0); tap.i[1] = j; tap.i[2] = j + 1; tap.i[3] = std::min(j + 2, P - 1);
+      const double t2 = t * t, t3 = t2 * t;
+      W[0] = (-t3 + 2.0 * t2 - t) / 2.0;
+      W[1] = (3.0 * t3 - 5.0 * t2 + 2.0) / 2.0;
+      W[2] = (-3.0 * t3 + 4.0 * t2 + t) / 2.0;
+      W[3] = (t3 - t2) / 2.0;
+    }
+  }
+  int last = 0;
+  for (int c = 0; c < 4; c++)
+    if (W[c] != 0.0) last = c;
+  volatile float sum = 0.f;   // (volatile: every partial sum exists as an f32, whatever the host compiler's excess precision)
+  for (int c = 0; c < 4; c++) {
+    if (c == last) {
+      tap.w[c] = 1.f - sum;
+      break;          // (the taps behind it weigh 0)
+    }
+    tap.w[c] = (float)W[c];
+    sum = sum + tap.w[c];
+  }
+  return tap;
+}
+
+std::vector<TrexPlanTap> build_plan_taps(const PlannerShape &p) {
+  std::vector<TrexPlanTap> taps((size_t)p.S);
+  for (int s = 0; s < p.S; s++) taps[s] = plan_tap(p.kind, p.P, (int64_t)s * (p.P - 1), p.S - 1);
+  return taps;
+}
+
+int plan_shift_key(const PlannerShape &p, int steps) {
+  if (steps < 0) throw Refusal("trex_planner_shift: steps " + std::to_string(steps) + " below 0");
+  return std::min(steps, p.S - 1);
+}
+
+std::vector<TrexPlanTap> build_plan_shift(const PlannerShape &p, int steps) {
+  const int64_t k = plan_shift_key(p, steps), end = (int64_t)(p.P - 1) * (p.S - 1);
+  std::vector<TrexPlanTap> taps((size_t)p.P);
+  for (int q = 0; q < p.P; q++) taps[q] = plan_tap(p.kind, p.P, std::min((int64_t)q * (p.S - 1) + k * (p.P - 1), end), p.S - 1);
+  return taps;
+}
+
+std::vector<float> build_plan_discount(int S, float gamma) {
+  std::vector<float> g((size_t)S + 1);
+  for (int s = 0; s <= S; s++) g[s] = (float)std::pow((double)gamma, s);
+  return g;
+}
+
+TrexPlanNoise build_plan_noise(const PlannerShape &p, const float *sigma, const float *lo, const float *hi, uint32_t env_offset) {
+  const std::string me = "trex_planner_set_noise: ";
+  if (!sigma || !lo || !hi) throw Refusal(me + "null argument");
+  TrexPlanNoise n;
+  for (int a = 0; a < TREX_PLAN_MAXACT; a++) { n.sigma[a] = 0.f; n.lo[a] = -INFINITY; n.hi[a] = INFINITY; }
+  for (int a = 0; a < p.A; a++) {
+    const std::string ck = me + "action " + std::to_string(a) + ": ";
+    if (!std::isfinite(sigma[a]) || sigma[a] < 0.f) throw Refusal(ck + "sigma is negative or not finite");
+    if (std::isnan(lo[a]) || std::isnan(hi[a])) throw Refusal(ck + "a limit is NaN");
+    if (lo[a] > hi[a]) throw Refusal(ck + "lo > hi");
+    n.sigma[a] = sigma[a]; n.lo[a] = lo[a]; n.hi[a] = hi[a];
+  }
+  check_env_offset(me, env_offset, p.N);
+  return n;
+}
+
+void check_plan_update(const PlannerShape &p, bool noise_set, bool reward, int64_t step_stride, int64_t env_stride, float gamma,
+                       float temperature) {
+  const std::string me = "trex_planner_update: ";
+  if (!noise_set) throw Refusal(me + "no noise is set (trex_planner_set_noise)");
+  if (!reward) throw Refusal(me + "reward is null");
+  if (step_stride < 1) throw Refusal(me + "step_stride below 1");
+  if (env_stride < 1) throw Refusal(me + "env_stride below 1");
+  if (!std::isfinite(gamma) || gamma < 0.f) throw Refusal(me + "gamma is negative or not finite");
+  if (!std::isfinite(temperature) || temperature < 0.f) throw Refusal(me + "temperature is negative or not finite");
+  // (S - 1) step_stride + (N - 1) env_stride must leave room for the byte count in 63 bits
+  if (step_stride > ((int64_t)1 << 40) || env_stride > ((int64_t)1 << 40)) throw Refusal(me + "a stride beyond 2^40");
+}
+
+size_t plan_column_bytes(const PlannerShape &p, int64_t step_stride, int64_t env_stride) {
+  return ((size_t)(p.S - 1) * (size_t)step_stride + (size_t)(p.N - 1) * (size_t)env_stride + 1) * sizeof(float);
+}
+
 }  // namespace trex

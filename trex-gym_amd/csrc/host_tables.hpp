@@ -1,6 +1,6 @@
 // The tables the kernels read and the layouts of the per-env state they write, as pure host arithmetic: everything the C-ABI computes
 // between its argument checks and its HIP calls.
-// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h, motion_limits.h, sensing_limits.h, start_state_limits.h, policy_limits.h and include/trex_batch.h, and nothing of HIP; it makes
+// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h, motion_limits.h, sensing_limits.h, start_state_limits.h, policy_limits.h, planner_limits.h and include/trex_batch.h, and nothing of HIP; it makes
 // no HIP call and knows no batch. It builds with plain g++ -std=c++17, as model.cpp does, so that tests/host/tables_harness.cpp runs
 // it under the sanitizers on a machine without a GPU. A refusal is a thrown Refusal whose text is the C-ABI's message, whole.
 #pragma once
@@ -18,6 +18,7 @@ struct float4;
 #include "model.hpp"
 #include "motion_limits.h"
 #include "observation_limits.h"
+#include "planner_limits.h"
 #include "policy_limits.h"
 #include "proximity_limits.h"
 #include "reward_limits.h"
@@ -233,6 +234,24 @@ struct PolicyMinibatchCall {
   float vf_coef;
 };
 void check_policy_minibatch(const PolicyShape *p, const PolicyMinibatchCall &c);
+
+// The planner (include/trex_planner.h): its sizes checked, its tap tables - the interpolation table, one tap set per step, and the
+// shift table of a `steps`, one per new knot -, the discount table of a gamma, the noise as the kernel reads it, and what the
+// calls refuse before any HIP call (the pointers as "is it there" flags).
+struct PlannerShape { int G = 0, K = 0, S = 0, P = 0, A = 0, kind = 0, N = 0; };
+PlannerShape check_planner_create(int groups, int samples, int horizon, int knots, int act_dim, int interpolation);
+// the four taps of the knot coordinate num / den (den 0: the constant), as the header defines them
+TrexPlanTap plan_tap(int kind, int P, int64_t num, int64_t den);
+std::vector<TrexPlanTap> build_plan_taps(const PlannerShape &p);
+// steps as the table is kept by: min(steps, S - 1)
+int plan_shift_key(const PlannerShape &p, int steps);
+std::vector<TrexPlanTap> build_plan_shift(const PlannerShape &p, int steps);
+std::vector<float> build_plan_discount(int S, float gamma);
+TrexPlanNoise build_plan_noise(const PlannerShape &p, const float *sigma, const float *lo, const float *hi, uint32_t env_offset);
+void check_plan_update(const PlannerShape &p, bool noise_set, bool reward, int64_t step_stride, int64_t env_stride, float gamma,
+                       float temperature);
+// the bytes a strided [S, N] column reaches: its last element ends it
+size_t plan_column_bytes(const PlannerShape &p, int64_t step_stride, int64_t env_stride);
 
 // trex_batch_render: the camera of include/trex_batch.h, checked, as the renderer's basis
 struct CameraBasis { float offset[3], fwd[3], right[3], up[3], tan_x, tan_y; };

@@ -439,7 +439,34 @@ def parse_args(argv=None):
     ap.add_argument("--dagger_beta", type=float, nargs="+", default=None, metavar=("B", "DECAY"),
                     help="with --distill: the probability B that an env follows the teacher during a rollout (default 1), "
                          "multiplied by DECAY (default 0.9) after every rollout")
+    ap.add_argument("--mpc", type=int, nargs=2, default=None, metavar=("SAMPLES", "HORIZON"),
+                    help="no training: control the envs with the sampling-based planner (trex_gym.planner) - SAMPLES rollouts of "
+                         "HORIZON steps per env and control step; --graphs replays a planning iteration, --frames writes PNGs")
+    ap.add_argument("--mpc_knots", type=int, default=None, metavar="P", help="with --mpc: spline knots of an action sequence (default min(HORIZON, 6))")
+    ap.add_argument("--mpc_sigma", type=float, default=None, metavar="X", help="with --mpc: the standard deviation of a knot's noise (default 0.1)")
+    ap.add_argument("--mpc_temperature", type=float, default=None, metavar="L",
+                    help="with --mpc: the temperature of the return weighting; 0 keeps the best sample alone (default 0.1)")
+    ap.add_argument("--mpc_iterations", type=int, default=None, metavar="I", help="with --mpc: sample - rollout - update rounds per control step (default 1)")
+    ap.add_argument("--mpc_steps", type=int, default=None, metavar="T", help="with --mpc: control steps to run (default 100)")
+    ap.add_argument("--save_clip", type=str, default=None, metavar="FILE.npz",
+                    help="with --mpc: the states the envs went through, [T, N, state width] with the frame time, for motion.Clip.from_states")
     args = ap.parse_args(argv)
+    mpc_flags = ("mpc_knots", "mpc_sigma", "mpc_temperature", "mpc_iterations", "mpc_steps", "save_clip")
+    if args.mpc is None and any(getattr(args, f) is not None for f in mpc_flags):
+        ap.error("--mpc_knots, --mpc_sigma, --mpc_temperature, --mpc_iterations, --mpc_steps and --save_clip need --mpc")
+    if args.mpc is not None:
+        if args.save is not None or args.play or args.export is not None or args.distill is not None or args.critic is not None \
+                or args.noptepochs is not None or args.preset != "reference":
+            ap.error("--mpc plans and does not train: not with --save, --play, --export, --distill, --critic, --noptepochs or --preset")
+        if not (1 <= args.mpc[0] <= 4096 and 1 <= args.mpc[1] <= 256):
+            ap.error("--mpc: 1 <= SAMPLES <= 4096, 1 <= HORIZON <= 256")
+        if args.mpc_knots is not None and not 1 <= args.mpc_knots <= min(args.mpc[1], 32):
+            ap.error("--mpc_knots: 1 <= P <= min(HORIZON, 32)")
+        if (args.mpc_sigma is not None and not (args.mpc_sigma >= 0.0 and math.isfinite(args.mpc_sigma))) or \
+                (args.mpc_temperature is not None and not (args.mpc_temperature >= 0.0 and math.isfinite(args.mpc_temperature))):
+            ap.error("--mpc_sigma and --mpc_temperature must be finite and not negative")
+        if (args.mpc_iterations is not None and args.mpc_iterations < 1) or (args.mpc_steps is not None and args.mpc_steps < 1):
+            ap.error("--mpc_iterations and --mpc_steps: at least 1")
     if args.distill is None and (args.teacher_rows != "clean" or args.distill_loss != "kl" or args.dagger_beta is not None):
         ap.error("--teacher_rows, --distill_loss and --dagger_beta need --distill")
     if args.dagger_beta is not None and (len(args.dagger_beta) > 2 or not all(0.0 <= x <= 1.0 for x in args.dagger_beta)):
@@ -561,9 +588,52 @@ def environment_from_args(args):
     return env
 
 
+def mpc_args(args):
+    """the dict for run_mpc(...) of the --mpc flags, None without --mpc"""
+    if args.mpc is None:
+        return None
+    pick = lambda v, default: default if v is None else v
+    return dict(samples=args.mpc[0], horizon=args.mpc[1], knots=args.mpc_knots, sigma=pick(args.mpc_sigma, 0.1),
+                temperature=pick(args.mpc_temperature, 0.1), iterations=pick(args.mpc_iterations, 1), steps=pick(args.mpc_steps, 100),
+                save_clip=args.save_clip, frames=args.frames, graphs=args.graphs, seed=args.random_seed)
+
+
+def run_mpc(env, samples, horizon, knots=None, sigma=0.1, temperature=0.1, iterations=1, steps=100, save_clip=None, frames=None,
+            graphs=False, seed=0, log=print, env_index=0, frame_size=(960, 720)):
+    """Control every env of `env` with trex_gym.planner.Planner for `steps` control steps -> (states [T, N, W], rewards [T, N]).
+    save_clip: an .npz of the states and the frame time, for motion.Clip.from_states; frames: a directory for one PNG per step."""
+    import numpy as np
+    from .planner import Planner
+    env.reset_tensor()
+    planner = Planner(env, samples, horizon, knots=knots, sigma=sigma, temperature=temperature, iterations=iterations, seed=seed,
+                      use_graphs=graphs)
+    if frames is not None:
+        Image = _png_writer()
+        os.makedirs(frames, exist_ok=True)
+    states, rewards = [], []
+    for t in range(int(steps)):
+        states.append(env.get_state())
+        _, rew, _ = planner.step()
+        rewards.append(rew.clone())
+        if frames is not None:
+            rgb = env.render_tensor([env_index], frame_size[0], frame_size[1], None)[0].cpu().numpy()
+            Image.fromarray(rgb).save(os.path.join(frames, "%05d-of-%05d.png" % (t, int(steps))))
+    states, rewards = torch.stack(states).cpu().numpy(), torch.stack(rewards).cpu().numpy()
+    log("MPC: %d steps, %d samples x %d steps per plan, mean return %.3f" % (len(rewards), samples, horizon, float(rewards.sum(0).mean())))
+    if save_clip:
+        dt = env.model.get_param("dt") * env.model.get_param("substeps")
+        np.savez_compressed(save_clip, states=states.astype(np.float32), frame_dt=np.float64(dt))
+    planner.close()
+    return states, rewards
+
+
 def main(argv=None):
     args = parse_args(argv)
     env = environment_from_args(args)
+    mpc = mpc_args(args)
+    if mpc is not None:
+        run_mpc(env, **mpc)
+        return
     agent, _ = train(env, args.num_timesteps, args.random_seed, args.nsteps, args.noptepochs, args.save, use_graphs=args.graphs,
                      preset=args.preset, distill=distill_args(args))
     if args.play:

@@ -1905,9 +1905,7 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
 // v_mov 0 / v_add per point). For the same reason the liveness of the points still to come needs nothing but
 // the new y: lam != 0 is settled per sweep (`lamnz`), and y > -lam is ONE compare against `thr` = -lam on the
 // normal lanes of the live slots, +inf elsewhere (formed per sweep), so vcc needs no masking.
-#define TREX_POINT_TEXT(P)                                                                             \
-               "s_bitcmp1_b64 %[al], %[ln" #P "]\n\t"                                                  \
-               "s_cbranch_scc0 " #P "f\n\t"                                                            \
+#define TREX_POINT_ROWS(P)                                                                             \
                /* normal row, bounds shifted by the impulse: d = max(y, -lam); the new impulse lam + d */ \
                "v_max_f32_e64 %[d], %[y], -%[lam]\n\t"                                                 \
                "v_add_f32_e32 %[t], %[lam], %[d]\n\t"                                                  \
@@ -1934,8 +1932,46 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
                "v_writelane_b32 %[dv], %[sd], %[ly" #P "]\n\t"                                         \
                /* which of the points still to come can change anything now */                         \
                "v_cmp_gt_f32_e32 vcc, %[y], %[thr]\n\t"                   /* lam + y > 0 */           \
-               "s_or_b64 %[al], vcc, %[lnz]\n\t"                                                       \
+               "s_or_b64 %[al], vcc, %[lnz]\n\t"
+// The slot WALK (the diagnostics instantiation keeps it: the in-tree reference of the dispatch below): every slot's rows behind a
+// test of its bit in `alive`.
+#define TREX_POINT_TEXT(P)                                                                             \
+               "s_bitcmp1_b64 %[al], %[ln" #P "]\n\t"                                                  \
+               "s_cbranch_scc0 " #P "f\n\t"                                                            \
+               TREX_POINT_ROWS(P)                                                                      \
                #P ":\n\t"
+// The slot DISPATCH (every other instantiation): ONE statement holds the rows of all 13 slots as blocks of equal size, and a
+// computed jump goes from the head of the statement, and from the end of every live block, straight to the lowest live slot
+// still to come - a live point costs one taken branch, a dead one nothing. `alive` is formed anew after every block (above),
+// so the dispatch may use it up: shifted right by the lane after the block's own three, its lowest set bit is 3 x the number
+// of slots to pass over (normal lanes are 3 apart, other lanes never have a bit); no bit left ends the statement. s_getpc
+// yields the address of the instruction that follows it, 12 bytes before the next block; the assembler checks that and the
+// size of every block (labels and directives only), as it does for the limit rows' table.
+#define TREX_POINT_JUMP                                                                                \
+               "s_ff1_i32_b64 %[sd], %[al]\n\t"                                                        \
+               "s_mul_i32 %[sd], %[sd], 56\n\t"                 /* block bytes / 3 */                 \
+               "s_addk_i32 %[sd], 12\n\t"                                                              \
+               "s_getpc_b64 vcc\n\t"                                                                   \
+               "77:\n\t"                                                                               \
+               "s_add_u32 vcc_lo, vcc_lo, %[sd]\n\t"                                                   \
+               "s_addc_u32 vcc_hi, vcc_hi, 0\n\t"                                                      \
+               "s_setpc_b64 vcc\n\t"                                                                   \
+               ".if (. - 77b) != 12\n\t.error \"point dispatch: the next block is not 12 bytes after the address s_getpc_b64 returns\"\n\t.endif\n\t"
+#define TREX_POINT_HEAD                                                                                \
+               "s_lshr_b64 %[al], %[al], %[ln0]\n\t"                                                   \
+               TREX_POINT_JUMP                                                                         \
+               "70:\n\t"
+#define TREX_POINT_BLOCK_END(K)                                                                        \
+               ".if (. - 70b) != 168 * " #K "\n\t.error \"point dispatch: block " #K " does not end 168 * " #K " bytes after the first\"\n\t.endif\n\t"
+#define TREX_POINT_BLOCK(P, K)                                                                         \
+               TREX_POINT_ROWS(P)                                                                      \
+               "s_lshr_b64 %[al], %[al], %[ln" #P "] + 3\n\t"                                          \
+               "s_cbranch_scc0 79f\n\t"                                                                \
+               TREX_POINT_JUMP                                                                         \
+               TREX_POINT_BLOCK_END(K)
+#define TREX_POINT_LAST(P)                                                                             \
+               TREX_POINT_ROWS(P)                                                                      \
+               "79:\n\t"
 #define TREX_POINT_OUTS [y] "+v"(y), [dv] "+v"(dvc), [al] "+s"(alive), [t] "=&v"(pt_), [d] "=&v"(pd_), [hi] "=&v"(ph_), \
                         [snl] "=&s"(psn_), [sd] "=&s"(psd_)
 #define TREX_POINT_INS [lam] "v"(lam), [mu] "v"(mu_v), [thr] "v"(thr), [lnz] "s"(lamnz)
@@ -1949,6 +1985,56 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
                : "vcc", "scc");
 #define TREX_POINTS1(S)                                                                                \
   asm volatile(TREX_POINT_TEXT(0) : TREX_POINT_OUTS : TREX_POINT_INS, TREX_POINT_OPS(0, S) : "vcc", "scc");
+#define TREX_POINTS_DISPATCH                                                                           \
+  static_assert(MAXC == 13, "the dispatch below is written out for 13 point slots");                   \
+  asm volatile(TREX_POINT_HEAD                                                                         \
+               TREX_POINT_BLOCK(0, 1) TREX_POINT_BLOCK(1, 2) TREX_POINT_BLOCK(2, 3) TREX_POINT_BLOCK(3, 4)         \
+               TREX_POINT_BLOCK(4, 5) TREX_POINT_BLOCK(5, 6) TREX_POINT_BLOCK(6, 7) TREX_POINT_BLOCK(7, 8)         \
+               TREX_POINT_BLOCK(8, 9) TREX_POINT_BLOCK(9, 10) TREX_POINT_BLOCK(10, 11) TREX_POINT_BLOCK(11, 12)    \
+               TREX_POINT_LAST(12)                                                                     \
+               : TREX_POINT_OUTS                                                                       \
+               : TREX_POINT_INS, TREX_POINT_OPS(0, 0), TREX_POINT_OPS(1, 1), TREX_POINT_OPS(2, 2), TREX_POINT_OPS(3, 3),     \
+                 TREX_POINT_OPS(4, 4), TREX_POINT_OPS(5, 5), TREX_POINT_OPS(6, 6), TREX_POINT_OPS(7, 7), TREX_POINT_OPS(8, 8), \
+                 TREX_POINT_OPS(9, 9), TREX_POINT_OPS(10, 10), TREX_POINT_OPS(11, 11), TREX_POINT_OPS(12, 12)       \
+               : "vcc", "scc");
+// The point rows of one sweep: the live point slots, in order (dead slots have no bit in `alive`). KNOWN: the caller's loop is
+// only entered with point rows (nrm_mask != 0), so the test is not repeated per sweep. WALK: by the slot walk.
+#define TREX_POINT_SWEEP(KNOWN, WALK)                                                                  \
+        {                                                                                              \
+          unsigned long long alive = 0ull, lamnz = 0ull;                                               \
+          if ((KNOWN) || nrm_mask != 0ull) {   /* (an airborne env has no point rows at all) */        \
+            lamnz = nrm_mask & __ballot(lam != 0.f);                                                   \
+            alive = lamnz | (nrm_mask & __ballot(y > -lam));                                           \
+          }                                                                                            \
+          TREX_STAMP_ALIVE                                                                             \
+          if (alive != 0ull) {                                                                         \
+            float pt_, pd_, ph_;                                                                       \
+            int psn_, psd_;                                                                            \
+            const float thr = is_nrm ? -lam : __builtin_inff();                                        \
+            float dvc = 0.f;      /* the impulse changes of this sweep's point rows, by lane */        \
+            if constexpr (WALK) {                                                                      \
+              /* (a dead point costs its bit test and a TAKEN branch, ~16 cycles, and of the slots of an env on 12 points one \
+                 or two are alive in a sweep: a group of slots without a live one is passed in one test) */ \
+              constexpr unsigned long long NB = 1ull << CLANE0;      /* normal row of slot S: lane CLANE0 + 3 S */ \
+              constexpr unsigned long long G0 = NB * 0111ull, G3 = G0 << 9, G6 = NB << 18, G7 = G0 << 21, G10 = G0 << 30; \
+              if ((alive & (G0 | G3 | G6)) != 0ull) {                                                  \
+                if ((alive & G0) != 0ull) { TREX_POINTS3(0) }                                          \
+                if ((alive & G3) != 0ull) { TREX_POINTS3(3) }                                          \
+                if ((alive & G6) != 0ull) { TREX_POINTS1(6) }                                          \
+              }                                                                                        \
+              if ((alive & G7) != 0ull) { TREX_POINTS3(7) }                                            \
+              if ((alive & G10) != 0ull) { TREX_POINTS3(10) }                                          \
+            } else {                                                                                   \
+              TREX_POINTS_DISPATCH                                                                     \
+            }                                                                                          \
+            lam += dvc;                                                                                \
+          }                                                                                            \
+        }
+#if TREX_STAMPS   // per wave: point slots alive / holding an impulse at the start of a sweep, summed over the launch
+#define TREX_STAMP_ALIVE stamp_alive += __popcll(alive); stamp_lamnz += __popcll(lamnz);
+#else
+#define TREX_STAMP_ALIVE
+#endif
       // lanes that hold the normal row of a live point slot
       float mu_v = mu;        // the friction coefficient as a vector operand of the point blocks
       if (PAIR) asm volatile("" : "+v"(mu_v));     // (made HERE: hoisted out of the substep loop it was a register carried - and spilled - through the whole kernel)
@@ -1957,6 +2043,170 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
 #if TREX_PRIO_MODE == 1
       set_sweep_priority(nc);
 #endif
+#define TREX_MOTOR_SWEEP                                                                                \
+        { \
+          static_assert(NJMAX == 25, "the blocks below are written out for 25 motor rows"); \
+          int sa_, sb_; \
+          float d_; \
+          const float blo = (-mhi - lam) + lam_c, bhi = (mhi - lam) + lam_c; \
+          asm volatile("v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "s_nop 0\n\t" \
+                       "v_readlane_b32 %3, %2, 1\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %7\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %3, 1\n\t" \
+                       "v_readlane_b32 %4, %2, 2\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %4, %8\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %4, 2\n\t" \
+                       "v_readlane_b32 %3, %2, 3\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %9\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %3, 3\n\t" \
+                       "v_readlane_b32 %4, %2, 4\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %4, %10\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %4, 4\n\t" \
+                       "v_readlane_b32 %3, %2, 5\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %11\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %3, 5\n\t" \
+                       "v_readlane_b32 %4, %2, 6\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %4, %12\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %4, 6\n\t" \
+                       "v_readlane_b32 %3, %2, 7\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %13\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %3, 7\n\t" \
+                       "v_readlane_b32 %4, %2, 8\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %4, %14\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %4, 8\n\t" \
+                       "v_readlane_b32 %3, %2, 9\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %15\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %3, 9\n\t" \
+                       "v_readlane_b32 %4, %2, 10\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %4, %16\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %4, 10\n\t" \
+                       "v_readlane_b32 %3, %2, 11\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %17\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %3, 11\n\t" \
+                       "v_readlane_b32 %4, %2, 12\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %4, %18\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %4, 12\n\t" \
+                       "v_readlane_b32 %3, %2, 13\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %19\n\t" \
+                       : "+v"(y), "+v"(dvec), "=&v"(d_), "=&s"(sa_), "=&s"(sb_) \
+                       : "v"(blo), "v"(bhi), "v"(Bm[0]), "v"(Bm[1]), "v"(Bm[2]), "v"(Bm[3]), "v"(Bm[4]), "v"(Bm[5]), "v"(Bm[6]), "v"(Bm[7]), "v"(Bm[8]), "v"(Bm[9]), "v"(Bm[10]), "v"(Bm[11]), "v"(Bm[12])); \
+          asm volatile("v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %3, 13\n\t" \
+                       "v_readlane_b32 %4, %2, 14\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %4, %7\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %4, 14\n\t" \
+                       "v_readlane_b32 %3, %2, 15\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %8\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %3, 15\n\t" \
+                       "v_readlane_b32 %4, %2, 16\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %4, %9\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %4, 16\n\t" \
+                       "v_readlane_b32 %3, %2, 17\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %10\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %3, 17\n\t" \
+                       "v_readlane_b32 %4, %2, 18\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %4, %11\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %4, 18\n\t" \
+                       "v_readlane_b32 %3, %2, 19\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %12\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %3, 19\n\t" \
+                       "v_readlane_b32 %4, %2, 20\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %4, %13\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %4, 20\n\t" \
+                       "v_readlane_b32 %3, %2, 21\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %14\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %3, 21\n\t" \
+                       "v_readlane_b32 %4, %2, 22\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %4, %15\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %4, 22\n\t" \
+                       "v_readlane_b32 %3, %2, 23\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %16\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %3, 23\n\t" \
+                       "v_readlane_b32 %4, %2, 24\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %4, %17\n\t" \
+                       "v_med3_f32 %2, %0, %5, %6\n\t" \
+                       "v_writelane_b32 %1, %4, 24\n\t" \
+                       "v_readlane_b32 %3, %2, 25\n\t" \
+                       "s_nop 1\n\t" \
+                       "v_fmac_f32_e32 %0, %3, %18\n\t" \
+                       "v_writelane_b32 %1, %3, 25\n\t" \
+                       : "+v"(y), "+v"(dvec), "=&v"(d_), "+s"(sa_), "=&s"(sb_) \
+                       : "v"(blo), "v"(bhi), "v"(Bm[13]), "v"(Bm[14]), "v"(Bm[15]), "v"(Bm[16]), "v"(Bm[17]), "v"(Bm[18]), "v"(Bm[19]), "v"(Bm[20]), "v"(Bm[21]), "v"(Bm[22]), "v"(Bm[23]), "v"(Bm[24])); \
+          {   /* lam += dvec, compensated (Kahan): lam - lam_c is the sum of the d's the other rows have seen */ \
+            const float y_ = __int_as_float(dvec) - lam_c, t_ = lam + y_; \
+            lam_c = (t_ - lam) - y_; \
+            lam = t_; \
+          } \
+        }
+      // One sweep loop per SOLVE SHAPE, chosen once per substep (both masks are wave-uniform and fixed over a substep's sweeps):
+      // M - no joint on a stop and no point rows (an airborne env): the motor block between its bounds and its commit, nothing else;
+      // P - no joint on a stop: motor block and point rows;  G - the general loop: limit rows, motor block, point rows.
+      // The diagnostics instantiation always takes G, with the point slots walked: the in-tree reference of the others (bitwise).
+      // (A warm solve starts with impulses on point rows only: without point rows - M - it starts from zero like a cold one.)
+      // The step_many instantiations with the actuator model keep G alone (with the dispatch): with three loops the allocator
+      // spilled one vector register there (8 B of scratch per lane; every other instantiation: none, as before).
+      constexpr bool SHAPE_LOOPS = !DEBUG && !(ACT && MULTI);
+      if (SHAPE_LOOPS && lim_mask == 0u) {
+        if (nrm_mask == 0ull) {
+#pragma unroll 1
+          for (int it = 0; it < iters; it++) {
+            TREX_MOTOR_SWEEP
+          }
+        } else {
+#pragma unroll 1
+          for (int it = 0; it < iters; it++) {
+            TREX_MOTOR_SWEEP
+            TREX_POINT_SWEEP(true, false)
+          }
+        }
+      } else {
 #pragma unroll 1
       for (int it = 0; it < iters; it++) {
         // limit rows: the row of joint j rides on motor lane j, whose y gives dv_j / diag = rhs - y
@@ -2086,177 +2336,22 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
         // airborne env - z is as large as a saturated impulse, y is small; a speculative UNCLAMPED block - d_j = y_j,
         // committed only if no bound was crossed - runs twice too often: under random actions 7 percent of the motor
         // rows sit at 3e5 N m.)
-        {
-          static_assert(NJMAX == 25, "the blocks below are written out for 25 motor rows");
-          int sa_, sb_;
-          float d_;
-          const float blo = (-mhi - lam) + lam_c, bhi = (mhi - lam) + lam_c;
-          asm volatile("v_med3_f32 %2, %0, %5, %6\n\t"
-                       "s_nop 0\n\t"
-                       "v_readlane_b32 %3, %2, 1\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %7\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %3, 1\n\t"
-                       "v_readlane_b32 %4, %2, 2\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %4, %8\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %4, 2\n\t"
-                       "v_readlane_b32 %3, %2, 3\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %9\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %3, 3\n\t"
-                       "v_readlane_b32 %4, %2, 4\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %4, %10\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %4, 4\n\t"
-                       "v_readlane_b32 %3, %2, 5\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %11\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %3, 5\n\t"
-                       "v_readlane_b32 %4, %2, 6\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %4, %12\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %4, 6\n\t"
-                       "v_readlane_b32 %3, %2, 7\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %13\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %3, 7\n\t"
-                       "v_readlane_b32 %4, %2, 8\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %4, %14\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %4, 8\n\t"
-                       "v_readlane_b32 %3, %2, 9\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %15\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %3, 9\n\t"
-                       "v_readlane_b32 %4, %2, 10\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %4, %16\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %4, 10\n\t"
-                       "v_readlane_b32 %3, %2, 11\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %17\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %3, 11\n\t"
-                       "v_readlane_b32 %4, %2, 12\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %4, %18\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %4, 12\n\t"
-                       "v_readlane_b32 %3, %2, 13\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %19\n\t"
-                       : "+v"(y), "+v"(dvec), "=&v"(d_), "=&s"(sa_), "=&s"(sb_)
-                       : "v"(blo), "v"(bhi), "v"(Bm[0]), "v"(Bm[1]), "v"(Bm[2]), "v"(Bm[3]), "v"(Bm[4]), "v"(Bm[5]), "v"(Bm[6]), "v"(Bm[7]), "v"(Bm[8]), "v"(Bm[9]), "v"(Bm[10]), "v"(Bm[11]), "v"(Bm[12]));
-          asm volatile("v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %3, 13\n\t"
-                       "v_readlane_b32 %4, %2, 14\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %4, %7\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %4, 14\n\t"
-                       "v_readlane_b32 %3, %2, 15\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %8\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %3, 15\n\t"
-                       "v_readlane_b32 %4, %2, 16\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %4, %9\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %4, 16\n\t"
-                       "v_readlane_b32 %3, %2, 17\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %10\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %3, 17\n\t"
-                       "v_readlane_b32 %4, %2, 18\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %4, %11\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %4, 18\n\t"
-                       "v_readlane_b32 %3, %2, 19\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %12\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %3, 19\n\t"
-                       "v_readlane_b32 %4, %2, 20\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %4, %13\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %4, 20\n\t"
-                       "v_readlane_b32 %3, %2, 21\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %14\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %3, 21\n\t"
-                       "v_readlane_b32 %4, %2, 22\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %4, %15\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %4, 22\n\t"
-                       "v_readlane_b32 %3, %2, 23\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %16\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %3, 23\n\t"
-                       "v_readlane_b32 %4, %2, 24\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %4, %17\n\t"
-                       "v_med3_f32 %2, %0, %5, %6\n\t"
-                       "v_writelane_b32 %1, %4, 24\n\t"
-                       "v_readlane_b32 %3, %2, 25\n\t"
-                       "s_nop 1\n\t"
-                       "v_fmac_f32_e32 %0, %3, %18\n\t"
-                       "v_writelane_b32 %1, %3, 25\n\t"
-                       : "+v"(y), "+v"(dvec), "=&v"(d_), "+s"(sa_), "=&s"(sb_)
-                       : "v"(blo), "v"(bhi), "v"(Bm[13]), "v"(Bm[14]), "v"(Bm[15]), "v"(Bm[16]), "v"(Bm[17]), "v"(Bm[18]), "v"(Bm[19]), "v"(Bm[20]), "v"(Bm[21]), "v"(Bm[22]), "v"(Bm[23]), "v"(Bm[24]));
-          {   // lam += dvec, compensated (Kahan): lam - lam_c is the sum of the d's the other rows have seen
-            const float y_ = __int_as_float(dvec) - lam_c, t_ = lam + y_;
-            lam_c = (t_ - lam) - y_;
-            lam = t_;
-          }
-        }
-        // the live point slots, in order (dead slots have no bit in `alive`)
-        unsigned long long alive = 0ull, lamnz = 0ull;
-        if (nrm_mask != 0ull) {   // (an airborne env has no point rows at all)
-          lamnz = nrm_mask & __ballot(lam != 0.f);
-          alive = lamnz | (nrm_mask & __ballot(y > -lam));
-        }
-#if TREX_STAMPS   // per wave: point slots alive / holding an impulse at the start of a sweep, summed over the launch
-        stamp_alive += __popcll(alive); stamp_lamnz += __popcll(lamnz);
-#endif
-        if (alive != 0ull) {
-          float pt_, pd_, ph_;
-          int psn_, psd_;
-          const float thr = is_nrm ? -lam : __builtin_inff();
-          float dvc = 0.f;      // the impulse changes of this sweep's point rows, by lane
-          // (a dead point costs its bit test and a TAKEN branch, ~16 cycles, and of the slots of an env on 12 points one
-          // or two are alive in a sweep: a group of slots without a live one is passed in one test)
-          constexpr unsigned long long NB = 1ull << CLANE0;      // normal row of slot S: lane CLANE0 + 3 S
-          constexpr unsigned long long G0 = NB * 0111ull, G3 = G0 << 9, G6 = NB << 18, G7 = G0 << 21, G10 = G0 << 30;
-          if ((alive & (G0 | G3 | G6)) != 0ull) {
-            if ((alive & G0) != 0ull) { TREX_POINTS3(0) }
-            if ((alive & G3) != 0ull) { TREX_POINTS3(3) }
-            if ((alive & G6) != 0ull) { TREX_POINTS1(6) }
-          }
-          if ((alive & G7) != 0ull) { TREX_POINTS3(7) }
-          if ((alive & G10) != 0ull) { TREX_POINTS3(10) }
-          lam += dvc;
-        }
+        TREX_MOTOR_SWEEP
+        TREX_POINT_SWEEP(false, DEBUG)
+      }
       }
 #undef TREX_ROW
+#undef TREX_MOTOR_SWEEP
+#undef TREX_POINT_SWEEP
+#undef TREX_STAMP_ALIVE
+#undef TREX_POINTS_DISPATCH
+#undef TREX_POINT_ROWS
 #undef TREX_POINT_TEXT
+#undef TREX_POINT_JUMP
+#undef TREX_POINT_HEAD
+#undef TREX_POINT_BLOCK
+#undef TREX_POINT_BLOCK_END
+#undef TREX_POINT_LAST
 #undef TREX_POINTS3
 #undef TREX_POINTS1
       lam -= lam_c;

@@ -5,8 +5,10 @@
 #include <memory>
 
 #include "../../include/trex_policy.h"
+#include "../../include/trex_symmetry.h"
 #include "internal.hpp"
 #include "policy_launch.h"
+#include "symmetry.h"
 
 using namespace trex_policy;
 
@@ -473,6 +475,31 @@ int trex_policy_distill_minibatch_grad(TrexPolicy *p, const float *theta_dev, fl
   c.num_samples = num_samples; c.perm = perm_dev; c.first = first; c.mb = mb; c.kind = kind; c.vf_coef = vf_coef;
   c.grad_scale = grad_scale; c.loss_sums = loss_sums_dev; c.stream = stream;
   return run_minibatch(p, c);
+}
+
+// include/trex_symmetry.h: the moments of a block become those of the stream that holds every row and its mirror image
+int trex_policy_symmetrize_stats(TrexPolicy *p, const TrexMirrorTable *obs_table, const TrexMirrorTable *critic_table, void *stream) {
+  // (the moments launch is ONE workgroup with a lane per column: a policy's rows, the critic's too, must fit it)
+  static_assert(POLICY_MAX_OBS <= TREX_MIRROR_BLOCK, "mirror_moments_kernel takes a column per lane of one workgroup");
+  const std::string me = "trex_policy_symmetrize_stats: ";
+  if (!p || !obs_table) return fail(TREX_E_INVALID, me + "null argument");
+  int width = 0, device = 0, width_v = 0, device_v = p->device;
+  const uint32_t *words = trex_mirror_table_words(obs_table, &width, &device);
+  const uint32_t *words_v = critic_table ? trex_mirror_table_words(critic_table, &width_v, &device_v) : nullptr;
+  if (width != p->D) return fail(TREX_E_INVALID, me + "the obs table is " + std::to_string(width) + " wide, the policy's rows " + std::to_string(p->D));
+  if (critic_table && !p->Dv) return fail(TREX_E_INVALID, me + "no critic width is set (trex_policy_set_critic)");
+  if (critic_table && width_v != p->Dv)
+    return fail(TREX_E_INVALID, me + "the critic table is " + std::to_string(width_v) + " wide, the critic's rows " + std::to_string(p->Dv));
+  if (device != p->device || device_v != p->device) return fail(TREX_E_INVALID, me + "a table lives on another device than the policy");
+  TrexDeviceGuard guard(p->device);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(trex_launch_mirror_moments(words, p->obs.stats.as<double>(), p->D, s));
+  HIP_TRY(trex_launch_policy_refresh_norm(p->obs.stats.as<double>(), p->obs.norm.as<float>(), p->D, p->epsilon, s));
+  if (critic_table) {
+    HIP_TRY(trex_launch_mirror_moments(words_v, p->critic.stats.as<double>(), p->Dv, s));
+    HIP_TRY(trex_launch_policy_refresh_norm(p->critic.stats.as<double>(), p->critic.norm.as<float>(), p->Dv, p->epsilon, s));
+  }
+  return TREX_OK;
 }
 
 }  // extern "C"

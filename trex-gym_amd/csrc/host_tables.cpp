@@ -973,4 +973,288 @@ size_t plan_column_bytes(const PlannerShape &p, int64_t step_stride, int64_t env
   return ((size_t)(p.S - 1) * (size_t)step_stride + (size_t)(p.N - 1) * (size_t)env_stride + 1) * sizeof(float);
 }
 
+// ---- the mirror maps (include/trex_symmetry.h)
+
+MirrorWords build_mirror_words(const int32_t *src, const int8_t *sign, int width) {
+  const std::string me = "trex_mirror_table_create: ";
+  if (!src || !sign) throw Refusal(me + "null argument");
+  if (width < 1 || width > TREX_MIRROR_MAXWIDTH)
+    throw Refusal(me + "width " + std::to_string(width) + " outside [1, " + std::to_string(TREX_MIRROR_MAXWIDTH) + "]");
+  MirrorWords t;
+  t.word.resize(width);
+  std::vector<char> taken(width, 0);
+  for (int c = 0; c < width; c++) {
+    const std::string col = me + "column " + std::to_string(c) + ": ";
+    if (src[c] < 0 || src[c] >= width) throw Refusal(col + "src " + std::to_string(src[c]) + " outside [0, width)");
+    if (taken[src[c]]) throw Refusal(col + "src " + std::to_string(src[c]) + " is named twice: src is no permutation");
+    if (sign[c] != 1 && sign[c] != -1) throw Refusal(col + "sign " + std::to_string((int)sign[c]) + " is neither +1 nor -1");
+    taken[src[c]] = 1;
+    t.word[c] = (uint32_t)src[c] | (sign[c] < 0 ? TREX_MIRROR_NEG : 0u);
+  }
+  t.involution = true;
+  for (int c = 0; c < width; c++) t.involution = t.involution && src[src[c]] == c && sign[src[c]] == sign[c];
+  return t;
+}
+
+void check_mirror_rows(int table_width, const void *in, int in_stride, const void *out, int out_stride, int n, int width) {
+  const std::string me = "trex_mirror_rows: ";
+  if (!in || !out) throw Refusal(me + "null argument");
+  if (n < 1) throw Refusal(me + "n " + std::to_string(n) + " below 1");
+  if (width != table_width) throw Refusal(me + "width " + std::to_string(width) + " is not the table's " + std::to_string(table_width));
+  if (in_stride < width || out_stride < width) throw Refusal(me + "a stride below the width");
+  if ((int64_t)n * std::max(in_stride, out_stride) >= (int64_t)1 << 31)
+    throw Refusal(me + "n x stride is beyond 2^31: an index would not fit 32 bits");
+  if (in == out && in_stride == out_stride) return;      // in place: a row is read completely before any of it is stored
+  if (ranges_overlap(in, row_block_bytes((size_t)n, in_stride, width), out, row_block_bytes((size_t)n, out_stride, width)))
+    throw Refusal(me + "in and out overlap (only in == out with equal strides may)");
+}
+
+void check_mirror_augment(int obs_width, int act_width, int critic_width, bool has_critic_table, bool buffers, bool obs_v,
+                          int64_t num_samples, int D, int A, int Dv) {
+  const std::string me = "trex_mirror_augment: ";
+  if (!buffers) throw Refusal(me + "null argument");
+  if (has_critic_table != obs_v || has_critic_table != (Dv != 0))
+    throw Refusal(me + "critic_table, obs_v and Dv go together: all given, or NULL, NULL and 0");
+  if (num_samples < 1) throw Refusal(me + "num_samples " + std::to_string(num_samples) + " below 1");
+  if (D != obs_width) throw Refusal(me + "D " + std::to_string(D) + " is not the obs table's width " + std::to_string(obs_width));
+  if (A != act_width) throw Refusal(me + "A " + std::to_string(A) + " is not the act table's width " + std::to_string(act_width));
+  if (has_critic_table && Dv != critic_width)
+    throw Refusal(me + "Dv " + std::to_string(Dv) + " is not the critic table's width " + std::to_string(critic_width));
+  if (num_samples >= ((int64_t)1 << 30) / std::max(D, std::max(A, std::max(Dv, 1))))
+    throw Refusal(me + "2 num_samples x the widest width is beyond 2^31: an index would not fit 32 bits");
+}
+
+namespace {
+
+struct Frame { double R[9], t[3]; };     // child <- in parent: x_parent = R x_child + t
+Frame frame_mul(const Frame &a, const Frame &b) {
+  Frame c;
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) c.R[3 * i + j] = a.R[3 * i] * b.R[j] + a.R[3 * i + 1] * b.R[3 + j] + a.R[3 * i + 2] * b.R[6 + j];
+    c.t[i] = a.R[3 * i] * b.t[0] + a.R[3 * i + 1] * b.t[1] + a.R[3 * i + 2] * b.t[2] + a.t[i];
+  }
+  return c;
+}
+Frame frame_inverse(const Frame &a) {
+  Frame c;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) c.R[3 * i + j] = a.R[3 * j + i];
+  for (int i = 0; i < 3; i++) c.t[i] = -(c.R[3 * i] * a.t[0] + c.R[3 * i + 1] * a.t[1] + c.R[3 * i + 2] * a.t[2]);
+  return c;
+}
+Frame frame_of(const Mat3 &R, const Vec3 &t) {
+  Frame c;
+  std::copy(R.m, R.m + 9, c.R);
+  c.t[0] = t.x; c.t[1] = t.y; c.t[2] = t.z;
+  return c;
+}
+void rotate(const Frame &f, const Vec3 &v, bool translate, double out[3]) {
+  for (int i = 0; i < 3; i++) out[i] = f.R[3 * i] * v.x + f.R[3 * i + 1] * v.y + f.R[3 * i + 2] * v.z + (translate ? f.t[i] : 0.0);
+}
+double dist3(const double a[3], const double b[3]) {
+  return std::sqrt((a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1]) + (a[2] - b[2]) * (a[2] - b[2]));
+}
+
+// every body's frame at q = 0 in URDF link 0's frame
+std::vector<Frame> body_frames(const HostModel &h) {
+  const Frame link0 = frame_of(h.link_tf[0].R, h.link_tf[0].t);
+  std::vector<Frame> T(h.nb);
+  for (int i = 0; i < h.nb; i++)
+    T[i] = i == 0 ? frame_inverse(link0) : frame_mul(T[h.parent[i]], frame_of(h.joint_rot[i], h.joint_pos[i]));
+  return T;
+}
+
+// the pairing about one axis; false with `why` where the model has none
+bool mirror_about(const HostModel &h, int lat, double tol, ModelMirror &out, std::string &why) {
+  const int nb = h.nb, nj = nb - 1;
+  // every body's frame at q = 0 in URDF link 0's frame; its joint origin, joint axis and COM there (body 0: link 0's origin, no axis)
+  const std::vector<Frame> T = body_frames(h);
+  std::vector<std::array<double, 3>> o(nb), a(nb), c(nb);
+  for (int i = 0; i < nb; i++) {
+    for (int k = 0; k < 3; k++) o[i][k] = i == 0 ? 0.0 : T[i].t[k];
+    rotate(T[i], h.joint_axis[i], false, a[i].data());
+    rotate(T[i], h.com[i], true, c[i].data());
+  }
+  auto image = [&](const std::array<double, 3> &v) { std::array<double, 3> r = v; r[lat] = -r[lat]; return r; };
+  out.lateral = lat;
+  out.body_pair.assign(nb, -1);
+  for (int i = 0; i < nb; i++) {
+    const std::array<double, 3> want = image(o[i]);
+    if (dist3(want.data(), o[i].data()) <= tol) { out.body_pair[i] = i; continue; }
+    double best = tol;
+    for (int j = 0; j < nb; j++) {
+      const double d = dist3(want.data(), o[j].data());
+      if (j != i && d <= best && (out.body_pair[i] < 0 || d < best)) { best = d; out.body_pair[i] = j; }
+    }
+    if (out.body_pair[i] < 0) { why = "body " + std::to_string(i) + " (" + h.body_names[i] + ") has no partner within tol_pos"; return false; }
+  }
+  for (int i = 0; i < nb; i++) {
+    const int j = out.body_pair[i];
+    if (out.body_pair[j] != i) { why = "the pairing of body " + std::to_string(i) + " (" + h.body_names[i] + ") is not an involution"; return false; }
+    if (i > 0 && out.body_pair[h.parent[i]] != h.parent[j]) {
+      why = "the parents of body " + std::to_string(i) + " (" + h.body_names[i] + ") and of its partner are not paired";
+      return false;
+    }
+  }
+  std::vector<int> slot(nb, -1);
+  for (int k = 0; k < nj; k++) slot[h.obs_order[k]] = k;
+  out.pair.assign(nj, 0); out.sign.assign(nj, 1);
+  for (double &r : out.residual) r = 0.0;
+  for (int i = 0; i < nb; i++) {
+    const int j = out.body_pair[i];
+    const std::array<double, 3> oj = image(o[j]), cj = image(c[j]);
+    out.residual[0] = std::max(out.residual[0], std::fabs(h.mass[i] - h.mass[j]) / std::max(h.mass[i], h.mass[j]));
+    out.residual[1] = std::max(out.residual[1], dist3(o[i].data(), oj.data()));
+    out.residual[3] = std::max(out.residual[3], dist3(c[i].data(), cj.data()));
+    if (i == 0) continue;
+    // an axis reflects as an axial vector: the image of a is -S a
+    std::array<double, 3> aj = image(a[j]);
+    for (double &v : aj) v = -v;
+    const double d = a[i][0] * aj[0] + a[i][1] * aj[1] + a[i][2] * aj[2];
+    const double cr[3] = {a[i][1] * aj[2] - a[i][2] * aj[1], a[i][2] * aj[0] - a[i][0] * aj[2], a[i][0] * aj[1] - a[i][1] * aj[0]};
+    const int8_t s = d < 0.0 ? -1 : 1;
+    out.residual[2] = std::max(out.residual[2], std::atan2(std::sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]), std::fabs(d)));
+    const double lo = s > 0 ? h.q_lower[j] : -h.q_upper[j], hi = s > 0 ? h.q_upper[j] : -h.q_lower[j];
+    if (std::fabs(h.q_lower[i] - lo) > tol || std::fabs(h.q_upper[i] - hi) > tol) {
+      why = "the limits of joint " + h.joint_names[i] + " and of its partner's image differ by more than tol_pos";
+      return false;
+    }
+    out.pair[slot[i]] = slot[j]; out.sign[slot[i]] = s;
+  }
+  out.residual[4] = std::fabs(c[0][lat]);
+  return true;
+}
+
+}  // namespace
+
+ModelMirror build_model_mirror(const HostModel &h, int lateral, double tol_pos) {
+  const std::string me = "trex_model_mirror_table: ";
+  if (lateral < -1 || lateral > 2) throw Refusal(me + "lateral " + std::to_string(lateral) + " is none of -1, 0, 1, 2");
+  if (!(tol_pos >= 0.0) || !std::isfinite(tol_pos)) throw Refusal(me + "tol_pos is negative or not finite");
+  ModelMirror m;
+  std::string why;
+  if (lateral >= 0) {
+    if (!mirror_about(h, lateral, tol_pos, m, why)) throw Refusal(me + why);
+    return m;
+  }
+  // the search: the first axis that pairs some body with ANOTHER one; where none does, the first that pairs at all
+  ModelMirror first;
+  bool have = false;
+  std::string first_why;
+  for (int lat = 0; lat < 3; lat++) {
+    if (!mirror_about(h, lat, tol_pos, m, why)) { if (first_why.empty()) first_why = "about axis " + std::to_string(lat) + ": " + why; continue; }
+    for (int i = 0; i < h.nb; i++)
+      if (m.body_pair[i] != i) return m;
+    if (!have) { first = m; have = true; }
+  }
+  if (!have) throw Refusal(me + "no axis of link 0 is normal to a mirror plane of the model (" + first_why + ")");
+  return first;
+}
+
+RowMirror build_mirror_row_table(const HostModel &h, const ModelMirror &mm, double tol_pos, const TrexObsChannel *channels, int num_channels,
+                                 int action_cols, int tail, const int32_t *extern_src, const int8_t *extern_sign) {
+  const std::string me = "trex_model_mirror_row_table: ";
+  const int nj = h.nb - 1, lat = mm.lateral, links = (int)h.link_body.size();
+  if (num_channels < 0 || (num_channels > 0 && !channels)) throw Refusal(me + "null argument");
+  if (action_cols != nj && action_cols != 2 * nj) throw Refusal(me + "action_cols " + std::to_string(action_cols) + " is neither J nor 2 J");
+  if (tail != 2 && tail != 5) throw Refusal(me + "tail " + std::to_string(tail) + " is neither 2 nor 5");
+  // the first column of every channel, its width, and the columns of the EXTERNAL block
+  std::vector<int> col0(num_channels), width(num_channels), ext0(num_channels, 0);
+  std::vector<int> ext_col;                       // extern index -> column of the row
+  int col = 3 * nj;
+  for (int k = 0; k < num_channels; k++) {
+    const TrexObsChannel &c = channels[k];
+    const std::string ck = me + "channel " + std::to_string(k) + ": ";
+    if (c.kind < 0 || c.kind >= TREX_OBS_KINDS) throw Refusal(ck + "unknown kind " + std::to_string(c.kind));
+    const bool linked = c.kind == TREX_OBS_POINT_POSITION || c.kind == TREX_OBS_POINT_VELOCITY || c.kind == TREX_OBS_POINT_HEIGHT ||
+                        c.kind == TREX_OBS_CONTACT_FORCE;
+    if (linked && (c.link < 0 || c.link >= links)) throw Refusal(ck + "link " + std::to_string(c.link) + " out of range");
+    if (c.kind == TREX_OBS_EXTERNAL && c.link < 1) throw Refusal(ck + "an EXTERNAL channel needs link = k >= 1 columns");
+    col0[k] = col;
+    width[k] = c.kind == TREX_OBS_PREV_ACTION ? action_cols : c.kind == TREX_OBS_EXTERNAL ? c.link :
+               (c.kind == TREX_OBS_BASE_HEIGHT || c.kind == TREX_OBS_POINT_HEIGHT || c.kind == TREX_OBS_CONTACT_FORCE) ? 1 : 3;
+    if (c.kind == TREX_OBS_EXTERNAL) {
+      ext0[k] = (int)ext_col.size();
+      for (int i = 0; i < width[k]; i++) ext_col.push_back(col + i);
+      if (!extern_src || !extern_sign) throw Refusal(ck + "an EXTERNAL channel needs extern_src and extern_sign");
+    }
+    col += width[k];
+    if (col + tail > TREX_MIRROR_MAXWIDTH) throw Refusal(me + "the row is wider than " + std::to_string(TREX_MIRROR_MAXWIDTH) + " columns");
+  }
+  const int X = (int)ext_col.size(), W = col + tail;
+  std::vector<char> taken(X, 0);
+  for (int e = 0; e < X; e++) {
+    if (extern_src[e] < 0 || extern_src[e] >= X || taken[extern_src[e]] || (extern_sign[e] != 1 && extern_sign[e] != -1))
+      throw Refusal(me + "extern column " + std::to_string(e) + ": extern_src is no permutation of the EXTERNAL columns or a sign is neither +1 nor -1");
+    taken[extern_src[e]] = 1;
+  }
+  // a channel's point at q = 0 in link 0's frame
+  const std::vector<Frame> T = body_frames(h);
+  auto point_of = [&](const TrexObsChannel &c, double out[3]) {
+    const Frame f = frame_mul(T[h.link_body[c.link]], frame_of(h.link_tf[c.link].R, h.link_tf[c.link].t));
+    rotate(f, Vec3{c.local_xyz[0], c.local_xyz[1], c.local_xyz[2]}, true, out);
+  };
+  auto partner = [&](int k) {
+    const TrexObsChannel &c = channels[k];
+    if (c.kind <= TREX_OBS_BASE_HEIGHT || c.kind >= TREX_OBS_PREV_ACTION) return k;
+    double x[3];
+    if (c.kind != TREX_OBS_CONTACT_FORCE) { point_of(c, x); x[lat] = -x[lat]; }
+    for (int j = 0; j < num_channels; j++) {
+      const TrexObsChannel &d = channels[j];
+      if (d.kind != c.kind || d.scale != c.scale || mm.body_pair[h.link_body[c.link]] != h.link_body[d.link]) continue;
+      if (c.kind == TREX_OBS_CONTACT_FORCE) return j;
+      double y[3];
+      point_of(d, y);
+      if (dist3(x, y) <= tol_pos) return j;
+    }
+    throw Refusal(me + "channel " + std::to_string(k) + " has no mirrored channel in the specification (the same kind and scale, the mirrored "
+                  "link" + (c.kind == TREX_OBS_CONTACT_FORCE ? ")" : ", the image of local_xyz within tol_pos)"));
+  };
+  RowMirror r;
+  r.src.resize(W); r.sign.assign(W, 1);
+  for (int b = 0; b < 3; b++)
+    for (int k = 0; k < nj; k++) { r.src[b * nj + k] = b * nj + mm.pair[k]; r.sign[b * nj + k] = mm.sign[k]; }
+  for (int k = 0; k < num_channels; k++) {
+    const TrexObsChannel &c = channels[k];
+    const int p = partner(k);
+    for (int i = 0; i < width[k]; i++) {
+      const int at = col0[k] + i;
+      r.src[at] = col0[p] + i;
+      switch (c.kind) {
+        case TREX_OBS_PROJECTED_GRAVITY: case TREX_OBS_BASE_LINEAR_VELOCITY: case TREX_OBS_POINT_POSITION: case TREX_OBS_POINT_VELOCITY:
+          r.sign[at] = i == lat ? -1 : 1;      // a polar vector in base axes
+          break;
+        case TREX_OBS_BASE_ANGULAR_VELOCITY:
+          r.sign[at] = i == lat ? 1 : -1;      // an axial vector
+          break;
+        case TREX_OBS_PREV_ACTION:
+          r.src[at] = col0[k] + (i < nj ? mm.pair[i] : nj + mm.pair[i - nj]);
+          r.sign[at] = i < nj ? mm.sign[i] : 1;
+          break;
+        case TREX_OBS_EXTERNAL:
+          r.src[at] = ext_col[extern_src[ext0[k] + i]];
+          r.sign[at] = extern_sign[ext0[k] + i];
+          break;
+        default: break;                        // a height, a contact force: unchanged
+      }
+    }
+  }
+  for (int i = 0; i < tail; i++) r.src[col + i] = col + i;
+  return r;
+}
+
+void build_mirror_action_table(const int32_t *pair, const int8_t *sign, int nj, bool stiffness, int32_t *src_out, int8_t *sign_out) {
+  for (int k = 0; k < nj; k++) {
+    src_out[k] = pair[k]; sign_out[k] = sign[k];
+    if (stiffness) { src_out[nj + k] = nj + pair[k]; sign_out[nj + k] = 1; }
+  }
+}
+
+void build_mirror_command_table(int lateral, int32_t src_out[3], int8_t sign_out[3]) {
+  for (int k = 0; k < 3; k++) src_out[k] = k;
+  sign_out[0] = lateral == 0 ? -1 : 1;
+  sign_out[1] = lateral == 1 ? -1 : 1;
+  sign_out[2] = lateral == 2 ? 1 : -1;      // wz is the z component of an axial vector
+}
+
 }  // namespace trex

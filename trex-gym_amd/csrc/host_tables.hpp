@@ -1,6 +1,6 @@
 // The tables the kernels read and the layouts of the per-env state they write, as pure host arithmetic: everything the C-ABI computes
 // between its argument checks and its HIP calls.
-// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h, motion_limits.h, sensing_limits.h, start_state_limits.h, policy_limits.h, planner_limits.h and include/trex_batch.h, and nothing of HIP; it makes
+// INCLUDE RULE: this unit includes model.hpp, device_model.h, proximity_limits.h, observation_limits.h, reward_limits.h, motion_limits.h, sensing_limits.h, start_state_limits.h, policy_limits.h, planner_limits.h, symmetry_limits.h and include/trex_batch.h, and nothing of HIP; it makes
 // no HIP call and knows no batch. It builds with plain g++ -std=c++17, as model.cpp does, so that tests/host/tables_harness.cpp runs
 // it under the sanitizers on a machine without a GPU. A refusal is a thrown Refusal whose text is the C-ABI's message, whole.
 #pragma once
@@ -24,6 +24,7 @@ struct float4;
 #include "reward_limits.h"
 #include "sensing_limits.h"
 #include "start_state_limits.h"
+#include "symmetry_limits.h"
 
 namespace trex {
 
@@ -252,6 +253,38 @@ void check_plan_update(const PlannerShape &p, bool noise_set, bool reward, int64
                        float temperature);
 // the bytes a strided [S, N] column reaches: its last element ends it
 size_t plan_column_bytes(const PlannerShape &p, int64_t step_stride, int64_t env_stride);
+
+// The mirror maps (include/trex_symmetry.h): a table checked and as the kernels read it - word c is src[c], with TREX_MIRROR_NEG set
+// where sign[c] < 0 -, whether it is an involution, and what the two row launches refuse before any HIP call. The pointers are
+// looked at as addresses only (null, overlap).
+struct MirrorWords { std::vector<uint32_t> word; bool involution = false; };
+MirrorWords build_mirror_words(const int32_t *src, const int8_t *sign, int width);
+void check_mirror_rows(int table_width, const void *in, int in_stride, const void *out, int out_stride, int n, int width);
+// widths: the tables' (critic 0: none); has_critic_table, obs_v: what was given; buffers: every required pointer is there
+void check_mirror_augment(int obs_width, int act_width, int critic_width, bool has_critic_table, bool buffers, bool obs_v,
+                          int64_t num_samples, int D, int A, int Dv);
+
+// trex_model_mirror_table: the bodies paired by the reflection of their joint origins at q = 0 in the plane through URDF link 0's
+// origin whose normal is link 0's axis `lateral` (-1: searched), the joints' pairs and signs in observation order, and what of
+// the model is NOT symmetric (include/trex_symmetry.h lists the five residuals). Refuses what the header says.
+struct ModelMirror {
+  int lateral = 0;
+  std::vector<int32_t> pair, body_pair;     // [J] observation slots, [B] bodies
+  std::vector<int8_t> sign;                 // [J]
+  double residual[5] = {0, 0, 0, 0, 0};
+};
+ModelMirror build_model_mirror(const HostModel &h, int lateral, double tol_pos);
+// trex_model_mirror_row_table: the table of a composed row [q J | qd J | torque J | the E channel columns | tail] - the rules of
+// include/trex_symmetry.h. action_cols: J or 2 J (what PREV_ACTION copies); extern_src / extern_sign: the caller's table of the
+// EXTERNAL columns, concatenated in channel order (nullable where no such channel is set).
+struct RowMirror { std::vector<int32_t> src; std::vector<int8_t> sign; };
+RowMirror build_mirror_row_table(const HostModel &h, const ModelMirror &mm, double tol_pos, const TrexObsChannel *channels, int num_channels,
+                                 int action_cols, int tail, const int32_t *extern_src, const int8_t *extern_sign);
+// the action table [A] of a joint table [J]: the joint table, and with stiffness actions (A = 2 J) a second block of the same
+// permutation with sign +1
+void build_mirror_action_table(const int32_t *pair, const int8_t *sign, int nj, bool stiffness, int32_t *src_out, int8_t *sign_out);
+// the table of a velocity command (vx, vy, wz) in base axes: the lateral component and wz change sign
+void build_mirror_command_table(int lateral, int32_t src_out[3], int8_t sign_out[3]);
 
 // trex_batch_render: the camera of include/trex_batch.h, checked, as the renderer's basis
 struct CameraBasis { float offset[3], fwd[3], right[3], up[3], tan_x, tan_y; };

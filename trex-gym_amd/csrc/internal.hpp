@@ -14,6 +14,10 @@ int trex_fail(int code, const std::string &msg);
 struct TrexSeen { const void *p; size_t bytes; };
 int trex_check_device_buffer(int device, std::vector<TrexSeen> &seen, const void *p, size_t bytes, const char *what);
 
+// a mirror table (include/trex_symmetry.h, capi_symmetry.cpp) as another unit's launch reads it: its device words, width and device
+struct TrexMirrorTable;
+const uint32_t *trex_mirror_table_words(const TrexMirrorTable *table, int *width, int *device);
+
 struct TrexDeviceGuard {
   int prev = -1;
   bool ok;

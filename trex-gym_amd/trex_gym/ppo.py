@@ -123,6 +123,8 @@ def dp_minibatch_step(kern, theta, grad, m, v, srcs, perm, first, mb, stats_row,
 
 
 class PPO:
+    _symmetry = (None, None, 1.0)      # (mode, mirror, sym_coef): trex_gym.symmetry.MirrorPPO sets it on the instance before this __init__ runs
+
     def __init__(self, env, nsteps=32, nminibatches=32, noptepochs=4, gamma=0.99, lam=0.95, lr=3e-4,
                  cliprange=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, clip_obs=10.0, clip_rew=10.0,
                  seed=0, use_graphs=False, native_learner=True, critic=None):
@@ -135,7 +137,10 @@ class PPO:
         critic: True trains an asymmetric actor-critic (include/trex_policy_critic.h): the value net reads env.critic_rows
         (trex_gym.critic.attach), normalised by running moments of its own, the policy net keeps env.rows; `b_obs_v` is the second
         rollout buffer. Single process only: the moment merge of a data-parallel run is not written. No training benefit is
-        claimed: that takes long runs nobody has made."""
+        claimed: that takes long runs nobody has made.
+        Mirror symmetry: trex_gym.symmetry.MirrorPPO, a subclass, sets `_symmetry` to (mode, a Mirror of this env, sym_coef)
+        (include/trex_symmetry.h); its docstring says what "augment", "loss" and "both" allocate and launch. PPO itself
+        allocates and launches nothing of this."""
         self.env = env
         self.dev = env.device
         # DATA-PARALLEL (BASELINE config 3 on N GPUs; SURVEY 8e: "only PPO gradient all-reduce remains"): one process per GPU, env
@@ -149,6 +154,22 @@ class PPO:
         if self.world > 1 and (use_graphs or not native_learner):
             raise ValueError("the data-parallel trainer runs the native learner, eagerly (collectives inside a captured graph are not supported here)")
         self.nsteps, self.nminibatches, self.noptepochs = nsteps, nminibatches, noptepochs
+        symmetry, mirror, sym_coef = self._symmetry
+        if symmetry not in (None, "augment", "loss", "both"):
+            raise ValueError("symmetry: expected None, \"augment\", \"loss\" or \"both\", got %r" % (symmetry,))
+        if symmetry and mirror is None:
+            raise ValueError("symmetry: a trex_gym.symmetry.Mirror of the env is required")
+        if symmetry and self.world > 1:
+            raise ValueError("symmetry: not written for the data-parallel trainer")
+        if symmetry in ("loss", "both") and critic:
+            raise ValueError("symmetry: the mirror loss is refused together with critic=, as distillation is")
+        if symmetry and critic and getattr(mirror, "critic_table", None) is None:
+            raise ValueError("symmetry: critic= needs the mirror's critic table (trex_gym.symmetry.MirrorPPO builds it)")
+        self.symmetry, self.mirror, self.sym_coef = symmetry, mirror if symmetry else None, float(sym_coef)
+        self._augment, self._mirror_loss = symmetry in ("augment", "both"), symmetry in ("loss", "both")
+        if self._mirror_loss and not native_learner:
+            raise ValueError("symmetry: the mirror loss is a launch of the native learner (native_learner=True)")
+        self._steps = nminibatches * (2 if self._augment else 1)      # optimiser steps of an epoch
         self.gamma, self.lam, self.cliprange, self.lr = gamma, lam, cliprange, lr
         self.ent_coef, self.vf_coef, self.max_grad_norm = ent_coef, vf_coef, max_grad_norm
         self.clip_obs, self.clip_rew = clip_obs, clip_rew
@@ -181,7 +202,7 @@ class PPO:
         self.adam_v = torch.zeros_like(self.policy.theta)
         self.use_graphs, self.native_learner = use_graphs, native_learner
         self._rollout_graph = self._update_graph = None
-        self.mb_stats = torch.zeros(nminibatches, 2, device=self.dev)
+        self.mb_stats = torch.zeros(self._steps, 2, device=self.dev)
         self.loss_sums = torch.zeros(2, device=self.dev)
         self.total_env_steps = 0
         if self.world > 1:      # same initial parameters everywhere (seeded above), different exploration noise per rank
@@ -189,19 +210,37 @@ class PPO:
             dist.broadcast(self.policy.theta.data, 0, group=self.group)
             torch.manual_seed(seed + 1000003 * (self.rank + 1))
         T = nsteps
+        if symmetry and (mirror.obs_dim != od or mirror.act_table.width != ad):
+            raise ValueError("symmetry: the mirror's tables are %d and %d columns wide, the policy's rows %d and %d"
+                             % (mirror.obs_dim, mirror.act_table.width, od, ad))
+        self._rows_T = 2 * T if self._augment else T            # steps' worth of samples the learner reads
         self.noise = torch.empty(T, n, ad, device=self.dev)
         self.actions = torch.empty(n, ad, device=self.dev)
+        T, T_rollout = self._rows_T, T                           # (the mirrored samples lie behind the rollout's, in every buffer)
         self.b_obs = torch.empty(T, n, od, device=self.dev)
         self.b_obs_v = torch.empty(T, n, self.critic_dim, device=self.dev) if self.crit else None   # the NORMALISED critic observation
         self.b_act = torch.empty(T, n, ad, device=self.dev)
         self.b_logp = torch.empty(T, n, device=self.dev)
-        self.b_val = torch.empty(T + 1, n, device=self.dev)
+        # (GAE reads the bootstrap value in row T_rollout; the augment launch behind it overwrites that row with mirrored samples)
+        self.b_val = torch.empty(max(T_rollout + 1, T), n, device=self.dev)
+        self.b_adv = torch.empty(T, n, device=self.dev)
+        self.b_ret = torch.empty(T, n, device=self.dev)
+        T = T_rollout
         self.b_rew = torch.empty(T, n, device=self.dev)          # RAW rewards; GAE applies scale[t] and the clip
         self.b_scale = torch.empty(T, device=self.dev)
         self.b_done = torch.empty(T, n, device=self.dev)
-        self.b_adv = torch.empty(T, n, device=self.dev)
-        self.b_ret = torch.empty(T, n, device=self.dev)
         self._raw_sum = 0.0
+        if self._mirror_loss:
+            # the proximal mirror target M_a mu_old(M_o s) of every sample the learner reads, the scratch of its two act calls, the
+            # second gradient and the loss sums of the distillation launch
+            from . import distill_capi
+            self._distill = distill_capi.PolicyDistill(self.kern)
+            self.b_tgt = torch.zeros(self._rows_T, n, ad, device=self.dev)
+            self._rows_m = torch.zeros_like(env.rows)
+            self._zero_noise = torch.zeros(n, ad, device=self.dev)
+            self._mean = torch.zeros(n, ad, device=self.dev)
+            self.grad_sym = torch.zeros_like(self.policy.theta)
+            self.sym_sums = torch.zeros(2, device=self.dev)
         # reward terms (TrexVecEnv(rewards=...)): the weighted value of every term summed over the rollout, on the device
         rt = getattr(env, "reward_terms", None)
         self.term_names = list(getattr(env, "reward_names", [])) if rt is not None else []
@@ -221,11 +260,34 @@ class PPO:
         self.kern.observe(env.rows, with_reward=False)           # VecNormalize.reset: the statistics see the first obs
         if self.crit:
             self.crit.observe(env.critic_rows)
+        self._symmetrize()
 
     @property
     def obs(self):
         """The normalised observation the policy saw at the last step of the last rollout (diagnostics)."""
-        return self.b_obs[-1]
+        return self.b_obs[self.nsteps - 1]
+
+    def _mirror_targets(self, t):
+        """b_tgt[t] = M_a mu_old(M_o s) on the rows the policy is acting on: the rows mirrored, a second act call with zero noise
+        - its action IS its mean -, the mean mirrored. With the mirrored samples ("both") their target too, M_a mu_old(s): a third
+        act call, on the rows themselves."""
+        m, k, th = self.mirror, self.kern, self.policy.theta
+        m.rows(self.env.rows, self._rows_m)
+        k.act(th, self._rows_m, self._zero_noise, self._mean, clip_obs=self.clip_obs)
+        m.actions(self._mean, self.b_tgt[t])
+        if self._augment:
+            k.act(th, self.env.rows, self._zero_noise, self._mean, clip_obs=self.clip_obs)
+            m.actions(self._mean, self.b_tgt[self.nsteps + t])
+
+    def _symmetrize(self):
+        """In EVERY symmetry mode the running observation moments become those of the stream that holds every row and its image.
+        "augment" needs it to mirror the stored normalised observations; "loss" needs it as much: its target M_a mu_old(M_o s)
+        normalises the mirrored RAW rows, and only with symmetric moments is that the policy at the mirror image of the
+        observation the learner reads - else the loss would ask a symmetric policy to be asymmetric (for symmetrize_theta'd
+        parameters it would not be zero). The policy then trains under the symmetrised normalisation; a checkpoint stores it."""
+        if self.symmetry:
+            from . import symmetry_capi
+            symmetry_capi.symmetrize_stats(self.kern, self.mirror.obs_table, self.mirror.critic_table if self.crit else None)
 
     @torch.no_grad()
     def _rollout(self):
@@ -241,6 +303,8 @@ class PPO:
             else:
                 k.act(th, env.rows, self.noise[t], self.actions, self.b_obs[t], self.b_act[t], self.b_logp[t], self.b_val[t],
                       clip_obs=self.clip_obs)
+            if self._mirror_loss:
+                self._mirror_targets(t)
             if self.b_terms is not None:
                 env.reward_terms = self.b_terms[t]
             if self.b_motion is not None:
@@ -249,6 +313,7 @@ class PPO:
             k.observe(env.rows, True, self.gamma, self.b_rew[t], self.b_done[t], self.b_scale[t:t + 1])
             if c:
                 c.observe(env.critic_rows)
+            self._symmetrize()
         if self.b_terms is not None:
             torch.sum(self.b_terms, dim=(0, 1), out=self.term_sum)
         if self.b_motion is not None:
@@ -258,6 +323,11 @@ class PPO:
         else:
             k.act(th, env.rows, None, None, value_out=self.b_val[T], clip_obs=self.clip_obs, value_only=True)
         k.gae(self.b_rew, self.b_scale, self.b_done, self.b_val, self.b_adv, self.b_ret, self.gamma, self.lam, self.clip_rew)
+        if self._augment:       # ONE launch: the samples [T n, 2 T n) of the six buffers from the samples [0, T n)
+            from . import symmetry_capi
+            symmetry_capi.augment(self.mirror.obs_table, self.mirror.act_table, self.b_obs, self.b_act, self.b_logp, self.b_val,
+                                  self.b_adv, self.b_ret, T * env.num_envs, critic_table=self.mirror.critic_table if c else None,
+                                  obs_v=self.b_obs_v if c else None)
 
     @torch.no_grad()
     def collect(self):
@@ -276,7 +346,8 @@ class PPO:
         self.total_env_steps += T * n * self.world
         if self.world > 1:
             self._merge_statistics()
-        flat = lambda x: x.reshape(T * n, *x.shape[2:])
+        R = self._rows_T        # (T, or 2 T with the mirrored samples)
+        flat = lambda x: x.reshape(R * n, *x.shape[2:])
         raw = self.kern.get_stats()["raw_reward_sum"]            # (the one host read-back per rollout)
         mean_rew, self._raw_sum = (raw - self._raw_sum) / (T * n), raw
         if self.term_sum is not None:                            # (behind that read-back: the stream is drained, one small copy)
@@ -291,7 +362,7 @@ class PPO:
                 summary = self._merge_monitor(summary)
             from . import monitor
             self.episode_stats = monitor.stats_from_summary(summary, monitor.column_names(self.env))
-        return (flat(self.b_obs), flat(self.b_act), flat(self.b_logp), flat(self.b_val[:T]), flat(self.b_adv), flat(self.b_ret),
+        return (flat(self.b_obs), flat(self.b_act), flat(self.b_logp), flat(self.b_val[:R]), flat(self.b_adv), flat(self.b_ret),
                 mean_rew)
 
     def _merge_statistics(self):
@@ -352,7 +423,8 @@ class PPO:
         return pg.detach(), vf.detach(), ent.detach()
 
     def _epoch(self, srcs, N, mb):
-        """One epoch: a fresh permutation, nminibatches optimiser steps; returns the summed (pg, vf, ent)."""
+        """One epoch: a fresh permutation, nminibatches optimiser steps (twice as many over the mirrored samples too); returns the
+        summed (pg, vf, ent)."""
         perm = torch.rand(N, device=self.dev).argsort()     # (capturable: no host round trip, unlike randperm's size logic)
         if self.native_learner:
             obs, act, logp0, val0, adv, ret = srcs[:6]
@@ -360,30 +432,44 @@ class PPO:
             self.loss_sums.zero_()
             if self.world > 1:
                 self._dp_minibatch_stats(adv, perm, mb)
-                for i in range(self.nminibatches):
+                for i in range(self._steps):
                     self.dp_minibatch_step(srcs, perm, i * mb, mb, self.mb_stats[i])
                 import torch.distributed as dist
                 dist.all_reduce(self.loss_sums, group=self.group)
-                ent = (pol.logstd.detach() + 0.5 * (math.log(2 * math.pi) + 1.0)).sum() * self.nminibatches
+                ent = (pol.logstd.detach() + 0.5 * (math.log(2 * math.pi) + 1.0)).sum() * self._steps
                 return torch.cat([self.loss_sums, ent.reshape(1)])
-            k.minibatch_stats(adv, perm, self.nminibatches, mb, self.mb_stats)
-            for i in range(self.nminibatches):
+            k.minibatch_stats(adv, perm, self._steps, mb, self.mb_stats)
+            for i in range(self._steps):
                 if self.crit:
                     self.crit.minibatch_step(pol.theta, pol.grad, self.adam_m, self.adam_v, obs, srcs[6], act, logp0, val0, adv, ret,
                                              perm, i * mb, mb, self.mb_stats[i], self.cliprange, self.ent_coef, self.vf_coef, self.lr,
                                              0.9, 0.999, 1e-5, self.max_grad_norm, self.loss_sums)
                     continue
+                if self._mirror_loss:
+                    # PPO's gradient, the mirror loss' - sym_coef (1 / mb) sum (mu - target)^2 / 2, the distillation launch at its
+                    # output layer - into a second buffer, their sum, then clip + Adam
+                    k.minibatch_grad(pol.theta, pol.grad, obs, act, logp0, val0, adv, ret, perm, i * mb, mb, self.mb_stats[i],
+                                     self.cliprange, self.ent_coef, self.vf_coef, 1.0, self.loss_sums)
+                    self._distill.minibatch_grad(pol.theta, self.grad_sym, obs, self.b_tgt, val0, None, perm, i * mb, mb, "mse", 0.0,
+                                                 self.sym_coef, self.sym_sums)
+                    pol.grad.add_(self.grad_sym)
+                    k.adam(pol.theta, pol.grad, self.adam_m, self.adam_v, self.lr, 0.9, 0.999, 1e-5, self.max_grad_norm)
+                    continue
                 k.minibatch_step(pol.theta, pol.grad, self.adam_m, self.adam_v, obs, act, logp0, val0, adv, ret, perm, i * mb, mb,
                                  self.mb_stats[i], self.cliprange, self.ent_coef, self.vf_coef, self.lr, 0.9, 0.999, 1e-5,
                                  self.max_grad_norm, self.loss_sums)
-            ent = (pol.logstd.detach() + 0.5 * (math.log(2 * math.pi) + 1.0)).sum() * self.nminibatches   # (of the updated policy)
+            ent = (pol.logstd.detach() + 0.5 * (math.log(2 * math.pi) + 1.0)).sum() * self._steps   # (of the updated policy)
             return torch.cat([self.loss_sums, ent.reshape(1)])
         acc = torch.zeros(3, device=self.dev)
-        for k in range(self.nminibatches):
+        for k in range(self._steps):
             idx = perm[k * mb:(k + 1) * mb]
             out = self._minibatch_step(*[x.index_select(0, idx) for x in srcs])
             acc = acc + torch.stack(out)
         return acc
+
+    def _mb(self, N):
+        """the minibatch size of N samples: with the mirrored samples N is twice the rollout's and the steps are twice as many"""
+        return N // self._steps
 
     def update(self, batch):
         obs, act, logp0, val0, adv, ret, _ = batch
@@ -391,7 +477,7 @@ class PPO:
         if self.crit:       # (the critic observation of the same samples: the second rollout buffer, behind the six)
             srcs += (self.b_obs_v.reshape(-1, self.critic_dim),)
         N = obs.shape[0]
-        mb = N // self.nminibatches
+        mb = self._mb(N)
         if self.use_graphs:
             # ONE graph per epoch (a permutation + all its minibatch steps)
             if self._update_graph is None:
@@ -424,7 +510,7 @@ class PPO:
             total = torch.zeros(3, device=self.dev)
             for _ in range(self.noptepochs):
                 total += self._epoch(srcs, N, mb)
-        pg, vf, ent = (total / (self.noptepochs * self.nminibatches)).tolist()
+        pg, vf, ent = (total / (self.noptepochs * self._steps)).tolist()
         return dict(policy_loss=pg, value_loss=vf, entropy=ent)
 
     def learn(self, total_timesteps, log=print):

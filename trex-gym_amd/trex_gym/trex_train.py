@@ -89,9 +89,14 @@ def build_environment(num_envs, device="cuda:0", max_episode_steps=1000, warmsta
         terms = M.imitation(env.model, end_effectors=bool(feet)) if motion.get("terms") is None else M.from_tuples(motion["terms"])
         if motion.get("terms") is None:
             terms = [t._replace(weight=t.weight * weight) for t in terms]
-        M.attach(env, motion["clip"], terms=terms, end_effectors=feet, rsi=bool(motion.get("rsi", False)), seed=seed)
-        # what a checkpoint stores: the clip's path, the terms as set (the weight is in them), the rsi flag
-        env.motion_config = dict(clip=str(motion["clip"]), rsi=bool(motion.get("rsi", False)), weight=1.0, terms=M.as_tuples(terms))
+        clip = motion["clip"]
+        if motion.get("mirror_clip"):       # the clip and its mirror image, one behind the other (trex_gym.symmetry.clip_with_mirror)
+            from .symmetry import Mirror, clip_with_mirror
+            clip = clip_with_mirror(M.Clip.load(clip), Mirror(env, log=None))
+        M.attach(env, clip, terms=terms, end_effectors=feet, rsi=bool(motion.get("rsi", False)), seed=seed)
+        # what a checkpoint stores: the clip's path, the terms as set (the weight is in them), the rsi and mirror flags
+        env.motion_config = dict(clip=str(motion["clip"]), rsi=bool(motion.get("rsi", False)), weight=1.0, terms=M.as_tuples(terms),
+                                 mirror_clip=bool(motion.get("mirror_clip", False)))
     # sensing: dict(preset="typical" or None, scale=, obs_delay=(min, max), action_delay=(min, max)) as the flags give it, or
     # dict(groups=, action_delay=, seed=) - a checkpoint's, the recorded specification of trex_gym.sensing.attach: the policy reads
     # its observations through sensors (noise, bias, resolution, latency, on the device) and its actions reach the motors late
@@ -201,10 +206,12 @@ PRESETS = {
 
 
 def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, log=print, use_graphs=False,
-          preset="throughput", distill=None):
+          preset="throughput", distill=None, symmetry=None, sym_coef=1.0):
     """distill: dict(teacher=PATH, rows="clean" | "critic" | "rows", loss="kl" | "mse", beta=, decay=) - the student of
     trex_gym.distill.Distill is trained onto that teacher instead of PPO on the reward (the preset's nminibatches, noptepochs and lr
-    hold); the checkpoint is an ordinary one and records the teacher's path and row choice."""
+    hold); the checkpoint is an ordinary one and records the teacher's path and row choice.
+    symmetry: "augment", "loss" or "both" trains trex_gym.symmetry.MirrorPPO - on every rollout sample and its mirror image, with
+    the mirror loss weighted sym_coef, or both -; the mirror tables and the option travel in the checkpoint."""
     hp = dict(PRESETS[preset])
     if noptepochs is not None:
         hp["noptepochs"] = noptepochs
@@ -214,6 +221,12 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
         agent = Distill(env, teacher, nsteps=nsteps, nminibatches=hp["nminibatches"], noptepochs=hp["noptepochs"], lr=hp["lr"],
                         loss=distill.get("loss", "kl"), beta=float(distill.get("beta", 1.0)), beta_decay=float(distill.get("decay", 0.9)),
                         seed=seed, use_graphs=use_graphs)
+    elif symmetry is not None:
+        from .symmetry import Mirror, MirrorPPO
+        if getattr(env, "critic_config", None) is not None:
+            raise ValueError("--symmetry is not written for --critic")
+        agent = MirrorPPO(env, Mirror(env, log=log), symmetry=symmetry, sym_coef=sym_coef, nsteps=nsteps, seed=seed,
+                          use_graphs=use_graphs, **hp)
     else:
         agent = PPO(env, nsteps=nsteps, seed=seed, use_graphs=use_graphs, critic=getattr(env, "critic_config", None) is not None, **hp)
     log("Number of actions: %d; number of joints: %d; model mass: %.2f; nsteps %d x %d envs; preset %s, noptepochs %d"
@@ -231,7 +244,9 @@ def train(env, num_timesteps, seed, nsteps=32, noptepochs=None, save_path=None, 
                     "start_state": getattr(env, "start_state_config", None),
                     "monitor": getattr(env, "monitor_config", None), "critic": critic_checkpoint(agent),
                     "distill": None if distill is None else dict(teacher=str(distill["teacher"]), rows=str(distill.get("rows", "clean")),
-                                                                 loss=str(distill.get("loss", "kl")))},
+                                                                 loss=str(distill.get("loss", "kl"))),
+                    "symmetry": None if getattr(agent, "mirror", None) is None else dict(mode=agent.symmetry, sym_coef=float(agent.sym_coef),
+                                                                                         **agent.mirror.tables())},
                    save_path)   # (the channels, the terms, the clip and the sensor model: --play rebuilds the same row)
     return agent, hist
 
@@ -268,7 +283,7 @@ def _png_writer():
 
 
 def play(agent, num_play_timesteps, export_path=None, env_index=0, log=print, deterministic=False, update_stats=True, seed=0,
-         frames_dir=None, frame_size=(960, 720), camera=None):
+         frames_dir=None, frame_size=(960, 720), camera=None, symmetric=False):
     """The reference's play loop (trex_train.py:126-136: model.step -> env.step -> render a frame -> PNGs -> ffmpeg) up to
     the movie: every frame's world poses of the 252 visual meshes are recorded (trex_batch_visual_transforms) - what an
     external mesh renderer needs -, and with frames_dir a PNG of the collision hulls is written per step.
@@ -289,12 +304,18 @@ def play(agent, num_play_timesteps, export_path=None, env_index=0, log=print, de
     if frames_dir is not None:
         Image = _png_writer()
         os.makedirs(frames_dir, exist_ok=True)
+    mirror = None
+    if symmetric:       # (the mean action made mirror-equivariant: trex_gym.symmetry.Mirror.symmetric_action; no noise is drawn)
+        from .symmetry import Mirror
+        mirror = getattr(agent, "mirror", None) or Mirror(env, log=log)
     env.reset_tensor()
     k.observe(env.rows, with_reward=False)
     for _ in range(num_play_timesteps):
         if not deterministic:
             noise.normal_(generator=gen)
-        if getattr(agent, "crit", None) is not None:    # (trained with a privileged critic: the policy alone, no critic row)
+        if mirror is not None:
+            mirror.symmetric_action(agent, out=agent.actions)
+        elif getattr(agent, "crit", None) is not None:    # (trained with a privileged critic: the policy alone, no critic row)
             agent.crit.act(agent.policy.theta, env.rows, None, noise, agent.actions, clip_obs=agent.clip_obs)
         else:
             k.act(agent.policy.theta, env.rows, noise, agent.actions, clip_obs=agent.clip_obs)
@@ -392,6 +413,8 @@ def parse_args(argv=None):
                     help="a reference motion (trex_gym.motion.Clip.save): DeepMimic's tracking terms against it are added to the reward on "
                          "the device; with --observations, sin and cos of the clip's phase join the observation (with --observations "
                          "locomotion and --rewards that is 93 + 3 + 2 = 98 columns, more than the learner's 96: not supported)")
+    ap.add_argument("--mirror_clip", action="store_true",
+                    help="with --motion: train on the clip and its mirror image, one behind the other (trex_gym.symmetry.clip_with_mirror)")
     ap.add_argument("--rsi", action="store_true", help="with --motion: every new episode starts at a random instant of the clip")
     ap.add_argument("--motion_weight", type=float, default=1.0, help="with --motion: a factor on the weights of the tracking terms")
     ap.add_argument("--sensing", choices=["typical"], default=None,
@@ -425,6 +448,12 @@ def parse_args(argv=None):
                     help="with --start_noise: place the perturbed robot with its lowest collision point LO..HI metres above the floor")
     ap.add_argument("--no_start_noise", action="store_true", help="with --play: run the policy without the start-state randomisation it was trained with")
     ap.add_argument("--fall_penalty", type=float, default=0.0, help="taken from the reward of the step in which an episode ends by a fall")
+    ap.add_argument("--symmetry", choices=["augment", "loss", "both"], default=None,
+                    help="train on every rollout sample and its mirror image, with a mirror loss on the policy mean, or both "
+                         "(trex_gym.symmetry.MirrorPPO; include/trex_symmetry.h)")
+    ap.add_argument("--sym_coef", type=float, default=1.0, help="with --symmetry loss | both: the weight of the mirror loss")
+    ap.add_argument("--symmetric", action="store_true",
+                    help="with --play: step the env with (mu(s) + M_a mu(M_o s)) / 2, the mean action made mirror-equivariant")
     ap.add_argument("--critic", choices=["clean", "privileged"], default=None,
                     help="asymmetric actor-critic: the value net reads a row of its own - the observation before the sensor model "
                          "(clean), plus friction, push force, mass scale and foot contact forces where the env has them (privileged) - "
@@ -480,8 +509,8 @@ def parse_args(argv=None):
             ap.error(str(e))
     if args.command is not None and args.rewards is None:
         ap.error("--command needs --rewards")
-    if args.motion is None and (args.rsi or args.motion_weight != 1.0):
-        ap.error("--rsi and --motion_weight need --motion")
+    if args.motion is None and (args.rsi or args.motion_weight != 1.0 or args.mirror_clip):
+        ap.error("--rsi, --mirror_clip and --motion_weight need --motion")
     if args.rsi and args.graphs:   # (the instants are drawn per step by a generator of the env's own: not in a replayed graph)
         ap.error("--rsi cannot be combined with --graphs")
     if args.sensing is None and args.sense_scale != 1.0:
@@ -577,7 +606,8 @@ def environment_from_args(args):
                             push_force=args.push_force, push_interval=args.push_interval, push_duration=args.push_duration,
                             seed=args.random_seed, control_mode=None if args.control_mode == "position" else args.control_mode,
                             gain_scale=args.gain_scale, observations=args.observations, rewards=args.rewards, command=args.command,
-                            motion=None if args.motion is None else dict(clip=args.motion, rsi=args.rsi, weight=args.motion_weight),
+                            motion=None if args.motion is None else dict(clip=args.motion, rsi=args.rsi, weight=args.motion_weight,
+                                                                              mirror_clip=args.mirror_clip),
                             sensing=sensing_args(args), randomize=randomize_args(args), monitor=monitor_args(args), critic=args.critic,
                             start_state=start_state_args(args))
     if terminate is not None:   # (set on the built env: 'auto' needs its model - every body that does not stand on the floor at the start)
@@ -635,7 +665,8 @@ def main(argv=None):
         run_mpc(env, **mpc)
         return
     agent, _ = train(env, args.num_timesteps, args.random_seed, args.nsteps, args.noptepochs, args.save, use_graphs=args.graphs,
-                     preset=args.preset, distill=distill_args(args))
+                     preset=args.preset, distill=distill_args(args), symmetry=args.symmetry,
+                     sym_coef=args.sym_coef)
     if args.play:
         if env.critic_rows is not None:         # (playing runs the policy alone: the critic row is no longer filled)
             from . import critic as critics
@@ -649,7 +680,8 @@ def main(argv=None):
         if args.no_start_noise and env.start_api is not None:  # (likewise its start-state randomisation)
             from . import start_state as SS
             SS.attach(env, None)
-        play(agent, args.num_play_timesteps, args.export, deterministic=args.play_deterministic, update_stats=not args.play_deterministic,
+        play(agent, args.num_play_timesteps, args.export, symmetric=args.symmetric, deterministic=args.play_deterministic,
+             update_stats=not args.play_deterministic,
              frames_dir=args.frames)
 
 

@@ -27,7 +27,12 @@ struct TrexDeviceModel {
   float base_pos0[4], base_quat0[4];
   int parent[TREX_TL], depth[TREX_TL];
   int obs_slot[TREX_TL];              /* body -> index in the sorted-joint observation order, -1 for base */
-  int anc[TREX_MAXD][TREX_TL];        /* anc[d-1][b] = ancestor of body b at depth d (b itself at its own depth), -1 beyond */
+  /* The step kernel's packed per-body words (described at the end of the struct). They sit HERE, in the place `anc` had, so that
+   * with FK's words (axis .. jrot) they lie within the 4 KB an immediate load offset reaches: one base register, one batch of loads.
+   * (At the end of the struct the pair kernel spilled one scalar register more.) The offsets of everything behind are unchanged. */
+  unsigned tree_pack[TREX_TL], child_pack[TREX_TL];
+  int hull_range[TREX_TL][2];
+  int pad4[64];
   int child[TREX_MAXCH][TREX_TL];     /* moving children of body b, -1 = none */
   unsigned desc_mask[TREX_TL];        /* per DOF LANE: bit b set if body b's chain contains this dof (base dof lanes: all bodies) */
   int hull_start[TREX_TL + 1];
@@ -46,7 +51,20 @@ struct TrexDeviceModel {
   int nchunk, pad3[3];
   int chunk_body[TREX_TL], chunk_v0[TREX_TL], chunk_v1[TREX_TL];
   float chunk_c[3][TREX_TL], chunk_h[3][TREX_TL];
+  /* What the step kernel reads of the tables above once per substep, packed so that a lane fetches it unconditionally at its
+   * own index (rows stay 32 wide) in one batch of loads: no select in front of a load, no word that waits for another. The
+   * fields above stay as they are (the other kernels read them); fill_device_model derives these from them.
+   *   tree_pack[b]   max(parent, 0) | depth << 8; a lane that is no body: parent 0, depth 255 (TREX_NO_DEPTH)
+   *   child_pack[b]  child[0..3][b], 8 bits each, 255 = none (a lane that is no body: none)
+   *   hull_range[b]  {hull_start[b], hull_start[b + 1]}; a lane that is no body: the empty range at hull_start[nb]
+   *   chunk_row[k]   scan unit k: {body | cm_pack[body] << 8, v0, v1, hull_start[body]}; a lane that is no unit: all 0
+   *   chunk_box[k]   {chunk_c[0..2][k], 0, chunk_h[0..2][k], 0} */
+  __attribute__((aligned(16))) int chunk_row[TREX_TL][4];   /* (16 bytes: a row is one 4-word load) */
+  float chunk_box[TREX_TL][8];
+  int anc[TREX_MAXD][TREX_TL];        /* anc[d-1][b] = ancestor of body b at depth d (b itself at its own depth), -1 beyond
+                                         (not read by the step kernel: it gave its place near the front to the packed words) */
 };
+#define TREX_NO_DEPTH 255
 
 /* Per-env state in HBM. One row per env, padded so that a 32-lane team reads whole 128-B segments:
  *   base  [N][16]  pos(3) quat xyzw(4) v(3) w(3) | [13] contact count of the last substep (bits 0..7) + motors-on flag

@@ -201,6 +201,26 @@ void fill_device_model(const trex::HostModel &h, TrexDeviceModel &d) {
     }
     d.desc_mask[l] = m;
   }
+  // the step kernel's packed words (device_model.h), derived from the tables above: what the kernel used to form per lane
+  for (int l = 0; l < TREX_TL; l++) {
+    const bool body = l < h.nb;
+    const int parent = body ? d.parent[l] : 0, depth = body ? d.depth[l] : -1;
+    d.tree_pack[l] = (unsigned)(parent < 0 ? 0 : parent) | (unsigned)(depth < 0 ? TREX_NO_DEPTH : depth) << 8;
+    unsigned ch4 = 0u;
+    for (int k = 0; k < TREX_MAXCH; k++) {
+      const int c = body ? d.child[k][l] : -1;
+      ch4 |= (unsigned)(c < 0 ? 255 : c) << (8 * k);
+    }
+    d.child_pack[l] = ch4;
+    d.hull_range[l][0] = d.hull_start[body ? l : h.nb]; d.hull_range[l][1] = d.hull_start[body ? l + 1 : h.nb];
+    const bool unit = l < d.nchunk;
+    const int cb = d.chunk_body[l];
+    d.chunk_row[l][0] = unit ? (cb | (d.cm_pack[cb] << 8)) : 0;
+    d.chunk_row[l][1] = unit ? d.chunk_v0[l] : 0; d.chunk_row[l][2] = unit ? d.chunk_v1[l] : 0;
+    d.chunk_row[l][3] = unit ? d.hull_start[cb] : 0;
+    for (int c = 0; c < 3; c++) { d.chunk_box[l][c] = d.chunk_c[c][l]; d.chunk_box[l][4 + c] = d.chunk_h[c][l]; }
+    d.chunk_box[l][3] = d.chunk_box[l][7] = 0.f;
+  }
 }
 
 void tf12(const Tf &t, float out[12]) {

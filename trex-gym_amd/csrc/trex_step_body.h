@@ -347,6 +347,18 @@ static_assert(sizeof(CgLds) <= sizeof(WaveLds::u), "contact-generation scratch f
 
 constexpr int ACT_GAINS = TREX_ACT_GAINS, ACT_ROWS = TREX_ACT_ROWS, SENS_ROWS = TREX_SENS_ROWS;   // their rows: step_launch.h
 
+// The model as the step body reads it: through a pointer in the GLOBAL address space (global_load: counted on vmcnt alone), and its
+// packed rows (device_model.h) as 2 and 4 words per load.
+#ifndef TREX_GLOBAL   // (ablation: make variant XFLAGS=-DTREX_GLOBAL= gives the flat loads back)
+#define TREX_GLOBAL __attribute__((address_space(1)))
+#endif
+typedef const TREX_GLOBAL TrexDeviceModel *GlobalModel;
+typedef int gm_int2 __attribute__((ext_vector_type(2)));
+typedef int gm_int4 __attribute__((ext_vector_type(4)));
+typedef float gm_float4 __attribute__((ext_vector_type(4)));
+static_assert(offsetof(TrexDeviceModel, hull_range) % 8 == 0 && offsetof(TrexDeviceModel, chunk_row) % 16 == 0 &&
+              offsetof(TrexDeviceModel, chunk_box) % 16 == 0, "the packed rows are fetched as aligned 8- and 16-byte words");
+
 }  // namespace
 
 // DEBUG instantiations carry the diagnostics dump (scripts/gpu_debug.py, phase stamps); the product launches
@@ -452,6 +464,24 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
   // (workgroups j, 1024 + j, ...) gets the j-th heaviest env together with the j-th lightest of each later block -
   // the sums of work per SIMD are level. Device-side state only (phase, counts, lists): nothing to launch before
   // the step, and a captured graph replays correctly.
+  // EARLY (the pair form): the model's launch-wide scalars, fetched HERE in one batch of loads, in front of the rank look-up (three dependent loads
+  // that cannot be shortened: phase -> counts -> list entry). Read where they are first used - after the look-up, one statement and
+  // one wait each - they were more dependent L2 round trips before the first substep of every wave (waits on all loads in the
+  // prologue: 20 -> 15). The single-env forms read them with scalar loads where they always did: fetched early they lived in scalar
+  // registers across the look-up and cost two spills more (58 against 56, 90 against 88).
+  // (PAIR: scalars - as values the compiler loads with vector loads, dt and the products it hoists out of the substep loop,
+  // 0.5 dt and 0.25 dt^2, sat in vector registers for the whole kernel and were spilled to SCRATCH: 12 MB of traffic per launch)
+  // (Not the pair form with the wrench or the actuator model and without the sensor: those instantiations spilled one scalar
+  // register more with it; they read the scalars where they always did.)
+  constexpr bool EARLY = PAIR && (SENS || !(EXT || ACT));
+  int nb_e = 0, maxdepth_e = 0, n_sub_e = 0, iters_e = 0, maxc_e = 0;
+  float dt_e = 0.f, inv_dt_e = 0.f, mu_e = 0.f, floor_e = 0.f, margin_e = 0.f;
+  if constexpr (EARLY) {
+    nb_e = M->nb; maxdepth_e = M->maxdepth; n_sub_e = M->n_substeps; iters_e = M->n_iterations; maxc_e = M->max_contacts;
+    const float dt_l = M->prm[TP_DT], inv_dt_l = M->inv_dt, mu_l = M->prm[TP_FRICTION];
+    const float floor_l = M->prm[TP_FLOOR_Z], margin_l = M->prm[TP_CONTACT_MARGIN];
+    dt_e = uni_sgpr(dt_l); inv_dt_e = uni_sgpr(inv_dt_l); mu_e = uni_sgpr(mu_l); floor_e = uni_sgpr(floor_l); margin_e = uni_sgpr(margin_l);
+  }
   int env = wg;
   int bal_phase = 0;
   if (args.bal) {
@@ -494,17 +524,17 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
   }
   env = uni(env);
 
-  const int nb = M->nb, maxdepth = M->maxdepth;
-  // (PAIR: scalars - as values the compiler loads with vector loads, dt and the products it hoists out of the substep loop,
-  // 0.5 dt and 0.25 dt^2, sat in vector registers for the whole kernel and were spilled to SCRATCH: 12 MB of traffic per launch)
-  const float dt = PAIR ? uni_sgpr(M->prm[TP_DT]) : M->prm[TP_DT];
-  const float inv_dt = PAIR ? uni_sgpr(M->inv_dt) : M->inv_dt;
+  const int nb = EARLY ? nb_e : M->nb, maxdepth = EARLY ? maxdepth_e : M->maxdepth;
+  const float dt = EARLY ? dt_e : (PAIR ? uni_sgpr(M->prm[TP_DT]) : M->prm[TP_DT]);
+  const float inv_dt = EARLY ? inv_dt_e : (PAIR ? uni_sgpr(M->inv_dt) : M->inv_dt);
   const float dt_half = PAIR ? uni_sgpr(0.5f * dt) : 0.5f * dt, dt2_quarter = PAIR ? uni_sgpr(0.25f * dt * dt) : 0.25f * dt * dt;
   const int nj = nb - 1;
   // Everything about the model is (re)read from the L2-resident struct in the phase that uses it, through an
   // opaque pointer, and every lane-derived mask / index is re-derived from an opaque copy of the lane id, so
   // that nothing loop-invariant is hoisted out of the substep loop and then spilled across the solver.
-  auto Mo = [&]() { const TrexDeviceModel *Mi = M; asm volatile("" : "+s"(Mi)); return Mi; };
+  // (the opaque copy comes back as a GLOBAL pointer: as a generic one its loads were flat loads, which count on lgkmcnt too -
+  // every LDS read behind them waited for an L2 round trip it has nothing to do with)
+  auto Mo = [&]() { const TrexDeviceModel *Mi = M; asm volatile("" : "+s"(Mi)); return (GlobalModel)Mi; };
   auto lane_id = [&]() {   // (volatile: recomputed at every use site, never kept live or spilled)
     int l;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
@@ -514,7 +544,7 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
   // ---- per-env state: the base pose and twist are wave-uniform (SGPRs); q / qd / motor torque / target of
   // body lane b are parked in LDS (W.st) and read where a phase needs them
   float pos[3], quat[4], bv[3], bw[3];
-  const float mu = args.arr.domain ? uni(args.arr.friction[env]) : (PAIR ? uni_sgpr(M->prm[TP_FRICTION]) : M->prm[TP_FRICTION]);
+  const float mu = args.arr.domain ? uni(args.arr.friction[env]) : (EARLY ? mu_e : (PAIR ? uni_sgpr(M->prm[TP_FRICTION]) : M->prm[TP_FRICTION]));
   bool motors_on;
   int flags_in = 0, steps_in = 0;      // base row words 13 and 15 (device_model.h)
   bool do_reset = false;
@@ -579,7 +609,7 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
     }
   }
   WSYNC();
-  const int n_sub = RESET ? (do_reset ? 1 : 0) : M->n_substeps;
+  const int n_sub = RESET ? (do_reset ? 1 : 0) : (EARLY ? n_sub_e : M->n_substeps);
   // Wave priority: the launch lasts as long as its slowest wave, and with one env per wave that is an env with
   // many contact rows. During its sweeps such a wave wins the issue arbitration against the lighter waves of
   // its SIMD, which fill the slots its dependency chain leaves empty. (Mode 2, priority for the whole substep,
@@ -626,9 +656,10 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
   if (!RESET) { prio_nc = flags_in & 255; set_tree_priority(0); }
 #endif
 
-  const float floor_z = PAIR ? uni_sgpr(M->prm[TP_FLOOR_Z]) : M->prm[TP_FLOOR_Z], margin = PAIR ? uni_sgpr(M->prm[TP_CONTACT_MARGIN]) : M->prm[TP_CONTACT_MARGIN];
-  const int iters = M->n_iterations;
-  int maxc = M->max_contacts;
+  const float floor_z = EARLY ? floor_e : (PAIR ? uni_sgpr(M->prm[TP_FLOOR_Z]) : M->prm[TP_FLOOR_Z]);
+  const float margin = EARLY ? margin_e : (PAIR ? uni_sgpr(M->prm[TP_CONTACT_MARGIN]) : M->prm[TP_CONTACT_MARGIN]);
+  const int iters = EARLY ? iters_e : M->n_iterations;
+  int maxc = EARLY ? maxc_e : M->max_contacts;
   if (maxc > MAXC) maxc = MAXC;
 
   int stat_nc = 0;
@@ -637,8 +668,8 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
   // FK: world rotation R and origin r (relative to the base origin) of every body, the offset dpar from the
   // parent's origin and the joint axis Sa in world axes (motion subspace about the body's own origin
   // S = [Sa; 0]).  Base-to-tip, parent data via shuffles.
-  auto forward_kinematics = [&](int lt, int psrc, int depth, float *R, float *r, float *dpar, float *Sa) {
-    const TrexDeviceModel *Mi = Mo();
+  // Mi: the caller's opaque model pointer - its tree words and the 15 words here go out as ONE batch of loads, one wait.
+  auto forward_kinematics = [&](GlobalModel Mi, int lt, int psrc, int depth, float *R, float *r, float *dpar, float *Sa) {
     const int bl = lt & (TL - 1);
     float axis[3], jpos[3], jrot[9];
 #pragma unroll
@@ -700,8 +731,11 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
       const int parent = is_body ? M->parent[bl] : 0;
       const int psrc = parent < 0 ? 0 : parent;
       const int depth = is_body ? M->depth[bl] : -1;
+      // (once per env-step: left on the unpacked tables - with the packed word here trex_step_many_kernel spilled one scalar
+      // register more, 89 against 88)
+      GlobalModel Mi = Mo();
       float R[9], r[3], dpar[3], Sa[3];
-      forward_kinematics(lt, psrc, depth, R, r, dpar, Sa);
+      forward_kinematics(Mi, lt, psrc, depth, R, r, dpar, Sa);
       const float hp[3] = {M->head_point[0], M->head_point[1], M->head_point[2]};
       float o[3];
       matvec3(R, hp, o);
@@ -761,7 +795,7 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
     if (l < TL) {
       float target = 0.f;
       if (l >= 1 && l < nb) {
-        const TrexDeviceModel *Mi = Mo();
+        GlobalModel Mi = Mo();
         if constexpr (ACT) {   // the command of this joint by its mode: angle, velocity or torque, each clipped to its own range
           const float a = args.actions[((size_t)(MULTI ? ls : 0) * args.n_envs + env) * args.act_cols + Mi->obs_slot[l]];
           const unsigned bit = 1u << l;
@@ -825,28 +859,21 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
     }
     RELANE();
     {
-      const TrexDeviceModel *Mi = Mo();
-      const int parent = is_body ? Mi->parent[bl] : 0;
-      psrc = parent < 0 ? 0 : parent;
-      depth = is_body ? Mi->depth[bl] : -1;
-    }
-    {
+      // the tree words of this lane's body, packed by the host (device_model.h), and FK's 15 words: every lane reads at bl,
+      // unconditionally, in one batch - one L2 round trip where the selects in front of the loads made seven dependent ones
+      GlobalModel Mi = Mo();
+      // (selected after the load: a lane >= TL aliases a body's word. No depth = TREX_NO_DEPTH, beyond any level: the record's word)
+      const unsigned tw0 = Mi->tree_pack[bl], ch4 = Mi->child_pack[bl], tw = is_body ? tw0 : (unsigned)TREX_NO_DEPTH << 8;
+      psrc = (int)(tw & 255u); depth = (int)(tw >> 8);
       float dpar0[3], Sa0[3];
-      forward_kinematics(lt, psrc, depth, R, r, dpar0, Sa0);
+      forward_kinematics(Mi, lt, psrc, depth, R, r, dpar0, Sa0);
       if (lt < TL) {   // what later phases need of this body's pose and place in the tree goes to its record now
         float4 *rec = &W.body[BREC * lt];
         rec[0] = make_float4(Sa0[0], Sa0[1], Sa0[2], 0.f);
         rec[1] = make_float4(r[0], r[1], r[2], 0.f);
-        rec[3] = make_float4(0.f, 0.f, __int_as_float(psrc + 256 * (depth < 0 ? 255 : depth)), 0.f);
-        // children, 8 bits each (255 = none): the tip-to-base pass reads them here, not from the model (4 dependent
-        // L2 round trips per level)
-        const TrexDeviceModel *Mi = Mo();
-        unsigned ch4 = 0u;
-#pragma unroll
-        for (int k = 0; k < MAXCH; k++) {
-          const int c = is_body ? Mi->child[k][bl] : -1;
-          ch4 |= (unsigned)(c < 0 ? 255 : c) << (8 * k);
-        }
+        rec[3] = make_float4(0.f, 0.f, __uint_as_float(tw), 0.f);   // parent + 256 * depth (255 = none)
+        // children, 8 bits each (255 = none; a lane < TL that is no body holds none): the tip-to-base pass reads them here, not
+        // from the model (4 dependent L2 round trips per level)
         rec[4] = make_float4(dpar0[0], dpar0[1], dpar0[2], __uint_as_float(ch4));
       }
     }
@@ -906,13 +933,19 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
     // The points go to LDS (W.cpt) in contact order; only their number nc stays in a register.
     nc = 0;
     {
-      const TrexDeviceModel *Mi = Mo();
-      const int hull_v0 = Mi->hull_start[is_body ? lt : nb], hull_v1 = Mi->hull_start[is_body ? lt + 1 : nb];
+      // the broad phase's constants in one batch of loads, every lane at bl (packed rows of device_model.h): the body's hull
+      // range, the scan unit's row - which carries its body's mask word and first vertex, so that the near-hull table below waits
+      // for no load of its own - and its box
+      GlobalModel Mi = Mo();
+      const gm_int2 hr = *(const TREX_GLOBAL gm_int2 *)&Mi->hull_range[bl][0];
+      const gm_int4 cr = *(const TREX_GLOBAL gm_int4 *)&Mi->chunk_row[bl][0];
+      const gm_float4 cbc = *(const TREX_GLOBAL gm_float4 *)&Mi->chunk_box[bl][0], cbh = *(const TREX_GLOBAL gm_float4 *)&Mi->chunk_box[bl][4];
+      const int nchunk = Mi->nchunk;
+      const int hull_v0 = hr.x, hull_v1 = hr.y;     // (read through a body lane only: wshfl(.., b) below)
       CgLds &G = PAIR ? *reinterpret_cast<CgLds *>(Gpair) : *reinterpret_cast<CgLds *>(&W.u);
       // ---- broad phase, one hull per lane
-      const int nchunk = Mi->nchunk;
       const bool is_chunk = lt < nchunk;
-      const int cbody = Mi->chunk_body[bl], cv0 = Mi->chunk_v0[bl], cv1 = is_chunk ? Mi->chunk_v1[bl] : 0;
+      const int cbody = cr.x & 255, cv0 = cr.y, cv1 = is_chunk ? cr.z : 0;
       float Rz[3], zbc;
       {
         const float zb = posz + r[2] - floor_z;    // body origin above the floor (body lanes)
@@ -922,8 +955,8 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
       }
       bool near = false;
       if (is_chunk) {
-        const float cz = Rz[0] * Mi->chunk_c[0][bl] + Rz[1] * Mi->chunk_c[1][bl] + Rz[2] * Mi->chunk_c[2][bl];
-        const float reach = fabsf(Rz[0]) * Mi->chunk_h[0][bl] + fabsf(Rz[1]) * Mi->chunk_h[1][bl] + fabsf(Rz[2]) * Mi->chunk_h[2][bl];
+        const float cz = Rz[0] * cbc.x + Rz[1] * cbc.y + Rz[2] * cbc.z;
+        const float reach = fabsf(Rz[0]) * cbh.x + fabsf(Rz[1]) * cbh.y + fabsf(Rz[2]) * cbh.z;
         near = cv1 > cv0 && (zbc + cz - reach < margin);
       }
       const unsigned near_mask = (unsigned)__ballot(near);
@@ -952,7 +985,7 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
         if (near) {
           const int e = __popc(near_mask & ((1u << bl) - 1u));
           G.ent[e][0] = make_float4(__int_as_float(my_off + (cv1 - cv0)), __int_as_float(cv0 - my_off),
-                                    __int_as_float(cbody | (Mi->cm_pack[cbody] << 8)), __int_as_float(Mi->hull_start[cbody]));
+                                    __int_as_float(cr.x), __int_as_float(cr.w));
           // (.z: body in bits 0..7, its mask's log2 period in 8..15, its first mask word from bit 16)
           G.ent[e][1] = make_float4(Rz[0], Rz[1], Rz[2], zbc);
         }
@@ -1280,7 +1313,7 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
       float Rh[9];   // the body's rotation (pair: from the table in LDS)
 #pragma unroll
       for (int c = 0; c < 9; c++) Rh[c] = PAIR ? H->u.t.rtab[bl][c] : R[c];
-      const TrexDeviceModel *Mi = Mo();
+      GlobalModel Mi = Mo();
       float comb[3], inb[6];
       const float mscale = args.arr.domain ? args.arr.mass_scale[(size_t)(PAIR ? __float_as_int(H->xch[6]) : env) * TL + bl] : 1.0f;
       const float mass = Mi->mass[bl] * mscale;
@@ -1392,7 +1425,7 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
     // shift to the parent's origin and put the result back for the parent. One LDS round trip and one barrier
     // per level; nothing of this is carried in registers between levels. Level 0 is the base: it only sums.
     {
-      const TrexDeviceModel *Mi = Mo();
+      GlobalModel Mi = Mo();
       float tau_j = -Mi->damp[bl] * H->st[ST_QD][bl];  // explicit joint damping torque
       if constexpr (ACT) {   // ... and the commanded torque of a TORQUE joint (not on the settle substep of a reset)
         if (sub < n_sub && ((args.act_tor >> bl) & 1u)) tau_j += H->st[ST_TARGET][bl];
@@ -1711,9 +1744,12 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
       chol6_solve(I0c, r00, z00);
       diag += dot6(r00, z00);
       inv0 = live ? 1.0f / diag : 0.f;
-      const TrexDeviceModel *Mi = Mo();
+      // the set-up's constants in one batch of loads, every lane, in front of the row kinds' branches (one L2 round trip, not one per
+      // branch: they were three dependent ones)
+      GlobalModel Mi = Mo();
+      const float cerp = Mi->prm[TP_CONTACT_ERP], erp = Mi->prm[TP_ERP], kp_m = Mi->prm[TP_MOTOR_KP], kd_m = Mi->prm[TP_MOTOR_KD];
+      const float max_imp_m = Mi->motor_max_impulse, q_lo = Mi->lower[bl], q_hi = Mi->upper[bl];
       if (crow) {
-        const float cerp = Mi->prm[TP_CONTACT_ERP];
         float tv = 0.f;
         if (cdir == 0) tv = (cdist > 0.f) ? -cdist * inv_dt : -cdist * cerp * inv_dt;
         float wxx[3];
@@ -1722,9 +1758,7 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
         y = (tv - (jv + dot3(dir, pv))) * inv0;
       }
       if (mrow) {
-        const float erp = Mi->prm[TP_ERP];
-        float kp = Mi->prm[TP_MOTOR_KP], kd = Mi->prm[TP_MOTOR_KD];
-        float max_imp = Mi->motor_max_impulse;
+        float kp = kp_m, kd = kd_m, max_imp = max_imp_m;
         const float q = W.st[ST_Q][bl], nqd = W.st[ST_NQD][bl];
         float target = W.st[ST_TARGET][bl], vt = 0.f;
         if constexpr (ACT) {   // this env's gains of the joint; by mode: which of them the row uses, and what its command is
@@ -1744,7 +1778,6 @@ __device__ __forceinline__ void trex_step_body(const TrexStepArgs &args, const i
         } else
         y = (kp * (target - q) * inv_dt + kd * (0.f - nqd)) * inv0;
         mhi = motors_on ? max_imp : 0.f;
-        const float q_lo = Mi->lower[bl], q_hi = Mi->upper[bl];
         float pen = 0.f;
         if (q - q_lo <= 0.f) { pen = q - q_lo; ldir = 1.f; }
         else if (q_hi - q <= 0.f) { pen = q_hi - q; ldir = -1.f; }
